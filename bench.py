@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the MI355X bundle-adjustment engine (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W [--workload venice1778_heavy]
+  python bench.py --gpus N --steps K --warmup W [--workload venice1778_heavy] [--dump-outputs DIR] [--full]
 
 A "step" is one Levenberg-Marquardt iteration (linearize, eliminate tracks,
 build + solve the reduced camera system, back-substitute, trial cost) of the
@@ -16,10 +16,24 @@ ceil(K / 10) solves of <= 10 iterations from the same perturbed start
 solve would coast at the fixed point) with a device-side parameter reset in
 between; W warm-up iterations run first.  value = N_obs * K / wall time =
 observations/s over all ranks (strong scaling: the problem is fixed, tracks
-are sharded over ranks).  Beside the headline (1 GPU): the reference's default
-operating point (inner iterations on), the CPU port on all cores and on one
-core, the end-to-end wall clock of the C++ entry point, the side kernels and
-the plain venice1778 variant.
+are sharded over ranks).
+
+A plain run does only what the headline needs: set up, warm up, time the K
+iterations (no HIP events in the timed region), write the outputs if asked,
+print the line.  --full adds everything else, as before: an untimed pass of
+the same K iterations with every kernel class timed (the per-class table and
+the roofline; the timed region then carries events for the dominant class),
+and beside the headline (1 GPU) the reference's default operating point (inner
+iterations on), the CPU port on all cores and on one core, the end-to-end wall
+clock of the C++ entry point, the side kernels and the other variants;
+--no-extras / --no-cpu-baseline leave parts of that out.
+
+--dump-outputs DIR writes what the timed path computed in its last solve, the
+arrays a caller of tmi_ba_solver_solve + download receives, as float64 .npy:
+extrinsics [Nc, 6], intrinsics, points [Np, 4] (a fixed, seeded sample of the
+rows if the whole would pass 64 MB) and costs = [initial cost, final cost,
+initial RMSE, final RMSE].  The inputs are seeded: the same arguments give the
+same inputs in every run.
 
 For N > 1 launch with
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
@@ -200,6 +214,24 @@ def write_problem_file(prob, path):
         prob.obs_xy.astype(np.float64).tofile(f)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, prob, s):
+    """--dump-outputs: the parameters `prob` holds after download and the costs of summary `s`, float64 .npy files"""
+    import numpy as np
+    arrays = dict(extrinsics=prob.extrinsics, intrinsics=prob.intrinsics, points=prob.points,
+                  costs=np.array([s.initial_cost, s.final_cost, s.initial_rmse, s.final_rmse]))
+    rest = sum(a.nbytes for k, a in arrays.items() if k != "points")
+    rows = max(0, (DUMP_LIMIT_BYTES - rest) // (prob.points.shape[1] * 8))
+    if prob.num_points > rows:
+        keep = np.sort(np.random.default_rng(0).choice(prob.num_points, rows, replace=False))
+        arrays["points"] = prob.points[keep]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -211,10 +243,16 @@ def main():
                     help="LM iterations per solve: the K timed iterations are ceil(K / this) solves from the "
                          "same perturbed start (the problem converges in ~12 iterations; a single K-iteration "
                          "solve would coast at the fixed point)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the per-class kernel table and roofline (an untimed pass of their "
+                         "own), the CPU baselines, the other operating points, sizes and configurations, the "
+                         "end-to-end C++ entry point and the side kernels")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the parameters and costs of the last timed solve to DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baselines, no side kernels")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the lines beside the headline: plain venice1778, inner iterations, end-to-end "
-                         "C++ entry point, side kernels")
+                    help="with --full: skip the lines beside the headline: plain venice1778, inner iterations, "
+                         "end-to-end C++ entry point, side kernels")
     ap.add_argument("--cpu-iters", type=int, default=2)
     ap.add_argument("--transport", default="rccl", choices=["rccl", "torch", "staged", "torch_staged"],
                     help="rccl: ncclAllReduce issued by the engine; torch: torch.distributed (nccl) hook; staged: "
@@ -308,13 +346,15 @@ def main():
                 solver.reset()
         return done, secs, launches, s, pcg, acc, mf
 
-    def measure(workload, steps, warmup, with_transport, overrides=None):
-        """creates the resident solver, warms up, profiles, times; returns a dict of raw results"""
+    def measure(workload, steps, warmup, with_transport, overrides=None, profiled=True):
+        """creates the resident solver, warms up, profiles (profiled = True), times; returns a dict of raw results"""
         t0 = time.perf_counter()
         prob = synth.config(workload)
         t_gen = time.perf_counter() - t0
         base = {**base_options(prob.num_cameras), **(overrides or {})}
-        prob0 = prob.copy() if rank == 0 else None  # Solver.download() writes into `prob`
+        # Solver.download() writes into `prob`: the start for the legs of --full, and on every rank for merging the
+        # dumped outputs over ranks
+        prob0 = prob.copy() if (rank == 0 and args.full) or (world > 1 and args.dump_outputs) else None
         t0 = time.perf_counter()
         solver = lib.Solver(prob, abi.default_options(max_num_iterations=1, **base), rank, world)
         transport = "none"
@@ -340,17 +380,21 @@ def main():
             if st != 0:
                 raise RuntimeError(f"warm-up solve failed: {st} {s.message!r}")
             solver.reset()
-        # untimed pass of the same iterations with every kernel class timed (HIP events on the engine's
-        # stream): the per-class table, and which class dominates.  The timed region carries events for
-        # THAT class only (two event records per launch of every class cost a few % of an iteration).
-        _, secs_p, launches_p, _, _, _, _ = run_chunks(solver, base, steps, 1)
-        secs_nc = list(secs_p)
-        secs_nc[abi.KERNEL_CLASS_NAMES.index("allreduce")] = 0.0
-        dom_idx = max(range(len(secs_nc)), key=lambda i: secs_nc[i])
-        solver.reset()
+        secs_p = launches_p = dom_idx = None
+        timed_profile = 0
+        if profiled:
+            # untimed pass of the same iterations with every kernel class timed (HIP events on the engine's
+            # stream): the per-class table, and which class dominates.  The timed region carries events for
+            # THAT class only (two event records per launch of every class cost a few % of an iteration).
+            _, secs_p, launches_p, _, _, _, _ = run_chunks(solver, base, steps, 1)
+            secs_nc = list(secs_p)
+            secs_nc[abi.KERNEL_CLASS_NAMES.index("allreduce")] = 0.0
+            dom_idx = max(range(len(secs_nc)), key=lambda i: secs_nc[i])
+            timed_profile = (1 << dom_idx) if dom_idx > 0 else 1
+            solver.reset()
         sync_all()
         t0 = time.perf_counter()
-        done, secs_t, launches_t, s, pcg, acc, mf = run_chunks(solver, base, steps, (1 << dom_idx) if dom_idx > 0 else 1)
+        done, secs_t, launches_t, s, pcg, acc, mf = run_chunks(solver, base, steps, timed_profile)
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
         if world > 1:
@@ -373,17 +417,30 @@ def main():
     # repeated with the stored camera block and the line says so -- a failed solve is never reported as a number.
     compact_retry = None
     try:
-        m = measure(args.workload, args.steps, args.warmup, True)
+        m = measure(args.workload, args.steps, args.warmup, True, profiled=args.full)
     except RuntimeError as ex:
         if world != 1 or os.environ.get("TMI_BA_COMPACT_PLANES") == "0" or "solve failed" not in str(ex):
             raise
         compact_retry = str(ex)[:300]
         os.environ["TMI_BA_COMPACT_PLANES"] = "0"
-        m = measure(args.workload, args.steps, args.warmup, True)
+        m = measure(args.workload, args.steps, args.warmup, True, profiled=args.full)
     solver, s, prob, prob0, base = m["solver"], m["summary"], m["prob"], m["prob0"], m["base"]
     steps_run, elapsed = m["steps_run"], m["elapsed"]
     n_obs, n_cam, n_pts = prob.num_observations, prob.num_cameras, prob.num_points
     solver_type, solver_name = solver_policy(n_cam)
+    if args.dump_outputs:
+        solver.download()  # into `prob`
+        if world > 1:
+            # a rank downloads the points of its own tracks only: every point comes from the one rank that moved it
+            dev = "cpu" if one_gpu else "cuda"
+            moved = (prob.points != prob0.points).any(axis=1)
+            owners = torch.from_numpy(moved.astype(np.float64)).to(dev)
+            pts = torch.from_numpy(np.where(moved[:, None], prob.points, 0.0)).to(dev)
+            torch.distributed.all_reduce(owners)
+            torch.distributed.all_reduce(pts)
+            prob.points[:] = np.where(owners.cpu().numpy()[:, None] > 0, pts.cpu().numpy(), prob0.points)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, prob, s)
     if rank != 0:
         solver.close()
         return
@@ -406,53 +463,55 @@ def main():
                              achieved_GBs=round(ab / avg / 1e9, 2) if avg > 0 else None))
         return rows
 
-    kernels = table(m["launches_p"], m["secs_p"])
-    dom_name = abi.KERNEL_CLASS_NAMES[m["dom_idx"]]
-    timed_rows = [k for k in table(m["launches_t"], m["secs_t"]) if k["kernel"] == dom_name]
-    dom = timed_rows[0] if timed_rows else max((k for k in kernels if k["kernel"] != "allreduce"),
-                                               key=lambda k: k["total_ms"])
-    roofline = dict(bound="hbm", kernel=dom["kernel"], achieved=dom["achieved_GBs"], peak=HBM_PEAK_GBS,
-                    unit="GB/s", frac=round(dom["achieved_GBs"] / HBM_PEAK_GBS, 5),
-                    traffic=pmc_traffic(dom["kernel"], args.workload, world, mf_frac),
-                    traffic_source="profiles/pmc_latest.json: rocprofv3 --pmc passes of this command, committed "
-                                   "(counters cannot be read from inside the process); null when that pass was "
-                                   "taken with other kernel sources (traffic_build.stale)",
-                    traffic_build=pmc_build(),
-                    launches=dom["launches"], avg_us=dom["avg_us"],
-                    algorithmic_bytes_per_launch=dom["algorithmic_bytes_per_launch"],
-                    algorithmic_bytes_definition="SURVEY 8(d): per product nnzb * 8 d_c^2 + 6 N_c 8 d_c (S blocks once, "
-                                                 "whichever operator applies S); per-observation classes 24 B/observation "
-                                                 "+ parameters + normal-equation blocks",
-                    measured="HIP events on the engine's stream inside the timed region")
-    if dom["kernel"] == "spmv" and mf_frac > 0.0:
-        # beside the contract's figure, under its own key: what a matrix-free product has to read in this layout
-        # which product / plane layout THIS handle runs is the engine's answer, not a copy of its rules
-        info = solver.operator_info()
-        one_sweep, drop_pos = info["one_sweep_product"], info["position_columns_formed"]
-        compact = info.get("compact_planes", False)
-        # (compact planes: the camera block is ONE 16-byte pair per observation -- the normalised image point)
-        lf = matrix_free_layout_floor(n_obs // world, n_cam, n_pts // world, dc, dp, 1 if compact else (dc - 3 if drop_pos else dc))
-        roofline["kernel"] = ("spmv (one product q = S p; matrix-free in %d of %d timed LM iterations: %s)"
-                              % (m["matrix_free"], steps_run,
-                                 "mfc::product_kernel + mfc::reduce_kernel, the one-sweep product of mf_chunks.h" if one_sweep
-                                 else "implicit_tracks_q + implicit_cameras_q, the two-pass product"))
-        roofline["layout_floor"] = dict(
-            bytes_per_launch=int(lf), achieved=round(lf / (dom["avg_us"] * 1e-6) / 1e9, 2),
-            frac=round(lf / (dom["avg_us"] * 1e-6) / 1e9 / HBM_PEAK_GBS, 5),
-            note="matrix-free product, every stored Jacobian block read once%s (NOT SURVEY 8(d)'s bytes; round 2 "
-                 "quoted this figure as roofline.frac)" % (" -- compact planes: the camera block is formed from the point "
-                                                           "block, the normalised image point (the one stored pair), the "
-                                                           "track and the view" if compact else
-                                                           " -- the position columns of the camera block are not "
-                                                           "stored" if drop_pos else ""))
-        roofline["compact_planes"] = bool(compact)
-    # the other large classes of the same timed region (schur_offdiag was the dominant one until the adaptive
-    # operator choice took it out of the short PCG solves): same definition, for comparison across rounds
-    roofline["other_classes"] = {
-        k["kernel"]: dict(achieved=k["achieved_GBs"], frac=round(k["achieved_GBs"] / HBM_PEAK_GBS, 5), launches=k["launches"],
-                          avg_us=k["avg_us"], traffic=pmc_traffic(k["kernel"], args.workload, world, mf_frac))
-        for k in kernels  # the separate pass with every class timed (kernels_note)
-        if k["kernel"] in ("schur_offdiag", "spmv", "point_eliminate", "linearize") and k["kernel"] != dom["kernel"]}
+    roofline = kernels = None
+    if args.full:
+        kernels = table(m["launches_p"], m["secs_p"])
+        dom_name = abi.KERNEL_CLASS_NAMES[m["dom_idx"]]
+        timed_rows = [k for k in table(m["launches_t"], m["secs_t"]) if k["kernel"] == dom_name]
+        dom = timed_rows[0] if timed_rows else max((k for k in kernels if k["kernel"] != "allreduce"),
+                                                   key=lambda k: k["total_ms"])
+        roofline = dict(bound="hbm", kernel=dom["kernel"], achieved=dom["achieved_GBs"], peak=HBM_PEAK_GBS,
+                        unit="GB/s", frac=round(dom["achieved_GBs"] / HBM_PEAK_GBS, 5),
+                        traffic=pmc_traffic(dom["kernel"], args.workload, world, mf_frac),
+                        traffic_source="profiles/pmc_latest.json: rocprofv3 --pmc passes of this command, committed "
+                                       "(counters cannot be read from inside the process); null when that pass was "
+                                       "taken with other kernel sources (traffic_build.stale)",
+                        traffic_build=pmc_build(),
+                        launches=dom["launches"], avg_us=dom["avg_us"],
+                        algorithmic_bytes_per_launch=dom["algorithmic_bytes_per_launch"],
+                        algorithmic_bytes_definition="SURVEY 8(d): per product nnzb * 8 d_c^2 + 6 N_c 8 d_c (S blocks once, "
+                                                     "whichever operator applies S); per-observation classes 24 B/observation "
+                                                     "+ parameters + normal-equation blocks",
+                        measured="HIP events on the engine's stream inside the timed region")
+        if dom["kernel"] == "spmv" and mf_frac > 0.0:
+            # beside the contract's figure, under its own key: what a matrix-free product has to read in this layout
+            # which product / plane layout THIS handle runs is the engine's answer, not a copy of its rules
+            info = solver.operator_info()
+            one_sweep, drop_pos = info["one_sweep_product"], info["position_columns_formed"]
+            compact = info.get("compact_planes", False)
+            # (compact planes: the camera block is ONE 16-byte pair per observation -- the normalised image point)
+            lf = matrix_free_layout_floor(n_obs // world, n_cam, n_pts // world, dc, dp, 1 if compact else (dc - 3 if drop_pos else dc))
+            roofline["kernel"] = ("spmv (one product q = S p; matrix-free in %d of %d timed LM iterations: %s)"
+                                  % (m["matrix_free"], steps_run,
+                                     "mfc::product_kernel + mfc::reduce_kernel, the one-sweep product of mf_chunks.h" if one_sweep
+                                     else "implicit_tracks_q + implicit_cameras_q, the two-pass product"))
+            roofline["layout_floor"] = dict(
+                bytes_per_launch=int(lf), achieved=round(lf / (dom["avg_us"] * 1e-6) / 1e9, 2),
+                frac=round(lf / (dom["avg_us"] * 1e-6) / 1e9 / HBM_PEAK_GBS, 5),
+                note="matrix-free product, every stored Jacobian block read once%s (NOT SURVEY 8(d)'s bytes; round 2 "
+                     "quoted this figure as roofline.frac)" % (" -- compact planes: the camera block is formed from the point "
+                                                               "block, the normalised image point (the one stored pair), the "
+                                                               "track and the view" if compact else
+                                                               " -- the position columns of the camera block are not "
+                                                               "stored" if drop_pos else ""))
+            roofline["compact_planes"] = bool(compact)
+        # the other large classes of the same timed region (schur_offdiag was the dominant one until the adaptive
+        # operator choice took it out of the short PCG solves): same definition, for comparison across rounds
+        roofline["other_classes"] = {
+            k["kernel"]: dict(achieved=k["achieved_GBs"], frac=round(k["achieved_GBs"] / HBM_PEAK_GBS, 5), launches=k["launches"],
+                              avg_us=k["avg_us"], traffic=pmc_traffic(k["kernel"], args.workload, world, mf_frac))
+            for k in kernels  # the separate pass with every class timed (kernels_note)
+            if k["kernel"] in ("schur_offdiag", "spmv", "point_eliminate", "linearize") and k["kernel"] != dom["kernel"]}
 
     explicit = not (int(s.num_schur_pairs) == 0 and solver_type == abi.ITERATIVE_SCHUR)
     n_r = n_cam * dc
@@ -499,20 +558,23 @@ def main():
         initial_cost=s.initial_cost, final_cost=s.final_cost, initial_rmse=s.initial_rmse,
         final_rmse=s.final_rmse, accepted_steps=int(m["accepted"]),
         schur_blocks_upper=nnzb, schur_pairs=int(s.num_schur_pairs),
-        setup_seconds=dict(generate=round(m["t_gen"], 3), create_upload=round(m["t_create"], 3)),
-        roofline=roofline, kernels=kernels,
-        kernels_note="per-class table: separate untimed pass of the same iterations with every class timed")
+        setup_seconds=dict(generate=round(m["t_gen"], 3), create_upload=round(m["t_create"], 3)))
+    if args.full:
+        out.update(roofline=roofline, kernels=kernels,
+                   kernels_note="per-class table: separate untimed pass of the same iterations with every class timed")
     if allreduce:
         # what the first real multi-GPU run needs to be read from ONE line: every rank's own time for the same K
         # iterations (the slowest is the headline), rank 0's time inside the all-reduce callback and its launches from
-        # the pass with every class timed, and -- with the torch.distributed hook -- the hook's own call / byte counts
+        # the pass with every class timed (--full), and -- with the torch.distributed hook -- the hook's own call / byte
+        # counts
         i_ar = abi.KERNEL_CLASS_NAMES.index("allreduce")
         allreduce["per_rank_ms_per_step"] = [round(1e3 * e / max(steps_run, 1), 4) for e in m["per_rank_elapsed"]]
-        allreduce["rank0_calls_per_lm_iteration_measured"] = round(m["launches_p"][i_ar] / max(steps_run, 1), 2)
-        allreduce["rank0_ms_per_step_in_callback"] = round(1e3 * m["secs_p"][i_ar] / max(steps_run, 1), 4)
+        if args.full:
+            allreduce["rank0_calls_per_lm_iteration_measured"] = round(m["launches_p"][i_ar] / max(steps_run, 1), 2)
+            allreduce["rank0_ms_per_step_in_callback"] = round(1e3 * m["secs_p"][i_ar] / max(steps_run, 1), 4)
         if hook_stats:
             allreduce["torch_hook"] = dict(calls=int(hook_stats.get("calls", 0)), bytes=int(hook_stats.get("bytes", 0)),
-                                           note="over warm-up, the profiled pass and the timed region")
+                                           note="over warm-up, the profiled pass (--full) and the timed region")
         out["allreduce"] = allreduce
     if steps_run != args.steps:
         out["note"] = f"solver stopped after {steps_run} of {args.steps} iterations: {s.message!r}"
@@ -540,7 +602,8 @@ def main():
              "bytes (profiles/) because Jacobian blocks and the per-observation Schur factors are stored and gathered "
              "rather than recomputed")
 
-    extras = world == 1 and not args.no_extras
+    extras = world == 1 and args.full and not args.no_extras
+    cpu_baseline = world == 1 and args.full and not args.no_cpu_baseline
     if extras:
         # ---- the reference's default operating point: inner iterations ON
         # (reconstruction_estimator_utils.cc:117, bundle_adjustment.h:112), same problem, same start
@@ -559,7 +622,7 @@ def main():
             note="one solve of the first iterations with use_inner_iterations = 1 (Ceres switches the sweeps off "
                  "once their relative gain drops below 1e-3)")
 
-    if world == 1 and not args.no_cpu_baseline:
+    if cpu_baseline:
         # CPU baseline: the in-repo oracle (Ceres-semantics restatement; the real
         # Theia + Ceres cannot be built offline) on the SAME problem and options
         # for a bounded number of LM iterations, all host cores via OpenMP.
@@ -652,7 +715,7 @@ def main():
         if solver is None:
             solver = lib.Solver(prob0.copy(), abi.default_options(max_num_iterations=1, **base), 0, 1)
 
-    if world == 1 and not args.no_cpu_baseline:
+    if cpu_baseline:
         from oracle import oracle
         # The steps either side of the BA on the same resident
         # problem, outside the timed region: kernel time from HIP events, the oracle beside it.

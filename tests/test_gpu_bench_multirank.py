@@ -13,6 +13,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -20,12 +21,14 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def run_bench(n, port, *extra, timeout=900):
+def run_bench(n, port, *extra, timeout=900, full=True):
+    """full: the headline with its per-class pass (roofline, kernels, the measured all-reduce calls), no other legs"""
     cmd = [sys.executable]
     if n > 1:
         cmd += ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
                 "--master-port", str(port)]
-    cmd += [os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--no-extras", "--no-cpu-baseline"] + list(extra)
+    cmd += [os.path.join(ROOT, "bench.py"), "--gpus", str(n)] + (["--full", "--no-extras", "--no-cpu-baseline"] if full else [])
+    cmd += list(extra)
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=timeout)
     assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-3000:])
@@ -79,6 +82,29 @@ def test_bench_two_ranks_torch_hook_with_a_gloo_collective():
     assert abs(max(ar["per_rank_ms_per_step"]) - two["ms_per_step"]) <= 1e-3 * two["ms_per_step"]
     assert ar["torch_hook"]["calls"] > 0 and ar["torch_hook"]["bytes"] > 0
     assert ar["rank0_calls_per_lm_iteration_measured"] >= 2
+
+
+def test_plain_run_times_the_steps_and_dumps_the_outputs_of_the_last_solve(tmp_path):
+    """bench.py without --full: the headline line alone, exactly --steps timed iterations; --dump-outputs writes the
+    parameters and costs of the last timed solve as float64 arrays, and two ranks (each downloads its own tracks) dump
+    what one rank does"""
+    args = ["--workload", "ladybug49", "--steps", "4", "--warmup", "1"]
+    one = run_bench(1, 0, *args, "--dump-outputs", str(tmp_path / "one"), full=False)
+    two = run_bench(2, 29625, "--transport", "staged", *args, "--dump-outputs", str(tmp_path / "two"), full=False)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in one, k
+    assert one["steps"] == 4 and one["warmup"] == 1 and one["value"] > 0 and one["ms_per_step"] > 0
+    assert "kernels" not in one and "roofline" not in one and "cpu_baseline" not in one and "variants" not in one
+    names = ("extrinsics", "intrinsics", "points", "costs")
+    d1 = {k: np.load(tmp_path / "one" / (k + ".npy")) for k in names}
+    d2 = {k: np.load(tmp_path / "two" / (k + ".npy")) for k in names}
+    assert all(a.dtype == np.float64 for a in list(d1.values()) + list(d2.values()))
+    assert d1["extrinsics"].shape == (one["config"]["cameras"], 6) and d1["points"].shape == (one["config"]["tracks"], 4)
+    assert d1["costs"][1] == one["final_cost"] and d1["costs"][3] == one["final_rmse"]
+    assert abs(d2["costs"][1] - d1["costs"][1]) <= 1e-9 * d1["costs"][1]
+    for k in ("extrinsics", "intrinsics", "points"):
+        assert d2[k].shape == d1[k].shape
+        assert np.abs(d2[k] - d1[k]).max() <= 1e-6 * max(1.0, np.abs(d1[k]).max()), k
 
 
 def test_native_rccl_refuses_two_ranks_on_one_device_cleanly():

@@ -1,5 +1,8 @@
 """CPU: on-disk interchange: cereal Reconstruction archive out and in
 again, BAL text out and in again."""
+import hashlib
+import json
+import lzma
 import os
 
 import numpy as np
@@ -7,19 +10,46 @@ import pytest
 
 from theiasfm_amd import abi, io, synth
 
-FOUNTAIN = "/root/reference/data/sfm/fountain11.bin"  # only in the development container
 HERE = os.path.dirname(os.path.abspath(__file__))
+GOLDEN = os.path.join(HERE, "golden")
+# the reference's data/sfm archives, kept under golden/ (see _archive)
+FOUNTAIN = "fountain11.bin"
+GT_FOUNTAIN = "gt_fountain11.bin"  # Camera v0 / CameraIntrinsicsPrior v0 archive
 
 
-GT_FOUNTAIN = "/root/reference/data/sfm/gt_fountain11.bin"  # Camera v0 / CameraIntrinsicsPrior v0 archive
+def _archive(tmp_path, name):
+    """The reference's archive `name` as a file under tmp_path.  gt_fountain11.bin is stored xz-compressed.
+    fountain11.bin is stored as its skeleton (golden/make_fountain11_skeleton.py): the archive with the doubles that
+    fountain11_flat.npz holds verbatim -- track points, image coordinates of the observations -- set to zero.  They are
+    filled back in here, and the size and SHA-256 of the reference's file prove that the result is that file."""
+    path = tmp_path / name
+    if name != FOUNTAIN:
+        path.write_bytes(lzma.decompress(open(os.path.join(GOLDEN, name + ".xz"), "rb").read()))
+        return str(path)
+    skeleton = tmp_path / "fountain11_skeleton.bin"
+    skeleton.write_bytes(lzma.decompress(open(os.path.join(GOLDEN, "fountain11_skeleton.bin.xz"), "rb").read()))
+    rec = io.read_theia_reconstruction(str(skeleton))
+    prob = io.flatten_reconstruction(rec)  # the same residual set, hence the same order, as the npz
+    gold = np.load(os.path.join(GOLDEN, "fountain11_flat.npz"))
+    vids, tids = prob.meta["view_ids"], prob.meta["track_ids"]
+    np.testing.assert_array_equal(prob.obs_camera, gold["obs_camera"])
+    np.testing.assert_array_equal(prob.obs_point, gold["obs_point"])
+    for t, point in zip(tids, gold["points"]):
+        rec.tracks[t].point = point.copy()
+    for c, p, (x, y) in zip(gold["obs_camera"], gold["obs_point"], gold["obs_xy"]):
+        rec.views[vids[c]].features[tids[p]] = (float(x), float(y))
+    io.write_theia_reconstruction(str(path), rec)
+    data, want = path.read_bytes(), json.load(open(os.path.join(GOLDEN, "fountain11_archive.json")))
+    assert len(data) == want["size"] and hashlib.sha256(data).hexdigest() == want["sha256"]
+    return str(path)
 
 
-@pytest.mark.skipif(not os.path.exists(FOUNTAIN), reason="reference fixture not on this machine")
-@pytest.mark.parametrize("path", [FOUNTAIN, GT_FOUNTAIN])
-def test_cereal_archive_regenerated_from_parsed_fields_is_byte_identical(tmp_path, path):
+@pytest.mark.parametrize("name", [FOUNTAIN, GT_FOUNTAIN])
+def test_cereal_archive_regenerated_from_parsed_fields_is_byte_identical(tmp_path, name):
     """The writer builds the archive from scratch (no bytes of the input are reused): what it emits
     for the parsed fields of the reference's own files must be those files, in both the current
     class versions (fountain11.bin) and the legacy ones (gt_fountain11.bin)."""
+    path = _archive(tmp_path, name)
     rec = io.read_theia_reconstruction(path)
     rec.raw = b""
     out = tmp_path / "same.bin"
@@ -125,9 +155,9 @@ def test_bundler_reader_follows_the_reference_importer(tmp_path):
 
 
 
-@pytest.mark.skipif(not os.path.exists(FOUNTAIN), reason="reference fixture not on this machine")
 def test_cereal_archive_carries_adjusted_values(tmp_path):
-    rec = io.read_theia_reconstruction(FOUNTAIN)
+    fountain = _archive(tmp_path, FOUNTAIN)
+    rec = io.read_theia_reconstruction(fountain)
     prob = io.flatten_reconstruction(rec)
     gold = np.load(os.path.join(HERE, "golden", "fountain11_flat.npz"))
     np.testing.assert_array_equal(prob.points, gold["points"])  # same flattening as the fixture
@@ -140,7 +170,7 @@ def test_cereal_archive_carries_adjusted_values(tmp_path):
     io.update_reconstruction(rec, prob, track_flags=flags)
     out = tmp_path / "adjusted.bin"
     io.write_theia_reconstruction(str(out), rec)
-    assert os.path.getsize(out) == os.path.getsize(FOUNTAIN)
+    assert os.path.getsize(out) == os.path.getsize(fountain)
     rec2 = io.read_theia_reconstruction(str(out))
     # the filtered tracks are gone from the flattened problem, everything else is what was written
     prob2 = io.flatten_reconstruction(rec2)

@@ -9,7 +9,7 @@ W=${1:-venice1778_heavy}
 for rep in 1 2 3; do
 for which in base new; do
 cp $L/ab_$which.so $L/libtheia_mi355_ba.so
-python bench.py --workload $W --steps 20 --no-cpu-baseline --no-extras 2>/dev/null | python -c "
+python bench.py --workload $W --steps 20 --full --no-cpu-baseline --no-extras 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline()); print('$which', round(d['ms_per_step'],3), d['pcg_iterations'], d['final_cost'], {k['kernel']:k['avg_us'] for k in d['kernels'] if k['kernel'] in ('spmv','back_substitute','point_eliminate','linearize','update_cost','camera_diag')})"
 done

@@ -30,7 +30,7 @@ tail -1 $O/${T}_refdef.log | cut -c1-300
 # the default bench line AFTER the PMC passes: pmc_latest.json now carries this build's stamp, so roofline.traffic is
 # filled (the committed r04 line was taken before the passes and said traffic: null / stale)
 SECONDS=0
-timeout 900 python bench.py > $O/${T}_bench.json 2> $O/${T}_bench.err
+timeout 900 python bench.py --full > $O/${T}_bench.json 2> $O/${T}_bench.err
 echo "default bench.py wall: $SECONDS s"
 head -c 300 $O/${T}_bench.json; echo
 # the exact-solver variant (config 3): kernel trace of the alamo-sized workload
