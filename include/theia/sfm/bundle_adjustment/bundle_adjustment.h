@@ -115,5 +115,14 @@ BundleAdjustmentSummary BundleAdjustTrack(const BundleAdjustmentOptions& options
 std::unordered_map<TrackId, BundleAdjustmentSummary> BundleAdjustTracks(
     const BundleAdjustmentOptions& options, const std::unordered_set<TrackId>& track_ids,
     Reconstruction* reconstruction);
+
+// Extension of the MI355X path: BundleAdjustView for many views in ONE device launch
+// (theiasfm_amd/host/view_ops.cc; tmi_ba_adjust_views).  The result equals calling BundleAdjustView once per view
+// in ascending ViewId order, each call starting from the parameters the previous ones left (views sharing
+// intrinsics with free entries run in sequence on the device).  Views that are not estimated are skipped
+// (absent from the result).
+std::unordered_map<ViewId, BundleAdjustmentSummary> BundleAdjustViews(const BundleAdjustmentOptions& options,
+                                                                      const std::unordered_set<ViewId>& view_ids,
+                                                                      Reconstruction* reconstruction);
 }  // namespace theia
 #endif

@@ -517,6 +517,56 @@ int32_t tmi_ba_adjust_tracks(tmi_ba_problem* problem, const tmi_ba_options* opti
                              double* track_initial_cost, double* track_final_cost,
                              tmi_ba_track_batch_summary* summary);
 
+/* Batched theia::BundleAdjustView (bundle_adjustment.cc:83-93; called once per newly localised view from
+ * localize_view_to_reconstruction.cc:248-252, for a whole list of views per round by
+ * incremental_reconstruction_estimator.cc:219-233).  The result equals calling the per-view path
+ * (tmi_ba_solve on the view's one-view problem, linear_solver_type DENSE_QR, no inner iterations) once for
+ * every selected view in ascending camera index order, each call starting from the parameters the previous
+ * calls left:
+ *   - view_mask[num_cameras] selects the views (NULL = all).  A selected view's free parameters are its
+ *     extrinsics minus the halves camera_flags fix, and the free entries (intrinsics_constant == 0) of its
+ *     intrinsics group; its residuals are its own observations under the options' loss.  Every point is
+ *     constant and never written; views that are not selected neither move nor contribute residuals, even
+ *     when they share the selected view's group (what BundleAdjuster::AddView alone builds,
+ *     bundle_adjuster.cc:102-135).
+ *   - Two selected views of a group with free entries run one after the other (a CHAIN): the later one starts
+ *     from the intrinsics the earlier one produced.  Views that share no free group are independent and run
+ *     concurrently, one 256-thread workgroup per chain, all chains in one launch, longest first.
+ *   - The trust-region loop is tmi_ba_solve's (Jacobi scaling, LM radius rules, function / gradient /
+ *     parameter tolerances, max_num_iterations, max_num_consecutive_invalid_steps); the linear step is the
+ *     exact solve of the view's damped D x D normal equations (D <= 16).  max_solver_time_in_seconds is not
+ *     enforced; evaluation is fp64 whatever residual_precision says; linear_solver_type, preconditioner_type,
+ *     use_inner_iterations and point_dof are irrelevant.
+ * view_termination[num_cameras]: 0 CONVERGENCE, 1 NO_CONVERGENCE, 2 FAILURE, 3 residual evaluation failed at
+ * the start point (reprojection_error.h:75-77; tmi_ba_solve's TMI_BA_ERR_EVALUATION_FAILED: both costs 0),
+ * -1 not adjusted (not selected, no observations, or nothing free).  Extrinsics and group intrinsics are
+ * written back exactly when the code is 0 or 1 (IsSolutionUsable).  All per-view outputs may be NULL. */
+typedef struct tmi_ba_view_batch_summary {
+  int64_t num_views;        /* views adjusted (termination >= 0) */
+  int64_t num_success;      /* termination 0 or 1 */
+  int64_t total_iterations; /* sum of LM iterations over the views */
+  int64_t num_chains;       /* workgroups of the launch (chains of views run in sequence) */
+  double seconds;           /* wall time of the call */
+  double kernel_seconds;    /* the device kernel alone (HIP events) */
+} tmi_ba_view_batch_summary;
+
+/* One-shot form: uploads the cameras, the groups, the points and the observations of the views to adjust (no Schur
+ * structure), adjusts, updates problem->extrinsics / intrinsics in place.  The device is options->device
+ * (-1 = current). */
+int32_t tmi_ba_adjust_views(tmi_ba_problem* problem, const tmi_ba_options* options, const uint8_t* view_mask,
+                            int8_t* view_termination, int32_t* view_iterations, double* view_initial_cost,
+                            double* view_final_cost, tmi_ba_view_batch_summary* summary);
+
+/* Resident form: on the parameters already in `solver` (e.g. right after tmi_ba_solver_solve or
+ * tmi_ba_solver_set_parameters); nothing is uploaded.  The first call builds a view-major index of the
+ * handle's observations on the device (radix sort of (view, slot) keys) and keeps it in the handle; it does
+ * not depend on the reduced-block layout, so views without a reduced block (constant views) can be selected.
+ * The camera-derived caches of the handle are invalidated, so a later tmi_ba_solver_solve / download sees the
+ * new cameras.  TMI_BA_ERR_INVALID_ARGUMENT on a sharded handle (world > 1). */
+int32_t tmi_ba_solver_adjust_views(tmi_ba_solver* solver, const tmi_ba_options* options, const uint8_t* view_mask,
+                                   int8_t* view_termination, int32_t* view_iterations, double* view_initial_cost,
+                                   double* view_final_cost, tmi_ba_view_batch_summary* summary);
+
 /* Pre-BA track sub-sampling: theia::SelectGoodTracksForBundleAdjustment
  * (src/theia/sfm/select_good_tracks_for_bundle_adjustment.cc:251-327; callers
  * global_reconstruction_estimator.cc:475-486, incremental_reconstruction_estimator.cc:497-515).

@@ -179,6 +179,18 @@ class CTrackBatchSummary(C.Structure):
     ]
 
 
+class CViewBatchSummary(C.Structure):
+    """tmi_ba_view_batch_summary (batched BundleAdjustView)."""
+    _fields_ = [
+        ("num_views", C.c_int64),
+        ("num_success", C.c_int64),
+        ("total_iterations", C.c_int64),
+        ("num_chains", C.c_int64),
+        ("seconds", C.c_double),
+        ("kernel_seconds", C.c_double),
+    ]
+
+
 class CTwoViewBatch(C.Structure):
     _fields_ = [
         ("num_pairs", C.c_int32),

@@ -35,6 +35,7 @@
 #include "track_kernels.h"
 #include "inner_kernels.h"
 #include "two_view_kernels.h"
+#include "view_kernels.h"
 #include "select_kernels.h"
 #include "structure_gpu.h"
 #include <hipcub/hipcub.hpp>
@@ -625,6 +626,17 @@ struct tmi_ba_solver {
   // are fetched on demand (inner iterations, tmi_ba_solver_evaluate)
   bool device_structure = false;
   long long* d_obs_orig = nullptr;        // [No_pad] caller's observation index or -1
+  // batched view adjustment (view_kernels.h): camera flags and group models kept from create; the view-major
+  // index of the observations and the per-camera records are built on first use
+  std::vector<uint8_t> cam_flags_h;
+  std::vector<int> grp_model_h;
+  unsigned long long* d_view_keys = nullptr;  // [No_pad] (view << 32 | slot) sorted
+  int* d_view_slot_pt = nullptr;          // [No_pad] padded track index of a slot
+  long long* d_view_ptr = nullptr;        // [Nc + 1]
+  std::vector<long long> view_ptr_h;
+  std::vector<int4> view_cam_h;
+  int4* d_view_cam = nullptr;
+  bool view_index_ready = false;          // all of the above built (tmi_ba_solver_adjust_views)
   int n_order_dev = 0, n_spc_dev = 0;
 };
 
@@ -2064,6 +2076,8 @@ static int create_impl(tmi_ba_solver* s, const tmi_ba_problem* P, const tmi_ba_o
   std::vector<int> grp_model(P->group_model, P->group_model + st.G);
   std::vector<int> grp_off(P->group_offset, P->group_offset + st.G + 1);
   s->grp_off_h = grp_off;
+  s->grp_model_h = grp_model;
+  if (P->camera_flags) s->cam_flags_h.assign(P->camera_flags, P->camera_flags + st.Nc);
   std::vector<signed char> rb_cols(st.rb_cols.begin(), st.rb_cols.end());
   std::vector<long long> pair_ptr(st.pair_ptr.begin(), st.pair_ptr.end());
   {
@@ -4049,6 +4063,356 @@ int32_t tmi_ba_adjust_tracks(tmi_ba_problem* P, const tmi_ba_options* O, int8_t*
     g_last_error = s->error;
   }
   tmi_ba_solver_destroy(s);
+  sum->seconds = now_s() - t0;
+  return rc;
+}
+
+// ---- batched BundleAdjustView (view_kernels.h) ---------------------------------------------
+}  // extern "C"
+namespace {
+// device memory of one call, freed on every way out
+struct VbScratch {
+  std::string error;
+  std::vector<void*> allocs;
+  template <class T>
+  hipError_t alloc(T** p, size_t n) {
+    *p = nullptr;
+    const hipError_t e = hipMalloc((void**)p, std::max<size_t>(n, 1) * sizeof(T));
+    if (e == hipSuccess) allocs.push_back((void*)*p);
+    return e;
+  }
+  template <class T>
+  hipError_t upload(T** p, const T* h, size_t n, hipStream_t st) {
+    hipError_t e = alloc(p, n);
+    if (e == hipSuccess && n) e = hipMemcpyAsync(*p, h, n * sizeof(T), hipMemcpyHostToDevice, st);
+    return e;
+  }
+  ~VbScratch() {
+    for (void* p : allocs) hipFree(p);
+  }
+};
+
+// Chains of the views to adjust (selected, observed, something free): the selected views of a group with free
+// entries form one chain in ascending index order, every other view is a chain of its own; longest first.
+void build_view_chains(int Nc, const std::vector<int4>& cam, const int* cam_group, int G,
+                       const std::vector<long long>& vptr, const uint8_t* view_mask, std::vector<int>* chain_ptr,
+                       std::vector<int>* chain_views) {
+  std::vector<std::vector<int> > chains;
+  std::vector<int> group_chain(std::max(G, 0), -1);
+  for (int c = 0; c < Nc; ++c) {
+    if (view_mask && !view_mask[c]) continue;
+    if (cam[c].w == 0 || vptr[c + 1] == vptr[c]) continue;
+    const int g = cam_group[c];
+    if (((unsigned)cam[c].w >> 6) != 0) {
+      if (group_chain[g] < 0) {
+        group_chain[g] = (int)chains.size();
+        chains.emplace_back();
+      }
+      chains[group_chain[g]].push_back(c);
+    } else {
+      chains.push_back({c});
+    }
+  }
+  std::stable_sort(chains.begin(), chains.end(),
+                   [](const std::vector<int>& a, const std::vector<int>& b) { return a.size() > b.size(); });
+  chain_ptr->assign(1, 0);
+  chain_views->clear();
+  for (const auto& ch : chains) {
+    chain_views->insert(chain_views->end(), ch.begin(), ch.end());
+    chain_ptr->push_back((int)chain_views->size());
+  }
+}
+
+// (model, intrinsics offset, intrinsics size, free mask over [extrinsics(6) | intrinsics(10)]) per camera
+int4 view_cam_record(int flags, int model, int offset, int nk, uint32_t free_intr) {
+  uint32_t m = 0;
+  if (!(flags & TMI_BA_CAMERA_POSITION_CONSTANT)) m |= 0x07;
+  if (!(flags & TMI_BA_CAMERA_ORIENTATION_CONSTANT)) m |= 0x38;
+  m |= (free_intr & 0x3ffu) << 6;
+  return make_int4(model, offset, nk, (int)m);
+}
+
+ViewLmArgs view_lm_args(const tmi_ba_options* O) {
+  ViewLmArgs A;
+  A.loss_type = O->loss_function_type;
+  A.loss_width = O->robust_loss_width;
+  A.jacobi_scaling = O->jacobi_scaling;
+  A.max_num_iterations = O->max_num_iterations;
+  A.max_num_consecutive_invalid_steps = O->max_num_consecutive_invalid_steps;
+  A.function_tolerance = O->function_tolerance;
+  A.gradient_tolerance = O->gradient_tolerance;
+  A.parameter_tolerance = O->parameter_tolerance;
+  A.initial_radius = O->initial_trust_region_radius;
+  A.max_radius = O->max_trust_region_radius;
+  A.min_radius = O->min_trust_region_radius;
+  A.min_relative_decrease = O->min_relative_decrease;
+  A.lm_lo = O->min_lm_diagonal;
+  A.lm_hi = O->max_lm_diagonal;
+  return A;
+}
+
+// Launches the chains on `stream` (B holds the parameter / observation pointers) and fills the per-view outputs.
+int run_view_batch(VbScratch* s, hipStream_t stream, ViewBatch B, const tmi_ba_options* O, int Nc,
+                   const std::vector<int4>& cam, const std::vector<int>& chain_ptr, const std::vector<int>& chain_views,
+                   int8_t* view_termination, int32_t* view_iterations, double* view_initial_cost,
+                   double* view_final_cost, tmi_ba_view_batch_summary* sum) {
+  const int n_chains = (int)chain_ptr.size() - 1;
+  int* d_cptr;
+  int* d_cviews;
+  TMI_HIP(s->upload(&d_cptr, chain_ptr.data(), chain_ptr.size(), stream));
+  TMI_HIP(s->upload(&d_cviews, chain_views.data(), chain_views.size(), stream));
+  TMI_HIP(s->alloc(&B.term, (size_t)Nc));
+  TMI_HIP(s->alloc(&B.iters, (size_t)Nc));
+  TMI_HIP(s->alloc(&B.c0, (size_t)Nc));
+  TMI_HIP(s->alloc(&B.c1, (size_t)Nc));
+  TMI_HIP(hipMemsetAsync(B.term, 0xff, std::max(Nc, 1), stream));  // -1: not adjusted
+  TMI_HIP(hipMemsetAsync(B.iters, 0, std::max(Nc, 1) * sizeof(int), stream));
+  TMI_HIP(hipMemsetAsync(B.c0, 0, std::max(Nc, 1) * sizeof(double), stream));
+  TMI_HIP(hipMemsetAsync(B.c1, 0, std::max(Nc, 1) * sizeof(double), stream));
+  B.chain_ptr = d_cptr;
+  B.chain_views = d_cviews;
+  bool pinhole = true;
+  for (const int c : chain_views) pinhole = pinhole && cam[c].x == TMI_BA_PINHOLE;
+  const ViewLmArgs A = view_lm_args(O);
+  hipEvent_t ea, eb;
+  TMI_HIP(hipEventCreate(&ea));
+  TMI_HIP(hipEventCreate(&eb));
+  hipEventRecord(ea, stream);
+  if (n_chains > 0) {
+    if (pinhole)
+      hipLaunchKernelGGL((view_lm_kernel<0>), dim3(n_chains), dim3(256), 0, stream, B, A);
+    else
+      hipLaunchKernelGGL(view_lm_kernel<-1>, dim3(n_chains), dim3(256), 0, stream, B, A);
+  }
+  hipEventRecord(eb, stream);
+  const hipError_t le = hipGetLastError();
+  std::vector<signed char> term((size_t)Nc);
+  std::vector<int> iters((size_t)Nc);
+  std::vector<double> c0((size_t)Nc), c1((size_t)Nc);
+  if (Nc) {
+    TMI_HIP(hipMemcpyAsync(term.data(), B.term, (size_t)Nc, hipMemcpyDeviceToHost, stream));
+    TMI_HIP(hipMemcpyAsync(iters.data(), B.iters, (size_t)Nc * sizeof(int), hipMemcpyDeviceToHost, stream));
+    TMI_HIP(hipMemcpyAsync(c0.data(), B.c0, (size_t)Nc * sizeof(double), hipMemcpyDeviceToHost, stream));
+    TMI_HIP(hipMemcpyAsync(c1.data(), B.c1, (size_t)Nc * sizeof(double), hipMemcpyDeviceToHost, stream));
+  }
+  const hipError_t se = hipStreamSynchronize(stream);
+  float ms = 0.f;
+  hipEventElapsedTime(&ms, ea, eb);
+  hipEventDestroy(ea);
+  hipEventDestroy(eb);
+  TMI_HIP(le);
+  TMI_HIP(se);
+  for (int c = 0; c < Nc; ++c) {
+    if (term[c] >= 0) {
+      sum->num_views++;
+      if (term[c] == 0 || term[c] == 1) sum->num_success++;
+      sum->total_iterations += iters[c];
+    }
+    if (view_termination) view_termination[c] = (int8_t)term[c];
+    if (view_iterations) view_iterations[c] = iters[c];
+    if (view_initial_cost) view_initial_cost[c] = c0[c];
+    if (view_final_cost) view_final_cost[c] = c1[c];
+  }
+  sum->num_chains = n_chains;
+  sum->kernel_seconds = 1e-3 * ms;
+  return TMI_BA_OK;
+}
+}  // namespace
+extern "C" {
+
+int32_t tmi_ba_solver_adjust_views(tmi_ba_solver* s, const tmi_ba_options* O, const uint8_t* view_mask,
+                                   int8_t* view_termination, int32_t* view_iterations, double* view_initial_cost,
+                                   double* view_final_cost, tmi_ba_view_batch_summary* sum) {
+  if (!s || !O || !sum) return TMI_BA_ERR_INVALID_ARGUMENT;
+  memset(sum, 0, sizeof(*sum));
+  const Structure& st = s->st;
+  if (st.world > 1) {
+    g_last_error = s->error = "view adjustment needs every observation of a view: run it on an unsharded handle";
+    return TMI_BA_ERR_INVALID_ARGUMENT;
+  }
+  const double t0 = now_s();
+  TMI_HIP(hipSetDevice(s->device));
+  const int Nc = st.Nc;
+  hipStream_t stream = s->stream;
+  int rc;
+  // static per handle: the view-major index of the handle's observations (device radix sort of (view, slot) keys).
+  // Marked ready only once every part of it exists: a build that fails part-way is redone by the next call (the
+  // temporaries are freed on every way out, the handle's own arrays at destroy).
+  if (!s->view_index_ready) {
+    if (st.No_pad >= (int64_t)0xffffffffLL) {
+      g_last_error = s->error = "view adjustment: more than 2^32 observation slots";
+      return TMI_BA_ERR_UNSUPPORTED;
+    }
+    if ((rc = dev_alloc(s, &s->d_view_ptr, (size_t)Nc + 2))) return rc;
+    if ((rc = dev_alloc(s, &s->d_view_keys, (size_t)std::max<int64_t>(st.No_pad, 1)))) return rc;
+    if ((rc = dev_alloc(s, &s->d_view_slot_pt, (size_t)std::max<int64_t>(st.No_pad, 1)))) return rc;
+    if (st.No_pad > 0) {
+      VbScratch tmp_mem;
+      unsigned long long* keys_in = nullptr;
+      TMI_HIP(tmp_mem.alloc(&keys_in, (size_t)st.No_pad));
+      hipLaunchKernelGGL(view_keys_kernel, dim3(s->nblocks_slices), dim3(256), 0, stream, s->v, keys_in, s->d_view_slot_pt);
+      size_t tmp_bytes = 0;
+      TMI_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, tmp_bytes, keys_in, s->d_view_keys, (int)st.No_pad, 0, 64, stream));
+      unsigned char* tmp = nullptr;
+      TMI_HIP(tmp_mem.alloc(&tmp, std::max<size_t>(tmp_bytes, 16)));
+      TMI_HIP(hipcub::DeviceRadixSort::SortKeys(tmp, tmp_bytes, keys_in, s->d_view_keys, (int)st.No_pad, 0, 64, stream));
+      TMI_HIP(hipStreamSynchronize(stream));
+    }
+    hipLaunchKernelGGL(select_view_ptr_kernel, dim3((Nc + 1 + 255) / 256), dim3(256), 0, stream, s->d_view_keys,
+                       (long long)st.No_pad, Nc, s->d_view_ptr);
+    std::vector<long long> vptr_h((size_t)Nc + 1, 0);
+    TMI_HIP(hipMemcpyAsync(vptr_h.data(), s->d_view_ptr, ((size_t)Nc + 1) * sizeof(long long), hipMemcpyDeviceToHost,
+                           stream));
+    TMI_HIP(hipStreamSynchronize(stream));
+    std::vector<int4> cam_h((size_t)Nc);
+    for (int c = 0; c < Nc; ++c) {
+      const int g = st.cam_group[c];
+      const int o = st.group_offset[g];
+      cam_h[c] = view_cam_record(s->cam_flags_h.empty() ? 0 : s->cam_flags_h[c], s->grp_model_h[g], o,
+                                 st.group_offset[g + 1] - o, st.grp_free[g]);
+    }
+    if ((rc = dev_upload(s, &s->d_view_cam, cam_h))) return rc;
+    s->view_ptr_h.swap(vptr_h);
+    s->view_cam_h.swap(cam_h);
+    s->view_index_ready = true;
+  }
+  std::vector<int> chain_ptr, chain_views;
+  build_view_chains(Nc, s->view_cam_h, st.cam_group.data(), st.G, s->view_ptr_h, view_mask, &chain_ptr, &chain_views);
+  ViewBatch B;
+  memset(&B, 0, sizeof(B));
+  B.ext = s->v.ext;
+  B.intr = s->v.intr;
+  B.cam = s->d_view_cam;
+  B.keys = s->d_view_keys;
+  B.vptr = s->d_view_ptr;
+  B.slot_pt = s->d_view_slot_pt;
+  B.obs_xy = s->v.obs_xy;
+  B.pts = s->v.pts;
+  VbScratch scratch;
+  rc = run_view_batch(&scratch, stream, B, O, Nc, s->view_cam_h, chain_ptr, chain_views, view_termination,
+                      view_iterations, view_initial_cost, view_final_cost, sum);
+  if (rc) {
+    g_last_error = s->error = scratch.error;
+    return rc;
+  }
+  // the cameras moved: every camera-derived cache of the handle is stale
+  prepare_cameras(s, s->v.ext, s->v.intr, s->v.prep);
+  s->v.compact = 0;
+  s->v.sums_ready = 0;
+  TMI_HIP(hipStreamSynchronize(stream));
+  sum->seconds = now_s() - t0;
+  return TMI_BA_OK;
+}
+
+int32_t tmi_ba_adjust_views(tmi_ba_problem* P, const tmi_ba_options* O, const uint8_t* view_mask,
+                            int8_t* view_termination, int32_t* view_iterations, double* view_initial_cost,
+                            double* view_final_cost, tmi_ba_view_batch_summary* sum) {
+  if (!P || !O || !sum) return TMI_BA_ERR_INVALID_ARGUMENT;
+  memset(sum, 0, sizeof(*sum));
+  const double t0 = now_s();
+  VbScratch sc;
+  VbScratch* s = &sc;  // (TMI_HIP reports into s->error)
+  auto bad = [&](const char* why) {
+    g_last_error = why;
+    return TMI_BA_ERR_INVALID_ARGUMENT;
+  };
+  const int Nc = P->num_cameras, G = P->num_groups, Np = P->num_points;
+  const int64_t No = P->num_observations;
+  if (Nc < 0 || G < 0 || Np < 0 || No < 0) return bad("negative size");
+  if ((Nc && (!P->extrinsics || !P->camera_group)) || (G && (!P->group_model || !P->group_offset)) ||
+      (Np && !P->points) || (No && (!P->obs_camera || !P->obs_point || !P->obs_xy)))
+    return bad("missing array");
+  if (No >= (int64_t)0xffffffffLL) return bad("more than 2^32 observations");
+  const int n_intr = G ? P->group_offset[G] : 0;
+  if (n_intr && !P->intrinsics) return bad("missing intrinsics");
+  std::vector<uint32_t> grp_free((size_t)G, 0);
+  for (int g = 0; g < G; ++g) {
+    const int o = P->group_offset[g], nk = P->group_offset[g + 1] - o;
+    if (P->group_model[g] < 0 || P->group_model[g] > 4 || nk != tmi_ba_intrinsics_size(P->group_model[g]) || o < 0)
+      return bad("bad intrinsics group");
+    for (int j = 0; j < nk; ++j)
+      if (!P->intrinsics_constant || !P->intrinsics_constant[o + j]) grp_free[g] |= 1u << j;
+  }
+  std::vector<int4> cam((size_t)Nc);
+  for (int c = 0; c < Nc; ++c) {
+    const int g = P->camera_group[c];
+    if (g < 0 || g >= G) return bad("bad camera group");
+    const int o = P->group_offset[g];
+    cam[c] = view_cam_record(P->camera_flags ? P->camera_flags[c] : 0, P->group_model[g], o,
+                             P->group_offset[g + 1] - o, grp_free[g]);
+  }
+  // host work that does not shrink with the batch: one pass over all observations (check + count) and one over their
+  // cameras (the gather below); summary.seconds - kernel_seconds is this plus the uploads
+  std::vector<long long> optr((size_t)Nc + 1, 0);  // observations per view as ranges of the view-major order
+  for (int64_t i = 0; i < No; ++i) {
+    const int c = P->obs_camera[i], p = P->obs_point[i];
+    if (c < 0 || c >= Nc || p < 0 || p >= Np) return bad("bad observation index");
+    optr[(size_t)c + 1]++;
+  }
+  for (int c = 0; c < Nc; ++c) optr[(size_t)c + 1] += optr[c];
+  std::vector<int> chain_ptr, chain_views;
+  build_view_chains(Nc, cam, P->camera_group, G, optr, view_mask, &chain_ptr, &chain_views);
+  // Of the observations only the chains' views' go up, gathered in view-major order (ascending observation index
+  // inside a view); the points go up whole (one sequential copy: renumbering the observed ones costs a random access
+  // per observation on the host, more than the copy).
+  std::vector<uint8_t> in_chain((size_t)Nc, 0);
+  for (const int c : chain_views) in_chain[c] = 1;
+  std::vector<long long> vptr((size_t)Nc + 1, 0);
+  for (int c = 0; c < Nc; ++c) vptr[(size_t)c + 1] = vptr[c] + (in_chain[c] ? optr[(size_t)c + 1] - optr[c] : 0);
+  const size_t M = (size_t)vptr[Nc];
+  std::vector<unsigned long long> keys(M);
+  std::vector<int> slot_pt(M);
+  std::vector<double> xy(2 * M);
+  if (M) {
+    std::vector<long long> fill(vptr.begin(), vptr.end() - 1);
+    for (int64_t i = 0; i < No; ++i) {
+      const int c = P->obs_camera[i];
+      if (!in_chain[c]) continue;
+      const size_t o = (size_t)fill[c]++;
+      keys[o] = ((unsigned long long)(unsigned)c << 32) | (unsigned long long)o;
+      slot_pt[o] = P->obs_point[i];
+      xy[2 * o] = P->obs_xy[2 * i];
+      xy[2 * o + 1] = P->obs_xy[2 * i + 1];
+    }
+  }
+  if (O->device >= 0) TMI_HIP(hipSetDevice(O->device));
+  hipStream_t stream;
+  TMI_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+  struct StreamGuard {
+    hipStream_t st;
+    ~StreamGuard() { hipStreamDestroy(st); }
+  } guard{stream};
+  ViewBatch B;
+  memset(&B, 0, sizeof(B));
+  int4* d_cam;
+  long long* d_vptr;
+  unsigned long long* d_keys;
+  int* d_slot_pt;
+  double *d_xy, *d_pts;
+  TMI_HIP(s->upload(&B.ext, P->extrinsics, (size_t)6 * Nc, stream));
+  TMI_HIP(s->upload(&B.intr, P->intrinsics, (size_t)n_intr, stream));
+  TMI_HIP(s->upload(&d_cam, cam.data(), cam.size(), stream));
+  TMI_HIP(s->upload(&d_vptr, vptr.data(), vptr.size(), stream));
+  TMI_HIP(s->upload(&d_keys, keys.data(), keys.size(), stream));
+  TMI_HIP(s->upload(&d_slot_pt, slot_pt.data(), slot_pt.size(), stream));
+  TMI_HIP(s->upload(&d_xy, xy.data(), xy.size(), stream));
+  TMI_HIP(s->upload(&d_pts, M ? P->points : nullptr, M ? (size_t)4 * Np : 0, stream));
+  B.cam = d_cam;
+  B.vptr = d_vptr;
+  B.keys = d_keys;
+  B.slot_pt = d_slot_pt;
+  B.obs_xy = d_xy;
+  B.pts = d_pts;
+  int rc = run_view_batch(s, stream, B, O, Nc, cam, chain_ptr, chain_views, view_termination, view_iterations,
+                          view_initial_cost, view_final_cost, sum);
+  if (rc == TMI_BA_OK && Nc) {
+    // the kernel wrote back exactly the usable views' cameras and their groups' free intrinsics
+    TMI_HIP(hipMemcpyAsync(P->extrinsics, B.ext, (size_t)6 * Nc * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (n_intr)
+      TMI_HIP(hipMemcpyAsync(P->intrinsics, B.intr, (size_t)n_intr * sizeof(double), hipMemcpyDeviceToHost, stream));
+    TMI_HIP(hipStreamSynchronize(stream));
+  }
+  if (rc) g_last_error = s->error;
   sum->seconds = now_s() - t0;
   return rc;
 }

@@ -29,6 +29,7 @@ EXPORTS = (
     "tmi_ba_rccl_unique_id", "tmi_ba_solver_init_rccl", "tmi_ba_solver_debug_allreduce",
     "tmi_ba_solver_filter_outlier_tracks", "tmi_ba_filter_outlier_tracks",
     "tmi_ba_solver_adjust_tracks", "tmi_ba_adjust_tracks",
+    "tmi_ba_solver_adjust_views", "tmi_ba_adjust_views",
     "tmi_ba_solver_select_good_tracks", "tmi_ba_select_good_tracks",
     "tmi_ba_adjust_two_views", "tmi_ba_adjust_two_views_angular", "tmi_ba_solver_structure_checksums",
     "tmi_ba_solver_operator_info",
@@ -115,6 +116,12 @@ def load():
     L.tmi_ba_solver_adjust_tracks.restype = C.c_int32
     L.tmi_ba_adjust_tracks.argtypes = [P, O, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, TS]
     L.tmi_ba_adjust_tracks.restype = C.c_int32
+    VS = C.POINTER(abi.CViewBatchSummary)
+    L.tmi_ba_solver_adjust_views.argtypes = [C.c_void_p, O, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, VS]
+    L.tmi_ba_solver_adjust_views.restype = C.c_int32
+    L.tmi_ba_adjust_views.argtypes = [P, O, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, VS]
+    L.tmi_ba_adjust_views.restype = C.c_int32
     L.tmi_ba_adjust_two_views.argtypes = [C.POINTER(abi.CTwoViewBatch), C.c_int32, C.c_int32, C.c_int32,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, TS]
     L.tmi_ba_adjust_two_views.restype = C.c_int32
@@ -238,6 +245,28 @@ def adjust_tracks(problem: abi.Problem, options: abi.COptions):
     if st != 0:
         raise EngineError(st, "tmi_ba_adjust_tracks")
     return term, iters, c0, c1, ts
+
+
+def _view_outputs(n, view_mask):
+    vm = None if view_mask is None else np.ascontiguousarray(view_mask, dtype=np.uint8)
+    if vm is not None and vm.shape != (n,):
+        raise ValueError(f"view_mask must have num_cameras = {n} entries")
+    return (vm, np.full(n, -1, dtype=np.int8), np.zeros(n, dtype=np.int32), np.zeros(n), np.zeros(n),
+            abi.CViewBatchSummary())
+
+
+def adjust_views(problem: abi.Problem, options: abi.COptions, view_mask=None):
+    """One-shot batched BundleAdjustView over the views view_mask selects (None = all); problem.extrinsics /
+    intrinsics are updated in place for the usable views.  Returns (termination [Nc] int8, iterations [Nc] int32,
+    initial cost [Nc], final cost [Nc], CViewBatchSummary)."""
+    L = load()
+    cp = problem.as_c()
+    vm, term, iters, c0, c1, vs = _view_outputs(problem.num_cameras, view_mask)
+    st = L.tmi_ba_adjust_views(C.byref(cp), C.byref(options), None if vm is None else vm.ctypes.data,
+                               term.ctypes.data, iters.ctypes.data, c0.ctypes.data, c1.ctypes.data, C.byref(vs))
+    if st != 0:
+        raise EngineError(st, "tmi_ba_adjust_views")
+    return term, iters, c0, c1, vs
 
 
 def adjust_two_views(batch: abi.TwoViewBatch, point_dof: int = 4, max_num_iterations: int = 200, device: int = -1):
@@ -398,6 +427,17 @@ class Solver:
         if st != 0:
             raise EngineError(st, "tmi_ba_solver_adjust_tracks")
         return term, iters, c0, c1, ts
+
+    def adjust_views(self, options: abi.COptions, view_mask=None):
+        """Batched BundleAdjustView on the resident parameters (unsharded handle); a later solve() / download()
+        sees the new cameras."""
+        vm, term, iters, c0, c1, vs = _view_outputs(self.problem.num_cameras, view_mask)
+        st = self._L.tmi_ba_solver_adjust_views(self._h, C.byref(options), None if vm is None else vm.ctypes.data,
+                                                term.ctypes.data, iters.ctypes.data, c0.ctypes.data, c1.ctypes.data,
+                                                C.byref(vs))
+        if st != 0:
+            raise EngineError(st, "tmi_ba_solver_adjust_views")
+        return term, iters, c0, c1, vs
 
     def structure_checksums(self):
         """Test hook: [24] uint64 checksums of the static structure arrays in HBM ([0] = built on the device)."""
