@@ -567,6 +567,63 @@ int32_t tmi_ba_solver_adjust_views(tmi_ba_solver* solver, const tmi_ba_options* 
                                    int8_t* view_termination, int32_t* view_iterations, double* view_initial_cost,
                                    double* view_final_cost, tmi_ba_view_batch_summary* summary);
 
+/* Batched theia::TrackEstimator (src/theia/sfm/estimate_track.cc:205-264; called from
+ * global_reconstruction_estimator.cc:438-452 and incremental_reconstruction_estimator.cc): every selected track is
+ * (re)estimated from scratch from its observations, every camera of the problem counting as an estimated view and
+ * held constant.  The input point of a selected track is ignored.  Per track:
+ *   1. fewer than 2 observations                                         -> status 1
+ *   2. rays: Camera::PixelToUnitDepthRay(pixel).normalized() (camera.cc:215-223): R^T times the model's
+ *      PixelToCameraCoordinates (the iterative UndistortPoint of PINHOLE, RADIAL_TANGENTIAL and FISHEYE: at most
+ *      100 steps, stop at |delta| < 1e-10 per coordinate; FOV and DIVISION closed form), R from
+ *      ceres::AngleAxisToRotationMatrix
+ *   3. no pair of rays with dot < cos(min_triangulation_angle_degrees) (SufficientTriangulationAngle,
+ *      triangulation.cc:236-250)                                         -> status 1
+ *   4. TriangulateMidpoint (triangulation.cc:130-157): A = sum (I - d d^T), b = sum (I - d d^T) [C; 1] over the
+ *      4 x 4 homogeneous form, Eigen's LLT (a pivot <= 0 fails)          -> status 2 on failure
+ *   5. bundle_adjustment != 0: BundleAdjustTrack with ba_options (bundle_adjustment.cc:96-107; the trust-region
+ *      loop of tmi_ba_adjust_tracks); a termination other than CONVERGENCE / NO_CONVERGENCE -> status 3, the point
+ *      keeps the triangulated value
+ *   6. AcceptableReprojectionError (estimate_track.cc:90-115): any Camera::ProjectPoint depth < 0, or a mean
+ *      squared reprojection error not below max_acceptable_reprojection_error_pixels^2 -> status 4
+ *   otherwise status 0: the track is estimated (the caller calls Track::SetEstimated(true)).
+ * track_status[num_points] (int8): -1 not attempted (not selected, or a constant point), 0..4 as above.  Points
+ * are written for statuses 0, 3 and 4 (where the reference writes Track::MutablePoint) and left untouched for
+ * -1, 1 and 2.  track_mask[num_points]: 1 = estimate (NULL = every track).  track_status may be NULL.
+ * ba_options->point_dof chooses the point parameterisation of step 5 and of the handle. */
+typedef struct tmi_ba_track_estimator_options {
+  double max_acceptable_reprojection_error_pixels; /* 5.0 (estimate_track.h:63-64) */
+  double min_triangulation_angle_degrees;          /* 3.0 (estimate_track.h:66-69) */
+  int32_t bundle_adjustment;                       /* 1   (estimate_track.h:71-73) */
+} tmi_ba_track_estimator_options;
+
+void tmi_ba_track_estimator_options_init(tmi_ba_track_estimator_options* options);
+
+typedef struct tmi_ba_track_estimate_summary {
+  int64_t num_attempts;             /* tracks with a status >= 0 */
+  int64_t num_estimated;            /* status 0 */
+  int64_t num_bad_angle;            /* status 1 (the reference's num_bad_angles_) */
+  int64_t num_failed_triangulation; /* status 2 */
+  int64_t num_failed_ba;            /* status 3 */
+  int64_t num_bad_reprojection;     /* status 4 */
+  double seconds;                   /* wall time of the call */
+  double kernel_seconds;            /* the device kernels alone (HIP events) */
+} tmi_ba_track_estimate_summary;
+
+/* One-shot form: uploads the problem (no Schur structure), estimates, updates problem->points in place.  The
+ * device is ba_options->device (-1 = current). */
+int32_t tmi_ba_estimate_tracks(tmi_ba_problem* problem, const tmi_ba_track_estimator_options* estimator_options,
+                               const tmi_ba_options* ba_options, const uint8_t* track_mask, int8_t* track_status,
+                               tmi_ba_track_estimate_summary* summary);
+
+/* Resident form: the selected tracks of the handle from the handle's cameras; nothing is uploaded but the mask.
+ * The cameras do not move, so the handle's camera-derived caches stay valid, and which tracks a later
+ * tmi_ba_solver_solve includes does not change.  A selected track without observations gets status 1.
+ * TMI_BA_ERR_INVALID_ARGUMENT on a sharded handle (world > 1) or when ba_options->point_dof differs from the
+ * handle's. */
+int32_t tmi_ba_solver_estimate_tracks(tmi_ba_solver* solver, const tmi_ba_track_estimator_options* estimator_options,
+                                      const tmi_ba_options* ba_options, const uint8_t* track_mask,
+                                      int8_t* track_status, tmi_ba_track_estimate_summary* summary);
+
 /* Pre-BA track sub-sampling: theia::SelectGoodTracksForBundleAdjustment
  * (src/theia/sfm/select_good_tracks_for_bundle_adjustment.cc:251-327; callers
  * global_reconstruction_estimator.cc:475-486, incremental_reconstruction_estimator.cc:497-515).

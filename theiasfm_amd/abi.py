@@ -191,6 +191,42 @@ class CViewBatchSummary(C.Structure):
     ]
 
 
+class CTrackEstimatorOptions(C.Structure):
+    """tmi_ba_track_estimator_options (TrackEstimator::Options, estimate_track.h:55-83)."""
+    _fields_ = [
+        ("max_acceptable_reprojection_error_pixels", C.c_double),
+        ("min_triangulation_angle_degrees", C.c_double),
+        ("bundle_adjustment", C.c_int32),
+    ]
+
+
+def track_estimator_options(**overrides) -> CTrackEstimatorOptions:
+    """TrackEstimator::Options defaults; mirrors tmi_ba_track_estimator_options_init."""
+    o = CTrackEstimatorOptions()
+    o.max_acceptable_reprojection_error_pixels = 5.0
+    o.min_triangulation_angle_degrees = 3.0
+    o.bundle_adjustment = 1
+    for k, v in overrides.items():
+        if not hasattr(o, k):
+            raise AttributeError(f"tmi_ba_track_estimator_options has no field {k!r}")
+        setattr(o, k, v)
+    return o
+
+
+class CTrackEstimateSummary(C.Structure):
+    """tmi_ba_track_estimate_summary (batched TrackEstimator)."""
+    _fields_ = [
+        ("num_attempts", C.c_int64),
+        ("num_estimated", C.c_int64),
+        ("num_bad_angle", C.c_int64),
+        ("num_failed_triangulation", C.c_int64),
+        ("num_failed_ba", C.c_int64),
+        ("num_bad_reprojection", C.c_int64),
+        ("seconds", C.c_double),
+        ("kernel_seconds", C.c_double),
+    ]
+
+
 class CTwoViewBatch(C.Structure):
     _fields_ = [
         ("num_pairs", C.c_int32),

@@ -33,6 +33,7 @@
 #include "direct_diag.h"
 #include "pcg_persist.h"
 #include "track_kernels.h"
+#include "track_estimate_kernels.h"
 #include "inner_kernels.h"
 #include "two_view_kernels.h"
 #include "view_kernels.h"
@@ -4413,6 +4414,175 @@ int32_t tmi_ba_adjust_views(tmi_ba_problem* P, const tmi_ba_options* O, const ui
     TMI_HIP(hipStreamSynchronize(stream));
   }
   if (rc) g_last_error = s->error;
+  sum->seconds = now_s() - t0;
+  return rc;
+}
+
+// ---- batched TrackEstimator (track_estimate_kernels.h) ------------------------------------
+void tmi_ba_track_estimator_options_init(tmi_ba_track_estimator_options* o) {
+  if (!o) return;
+  o->max_acceptable_reprojection_error_pixels = 5.0;  // estimate_track.h:63-70
+  o->min_triangulation_angle_degrees = 3.0;
+  o->bundle_adjustment = 1;
+}
+
+int32_t tmi_ba_solver_estimate_tracks(tmi_ba_solver* s, const tmi_ba_track_estimator_options* eo,
+                                      const tmi_ba_options* O, const uint8_t* track_mask, int8_t* track_status,
+                                      tmi_ba_track_estimate_summary* sum) {
+  if (!s || !eo || !O || !sum) return TMI_BA_ERR_INVALID_ARGUMENT;
+  memset(sum, 0, sizeof(*sum));
+  const Structure& st = s->st;
+  if (st.world > 1) {
+    g_last_error = s->error = "track estimation needs every observation of a track: run it on an unsharded handle";
+    return TMI_BA_ERR_INVALID_ARGUMENT;
+  }
+  if (O->point_dof != s->DP) {
+    g_last_error = s->error = "track estimation: options->point_dof differs from the handle's";
+    return TMI_BA_ERR_INVALID_ARGUMENT;
+  }
+  const double t0 = now_s();
+  TMI_HIP(hipSetDevice(s->device));
+  hipStream_t stream = s->stream;
+  int rc = ensure_track_outputs(s);
+  if (rc) return rc;
+  const size_t npad = (size_t)st.Np_pad;
+  // the caller's mask on the padded track order
+  std::vector<unsigned char> attempt_h(npad, 0);
+  for (size_t lp = 0; lp < npad; ++lp) {
+    const int p = st.pt_orig[lp];
+    if (p >= 0 && (!track_mask || track_mask[p])) attempt_h[lp] = 1;
+  }
+  VbScratch scratch;
+  unsigned char* d_attempt = nullptr;
+  signed char* d_status = nullptr;
+  double* d_ray = nullptr;
+  TMI_HIP(scratch.upload(&d_attempt, attempt_h.data(), npad, stream));
+  TMI_HIP(scratch.alloc(&d_status, npad));
+  TMI_HIP(scratch.alloc(&d_ray, (size_t)3 * (size_t)std::max<int64_t>(st.No_pad, 1)));
+  const double cos_min = std::cos(eo->min_triangulation_angle_degrees * (M_PI / 180.0));
+  const double max_err = eo->max_acceptable_reprojection_error_pixels;
+  hipEvent_t ea, eb;
+  TMI_HIP(hipEventCreate(&ea));
+  TMI_HIP(hipEventCreate(&eb));
+  hipEventRecord(ea, stream);
+  if (st.nslices > 0) {
+    hipLaunchKernelGGL(track_rays_kernel, dim3(s->nblocks_tracks), dim3(256), 0, stream, s->v, d_attempt, d_ray);
+    hipLaunchKernelGGL(track_triangulate_kernel, dim3(s->nblocks_tracks), dim3(256), 0, stream, s->v, d_attempt,
+                       d_ray, cos_min, d_status);
+    const signed char* term = nullptr;
+    if (eo->bundle_adjustment) {
+      // BundleAdjustTrack with the caller's options (DENSE_QR and no inner iterations change nothing for a
+      // single track) on the tracks the triangulation accepted; the others are skipped like constant tracks
+      TrackLmArgs A;
+      A.loss_type = O->loss_function_type;
+      A.loss_width = O->robust_loss_width;
+      A.jacobi_scaling = O->jacobi_scaling;
+      A.max_num_iterations = O->max_num_iterations;
+      A.max_num_consecutive_invalid_steps = O->max_num_consecutive_invalid_steps;
+      A.function_tolerance = O->function_tolerance;
+      A.gradient_tolerance = O->gradient_tolerance;
+      A.parameter_tolerance = O->parameter_tolerance;
+      A.initial_radius = O->initial_trust_region_radius;
+      A.max_radius = O->max_trust_region_radius;
+      A.min_radius = O->min_trust_region_radius;
+      A.min_relative_decrease = O->min_relative_decrease;
+      A.lm_lo = O->min_lm_diagonal;
+      A.lm_hi = O->max_lm_diagonal;
+      prepare_cameras(s, s->v.ext, s->v.intr, s->v.prep);
+      if (s->DP == 3 && s->v.uniform_pinhole_default)
+        hipLaunchKernelGGL((track_lm_kernel<3, 0>), dim3(s->nblocks_tracks), dim3(256), 0, stream, s->v, s->v.prep, A,
+                           s->d_trk_term, s->d_trk_iter, s->d_trk_c0, s->d_trk_c1, d_status);
+      else if (s->DP == 3)
+        hipLaunchKernelGGL(track_lm_kernel<3>, dim3(s->nblocks_tracks), dim3(256), 0, stream, s->v, s->v.prep, A,
+                           s->d_trk_term, s->d_trk_iter, s->d_trk_c0, s->d_trk_c1, d_status);
+      else if (s->v.uniform_pinhole_default)
+        hipLaunchKernelGGL((track_lm_kernel<4, 0>), dim3(s->nblocks_tracks), dim3(256), 0, stream, s->v, s->v.prep, A,
+                           s->d_trk_term, s->d_trk_iter, s->d_trk_c0, s->d_trk_c1, d_status);
+      else
+        hipLaunchKernelGGL(track_lm_kernel<4>, dim3(s->nblocks_tracks), dim3(256), 0, stream, s->v, s->v.prep, A,
+                           s->d_trk_term, s->d_trk_iter, s->d_trk_c0, s->d_trk_c1, d_status);
+      term = s->d_trk_term;
+    }
+    hipLaunchKernelGGL(track_accept_kernel, dim3(s->nblocks_tracks), dim3(256), 0, stream, s->v, max_err * max_err,
+                       term, d_status);
+  }
+  hipEventRecord(eb, stream);
+  const hipError_t le = hipGetLastError();
+  std::vector<signed char> status_h(npad);
+  if (npad) TMI_HIP(hipMemcpyAsync(status_h.data(), d_status, npad, hipMemcpyDeviceToHost, stream));
+  const hipError_t se = hipStreamSynchronize(stream);
+  float ms = 0.f;
+  hipEventElapsedTime(&ms, ea, eb);
+  hipEventDestroy(ea);
+  hipEventDestroy(eb);
+  TMI_HIP(le);
+  TMI_HIP(se);
+  auto count = [sum](int code) {
+    if (code < 0) return;
+    sum->num_attempts++;
+    switch (code) {
+      case 0: sum->num_estimated++; break;
+      case 1: sum->num_bad_angle++; break;
+      case 2: sum->num_failed_triangulation++; break;
+      case 3: sum->num_failed_ba++; break;
+      default: sum->num_bad_reprojection++; break;
+    }
+  };
+  for (size_t lp = 0; lp < npad; ++lp) {
+    const int p = st.pt_orig[lp];
+    if (p < 0) continue;
+    count(status_h[lp]);
+    if (track_status) track_status[p] = (int8_t)status_h[lp];
+  }
+  // a track without observations has fewer than two views (estimate_track.cc:224-230)
+  for (const int p : st.unobserved) {
+    const int code = (!track_mask || track_mask[p]) ? 1 : -1;
+    count(code);
+    if (track_status) track_status[p] = (int8_t)code;
+  }
+  sum->kernel_seconds = 1e-3 * ms;
+  sum->seconds = now_s() - t0;
+  return TMI_BA_OK;
+}
+
+int32_t tmi_ba_estimate_tracks(tmi_ba_problem* P, const tmi_ba_track_estimator_options* eo,
+                               const tmi_ba_options* O, const uint8_t* track_mask, int8_t* track_status,
+                               tmi_ba_track_estimate_summary* sum) {
+  if (!P || !eo || !O || !sum) return TMI_BA_ERR_INVALID_ARGUMENT;
+  memset(sum, 0, sizeof(*sum));
+  const double t0 = now_s();
+  // argument errors before the device is touched
+  auto bad = [](const char* why) {
+    g_last_error = why;
+    return TMI_BA_ERR_INVALID_ARGUMENT;
+  };
+  const int Nc = P->num_cameras, Np = P->num_points;
+  const int64_t No = P->num_observations;
+  if (Nc < 0 || P->num_groups < 0 || Np < 0 || No < 0) return bad("negative size");
+  if ((Nc && (!P->extrinsics || !P->camera_group)) || (Np && !P->points) ||
+      (No && (!P->obs_camera || !P->obs_point || !P->obs_xy)))
+    return bad("missing array");
+  if (O->point_dof != 3 && O->point_dof != 4) return bad("point_dof must be 3 or 4");
+  for (int64_t i = 0; i < No; ++i)
+    if (P->obs_camera[i] < 0 || P->obs_camera[i] >= Nc || P->obs_point[i] < 0 || P->obs_point[i] >= Np)
+      return bad("observation index out of range");
+  // constant points are never attempted, observed or not
+  std::vector<uint8_t> mask;
+  if (P->point_constant && P->num_points > 0) {
+    mask.assign((size_t)P->num_points, 1);
+    for (int p = 0; p < P->num_points; ++p)
+      mask[p] = (uint8_t)((!track_mask || track_mask[p]) && !P->point_constant[p]);
+  }
+  tmi_ba_solver* s = new tmi_ba_solver();
+  int rc = create_impl(s, P, O, 0, 1, /*light=*/true);
+  if (rc == TMI_BA_OK) {
+    rc = tmi_ba_solver_estimate_tracks(s, eo, O, mask.empty() ? track_mask : mask.data(), track_status, sum);
+    if (rc == TMI_BA_OK) rc = tmi_ba_solver_download(s, P);  // cameras are constant here: only points changed
+    else g_last_error = s->error;
+  } else {
+    g_last_error = s->error;
+  }
+  tmi_ba_solver_destroy(s);
   sum->seconds = now_s() - t0;
   return rc;
 }

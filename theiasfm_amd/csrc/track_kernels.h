@@ -266,18 +266,21 @@ __device__ __forceinline__ bool track_cost(const DeviceView& v, const double* __
 // IsSolutionUsable, bundle_adjuster.cc:213-216).  The trust-region loop is the one the
 // full solver runs (engine.hip / Ceres 1.14 TrustRegionMinimizer) with an empty camera
 // side: the step is -(V + D)^-1 g on the track's own 2k x DP Jacobian.
+// skip[lp] != 0 (optional, padded track order): the track is left alone like a constant one
+// (the track estimator adjusts only the tracks its triangulation accepted).
 template <int DP, int UMODEL = -1>
 __global__ __launch_bounds__(256) void track_lm_kernel(DeviceView v, const double* __restrict__ prep, TrackLmArgs A,
                                                        signed char* __restrict__ termination,
                                                        int* __restrict__ iterations,
                                                        double* __restrict__ initial_cost,
-                                                       double* __restrict__ final_cost) {
+                                                       double* __restrict__ final_cost,
+                                                       const signed char* __restrict__ skip = nullptr) {
   constexpr int NS = sym_size(DP);
   const TrackMap tm = track_map(v);
   if (!tm.valid) return;
   const int lp = tm.lp;
   const int k = tm.k;
-  if (k == 0 || v.pt_const[lp]) {  // uniform over the lanes that share a track
+  if (k == 0 || v.pt_const[lp] || (skip && skip[lp])) {  // uniform over the lanes that share a track
     if (tm.leader) {
       termination[lp] = -1;
       iterations[lp] = 0;

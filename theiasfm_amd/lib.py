@@ -30,6 +30,7 @@ EXPORTS = (
     "tmi_ba_solver_filter_outlier_tracks", "tmi_ba_filter_outlier_tracks",
     "tmi_ba_solver_adjust_tracks", "tmi_ba_adjust_tracks",
     "tmi_ba_solver_adjust_views", "tmi_ba_adjust_views",
+    "tmi_ba_track_estimator_options_init", "tmi_ba_solver_estimate_tracks", "tmi_ba_estimate_tracks",
     "tmi_ba_solver_select_good_tracks", "tmi_ba_select_good_tracks",
     "tmi_ba_adjust_two_views", "tmi_ba_adjust_two_views_angular", "tmi_ba_solver_structure_checksums",
     "tmi_ba_solver_operator_info",
@@ -122,6 +123,13 @@ def load():
     L.tmi_ba_solver_adjust_views.restype = C.c_int32
     L.tmi_ba_adjust_views.argtypes = [P, O, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, VS]
     L.tmi_ba_adjust_views.restype = C.c_int32
+    EO, ES = C.POINTER(abi.CTrackEstimatorOptions), C.POINTER(abi.CTrackEstimateSummary)
+    L.tmi_ba_track_estimator_options_init.argtypes = [EO]
+    L.tmi_ba_track_estimator_options_init.restype = None
+    L.tmi_ba_solver_estimate_tracks.argtypes = [C.c_void_p, EO, O, C.c_void_p, C.c_void_p, ES]
+    L.tmi_ba_solver_estimate_tracks.restype = C.c_int32
+    L.tmi_ba_estimate_tracks.argtypes = [P, EO, O, C.c_void_p, C.c_void_p, ES]
+    L.tmi_ba_estimate_tracks.restype = C.c_int32
     L.tmi_ba_adjust_two_views.argtypes = [C.POINTER(abi.CTwoViewBatch), C.c_int32, C.c_int32, C.c_int32,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, TS]
     L.tmi_ba_adjust_two_views.restype = C.c_int32
@@ -267,6 +275,27 @@ def adjust_views(problem: abi.Problem, options: abi.COptions, view_mask=None):
     if st != 0:
         raise EngineError(st, "tmi_ba_adjust_views")
     return term, iters, c0, c1, vs
+
+
+def _track_mask(n, track_mask):
+    tm = None if track_mask is None else np.ascontiguousarray(track_mask, dtype=np.uint8)
+    if tm is not None and tm.shape != (n,):
+        raise ValueError(f"track_mask must have num_points = {n} entries")
+    return tm, np.full(n, -1, dtype=np.int8), abi.CTrackEstimateSummary()
+
+
+def estimate_tracks(problem: abi.Problem, estimator_options: abi.CTrackEstimatorOptions, ba_options: abi.COptions,
+                    track_mask=None):
+    """One-shot batched TrackEstimator over the tracks track_mask selects (None = all); problem.points is updated in
+    place for the statuses 0, 3 and 4.  Returns (status [Np] int8, CTrackEstimateSummary)."""
+    L = load()
+    cp = problem.as_c()
+    tm, status, es = _track_mask(problem.num_points, track_mask)
+    st = L.tmi_ba_estimate_tracks(C.byref(cp), C.byref(estimator_options), C.byref(ba_options),
+                                  None if tm is None else tm.ctypes.data, status.ctypes.data, C.byref(es))
+    if st != 0:
+        raise EngineError(st, "tmi_ba_estimate_tracks")
+    return status, es
 
 
 def adjust_two_views(batch: abi.TwoViewBatch, point_dof: int = 4, max_num_iterations: int = 200, device: int = -1):
@@ -438,6 +467,18 @@ class Solver:
         if st != 0:
             raise EngineError(st, "tmi_ba_solver_adjust_views")
         return term, iters, c0, c1, vs
+
+    def estimate_tracks(self, estimator_options: abi.CTrackEstimatorOptions, ba_options: abi.COptions,
+                        track_mask=None):
+        """Batched TrackEstimator on the resident cameras (unsharded handle); a later solve() / download() sees the
+        new points.  Returns (status [Np] int8, CTrackEstimateSummary)."""
+        tm, status, es = _track_mask(self.problem.num_points, track_mask)
+        st = self._L.tmi_ba_solver_estimate_tracks(self._h, C.byref(estimator_options), C.byref(ba_options),
+                                                   None if tm is None else tm.ctypes.data, status.ctypes.data,
+                                                   C.byref(es))
+        if st != 0:
+            raise EngineError(st, "tmi_ba_solver_estimate_tracks")
+        return status, es
 
     def structure_checksums(self):
         """Test hook: [24] uint64 checksums of the static structure arrays in HBM ([0] = built on the device)."""
