@@ -3051,6 +3051,23 @@ static int solve_reduced_dense(tmi_ba_solver* s, int* usable) {
 // ---- inner iterations: one coordinate-descent sweep over the candidate arrays -----------
 static int ensure_track_outputs(tmi_ba_solver* s);
 
+// track_lm_kernel on every track of v (prep: its cameras' prepared records) into the handle's per-track outputs;
+// tracks with skip[lp] != 0 are left alone (optional).  One camera model for the whole problem: the instantiation
+// without the model switch (track_kernels.h).
+static void launch_track_lm(tmi_ba_solver* s, const DeviceView& v, const double* prep, const SmallLmArgs& A,
+                            const signed char* skip = nullptr) {
+  const SmallLmOut out{s->d_trk_term, s->d_trk_iter, s->d_trk_c0, s->d_trk_c1};
+  const dim3 grid(s->nblocks_tracks), block(256);
+  if (s->DP == 3 && v.uniform_pinhole_default)
+    hipLaunchKernelGGL((track_lm_kernel<3, 0>), grid, block, 0, s->stream, v, prep, A, out, skip);
+  else if (s->DP == 3)
+    hipLaunchKernelGGL(track_lm_kernel<3>, grid, block, 0, s->stream, v, prep, A, out, skip);
+  else if (v.uniform_pinhole_default)
+    hipLaunchKernelGGL((track_lm_kernel<4, 0>), grid, block, 0, s->stream, v, prep, A, out, skip);
+  else
+    hipLaunchKernelGGL(track_lm_kernel<4>, grid, block, 0, s->stream, v, prep, A, out, skip);
+}
+
 static int ensure_inner(tmi_ba_solver* s) {
   tmi_ba_solver::InnerCtx& I = s->inner;
   if (I.ready) return TMI_BA_OK;
@@ -3246,21 +3263,6 @@ static int run_inner_sweep(tmi_ba_solver* s, const tmi_ba_options* O) {
   // the points, each against its (now constant) cameras: the batched single-track solver on
   // the candidate arrays, Ceres' default minimizer options
   if (st.nslices > 0) {
-    TrackLmArgs A;
-    A.loss_type = O->loss_function_type;
-    A.loss_width = O->robust_loss_width;
-    A.jacobi_scaling = 1;
-    A.max_num_iterations = 50;
-    A.max_num_consecutive_invalid_steps = 5;
-    A.function_tolerance = 1e-6;
-    A.gradient_tolerance = 1e-10;
-    A.parameter_tolerance = 1e-8;
-    A.initial_radius = 1e4;
-    A.max_radius = 1e16;
-    A.min_radius = 1e-32;
-    A.min_relative_decrease = 1e-3;
-    A.lm_lo = 1e-6;
-    A.lm_hi = 1e32;
     if ((rc = ensure_track_outputs(s))) return rc;
     DeviceView vc = v;
     vc.ext = v.ext_c;
@@ -3268,19 +3270,7 @@ static int run_inner_sweep(tmi_ba_solver* s, const tmi_ba_options* O) {
     vc.pts = v.pts_c;
     Timed t(s, TMI_BA_K_LINEARIZE);
     prepare_cameras(s, v.ext_c, v.intr_c, v.prep_c);  // the two view sets moved the candidate cameras
-    // (one camera model for the whole problem: the instantiation without the model switch, track_kernels.h)
-    if (s->DP == 3 && v.uniform_pinhole_default)
-      hipLaunchKernelGGL((track_lm_kernel<3, 0>), dim3(s->nblocks_tracks), dim3(256), 0, stream, vc, v.prep_c, A, s->d_trk_term,
-                         s->d_trk_iter, s->d_trk_c0, s->d_trk_c1);
-    else if (s->DP == 3)
-      hipLaunchKernelGGL(track_lm_kernel<3>, dim3(s->nblocks_tracks), dim3(256), 0, stream, vc, v.prep_c, A, s->d_trk_term,
-                         s->d_trk_iter, s->d_trk_c0, s->d_trk_c1);
-    else if (v.uniform_pinhole_default)
-      hipLaunchKernelGGL((track_lm_kernel<4, 0>), dim3(s->nblocks_tracks), dim3(256), 0, stream, vc, v.prep_c, A, s->d_trk_term,
-                         s->d_trk_iter, s->d_trk_c0, s->d_trk_c1);
-    else
-      hipLaunchKernelGGL(track_lm_kernel<4>, dim3(s->nblocks_tracks), dim3(256), 0, stream, vc, v.prep_c, A, s->d_trk_term,
-                         s->d_trk_iter, s->d_trk_c0, s->d_trk_c1);
+    launch_track_lm(s, vc, v.prep_c, ceres_default_lm_args(50, O->loss_function_type, O->robust_loss_width));
   }
   return TMI_BA_OK;
 }
@@ -3833,6 +3823,135 @@ int32_t tmi_ba_solve(tmi_ba_problem* P, const tmi_ba_options* O, tmi_ba_summary*
   return rc2;
 }
 
+// ---- one-shot calls and the batched small-problem solvers (small_lm.h) --------------------------
+}  // extern "C"
+namespace {
+// Device memory of one call, freed on every way out, and the stream it runs on: a stream of its own (open) or a
+// borrowed one.  error: what TMI_HIP reports.
+struct OneShot {
+  std::string error;
+  std::vector<void*> allocs;
+  hipStream_t stream = nullptr;
+  bool own_stream = false;
+  explicit OneShot(hipStream_t borrowed = nullptr) : stream(borrowed) {}
+  OneShot(const OneShot&) = delete;
+  OneShot& operator=(const OneShot&) = delete;
+  // a stream of its own on `device` (< 0: the current device)
+  int open(int device) {
+    OneShot* s = this;
+    if (device >= 0) TMI_HIP(hipSetDevice(device));
+    TMI_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    own_stream = true;
+    return TMI_BA_OK;
+  }
+  template <class T>
+  hipError_t alloc(T** p, size_t n) {
+    *p = nullptr;
+    const hipError_t e = hipMalloc((void**)p, std::max<size_t>(n, 1) * sizeof(T));
+    if (e == hipSuccess) allocs.push_back((void*)*p);
+    return e;
+  }
+  template <class T>
+  hipError_t upload(T** p, const T* h, size_t n) {
+    hipError_t e = alloc(p, n);
+    if (e == hipSuccess && n) e = hipMemcpyAsync(*p, h, n * sizeof(T), hipMemcpyHostToDevice, stream);
+    return e;
+  }
+  // per-item outputs of a batched solve, preset to "nothing to solve" (-1, 0, 0, 0)
+  int alloc_outputs(SmallLmOut* o, size_t n) {
+    OneShot* s = this;
+    TMI_HIP(alloc(&o->term, n));
+    TMI_HIP(alloc(&o->iters, n));
+    TMI_HIP(alloc(&o->c0, n));
+    TMI_HIP(alloc(&o->c1, n));
+    n = std::max<size_t>(n, 1);
+    TMI_HIP(hipMemsetAsync(o->term, 0xff, n, stream));
+    TMI_HIP(hipMemsetAsync(o->iters, 0, n * sizeof(int), stream));
+    TMI_HIP(hipMemsetAsync(o->c0, 0, n * sizeof(double), stream));
+    TMI_HIP(hipMemsetAsync(o->c1, 0, n * sizeof(double), stream));
+    return TMI_BA_OK;
+  }
+  ~OneShot() {
+    if (own_stream) hipStreamDestroy(stream);
+    for (void* p : allocs) hipFree(p);
+  }
+};
+
+// The caller's per-item arrays (each may be null).
+struct ItemArrays {
+  int8_t* term;
+  int32_t* iters;
+  double* c0;
+  double* c1;
+};
+
+// One batched small-problem solve: launch() queues it on `stream` between two events (sum->kernel_seconds), then the n
+// per-item outputs d are read back, counted (*num_items: termination >= 0; successes 0 and 1) and item i is written to
+// the caller's arrays at map[i] (null: the identity; map[i] < 0: padding).  term_h (optional): the terminations.
+// TMI_HIP reports into s->error.
+template <class Holder, class Sum, class Launch>
+int run_small_lm(Holder* s, hipStream_t stream, const SmallLmOut& d, size_t n, const int* map, Launch launch,
+                 const ItemArrays& out, Sum* sum, int64_t* num_items, std::vector<signed char>* term_h = nullptr) {
+  hipEvent_t ea, eb;
+  TMI_HIP(hipEventCreate(&ea));
+  TMI_HIP(hipEventCreate(&eb));
+  hipEventRecord(ea, stream);
+  launch();
+  hipEventRecord(eb, stream);
+  const hipError_t le = hipGetLastError();
+  std::vector<signed char> term(n);
+  std::vector<int> iters(n);
+  std::vector<double> c0(out.c0 ? n : 0), c1(out.c1 ? n : 0);
+  hipError_t ce = hipSuccess;
+  if (n) {
+    ce = hipMemcpyAsync(term.data(), d.term, n, hipMemcpyDeviceToHost, stream);
+    if (ce == hipSuccess) ce = hipMemcpyAsync(iters.data(), d.iters, n * sizeof(int), hipMemcpyDeviceToHost, stream);
+    if (ce == hipSuccess && out.c0) ce = hipMemcpyAsync(c0.data(), d.c0, n * sizeof(double), hipMemcpyDeviceToHost, stream);
+    if (ce == hipSuccess && out.c1) ce = hipMemcpyAsync(c1.data(), d.c1, n * sizeof(double), hipMemcpyDeviceToHost, stream);
+  }
+  const hipError_t se = hipStreamSynchronize(stream);
+  float ms = 0.f;
+  hipEventElapsedTime(&ms, ea, eb);
+  hipEventDestroy(ea);
+  hipEventDestroy(eb);
+  TMI_HIP(le);
+  TMI_HIP(ce);
+  TMI_HIP(se);
+  for (size_t i = 0; i < n; ++i) {
+    const int p = map ? map[i] : (int)i;
+    if (p < 0) continue;
+    const int t = term[i];
+    if (t >= 0) {
+      ++*num_items;
+      if (t == 0 || t == 1) sum->num_success++;
+      sum->total_iterations += iters[i];
+    }
+    if (out.term) out.term[p] = (int8_t)t;
+    if (out.iters) out.iters[p] = iters[i];
+    if (out.c0) out.c0[p] = c0[i];
+    if (out.c1) out.c1[p] = c1[i];
+  }
+  sum->kernel_seconds = 1e-3 * ms;
+  if (term_h) term_h->swap(term);
+  return TMI_BA_OK;
+}
+
+// One-shot form of a resident track entry point: call(s) on a light handle of P, the points downloaded into
+// `download` afterwards if it is given (the cameras are constant on these paths), the handle destroyed on every way
+// out.
+template <class Call>
+int with_light_handle(const tmi_ba_problem* P, const tmi_ba_options* O, tmi_ba_problem* download, Call call) {
+  tmi_ba_solver* s = new tmi_ba_solver();
+  int rc = create_impl(s, P, O, 0, 1, /*light=*/true);
+  if (rc == TMI_BA_OK) rc = call(s);
+  if (rc == TMI_BA_OK && download) rc = tmi_ba_solver_download(s, download);
+  if (rc != TMI_BA_OK) g_last_error = s->error;
+  tmi_ba_solver_destroy(s);
+  return rc;
+}
+}  // namespace
+extern "C" {
+
 // ---- per-track side kernels ----------------------------------
 static int ensure_track_outputs(tmi_ba_solver* s) {
   if (s->d_trk_flag) return TMI_BA_OK;
@@ -3947,15 +4066,10 @@ int32_t tmi_ba_filter_outlier_tracks(const tmi_ba_problem* P, int32_t device,
   tmi_ba_options O;
   tmi_ba_options_init(&O);
   O.device = device;
-  tmi_ba_solver* s = new tmi_ba_solver();
-  int rc = create_impl(s, P, &O, 0, 1, /*light=*/true);
-  if (rc == TMI_BA_OK)
-    rc = tmi_ba_solver_filter_outlier_tracks(s, max_inlier_reprojection_error,
-                                             min_triangulation_angle_degrees, track_flag,
-                                             track_mean_sq_error, sum);
-  else
-    g_last_error = s->error;
-  tmi_ba_solver_destroy(s);
+  const int rc = with_light_handle(P, &O, nullptr, [&](tmi_ba_solver* s) {
+    return tmi_ba_solver_filter_outlier_tracks(s, max_inlier_reprojection_error, min_triangulation_angle_degrees,
+                                               track_flag, track_mean_sq_error, sum);
+  });
   sum->seconds = now_s() - t0;
   return rc;
 }
@@ -3971,77 +4085,20 @@ int32_t tmi_ba_solver_adjust_tracks(tmi_ba_solver* s, const tmi_ba_options* O, i
   int rc = ensure_track_outputs(s);
   if (rc) return rc;
   const Structure& st = s->st;
-  TrackLmArgs A;
-  A.loss_type = O->loss_function_type;
-  A.loss_width = O->robust_loss_width;
-  A.jacobi_scaling = O->jacobi_scaling;
-  A.max_num_iterations = O->max_num_iterations;
-  A.max_num_consecutive_invalid_steps = O->max_num_consecutive_invalid_steps;
-  A.function_tolerance = O->function_tolerance;
-  A.gradient_tolerance = O->gradient_tolerance;
-  A.parameter_tolerance = O->parameter_tolerance;
-  A.initial_radius = O->initial_trust_region_radius;
-  A.max_radius = O->max_trust_region_radius;
-  A.min_radius = O->min_trust_region_radius;
-  A.min_relative_decrease = O->min_relative_decrease;
-  A.lm_lo = O->min_lm_diagonal;
-  A.lm_hi = O->max_lm_diagonal;
-  hipEvent_t ea, eb;
-  TMI_HIP(hipEventCreate(&ea));
-  TMI_HIP(hipEventCreate(&eb));
-  TMI_HIP(hipEventRecord(ea, s->stream));
-  prepare_cameras(s, s->v.ext, s->v.intr, s->v.prep);  // (inside the timed region: part of the call's device work)
-  if (st.nslices > 0) {
-    if (s->DP == 3 && s->v.uniform_pinhole_default)
-      hipLaunchKernelGGL((track_lm_kernel<3, 0>), dim3(s->nblocks_tracks), dim3(256), 0, s->stream, s->v, s->v.prep, A,
-                         s->d_trk_term, s->d_trk_iter, s->d_trk_c0, s->d_trk_c1);
-    else if (s->DP == 3)
-      hipLaunchKernelGGL(track_lm_kernel<3>, dim3(s->nblocks_tracks), dim3(256), 0, s->stream, s->v, s->v.prep, A,
-                         s->d_trk_term, s->d_trk_iter, s->d_trk_c0, s->d_trk_c1);
-    else if (s->v.uniform_pinhole_default)
-      hipLaunchKernelGGL((track_lm_kernel<4, 0>), dim3(s->nblocks_tracks), dim3(256), 0, s->stream, s->v, s->v.prep, A,
-                         s->d_trk_term, s->d_trk_iter, s->d_trk_c0, s->d_trk_c1);
-    else
-      hipLaunchKernelGGL(track_lm_kernel<4>, dim3(s->nblocks_tracks), dim3(256), 0, s->stream, s->v, s->v.prep, A,
-                         s->d_trk_term, s->d_trk_iter, s->d_trk_c0, s->d_trk_c1);
-  }
-  TMI_HIP(hipEventRecord(eb, s->stream));
-  const size_t n = (size_t)st.Np_pad;
-  std::vector<signed char> term(n);
-  std::vector<int> iters(n);
-  std::vector<double> c0(track_initial_cost ? n : 0), c1(track_final_cost ? n : 0);
-  if (n) {
-    TMI_HIP(hipMemcpyAsync(term.data(), s->d_trk_term, n, hipMemcpyDeviceToHost, s->stream));
-    TMI_HIP(hipMemcpyAsync(iters.data(), s->d_trk_iter, n * sizeof(int), hipMemcpyDeviceToHost, s->stream));
-    if (!c0.empty()) TMI_HIP(hipMemcpyAsync(c0.data(), s->d_trk_c0, n * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    if (!c1.empty()) TMI_HIP(hipMemcpyAsync(c1.data(), s->d_trk_c1, n * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-  }
-  TMI_HIP(hipStreamSynchronize(s->stream));
-  float ms = 0.f;
-  hipEventElapsedTime(&ms, ea, eb);
-  hipEventDestroy(ea);
-  hipEventDestroy(eb);
-  for (int lp = 0; lp < st.Np_pad; ++lp) {
-    const int p = st.pt_orig[lp];
-    if (p < 0) continue;
-    const int t = term[lp];
-    if (t >= 0) {
-      sum->num_tracks++;
-      if (t == 0 || t == 1) sum->num_success++;
-      sum->total_iterations += iters[lp];
-    }
-    if (track_termination) track_termination[p] = (int8_t)t;
-    if (track_iterations) track_iterations[p] = iters[lp];
-    if (track_initial_cost) track_initial_cost[p] = c0[lp];
-    if (track_final_cost) track_final_cost[p] = c1[lp];
-  }
+  const SmallLmArgs A = small_lm_args(O);
+  const SmallLmOut d{s->d_trk_term, s->d_trk_iter, s->d_trk_c0, s->d_trk_c1};
+  const ItemArrays out{track_termination, track_iterations, track_initial_cost, track_final_cost};
+  rc = run_small_lm(s, s->stream, d, (size_t)st.Np_pad, st.pt_orig.data(), [&] {
+    prepare_cameras(s, s->v.ext, s->v.intr, s->v.prep);  // (inside the timed region: part of the call's device work)
+    if (st.nslices > 0) launch_track_lm(s, s->v, s->v.prep, A);
+  }, out, sum, &sum->num_tracks);
+  if (rc) return rc;
   for (const int p : st.unobserved) {
     if (track_termination) track_termination[p] = -1;
     if (track_iterations) track_iterations[p] = 0;
     if (track_initial_cost) track_initial_cost[p] = 0.0;
     if (track_final_cost) track_final_cost[p] = 0.0;
   }
-  sum->kernel_seconds = ms * 1e-3;
   sum->seconds = now_s() - t0;
   return TMI_BA_OK;
 }
@@ -4052,18 +4109,10 @@ int32_t tmi_ba_adjust_tracks(tmi_ba_problem* P, const tmi_ba_options* O, int8_t*
   if (!P || !O || !sum) return TMI_BA_ERR_INVALID_ARGUMENT;
   memset(sum, 0, sizeof(*sum));
   const double t0 = now_s();
-  tmi_ba_solver* s = new tmi_ba_solver();
-  int rc = create_impl(s, P, O, 0, 1, /*light=*/true);
-  if (rc == TMI_BA_OK) {
-    rc = tmi_ba_solver_adjust_tracks(s, O, track_termination, track_iterations, track_initial_cost,
-                                     track_final_cost, sum);
-    if (rc == TMI_BA_OK) {
-      rc = tmi_ba_solver_download(s, P);  // cameras are constant here: only points changed
-    }
-  } else {
-    g_last_error = s->error;
-  }
-  tmi_ba_solver_destroy(s);
+  const int rc = with_light_handle(P, O, P, [&](tmi_ba_solver* s) {
+    return tmi_ba_solver_adjust_tracks(s, O, track_termination, track_iterations, track_initial_cost,
+                                       track_final_cost, sum);
+  });
   sum->seconds = now_s() - t0;
   return rc;
 }
@@ -4071,28 +4120,6 @@ int32_t tmi_ba_adjust_tracks(tmi_ba_problem* P, const tmi_ba_options* O, int8_t*
 // ---- batched BundleAdjustView (view_kernels.h) ---------------------------------------------
 }  // extern "C"
 namespace {
-// device memory of one call, freed on every way out
-struct VbScratch {
-  std::string error;
-  std::vector<void*> allocs;
-  template <class T>
-  hipError_t alloc(T** p, size_t n) {
-    *p = nullptr;
-    const hipError_t e = hipMalloc((void**)p, std::max<size_t>(n, 1) * sizeof(T));
-    if (e == hipSuccess) allocs.push_back((void*)*p);
-    return e;
-  }
-  template <class T>
-  hipError_t upload(T** p, const T* h, size_t n, hipStream_t st) {
-    hipError_t e = alloc(p, n);
-    if (e == hipSuccess && n) e = hipMemcpyAsync(*p, h, n * sizeof(T), hipMemcpyHostToDevice, st);
-    return e;
-  }
-  ~VbScratch() {
-    for (void* p : allocs) hipFree(p);
-  }
-};
-
 // Chains of the views to adjust (selected, observed, something free): the selected views of a group with free
 // entries form one chain in ascending index order, every other view is a chain of its own; longest first.
 void build_view_chains(int Nc, const std::vector<int4>& cam, const int* cam_group, int G,
@@ -4133,90 +4160,31 @@ int4 view_cam_record(int flags, int model, int offset, int nk, uint32_t free_int
   return make_int4(model, offset, nk, (int)m);
 }
 
-ViewLmArgs view_lm_args(const tmi_ba_options* O) {
-  ViewLmArgs A;
-  A.loss_type = O->loss_function_type;
-  A.loss_width = O->robust_loss_width;
-  A.jacobi_scaling = O->jacobi_scaling;
-  A.max_num_iterations = O->max_num_iterations;
-  A.max_num_consecutive_invalid_steps = O->max_num_consecutive_invalid_steps;
-  A.function_tolerance = O->function_tolerance;
-  A.gradient_tolerance = O->gradient_tolerance;
-  A.parameter_tolerance = O->parameter_tolerance;
-  A.initial_radius = O->initial_trust_region_radius;
-  A.max_radius = O->max_trust_region_radius;
-  A.min_radius = O->min_trust_region_radius;
-  A.min_relative_decrease = O->min_relative_decrease;
-  A.lm_lo = O->min_lm_diagonal;
-  A.lm_hi = O->max_lm_diagonal;
-  return A;
-}
-
-// Launches the chains on `stream` (B holds the parameter / observation pointers) and fills the per-view outputs.
-int run_view_batch(VbScratch* s, hipStream_t stream, ViewBatch B, const tmi_ba_options* O, int Nc,
-                   const std::vector<int4>& cam, const std::vector<int>& chain_ptr, const std::vector<int>& chain_views,
-                   int8_t* view_termination, int32_t* view_iterations, double* view_initial_cost,
-                   double* view_final_cost, tmi_ba_view_batch_summary* sum) {
+// Launches the chains on s->stream (B holds the parameter / observation pointers) and fills the per-view outputs.
+int run_view_batch(OneShot* s, ViewBatch B, const tmi_ba_options* O, int Nc, const std::vector<int4>& cam,
+                   const std::vector<int>& chain_ptr, const std::vector<int>& chain_views, const ItemArrays& out,
+                   tmi_ba_view_batch_summary* sum) {
   const int n_chains = (int)chain_ptr.size() - 1;
   int* d_cptr;
   int* d_cviews;
-  TMI_HIP(s->upload(&d_cptr, chain_ptr.data(), chain_ptr.size(), stream));
-  TMI_HIP(s->upload(&d_cviews, chain_views.data(), chain_views.size(), stream));
-  TMI_HIP(s->alloc(&B.term, (size_t)Nc));
-  TMI_HIP(s->alloc(&B.iters, (size_t)Nc));
-  TMI_HIP(s->alloc(&B.c0, (size_t)Nc));
-  TMI_HIP(s->alloc(&B.c1, (size_t)Nc));
-  TMI_HIP(hipMemsetAsync(B.term, 0xff, std::max(Nc, 1), stream));  // -1: not adjusted
-  TMI_HIP(hipMemsetAsync(B.iters, 0, std::max(Nc, 1) * sizeof(int), stream));
-  TMI_HIP(hipMemsetAsync(B.c0, 0, std::max(Nc, 1) * sizeof(double), stream));
-  TMI_HIP(hipMemsetAsync(B.c1, 0, std::max(Nc, 1) * sizeof(double), stream));
+  TMI_HIP(s->upload(&d_cptr, chain_ptr.data(), chain_ptr.size()));
+  TMI_HIP(s->upload(&d_cviews, chain_views.data(), chain_views.size()));
+  int rc = s->alloc_outputs(&B.out, (size_t)Nc);  // -1: not adjusted
+  if (rc) return rc;
   B.chain_ptr = d_cptr;
   B.chain_views = d_cviews;
   bool pinhole = true;
   for (const int c : chain_views) pinhole = pinhole && cam[c].x == TMI_BA_PINHOLE;
-  const ViewLmArgs A = view_lm_args(O);
-  hipEvent_t ea, eb;
-  TMI_HIP(hipEventCreate(&ea));
-  TMI_HIP(hipEventCreate(&eb));
-  hipEventRecord(ea, stream);
-  if (n_chains > 0) {
+  const SmallLmArgs A = small_lm_args(O);
+  rc = run_small_lm(s, s->stream, B.out, (size_t)Nc, nullptr, [&] {
+    if (n_chains == 0) return;
     if (pinhole)
-      hipLaunchKernelGGL((view_lm_kernel<0>), dim3(n_chains), dim3(256), 0, stream, B, A);
+      hipLaunchKernelGGL((view_lm_kernel<0>), dim3(n_chains), dim3(256), 0, s->stream, B, A);
     else
-      hipLaunchKernelGGL(view_lm_kernel<-1>, dim3(n_chains), dim3(256), 0, stream, B, A);
-  }
-  hipEventRecord(eb, stream);
-  const hipError_t le = hipGetLastError();
-  std::vector<signed char> term((size_t)Nc);
-  std::vector<int> iters((size_t)Nc);
-  std::vector<double> c0((size_t)Nc), c1((size_t)Nc);
-  if (Nc) {
-    TMI_HIP(hipMemcpyAsync(term.data(), B.term, (size_t)Nc, hipMemcpyDeviceToHost, stream));
-    TMI_HIP(hipMemcpyAsync(iters.data(), B.iters, (size_t)Nc * sizeof(int), hipMemcpyDeviceToHost, stream));
-    TMI_HIP(hipMemcpyAsync(c0.data(), B.c0, (size_t)Nc * sizeof(double), hipMemcpyDeviceToHost, stream));
-    TMI_HIP(hipMemcpyAsync(c1.data(), B.c1, (size_t)Nc * sizeof(double), hipMemcpyDeviceToHost, stream));
-  }
-  const hipError_t se = hipStreamSynchronize(stream);
-  float ms = 0.f;
-  hipEventElapsedTime(&ms, ea, eb);
-  hipEventDestroy(ea);
-  hipEventDestroy(eb);
-  TMI_HIP(le);
-  TMI_HIP(se);
-  for (int c = 0; c < Nc; ++c) {
-    if (term[c] >= 0) {
-      sum->num_views++;
-      if (term[c] == 0 || term[c] == 1) sum->num_success++;
-      sum->total_iterations += iters[c];
-    }
-    if (view_termination) view_termination[c] = (int8_t)term[c];
-    if (view_iterations) view_iterations[c] = iters[c];
-    if (view_initial_cost) view_initial_cost[c] = c0[c];
-    if (view_final_cost) view_final_cost[c] = c1[c];
-  }
+      hipLaunchKernelGGL(view_lm_kernel<-1>, dim3(n_chains), dim3(256), 0, s->stream, B, A);
+  }, out, sum, &sum->num_views);
   sum->num_chains = n_chains;
-  sum->kernel_seconds = 1e-3 * ms;
-  return TMI_BA_OK;
+  return rc;
 }
 }  // namespace
 extern "C" {
@@ -4248,7 +4216,7 @@ int32_t tmi_ba_solver_adjust_views(tmi_ba_solver* s, const tmi_ba_options* O, co
     if ((rc = dev_alloc(s, &s->d_view_keys, (size_t)std::max<int64_t>(st.No_pad, 1)))) return rc;
     if ((rc = dev_alloc(s, &s->d_view_slot_pt, (size_t)std::max<int64_t>(st.No_pad, 1)))) return rc;
     if (st.No_pad > 0) {
-      VbScratch tmp_mem;
+      OneShot tmp_mem(stream);
       unsigned long long* keys_in = nullptr;
       TMI_HIP(tmp_mem.alloc(&keys_in, (size_t)st.No_pad));
       hipLaunchKernelGGL(view_keys_kernel, dim3(s->nblocks_slices), dim3(256), 0, stream, s->v, keys_in, s->d_view_slot_pt);
@@ -4289,9 +4257,9 @@ int32_t tmi_ba_solver_adjust_views(tmi_ba_solver* s, const tmi_ba_options* O, co
   B.slot_pt = s->d_view_slot_pt;
   B.obs_xy = s->v.obs_xy;
   B.pts = s->v.pts;
-  VbScratch scratch;
-  rc = run_view_batch(&scratch, stream, B, O, Nc, s->view_cam_h, chain_ptr, chain_views, view_termination,
-                      view_iterations, view_initial_cost, view_final_cost, sum);
+  OneShot scratch(stream);
+  rc = run_view_batch(&scratch, B, O, Nc, s->view_cam_h, chain_ptr, chain_views,
+                      {view_termination, view_iterations, view_initial_cost, view_final_cost}, sum);
   if (rc) {
     g_last_error = s->error = scratch.error;
     return rc;
@@ -4311,8 +4279,8 @@ int32_t tmi_ba_adjust_views(tmi_ba_problem* P, const tmi_ba_options* O, const ui
   if (!P || !O || !sum) return TMI_BA_ERR_INVALID_ARGUMENT;
   memset(sum, 0, sizeof(*sum));
   const double t0 = now_s();
-  VbScratch sc;
-  VbScratch* s = &sc;  // (TMI_HIP reports into s->error)
+  OneShot sc;
+  OneShot* s = &sc;  // (TMI_HIP reports into s->error)
   auto bad = [&](const char* why) {
     g_last_error = why;
     return TMI_BA_ERR_INVALID_ARGUMENT;
@@ -4376,13 +4344,12 @@ int32_t tmi_ba_adjust_views(tmi_ba_problem* P, const tmi_ba_options* O, const ui
       xy[2 * o + 1] = P->obs_xy[2 * i + 1];
     }
   }
-  if (O->device >= 0) TMI_HIP(hipSetDevice(O->device));
-  hipStream_t stream;
-  TMI_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-  struct StreamGuard {
-    hipStream_t st;
-    ~StreamGuard() { hipStreamDestroy(st); }
-  } guard{stream};
+  int rc = s->open(O->device);
+  if (rc) {
+    g_last_error = s->error;
+    return rc;
+  }
+  const hipStream_t stream = s->stream;
   ViewBatch B;
   memset(&B, 0, sizeof(B));
   int4* d_cam;
@@ -4390,22 +4357,22 @@ int32_t tmi_ba_adjust_views(tmi_ba_problem* P, const tmi_ba_options* O, const ui
   unsigned long long* d_keys;
   int* d_slot_pt;
   double *d_xy, *d_pts;
-  TMI_HIP(s->upload(&B.ext, P->extrinsics, (size_t)6 * Nc, stream));
-  TMI_HIP(s->upload(&B.intr, P->intrinsics, (size_t)n_intr, stream));
-  TMI_HIP(s->upload(&d_cam, cam.data(), cam.size(), stream));
-  TMI_HIP(s->upload(&d_vptr, vptr.data(), vptr.size(), stream));
-  TMI_HIP(s->upload(&d_keys, keys.data(), keys.size(), stream));
-  TMI_HIP(s->upload(&d_slot_pt, slot_pt.data(), slot_pt.size(), stream));
-  TMI_HIP(s->upload(&d_xy, xy.data(), xy.size(), stream));
-  TMI_HIP(s->upload(&d_pts, M ? P->points : nullptr, M ? (size_t)4 * Np : 0, stream));
+  TMI_HIP(s->upload(&B.ext, P->extrinsics, (size_t)6 * Nc));
+  TMI_HIP(s->upload(&B.intr, P->intrinsics, (size_t)n_intr));
+  TMI_HIP(s->upload(&d_cam, cam.data(), cam.size()));
+  TMI_HIP(s->upload(&d_vptr, vptr.data(), vptr.size()));
+  TMI_HIP(s->upload(&d_keys, keys.data(), keys.size()));
+  TMI_HIP(s->upload(&d_slot_pt, slot_pt.data(), slot_pt.size()));
+  TMI_HIP(s->upload(&d_xy, xy.data(), xy.size()));
+  TMI_HIP(s->upload(&d_pts, M ? P->points : nullptr, M ? (size_t)4 * Np : 0));
   B.cam = d_cam;
   B.vptr = d_vptr;
   B.keys = d_keys;
   B.slot_pt = d_slot_pt;
   B.obs_xy = d_xy;
   B.pts = d_pts;
-  int rc = run_view_batch(s, stream, B, O, Nc, cam, chain_ptr, chain_views, view_termination, view_iterations,
-                          view_initial_cost, view_final_cost, sum);
+  rc = run_view_batch(s, B, O, Nc, cam, chain_ptr, chain_views,
+                      {view_termination, view_iterations, view_initial_cost, view_final_cost}, sum);
   if (rc == TMI_BA_OK && Nc) {
     // the kernel wrote back exactly the usable views' cameras and their groups' free intrinsics
     TMI_HIP(hipMemcpyAsync(P->extrinsics, B.ext, (size_t)6 * Nc * sizeof(double), hipMemcpyDeviceToHost, stream));
@@ -4452,11 +4419,11 @@ int32_t tmi_ba_solver_estimate_tracks(tmi_ba_solver* s, const tmi_ba_track_estim
     const int p = st.pt_orig[lp];
     if (p >= 0 && (!track_mask || track_mask[p])) attempt_h[lp] = 1;
   }
-  VbScratch scratch;
+  OneShot scratch(stream);
   unsigned char* d_attempt = nullptr;
   signed char* d_status = nullptr;
   double* d_ray = nullptr;
-  TMI_HIP(scratch.upload(&d_attempt, attempt_h.data(), npad, stream));
+  TMI_HIP(scratch.upload(&d_attempt, attempt_h.data(), npad));
   TMI_HIP(scratch.alloc(&d_status, npad));
   TMI_HIP(scratch.alloc(&d_ray, (size_t)3 * (size_t)std::max<int64_t>(st.No_pad, 1)));
   const double cos_min = std::cos(eo->min_triangulation_angle_degrees * (M_PI / 180.0));
@@ -4473,34 +4440,8 @@ int32_t tmi_ba_solver_estimate_tracks(tmi_ba_solver* s, const tmi_ba_track_estim
     if (eo->bundle_adjustment) {
       // BundleAdjustTrack with the caller's options (DENSE_QR and no inner iterations change nothing for a
       // single track) on the tracks the triangulation accepted; the others are skipped like constant tracks
-      TrackLmArgs A;
-      A.loss_type = O->loss_function_type;
-      A.loss_width = O->robust_loss_width;
-      A.jacobi_scaling = O->jacobi_scaling;
-      A.max_num_iterations = O->max_num_iterations;
-      A.max_num_consecutive_invalid_steps = O->max_num_consecutive_invalid_steps;
-      A.function_tolerance = O->function_tolerance;
-      A.gradient_tolerance = O->gradient_tolerance;
-      A.parameter_tolerance = O->parameter_tolerance;
-      A.initial_radius = O->initial_trust_region_radius;
-      A.max_radius = O->max_trust_region_radius;
-      A.min_radius = O->min_trust_region_radius;
-      A.min_relative_decrease = O->min_relative_decrease;
-      A.lm_lo = O->min_lm_diagonal;
-      A.lm_hi = O->max_lm_diagonal;
       prepare_cameras(s, s->v.ext, s->v.intr, s->v.prep);
-      if (s->DP == 3 && s->v.uniform_pinhole_default)
-        hipLaunchKernelGGL((track_lm_kernel<3, 0>), dim3(s->nblocks_tracks), dim3(256), 0, stream, s->v, s->v.prep, A,
-                           s->d_trk_term, s->d_trk_iter, s->d_trk_c0, s->d_trk_c1, d_status);
-      else if (s->DP == 3)
-        hipLaunchKernelGGL(track_lm_kernel<3>, dim3(s->nblocks_tracks), dim3(256), 0, stream, s->v, s->v.prep, A,
-                           s->d_trk_term, s->d_trk_iter, s->d_trk_c0, s->d_trk_c1, d_status);
-      else if (s->v.uniform_pinhole_default)
-        hipLaunchKernelGGL((track_lm_kernel<4, 0>), dim3(s->nblocks_tracks), dim3(256), 0, stream, s->v, s->v.prep, A,
-                           s->d_trk_term, s->d_trk_iter, s->d_trk_c0, s->d_trk_c1, d_status);
-      else
-        hipLaunchKernelGGL(track_lm_kernel<4>, dim3(s->nblocks_tracks), dim3(256), 0, stream, s->v, s->v.prep, A,
-                           s->d_trk_term, s->d_trk_iter, s->d_trk_c0, s->d_trk_c1, d_status);
+      launch_track_lm(s, s->v, s->v.prep, small_lm_args(O), d_status);
       term = s->d_trk_term;
     }
     hipLaunchKernelGGL(track_accept_kernel, dim3(s->nblocks_tracks), dim3(256), 0, stream, s->v, max_err * max_err,
@@ -4573,16 +4514,9 @@ int32_t tmi_ba_estimate_tracks(tmi_ba_problem* P, const tmi_ba_track_estimator_o
     for (int p = 0; p < P->num_points; ++p)
       mask[p] = (uint8_t)((!track_mask || track_mask[p]) && !P->point_constant[p]);
   }
-  tmi_ba_solver* s = new tmi_ba_solver();
-  int rc = create_impl(s, P, O, 0, 1, /*light=*/true);
-  if (rc == TMI_BA_OK) {
-    rc = tmi_ba_solver_estimate_tracks(s, eo, O, mask.empty() ? track_mask : mask.data(), track_status, sum);
-    if (rc == TMI_BA_OK) rc = tmi_ba_solver_download(s, P);  // cameras are constant here: only points changed
-    else g_last_error = s->error;
-  } else {
-    g_last_error = s->error;
-  }
-  tmi_ba_solver_destroy(s);
+  const int rc = with_light_handle(P, O, P, [&](tmi_ba_solver* s) {
+    return tmi_ba_solver_estimate_tracks(s, eo, O, mask.empty() ? track_mask : mask.data(), track_status, sum);
+  });
   sum->seconds = now_s() - t0;
   return rc;
 }
@@ -4609,109 +4543,48 @@ int32_t tmi_ba_adjust_two_views_angular(tmi_ba_two_view_angular_batch* Bh, int32
   }
   if (device >= ndev) return TMI_BA_ERR_INVALID_ARGUMENT;
   if (P == 0) return TMI_BA_OK;
-  tmi_ba_solver* s = new tmi_ba_solver();  // holder of the allocations (freed by tmi_ba_solver_destroy)
-  s->light = true;
-  auto done = [&](int rc) {
-    if (rc != TMI_BA_OK) g_last_error = s->error;
-    tmi_ba_solver_destroy(s);
-    sum->seconds = now_s() - t0;
-    return rc;
-  };
-  if (device >= 0) s->device = device;
-  else if (hipGetDevice(&s->device) != hipSuccess) return done(TMI_BA_ERR_DEVICE);
-  if (hipSetDevice(s->device) != hipSuccess) return done(TMI_BA_ERR_DEVICE);
-  if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) return done(TMI_BA_ERR_DEVICE);
-  int rc;
-  auto up = [&](double** dst, const double* src, size_t n) -> int {
-    double* d = nullptr;
-    int r = dev_alloc(s, &d, n);
-    if (r) return r;
-    if (n && hipMemcpyAsync(d, src, n * sizeof(double), hipMemcpyHostToDevice, s->stream) != hipSuccess) {
-      s->error = "hipMemcpyAsync failed";
-      return TMI_BA_ERR_DEVICE;
-    }
-    *dst = d;
-    return TMI_BA_OK;
-  };
-  std::vector<long long> cptr(Bh->correspondence_ptr, Bh->correspondence_ptr + P + 1);
-  TwoViewAngularBatch B;
-  memset(&B, 0, sizeof(B));
-  B.num_pairs = P;
-  double *d_rot, *d_pos, *d_f1, *d_f2;
-  long long* d_cptr = nullptr;
-  if ((rc = up(&d_rot, Bh->rotation2, (size_t)3 * P))) return done(rc);
-  if ((rc = up(&d_pos, Bh->position2, (size_t)3 * P))) return done(rc);
-  if ((rc = up(&d_f1, Bh->features1, (size_t)2 * N))) return done(rc);
-  if ((rc = up(&d_f2, Bh->features2, (size_t)2 * N))) return done(rc);
-  if ((rc = dev_alloc(s, &d_cptr, (size_t)P + 1))) return done(rc);
-  if (hipMemcpyAsync(d_cptr, cptr.data(), ((size_t)P + 1) * sizeof(long long), hipMemcpyHostToDevice, s->stream) != hipSuccess)
-    return done(TMI_BA_ERR_DEVICE);
-  B.rot2 = d_rot; B.pos2 = d_pos; B.corr_ptr = d_cptr; B.feat1 = d_f1; B.feat2 = d_f2;
-  signed char* d_term;
-  int* d_iter;
-  double *d_c0, *d_cf;
-  if ((rc = dev_alloc(s, &d_term, (size_t)P))) return done(rc);
-  if ((rc = dev_alloc(s, &d_iter, (size_t)P))) return done(rc);
-  if ((rc = dev_alloc(s, &d_c0, (size_t)P))) return done(rc);
-  if ((rc = dev_alloc(s, &d_cf, (size_t)P))) return done(rc);
-  TwoViewArgs A;
-  memset(&A, 0, sizeof(A));
-  A.max_num_iterations = max_num_iterations;
-  A.jacobi_scaling = 1;
-  // Ceres Solver::Options defaults (SetSolverOptions, bundle_adjust_two_views.cc:57-69, overrides none of these)
-  A.function_tolerance = 1e-6;
-  A.gradient_tolerance = 1e-10;
-  A.parameter_tolerance = 1e-8;
-  A.initial_radius = 1e4;
-  A.max_radius = 1e16;
-  A.min_radius = 1e-32;
-  A.min_relative_decrease = 1e-3;
-  A.lm_lo = 1e-6;
-  A.lm_hi = 1e32;
-  A.max_num_consecutive_invalid_steps = 5;
-  hipEvent_t ea, eb;
-  if (hipEventCreate(&ea) != hipSuccess || hipEventCreate(&eb) != hipSuccess) return done(TMI_BA_ERR_DEVICE);
-  hipEventRecord(ea, s->stream);
-  hipLaunchKernelGGL(two_view_angular_kernel, dim3((P + 3) / 4), dim3(256), 0, s->stream, B, A, d_term, d_iter, d_c0, d_cf);
-  hipEventRecord(eb, s->stream);
-  std::vector<signed char> term((size_t)P);
-  std::vector<int> iters((size_t)P);
-  std::vector<double> c0((size_t)P), cf((size_t)P), rot((size_t)3 * P), pos((size_t)3 * P);
-  bool okc = hipMemcpyAsync(term.data(), d_term, (size_t)P, hipMemcpyDeviceToHost, s->stream) == hipSuccess;
-  okc = okc && hipMemcpyAsync(iters.data(), d_iter, (size_t)P * sizeof(int), hipMemcpyDeviceToHost, s->stream) == hipSuccess;
-  okc = okc && hipMemcpyAsync(c0.data(), d_c0, (size_t)P * 8, hipMemcpyDeviceToHost, s->stream) == hipSuccess;
-  okc = okc && hipMemcpyAsync(cf.data(), d_cf, (size_t)P * 8, hipMemcpyDeviceToHost, s->stream) == hipSuccess;
-  okc = okc && hipMemcpyAsync(rot.data(), d_rot, rot.size() * 8, hipMemcpyDeviceToHost, s->stream) == hipSuccess;
-  okc = okc && hipMemcpyAsync(pos.data(), d_pos, pos.size() * 8, hipMemcpyDeviceToHost, s->stream) == hipSuccess;
-  const hipError_t se = hipStreamSynchronize(s->stream);
-  float ms = 0.f;
-  hipEventElapsedTime(&ms, ea, eb);
-  hipEventDestroy(ea);
-  hipEventDestroy(eb);
-  if (!okc || se != hipSuccess) {
-    s->error = std::string("angular two-view batch failed on the device: ") + hipGetErrorString(se);
-    return done(TMI_BA_ERR_DEVICE);
-  }
-  for (int p = 0; p < P; ++p) {
-    const int t = term[p];
-    if (t >= 0) {
-      sum->num_tracks++;
-      if (t == 0 || t == 1) sum->num_success++;
-      sum->total_iterations += iters[p];
-    }
-    if (t == 0 || t == 1) {  // termination != FAILURE: write back
+  OneShot sc;
+  OneShot* s = &sc;  // (TMI_HIP reports into s->error)
+  const int rc = [&]() -> int {
+    int rc = s->open(device);
+    if (rc) return rc;
+    TwoViewAngularBatch B;
+    memset(&B, 0, sizeof(B));
+    B.num_pairs = P;
+    double *d_f1, *d_f2;
+    long long* d_cptr;
+    TMI_HIP(s->upload(&B.rot2, Bh->rotation2, (size_t)3 * P));
+    TMI_HIP(s->upload(&B.pos2, Bh->position2, (size_t)3 * P));
+    TMI_HIP(s->upload(&d_f1, Bh->features1, (size_t)2 * N));
+    TMI_HIP(s->upload(&d_f2, Bh->features2, (size_t)2 * N));
+    TMI_HIP(s->upload(&d_cptr, (const long long*)Bh->correspondence_ptr, (size_t)P + 1));
+    B.feat1 = d_f1;
+    B.feat2 = d_f2;
+    B.corr_ptr = d_cptr;
+    SmallLmOut d;
+    if ((rc = s->alloc_outputs(&d, (size_t)P))) return rc;
+    const SmallLmArgs A = ceres_default_lm_args(max_num_iterations, TMI_BA_LOSS_TRIVIAL, 0.0);
+    std::vector<signed char> term;
+    rc = run_small_lm(s, s->stream, d, (size_t)P, nullptr, [&] {
+      hipLaunchKernelGGL(two_view_angular_kernel, dim3((P + 3) / 4), dim3(256), 0, s->stream, B, A, d);
+    }, ItemArrays{pair_termination, pair_iterations, pair_initial_cost, pair_final_cost}, sum, &sum->num_tracks, &term);
+    if (rc) return rc;
+    std::vector<double> rot((size_t)3 * P), pos((size_t)3 * P);
+    TMI_HIP(hipMemcpyAsync(rot.data(), B.rot2, rot.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    TMI_HIP(hipMemcpyAsync(pos.data(), B.pos2, pos.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    TMI_HIP(hipStreamSynchronize(s->stream));
+    for (int p = 0; p < P; ++p) {
+      if (term[p] != 0 && term[p] != 1) continue;  // termination != FAILURE: write back
       for (int a = 0; a < 3; ++a) {
         Bh->rotation2[(size_t)3 * p + a] = rot[(size_t)3 * p + a];
         Bh->position2[(size_t)3 * p + a] = pos[(size_t)3 * p + a];
       }
     }
-    if (pair_termination) pair_termination[p] = (int8_t)t;
-    if (pair_iterations) pair_iterations[p] = iters[p];
-    if (pair_initial_cost) pair_initial_cost[p] = c0[p];
-    if (pair_final_cost) pair_final_cost[p] = cf[p];
-  }
-  sum->kernel_seconds = ms * 1e-3;
-  return done(TMI_BA_OK);
+    return TMI_BA_OK;
+  }();
+  if (rc) g_last_error = s->error;
+  sum->seconds = now_s() - t0;
+  return rc;
 }
 
 // SelectGoodTracksForBundleAdjustment (select_good_tracks_for_bundle_adjustment.cc:251-327):
@@ -4931,132 +4804,84 @@ int32_t tmi_ba_adjust_two_views(tmi_ba_two_view_batch* Bh, int32_t point_dof, in
   }
   if (device >= ndev) return TMI_BA_ERR_INVALID_ARGUMENT;
   if (P == 0) return TMI_BA_OK;
-  // a throw-away holder for the allocations (freed by tmi_ba_solver_destroy)
-  tmi_ba_solver* s = new tmi_ba_solver();
-  s->light = true;
-  auto done = [&](int rc) {
-    if (rc != TMI_BA_OK) g_last_error = s->error;
-    tmi_ba_solver_destroy(s);
-    sum->seconds = now_s() - t0;
-    return rc;
-  };
-  if (device >= 0) s->device = device;
-  else if (hipGetDevice(&s->device) != hipSuccess) return done(TMI_BA_ERR_DEVICE);
-  if (hipSetDevice(s->device) != hipSuccess) return done(TMI_BA_ERR_DEVICE);
-  if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) return done(TMI_BA_ERR_DEVICE);
-  int rc;
-  TwoViewBatch B;
-  memset(&B, 0, sizeof(B));
-  B.num_pairs = P;
-  auto up = [&](auto** dst, const auto* src, size_t n) -> int {
-    typedef typename std::remove_const<typename std::remove_pointer<decltype(src)>::type>::type T;
-    T* d = nullptr;
-    int r = dev_alloc(s, &d, n);
-    if (r) return r;
-    if (n && hipMemcpyAsync(d, src, n * sizeof(T), hipMemcpyHostToDevice, s->stream) != hipSuccess) {
-      s->error = "hipMemcpyAsync failed";
-      return TMI_BA_ERR_DEVICE;
-    }
-    *dst = d;
-    return TMI_BA_OK;
-  };
-  std::vector<unsigned char> c1((size_t)P, 1), c2((size_t)P, 1);
-  if (Bh->constant_intrinsics1) c1.assign(Bh->constant_intrinsics1, Bh->constant_intrinsics1 + P);
-  if (Bh->constant_intrinsics2) c2.assign(Bh->constant_intrinsics2, Bh->constant_intrinsics2 + P);
-  std::vector<long long> cptr(Bh->correspondence_ptr, Bh->correspondence_ptr + P + 1);
-  double *d_e1, *d_e2, *d_k1, *d_k2, *d_f1, *d_f2, *d_pts;
-  int *d_m1, *d_m2;
-  unsigned char *d_c1, *d_c2;
-  long long* d_cptr;
-  const size_t Nn = (size_t)std::max<int64_t>(N, 1);
-  if ((rc = up(&d_e1, Bh->extrinsics1, (size_t)6 * P))) return done(rc);
-  if ((rc = up(&d_e2, (const double*)Bh->extrinsics2, (size_t)6 * P))) return done(rc);
-  if ((rc = up(&d_m1, Bh->model1, (size_t)P))) return done(rc);
-  if ((rc = up(&d_m2, Bh->model2, (size_t)P))) return done(rc);
-  if ((rc = up(&d_k1, (const double*)Bh->intrinsics1, (size_t)10 * P))) return done(rc);
-  if ((rc = up(&d_k2, (const double*)Bh->intrinsics2, (size_t)10 * P))) return done(rc);
-  if ((rc = up(&d_c1, (const unsigned char*)c1.data(), (size_t)P))) return done(rc);
-  if ((rc = up(&d_c2, (const unsigned char*)c2.data(), (size_t)P))) return done(rc);
-  if ((rc = up(&d_cptr, (const long long*)cptr.data(), (size_t)P + 1))) return done(rc);
-  if ((rc = up(&d_f1, Bh->features1, (size_t)2 * N))) return done(rc);
-  if ((rc = up(&d_f2, Bh->features2, (size_t)2 * N))) return done(rc);
-  if ((rc = up(&d_pts, (const double*)Bh->points, (size_t)4 * N))) return done(rc);
-  B.ext1 = d_e1; B.ext2 = d_e2; B.model1 = d_m1; B.model2 = d_m2; B.intr1 = d_k1; B.intr2 = d_k2;
-  B.const1 = d_c1; B.const2 = d_c2; B.corr_ptr = d_cptr; B.feat1 = d_f1; B.feat2 = d_f2; B.points = d_pts;
-  if ((rc = dev_alloc(s, &B.points_c, 4 * Nn))) return done(rc);
-  if ((rc = dev_alloc(s, &B.scale_p, 4 * Nn))) return done(rc);
-  signed char* d_term;
-  int* d_iter;
-  double *d_c0, *d_cf;
-  if ((rc = dev_alloc(s, &d_term, (size_t)P))) return done(rc);
-  if ((rc = dev_alloc(s, &d_iter, (size_t)P))) return done(rc);
-  if ((rc = dev_alloc(s, &d_c0, (size_t)P))) return done(rc);
-  if ((rc = dev_alloc(s, &d_cf, (size_t)P))) return done(rc);
-  TwoViewArgs A;
-  A.point_dof = point_dof;
-  A.max_num_iterations = max_num_iterations;
-  A.jacobi_scaling = 1;
-  // Ceres Solver::Options defaults: bundle_adjust_two_views.cc:58-68 overrides none of these
-  A.function_tolerance = 1e-6;
-  A.gradient_tolerance = 1e-10;
-  A.parameter_tolerance = 1e-8;
-  A.initial_radius = 1e4;
-  A.max_radius = 1e16;
-  A.min_radius = 1e-32;
-  A.min_relative_decrease = 1e-3;
-  A.lm_lo = 1e-6;
-  A.lm_hi = 1e32;
-  A.max_num_consecutive_invalid_steps = 5;
-  hipEvent_t ea, eb;
-  if (hipEventCreate(&ea) != hipSuccess || hipEventCreate(&eb) != hipSuccess) return done(TMI_BA_ERR_DEVICE);
-  hipEventRecord(ea, s->stream);
-  if (point_dof == 3)
-    hipLaunchKernelGGL(two_view_lm_kernel<3>, dim3((P + 3) / 4), dim3(256), 0, s->stream, B, A, d_term, d_iter, d_c0, d_cf);
-  else
-    hipLaunchKernelGGL(two_view_lm_kernel<4>, dim3((P + 3) / 4), dim3(256), 0, s->stream, B, A, d_term, d_iter, d_c0, d_cf);
-  hipEventRecord(eb, s->stream);
-  std::vector<signed char> term((size_t)P);
-  std::vector<int> iters((size_t)P);
-  std::vector<double> c0((size_t)P), cf((size_t)P), e2((size_t)6 * P), k1((size_t)10 * P), k2((size_t)10 * P),
-      pts((size_t)4 * N);
-  bool okc = hipMemcpyAsync(term.data(), d_term, (size_t)P, hipMemcpyDeviceToHost, s->stream) == hipSuccess;
-  okc = okc && hipMemcpyAsync(iters.data(), d_iter, (size_t)P * sizeof(int), hipMemcpyDeviceToHost, s->stream) == hipSuccess;
-  okc = okc && hipMemcpyAsync(c0.data(), d_c0, (size_t)P * 8, hipMemcpyDeviceToHost, s->stream) == hipSuccess;
-  okc = okc && hipMemcpyAsync(cf.data(), d_cf, (size_t)P * 8, hipMemcpyDeviceToHost, s->stream) == hipSuccess;
-  okc = okc && hipMemcpyAsync(e2.data(), d_e2, e2.size() * 8, hipMemcpyDeviceToHost, s->stream) == hipSuccess;
-  okc = okc && hipMemcpyAsync(k1.data(), d_k1, k1.size() * 8, hipMemcpyDeviceToHost, s->stream) == hipSuccess;
-  okc = okc && hipMemcpyAsync(k2.data(), d_k2, k2.size() * 8, hipMemcpyDeviceToHost, s->stream) == hipSuccess;
-  if (N) okc = okc && hipMemcpyAsync(pts.data(), d_pts, pts.size() * 8, hipMemcpyDeviceToHost, s->stream) == hipSuccess;
-  const hipError_t se = hipStreamSynchronize(s->stream);
-  float ms = 0.f;
-  hipEventElapsedTime(&ms, ea, eb);
-  hipEventDestroy(ea);
-  hipEventDestroy(eb);
-  if (!okc || se != hipSuccess) {
-    s->error = std::string("two-view batch failed on the device: ") + hipGetErrorString(se);
-    return done(TMI_BA_ERR_DEVICE);
-  }
-  for (int p = 0; p < P; ++p) {
-    const int t = term[p];
-    if (t >= 0) {
-      sum->num_tracks++;
-      if (t == 0 || t == 1) sum->num_success++;
-      sum->total_iterations += iters[p];
-    }
-    if (t == 0 || t == 1) {  // IsSolutionUsable: write back
+  OneShot sc;
+  OneShot* s = &sc;  // (TMI_HIP reports into s->error)
+  const int rc = [&]() -> int {
+    int rc = s->open(device);
+    if (rc) return rc;
+    std::vector<unsigned char> c1((size_t)P, 1), c2((size_t)P, 1);
+    if (Bh->constant_intrinsics1) c1.assign(Bh->constant_intrinsics1, Bh->constant_intrinsics1 + P);
+    if (Bh->constant_intrinsics2) c2.assign(Bh->constant_intrinsics2, Bh->constant_intrinsics2 + P);
+    TwoViewBatch B;
+    memset(&B, 0, sizeof(B));
+    B.num_pairs = P;
+    double *d_e1, *d_f1, *d_f2;
+    int *d_m1, *d_m2;
+    unsigned char *d_c1, *d_c2;
+    long long* d_cptr;
+    const size_t Nn = (size_t)std::max<int64_t>(N, 1);
+    TMI_HIP(s->upload(&d_e1, Bh->extrinsics1, (size_t)6 * P));
+    TMI_HIP(s->upload(&B.ext2, (const double*)Bh->extrinsics2, (size_t)6 * P));
+    TMI_HIP(s->upload(&d_m1, Bh->model1, (size_t)P));
+    TMI_HIP(s->upload(&d_m2, Bh->model2, (size_t)P));
+    TMI_HIP(s->upload(&B.intr1, (const double*)Bh->intrinsics1, (size_t)10 * P));
+    TMI_HIP(s->upload(&B.intr2, (const double*)Bh->intrinsics2, (size_t)10 * P));
+    TMI_HIP(s->upload(&d_c1, (const unsigned char*)c1.data(), (size_t)P));
+    TMI_HIP(s->upload(&d_c2, (const unsigned char*)c2.data(), (size_t)P));
+    TMI_HIP(s->upload(&d_cptr, (const long long*)Bh->correspondence_ptr, (size_t)P + 1));
+    TMI_HIP(s->upload(&d_f1, Bh->features1, (size_t)2 * N));
+    TMI_HIP(s->upload(&d_f2, Bh->features2, (size_t)2 * N));
+    TMI_HIP(s->upload(&B.points, (const double*)Bh->points, (size_t)4 * N));
+    TMI_HIP(s->alloc(&B.points_c, 4 * Nn));
+    TMI_HIP(s->alloc(&B.scale_p, 4 * Nn));
+    B.ext1 = d_e1; B.model1 = d_m1; B.model2 = d_m2; B.const1 = d_c1; B.const2 = d_c2; B.corr_ptr = d_cptr;
+    B.feat1 = d_f1; B.feat2 = d_f2;
+    SmallLmOut d;
+    if ((rc = s->alloc_outputs(&d, (size_t)P))) return rc;
+    const SmallLmArgs L = ceres_default_lm_args(max_num_iterations, TMI_BA_LOSS_TRIVIAL, 0.0);
+    TwoViewArgs A;  // (two_view_lm_kernel keeps its own argument layout: two_view_kernels.h)
+    A.point_dof = point_dof;
+    A.max_num_iterations = L.max_num_iterations;
+    A.jacobi_scaling = L.jacobi_scaling;
+    A.function_tolerance = L.function_tolerance;
+    A.gradient_tolerance = L.gradient_tolerance;
+    A.parameter_tolerance = L.parameter_tolerance;
+    A.initial_radius = L.initial_radius;
+    A.max_radius = L.max_radius;
+    A.min_radius = L.min_radius;
+    A.min_relative_decrease = L.min_relative_decrease;
+    A.lm_lo = L.lm_lo;
+    A.lm_hi = L.lm_hi;
+    A.max_num_consecutive_invalid_steps = L.max_num_consecutive_invalid_steps;
+    std::vector<signed char> term;
+    rc = run_small_lm(s, s->stream, d, (size_t)P, nullptr, [&] {
+      if (point_dof == 3)
+        hipLaunchKernelGGL(two_view_lm_kernel<3>, dim3((P + 3) / 4), dim3(256), 0, s->stream, B, A, d.term, d.iters,
+                           d.c0, d.c1);
+      else
+        hipLaunchKernelGGL(two_view_lm_kernel<4>, dim3((P + 3) / 4), dim3(256), 0, s->stream, B, A, d.term, d.iters,
+                           d.c0, d.c1);
+    }, ItemArrays{pair_termination, pair_iterations, pair_initial_cost, pair_final_cost}, sum, &sum->num_tracks, &term);
+    if (rc) return rc;
+    std::vector<double> e2((size_t)6 * P), k1((size_t)10 * P), k2((size_t)10 * P), pts((size_t)4 * N);
+    TMI_HIP(hipMemcpyAsync(e2.data(), B.ext2, e2.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    TMI_HIP(hipMemcpyAsync(k1.data(), B.intr1, k1.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    TMI_HIP(hipMemcpyAsync(k2.data(), B.intr2, k2.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    if (N) TMI_HIP(hipMemcpyAsync(pts.data(), B.points, pts.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    TMI_HIP(hipStreamSynchronize(s->stream));
+    for (int p = 0; p < P; ++p) {
+      if (term[p] != 0 && term[p] != 1) continue;  // IsSolutionUsable: write back
       for (int a = 0; a < 6; ++a) Bh->extrinsics2[(size_t)6 * p + a] = e2[(size_t)6 * p + a];
       Bh->intrinsics1[(size_t)10 * p] = k1[(size_t)10 * p];
       Bh->intrinsics2[(size_t)10 * p] = k2[(size_t)10 * p];
       for (int64_t q = Bh->correspondence_ptr[p]; q < Bh->correspondence_ptr[p + 1]; ++q)
         for (int a = 0; a < 4; ++a) Bh->points[4 * q + a] = pts[4 * q + a];
     }
-    if (pair_termination) pair_termination[p] = (int8_t)t;
-    if (pair_iterations) pair_iterations[p] = iters[p];
-    if (pair_initial_cost) pair_initial_cost[p] = c0[p];
-    if (pair_final_cost) pair_final_cost[p] = cf[p];
-  }
-  sum->kernel_seconds = ms * 1e-3;
-  return done(TMI_BA_OK);
+    return TMI_BA_OK;
+  }();
+  if (rc) g_last_error = s->error;
+  sum->seconds = now_s() - t0;
+  return rc;
 }
 
 int32_t tmi_ba_structure_stats(const tmi_ba_problem* P, int32_t rank, int32_t world, int64_t out[12]) {

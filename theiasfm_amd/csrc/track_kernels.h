@@ -15,6 +15,7 @@
 #include "camera_models.h"
 #include "device_view.h"
 #include "kernels.h"
+#include "small_lm.h"
 
 namespace tmi {
 
@@ -138,18 +139,6 @@ __global__ __launch_bounds__(256) void track_stats_kernel(DeviceView v, const do
 // ------------------------------------------------------------------------------------
 // Batched single-track bundle adjustment.
 // ------------------------------------------------------------------------------------
-struct TrackLmArgs {
-  int loss_type;
-  double loss_width;
-  int jacobi_scaling;
-  int max_num_iterations;
-  int max_num_consecutive_invalid_steps;
-  double function_tolerance, gradient_tolerance, parameter_tolerance;
-  double initial_radius, max_radius, min_radius;
-  double min_relative_decrease;
-  double lm_lo, lm_hi;
-};
-
 // One pass over a track's observations at point X: robustified, column-scaled point
 // Jacobian accumulated into V0 = sum Jp^T Jp (packed upper), g = sum Jp^T r, cost.
 // Returns false if any residual cannot be evaluated.
@@ -260,33 +249,22 @@ __device__ __forceinline__ bool track_cost(const DeviceView& v, const double* __
   return group_sum(bad, tm.wide) == 0.0;
 }
 
-// termination[lp]: 0 CONVERGENCE, 1 NO_CONVERGENCE (iteration limit), 2 FAILURE,
-// 3 residual evaluation failed at the start point, -1 not a problem (padding, constant or
-// unobserved track).  The point is written back unless the code is 2 or 3 (Ceres'
-// IsSolutionUsable, bundle_adjuster.cc:213-216).  The trust-region loop is the one the
-// full solver runs (engine.hip / Ceres 1.14 TrustRegionMinimizer) with an empty camera
-// side: the step is -(V + D)^-1 g on the track's own 2k x DP Jacobian.
+// Termination codes as in SmallLmOut, -1 also for a padding or constant track.  The point is written back unless
+// the code is 2 or 3 (Ceres' IsSolutionUsable, bundle_adjuster.cc:213-216).  The trust-region loop is the one the
+// full solver runs (small_lm.h) with an empty camera side: the step is -(V + D)^-1 g on the track's own
+// 2k x DP Jacobian.
 // skip[lp] != 0 (optional, padded track order): the track is left alone like a constant one
 // (the track estimator adjusts only the tracks its triangulation accepted).
 template <int DP, int UMODEL = -1>
-__global__ __launch_bounds__(256) void track_lm_kernel(DeviceView v, const double* __restrict__ prep, TrackLmArgs A,
-                                                       signed char* __restrict__ termination,
-                                                       int* __restrict__ iterations,
-                                                       double* __restrict__ initial_cost,
-                                                       double* __restrict__ final_cost,
-                                                       const signed char* __restrict__ skip = nullptr) {
+__global__ __launch_bounds__(256) void track_lm_kernel(DeviceView v, const double* __restrict__ prep, SmallLmArgs A,
+                                                       SmallLmOut out, const signed char* __restrict__ skip = nullptr) {
   constexpr int NS = sym_size(DP);
   const TrackMap tm = track_map(v);
   if (!tm.valid) return;
   const int lp = tm.lp;
   const int k = tm.k;
   if (k == 0 || v.pt_const[lp] || (skip && skip[lp])) {  // uniform over the lanes that share a track
-    if (tm.leader) {
-      termination[lp] = -1;
-      iterations[lp] = 0;
-      initial_cost[lp] = 0.0;
-      final_cost[lp] = 0.0;
-    }
+    if (tm.leader) out.write(lp, -1, 0, 0.0, 0.0);
     return;
   }
   double X[4];
@@ -298,13 +276,9 @@ __global__ __launch_bounds__(256) void track_lm_kernel(DeviceView v, const doubl
   double V0[NS], g[DP], cost;
   // iteration zero
   bool ok = track_linearize<DP, UMODEL>(v, prep, tm, X, sp, A.loss_type, A.loss_width, V0, g, &cost);
-  if (tm.leader) initial_cost[lp] = cost;
+  if (tm.leader) out.c0[lp] = cost;
   if (!ok) {
-    if (tm.leader) {
-      termination[lp] = 3;
-      iterations[lp] = 0;
-      final_cost[lp] = cost;
-    }
+    if (tm.leader) out.write(lp, 3, 0, cost, cost);
     return;
   }
   double gmax = 0.0;
@@ -316,21 +290,22 @@ __global__ __launch_bounds__(256) void track_lm_kernel(DeviceView v, const doubl
     track_linearize<DP, UMODEL>(v, prep, tm, X, sp, A.loss_type, A.loss_width, V0, g, &cost);
   }
   double x_norm = sqrt(X[0] * X[0] + X[1] * X[1] + X[2] * X[2] + X[3] * X[3]);
-  double radius = A.initial_radius, decrease_factor = 2.0;
-  int invalid_run = 0, iter = 0, term = 1;
+  TrustRegion tr(A);
+  int iter = 0, term = 1;
   if (gmax <= A.gradient_tolerance) {
     term = 0;
   } else {
     for (;;) {
       if (iter >= A.max_num_iterations) break;
       ++iter;
-      // (V0 + D) y = g by Cholesky
-      double Lm[DP][DP];
+      // (V0 + D) y = g.  The factorisation is small_chol's, damped by / radius, written out here: through the helper
+      // the register allocator gives this kernel no second wavefront per SIMD (the rest of the solve takes it fine).
+      double Lm[DP][DP], y[DP];
       bool step_ok = true;
 #pragma unroll
       for (int j = 0; j < DP; ++j) {
         const double dj = V0[sym_idx(j, j, DP)];
-        double d = dj + fmin(fmax(dj, A.lm_lo), A.lm_hi) / radius;
+        double d = dj + TrustRegion::lm_diag(A, dj) / tr.radius;
 #pragma unroll
         for (int m = 0; m < j; ++m) d -= Lm[j][m] * Lm[j][m];
         if (!(d > 0.0)) {
@@ -348,52 +323,16 @@ __global__ __launch_bounds__(256) void track_lm_kernel(DeviceView v, const doubl
           Lm[i][j] = t * il;
         }
       }
-      double y[DP];
       double mcc = 0.0;
       if (step_ok) {
-        // forward / backward substitution
-        double z[DP];
-#pragma unroll
-        for (int i = 0; i < DP; ++i) {
-          double t = g[i];
-#pragma unroll
-          for (int m = 0; m < i; ++m) t -= Lm[i][m] * z[m];
-          z[i] = t / Lm[i][i];
-        }
-#pragma unroll
-        for (int i = DP - 1; i >= 0; --i) {
-          double t = z[i];
-#pragma unroll
-          for (int m = i + 1; m < DP; ++m) t -= Lm[m][i] * y[m];
-          y[i] = t / Lm[i][i];
-        }
-        // model cost change of the step d = -y:  y^T g - 1/2 y^T V0 y
-        double yg = 0.0, yVy = 0.0;
-#pragma unroll
-        for (int a = 0; a < DP; ++a) {
-          yg += y[a] * g[a];
-          double t = 0.0;
-#pragma unroll
-          for (int b = 0; b < DP; ++b) t += V0[a <= b ? sym_idx(a, b, DP) : sym_idx(b, a, DP)] * y[b];
-          yVy += y[a] * t;
-        }
-        mcc = yg - 0.5 * yVy;
+        small_chol_solve<DP>(Lm, g, y);
+        mcc = model_cost_change<DP>(V0, g, y);
         if (!(mcc > 0.0)) step_ok = false;
       }
-      if (!step_ok) {  // HandleInvalidStep
-        if (++invalid_run >= A.max_num_consecutive_invalid_steps) {
-          term = 2;
-          break;
-        }
-        radius /= decrease_factor;
-        decrease_factor *= 2.0;
-        if (radius < A.min_radius) {
-          term = 0;
-          break;
-        }
+      if (!step_ok) {
+        if (tr.invalid_step(A, &term)) break;
         continue;
       }
-      invalid_run = 0;
       double Xc[4] = {X[0], X[1], X[2], X[3]};
       double step_sq = 0.0;
 #pragma unroll
@@ -404,17 +343,8 @@ __global__ __launch_bounds__(256) void track_lm_kernel(DeviceView v, const doubl
       }
       double cand_cost;
       if (!track_cost<UMODEL>(v, prep, tm, Xc, A.loss_type, A.loss_width, &cand_cost)) cand_cost = 1.7976931348623157e308;
-      if (sqrt(step_sq) <= A.parameter_tolerance * (x_norm + A.parameter_tolerance)) {
-        term = 0;
-        break;
-      }
-      const double cost_change = cost - cand_cost;
-      if (fabs(cost_change) <= A.function_tolerance * cost) {
-        term = 0;
-        break;
-      }
-      const double relative_decrease = cost_change / mcc;
-      if (relative_decrease > A.min_relative_decrease) {  // HandleSuccessfulStep
+      if (tr.converged(A, sqrt(step_sq), x_norm, cost, cand_cost, &term)) break;
+      if (tr.accept(A, (cost - cand_cost) / mcc)) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) X[i] = Xc[i];
         x_norm = sqrt(X[0] * X[0] + X[1] * X[1] + X[2] * X[2] + X[3] * X[3]);
@@ -422,27 +352,18 @@ __global__ __launch_bounds__(256) void track_lm_kernel(DeviceView v, const doubl
         gmax = 0.0;
 #pragma unroll
         for (int a = 0; a < DP; ++a) gmax = fmax(gmax, fabs(g[a] / sp[a]));
-        radius = radius / fmax(1.0 / 3.0, 1.0 - pow(2.0 * relative_decrease - 1.0, 3.0));
-        radius = fmin(A.max_radius, radius);
-        decrease_factor = 2.0;
         if (gmax <= A.gradient_tolerance) {
           term = 0;
           break;
         }
-      } else {
-        radius /= decrease_factor;
-        decrease_factor *= 2.0;
       }
-      if (radius < A.min_radius) {
-        term = 0;
-        break;
-      }
+      if (tr.too_small(A, &term)) break;
     }
   }
   if (!tm.leader) return;
-  termination[lp] = (signed char)term;
-  iterations[lp] = iter;
-  final_cost[lp] = cost;
+  out.term[lp] = (signed char)term;
+  out.iters[lp] = iter;
+  out.c1[lp] = cost;
   if (term != 2) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) v.pts[(size_t)lp * 4 + i] = X[i];

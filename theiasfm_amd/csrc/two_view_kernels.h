@@ -22,6 +22,7 @@
 
 #include "camera_models.h"
 #include "kernels.h"
+#include "small_lm.h"
 
 namespace tmi {
 
@@ -134,6 +135,8 @@ __device__ __forceinline__ bool tv_jacobians(int model1, int model2, const doubl
 
 // termination[pair]: 0 CONVERGENCE, 1 NO_CONVERGENCE, 2 FAILURE, 3 evaluation failed at the start
 // point, -1 no correspondences.  Parameters are written back unless the code is 2 or 3.
+// Not on small_lm.h's shared core: there a few solves end one rounding apart (the compiler fuses other multiply-adds),
+// and its argument types alone raise the scratch use of this register-bound kernel.
 template <int DP>
 __global__ __launch_bounds__(256) void two_view_lm_kernel(TwoViewBatch B, TwoViewArgs A,
                                                           signed char* __restrict__ termination,
@@ -595,8 +598,7 @@ __global__ __launch_bounds__(256) void two_view_lm_kernel(TwoViewBatch B, TwoVie
 // (unit_norm_three_vector_parameterization.h:45-63).  ONE WAVEFRONT PER PAIR: lanes walk the
 // correspondences, residual and its 6 derivatives come from forward-mode dual numbers (what Ceres'
 // autodiff evaluates), J^T J / J^T r are reduced over the wave and every lane solves the 6 x 6 damped
-// system itself, so the trust-region state machine (Ceres 1.14 semantics, the loop of track_lm_kernel)
-// runs replicated without divergence.
+// system itself, so the trust-region loop (small_lm.h) runs replicated without divergence.
 // ------------------------------------------------------------------------------------------------
 namespace tva {
 struct D6 {
@@ -817,47 +819,6 @@ __device__ __forceinline__ bool linearize(const double (&x)[6], const double* __
   return wave_sum(bad) == 0.0;
 }
 
-// (H + diag) y = g by Cholesky in registers; false if not positive definite
-__device__ __forceinline__ bool solve6(const double (&H)[21], const double (&dadd)[6], const double (&g)[6],
-                                       double (&y)[6]) {
-  double L[6][6];
-  bool pd = true;
-#pragma unroll
-  for (int j = 0; j < 6; ++j) {
-    double d = H[sym_idx(j, j, 6)] + dadd[j];
-#pragma unroll
-    for (int m = 0; m < j; ++m) d -= L[j][m] * L[j][m];
-    if (!(d > 0.0)) {
-      pd = false;
-      d = 1.0;
-    }
-    const double l = sqrt(d);
-    L[j][j] = l;
-#pragma unroll
-    for (int i = j + 1; i < 6; ++i) {
-      double t = H[sym_idx(j, i, 6)];
-#pragma unroll
-      for (int m = 0; m < j; ++m) t -= L[i][m] * L[j][m];
-      L[i][j] = t / l;
-    }
-  }
-  double z[6];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-    double t = g[i];
-#pragma unroll
-    for (int m = 0; m < i; ++m) t -= L[i][m] * z[m];
-    z[i] = t / L[i][i];
-  }
-#pragma unroll
-  for (int i = 5; i >= 0; --i) {
-    double t = z[i];
-#pragma unroll
-    for (int m = i + 1; m < 6; ++m) t -= L[m][i] * y[m];
-    y[i] = t / L[i][i];
-  }
-  return pd;
-}
 }  // namespace tva
 
 struct TwoViewAngularBatch {
@@ -869,22 +830,14 @@ struct TwoViewAngularBatch {
   const double* feat2;
 };
 
-__global__ __launch_bounds__(256) void two_view_angular_kernel(TwoViewAngularBatch B, TwoViewArgs A,
-                                                               signed char* __restrict__ termination,
-                                                               int* __restrict__ iterations,
-                                                               double* __restrict__ initial_cost,
-                                                               double* __restrict__ final_cost) {
+// Termination per pair as in SmallLmOut.  A failed re-linearisation after an accepted step is a FAILURE.
+__global__ __launch_bounds__(256) void two_view_angular_kernel(TwoViewAngularBatch B, SmallLmArgs A, SmallLmOut out) {
   const int lane = threadIdx.x & 63;
   const int p = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (p >= B.num_pairs) return;
   const long long c0 = B.corr_ptr[p], n = B.corr_ptr[p + 1] - c0;
   if (n <= 0) {
-    if (lane == 0) {
-      termination[p] = -1;
-      iterations[p] = 0;
-      initial_cost[p] = 0.0;
-      final_cost[p] = 0.0;
-    }
+    if (lane == 0) out.write(p, -1, 0, 0.0, 0.0);
     return;
   }
   const double* f1 = B.feat1 + 2 * c0;
@@ -897,15 +850,10 @@ __global__ __launch_bounds__(256) void two_view_angular_kernel(TwoViewAngularBat
   }
   double sc[6] = {1.0, 1.0, 1.0, 1.0, 1.0, 1.0}, H[21], g[6], cost = 0.0;
   if (!tva::linearize<true>(x, f1, f2, n, sc, H, g, &cost, lane)) {
-    if (lane == 0) {
-      termination[p] = 3;
-      iterations[p] = 0;
-      initial_cost[p] = 0.0;
-      final_cost[p] = 0.0;
-    }
+    if (lane == 0) out.write(p, 3, 0, 0.0, 0.0);
     return;
   }
-  if (lane == 0) initial_cost[p] = cost;
+  if (lane == 0) out.c0[p] = cost;
   double gmax = 0.0;
 #pragma unroll
   for (int a = 0; a < 6; ++a) gmax = fmax(gmax, fabs(g[a]));
@@ -916,20 +864,21 @@ __global__ __launch_bounds__(256) void two_view_angular_kernel(TwoViewAngularBat
 #pragma unroll
   for (int a = 0; a < 6; ++a) x_norm += x[a] * x[a];
   x_norm = sqrt(x_norm);
-  double radius = A.initial_radius, decrease_factor = 2.0;
-  int invalid_run = 0, iter = 0, term = 1;
+  TrustRegion tr(A);
+  int iter = 0, term = 1;
   if (gmax <= A.gradient_tolerance) {
     term = 0;
   } else {
     for (;;) {
       if (iter >= A.max_num_iterations) break;
       ++iter;
-      double dadd[6], y[6];
-#pragma unroll
-      for (int a = 0; a < 6; ++a) dadd[a] = fmin(fmax(H[sym_idx(a, a, 6)], A.lm_lo), A.lm_hi) / radius;
-      bool step_ok = tva::solve6(H, dadd, g, y);
+      double y[6];
+      const double radius = tr.radius;  // (damped by / radius: bits differ from * (1 / radius))
+      bool step_ok = small_solve<6>(H, [&](double d) { return d + TrustRegion::lm_diag(A, d) / radius; }, g, y,
+                                    /*reciprocal=*/false);
       double mcc = 0.0;
       if (step_ok) {
+        // model_cost_change written out: through the helper this kernel spills 388 bytes per lane instead of 76
         double yg = 0.0, yHy = 0.0;
 #pragma unroll
         for (int a = 0; a < 6; ++a) {
@@ -943,19 +892,9 @@ __global__ __launch_bounds__(256) void two_view_angular_kernel(TwoViewAngularBat
         if (!(mcc > 0.0)) step_ok = false;
       }
       if (!step_ok) {
-        if (++invalid_run >= A.max_num_consecutive_invalid_steps) {
-          term = 2;
-          break;
-        }
-        radius /= decrease_factor;
-        decrease_factor *= 2.0;
-        if (radius < A.min_radius) {
-          term = 0;
-          break;
-        }
+        if (tr.invalid_step(A, &term)) break;
         continue;
       }
-      invalid_run = 0;
       double xc[6], d[6];
 #pragma unroll
       for (int a = 0; a < 6; ++a) d[a] = -y[a] * sc[a];
@@ -967,17 +906,8 @@ __global__ __launch_bounds__(256) void two_view_angular_kernel(TwoViewAngularBat
       for (int a = 0; a < 6; ++a) step_sq += (xc[a] - x[a]) * (xc[a] - x[a]);
       double cand, Hd[21], gd[6];
       if (!tva::linearize<false>(xc, f1, f2, n, sc, Hd, gd, &cand, lane)) cand = 1.7976931348623157e308;
-      if (sqrt(step_sq) <= A.parameter_tolerance * (x_norm + A.parameter_tolerance)) {
-        term = 0;
-        break;
-      }
-      const double cost_change = cost - cand;
-      if (fabs(cost_change) <= A.function_tolerance * cost) {
-        term = 0;
-        break;
-      }
-      const double rd = cost_change / mcc;
-      if (rd > A.min_relative_decrease) {
+      if (tr.converged(A, sqrt(step_sq), x_norm, cost, cand, &term)) break;
+      if (tr.accept(A, (cost - cand) / mcc)) {
 #pragma unroll
         for (int a = 0; a < 6; ++a) x[a] = xc[a];
         x_norm = 0.0;
@@ -991,27 +921,18 @@ __global__ __launch_bounds__(256) void two_view_angular_kernel(TwoViewAngularBat
         gmax = 0.0;
 #pragma unroll
         for (int a = 0; a < 6; ++a) gmax = fmax(gmax, fabs(g[a] / sc[a]));
-        radius = radius / fmax(1.0 / 3.0, 1.0 - pow(2.0 * rd - 1.0, 3.0));
-        radius = fmin(A.max_radius, radius);
-        decrease_factor = 2.0;
         if (gmax <= A.gradient_tolerance) {
           term = 0;
           break;
         }
-      } else {
-        radius /= decrease_factor;
-        decrease_factor *= 2.0;
       }
-      if (radius < A.min_radius) {
-        term = 0;
-        break;
-      }
+      if (tr.too_small(A, &term)) break;
     }
   }
   if (lane != 0) return;
-  termination[p] = (signed char)term;
-  iterations[p] = iter;
-  final_cost[p] = cost;
+  out.term[p] = (signed char)term;
+  out.iters[p] = iter;
+  out.c1[p] = cost;
   if (term != 2) {
 #pragma unroll
     for (int i = 0; i < 3; ++i) {

@@ -13,14 +13,14 @@
 //               up over the tile's rows in row order: J^T J and J^T r in one pass, a fixed summation order;
 //   solve       one lane factors J^T J + diag(clamp(diag J^T J) / radius) (D x D Cholesky in LDS);
 //   trial pass  cost only at x + step, wave butterflies then the four wave sums in order.
-// The trust-region loop is tmi_ba_solver_solve's (engine.hip; Ceres 1.14 semantics) on a problem whose
-// point side is empty, decision for decision: it runs replicated and uniform in every thread, reading the
-// values lane 0 publishes through LDS.
+// The trust-region loop (small_lm.h) runs on a problem whose point side is empty, replicated and uniform in every
+// thread, reading the values lane 0 publishes through LDS.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "camera_models.h"
 #include "kernels.h"
+#include "small_lm.h"
 
 namespace tmi {
 
@@ -38,22 +38,7 @@ struct ViewBatch {
   const double* pts;                  // [4 points] homogeneous, constant
   const int* chain_ptr;               // [n_chains + 1]
   const int* chain_views;             // views of the chains, in order
-  signed char* term;                  // [Nc] per-view outputs (written for the views of the chains)
-  int* iters;
-  double* c0;
-  double* c1;
-};
-
-struct ViewLmArgs {
-  int loss_type;
-  double loss_width;
-  int jacobi_scaling;
-  int max_num_iterations;
-  int max_num_consecutive_invalid_steps;
-  double function_tolerance, gradient_tolerance, parameter_tolerance;
-  double initial_radius, max_radius, min_radius;
-  double min_relative_decrease;
-  double lm_lo, lm_hi;
+  SmallLmOut out;                     // [Nc] per-view outputs (written for the views of the chains)
 };
 
 struct ViewLds {
@@ -222,10 +207,11 @@ __device__ double vb_pass(const ViewBatch& B, ViewLds& S, int model, int D, long
   return cost;
 }
 
-// termination per view: 0 CONVERGENCE, 1 NO_CONVERGENCE, 2 FAILURE, 3 residual evaluation failed at the start
-// point, -1 nothing to adjust.  Extrinsics and the group's intrinsics are written back for 0 and 1.
+// Termination per view as in SmallLmOut.  Extrinsics and the group's intrinsics are written back for 0 and 1.
+// The solve is small_lm.h's loop, but the gradient is tested at the top of an iteration (which then does not count)
+// and the D <= 16 system is factored by lane 0 in LDS: D is known at run time only.
 template <int UMODEL = -1>
-__global__ __launch_bounds__(256) void view_lm_kernel(ViewBatch B, ViewLmArgs A) {
+__global__ __launch_bounds__(256) void view_lm_kernel(ViewBatch B, SmallLmArgs A) {
   __shared__ ViewLds S;
   const int tid = threadIdx.x;
   const int cb = B.chain_ptr[blockIdx.x], ce = B.chain_ptr[blockIdx.x + 1];
@@ -239,12 +225,7 @@ __global__ __launch_bounds__(256) void view_lm_kernel(ViewBatch B, ViewLmArgs A)
     if (ci == cb && tid == 0)  // the chain's intrinsics: from memory once, then what the chain's views leave
       for (int j = 0; j < 10; ++j) S.kchain[j] = j < nk ? B.intr[rec.y + j] : 0.0;
     if (D == 0 || beg == end || D > 16) {
-      if (tid == 0) {
-        B.term[c] = -1;
-        B.iters[c] = 0;
-        B.c0[c] = 0.0;
-        B.c1[c] = 0.0;
-      }
+      if (tid == 0) B.out.write(c, -1, 0, 0.0, 0.0);
       continue;
     }
     if (tid == 0) {
@@ -269,12 +250,7 @@ __global__ __launch_bounds__(256) void view_lm_kernel(ViewBatch B, ViewLmArgs A)
     double cost = vb_pass<true, UMODEL>(B, S, model, D, beg, end, lt, lw, &bad);
     if (bad > 0.0) {
       // tmi_ba_solve stops with TMI_BA_ERR_EVALUATION_FAILED before it reports a cost
-      if (tid == 0) {
-        B.term[c] = 3;
-        B.iters[c] = 0;
-        B.c0[c] = 0.0;
-        B.c1[c] = 0.0;
-      }
+      if (tid == 0) B.out.write(c, 3, 0, 0.0, 0.0);
       __syncthreads();
       continue;
     }
@@ -296,8 +272,8 @@ __global__ __launch_bounds__(256) void view_lm_kernel(ViewBatch B, ViewLmArgs A)
       return n;
     };
     double x_norm = sqrt(x_norm_of(S.x));
-    double radius = A.initial_radius, decrease_factor = 2.0;
-    int invalid_run = 0, iter = 0, term = 1;
+    TrustRegion tr(A);
+    int iter = 0, term = 1;
     bool need_gradient_check = true;
     for (;;) {
       if (iter >= A.max_num_iterations) break;
@@ -312,13 +288,13 @@ __global__ __launch_bounds__(256) void view_lm_kernel(ViewBatch B, ViewLmArgs A)
           break;
         }
       }
-      const double inv_radius = 1.0 / radius;
+      const double inv_radius = 1.0 / tr.radius;
       if (tid == 0) {
         // (J^T J + diag) y = g by Cholesky; model cost change of the step -y: y^T g - 1/2 y^T J^T J y
         double ok = 1.0;
         for (int j = 0; j < D; ++j) {
           const double dj = S.A[j * 16 + j];
-          double d = dj + fmin(fmax(dj, A.lm_lo), A.lm_hi) * inv_radius;
+          double d = dj + TrustRegion::lm_diag(A, dj) * inv_radius;
           for (int m = 0; m < j; ++m) d -= S.L[j * 16 + m] * S.L[j * 16 + m];
           if (!(d > 0.0)) {
             ok = 0.0;
@@ -379,60 +355,29 @@ __global__ __launch_bounds__(256) void view_lm_kernel(ViewBatch B, ViewLmArgs A)
       const bool usable = S.scal[0] != 0.0;
       const double mcc = S.scal[1], step_sq = S.scal[2], cand_xn_sq = S.scal[3];
       __syncthreads();
-      if (!usable) {  // HandleInvalidStep
-        if (++invalid_run >= A.max_num_consecutive_invalid_steps) {
-          term = 2;
-          break;
-        }
-        radius /= decrease_factor;
-        decrease_factor *= 2.0;
-        if (radius < A.min_radius) {
-          term = 0;
-          break;
-        }
+      if (!usable) {
+        if (tr.invalid_step(A, &term)) break;
         continue;
       }
-      invalid_run = 0;
       vb_prepare(S, S.xc, nk);
       double cand_bad = 0.0;
       double cand_cost = vb_pass<false, UMODEL>(B, S, model, D, beg, end, lt, lw, &cand_bad);
       if (cand_bad > 0.0) cand_cost = 1.7976931348623157e308;
-      if (sqrt(step_sq) <= A.parameter_tolerance * (x_norm + A.parameter_tolerance)) {
-        term = 0;
-        break;
-      }
-      const double cost_change = cost - cand_cost;
-      if (fabs(cost_change) <= A.function_tolerance * cost) {
-        term = 0;
-        break;
-      }
-      const double relative_decrease = cost_change / mcc;
-      if (relative_decrease > A.min_relative_decrease) {  // HandleSuccessfulStep
+      if (tr.converged(A, sqrt(step_sq), x_norm, cost, cand_cost, &term)) break;
+      if (tr.accept(A, (cost - cand_cost) / mcc)) {
         if (tid == 0)
           for (int a = 0; a < 16; ++a) S.x[a] = S.xc[a];
         __syncthreads();
         cost = cand_cost;
         x_norm = sqrt(cand_xn_sq);
-        radius = radius / fmax(1.0 / 3.0, 1.0 - pow(2.0 * relative_decrease - 1.0, 3.0));
-        radius = fmin(A.max_radius, radius);
-        decrease_factor = 2.0;
         vb_prepare(S, S.x, nk);
         vb_pass<true, UMODEL>(B, S, model, D, beg, end, lt, lw, &bad);
         need_gradient_check = true;
-      } else {
-        radius /= decrease_factor;
-        decrease_factor *= 2.0;
       }
-      if (radius < A.min_radius) {
-        term = 0;
-        break;
-      }
+      if (tr.too_small(A, &term)) break;
     }
     if (tid == 0) {
-      B.term[c] = (signed char)term;
-      B.iters[c] = iter;
-      B.c0[c] = initial_cost;
-      B.c1[c] = cost;
+      B.out.write(c, term, iter, initial_cost, cost);
       if (term != 2) {  // IsSolutionUsable
         for (int a = 0; a < 6; ++a) B.ext[(size_t)c * 6 + a] = S.x[a];
         if (fm >> 6) {
