@@ -4,10 +4,12 @@
 #define THEIA_MI355_SFM_TYPES_H_
 #include <atomic>
 #include <cstdint>
+#include <utility>
 namespace theia {
 using ViewId = std::uint32_t;
 using TrackId = std::uint32_t;
 using CameraIntrinsicsGroupId = std::uint32_t;
+using ViewIdPair = std::pair<ViewId, ViewId>;  // reference types.h: an edge of the view graph
 constexpr ViewId kInvalidViewId = UINT32_MAX;
 constexpr TrackId kInvalidTrackId = UINT32_MAX;
 constexpr CameraIntrinsicsGroupId kInvalidCameraIntrinsicsGroupId = UINT32_MAX;

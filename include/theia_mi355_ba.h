@@ -725,6 +725,46 @@ int32_t tmi_ba_adjust_two_views_angular(tmi_ba_two_view_angular_batch* batch, in
                                         double* pair_initial_cost, double* pair_final_cost,
                                         tmi_ba_track_batch_summary* summary);
 
+/* ---- batched OptimizeRelativePositionWithKnownRotation -------------------------------------
+ * reference: optimize_relative_position_with_known_rotation.cc:53-197, called once per view-graph edge
+ * by RefineRelativeTranslationsWithKnownRotations (reconstruction_estimator_utils.cc:244-269) -- the
+ * unit direction of camera 2's position in camera 1's frame from the pair's correspondences and the
+ * two known world-to-camera rotations: constraint columns c_i = R1 (R2^T [f2_i; 1] x R1^T [f1_i; 1])
+ * (:53-79), iteratively reweighted least squares on t^T c_i = 0 (:128-184; at most 100 iterations,
+ * stopping once the change max(|cost - new cost|, 1 - t^T t) stayed <= 1e-5 for 10 iterations in a
+ * row, weights clamped at 1e-7 -- the reference's constants, not options), then t -> -t unless more
+ * than n / 2 correspondences triangulate in front of both cameras (:189-194, triangulation.cc:216-232).
+ * The position is an output only (the reference overwrites its argument before reading it).
+ * Views and pairs: an orientation per view and an edge list, as the caller of the global pipeline has
+ * them.  With view_model / view_intrinsics the features are pixels and the device normalises them
+ * (PixelToNormalizedCoordinates(...).hnormalized(), reconstruction_estimator_utils.cc:84-88).
+ * One wavefront per pair on the device; a pair's result does not depend on the rest of the batch.
+ *   pair_status: 0 converged, 1 stopped at 100 iterations (position2 written for both, as the
+ *   reference returns true for both), 2 non-finite input (position2 untouched), -1 pair without
+ *   correspondences (untouched).  pair_cost: the final sum of |t^T c_i|.  pair_num_in_front: the
+ *   correspondences in front of both cameras for the returned sign.  Where neither sign has a
+ *   majority the returned sign is implementation-defined (in the reference: by its SVD).
+ *   All per-pair outputs may be NULL.  summary: num_tracks = pairs with correspondences,
+ *   num_success = pairs with status 0 or 1, total_iterations = IRLS iterations over the pairs. */
+typedef struct tmi_ba_relative_position_batch {
+  int32_t num_views;
+  const double*  view_rotation;     /* [3 * num_views] angle-axis, world to camera                      */
+  const int32_t* view_model;        /* [num_views] tmi_ba_camera_model; NULL = features are normalised   */
+  const double*  view_intrinsics;   /* [10 * num_views] model order, zero padded; NULL with view_model   */
+  int32_t num_pairs;
+  const int32_t* pair_view1;        /* [num_pairs] */
+  const int32_t* pair_view2;
+  const int64_t* correspondence_ptr;/* [num_pairs + 1] */
+  const double*  features1;         /* [2 * N] normalised coordinates, or pixels when view_model != NULL */
+  const double*  features2;
+  double*        position2;         /* [3 * num_pairs] OUT (untouched for status -1 / 2)                */
+} tmi_ba_relative_position_batch;
+
+int32_t tmi_ba_optimize_relative_positions(tmi_ba_relative_position_batch* batch, int32_t device,
+                                           int8_t* pair_status, int32_t* pair_iterations,
+                                           double* pair_cost, int32_t* pair_num_in_front,
+                                           tmi_ba_track_batch_summary* summary);
+
 /* Test hook: FNV-1a checksums of the static structure arrays resident in HBM -- built in HBM by
  * sort / scan kernels (one rank, no shared intrinsics blocks; TMI_BA_HOST_SETUP=1 disables) or on
  * host threads otherwise.  out[0] = 1 when the device built it; the other slots are documented at

@@ -20,6 +20,7 @@ import numpy as np
 # ---- enums ------------------------------------------------------------------
 PINHOLE, PINHOLE_RADIAL_TANGENTIAL, FISHEYE, FOV, DIVISION_UNDISTORTION = range(5)
 INTRINSICS_SIZE = (7, 10, 9, 5, 5)
+MAX_INTRINSICS = 10  # TMI_BA_MAX_INTRINSICS
 
 LOSS_TRIVIAL, LOSS_HUBER, LOSS_SOFTLONE, LOSS_CAUCHY, LOSS_ARCTAN, LOSS_TUKEY = range(6)
 
@@ -253,6 +254,22 @@ class CTwoViewAngularBatch(C.Structure):
         ("correspondence_ptr", C.POINTER(C.c_int64)),
         ("features1", C.POINTER(C.c_double)),
         ("features2", C.POINTER(C.c_double)),
+    ]
+
+
+class CRelativePositionBatch(C.Structure):
+    _fields_ = [
+        ("num_views", C.c_int32),
+        ("view_rotation", C.POINTER(C.c_double)),
+        ("view_model", C.POINTER(C.c_int32)),
+        ("view_intrinsics", C.POINTER(C.c_double)),
+        ("num_pairs", C.c_int32),
+        ("pair_view1", C.POINTER(C.c_int32)),
+        ("pair_view2", C.POINTER(C.c_int32)),
+        ("correspondence_ptr", C.POINTER(C.c_int64)),
+        ("features1", C.POINTER(C.c_double)),
+        ("features2", C.POINTER(C.c_double)),
+        ("position2", C.POINTER(C.c_double)),
     ]
 
 
@@ -573,4 +590,75 @@ class TwoViewAngularBatch:
         b.correspondence_ptr = _ptr(self.correspondence_ptr, C.c_int64)
         b.features1 = _ptr(self.features1, C.c_double)
         b.features2 = _ptr(self.features2, C.c_double)
+        return b
+
+
+@dataclass
+class RelativePositionBatch:
+    """View pairs for the batched OptimizeRelativePositionWithKnownRotation (``tmi_ba_relative_position_batch``):
+    an orientation per view, an edge list, the correspondences of every edge."""
+
+    view_rotation: np.ndarray          # [V, 3] angle-axis, world to camera
+    pair_view1: np.ndarray             # [P] int32
+    pair_view2: np.ndarray
+    correspondence_ptr: np.ndarray     # [P + 1] int64
+    features1: np.ndarray              # [N, 2] normalised coordinates, or pixels when view_model is given
+    features2: np.ndarray
+    position2: np.ndarray = None       # [P, 3] OUT (zeros when not given)
+    view_model: np.ndarray = None      # [V] int32 camera model, or None: the features are normalised
+    view_intrinsics: np.ndarray = None # [V, 10] model order, zero padded; given exactly when view_model is
+
+    def __post_init__(self):
+        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
+        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)  # noqa: E731
+        self.view_rotation = f64(self.view_rotation).reshape(-1, 3)
+        self.pair_view1 = i32(self.pair_view1)
+        self.pair_view2 = i32(self.pair_view2)
+        self.correspondence_ptr = np.ascontiguousarray(self.correspondence_ptr, dtype=np.int64)
+        self.features1 = f64(self.features1).reshape(-1, 2)
+        self.features2 = f64(self.features2).reshape(-1, 2)
+        if self.position2 is None:
+            self.position2 = np.zeros((self.pair_view1.shape[0], 3))
+        self.position2 = f64(self.position2).reshape(-1, 3)
+        if self.view_model is not None:
+            self.view_model = i32(self.view_model)
+        if self.view_intrinsics is not None:
+            self.view_intrinsics = f64(self.view_intrinsics).reshape(-1, MAX_INTRINSICS)
+
+    @property
+    def num_views(self) -> int:
+        return self.view_rotation.shape[0]
+
+    @property
+    def num_pairs(self) -> int:
+        return self.pair_view1.shape[0]
+
+    def copy(self) -> "RelativePositionBatch":
+        cp = lambda a: None if a is None else a.copy()  # noqa: E731
+        return RelativePositionBatch(self.view_rotation.copy(), self.pair_view1.copy(), self.pair_view2.copy(),
+                                     self.correspondence_ptr.copy(), self.features1.copy(), self.features2.copy(),
+                                     self.position2.copy(), cp(self.view_model), cp(self.view_intrinsics))
+
+    def pair(self, p: int) -> "RelativePositionBatch":
+        """pair p alone, on the same view tables (copies)"""
+        a, b = int(self.correspondence_ptr[p]), int(self.correspondence_ptr[p + 1])
+        cp = lambda x: None if x is None else x.copy()  # noqa: E731
+        return RelativePositionBatch(self.view_rotation.copy(), self.pair_view1[p:p + 1].copy(),
+                                     self.pair_view2[p:p + 1].copy(), np.array([0, b - a], dtype=np.int64),
+                                     self.features1[a:b].copy(), self.features2[a:b].copy(),
+                                     self.position2[p:p + 1].copy(), cp(self.view_model), cp(self.view_intrinsics))
+
+    def as_c(self) -> CRelativePositionBatch:
+        b = CRelativePositionBatch()
+        b.num_views = self.num_views
+        b.view_rotation = _ptr(self.view_rotation, C.c_double)
+        b.view_model = _ptr(self.view_model, C.c_int32)
+        b.view_intrinsics = _ptr(self.view_intrinsics, C.c_double)
+        b.num_pairs = self.num_pairs
+        b.pair_view1 = _ptr(self.pair_view1, C.c_int32)
+        b.pair_view2 = _ptr(self.pair_view2, C.c_int32)
+        b.correspondence_ptr = _ptr(self.correspondence_ptr, C.c_int64)
+        b.features1 = _ptr(self.features1, C.c_double)
+        b.features2 = _ptr(self.features2, C.c_double)
+        b.position2 = _ptr(self.position2, C.c_double)
         return b

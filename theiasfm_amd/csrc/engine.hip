@@ -33,6 +33,7 @@
 #include "direct_diag.h"
 #include "pcg_persist.h"
 #include "track_kernels.h"
+#include "relative_position_kernels.h"
 #include "track_estimate_kernels.h"
 #include "inner_kernels.h"
 #include "two_view_kernels.h"
@@ -4580,6 +4581,149 @@ int32_t tmi_ba_adjust_two_views_angular(tmi_ba_two_view_angular_batch* Bh, int32
         Bh->position2[(size_t)3 * p + a] = pos[(size_t)3 * p + a];
       }
     }
+    return TMI_BA_OK;
+  }();
+  if (rc) g_last_error = s->error;
+  sum->seconds = now_s() - t0;
+  return rc;
+}
+
+// OptimizeRelativePositionWithKnownRotation for a batch of view pairs (relative_position_kernels.h)
+int32_t tmi_ba_optimize_relative_positions(tmi_ba_relative_position_batch* Bh, int32_t device, int8_t* pair_status,
+                                           int32_t* pair_iterations, double* pair_cost, int32_t* pair_num_in_front,
+                                           tmi_ba_track_batch_summary* sum) {
+  if (!Bh || !sum) return TMI_BA_ERR_INVALID_ARGUMENT;
+  memset(sum, 0, sizeof(*sum));
+  // argument errors before the device is touched
+  auto bad = [](const char* why) {
+    g_last_error = why;
+    return TMI_BA_ERR_INVALID_ARGUMENT;
+  };
+  const int V = Bh->num_views, P = Bh->num_pairs;
+  if (V < 0 || P < 0) return bad("relative positions: negative size");
+  if ((V > 0 && !Bh->view_rotation) || (P > 0 && (!Bh->pair_view1 || !Bh->pair_view2 || !Bh->correspondence_ptr ||
+                                                   !Bh->position2)))
+    return bad("relative positions: missing array");
+  if ((Bh->view_model != nullptr) != (Bh->view_intrinsics != nullptr))
+    return bad("relative positions: view_model and view_intrinsics come together");
+  const bool pixels = Bh->view_model != nullptr;
+  if (pixels)
+    for (int v = 0; v < V; ++v)
+      if (Bh->view_model[v] < TMI_BA_PINHOLE || Bh->view_model[v] > TMI_BA_DIVISION_UNDISTORTION)
+        return bad("relative positions: unknown camera model");
+  const double t0 = now_s();
+  for (int p = 0; p < P; ++p) {
+    if (Bh->correspondence_ptr[p + 1] < Bh->correspondence_ptr[p] || Bh->correspondence_ptr[p] < 0)
+      return bad("relative positions: correspondence_ptr decreases");
+    if (Bh->pair_view1[p] < 0 || Bh->pair_view1[p] >= V || Bh->pair_view2[p] < 0 || Bh->pair_view2[p] >= V)
+      return bad("relative positions: view index out of range");
+  }
+  const int64_t N = P ? Bh->correspondence_ptr[P] : 0;
+  if (N > 0 && (!Bh->features1 || !Bh->features2)) return bad("relative positions: missing array");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+    g_last_error = "no HIP device visible (the device path has no CPU fallback)";
+    return TMI_BA_ERR_NO_DEVICE;
+  }
+  if (device >= ndev) return bad("relative positions: no such device");
+  if (P == 0) return TMI_BA_OK;
+  // pairs too long for the kernel's registers keep their columns in a scratch plane
+  std::vector<long long> sptr((size_t)P, -1);
+  long long slen = 0;
+  for (int p = 0; p < P; ++p) {
+    const long long n = Bh->correspondence_ptr[p + 1] - Bh->correspondence_ptr[p];
+    if (n > 64LL * kRelPosRegColumns) {
+      sptr[p] = slen;
+      slen += n;
+    }
+  }
+  OneShot sc;
+  OneShot* s = &sc;  // (TMI_HIP reports into s->error)
+  const int rc = [&]() -> int {
+    int rc = s->open(device);
+    if (rc) return rc;
+    RelativePositionBatch B;
+    memset(&B, 0, sizeof(B));
+    B.num_pairs = P;
+    double *d_rot, *d_intr = nullptr, *d_f1, *d_f2;
+    int *d_model = nullptr, *d_v1, *d_v2;
+    long long *d_cptr, *d_sptr;
+    TMI_HIP(s->upload(&d_rot, Bh->view_rotation, (size_t)3 * V));
+    TMI_HIP(s->upload(&d_v1, (const int*)Bh->pair_view1, (size_t)P));
+    TMI_HIP(s->upload(&d_v2, (const int*)Bh->pair_view2, (size_t)P));
+    TMI_HIP(s->upload(&d_cptr, (const long long*)Bh->correspondence_ptr, (size_t)P + 1));
+    TMI_HIP(s->upload(&d_sptr, (const long long*)sptr.data(), (size_t)P));
+    TMI_HIP(s->upload(&d_f1, Bh->features1, (size_t)2 * N));
+    TMI_HIP(s->upload(&d_f2, Bh->features2, (size_t)2 * N));
+    if (pixels) {
+      TMI_HIP(s->upload(&d_model, (const int*)Bh->view_model, (size_t)V));
+      TMI_HIP(s->upload(&d_intr, Bh->view_intrinsics, (size_t)10 * V));
+    }
+    B.view_rot = d_rot;
+    B.view_model = d_model;
+    B.view_intr = d_intr;
+    B.pair_view1 = d_v1;
+    B.pair_view2 = d_v2;
+    B.corr_ptr = d_cptr;
+    B.feat1 = d_f1;
+    B.feat2 = d_f2;
+    B.scratch_ptr = d_sptr;
+    B.scratch_len = slen;
+    TMI_HIP(s->alloc(&B.scratch, (size_t)3 * (size_t)slen));
+    TMI_HIP(s->alloc(&B.pos2, (size_t)3 * P));
+    TMI_HIP(s->alloc(&B.status, (size_t)P));
+    TMI_HIP(s->alloc(&B.iters, (size_t)P));
+    TMI_HIP(s->alloc(&B.cost, (size_t)P));
+    TMI_HIP(s->alloc(&B.in_front, (size_t)P));
+    double *d_n1 = nullptr, *d_n2 = nullptr;
+    if (pixels) {
+      TMI_HIP(s->alloc(&d_n1, (size_t)2 * N));
+      TMI_HIP(s->alloc(&d_n2, (size_t)2 * N));
+    }
+    hipEvent_t ea, eb;
+    TMI_HIP(hipEventCreate(&ea));
+    TMI_HIP(hipEventCreate(&eb));
+    hipEventRecord(ea, s->stream);
+    if (pixels) {
+      hipLaunchKernelGGL(relative_position_normalise_kernel, dim3((P + 3) / 4), dim3(256), 0, s->stream, B, d_n1, d_n2);
+      B.feat1 = d_n1;
+      B.feat2 = d_n2;
+    }
+    hipLaunchKernelGGL(relative_position_kernel, dim3((P + 3) / 4), dim3(256), 0, s->stream, B);
+    hipEventRecord(eb, s->stream);
+    const hipError_t le = hipGetLastError();
+    std::vector<double> pos((size_t)3 * P), cost((size_t)P);
+    std::vector<signed char> status((size_t)P);
+    std::vector<int> iters((size_t)P), front((size_t)P);
+    hipError_t ce = hipMemcpyAsync(pos.data(), B.pos2, pos.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream);
+    if (ce == hipSuccess) ce = hipMemcpyAsync(cost.data(), B.cost, (size_t)P * sizeof(double), hipMemcpyDeviceToHost, s->stream);
+    if (ce == hipSuccess) ce = hipMemcpyAsync(status.data(), B.status, (size_t)P, hipMemcpyDeviceToHost, s->stream);
+    if (ce == hipSuccess) ce = hipMemcpyAsync(iters.data(), B.iters, (size_t)P * sizeof(int), hipMemcpyDeviceToHost, s->stream);
+    if (ce == hipSuccess) ce = hipMemcpyAsync(front.data(), B.in_front, (size_t)P * sizeof(int), hipMemcpyDeviceToHost, s->stream);
+    const hipError_t se = hipStreamSynchronize(s->stream);
+    float ms = 0.f;
+    hipEventElapsedTime(&ms, ea, eb);
+    hipEventDestroy(ea);
+    hipEventDestroy(eb);
+    TMI_HIP(le);
+    TMI_HIP(ce);
+    TMI_HIP(se);
+    for (int p = 0; p < P; ++p) {
+      const int st = status[p];
+      if (st >= 0) {
+        sum->num_tracks++;
+        sum->total_iterations += iters[p];
+      }
+      if (st == 0 || st == 1) {  // the reference returns the position for both
+        sum->num_success++;
+        for (int a = 0; a < 3; ++a) Bh->position2[(size_t)3 * p + a] = pos[(size_t)3 * p + a];
+      }
+      if (pair_status) pair_status[p] = (int8_t)st;
+      if (pair_iterations) pair_iterations[p] = iters[p];
+      if (pair_cost) pair_cost[p] = cost[p];
+      if (pair_num_in_front) pair_num_in_front[p] = front[p];
+    }
+    sum->kernel_seconds = 1e-3 * ms;
     return TMI_BA_OK;
   }();
   if (rc) g_last_error = s->error;

@@ -32,7 +32,8 @@ EXPORTS = (
     "tmi_ba_solver_adjust_views", "tmi_ba_adjust_views",
     "tmi_ba_track_estimator_options_init", "tmi_ba_solver_estimate_tracks", "tmi_ba_estimate_tracks",
     "tmi_ba_solver_select_good_tracks", "tmi_ba_select_good_tracks",
-    "tmi_ba_adjust_two_views", "tmi_ba_adjust_two_views_angular", "tmi_ba_solver_structure_checksums",
+    "tmi_ba_adjust_two_views", "tmi_ba_adjust_two_views_angular", "tmi_ba_optimize_relative_positions",
+    "tmi_ba_solver_structure_checksums",
     "tmi_ba_solver_operator_info",
 )
 
@@ -137,6 +138,10 @@ def load():
                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                   C.POINTER(abi.CTrackBatchSummary)]
     L.tmi_ba_adjust_two_views_angular.restype = C.c_int32
+    L.tmi_ba_optimize_relative_positions.argtypes = [C.POINTER(abi.CRelativePositionBatch), C.c_int32, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.POINTER(abi.CTrackBatchSummary)]
+    L.tmi_ba_optimize_relative_positions.restype = C.c_int32
     L.tmi_ba_solver_structure_checksums.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     L.tmi_ba_solver_structure_checksums.restype = C.c_int32
     L.tmi_ba_solver_operator_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
@@ -335,6 +340,24 @@ def adjust_two_views_angular(batch: abi.TwoViewAngularBatch, max_num_iterations:
     if st != 0:
         raise EngineError(st, "tmi_ba_adjust_two_views_angular")
     return term, iters, c0, c1, ts
+
+
+def optimize_relative_positions(batch: abi.RelativePositionBatch, device: int = -1):
+    """Batched OptimizeRelativePositionWithKnownRotation; batch.position2 is written for the pairs with status 0 or 1.
+    Returns (status [P] int8, iterations [P] int32, cost [P], num_in_front [P] int32, CTrackBatchSummary)."""
+    L = load()
+    cb = batch.as_c()
+    n = batch.num_pairs
+    status = np.full(n, -1, dtype=np.int8)
+    iters = np.zeros(n, dtype=np.int32)
+    cost = np.zeros(n)
+    front = np.zeros(n, dtype=np.int32)
+    ts = abi.CTrackBatchSummary()
+    st = L.tmi_ba_optimize_relative_positions(C.byref(cb), int(device), status.ctypes.data, iters.ctypes.data,
+                                              cost.ctypes.data, front.ctypes.data, C.byref(ts))
+    if st != 0:
+        raise EngineError(st, "tmi_ba_optimize_relative_positions")
+    return status, iters, cost, front, ts
 
 
 class Solver:

@@ -485,3 +485,74 @@ def make_two_view_angular_batch(n_pairs: int, seed: int, *, min_corr: int = 30, 
     pos0 = pos_true + position_error * rng.normal(size=pos_true.shape)
     pos0 /= np.linalg.norm(pos0, axis=1, keepdims=True)
     return abi.TwoViewAngularBatch(rot0, pos0, ptr, f1, f2), rot_true, pos_true
+
+
+def make_relative_position_batch(n_pairs: int, seed: int, *, min_corr: int = 30, max_corr: int = 300,
+                                 pixel_noise: float = 0.5, models=None, n_views: int = 48, counts=None):
+    """Seeded view-graph edges for OptimizeRelativePositionWithKnownRotation: n_views views with known poses on the
+    ring scene (radius 100, looking at the centre), every pair one to three places apart on the ring (a baseline of
+    13 to 40 units against a depth of about 100) in either order, correspondences of points around the centre, in front
+    of both views.  models: optional list of (camera_model, fraction) -- the views then carry a model with
+    non-trivial distortion and the features are PIXELS projected through it; otherwise the features are NORMALISED
+    coordinates.  pixel_noise: uniform in +-pixel_noise pixels (divided by the focal length for normalised features).
+    counts: the correspondences of every pair (overrides min_corr / max_corr).
+    Returns (batch, true directions R1 (C2 - C1) / |C2 - C1| [P, 3])."""
+    rng = np.random.default_rng(seed)
+    V = int(n_views)
+    radius = 100.0
+    phi = (np.arange(V) + rng.uniform(-0.3, 0.3, V)) * (2 * np.pi / V)
+    rr = radius * (1.0 + rng.uniform(-0.08, 0.08, V))
+    Cw = np.stack([rr * np.cos(phi), radius * rng.uniform(-0.15, 0.15, V), rr * np.sin(phi)], 1)
+    aa = _look_at(Cw, radius * 0.05 * rng.normal(size=(V, 3)))
+    Rm = Rotation.from_rotvec(aa).as_matrix()
+    model = np.zeros(V, np.int32)
+    if models:
+        edges = np.cumsum([fr for _, fr in models])
+        u = rng.random(V) * edges[-1]
+        model[:] = [models[int(np.searchsorted(edges, x))][0] for x in u]
+    f = rng.uniform(600, 900, V)
+    K = np.zeros((V, abi.MAX_INTRINSICS))
+    for v in range(V):
+        m = model[v]
+        if m in (abi.PINHOLE, abi.PINHOLE_RADIAL_TANGENTIAL, abi.FISHEYE):
+            K[v, :5] = [f[v], 1.0, 0.0, 500.0, 400.0]
+            if m == abi.PINHOLE:
+                K[v, 5:7] = [-0.05, 0.01]
+            elif m == abi.PINHOLE_RADIAL_TANGENTIAL:
+                K[v, 5:10] = [-0.05, 0.01, 0.001, 1e-3, -1e-3]
+            else:
+                K[v, 5:9] = [-0.02, 0.003, 0.0, 0.0]
+        elif m == abi.FOV:
+            K[v, :5] = [f[v], 1.0, 500.0, 400.0, 0.2]
+        else:
+            K[v, :5] = [f[v], 1.0, 500.0, 400.0, -1e-7]
+    if counts is None:
+        counts = rng.integers(min_corr, max_corr + 1, n_pairs)
+    counts = np.asarray(counts, dtype=np.int64)
+    ptr = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    N = int(ptr[-1])
+    va = rng.integers(0, V, n_pairs)
+    vb = (va + rng.integers(1, 4, n_pairs)) % V
+    swap = rng.random(n_pairs) < 0.5
+    v1 = np.where(swap, vb, va).astype(np.int32)
+    v2 = np.where(swap, va, vb).astype(np.int32)
+    X = radius * 0.3 * rng.uniform(-1, 1, (N, 3))
+    pair_of = np.repeat(np.arange(n_pairs), counts)
+
+    def features(view):
+        vv = view[pair_of]
+        q = np.einsum("nij,nj->ni", Rm[vv], X - Cw[vv])
+        noise = rng.uniform(-pixel_noise, pixel_noise, (N, 2))
+        if not models:
+            return q[:, :2] / q[:, 2:3] + noise / f[vv][:, None]
+        out = np.empty((N, 2))
+        for m in np.unique(model):
+            sel = np.nonzero(model[vv] == m)[0]
+            out[sel] = _distort(int(m), K[vv[sel], :abi.INTRINSICS_SIZE[m]], q[sel])
+        return out + noise
+
+    f1, f2 = features(v1), features(v2)
+    d = Cw[v2] - Cw[v1]
+    truth = np.einsum("nij,nj->ni", Rm[v1], d / np.linalg.norm(d, axis=1, keepdims=True))
+    batch = abi.RelativePositionBatch(aa, v1, v2, ptr, f1, f2, None, model if models else None, K if models else None)
+    return batch, truth
