@@ -701,6 +701,83 @@ int32_t tmi_ba_adjust_two_views(tmi_ba_two_view_batch* batch, int32_t point_dof,
                                 double* pair_initial_cost, double* pair_final_cost,
                                 tmi_ba_track_batch_summary* summary);
 
+/* ---- batched two-view verification BA: triangulate, adjust, filter ------------------------
+ * reference: TwoViewMatchGeometricVerification::BundleAdjustRelativePose
+ * (src/theia/sfm/two_view_match_geometric_verification.cc:256-324), the one caller of BundleAdjustTwoViews, with the
+ * two tests VerifyMatches puts around it (:171-176, :181).  The input per pair is what that function has: the two
+ * cameras (SetupCameras :56-68), the two constant-intrinsics flags (:276-279) and the pair's correspondences in
+ * pixels; batch->points is an OUTPUT only (its input is ignored).  For a pair with n correspondences:
+ *   1. n <= min_num_inlier_matches: BundleAdjustRelativePose is not entered (:171-176) and :181 cannot hold
+ *                                                                        -> pair status 1, nothing written
+ *   2. TriangulatePoints (:185-254), per correspondence in input order:
+ *      rays Camera::PixelToUnitDepthRay(feature).normalized() of both cameras (:209-211; as step 2 of
+ *      tmi_ba_estimate_tracks);
+ *      SufficientTriangulationAngle (:212-216; dot < cos(min_triangulation_angle_degrees)) fails
+ *                                                                        -> correspondence status 1
+ *      TriangulateMidpoint over the origins {C1, C2} (:218-222; the 4 x 4 homogeneous form and Eigen's LLT rule of
+ *      step 4 of tmi_ba_estimate_tracks) fails                           -> correspondence status 2
+ *      AcceptableReprojectionError (:72-83) in camera 1, then camera 2, against
+ *      triangulation_max_reprojection_error (:226-238): a Camera::ProjectPoint depth < 0, or a squared error not
+ *      strictly below the squared threshold                              -> correspondence status 3
+ *      the survivors are compacted in their original order (:240-241, :253)
+ *   3. fewer than min_num_inlier_matches survivors (:268; `<`)           -> pair status 2, no adjustment
+ *   4. BundleAdjustTwoViews on the survivors (:272-289): tmi_ba_adjust_two_views' solve, bit for bit; a termination
+ *      other than CONVERGENCE / NO_CONVERGENCE (:291-293)                -> pair status 3, cameras untouched
+ *   5. the filter after the adjustment (:295-314): the same two-camera test against final_max_reprojection_error on
+ *      the adjusted cameras and points                                   -> correspondence status 4 where it fails
+ *   6. more than min_num_inlier_matches correspondences left (:181; `>`) -> pair status 0, otherwise 4.  For both,
+ *      extrinsics2 and the two focal lengths are updated in place: the reference updates the TwoViewInfo (:316-321)
+ *      before VerifyMatches applies that last test.
+ * correspondence_status[N] (int8): -1 not attempted (pair status 1), 0 kept, 1..4 as above.  A 0 means "verified" only
+ * in a pair of status 0 or 4; in a pair of status 2 or 3 it marks the survivors of the triangulation.
+ * points are written for the correspondences of status 0 and 4: adjusted in pairs of status 0 / 4, the triangulated
+ * value in pairs of status 2 / 3.  pair_num_verified[num_pairs]: the pair's correspondences at status 0.
+ * pair_termination / pair_iterations / pair_initial_cost / pair_final_cost: those of tmi_ba_adjust_two_views
+ * (termination -1 where no adjustment ran).  Every per-pair and per-correspondence output may be NULL.
+ * bundle_adjustment == 0 stops after step 3: pair status 0 or 2, the triangulated points written at their original
+ * indices.  That mode is NOT a path of the reference (which calls this function only to adjust): it is an extension
+ * for staging the steps and for tests.
+ * One wavefront per pair in three launches (triangulate, solve, accept); a pair's result does not depend on the rest
+ * of the batch.  Out of scope: the RANSAC of EstimateTwoViewInfo (:128-134), guided matching (:157-168)
+ * and the homography inlier count (:124). */
+typedef struct tmi_ba_two_view_verification_options {
+  int32_t min_num_inlier_matches;               /* 30   (two_view_match_geometric_verification.h:59-92) */
+  double triangulation_max_reprojection_error;  /* 15.0 */
+  double min_triangulation_angle_degrees;       /* 4.0  */
+  double final_max_reprojection_error;          /* 5.0  */
+  int32_t bundle_adjustment;                    /* 1    */
+} tmi_ba_two_view_verification_options;
+
+void tmi_ba_two_view_verification_options_init(tmi_ba_two_view_verification_options* options);
+
+typedef struct tmi_ba_two_view_verification_summary {
+  int64_t num_pairs;                         /* pairs of the batch */
+  int64_t num_pairs_verified;                /* pair status 0 */
+  int64_t num_pairs_too_few_matches;         /* pair status 1 */
+  int64_t num_pairs_too_few_triangulated;    /* pair status 2 */
+  int64_t num_pairs_failed_ba;               /* pair status 3 */
+  int64_t num_pairs_too_few_verified;        /* pair status 4 */
+  int64_t num_correspondences;               /* correspondences with a status >= 0 */
+  int64_t num_verified;                      /* correspondence status 0 */
+  int64_t num_bad_triangulation_angles;      /* 1 (the reference's VLOG counters, :198-200) */
+  int64_t num_failed_triangulations;         /* 2 */
+  int64_t num_bad_reprojection_errors;       /* 3 */
+  int64_t num_bad_final_reprojection_errors; /* 4 (:312-313) */
+  int64_t total_iterations;                  /* sum of LM iterations over the adjusted pairs */
+  double seconds;                            /* wall time of the call */
+  double kernel_seconds;                     /* all launches of the call (HIP events) */
+  double triangulate_kernel_seconds;         /* its split: two_view_triangulate_kernel */
+  double solve_kernel_seconds;               /*            two_view_lm_kernel */
+  double accept_kernel_seconds;              /*            two_view_accept_kernel: kernel_seconds minus the two
+                                              *            above, not an event pair of its own */
+} tmi_ba_two_view_verification_summary;
+
+int32_t tmi_ba_verify_two_views(tmi_ba_two_view_batch* batch, const tmi_ba_two_view_verification_options* options,
+                                int32_t point_dof, int32_t max_num_iterations, int32_t device,
+                                int8_t* correspondence_status, int8_t* pair_status, int32_t* pair_num_verified,
+                                int8_t* pair_termination, int32_t* pair_iterations, double* pair_initial_cost,
+                                double* pair_final_cost, tmi_ba_two_view_verification_summary* summary);
+
 /* ---- batched BundleAdjustTwoViewsAngular --------------------------------------------------
  * reference: bundle_adjust_two_views.cc:193-240 -- the relative pose of a view pair from
  * its correspondences alone: parameters TwoViewInfo::rotation_2 (angle-axis, 3) and

@@ -246,6 +246,57 @@ class CTwoViewBatch(C.Structure):
     ]
 
 
+class CTwoViewVerificationOptions(C.Structure):
+    """tmi_ba_two_view_verification_options (TwoViewMatchGeometricVerification::Options,
+    two_view_match_geometric_verification.h:59-92)."""
+    _fields_ = [
+        ("min_num_inlier_matches", C.c_int32),
+        ("triangulation_max_reprojection_error", C.c_double),
+        ("min_triangulation_angle_degrees", C.c_double),
+        ("final_max_reprojection_error", C.c_double),
+        ("bundle_adjustment", C.c_int32),
+    ]
+
+
+def two_view_verification_options(**overrides) -> CTwoViewVerificationOptions:
+    """The reference's defaults; mirrors tmi_ba_two_view_verification_options_init."""
+    o = CTwoViewVerificationOptions()
+    o.min_num_inlier_matches = 30
+    o.triangulation_max_reprojection_error = 15.0
+    o.min_triangulation_angle_degrees = 4.0
+    o.final_max_reprojection_error = 5.0
+    o.bundle_adjustment = 1
+    for k, v in overrides.items():
+        if not hasattr(o, k):
+            raise AttributeError(f"tmi_ba_two_view_verification_options has no field {k!r}")
+        setattr(o, k, v)
+    return o
+
+
+class CTwoViewVerificationSummary(C.Structure):
+    """tmi_ba_two_view_verification_summary (batched two-view verification BA)."""
+    _fields_ = [
+        ("num_pairs", C.c_int64),
+        ("num_pairs_verified", C.c_int64),
+        ("num_pairs_too_few_matches", C.c_int64),
+        ("num_pairs_too_few_triangulated", C.c_int64),
+        ("num_pairs_failed_ba", C.c_int64),
+        ("num_pairs_too_few_verified", C.c_int64),
+        ("num_correspondences", C.c_int64),
+        ("num_verified", C.c_int64),
+        ("num_bad_triangulation_angles", C.c_int64),
+        ("num_failed_triangulations", C.c_int64),
+        ("num_bad_reprojection_errors", C.c_int64),
+        ("num_bad_final_reprojection_errors", C.c_int64),
+        ("total_iterations", C.c_int64),
+        ("seconds", C.c_double),
+        ("kernel_seconds", C.c_double),
+        ("triangulate_kernel_seconds", C.c_double),
+        ("solve_kernel_seconds", C.c_double),
+        ("accept_kernel_seconds", C.c_double),
+    ]
+
+
 class CTwoViewAngularBatch(C.Structure):
     _fields_ = [
         ("num_pairs", C.c_int32),

@@ -37,6 +37,7 @@
 #include "track_estimate_kernels.h"
 #include "inner_kernels.h"
 #include "two_view_kernels.h"
+#include "two_view_verify_kernels.h"
 #include "view_kernels.h"
 #include "select_kernels.h"
 #include "structure_gpu.h"
@@ -5001,10 +5002,10 @@ int32_t tmi_ba_adjust_two_views(tmi_ba_two_view_batch* Bh, int32_t point_dof, in
     rc = run_small_lm(s, s->stream, d, (size_t)P, nullptr, [&] {
       if (point_dof == 3)
         hipLaunchKernelGGL(two_view_lm_kernel<3>, dim3((P + 3) / 4), dim3(256), 0, s->stream, B, A, d.term, d.iters,
-                           d.c0, d.c1);
+                           d.c0, d.c1, (const long long*)nullptr);
       else
         hipLaunchKernelGGL(two_view_lm_kernel<4>, dim3((P + 3) / 4), dim3(256), 0, s->stream, B, A, d.term, d.iters,
-                           d.c0, d.c1);
+                           d.c0, d.c1, (const long long*)nullptr);
     }, ItemArrays{pair_termination, pair_iterations, pair_initial_cost, pair_final_cost}, sum, &sum->num_tracks, &term);
     if (rc) return rc;
     std::vector<double> e2((size_t)6 * P), k1((size_t)10 * P), k2((size_t)10 * P), pts((size_t)4 * N);
@@ -5019,6 +5020,207 @@ int32_t tmi_ba_adjust_two_views(tmi_ba_two_view_batch* Bh, int32_t point_dof, in
       Bh->intrinsics1[(size_t)10 * p] = k1[(size_t)10 * p];
       Bh->intrinsics2[(size_t)10 * p] = k2[(size_t)10 * p];
       for (int64_t q = Bh->correspondence_ptr[p]; q < Bh->correspondence_ptr[p + 1]; ++q)
+        for (int a = 0; a < 4; ++a) Bh->points[4 * q + a] = pts[4 * q + a];
+    }
+    return TMI_BA_OK;
+  }();
+  if (rc) g_last_error = s->error;
+  sum->seconds = now_s() - t0;
+  return rc;
+}
+
+// ---- batched two-view verification BA: triangulate, adjust, filter (two_view_verify_kernels.h) ----
+void tmi_ba_two_view_verification_options_init(tmi_ba_two_view_verification_options* o) {
+  if (!o) return;
+  o->min_num_inlier_matches = 30;
+  o->triangulation_max_reprojection_error = 15.0;
+  o->min_triangulation_angle_degrees = 4.0;
+  o->final_max_reprojection_error = 5.0;
+  o->bundle_adjustment = 1;
+}
+
+int32_t tmi_ba_verify_two_views(tmi_ba_two_view_batch* Bh, const tmi_ba_two_view_verification_options* vo,
+                                int32_t point_dof, int32_t max_num_iterations, int32_t device,
+                                int8_t* correspondence_status, int8_t* pair_status, int32_t* pair_num_verified,
+                                int8_t* pair_termination, int32_t* pair_iterations, double* pair_initial_cost,
+                                double* pair_final_cost, tmi_ba_two_view_verification_summary* sum) {
+  if (!Bh || !vo || !sum) return TMI_BA_ERR_INVALID_ARGUMENT;
+  memset(sum, 0, sizeof(*sum));
+  if ((point_dof != 3 && point_dof != 4) || Bh->num_pairs < 0 || max_num_iterations < 0 ||
+      vo->min_num_inlier_matches < 0)
+    return TMI_BA_ERR_INVALID_ARGUMENT;
+  const int P = Bh->num_pairs;
+  if (P > 0 && (!Bh->extrinsics1 || !Bh->extrinsics2 || !Bh->model1 || !Bh->model2 || !Bh->intrinsics1 ||
+                !Bh->intrinsics2 || !Bh->correspondence_ptr))
+    return TMI_BA_ERR_INVALID_ARGUMENT;
+  const double t0 = now_s();
+  const int64_t N = P ? Bh->correspondence_ptr[P] : 0;
+  if (P > 0 && Bh->correspondence_ptr[0] < 0) return TMI_BA_ERR_INVALID_ARGUMENT;
+  for (int p = 0; p < P; ++p) {
+    if (Bh->correspondence_ptr[p + 1] < Bh->correspondence_ptr[p] || Bh->model1[p] < 0 || Bh->model1[p] > 4 ||
+        Bh->model2[p] < 0 || Bh->model2[p] > 4)
+      return TMI_BA_ERR_INVALID_ARGUMENT;
+  }
+  if (N > 0 && (!Bh->features1 || !Bh->features2 || !Bh->points)) return TMI_BA_ERR_INVALID_ARGUMENT;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+    g_last_error = "no HIP device visible (the device path has no CPU fallback)";
+    return TMI_BA_ERR_NO_DEVICE;
+  }
+  if (device >= ndev) return TMI_BA_ERR_INVALID_ARGUMENT;
+  sum->num_pairs = P;
+  if (P == 0) return TMI_BA_OK;
+  OneShot sc;
+  OneShot* s = &sc;  // (TMI_HIP reports into s->error)
+  const int rc = [&]() -> int {
+    int rc = s->open(device);
+    if (rc) return rc;
+    std::vector<unsigned char> c1((size_t)P, 1), c2((size_t)P, 1);
+    if (Bh->constant_intrinsics1) c1.assign(Bh->constant_intrinsics1, Bh->constant_intrinsics1 + P);
+    if (Bh->constant_intrinsics2) c2.assign(Bh->constant_intrinsics2, Bh->constant_intrinsics2 + P);
+    TwoViewBatch B;  // the caller's correspondences: what the triangulation reads
+    memset(&B, 0, sizeof(B));
+    B.num_pairs = P;
+    double *d_e1, *d_f1, *d_f2;
+    int *d_m1, *d_m2;
+    unsigned char *d_c1, *d_c2;
+    long long* d_cptr;
+    const size_t Nn = (size_t)std::max<int64_t>(N, 1);
+    TMI_HIP(s->upload(&d_e1, Bh->extrinsics1, (size_t)6 * P));
+    TMI_HIP(s->upload(&B.ext2, (const double*)Bh->extrinsics2, (size_t)6 * P));
+    TMI_HIP(s->upload(&d_m1, Bh->model1, (size_t)P));
+    TMI_HIP(s->upload(&d_m2, Bh->model2, (size_t)P));
+    TMI_HIP(s->upload(&B.intr1, (const double*)Bh->intrinsics1, (size_t)10 * P));
+    TMI_HIP(s->upload(&B.intr2, (const double*)Bh->intrinsics2, (size_t)10 * P));
+    TMI_HIP(s->upload(&d_c1, (const unsigned char*)c1.data(), (size_t)P));
+    TMI_HIP(s->upload(&d_c2, (const unsigned char*)c2.data(), (size_t)P));
+    TMI_HIP(s->upload(&d_cptr, (const long long*)Bh->correspondence_ptr, (size_t)P + 1));
+    TMI_HIP(s->upload(&d_f1, Bh->features1, (size_t)2 * N));
+    TMI_HIP(s->upload(&d_f2, Bh->features2, (size_t)2 * N));
+    B.ext1 = d_e1; B.model1 = d_m1; B.model2 = d_m2; B.const1 = d_c1; B.const2 = d_c2; B.corr_ptr = d_cptr;
+    B.feat1 = d_f1; B.feat2 = d_f2;
+    TwoViewVerifyBuffers O;
+    TMI_HIP(s->alloc(&O.feat1_c, 2 * Nn));
+    TMI_HIP(s->alloc(&O.feat2_c, 2 * Nn));
+    TMI_HIP(s->alloc(&O.points_c, 4 * Nn));
+    TMI_HIP(s->alloc(&O.orig, Nn));
+    TMI_HIP(s->alloc(&O.corr_end, (size_t)P));
+    TMI_HIP(s->alloc(&O.points_out, 4 * Nn));
+    TMI_HIP(s->alloc(&O.corr_status, Nn));
+    TMI_HIP(s->alloc(&O.pair_status, (size_t)P));
+    TMI_HIP(s->alloc(&O.pair_count, (size_t)P));
+    TMI_HIP(hipMemsetAsync(O.corr_status, 0xff, Nn, s->stream));
+    TwoViewBatch C = B;  // the compacted survivors: what the solve and the last filter read
+    C.feat1 = O.feat1_c;
+    C.feat2 = O.feat2_c;
+    C.points = O.points_c;
+    TMI_HIP(s->alloc(&C.points_c, 4 * Nn));
+    TMI_HIP(s->alloc(&C.scale_p, 4 * Nn));
+    SmallLmOut d;
+    if ((rc = s->alloc_outputs(&d, (size_t)P))) return rc;
+    const SmallLmArgs L = ceres_default_lm_args(max_num_iterations, TMI_BA_LOSS_TRIVIAL, 0.0);
+    TwoViewArgs A;  // (as tmi_ba_adjust_two_views fills it)
+    A.point_dof = point_dof;
+    A.max_num_iterations = L.max_num_iterations;
+    A.jacobi_scaling = L.jacobi_scaling;
+    A.function_tolerance = L.function_tolerance;
+    A.gradient_tolerance = L.gradient_tolerance;
+    A.parameter_tolerance = L.parameter_tolerance;
+    A.initial_radius = L.initial_radius;
+    A.max_radius = L.max_radius;
+    A.min_radius = L.min_radius;
+    A.min_relative_decrease = L.min_relative_decrease;
+    A.lm_lo = L.lm_lo;
+    A.lm_hi = L.lm_hi;
+    A.max_num_consecutive_invalid_steps = L.max_num_consecutive_invalid_steps;
+    TwoViewVerifyArgs V;
+    V.min_matches = vo->min_num_inlier_matches;
+    V.cos_min = std::cos(vo->min_triangulation_angle_degrees * (M_PI / 180.0));
+    V.tri_max_sq = vo->triangulation_max_reprojection_error * vo->triangulation_max_reprojection_error;
+    V.final_max_sq = vo->final_max_reprojection_error * vo->final_max_reprojection_error;
+    const bool ba = vo->bundle_adjustment != 0;
+    // between the launches: the split of kernel_seconds (created last of all that can fail here; destroyed on every
+    // way out below)
+    hipEvent_t e_0 = nullptr, e_tri = nullptr, e_lm = nullptr;
+    {
+      hipError_t ee = hipEventCreate(&e_0);
+      if (ee == hipSuccess) ee = hipEventCreate(&e_tri);
+      if (ee == hipSuccess) ee = hipEventCreate(&e_lm);
+      if (ee != hipSuccess) {
+        if (e_0) hipEventDestroy(e_0);
+        if (e_tri) hipEventDestroy(e_tri);
+        TMI_HIP(ee);
+      }
+    }
+    tmi_ba_track_batch_summary lm_sum;
+    memset(&lm_sum, 0, sizeof(lm_sum));
+    int64_t num_solved = 0;
+    const dim3 grid((P + 3) / 4), block(256);
+    rc = run_small_lm(s, s->stream, d, (size_t)P, nullptr, [&] {
+      hipEventRecord(e_0, s->stream);
+      hipLaunchKernelGGL(two_view_triangulate_kernel, grid, block, 0, s->stream, B, V, O);
+      hipEventRecord(e_tri, s->stream);
+      if (!ba) return;
+      if (point_dof == 3)
+        hipLaunchKernelGGL(two_view_lm_kernel<3>, grid, block, 0, s->stream, C, A, d.term, d.iters, d.c0, d.c1,
+                           (const long long*)O.corr_end);
+      else
+        hipLaunchKernelGGL(two_view_lm_kernel<4>, grid, block, 0, s->stream, C, A, d.term, d.iters, d.c0, d.c1,
+                           (const long long*)O.corr_end);
+      hipEventRecord(e_lm, s->stream);
+      hipLaunchKernelGGL(two_view_accept_kernel, grid, block, 0, s->stream, C, V, O, (const signed char*)d.term);
+    }, ItemArrays{pair_termination, pair_iterations, pair_initial_cost, pair_final_cost}, &lm_sum, &num_solved);
+    float ms_tri = 0.f, ms_lm = 0.f;
+    if (rc == TMI_BA_OK) {
+      hipEventElapsedTime(&ms_tri, e_0, e_tri);
+      if (ba) hipEventElapsedTime(&ms_lm, e_tri, e_lm);
+    }
+    hipEventDestroy(e_0);
+    hipEventDestroy(e_tri);
+    hipEventDestroy(e_lm);
+    if (rc) return rc;
+    sum->kernel_seconds = lm_sum.kernel_seconds;
+    sum->triangulate_kernel_seconds = 1e-3 * ms_tri;
+    sum->solve_kernel_seconds = 1e-3 * ms_lm;
+    sum->accept_kernel_seconds = ba ? std::max(0.0, sum->kernel_seconds - 1e-3 * (ms_tri + ms_lm)) : 0.0;
+    sum->total_iterations = lm_sum.total_iterations;
+    std::vector<double> e2((size_t)6 * P), k1((size_t)10 * P), k2((size_t)10 * P), pts((size_t)4 * N);
+    std::vector<signed char> cst((size_t)N), pst((size_t)P);
+    std::vector<int> cnt((size_t)P);
+    TMI_HIP(hipMemcpyAsync(e2.data(), B.ext2, e2.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    TMI_HIP(hipMemcpyAsync(k1.data(), B.intr1, k1.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    TMI_HIP(hipMemcpyAsync(k2.data(), B.intr2, k2.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    TMI_HIP(hipMemcpyAsync(pst.data(), O.pair_status, (size_t)P, hipMemcpyDeviceToHost, s->stream));
+    TMI_HIP(hipMemcpyAsync(cnt.data(), O.pair_count, (size_t)P * sizeof(int), hipMemcpyDeviceToHost, s->stream));
+    if (N) {
+      TMI_HIP(hipMemcpyAsync(pts.data(), O.points_out, pts.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+      TMI_HIP(hipMemcpyAsync(cst.data(), O.corr_status, (size_t)N, hipMemcpyDeviceToHost, s->stream));
+    }
+    TMI_HIP(hipStreamSynchronize(s->stream));
+    int64_t* const pair_counter[5] = {&sum->num_pairs_verified, &sum->num_pairs_too_few_matches,
+                                      &sum->num_pairs_too_few_triangulated, &sum->num_pairs_failed_ba,
+                                      &sum->num_pairs_too_few_verified};
+    int64_t* const corr_counter[5] = {&sum->num_verified, &sum->num_bad_triangulation_angles,
+                                      &sum->num_failed_triangulations, &sum->num_bad_reprojection_errors,
+                                      &sum->num_bad_final_reprojection_errors};
+    for (int p = 0; p < P; ++p) {
+      const int st = pst[p];
+      ++*pair_counter[st];
+      if (pair_status) pair_status[p] = (int8_t)st;
+      if (pair_num_verified) pair_num_verified[p] = cnt[p];
+      if (ba && (st == 0 || st == 4)) {  // :316-321 run before the last test of VerifyMatches
+        for (int a = 0; a < 6; ++a) Bh->extrinsics2[(size_t)6 * p + a] = e2[(size_t)6 * p + a];
+        Bh->intrinsics1[(size_t)10 * p] = k1[(size_t)10 * p];
+        Bh->intrinsics2[(size_t)10 * p] = k2[(size_t)10 * p];
+      }
+    }
+    for (int64_t q = 0; q < N; ++q) {
+      const int st = cst[q];
+      if (correspondence_status) correspondence_status[q] = (int8_t)st;
+      if (st < 0) continue;
+      ++sum->num_correspondences;
+      ++*corr_counter[st];
+      if (st == 0 || st == 4)
         for (int a = 0; a < 4; ++a) Bh->points[4 * q + a] = pts[4 * q + a];
     }
     return TMI_BA_OK;

@@ -135,6 +135,78 @@ __device__ __forceinline__ void pixel_to_camera(int model, const double* K, cons
   pt[2] = 1.0;
 }
 
+// Camera::PixelToUnitDepthRay(pixel).normalized() (camera.cc:215-223): R^T PixelToCameraCoordinates(pixel), R
+// column-major as angle_axis_to_rotation_matrix writes it, normalized as Eigen's normalized() does (divided by the
+// norm when the squared norm is positive).
+__device__ __forceinline__ void pixel_unit_ray(int model, const double* K, const double R[9], const double px[2],
+                                               double r[3]) {
+  double u[3];
+  pixel_to_camera(model, K, px, u);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) r[c] = R[3 * c] * u[0] + R[3 * c + 1] * u[1] + R[3 * c + 2] * u[2];  // R^T u
+  const double n2 = r[0] * r[0] + r[1] * r[1] + r[2] * r[2];
+  if (n2 > 0.0) {
+    const double n = sqrt(n2);
+    r[0] /= n;
+    r[1] /= n;
+    r[2] /= n;
+  }
+}
+
+// One ray of TriangulateMidpoint (triangulation.cc:130-157): A += I - d d^T (lower triangle 00 10 11 20 21 22),
+// b += (I - d d^T) o.  The w row of the 4 x 4 homogeneous form (d_w = 0) adds 1 to A_ww and b_w: the ray count.
+__device__ __forceinline__ void midpoint_accumulate(const double d[3], const double o[3], double A[6], double b[3]) {
+  double T[3][3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) T[r][c] = (r == c ? 1.0 : 0.0) - d[r] * d[c];
+  A[0] += T[0][0];
+  A[1] += T[1][0];
+  A[2] += T[1][1];
+  A[3] += T[2][0];
+  A[4] += T[2][1];
+  A[5] += T[2][2];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) b[r] += T[r][0] * o[0] + T[r][1] * o[1] + T[r][2] * o[2];
+}
+
+// The solve of TriangulateMidpoint over n rays: Eigen's unblocked LLT of [[A, 0], [0, n]] in its column order
+// (LLT.h llt_inplace::unblocked: pivot x = A_kk - |L_k,0:k|^2, failure where x <= 0) and the two triangular solves.
+// A_w* = 0 and A_ww = n, so w = (n / sqrt n) / sqrt n: 1 up to round-off, as in the reference.  False: the LLT failed.
+__device__ __forceinline__ bool midpoint_solve(const double A[6], const double b[3], double n, double X[4]) {
+  double L00, L10, L11, L20, L21, L22, L33;
+  bool ok = true;
+  {
+    double x = A[0];
+    if (x <= 0.0) ok = false;
+    L00 = sqrt(x);
+    L10 = A[1] / L00;
+    L20 = A[3] / L00;
+    x = A[2] - L10 * L10;
+    if (x <= 0.0) ok = false;
+    L11 = sqrt(x);
+    L21 = (A[4] - L20 * L10) / L11;
+    x = A[5] - (L20 * L20 + L21 * L21);
+    if (x <= 0.0) ok = false;
+    L22 = sqrt(x);
+    x = n;  // row w of L below the 3 x 3 block is zero
+    if (x <= 0.0) ok = false;
+    L33 = sqrt(x);
+  }
+  if (!ok) return false;
+  // L y = b, L^T X = y
+  const double y0 = b[0] / L00;
+  const double y1 = (b[1] - y0 * L10) / L11;
+  const double y2 = (b[2] - y0 * L20 - y1 * L21) / L22;
+  const double y3 = n / L33;
+  X[3] = y3 / L33;
+  X[2] = y2 / L22;
+  X[1] = (y1 - L21 * X[2]) / L11;
+  X[0] = (y0 - (L10 * X[1] + L20 * X[2])) / L00;
+  return true;
+}
+
 // attempt[lp]: the caller's mask on the padded track order (constant points are skipped here).
 __device__ __forceinline__ bool track_attempted(const DeviceView& v, const unsigned char* __restrict__ attempt, int lp) {
   return attempt[lp] != 0 && !v.pt_const[lp];
@@ -159,18 +231,8 @@ __global__ __launch_bounds__(256) void track_rays_kernel(DeviceView v, const uns
     double R[9];
     angle_axis_to_rotation_matrix(aa, R);
     const double px[2] = {v.obs_xy[2 * e], v.obs_xy[2 * e + 1]};
-    double u[3];
-    pixel_to_camera(rec.x, Kv, px, u);
     double r[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) r[c] = R[3 * c] * u[0] + R[3 * c + 1] * u[1] + R[3 * c + 2] * u[2];  // R^T u
-    const double n2 = r[0] * r[0] + r[1] * r[1] + r[2] * r[2];
-    if (n2 > 0.0) {
-      const double n = sqrt(n2);
-      r[0] /= n;
-      r[1] /= n;
-      r[2] /= n;
-    }
+    pixel_unit_ray(rec.x, Kv, R, px, r);
     ray[3 * e] = r[0];
     ray[3 * e + 1] = r[1];
     ray[3 * e + 2] = r[2];
@@ -222,64 +284,23 @@ __global__ __launch_bounds__(256) void track_triangulate_kernel(DeviceView v, co
     const int cam = v.obs_cam[e];
     const double d[3] = {ray[3 * e], ray[3 * e + 1], ray[3 * e + 2]};
     const double o[3] = {v.ext[(size_t)cam * 6], v.ext[(size_t)cam * 6 + 1], v.ext[(size_t)cam * 6 + 2]};
-    double T[3][3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) T[r][c] = (r == c ? 1.0 : 0.0) - d[r] * d[c];
-    A[0] += T[0][0];
-    A[1] += T[1][0];
-    A[2] += T[1][1];
-    A[3] += T[2][0];
-    A[4] += T[2][1];
-    A[5] += T[2][2];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) b[r] += T[r][0] * o[0] + T[r][1] * o[1] + T[r][2] * o[2];
+    midpoint_accumulate(d, o, A, b);
   }
 #pragma unroll
   for (int i = 0; i < 6; ++i) A[i] = group_sum(A[i], tm.wide);
 #pragma unroll
   for (int i = 0; i < 3; ++i) b[i] = group_sum(b[i], tm.wide);
   if (!tm.leader) return;
-  const double n = (double)k;
-  // LLT of [[A, 0], [0, n]] in Eigen's column order
-  double L00, L10, L11, L20, L21, L22, L33;
-  bool ok = true;
-  {
-    double x = A[0];
-    if (x <= 0.0) ok = false;
-    L00 = sqrt(x);
-    L10 = A[1] / L00;
-    L20 = A[3] / L00;
-    x = A[2] - L10 * L10;
-    if (x <= 0.0) ok = false;
-    L11 = sqrt(x);
-    L21 = (A[4] - L20 * L10) / L11;
-    x = A[5] - (L20 * L20 + L21 * L21);
-    if (x <= 0.0) ok = false;
-    L22 = sqrt(x);
-    x = n;  // row w of L below the 3 x 3 block is zero
-    if (x <= 0.0) ok = false;
-    L33 = sqrt(x);
-  }
-  if (!ok) {
+  double X[4];
+  if (!midpoint_solve(A, b, (double)k, X)) {
     status[lp] = 2;
     return;
   }
-  // L y = b, L^T X = y
-  const double y0 = b[0] / L00;
-  const double y1 = (b[1] - y0 * L10) / L11;
-  const double y2 = (b[2] - y0 * L20 - y1 * L21) / L22;
-  const double y3 = n / L33;
-  const double X3 = y3 / L33;
-  const double X2 = y2 / L22;
-  const double X1 = (y1 - L21 * X2) / L11;
-  const double X0 = (y0 - (L10 * X1 + L20 * X2)) / L00;
   double* P = v.pts + (size_t)lp * 4;
-  P[0] = X0;
-  P[1] = X1;
-  P[2] = X2;
-  P[3] = X3;
+  P[0] = X[0];
+  P[1] = X[1];
+  P[2] = X[2];
+  P[3] = X[3];
   status[lp] = 0;
 }
 

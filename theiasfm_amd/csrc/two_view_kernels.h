@@ -135,6 +135,8 @@ __device__ __forceinline__ bool tv_jacobians(int model1, int model2, const doubl
 
 // termination[pair]: 0 CONVERGENCE, 1 NO_CONVERGENCE, 2 FAILURE, 3 evaluation failed at the start
 // point, -1 no correspondences.  Parameters are written back unless the code is 2 or 3.
+// corr_end (NULL: none): the end of every pair's range in place of corr_ptr[pair + 1] -- the compacted survivors of
+// two_view_triangulate_kernel (two_view_verify_kernels.h), corr_end[pair] == corr_ptr[pair] for a gated pair.
 // Not on small_lm.h's shared core: there a few solves end one rounding apart (the compiler fuses other multiply-adds),
 // and its argument types alone raise the scratch use of this register-bound kernel.
 template <int DP>
@@ -142,12 +144,15 @@ __global__ __launch_bounds__(256) void two_view_lm_kernel(TwoViewBatch B, TwoVie
                                                           signed char* __restrict__ termination,
                                                           int* __restrict__ iterations,
                                                           double* __restrict__ initial_cost,
-                                                          double* __restrict__ final_cost) {
+                                                          double* __restrict__ final_cost,
+                                                          const long long* __restrict__ corr_end) {
   constexpr int NC = kTvNC, NSC = sym_size(NC), NSP = sym_size(DP);
   const int lane = threadIdx.x & 63;
   const int pair = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (pair >= B.num_pairs) return;  // wave-uniform; no workgroup barrier below
-  const long long c0 = B.corr_ptr[pair], c1 = B.corr_ptr[pair + 1];
+  const long long c0 = B.corr_ptr[pair];
+  long long c1 = B.corr_ptr[pair + 1];
+  if (corr_end) c1 = corr_end[__builtin_amdgcn_readfirstlane(pair)];  // (a scalar load: no register of the solve's)
   if (c1 <= c0) {
     if (lane == 0) {
       termination[pair] = -1;

@@ -33,6 +33,7 @@ EXPORTS = (
     "tmi_ba_track_estimator_options_init", "tmi_ba_solver_estimate_tracks", "tmi_ba_estimate_tracks",
     "tmi_ba_solver_select_good_tracks", "tmi_ba_select_good_tracks",
     "tmi_ba_adjust_two_views", "tmi_ba_adjust_two_views_angular", "tmi_ba_optimize_relative_positions",
+    "tmi_ba_two_view_verification_options_init", "tmi_ba_verify_two_views",
     "tmi_ba_solver_structure_checksums",
     "tmi_ba_solver_operator_info",
 )
@@ -134,6 +135,13 @@ def load():
     L.tmi_ba_adjust_two_views.argtypes = [C.POINTER(abi.CTwoViewBatch), C.c_int32, C.c_int32, C.c_int32,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, TS]
     L.tmi_ba_adjust_two_views.restype = C.c_int32
+    VO, VSUM = C.POINTER(abi.CTwoViewVerificationOptions), C.POINTER(abi.CTwoViewVerificationSummary)
+    L.tmi_ba_two_view_verification_options_init.argtypes = [VO]
+    L.tmi_ba_two_view_verification_options_init.restype = None
+    L.tmi_ba_verify_two_views.argtypes = [C.POINTER(abi.CTwoViewBatch), VO, C.c_int32, C.c_int32, C.c_int32,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, VSUM]
+    L.tmi_ba_verify_two_views.restype = C.c_int32
     L.tmi_ba_adjust_two_views_angular.argtypes = [C.POINTER(abi.CTwoViewAngularBatch), C.c_int32, C.c_int32,
                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                   C.POINTER(abi.CTrackBatchSummary)]
@@ -321,6 +329,37 @@ def adjust_two_views(batch: abi.TwoViewBatch, point_dof: int = 4, max_num_iterat
     if st != 0:
         raise EngineError(st, "tmi_ba_adjust_two_views")
     return term, iters, c0, c1, ts
+
+
+def verify_two_views(batch: abi.TwoViewBatch, options: abi.CTwoViewVerificationOptions = None, point_dof: int = 4,
+                     max_num_iterations: int = 200, device: int = -1):
+    """Batched two-view verification BA (TwoViewMatchGeometricVerification::BundleAdjustRelativePose): triangulate,
+    adjust, filter.  batch.points is an output only; batch.extrinsics2 / focal lengths are updated in place for the
+    pairs of status 0 or 4, batch.points for the correspondences of status 0 or 4.  Returns a dict: correspondence_status
+    [N] int8, pair_status [P] int8, pair_num_verified [P] int32, termination [P] int8, iterations [P] int32,
+    initial_cost [P], final_cost [P], summary (CTwoViewVerificationSummary)."""
+    L = load()
+    if options is None:
+        options = abi.two_view_verification_options()
+    cb = batch.as_c()
+    n = batch.num_pairs
+    N = batch.features1.shape[0]
+    out = {
+        "correspondence_status": np.full(N, -1, dtype=np.int8),
+        "pair_status": np.full(n, -1, dtype=np.int8),
+        "pair_num_verified": np.zeros(n, dtype=np.int32),
+        "termination": np.full(n, -1, dtype=np.int8),
+        "iterations": np.zeros(n, dtype=np.int32),
+        "initial_cost": np.zeros(n),
+        "final_cost": np.zeros(n),
+    }
+    vs = abi.CTwoViewVerificationSummary()
+    st = L.tmi_ba_verify_two_views(C.byref(cb), C.byref(options), int(point_dof), int(max_num_iterations), int(device),
+                                   *[a.ctypes.data for a in out.values()], C.byref(vs))
+    if st != 0:
+        raise EngineError(st, "tmi_ba_verify_two_views")
+    out["summary"] = vs
+    return out
 
 
 def adjust_two_views_angular(batch: abi.TwoViewAngularBatch, max_num_iterations: int = 200, device: int = -1):

@@ -379,6 +379,26 @@ def config(name: str, **kw) -> Problem:
     return make_problem(nc, npt, nobs, seed=seeds[name], scene="ring", **kw)
 
 
+def _model_intrinsics(model, f) -> np.ndarray:
+    """[n, 10] zero padded intrinsics of cameras with focal lengths f, principal point (500, 400) and a mild
+    distortion in each of the five models."""
+    K = np.zeros((len(model), abi.MAX_INTRINSICS))
+    for p, m in enumerate(model):
+        if m in (abi.PINHOLE, abi.PINHOLE_RADIAL_TANGENTIAL, abi.FISHEYE):
+            K[p, :5] = [f[p], 1.0, 0.0, 500.0, 400.0]
+            if m == abi.PINHOLE:
+                K[p, 5:7] = [-0.05, 0.01]
+            elif m == abi.PINHOLE_RADIAL_TANGENTIAL:
+                K[p, 5:10] = [-0.05, 0.01, 0.001, 1e-3, -1e-3]
+            else:
+                K[p, 5:9] = [-0.02, 0.003, 0.0, 0.0]
+        elif m == abi.FOV:
+            K[p, :5] = [f[p], 1.0, 500.0, 400.0, 0.2]
+        else:
+            K[p, :5] = [f[p], 1.0, 500.0, 400.0, -1e-7]
+    return K
+
+
 def make_two_view_batch(n_pairs: int, seed: int, *, min_corr: int = 30, max_corr: int = 400,
                         models=None, free_intrinsics: float = 0.0, pixel_noise: float = 0.5,
                         point_noise: float = 0.02) -> abi.TwoViewBatch:
@@ -404,23 +424,7 @@ def make_two_view_batch(n_pairs: int, seed: int, *, min_corr: int = 30, max_corr
             arr[:] = [models[int(np.searchsorted(edges, x))][0] for x in u]
 
     def intrinsics(model):
-        K = np.zeros((n_pairs, 10))
-        f = rng.uniform(600, 900, n_pairs)
-        for p in range(n_pairs):
-            m = model[p]
-            if m in (abi.PINHOLE, abi.PINHOLE_RADIAL_TANGENTIAL, abi.FISHEYE):
-                K[p, :5] = [f[p], 1.0, 0.0, 500.0, 400.0]
-                if m == abi.PINHOLE:
-                    K[p, 5:7] = [-0.05, 0.01]
-                elif m == abi.PINHOLE_RADIAL_TANGENTIAL:
-                    K[p, 5:10] = [-0.05, 0.01, 0.001, 1e-3, -1e-3]
-                else:
-                    K[p, 5:9] = [-0.02, 0.003, 0.0, 0.0]
-            elif m == abi.FOV:
-                K[p, :5] = [f[p], 1.0, 500.0, 400.0, 0.2]
-            else:
-                K[p, :5] = [f[p], 1.0, 500.0, 400.0, -1e-7]
-        return K
+        return _model_intrinsics(model, rng.uniform(600, 900, n_pairs))
 
     k1, k2 = intrinsics(m1), intrinsics(m2)
     X = np.concatenate([rng.uniform(-2, 2, (N, 2)), rng.uniform(4, 10, (N, 1)), np.ones((N, 1))], 1)
@@ -450,6 +454,113 @@ def make_two_view_batch(n_pairs: int, seed: int, *, min_corr: int = 30, max_corr
     k1_0[free, 0] *= 1.01
     k2_0[free, 0] *= 0.99
     return abi.TwoViewBatch(e1, e2_0, m1, m2, k1_0, k2_0, c1, c2, ptr, f1, f2, pts)
+
+
+VERIFICATION_ROLES = ("gate1_min", "gate1_below", "gate1_tiny", "gate2", "gate2", "end_min", "end_min_plus_1",
+                      "n63", "n64", "n65", "long", "long")
+
+
+def make_two_view_verification_batch(n_pairs: int, seed: int, *, min_matches: int = 30, min_corr: int = 40,
+                                     max_corr: int = 400, models=None, free_intrinsics: float = 0.0,
+                                     pixel_noise: float = 0.5, outlier_fraction: float = 0.2, roles: bool = True,
+                                     counts=None):
+    """Seeded view pairs as TwoViewMatchGeometricVerification::VerifyMatches has them when it reaches
+    BundleAdjustRelativePose (two_view_match_geometric_verification.cc:171-176): the two cameras of the estimated
+    TwoViewInfo (camera 1 at the origin, camera 2 a baseline away, its pose a little off the truth) and the pair's
+    correspondences in pixels.  The geometry is make_two_view_batch's; batch.points is zero (an output).
+
+    Of every ordinary pair's correspondences a fraction outlier_fraction is, in equal parts, kind
+      1  a gross mismatch (feature 2 anywhere in the image),
+      2  a far point (60-100 units away: below the triangulation angle),
+      3  a point behind both cameras,
+      4  a near miss (feature 2 off by 12-24 pixels);
+    kind 0 is an inlier with Gaussian pixel_noise.  roles: the first pairs (as many of VERIFICATION_ROLES as fit) are
+      gate1_*         min_matches, min_matches - 1 and 3 correspondences: at or under the input gate,
+      gate2           over the input gate, but most of it far points: under the gate after the triangulation,
+      end_min, end_min_plus_1   exactly min_matches / min_matches + 1 clean inliers (pixel noise 0.05) among far points,
+      n63, n64, n65   that many correspondences,
+      long            500-900 correspondences.
+    counts: the correspondences of every pair (overrides the sizes of the ordinary pairs and of n63 / n64 / n65 / long).
+    Returns (batch, truth): truth["extrinsics2"] [P, 6] the generating pose, truth["kind"] [N], truth["role"] [P] (""
+    for an ordinary pair), truth["points"] [N, 4]."""
+    rng = np.random.default_rng(seed)
+    role = [VERIFICATION_ROLES[p] if roles and p < len(VERIFICATION_ROLES) else "" for p in range(n_pairs)]
+    n = rng.integers(min_corr, max_corr + 1, n_pairs)
+    fixed = {"n63": 63, "n64": 64, "n65": 65}
+    for p, r in enumerate(role):
+        if r in fixed:
+            n[p] = fixed[r]
+        elif r == "long":
+            n[p] = rng.integers(500, 901)
+    if counts is not None:
+        n = np.asarray(counts, dtype=np.int64).copy()
+    kinds = []
+    for p, r in enumerate(role):
+        if r.startswith("gate1"):
+            k = np.zeros({"gate1_min": min_matches, "gate1_below": max(min_matches - 1, 0), "gate1_tiny": 3}[r], int)
+        elif r == "gate2":
+            k = np.concatenate([np.zeros(max(min_matches - 5, 0), int), np.full(20, 2)])
+        elif r.startswith("end_min"):
+            k = np.concatenate([np.zeros(min_matches + (r == "end_min_plus_1"), int), np.full(9, 2)])
+        else:
+            k = np.zeros(int(n[p]), int)
+            bad = rng.random(k.size) < outlier_fraction
+            k[bad] = rng.integers(1, 5, int(bad.sum()))
+        if r.startswith(("gate2", "end_min")):
+            k = k[rng.permutation(k.size)]
+        kinds.append(k)
+    counts = np.array([k.size for k in kinds], dtype=np.int64)
+    ptr = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    kind = np.concatenate(kinds) if kinds else np.zeros(0, int)
+    N = int(ptr[-1])
+    e1 = np.zeros((n_pairs, 6))
+    e2 = np.zeros((n_pairs, 6))
+    e2[:, :3] = rng.uniform(-1, 1, (n_pairs, 3)) * [0.3, 0.15, 0.15] + [1.2, 0, 0]
+    e2[:, 3:] = 0.1 * rng.normal(size=(n_pairs, 3))
+    m1 = np.zeros(n_pairs, np.int32)
+    m2 = np.zeros(n_pairs, np.int32)
+    if models:
+        edges = np.cumsum([fr for _, fr in models])
+        for arr in (m1, m2):
+            u = rng.random(n_pairs) * edges[-1]
+            arr[:] = [models[int(np.searchsorted(edges, x))][0] for x in u]
+    k1 = _model_intrinsics(m1, rng.uniform(600, 900, n_pairs))
+    k2 = _model_intrinsics(m2, rng.uniform(600, 900, n_pairs))
+    depth = rng.uniform(4, 8, N)
+    depth[kind == 2] = rng.uniform(60, 100, int((kind == 2).sum()))
+    depth[kind == 3] = -rng.uniform(4, 8, int((kind == 3).sum()))
+    X = np.concatenate([rng.uniform(-0.25, 0.25, (N, 2)) * np.abs(depth)[:, None] + [[0.6, 0.0]], depth[:, None],
+                        np.ones((N, 1))], 1)
+    pair_of = np.repeat(np.arange(n_pairs), counts)
+
+    def proj(ext, model, K):
+        Rm = Rotation.from_rotvec(ext[pair_of, 3:6]).as_matrix()
+        q = np.einsum("nij,nj->ni", Rm, X[:, :3] - ext[pair_of, :3])
+        out = np.empty((N, 2))
+        for m in np.unique(model):
+            sel = np.nonzero(model[pair_of] == m)[0]
+            out[sel] = _distort(int(m), K[pair_of[sel], :abi.INTRINSICS_SIZE[m]], q[sel])
+        return out
+
+    clean = np.array([r.startswith("end_min") for r in role], dtype=bool)
+    sigma = np.where(clean[pair_of], 0.05, pixel_noise)[:, None] if N else np.zeros((0, 1))
+    f1 = proj(e1, m1, k1) + sigma * rng.normal(size=(N, 2))
+    f2 = proj(e2, m2, k2) + sigma * rng.normal(size=(N, 2))
+    gross = kind == 1
+    f2[gross] = rng.uniform([100.0, 50.0], [900.0, 750.0], (int(gross.sum()), 2))
+    near = kind == 4
+    phi = rng.uniform(0, 2 * np.pi, int(near.sum()))
+    f2[near] += rng.uniform(12, 24, int(near.sum()))[:, None] * np.stack([np.cos(phi), np.sin(phi)], 1)
+    e2_0 = e2.copy()
+    e2_0[:, :3] += 0.01 * rng.normal(size=(n_pairs, 3))
+    e2_0[:, 3:] += 0.002 * rng.normal(size=(n_pairs, 3))
+    free = rng.random(n_pairs) < free_intrinsics
+    c1 = np.where(free, 0, 1).astype(np.uint8)
+    c2 = np.where(free, 0, 1).astype(np.uint8)
+    k1[free, 0] *= 1.005
+    k2[free, 0] *= 0.995
+    batch = abi.TwoViewBatch(e1, e2_0, m1, m2, k1, k2, c1, c2, ptr, f1, f2, np.zeros((N, 4)))
+    return batch, {"extrinsics2": e2, "kind": kind, "role": role, "points": X}
 
 
 def make_two_view_angular_batch(n_pairs: int, seed: int, *, min_corr: int = 30, max_corr: int = 300,
@@ -511,21 +622,7 @@ def make_relative_position_batch(n_pairs: int, seed: int, *, min_corr: int = 30,
         u = rng.random(V) * edges[-1]
         model[:] = [models[int(np.searchsorted(edges, x))][0] for x in u]
     f = rng.uniform(600, 900, V)
-    K = np.zeros((V, abi.MAX_INTRINSICS))
-    for v in range(V):
-        m = model[v]
-        if m in (abi.PINHOLE, abi.PINHOLE_RADIAL_TANGENTIAL, abi.FISHEYE):
-            K[v, :5] = [f[v], 1.0, 0.0, 500.0, 400.0]
-            if m == abi.PINHOLE:
-                K[v, 5:7] = [-0.05, 0.01]
-            elif m == abi.PINHOLE_RADIAL_TANGENTIAL:
-                K[v, 5:10] = [-0.05, 0.01, 0.001, 1e-3, -1e-3]
-            else:
-                K[v, 5:9] = [-0.02, 0.003, 0.0, 0.0]
-        elif m == abi.FOV:
-            K[v, :5] = [f[v], 1.0, 500.0, 400.0, 0.2]
-        else:
-            K[v, :5] = [f[v], 1.0, 500.0, 400.0, -1e-7]
+    K = _model_intrinsics(model, f)
     if counts is None:
         counts = rng.integers(min_corr, max_corr + 1, n_pairs)
     counts = np.asarray(counts, dtype=np.int64)
