@@ -177,6 +177,30 @@ struct DeviceView {
   int* pcg_done;    // set by pcg_step once PCG has stopped: pcg_p, enqueued behind it, returns at once
 };
 
+// The buffers of DeviceView that the COMPACT linearize writes and a later kernel of the same linearisation reads
+// (point_eliminate with sums_ready, the one-sweep product, back_substitute; DESIGN.md section 3 has the table).  The
+// engine keeps a second set so that the candidate of a trial step can be linearised while the current linearisation
+// stays intact (engine.hip, speculative linearisation): accepting the step swaps the pointers of the two sets, and
+// DeviceView::compact / sums_ready travel with them.  pm_A of the second set holds the compact planes only (4 per
+// observation), so a full-plane linearize always goes to the first set.
+struct LinearisationSet {
+  double* pm_r;
+  double* pm_A;
+  double* pm_Jp;
+  double* cp_trk;
+  double* Vraw;
+  double* gp;
+};
+inline void swap_linearisation_set(DeviceView& v, LinearisationSet& o) {
+  double* t;
+  t = v.pm_r, v.pm_r = o.pm_r, o.pm_r = t;
+  t = v.pm_A, v.pm_A = o.pm_A, o.pm_A = t;
+  t = v.pm_Jp, v.pm_Jp = o.pm_Jp, o.pm_Jp = t;
+  t = v.cp_trk, v.cp_trk = o.cp_trk, o.cp_trk = t;
+  t = v.Vraw, v.Vraw = o.Vraw, o.Vraw = t;
+  t = v.gp, v.gp = o.gp, o.gp = t;
+}
+
 // host-visible copy of the device scalars (pinned, mapped, coherent memory): published by a
 // kernel with system-scope stores + a release store of `seq`, polled by the host
 struct HostMirror {

@@ -518,8 +518,16 @@ struct tmi_ba_solver {
   bool compact_robust = true; // TMI_BA_COMPACT_ROBUST=0: compact planes for the TRIVIAL loss only
   bool cost_by_view = false;   // ... and the trial cost view by view (every observation owns a slot)
   bool cost_warm = true;       // ... which also reads linearize's observation stream into the Infinity Cache (TMI_BA_COST_WARM=0: off)
+  // Speculative linearisation (solve): the candidate of a trial step is linearised into a second set of buffers
+  // instead of a trial-cost pass, and an accepted step swaps the sets (device_view.h, LinearisationSet).
+  // TMI_BA_SPECULATIVE_LINEARIZE=0: the trial cost and a linearize after acceptance, as before.  The second set is
+  // allocated at the first speculated step; spec_off: that failed, the old sequence for the life of the handle.
+  bool spec_env = true;
+  bool spec_ready = false, spec_off = false;
+  bool spec_swapped = false;  // DeviceView currently holds the second set (whose pm_A has room for compact planes only)
+  LinearisationSet spec_set = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   bool implicit = false;      // S is never formed (schur_mode)
-  bool adaptive = false;      // schur_mode auto on one rank: both operators are resident and every LM iteration
+  bool adaptive = false;     // schur_mode auto on one rank: both operators are resident and every LM iteration
                               // takes the cheaper one for the PCG length it expects (see solve)
   bool implicit_now = false;  // the operator of the current LM iteration
   bool y_records = false;     // point_eliminate writes Y records (shared blocks, or the older Schur kernels by env)
@@ -694,6 +702,37 @@ struct Timed {
     if (on && !attached) hipEventRecord(ev->b, s->stream);
   }
 };
+
+// Speculative linearisation: the first set of linearisation buffers back into the view (its pm_A has room for the full
+// planes) -- before every full-plane linearize.  What either set holds is stale afterwards: the caller linearizes next.
+void primary_linearisation_set(tmi_ba_solver* s) {
+  if (!s->spec_swapped) return;
+  swap_linearisation_set(s->v, s->spec_set);
+  s->spec_swapped = false;
+}
+// ... and the second set, allocated on first use.  false: there is none -- the allocation failed (the sticky HIP error is
+// cleared and the handle keeps the trial-cost sequence for its life, as the other optional buffers do: ppcg_off).
+bool ensure_speculative_set(tmi_ba_solver* s) {
+  if (s->spec_ready) return true;
+  if (s->spec_off) return false;
+  const size_t N = std::max<size_t>((size_t)s->st.No_pad, 1), NP = std::max<size_t>((size_t)s->st.Np_pad, 1);
+  const size_t DP = (size_t)s->DP, NS = (size_t)sym_size(s->DP);
+  // (pm_A: four planes -- [C p_n | r^2 .] of a robust loss, DeviceView::compact == 2; two are used otherwise)
+  const size_t n[6] = {2 * N, 4 * N, 2 * DP * N, 7 * NP, NS * NP, DP * NP};
+  double* p[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  for (int i = 0; i < 6; ++i) {
+    if (hipMalloc((void**)&p[i], n[i] * sizeof(double)) != hipSuccess) {
+      (void)hipGetLastError();
+      for (int j = 0; j < i; ++j) (void)hipFree(p[j]);
+      s->spec_off = true;
+      return false;
+    }
+  }
+  for (int i = 0; i < 6; ++i) s->allocs.push_back((void*)p[i]);
+  s->spec_set = LinearisationSet{p[0], p[1], p[2], p[3], p[4], p[5]};
+  s->spec_ready = true;
+  return true;
+}
 
 void select_mirror(tmi_ba_solver* s, int slot) {
   s->h_scal = s->h_mirror[slot].scal;
@@ -2281,6 +2320,8 @@ static int create_impl(tmi_ba_solver* s, const tmi_ba_problem* P, const tmi_ba_o
     s->fuse_sums = !(env && env[0] == '0');
     env = getenv("TMI_BA_COMPACT_ROBUST");
     s->compact_robust = !(env && env[0] == '0');
+    env = getenv("TMI_BA_SPECULATIVE_LINEARIZE");
+    s->spec_env = !(env && env[0] == '0');
   }
   v.direct_diag = 0;
   {
@@ -3368,11 +3409,20 @@ int32_t tmi_ba_solver_solve(tmi_ba_solver* s, const tmi_ba_options* O, tmi_ba_su
     }
   }
   int last_pcg_len = 0;  // PCG iterations of the previous LM iteration (0: none yet)
+  // DeviceView::compact of a linearize enqueued now
+  auto compact_now = [&](bool full_planes) {
+    return (!full_planes && compact_possible && (s->implicit || (s->adaptive && last_pcg_len <= s->adaptive_break_even)))
+               ? (lt == 0 ? 1 : 2)  // (2: a robust loss -- the planes hold the corrected point and r^2)
+               : 0;
+  };
+  // (a second solve on the handle starts on the first set of linearisation buffers, like a fresh one: every plane is
+  //  rewritten before it is read)
+  primary_linearisation_set(s);
   auto linearize = [&](bool norms_only = false, bool full_planes = false) {
-    if (!norms_only)
-      v.compact = (!full_planes && compact_possible && (s->implicit || (s->adaptive && last_pcg_len <= s->adaptive_break_even)))
-                      ? (lt == 0 ? 1 : 2)  // (2: a robust loss -- the planes hold the corrected point and r^2)
-                      : 0;
+    if (!norms_only) {
+      v.compact = compact_now(full_planes);
+      if (!v.compact) primary_linearisation_set(s);  // (the second set's pm_A holds compact planes only)
+    }
     if (!norms_only) v.sums_ready = (v.compact && s->fuse_sums) ? 1 : 0;  // (the compact instantiation also leaves V and g_p)
     // cost and sum of squares land in d_sc[0..1] (finished by the kernel's last workgroup)
     Timed t(s, TMI_BA_K_LINEARIZE);
@@ -3497,6 +3547,7 @@ int32_t tmi_ba_solver_solve(tmi_ba_solver* s, const tmi_ba_options* O, tmi_ba_su
   bool need_gradient_check = true;  // after the first build and after every accepted step
   bool inner_enabled = O->use_inner_iterations != 0;
   bool time_up = false;
+  bool prev_step_ok = true;  // the previous trial step of this solve was accepted (or there was none): see the speculation below
 
   for (;;) {
     if (iter >= O->max_num_iterations) break;
@@ -3644,6 +3695,7 @@ int32_t tmi_ba_solver_solve(tmi_ba_solver* s, const tmi_ba_options* O, tmi_ba_su
     double model_cost_change = 0.0, step_sq = 0.0, cand_cost = 0.0, cand_ss = 0.0;
     double cand_xc_sq = 0.0, cand_xp_sq = 0.0;
     bool cand_invalid = false;
+    int spec_compact = 0;  // != 0: the candidate was linearised into the second set (DeviceView::compact of that set)
     if (usable) {
       {
         // candidate cameras + their prepared records (+ the scaled copy of y_c back_substitute gathers: first)
@@ -3655,10 +3707,35 @@ int32_t tmi_ba_solver_solve(tmi_ba_solver* s, const tmi_ba_options* O, tmi_ba_su
         Timed t(s, TMI_BA_K_BACK_SUBSTITUTE);
         s->launch.back_substitute(v, stream, nbs, v.partial, d_sc + 0);
       }
-      {
+      // d_sc: [mcc, step_sq_points, |x+|^2 points, cand_cost, cand_ss, invalid votes, singular
+      //        track votes, time-limit votes]
+      // Speculative linearisation.  An accepted step is linearised at the very point its trial cost was taken at, and
+      // linearize sums the same residuals (track by track instead of view by view): where the next linearisation is a
+      // compact one the candidate is linearised NOW, into the second set of buffers, and its cost, sum of squares and
+      // invalid vote go where the trial cost leaves them; acceptance swaps the sets.  Not in a solve with inner iterations
+      // (the sweep moves the candidate after the trial cost), and not right after a rejected or invalid step: a wasted
+      // linearize costs one linearize less one trial cost (~180 - ~90 us at Venice size), a hit saves one trial
+      // cost, so speculating pays above ~50 % acceptance -- and rejections come in runs.  Every rank decides alike
+      // (all-reduced scalars), so sharded solves speculate too.
+      spec_compact = 0;
+      if (s->spec_env && v.direct_diag && !O->use_inner_iterations && prev_step_ok) {
+        spec_compact = compact_now(false);
+        if (spec_compact && !ensure_speculative_set(s)) spec_compact = 0;
+      }
+      if (spec_compact) {
+        Timed t(s, TMI_BA_K_LINEARIZE);
+        DeviceView vs = v;  // the candidate's view: its points, the second set
+        LinearisationSet other = s->spec_set;
+        swap_linearisation_set(vs, other);
+        vs.pts = v.pts_c;
+        vs.compact = spec_compact;
+        vs.sums_ready = s->fuse_sums ? 1 : 0;
+        // linearize raises FL_INVALID where the trial cost counts a vote: cleared before, turned into d_sc[5] after
+        CKH(hipMemsetAsync(v.flags + FL_INVALID, 0, sizeof(int), stream));
+        s->launch.linearize(vs, stream, v.prep_c, lt, lw, nbs, d_sc + 3, 0);  // (writes d_sc[3..4] only)
+        hipLaunchKernelGGL(flag_to_scalar_kernel, dim3(1), dim3(64), 0, stream, v.flags + FL_INVALID, d_sc + 5);
+      } else {
         Timed t(s, TMI_BA_K_UPDATE_COST);
-        // d_sc: [mcc, step_sq_points, |x+|^2 points, cand_cost, cand_ss, invalid votes, singular
-        //        track votes, time-limit votes]
         trial_cost();
       }
       if (st.world > 1 && now_s() - t_start >= O->max_solver_time_in_seconds) {
@@ -3723,6 +3800,7 @@ int32_t tmi_ba_solver_solve(tmi_ba_solver* s, const tmi_ba_options* O, tmi_ba_su
       // HandleInvalidStep
       trace(-1.0, std::nan(""), model_cost_change, 0.0);
       sum->num_unsuccessful_steps++;
+      prev_step_ok = false;
       if (++invalid_run >= O->max_num_consecutive_invalid_steps) {
         termination = 2;
         why = "too many consecutive invalid steps";
@@ -3767,9 +3845,21 @@ int32_t tmi_ba_solver_solve(tmi_ba_solver* s, const tmi_ba_options* O, tmi_ba_su
       radius = radius / std::fmax(1.0 / 3.0, 1.0 - std::pow(2.0 * relative_decrease - 1.0, 3));
       radius = std::fmin(O->max_trust_region_radius, radius);
       decrease_factor = 2.0;
-      linearize();
+      if (spec_compact) {
+        // the candidate's linearisation is already there: the two sets change places (the old one is scratch now)
+        swap_linearisation_set(v, s->spec_set);
+        s->spec_swapped = !s->spec_swapped;
+        v.compact = spec_compact;
+        v.sums_ready = s->fuse_sums ? 1 : 0;
+      } else {
+        linearize();
+      }
+      prev_step_ok = true;
       need_gradient_check = true;
     } else {
+      // (a speculated linearisation is dropped: the current one is untouched, and the next iteration runs
+      //  point_eliminate and the rest on it with the new radius)
+      prev_step_ok = false;
       sum->num_unsuccessful_steps++;
       radius /= decrease_factor;
       decrease_factor *= 2.0;
@@ -5320,6 +5410,11 @@ int32_t tmi_ba_solver_operator_info(tmi_ba_solver* s, int32_t out[8]) {
   out[6] = ((s->st.has_shared || s->vis_clusters) && !s->cl_unavailable) ? 1 : 0;
   // the planes of the LAST linearisation are compact (device_view.h): p_n instead of the stored camera block
   out[7] = s->v.compact ? 1 : 0;
+  // bit 1: the handle may linearise the candidate of a trial step speculatively (solve): the switch is on, the second set
+  // of buffers has not failed to allocate, and the handle can run compact linearisations at all
+  if (s->spec_env && !s->spec_off && s->compact_env && s->v.drop_pos && s->v.uniform_pinhole_default && s->mf_ok && s->direct_ok &&
+      s->st.D == 9 && s->v.cp_trk != nullptr && !s->v.planes_fp32 && !s->cluster_blocks)
+    out[7] |= 2;
   return TMI_BA_OK;
 }
 
@@ -5344,6 +5439,7 @@ int32_t tmi_ba_solver_evaluate(tmi_ba_solver* s, double* residuals, double* jac_
   prepare_cameras(s, v.ext, v.intr, v.prep);
   hipLaunchKernelGGL(fill_kernel, dim3((unsigned)(((long long)st.Np_pad * DP + 255) / 256 + 1)), dim3(256), 0, stream, v.scale_p, (long long)st.Np_pad * DP, 1.0);
   // poison the residual planes so that invalid observations can be told apart
+  primary_linearisation_set(s);  // (the full planes: the set whose pm_A has room for them)
   {
     DeviceView ve = v;  // (the caller gets every column: stored, not formed from Jp)
     ve.drop_pos = 0;
