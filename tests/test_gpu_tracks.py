@@ -236,3 +236,67 @@ def test_select_then_partial_ba_on_resident_solver():
     with pytest.raises(lib.EngineError):
         s2.select_good_tracks(10, 100, 80)
     s2.close()
+
+
+@pytest.mark.parametrize("empty_views,dropped_view", [((), None), ((3, 11), 6)], ids=["all_views", "empty_and_masked"])
+def test_side_calls_share_one_resident_handle(empty_views, dropped_view):
+    """select -> adjust_views -> select -> filter on ONE handle: the selection's view/track index and the view
+    adjustment's view-major index are both cached on it, built in this order, and each is used again after the other
+    exists.  Every resident result is compared with the one-shot form of the same call on a copy of the same state:
+    selections, lengths, flags, terminations, iteration counts and counters are equal; statistics, means and costs to
+    1e-9 relative (the module's bound); the cameras at the bounds of test_gpu_adjust_views.py's check().  The second
+    case has two views without observations and a view_mask that drops a third: empty ranges in both view pointers."""
+    P = synth.make_problem(12, 600, 3000, seed=7, scene="ring", spread=0.4)
+    mask = None
+    if empty_views:
+        keep = ~np.isin(P.obs_camera, empty_views)
+        P.obs_camera, P.obs_point, P.obs_xy = P.obs_camera[keep], P.obs_point[keep], P.obs_xy[keep]
+        mask = np.ones(P.num_cameras, np.uint8)
+        mask[dropped_view] = 0
+    opts = abi.default_options(point_dof=3, linear_solver_type=abi.DENSE_QR, use_inner_iterations=0)
+    sel_args = (10, 100, 40)
+
+    def same_selection(res, one):
+        np.testing.assert_array_equal(res[0], one[0])
+        np.testing.assert_array_equal(res[1], one[1])
+        np.testing.assert_allclose(res[2], one[2], rtol=1e-9, atol=1e-12)
+        assert (res[3].num_tracks, res[3].num_selected_grid, res[3].num_selected) == \
+            (one[3].num_tracks, one[3].num_selected_grid, one[3].num_selected)
+        assert 0 < res[0].sum() < P.num_points
+
+    S = lib.Solver(P.copy(), opts)
+    first = S.select_good_tracks(*sel_args, view_mask=mask)
+    same_selection(first, lib.select_good_tracks(P, *sel_args, view_mask=mask))
+
+    views = S.adjust_views(opts, mask)
+    Pv = P.copy()
+    views_one = lib.adjust_views(Pv, opts, mask)
+    state = S.download().copy()
+    np.testing.assert_array_equal(views[0], views_one[0])
+    np.testing.assert_array_equal(views[1], views_one[1])
+    np.testing.assert_allclose(views[2], views_one[2], rtol=1e-9, atol=0)
+    np.testing.assert_allclose(views[3], views_one[3], rtol=1e-9, atol=0)
+    assert (views[4].num_views, views[4].num_chains) == (views_one[4].num_views, views_one[4].num_chains)
+    assert 0 < views[4].num_views == (views[0] >= 0).sum()
+    for c in empty_views + (() if dropped_view is None else (dropped_view,)):
+        assert views[0][c] == -1
+        np.testing.assert_array_equal(state.extrinsics[c], P.extrinsics[c])
+    scale = float(np.abs(Pv.extrinsics[:, :3]).max())
+    np.testing.assert_allclose(state.extrinsics, Pv.extrinsics, rtol=0, atol=1e-8 * scale)
+    np.testing.assert_allclose(state.intrinsics, Pv.intrinsics, rtol=1e-8, atol=1e-10)
+
+    second = S.select_good_tracks(*sel_args, view_mask=mask)
+    same_selection(second, lib.select_good_tracks(state, *sel_args, view_mask=mask))
+    np.testing.assert_array_equal(second[1], first[1])  # the lengths do not depend on the cameras
+    if np.array_equal(second[2], first[2], equal_nan=True):
+        np.testing.assert_array_equal(second[0], first[0])
+
+    flag, mean, fs = S.filter_outlier_tracks(4.0, 2.0)
+    flag_o, mean_o, fs_o = lib.filter_outlier_tracks(state, 4.0, 2.0)
+    S.close()
+    np.testing.assert_array_equal(flag, flag_o)
+    assert (fs.num_estimated_tracks, fs.num_bad_reprojections, fs.num_insufficient_viewing_angles) == \
+        (fs_o.num_estimated_tracks, fs_o.num_bad_reprojections, fs_o.num_insufficient_viewing_angles)
+    live = (flag_o != 1) & np.isfinite(mean_o)
+    np.testing.assert_allclose(mean[live], mean_o[live], rtol=1e-9, atol=1e-12)
+    assert np.array_equal(np.isnan(mean[flag_o != 1]), np.isnan(mean_o[flag_o != 1]))

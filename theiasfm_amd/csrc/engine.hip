@@ -633,6 +633,7 @@ struct tmi_ba_solver {
   long long* d_vt_ptr = nullptr;          // [Nc + 1]
   unsigned char* d_view_mask = nullptr;   // [Nc]
   int* d_vcount = nullptr;                // [2 Nc]: selected tracks per view after the grid phase | views needing a top-up
+  bool select_index_ready = false;        // d_vbox ... d_vcount all built (tmi_ba_solver_select_good_tracks)
   // device-built structure (structure_gpu.h): the big layout arrays exist in HBM only; host copies
   // are fetched on demand (inner iterations, tmi_ba_solver_evaluate)
   bool device_structure = false;
@@ -3915,1410 +3916,12 @@ int32_t tmi_ba_solve(tmi_ba_problem* P, const tmi_ba_options* O, tmi_ba_summary*
   return rc2;
 }
 
-// ---- one-shot calls and the batched small-problem solvers (small_lm.h) --------------------------
 }  // extern "C"
-namespace {
-// Device memory of one call, freed on every way out, and the stream it runs on: a stream of its own (open) or a
-// borrowed one.  error: what TMI_HIP reports.
-struct OneShot {
-  std::string error;
-  std::vector<void*> allocs;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
-  explicit OneShot(hipStream_t borrowed = nullptr) : stream(borrowed) {}
-  OneShot(const OneShot&) = delete;
-  OneShot& operator=(const OneShot&) = delete;
-  // a stream of its own on `device` (< 0: the current device)
-  int open(int device) {
-    OneShot* s = this;
-    if (device >= 0) TMI_HIP(hipSetDevice(device));
-    TMI_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-    own_stream = true;
-    return TMI_BA_OK;
-  }
-  template <class T>
-  hipError_t alloc(T** p, size_t n) {
-    *p = nullptr;
-    const hipError_t e = hipMalloc((void**)p, std::max<size_t>(n, 1) * sizeof(T));
-    if (e == hipSuccess) allocs.push_back((void*)*p);
-    return e;
-  }
-  template <class T>
-  hipError_t upload(T** p, const T* h, size_t n) {
-    hipError_t e = alloc(p, n);
-    if (e == hipSuccess && n) e = hipMemcpyAsync(*p, h, n * sizeof(T), hipMemcpyHostToDevice, stream);
-    return e;
-  }
-  // per-item outputs of a batched solve, preset to "nothing to solve" (-1, 0, 0, 0)
-  int alloc_outputs(SmallLmOut* o, size_t n) {
-    OneShot* s = this;
-    TMI_HIP(alloc(&o->term, n));
-    TMI_HIP(alloc(&o->iters, n));
-    TMI_HIP(alloc(&o->c0, n));
-    TMI_HIP(alloc(&o->c1, n));
-    n = std::max<size_t>(n, 1);
-    TMI_HIP(hipMemsetAsync(o->term, 0xff, n, stream));
-    TMI_HIP(hipMemsetAsync(o->iters, 0, n * sizeof(int), stream));
-    TMI_HIP(hipMemsetAsync(o->c0, 0, n * sizeof(double), stream));
-    TMI_HIP(hipMemsetAsync(o->c1, 0, n * sizeof(double), stream));
-    return TMI_BA_OK;
-  }
-  ~OneShot() {
-    if (own_stream) hipStreamDestroy(stream);
-    for (void* p : allocs) hipFree(p);
-  }
-};
 
-// The caller's per-item arrays (each may be null).
-struct ItemArrays {
-  int8_t* term;
-  int32_t* iters;
-  double* c0;
-  double* c1;
-};
+// ---- one-shot calls and the batched small-problem solvers -----------------------------------------
+#include "side_calls.h"
 
-// One batched small-problem solve: launch() queues it on `stream` between two events (sum->kernel_seconds), then the n
-// per-item outputs d are read back, counted (*num_items: termination >= 0; successes 0 and 1) and item i is written to
-// the caller's arrays at map[i] (null: the identity; map[i] < 0: padding).  term_h (optional): the terminations.
-// TMI_HIP reports into s->error.
-template <class Holder, class Sum, class Launch>
-int run_small_lm(Holder* s, hipStream_t stream, const SmallLmOut& d, size_t n, const int* map, Launch launch,
-                 const ItemArrays& out, Sum* sum, int64_t* num_items, std::vector<signed char>* term_h = nullptr) {
-  hipEvent_t ea, eb;
-  TMI_HIP(hipEventCreate(&ea));
-  TMI_HIP(hipEventCreate(&eb));
-  hipEventRecord(ea, stream);
-  launch();
-  hipEventRecord(eb, stream);
-  const hipError_t le = hipGetLastError();
-  std::vector<signed char> term(n);
-  std::vector<int> iters(n);
-  std::vector<double> c0(out.c0 ? n : 0), c1(out.c1 ? n : 0);
-  hipError_t ce = hipSuccess;
-  if (n) {
-    ce = hipMemcpyAsync(term.data(), d.term, n, hipMemcpyDeviceToHost, stream);
-    if (ce == hipSuccess) ce = hipMemcpyAsync(iters.data(), d.iters, n * sizeof(int), hipMemcpyDeviceToHost, stream);
-    if (ce == hipSuccess && out.c0) ce = hipMemcpyAsync(c0.data(), d.c0, n * sizeof(double), hipMemcpyDeviceToHost, stream);
-    if (ce == hipSuccess && out.c1) ce = hipMemcpyAsync(c1.data(), d.c1, n * sizeof(double), hipMemcpyDeviceToHost, stream);
-  }
-  const hipError_t se = hipStreamSynchronize(stream);
-  float ms = 0.f;
-  hipEventElapsedTime(&ms, ea, eb);
-  hipEventDestroy(ea);
-  hipEventDestroy(eb);
-  TMI_HIP(le);
-  TMI_HIP(ce);
-  TMI_HIP(se);
-  for (size_t i = 0; i < n; ++i) {
-    const int p = map ? map[i] : (int)i;
-    if (p < 0) continue;
-    const int t = term[i];
-    if (t >= 0) {
-      ++*num_items;
-      if (t == 0 || t == 1) sum->num_success++;
-      sum->total_iterations += iters[i];
-    }
-    if (out.term) out.term[p] = (int8_t)t;
-    if (out.iters) out.iters[p] = iters[i];
-    if (out.c0) out.c0[p] = c0[i];
-    if (out.c1) out.c1[p] = c1[i];
-  }
-  sum->kernel_seconds = 1e-3 * ms;
-  if (term_h) term_h->swap(term);
-  return TMI_BA_OK;
-}
-
-// One-shot form of a resident track entry point: call(s) on a light handle of P, the points downloaded into
-// `download` afterwards if it is given (the cameras are constant on these paths), the handle destroyed on every way
-// out.
-template <class Call>
-int with_light_handle(const tmi_ba_problem* P, const tmi_ba_options* O, tmi_ba_problem* download, Call call) {
-  tmi_ba_solver* s = new tmi_ba_solver();
-  int rc = create_impl(s, P, O, 0, 1, /*light=*/true);
-  if (rc == TMI_BA_OK) rc = call(s);
-  if (rc == TMI_BA_OK && download) rc = tmi_ba_solver_download(s, download);
-  if (rc != TMI_BA_OK) g_last_error = s->error;
-  tmi_ba_solver_destroy(s);
-  return rc;
-}
-}  // namespace
 extern "C" {
-
-// ---- per-track side kernels ----------------------------------
-static int ensure_track_outputs(tmi_ba_solver* s) {
-  if (s->d_trk_flag) return TMI_BA_OK;
-  const size_t n = (size_t)std::max(s->st.Np_pad, 1);
-  int rc;
-  if ((rc = dev_alloc(s, &s->d_trk_flag, n))) return rc;
-  if ((rc = dev_alloc(s, &s->d_trk_mean, n))) return rc;
-  if ((rc = dev_alloc(s, &s->d_trk_term, n))) return rc;
-  if ((rc = dev_alloc(s, &s->d_trk_iter, n))) return rc;
-  if ((rc = dev_alloc(s, &s->d_trk_c0, n))) return rc;
-  if ((rc = dev_alloc(s, &s->d_trk_c1, n))) return rc;
-  const size_t nt = (size_t)std::max(s->st.Np_total, 1);
-  if ((rc = dev_alloc(s, &s->d_out_u8, nt))) return rc;
-  if ((rc = dev_alloc(s, &s->d_out_f64, nt))) return rc;
-  if ((rc = dev_alloc(s, &s->d_out_i32, nt))) return rc;
-  if ((rc = dev_alloc(s, &s->d_counters, 4))) return rc;
-  TMI_HIP(hipHostMalloc((void**)&s->h_counters, 4 * sizeof(int), hipHostMallocDefault));
-  TMI_HIP(hipHostMalloc((void**)&s->h_cell_total, sizeof(long long), hipHostMallocDefault));
-  TMI_HIP(hipHostMalloc((void**)&s->h_stage, nt * 16, hipHostMallocDefault));
-  return TMI_BA_OK;
-}
-
-int32_t tmi_ba_solver_filter_outlier_tracks(tmi_ba_solver* s, double max_inlier_reprojection_error,
-                                            double min_triangulation_angle_degrees,
-                                            uint8_t* track_flag, double* track_mean_sq_error,
-                                            tmi_ba_filter_summary* sum) {
-  if (!s || !sum) return TMI_BA_ERR_INVALID_ARGUMENT;
-  memset(sum, 0, sizeof(*sum));
-  const double t0 = now_s();
-  TMI_HIP(hipSetDevice(s->device));
-  int rc = ensure_track_outputs(s);
-  if (rc) return rc;
-  const Structure& st = s->st;
-  const double max_sq = max_inlier_reprojection_error * max_inlier_reprojection_error;
-  const double cos_min = std::cos(min_triangulation_angle_degrees * (M_PI / 180.0));
-  hipEvent_t ea, eb;
-  TMI_HIP(hipEventCreate(&ea));
-  TMI_HIP(hipEventCreate(&eb));
-  TMI_HIP(hipEventRecord(ea, s->stream));
-  if (st.nslices > 0)
-    hipLaunchKernelGGL(outlier_filter_kernel, dim3(s->nblocks_tracks), dim3(256), 0, s->stream, s->v, max_sq,
-                       cos_min, s->d_trk_flag, s->d_trk_mean);
-  TMI_HIP(hipEventRecord(eb, s->stream));
-  float ms = 0.f;
-  if (st.world == 1) {
-    // counts and the permutation to the caller's track order happen on the device; one copy per
-    // requested output (round 1: flags + means of every slot copied out and walked on the host)
-    TMI_HIP(hipMemsetAsync(s->d_counters, 0, 4 * sizeof(int), s->stream));
-    if (st.Np_pad > 0)
-      hipLaunchKernelGGL(filter_finish_kernel, dim3((st.Np_pad + 255) / 256), dim3(256), 0, s->stream, s->d_pt_orig,
-                         st.Np_pad, s->d_trk_flag, s->d_trk_mean, track_flag ? s->d_out_u8 : nullptr,
-                         track_mean_sq_error ? s->d_out_f64 : nullptr, s->d_counters);
-    TMI_HIP(hipMemcpyAsync(s->h_counters, s->d_counters, 4 * sizeof(int), hipMemcpyDeviceToHost, s->stream));
-    const size_t ntot = (size_t)st.Np_total;
-    unsigned char* stage_u8 = s->h_stage;
-    double* stage_f64 = reinterpret_cast<double*>(s->h_stage + 8 * ntot);
-    if (track_flag && ntot > 0)
-      TMI_HIP(hipMemcpyAsync(stage_u8, s->d_out_u8, ntot, hipMemcpyDeviceToHost, s->stream));
-    if (track_mean_sq_error && ntot > 0)
-      TMI_HIP(hipMemcpyAsync(stage_f64, s->d_out_f64, ntot * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    TMI_HIP(hipStreamSynchronize(s->stream));
-    if (track_flag && ntot > 0) memcpy(track_flag, stage_u8, ntot);
-    if (track_mean_sq_error && ntot > 0) memcpy(track_mean_sq_error, stage_f64, ntot * sizeof(double));
-    hipEventElapsedTime(&ms, ea, eb);
-    hipEventDestroy(ea);
-    hipEventDestroy(eb);
-    sum->num_estimated_tracks = s->h_counters[0];
-    sum->num_bad_reprojections = s->h_counters[1];
-    sum->num_insufficient_viewing_angles = s->h_counters[2];
-  } else {
-    std::vector<unsigned char> flag((size_t)st.Np_pad);
-    std::vector<double> mean(track_mean_sq_error ? (size_t)st.Np_pad : 0);
-    if (!flag.empty())
-      TMI_HIP(hipMemcpyAsync(flag.data(), s->d_trk_flag, flag.size(), hipMemcpyDeviceToHost, s->stream));
-    if (!mean.empty())
-      TMI_HIP(hipMemcpyAsync(mean.data(), s->d_trk_mean, mean.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    TMI_HIP(hipStreamSynchronize(s->stream));
-    hipEventElapsedTime(&ms, ea, eb);
-    hipEventDestroy(ea);
-    hipEventDestroy(eb);
-    for (int lp = 0; lp < st.Np_pad; ++lp) {
-      const int p = st.pt_orig[lp];
-      if (p < 0) continue;
-      const unsigned char f = flag[lp];
-      sum->num_estimated_tracks++;
-      if (f == 1) sum->num_bad_reprojections++;
-      if (f == 2) sum->num_insufficient_viewing_angles++;
-      if (track_flag) track_flag[p] = f;
-      if (track_mean_sq_error) track_mean_sq_error[p] = mean[lp];
-    }
-  }
-  // a track nobody observes: mean = 0 / 0, no ray pair -> insufficient viewing angle
-  // (set_outlier_tracks_to_unestimated.cc:108,120-125 with empty lists)
-  for (const int p : st.unobserved) {
-    sum->num_estimated_tracks++;
-    sum->num_insufficient_viewing_angles++;
-    if (track_flag) track_flag[p] = 2;
-    if (track_mean_sq_error) track_mean_sq_error[p] = std::nan("");
-  }
-  sum->kernel_seconds = ms * 1e-3;
-  sum->seconds = now_s() - t0;
-  return TMI_BA_OK;
-}
-
-int32_t tmi_ba_filter_outlier_tracks(const tmi_ba_problem* P, int32_t device,
-                                     double max_inlier_reprojection_error,
-                                     double min_triangulation_angle_degrees, uint8_t* track_flag,
-                                     double* track_mean_sq_error, tmi_ba_filter_summary* sum) {
-  if (!P || !sum) return TMI_BA_ERR_INVALID_ARGUMENT;
-  memset(sum, 0, sizeof(*sum));
-  const double t0 = now_s();
-  tmi_ba_options O;
-  tmi_ba_options_init(&O);
-  O.device = device;
-  const int rc = with_light_handle(P, &O, nullptr, [&](tmi_ba_solver* s) {
-    return tmi_ba_solver_filter_outlier_tracks(s, max_inlier_reprojection_error, min_triangulation_angle_degrees,
-                                               track_flag, track_mean_sq_error, sum);
-  });
-  sum->seconds = now_s() - t0;
-  return rc;
-}
-
-int32_t tmi_ba_solver_adjust_tracks(tmi_ba_solver* s, const tmi_ba_options* O, int8_t* track_termination,
-                                    int32_t* track_iterations, double* track_initial_cost,
-                                    double* track_final_cost, tmi_ba_track_batch_summary* sum) {
-  if (!s || !O || !sum) return TMI_BA_ERR_INVALID_ARGUMENT;
-  memset(sum, 0, sizeof(*sum));
-  if (O->point_dof != s->DP) return TMI_BA_ERR_INVALID_ARGUMENT;
-  const double t0 = now_s();
-  TMI_HIP(hipSetDevice(s->device));
-  int rc = ensure_track_outputs(s);
-  if (rc) return rc;
-  const Structure& st = s->st;
-  const SmallLmArgs A = small_lm_args(O);
-  const SmallLmOut d{s->d_trk_term, s->d_trk_iter, s->d_trk_c0, s->d_trk_c1};
-  const ItemArrays out{track_termination, track_iterations, track_initial_cost, track_final_cost};
-  rc = run_small_lm(s, s->stream, d, (size_t)st.Np_pad, st.pt_orig.data(), [&] {
-    prepare_cameras(s, s->v.ext, s->v.intr, s->v.prep);  // (inside the timed region: part of the call's device work)
-    if (st.nslices > 0) launch_track_lm(s, s->v, s->v.prep, A);
-  }, out, sum, &sum->num_tracks);
-  if (rc) return rc;
-  for (const int p : st.unobserved) {
-    if (track_termination) track_termination[p] = -1;
-    if (track_iterations) track_iterations[p] = 0;
-    if (track_initial_cost) track_initial_cost[p] = 0.0;
-    if (track_final_cost) track_final_cost[p] = 0.0;
-  }
-  sum->seconds = now_s() - t0;
-  return TMI_BA_OK;
-}
-
-int32_t tmi_ba_adjust_tracks(tmi_ba_problem* P, const tmi_ba_options* O, int8_t* track_termination,
-                             int32_t* track_iterations, double* track_initial_cost,
-                             double* track_final_cost, tmi_ba_track_batch_summary* sum) {
-  if (!P || !O || !sum) return TMI_BA_ERR_INVALID_ARGUMENT;
-  memset(sum, 0, sizeof(*sum));
-  const double t0 = now_s();
-  const int rc = with_light_handle(P, O, P, [&](tmi_ba_solver* s) {
-    return tmi_ba_solver_adjust_tracks(s, O, track_termination, track_iterations, track_initial_cost,
-                                       track_final_cost, sum);
-  });
-  sum->seconds = now_s() - t0;
-  return rc;
-}
-
-// ---- batched BundleAdjustView (view_kernels.h) ---------------------------------------------
-}  // extern "C"
-namespace {
-// Chains of the views to adjust (selected, observed, something free): the selected views of a group with free
-// entries form one chain in ascending index order, every other view is a chain of its own; longest first.
-void build_view_chains(int Nc, const std::vector<int4>& cam, const int* cam_group, int G,
-                       const std::vector<long long>& vptr, const uint8_t* view_mask, std::vector<int>* chain_ptr,
-                       std::vector<int>* chain_views) {
-  std::vector<std::vector<int> > chains;
-  std::vector<int> group_chain(std::max(G, 0), -1);
-  for (int c = 0; c < Nc; ++c) {
-    if (view_mask && !view_mask[c]) continue;
-    if (cam[c].w == 0 || vptr[c + 1] == vptr[c]) continue;
-    const int g = cam_group[c];
-    if (((unsigned)cam[c].w >> 6) != 0) {
-      if (group_chain[g] < 0) {
-        group_chain[g] = (int)chains.size();
-        chains.emplace_back();
-      }
-      chains[group_chain[g]].push_back(c);
-    } else {
-      chains.push_back({c});
-    }
-  }
-  std::stable_sort(chains.begin(), chains.end(),
-                   [](const std::vector<int>& a, const std::vector<int>& b) { return a.size() > b.size(); });
-  chain_ptr->assign(1, 0);
-  chain_views->clear();
-  for (const auto& ch : chains) {
-    chain_views->insert(chain_views->end(), ch.begin(), ch.end());
-    chain_ptr->push_back((int)chain_views->size());
-  }
-}
-
-// (model, intrinsics offset, intrinsics size, free mask over [extrinsics(6) | intrinsics(10)]) per camera
-int4 view_cam_record(int flags, int model, int offset, int nk, uint32_t free_intr) {
-  uint32_t m = 0;
-  if (!(flags & TMI_BA_CAMERA_POSITION_CONSTANT)) m |= 0x07;
-  if (!(flags & TMI_BA_CAMERA_ORIENTATION_CONSTANT)) m |= 0x38;
-  m |= (free_intr & 0x3ffu) << 6;
-  return make_int4(model, offset, nk, (int)m);
-}
-
-// Launches the chains on s->stream (B holds the parameter / observation pointers) and fills the per-view outputs.
-int run_view_batch(OneShot* s, ViewBatch B, const tmi_ba_options* O, int Nc, const std::vector<int4>& cam,
-                   const std::vector<int>& chain_ptr, const std::vector<int>& chain_views, const ItemArrays& out,
-                   tmi_ba_view_batch_summary* sum) {
-  const int n_chains = (int)chain_ptr.size() - 1;
-  int* d_cptr;
-  int* d_cviews;
-  TMI_HIP(s->upload(&d_cptr, chain_ptr.data(), chain_ptr.size()));
-  TMI_HIP(s->upload(&d_cviews, chain_views.data(), chain_views.size()));
-  int rc = s->alloc_outputs(&B.out, (size_t)Nc);  // -1: not adjusted
-  if (rc) return rc;
-  B.chain_ptr = d_cptr;
-  B.chain_views = d_cviews;
-  bool pinhole = true;
-  for (const int c : chain_views) pinhole = pinhole && cam[c].x == TMI_BA_PINHOLE;
-  const SmallLmArgs A = small_lm_args(O);
-  rc = run_small_lm(s, s->stream, B.out, (size_t)Nc, nullptr, [&] {
-    if (n_chains == 0) return;
-    if (pinhole)
-      hipLaunchKernelGGL((view_lm_kernel<0>), dim3(n_chains), dim3(256), 0, s->stream, B, A);
-    else
-      hipLaunchKernelGGL(view_lm_kernel<-1>, dim3(n_chains), dim3(256), 0, s->stream, B, A);
-  }, out, sum, &sum->num_views);
-  sum->num_chains = n_chains;
-  return rc;
-}
-}  // namespace
-extern "C" {
-
-int32_t tmi_ba_solver_adjust_views(tmi_ba_solver* s, const tmi_ba_options* O, const uint8_t* view_mask,
-                                   int8_t* view_termination, int32_t* view_iterations, double* view_initial_cost,
-                                   double* view_final_cost, tmi_ba_view_batch_summary* sum) {
-  if (!s || !O || !sum) return TMI_BA_ERR_INVALID_ARGUMENT;
-  memset(sum, 0, sizeof(*sum));
-  const Structure& st = s->st;
-  if (st.world > 1) {
-    g_last_error = s->error = "view adjustment needs every observation of a view: run it on an unsharded handle";
-    return TMI_BA_ERR_INVALID_ARGUMENT;
-  }
-  const double t0 = now_s();
-  TMI_HIP(hipSetDevice(s->device));
-  const int Nc = st.Nc;
-  hipStream_t stream = s->stream;
-  int rc;
-  // static per handle: the view-major index of the handle's observations (device radix sort of (view, slot) keys).
-  // Marked ready only once every part of it exists: a build that fails part-way is redone by the next call (the
-  // temporaries are freed on every way out, the handle's own arrays at destroy).
-  if (!s->view_index_ready) {
-    if (st.No_pad >= (int64_t)0xffffffffLL) {
-      g_last_error = s->error = "view adjustment: more than 2^32 observation slots";
-      return TMI_BA_ERR_UNSUPPORTED;
-    }
-    if ((rc = dev_alloc(s, &s->d_view_ptr, (size_t)Nc + 2))) return rc;
-    if ((rc = dev_alloc(s, &s->d_view_keys, (size_t)std::max<int64_t>(st.No_pad, 1)))) return rc;
-    if ((rc = dev_alloc(s, &s->d_view_slot_pt, (size_t)std::max<int64_t>(st.No_pad, 1)))) return rc;
-    if (st.No_pad > 0) {
-      OneShot tmp_mem(stream);
-      unsigned long long* keys_in = nullptr;
-      TMI_HIP(tmp_mem.alloc(&keys_in, (size_t)st.No_pad));
-      hipLaunchKernelGGL(view_keys_kernel, dim3(s->nblocks_slices), dim3(256), 0, stream, s->v, keys_in, s->d_view_slot_pt);
-      size_t tmp_bytes = 0;
-      TMI_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, tmp_bytes, keys_in, s->d_view_keys, (int)st.No_pad, 0, 64, stream));
-      unsigned char* tmp = nullptr;
-      TMI_HIP(tmp_mem.alloc(&tmp, std::max<size_t>(tmp_bytes, 16)));
-      TMI_HIP(hipcub::DeviceRadixSort::SortKeys(tmp, tmp_bytes, keys_in, s->d_view_keys, (int)st.No_pad, 0, 64, stream));
-      TMI_HIP(hipStreamSynchronize(stream));
-    }
-    hipLaunchKernelGGL(select_view_ptr_kernel, dim3((Nc + 1 + 255) / 256), dim3(256), 0, stream, s->d_view_keys,
-                       (long long)st.No_pad, Nc, s->d_view_ptr);
-    std::vector<long long> vptr_h((size_t)Nc + 1, 0);
-    TMI_HIP(hipMemcpyAsync(vptr_h.data(), s->d_view_ptr, ((size_t)Nc + 1) * sizeof(long long), hipMemcpyDeviceToHost,
-                           stream));
-    TMI_HIP(hipStreamSynchronize(stream));
-    std::vector<int4> cam_h((size_t)Nc);
-    for (int c = 0; c < Nc; ++c) {
-      const int g = st.cam_group[c];
-      const int o = st.group_offset[g];
-      cam_h[c] = view_cam_record(s->cam_flags_h.empty() ? 0 : s->cam_flags_h[c], s->grp_model_h[g], o,
-                                 st.group_offset[g + 1] - o, st.grp_free[g]);
-    }
-    if ((rc = dev_upload(s, &s->d_view_cam, cam_h))) return rc;
-    s->view_ptr_h.swap(vptr_h);
-    s->view_cam_h.swap(cam_h);
-    s->view_index_ready = true;
-  }
-  std::vector<int> chain_ptr, chain_views;
-  build_view_chains(Nc, s->view_cam_h, st.cam_group.data(), st.G, s->view_ptr_h, view_mask, &chain_ptr, &chain_views);
-  ViewBatch B;
-  memset(&B, 0, sizeof(B));
-  B.ext = s->v.ext;
-  B.intr = s->v.intr;
-  B.cam = s->d_view_cam;
-  B.keys = s->d_view_keys;
-  B.vptr = s->d_view_ptr;
-  B.slot_pt = s->d_view_slot_pt;
-  B.obs_xy = s->v.obs_xy;
-  B.pts = s->v.pts;
-  OneShot scratch(stream);
-  rc = run_view_batch(&scratch, B, O, Nc, s->view_cam_h, chain_ptr, chain_views,
-                      {view_termination, view_iterations, view_initial_cost, view_final_cost}, sum);
-  if (rc) {
-    g_last_error = s->error = scratch.error;
-    return rc;
-  }
-  // the cameras moved: every camera-derived cache of the handle is stale
-  prepare_cameras(s, s->v.ext, s->v.intr, s->v.prep);
-  s->v.compact = 0;
-  s->v.sums_ready = 0;
-  TMI_HIP(hipStreamSynchronize(stream));
-  sum->seconds = now_s() - t0;
-  return TMI_BA_OK;
-}
-
-int32_t tmi_ba_adjust_views(tmi_ba_problem* P, const tmi_ba_options* O, const uint8_t* view_mask,
-                            int8_t* view_termination, int32_t* view_iterations, double* view_initial_cost,
-                            double* view_final_cost, tmi_ba_view_batch_summary* sum) {
-  if (!P || !O || !sum) return TMI_BA_ERR_INVALID_ARGUMENT;
-  memset(sum, 0, sizeof(*sum));
-  const double t0 = now_s();
-  OneShot sc;
-  OneShot* s = &sc;  // (TMI_HIP reports into s->error)
-  auto bad = [&](const char* why) {
-    g_last_error = why;
-    return TMI_BA_ERR_INVALID_ARGUMENT;
-  };
-  const int Nc = P->num_cameras, G = P->num_groups, Np = P->num_points;
-  const int64_t No = P->num_observations;
-  if (Nc < 0 || G < 0 || Np < 0 || No < 0) return bad("negative size");
-  if ((Nc && (!P->extrinsics || !P->camera_group)) || (G && (!P->group_model || !P->group_offset)) ||
-      (Np && !P->points) || (No && (!P->obs_camera || !P->obs_point || !P->obs_xy)))
-    return bad("missing array");
-  if (No >= (int64_t)0xffffffffLL) return bad("more than 2^32 observations");
-  const int n_intr = G ? P->group_offset[G] : 0;
-  if (n_intr && !P->intrinsics) return bad("missing intrinsics");
-  std::vector<uint32_t> grp_free((size_t)G, 0);
-  for (int g = 0; g < G; ++g) {
-    const int o = P->group_offset[g], nk = P->group_offset[g + 1] - o;
-    if (P->group_model[g] < 0 || P->group_model[g] > 4 || nk != tmi_ba_intrinsics_size(P->group_model[g]) || o < 0)
-      return bad("bad intrinsics group");
-    for (int j = 0; j < nk; ++j)
-      if (!P->intrinsics_constant || !P->intrinsics_constant[o + j]) grp_free[g] |= 1u << j;
-  }
-  std::vector<int4> cam((size_t)Nc);
-  for (int c = 0; c < Nc; ++c) {
-    const int g = P->camera_group[c];
-    if (g < 0 || g >= G) return bad("bad camera group");
-    const int o = P->group_offset[g];
-    cam[c] = view_cam_record(P->camera_flags ? P->camera_flags[c] : 0, P->group_model[g], o,
-                             P->group_offset[g + 1] - o, grp_free[g]);
-  }
-  // host work that does not shrink with the batch: one pass over all observations (check + count) and one over their
-  // cameras (the gather below); summary.seconds - kernel_seconds is this plus the uploads
-  std::vector<long long> optr((size_t)Nc + 1, 0);  // observations per view as ranges of the view-major order
-  for (int64_t i = 0; i < No; ++i) {
-    const int c = P->obs_camera[i], p = P->obs_point[i];
-    if (c < 0 || c >= Nc || p < 0 || p >= Np) return bad("bad observation index");
-    optr[(size_t)c + 1]++;
-  }
-  for (int c = 0; c < Nc; ++c) optr[(size_t)c + 1] += optr[c];
-  std::vector<int> chain_ptr, chain_views;
-  build_view_chains(Nc, cam, P->camera_group, G, optr, view_mask, &chain_ptr, &chain_views);
-  // Of the observations only the chains' views' go up, gathered in view-major order (ascending observation index
-  // inside a view); the points go up whole (one sequential copy: renumbering the observed ones costs a random access
-  // per observation on the host, more than the copy).
-  std::vector<uint8_t> in_chain((size_t)Nc, 0);
-  for (const int c : chain_views) in_chain[c] = 1;
-  std::vector<long long> vptr((size_t)Nc + 1, 0);
-  for (int c = 0; c < Nc; ++c) vptr[(size_t)c + 1] = vptr[c] + (in_chain[c] ? optr[(size_t)c + 1] - optr[c] : 0);
-  const size_t M = (size_t)vptr[Nc];
-  std::vector<unsigned long long> keys(M);
-  std::vector<int> slot_pt(M);
-  std::vector<double> xy(2 * M);
-  if (M) {
-    std::vector<long long> fill(vptr.begin(), vptr.end() - 1);
-    for (int64_t i = 0; i < No; ++i) {
-      const int c = P->obs_camera[i];
-      if (!in_chain[c]) continue;
-      const size_t o = (size_t)fill[c]++;
-      keys[o] = ((unsigned long long)(unsigned)c << 32) | (unsigned long long)o;
-      slot_pt[o] = P->obs_point[i];
-      xy[2 * o] = P->obs_xy[2 * i];
-      xy[2 * o + 1] = P->obs_xy[2 * i + 1];
-    }
-  }
-  int rc = s->open(O->device);
-  if (rc) {
-    g_last_error = s->error;
-    return rc;
-  }
-  const hipStream_t stream = s->stream;
-  ViewBatch B;
-  memset(&B, 0, sizeof(B));
-  int4* d_cam;
-  long long* d_vptr;
-  unsigned long long* d_keys;
-  int* d_slot_pt;
-  double *d_xy, *d_pts;
-  TMI_HIP(s->upload(&B.ext, P->extrinsics, (size_t)6 * Nc));
-  TMI_HIP(s->upload(&B.intr, P->intrinsics, (size_t)n_intr));
-  TMI_HIP(s->upload(&d_cam, cam.data(), cam.size()));
-  TMI_HIP(s->upload(&d_vptr, vptr.data(), vptr.size()));
-  TMI_HIP(s->upload(&d_keys, keys.data(), keys.size()));
-  TMI_HIP(s->upload(&d_slot_pt, slot_pt.data(), slot_pt.size()));
-  TMI_HIP(s->upload(&d_xy, xy.data(), xy.size()));
-  TMI_HIP(s->upload(&d_pts, M ? P->points : nullptr, M ? (size_t)4 * Np : 0));
-  B.cam = d_cam;
-  B.vptr = d_vptr;
-  B.keys = d_keys;
-  B.slot_pt = d_slot_pt;
-  B.obs_xy = d_xy;
-  B.pts = d_pts;
-  rc = run_view_batch(s, B, O, Nc, cam, chain_ptr, chain_views,
-                      {view_termination, view_iterations, view_initial_cost, view_final_cost}, sum);
-  if (rc == TMI_BA_OK && Nc) {
-    // the kernel wrote back exactly the usable views' cameras and their groups' free intrinsics
-    TMI_HIP(hipMemcpyAsync(P->extrinsics, B.ext, (size_t)6 * Nc * sizeof(double), hipMemcpyDeviceToHost, stream));
-    if (n_intr)
-      TMI_HIP(hipMemcpyAsync(P->intrinsics, B.intr, (size_t)n_intr * sizeof(double), hipMemcpyDeviceToHost, stream));
-    TMI_HIP(hipStreamSynchronize(stream));
-  }
-  if (rc) g_last_error = s->error;
-  sum->seconds = now_s() - t0;
-  return rc;
-}
-
-// ---- batched TrackEstimator (track_estimate_kernels.h) ------------------------------------
-void tmi_ba_track_estimator_options_init(tmi_ba_track_estimator_options* o) {
-  if (!o) return;
-  o->max_acceptable_reprojection_error_pixels = 5.0;  // estimate_track.h:63-70
-  o->min_triangulation_angle_degrees = 3.0;
-  o->bundle_adjustment = 1;
-}
-
-int32_t tmi_ba_solver_estimate_tracks(tmi_ba_solver* s, const tmi_ba_track_estimator_options* eo,
-                                      const tmi_ba_options* O, const uint8_t* track_mask, int8_t* track_status,
-                                      tmi_ba_track_estimate_summary* sum) {
-  if (!s || !eo || !O || !sum) return TMI_BA_ERR_INVALID_ARGUMENT;
-  memset(sum, 0, sizeof(*sum));
-  const Structure& st = s->st;
-  if (st.world > 1) {
-    g_last_error = s->error = "track estimation needs every observation of a track: run it on an unsharded handle";
-    return TMI_BA_ERR_INVALID_ARGUMENT;
-  }
-  if (O->point_dof != s->DP) {
-    g_last_error = s->error = "track estimation: options->point_dof differs from the handle's";
-    return TMI_BA_ERR_INVALID_ARGUMENT;
-  }
-  const double t0 = now_s();
-  TMI_HIP(hipSetDevice(s->device));
-  hipStream_t stream = s->stream;
-  int rc = ensure_track_outputs(s);
-  if (rc) return rc;
-  const size_t npad = (size_t)st.Np_pad;
-  // the caller's mask on the padded track order
-  std::vector<unsigned char> attempt_h(npad, 0);
-  for (size_t lp = 0; lp < npad; ++lp) {
-    const int p = st.pt_orig[lp];
-    if (p >= 0 && (!track_mask || track_mask[p])) attempt_h[lp] = 1;
-  }
-  OneShot scratch(stream);
-  unsigned char* d_attempt = nullptr;
-  signed char* d_status = nullptr;
-  double* d_ray = nullptr;
-  TMI_HIP(scratch.upload(&d_attempt, attempt_h.data(), npad));
-  TMI_HIP(scratch.alloc(&d_status, npad));
-  TMI_HIP(scratch.alloc(&d_ray, (size_t)3 * (size_t)std::max<int64_t>(st.No_pad, 1)));
-  const double cos_min = std::cos(eo->min_triangulation_angle_degrees * (M_PI / 180.0));
-  const double max_err = eo->max_acceptable_reprojection_error_pixels;
-  hipEvent_t ea, eb;
-  TMI_HIP(hipEventCreate(&ea));
-  TMI_HIP(hipEventCreate(&eb));
-  hipEventRecord(ea, stream);
-  if (st.nslices > 0) {
-    hipLaunchKernelGGL(track_rays_kernel, dim3(s->nblocks_tracks), dim3(256), 0, stream, s->v, d_attempt, d_ray);
-    hipLaunchKernelGGL(track_triangulate_kernel, dim3(s->nblocks_tracks), dim3(256), 0, stream, s->v, d_attempt,
-                       d_ray, cos_min, d_status);
-    const signed char* term = nullptr;
-    if (eo->bundle_adjustment) {
-      // BundleAdjustTrack with the caller's options (DENSE_QR and no inner iterations change nothing for a
-      // single track) on the tracks the triangulation accepted; the others are skipped like constant tracks
-      prepare_cameras(s, s->v.ext, s->v.intr, s->v.prep);
-      launch_track_lm(s, s->v, s->v.prep, small_lm_args(O), d_status);
-      term = s->d_trk_term;
-    }
-    hipLaunchKernelGGL(track_accept_kernel, dim3(s->nblocks_tracks), dim3(256), 0, stream, s->v, max_err * max_err,
-                       term, d_status);
-  }
-  hipEventRecord(eb, stream);
-  const hipError_t le = hipGetLastError();
-  std::vector<signed char> status_h(npad);
-  if (npad) TMI_HIP(hipMemcpyAsync(status_h.data(), d_status, npad, hipMemcpyDeviceToHost, stream));
-  const hipError_t se = hipStreamSynchronize(stream);
-  float ms = 0.f;
-  hipEventElapsedTime(&ms, ea, eb);
-  hipEventDestroy(ea);
-  hipEventDestroy(eb);
-  TMI_HIP(le);
-  TMI_HIP(se);
-  auto count = [sum](int code) {
-    if (code < 0) return;
-    sum->num_attempts++;
-    switch (code) {
-      case 0: sum->num_estimated++; break;
-      case 1: sum->num_bad_angle++; break;
-      case 2: sum->num_failed_triangulation++; break;
-      case 3: sum->num_failed_ba++; break;
-      default: sum->num_bad_reprojection++; break;
-    }
-  };
-  for (size_t lp = 0; lp < npad; ++lp) {
-    const int p = st.pt_orig[lp];
-    if (p < 0) continue;
-    count(status_h[lp]);
-    if (track_status) track_status[p] = (int8_t)status_h[lp];
-  }
-  // a track without observations has fewer than two views (estimate_track.cc:224-230)
-  for (const int p : st.unobserved) {
-    const int code = (!track_mask || track_mask[p]) ? 1 : -1;
-    count(code);
-    if (track_status) track_status[p] = (int8_t)code;
-  }
-  sum->kernel_seconds = 1e-3 * ms;
-  sum->seconds = now_s() - t0;
-  return TMI_BA_OK;
-}
-
-int32_t tmi_ba_estimate_tracks(tmi_ba_problem* P, const tmi_ba_track_estimator_options* eo,
-                               const tmi_ba_options* O, const uint8_t* track_mask, int8_t* track_status,
-                               tmi_ba_track_estimate_summary* sum) {
-  if (!P || !eo || !O || !sum) return TMI_BA_ERR_INVALID_ARGUMENT;
-  memset(sum, 0, sizeof(*sum));
-  const double t0 = now_s();
-  // argument errors before the device is touched
-  auto bad = [](const char* why) {
-    g_last_error = why;
-    return TMI_BA_ERR_INVALID_ARGUMENT;
-  };
-  const int Nc = P->num_cameras, Np = P->num_points;
-  const int64_t No = P->num_observations;
-  if (Nc < 0 || P->num_groups < 0 || Np < 0 || No < 0) return bad("negative size");
-  if ((Nc && (!P->extrinsics || !P->camera_group)) || (Np && !P->points) ||
-      (No && (!P->obs_camera || !P->obs_point || !P->obs_xy)))
-    return bad("missing array");
-  if (O->point_dof != 3 && O->point_dof != 4) return bad("point_dof must be 3 or 4");
-  for (int64_t i = 0; i < No; ++i)
-    if (P->obs_camera[i] < 0 || P->obs_camera[i] >= Nc || P->obs_point[i] < 0 || P->obs_point[i] >= Np)
-      return bad("observation index out of range");
-  // constant points are never attempted, observed or not
-  std::vector<uint8_t> mask;
-  if (P->point_constant && P->num_points > 0) {
-    mask.assign((size_t)P->num_points, 1);
-    for (int p = 0; p < P->num_points; ++p)
-      mask[p] = (uint8_t)((!track_mask || track_mask[p]) && !P->point_constant[p]);
-  }
-  const int rc = with_light_handle(P, O, P, [&](tmi_ba_solver* s) {
-    return tmi_ba_solver_estimate_tracks(s, eo, O, mask.empty() ? track_mask : mask.data(), track_status, sum);
-  });
-  sum->seconds = now_s() - t0;
-  return rc;
-}
-
-// BundleAdjustTwoViewsAngular for a batch of view pairs (two_view_kernels.h)
-int32_t tmi_ba_adjust_two_views_angular(tmi_ba_two_view_angular_batch* Bh, int32_t max_num_iterations, int32_t device,
-                                        int8_t* pair_termination, int32_t* pair_iterations,
-                                        double* pair_initial_cost, double* pair_final_cost,
-                                        tmi_ba_track_batch_summary* sum) {
-  if (!Bh || !sum) return TMI_BA_ERR_INVALID_ARGUMENT;
-  memset(sum, 0, sizeof(*sum));
-  if (Bh->num_pairs < 0 || max_num_iterations < 0) return TMI_BA_ERR_INVALID_ARGUMENT;
-  const int P = Bh->num_pairs;
-  if (P > 0 && (!Bh->rotation2 || !Bh->position2 || !Bh->correspondence_ptr)) return TMI_BA_ERR_INVALID_ARGUMENT;
-  const double t0 = now_s();
-  const int64_t N = P ? Bh->correspondence_ptr[P] : 0;
-  for (int p = 0; p < P; ++p)
-    if (Bh->correspondence_ptr[p + 1] < Bh->correspondence_ptr[p]) return TMI_BA_ERR_INVALID_ARGUMENT;
-  if (N > 0 && (!Bh->features1 || !Bh->features2)) return TMI_BA_ERR_INVALID_ARGUMENT;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    g_last_error = "no HIP device visible (the device path has no CPU fallback)";
-    return TMI_BA_ERR_NO_DEVICE;
-  }
-  if (device >= ndev) return TMI_BA_ERR_INVALID_ARGUMENT;
-  if (P == 0) return TMI_BA_OK;
-  OneShot sc;
-  OneShot* s = &sc;  // (TMI_HIP reports into s->error)
-  const int rc = [&]() -> int {
-    int rc = s->open(device);
-    if (rc) return rc;
-    TwoViewAngularBatch B;
-    memset(&B, 0, sizeof(B));
-    B.num_pairs = P;
-    double *d_f1, *d_f2;
-    long long* d_cptr;
-    TMI_HIP(s->upload(&B.rot2, Bh->rotation2, (size_t)3 * P));
-    TMI_HIP(s->upload(&B.pos2, Bh->position2, (size_t)3 * P));
-    TMI_HIP(s->upload(&d_f1, Bh->features1, (size_t)2 * N));
-    TMI_HIP(s->upload(&d_f2, Bh->features2, (size_t)2 * N));
-    TMI_HIP(s->upload(&d_cptr, (const long long*)Bh->correspondence_ptr, (size_t)P + 1));
-    B.feat1 = d_f1;
-    B.feat2 = d_f2;
-    B.corr_ptr = d_cptr;
-    SmallLmOut d;
-    if ((rc = s->alloc_outputs(&d, (size_t)P))) return rc;
-    const SmallLmArgs A = ceres_default_lm_args(max_num_iterations, TMI_BA_LOSS_TRIVIAL, 0.0);
-    std::vector<signed char> term;
-    rc = run_small_lm(s, s->stream, d, (size_t)P, nullptr, [&] {
-      hipLaunchKernelGGL(two_view_angular_kernel, dim3((P + 3) / 4), dim3(256), 0, s->stream, B, A, d);
-    }, ItemArrays{pair_termination, pair_iterations, pair_initial_cost, pair_final_cost}, sum, &sum->num_tracks, &term);
-    if (rc) return rc;
-    std::vector<double> rot((size_t)3 * P), pos((size_t)3 * P);
-    TMI_HIP(hipMemcpyAsync(rot.data(), B.rot2, rot.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    TMI_HIP(hipMemcpyAsync(pos.data(), B.pos2, pos.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    TMI_HIP(hipStreamSynchronize(s->stream));
-    for (int p = 0; p < P; ++p) {
-      if (term[p] != 0 && term[p] != 1) continue;  // termination != FAILURE: write back
-      for (int a = 0; a < 3; ++a) {
-        Bh->rotation2[(size_t)3 * p + a] = rot[(size_t)3 * p + a];
-        Bh->position2[(size_t)3 * p + a] = pos[(size_t)3 * p + a];
-      }
-    }
-    return TMI_BA_OK;
-  }();
-  if (rc) g_last_error = s->error;
-  sum->seconds = now_s() - t0;
-  return rc;
-}
-
-// OptimizeRelativePositionWithKnownRotation for a batch of view pairs (relative_position_kernels.h)
-int32_t tmi_ba_optimize_relative_positions(tmi_ba_relative_position_batch* Bh, int32_t device, int8_t* pair_status,
-                                           int32_t* pair_iterations, double* pair_cost, int32_t* pair_num_in_front,
-                                           tmi_ba_track_batch_summary* sum) {
-  if (!Bh || !sum) return TMI_BA_ERR_INVALID_ARGUMENT;
-  memset(sum, 0, sizeof(*sum));
-  // argument errors before the device is touched
-  auto bad = [](const char* why) {
-    g_last_error = why;
-    return TMI_BA_ERR_INVALID_ARGUMENT;
-  };
-  const int V = Bh->num_views, P = Bh->num_pairs;
-  if (V < 0 || P < 0) return bad("relative positions: negative size");
-  if ((V > 0 && !Bh->view_rotation) || (P > 0 && (!Bh->pair_view1 || !Bh->pair_view2 || !Bh->correspondence_ptr ||
-                                                   !Bh->position2)))
-    return bad("relative positions: missing array");
-  if ((Bh->view_model != nullptr) != (Bh->view_intrinsics != nullptr))
-    return bad("relative positions: view_model and view_intrinsics come together");
-  const bool pixels = Bh->view_model != nullptr;
-  if (pixels)
-    for (int v = 0; v < V; ++v)
-      if (Bh->view_model[v] < TMI_BA_PINHOLE || Bh->view_model[v] > TMI_BA_DIVISION_UNDISTORTION)
-        return bad("relative positions: unknown camera model");
-  const double t0 = now_s();
-  for (int p = 0; p < P; ++p) {
-    if (Bh->correspondence_ptr[p + 1] < Bh->correspondence_ptr[p] || Bh->correspondence_ptr[p] < 0)
-      return bad("relative positions: correspondence_ptr decreases");
-    if (Bh->pair_view1[p] < 0 || Bh->pair_view1[p] >= V || Bh->pair_view2[p] < 0 || Bh->pair_view2[p] >= V)
-      return bad("relative positions: view index out of range");
-  }
-  const int64_t N = P ? Bh->correspondence_ptr[P] : 0;
-  if (N > 0 && (!Bh->features1 || !Bh->features2)) return bad("relative positions: missing array");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    g_last_error = "no HIP device visible (the device path has no CPU fallback)";
-    return TMI_BA_ERR_NO_DEVICE;
-  }
-  if (device >= ndev) return bad("relative positions: no such device");
-  if (P == 0) return TMI_BA_OK;
-  // pairs too long for the kernel's registers keep their columns in a scratch plane
-  std::vector<long long> sptr((size_t)P, -1);
-  long long slen = 0;
-  for (int p = 0; p < P; ++p) {
-    const long long n = Bh->correspondence_ptr[p + 1] - Bh->correspondence_ptr[p];
-    if (n > 64LL * kRelPosRegColumns) {
-      sptr[p] = slen;
-      slen += n;
-    }
-  }
-  OneShot sc;
-  OneShot* s = &sc;  // (TMI_HIP reports into s->error)
-  const int rc = [&]() -> int {
-    int rc = s->open(device);
-    if (rc) return rc;
-    RelativePositionBatch B;
-    memset(&B, 0, sizeof(B));
-    B.num_pairs = P;
-    double *d_rot, *d_intr = nullptr, *d_f1, *d_f2;
-    int *d_model = nullptr, *d_v1, *d_v2;
-    long long *d_cptr, *d_sptr;
-    TMI_HIP(s->upload(&d_rot, Bh->view_rotation, (size_t)3 * V));
-    TMI_HIP(s->upload(&d_v1, (const int*)Bh->pair_view1, (size_t)P));
-    TMI_HIP(s->upload(&d_v2, (const int*)Bh->pair_view2, (size_t)P));
-    TMI_HIP(s->upload(&d_cptr, (const long long*)Bh->correspondence_ptr, (size_t)P + 1));
-    TMI_HIP(s->upload(&d_sptr, (const long long*)sptr.data(), (size_t)P));
-    TMI_HIP(s->upload(&d_f1, Bh->features1, (size_t)2 * N));
-    TMI_HIP(s->upload(&d_f2, Bh->features2, (size_t)2 * N));
-    if (pixels) {
-      TMI_HIP(s->upload(&d_model, (const int*)Bh->view_model, (size_t)V));
-      TMI_HIP(s->upload(&d_intr, Bh->view_intrinsics, (size_t)10 * V));
-    }
-    B.view_rot = d_rot;
-    B.view_model = d_model;
-    B.view_intr = d_intr;
-    B.pair_view1 = d_v1;
-    B.pair_view2 = d_v2;
-    B.corr_ptr = d_cptr;
-    B.feat1 = d_f1;
-    B.feat2 = d_f2;
-    B.scratch_ptr = d_sptr;
-    B.scratch_len = slen;
-    TMI_HIP(s->alloc(&B.scratch, (size_t)3 * (size_t)slen));
-    TMI_HIP(s->alloc(&B.pos2, (size_t)3 * P));
-    TMI_HIP(s->alloc(&B.status, (size_t)P));
-    TMI_HIP(s->alloc(&B.iters, (size_t)P));
-    TMI_HIP(s->alloc(&B.cost, (size_t)P));
-    TMI_HIP(s->alloc(&B.in_front, (size_t)P));
-    double *d_n1 = nullptr, *d_n2 = nullptr;
-    if (pixels) {
-      TMI_HIP(s->alloc(&d_n1, (size_t)2 * N));
-      TMI_HIP(s->alloc(&d_n2, (size_t)2 * N));
-    }
-    hipEvent_t ea, eb;
-    TMI_HIP(hipEventCreate(&ea));
-    TMI_HIP(hipEventCreate(&eb));
-    hipEventRecord(ea, s->stream);
-    if (pixels) {
-      hipLaunchKernelGGL(relative_position_normalise_kernel, dim3((P + 3) / 4), dim3(256), 0, s->stream, B, d_n1, d_n2);
-      B.feat1 = d_n1;
-      B.feat2 = d_n2;
-    }
-    hipLaunchKernelGGL(relative_position_kernel, dim3((P + 3) / 4), dim3(256), 0, s->stream, B);
-    hipEventRecord(eb, s->stream);
-    const hipError_t le = hipGetLastError();
-    std::vector<double> pos((size_t)3 * P), cost((size_t)P);
-    std::vector<signed char> status((size_t)P);
-    std::vector<int> iters((size_t)P), front((size_t)P);
-    hipError_t ce = hipMemcpyAsync(pos.data(), B.pos2, pos.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream);
-    if (ce == hipSuccess) ce = hipMemcpyAsync(cost.data(), B.cost, (size_t)P * sizeof(double), hipMemcpyDeviceToHost, s->stream);
-    if (ce == hipSuccess) ce = hipMemcpyAsync(status.data(), B.status, (size_t)P, hipMemcpyDeviceToHost, s->stream);
-    if (ce == hipSuccess) ce = hipMemcpyAsync(iters.data(), B.iters, (size_t)P * sizeof(int), hipMemcpyDeviceToHost, s->stream);
-    if (ce == hipSuccess) ce = hipMemcpyAsync(front.data(), B.in_front, (size_t)P * sizeof(int), hipMemcpyDeviceToHost, s->stream);
-    const hipError_t se = hipStreamSynchronize(s->stream);
-    float ms = 0.f;
-    hipEventElapsedTime(&ms, ea, eb);
-    hipEventDestroy(ea);
-    hipEventDestroy(eb);
-    TMI_HIP(le);
-    TMI_HIP(ce);
-    TMI_HIP(se);
-    for (int p = 0; p < P; ++p) {
-      const int st = status[p];
-      if (st >= 0) {
-        sum->num_tracks++;
-        sum->total_iterations += iters[p];
-      }
-      if (st == 0 || st == 1) {  // the reference returns the position for both
-        sum->num_success++;
-        for (int a = 0; a < 3; ++a) Bh->position2[(size_t)3 * p + a] = pos[(size_t)3 * p + a];
-      }
-      if (pair_status) pair_status[p] = (int8_t)st;
-      if (pair_iterations) pair_iterations[p] = iters[p];
-      if (pair_cost) pair_cost[p] = cost[p];
-      if (pair_num_in_front) pair_num_in_front[p] = front[p];
-    }
-    sum->kernel_seconds = 1e-3 * ms;
-    return TMI_BA_OK;
-  }();
-  if (rc) g_last_error = s->error;
-  sum->seconds = now_s() - t0;
-  return rc;
-}
-
-// SelectGoodTracksForBundleAdjustment (select_good_tracks_for_bundle_adjustment.cc:251-327):
-// the projections (track statistics) run on the device, the per-view grid / ranking logic --
-// integer compares over the view's feature list -- on the host.
-int32_t tmi_ba_solver_select_good_tracks(tmi_ba_solver* s, int32_t long_track_length_threshold,
-                                         int32_t image_grid_cell_size_pixels,
-                                         int32_t min_num_optimized_tracks_per_view,
-                                         const uint8_t* view_mask, uint8_t* selected,
-                                         int32_t* stats_len, double* stats_err,
-                                         tmi_ba_select_summary* sum) {
-  if (!s || !sum || !selected || image_grid_cell_size_pixels <= 0) return TMI_BA_ERR_INVALID_ARGUMENT;
-  memset(sum, 0, sizeof(*sum));
-  const Structure& st = s->st;
-  if (st.world > 1) {
-    g_last_error = s->error = "track selection ranks every view's tracks: run it on an unsharded handle";
-    return TMI_BA_ERR_UNSUPPORTED;
-  }
-  const double t0 = now_s();
-  TMI_HIP(hipSetDevice(s->device));
-  int rc = ensure_track_outputs(s);
-  if (rc) return rc;
-  hipEvent_t ea, eb;
-  TMI_HIP(hipEventCreate(&ea));
-  TMI_HIP(hipEventCreate(&eb));
-  TMI_HIP(hipEventRecord(ea, s->stream));
-  prepare_cameras(s, s->v.ext, s->v.intr, s->v.prep);
-  if (st.nslices > 0)
-    hipLaunchKernelGGL(track_stats_kernel, dim3(s->nblocks_tracks), dim3(256), 0, s->stream, s->v, s->v.prep,
-                       s->d_trk_iter, s->d_trk_mean);
-  TMI_HIP(hipEventRecord(eb, s->stream));
-  const int Np = st.Np_total, Nc = st.Nc;
-  hipStream_t stream = s->stream;
-  // static per handle: every view's tracks sorted by track index (device radix sort)
-  if (!s->d_vt_ptr) {
-    if ((rc = dev_alloc(s, &s->d_vt_ptr, (size_t)Nc + 2))) return rc;
-    if ((rc = dev_alloc(s, &s->d_vt_keys, (size_t)std::max<int64_t>(st.No_pad, 1)))) return rc;
-    if ((rc = dev_alloc(s, &s->d_vbox, (size_t)std::max(Nc, 1) * 4))) return rc;
-    if ((rc = dev_alloc(s, &s->d_cell_off, (size_t)Nc + 2))) return rc;
-    if ((rc = dev_alloc(s, &s->d_sel, (size_t)std::max(Np, 1)))) return rc;
-    if ((rc = dev_alloc(s, &s->d_view_mask, (size_t)std::max(Nc, 1)))) return rc;
-    if ((rc = dev_alloc(s, &s->d_vcount, (size_t)2 * std::max(Nc, 1)))) return rc;
-    if (st.No_pad > 0) {
-      unsigned long long* keys_in = nullptr;
-      TMI_HIP(hipMalloc((void**)&keys_in, (size_t)st.No_pad * sizeof(unsigned long long)));
-      hipLaunchKernelGGL(select_keys_kernel, dim3(s->nblocks_slices), dim3(256), 0, stream, s->v, s->d_pt_orig, keys_in);
-      size_t tmp_bytes = 0;
-      hipcub::DeviceRadixSort::SortKeys(nullptr, tmp_bytes, keys_in, s->d_vt_keys, (int)st.No_pad, 0, 64, stream);
-      void* tmp = nullptr;
-      TMI_HIP(hipMalloc(&tmp, std::max<size_t>(tmp_bytes, 16)));
-      hipcub::DeviceRadixSort::SortKeys(tmp, tmp_bytes, keys_in, s->d_vt_keys, (int)st.No_pad, 0, 64, stream);
-      TMI_HIP(hipStreamSynchronize(stream));
-      hipFree(tmp);
-      hipFree(keys_in);
-    }
-    hipLaunchKernelGGL(select_view_ptr_kernel, dim3((Nc + 1 + 255) / 256), dim3(256), 0, stream, s->d_vt_keys,
-                       (long long)st.No_pad, Nc, s->d_vt_ptr);
-  }
-  SelectView S;
-  memset(&S, 0, sizeof(S));
-  S.Nc = Nc;
-  S.Np_total = Np;
-  S.view_mask = nullptr;
-  if (view_mask && Nc > 0) {
-    TMI_HIP(hipMemcpyAsync(s->d_view_mask, view_mask, (size_t)Nc, hipMemcpyHostToDevice, stream));
-    S.view_mask = s->d_view_mask;
-  }
-  S.pt_orig = s->d_pt_orig;
-  S.cnt = s->d_trk_iter;
-  S.mean = s->d_trk_mean;
-  S.long_thr = long_track_length_threshold;
-  S.inv_cell = 1.0 / image_grid_cell_size_pixels;
-  S.vbox = s->d_vbox;
-  S.cell_off = s->d_cell_off;
-  S.sel = s->d_sel;
-  S.counters = s->d_counters;
-  const int nb_init = (std::max(std::max(Nc, Np), 4) + 255) / 256;
-  hipLaunchKernelGGL(select_init_kernel, dim3(nb_init), dim3(256), 0, stream, S);
-  if (st.nslices > 0) hipLaunchKernelGGL(select_bounds_kernel, dim3(s->nblocks_tracks), dim3(256), 0, stream, s->v, S);
-  hipLaunchKernelGGL(select_offsets_kernel, dim3(1), dim3(1024), 0, stream, S);
-  TMI_HIP(hipMemcpyAsync(s->h_cell_total, s->d_cell_off + Nc, sizeof(long long), hipMemcpyDeviceToHost, stream));
-  TMI_HIP(hipStreamSynchronize(stream));
-  const long long ncells = *s->h_cell_total;
-  if (ncells > ((long long)1 << 31)) {
-    g_last_error = s->error = "track selection: the image grids need more than 2^31 cells (cell size too small "
-                              "for the pixel range of the features)";
-    hipEventDestroy(ea);
-    hipEventDestroy(eb);
-    return TMI_BA_ERR_UNSUPPORTED;
-  }
-  if (ncells > s->cell_capacity) {
-    for (void* p : s->cell_allocs) hipFree(p);
-    s->cell_allocs.clear();
-    s->cell_capacity = 0;
-    const size_t cap = (size_t)(ncells + ncells / 4 + 1024);
-    TMI_HIP(hipMalloc((void**)&s->d_cell_len, cap * sizeof(unsigned)));
-    s->cell_allocs.push_back(s->d_cell_len);
-    TMI_HIP(hipMalloc((void**)&s->d_cell_err, cap * sizeof(unsigned long long)));
-    s->cell_allocs.push_back(s->d_cell_err);
-    TMI_HIP(hipMalloc((void**)&s->d_cell_trk, cap * sizeof(unsigned)));
-    s->cell_allocs.push_back(s->d_cell_trk);
-    s->cell_capacity = (long long)cap;
-  }
-  S.cell_len = s->d_cell_len;
-  S.cell_err = s->d_cell_err;
-  S.cell_trk = s->d_cell_trk;
-  if (ncells > 0) {
-    const unsigned nbc = (unsigned)((ncells + 255) / 256);
-    hipLaunchKernelGGL(select_fill_cells_kernel, dim3(nbc), dim3(256), 0, stream, S, ncells);
-    hipLaunchKernelGGL(select_cells_kernel<1>, dim3(s->nblocks_tracks), dim3(256), 0, stream, s->v, S);
-    hipLaunchKernelGGL(select_cells_kernel<2>, dim3(s->nblocks_tracks), dim3(256), 0, stream, s->v, S);
-    hipLaunchKernelGGL(select_cells_kernel<3>, dim3(s->nblocks_tracks), dim3(256), 0, stream, s->v, S);
-    hipLaunchKernelGGL(select_mark_kernel, dim3(nbc), dim3(256), 0, stream, S, ncells);
-  }
-  if (Nc > 0 && st.No_pad > 0) {
-    hipLaunchKernelGGL(select_view_count_kernel, dim3(Nc), dim3(256), 0, stream, S, s->d_vt_keys, s->d_vt_ptr, s->d_vcount);
-    // the flags of all tracks as a bit vector in LDS when they fit beside the kernel's static 4 KB
-    const size_t bit_bytes = ((size_t)Np + 31) / 32 * 4;
-    if (bit_bytes <= 152 * 1024) {
-      static bool attr_set = false;
-      if (!attr_set) {
-        TMI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&select_topup_kernel<true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
-        attr_set = true;
-      }
-      hipLaunchKernelGGL(select_topup_kernel<true>, dim3(1), dim3(kTopupThreads), bit_bytes, stream, S, s->d_vt_keys,
-                         s->d_vt_ptr, s->d_vcount, s->d_vcount + Nc, min_num_optimized_tracks_per_view);
-    } else {
-      hipLaunchKernelGGL(select_topup_kernel<false>, dim3(1), dim3(kTopupThreads), 0, stream, S, s->d_vt_keys, s->d_vt_ptr,
-                         s->d_vcount, s->d_vcount + Nc, min_num_optimized_tracks_per_view);
-    }
-  }
-  if (Np > 0) hipLaunchKernelGGL(select_finish_kernel, dim3((Np + 255) / 256), dim3(256), 0, stream, S, s->d_out_u8);
-  if ((stats_len || stats_err) && st.Np_pad > 0) {
-    // tracks without observations keep length 0 / NaN error
-    if (stats_len) TMI_HIP(hipMemsetAsync(s->d_out_i32, 0, (size_t)Np * sizeof(int), stream));
-    if (stats_err) TMI_HIP(hipMemsetAsync(s->d_out_f64, 0xff, (size_t)Np * sizeof(double), stream));
-    hipLaunchKernelGGL(scatter_track_stats_kernel, dim3((st.Np_pad + 255) / 256), dim3(256), 0, stream, s->d_pt_orig,
-                       st.Np_pad, s->d_trk_iter, s->d_trk_mean, long_track_length_threshold,
-                       stats_len ? s->d_out_i32 : nullptr, stats_err ? s->d_out_f64 : nullptr);
-  }
-  TMI_HIP(hipMemcpyAsync(s->h_counters, s->d_counters, 4 * sizeof(int), hipMemcpyDeviceToHost, stream));
-  unsigned char* stage_u8 = s->h_stage;
-  int* stage_i32 = reinterpret_cast<int*>(s->h_stage + 4 * (size_t)std::max(Np, 1));
-  double* stage_f64 = reinterpret_cast<double*>(s->h_stage + 8 * (size_t)std::max(Np, 1));
-  if (Np > 0) TMI_HIP(hipMemcpyAsync(stage_u8, s->d_out_u8, (size_t)Np, hipMemcpyDeviceToHost, stream));
-  if (stats_len && Np > 0) TMI_HIP(hipMemcpyAsync(stage_i32, s->d_out_i32, (size_t)Np * sizeof(int), hipMemcpyDeviceToHost, stream));
-  if (stats_err && Np > 0) TMI_HIP(hipMemcpyAsync(stage_f64, s->d_out_f64, (size_t)Np * sizeof(double), hipMemcpyDeviceToHost, stream));
-  TMI_HIP(hipStreamSynchronize(stream));
-  if (Np > 0) memcpy(selected, stage_u8, (size_t)Np);
-  if (stats_len && Np > 0) memcpy(stats_len, stage_i32, (size_t)Np * sizeof(int));
-  if (stats_err && Np > 0) memcpy(stats_err, stage_f64, (size_t)Np * sizeof(double));
-  float ms = 0.f;
-  hipEventElapsedTime(&ms, ea, eb);
-  hipEventDestroy(ea);
-  hipEventDestroy(eb);
-  sum->kernel_seconds = ms * 1e-3;
-  if (stats_err)  // 0xff.. is a NaN pattern; make it the quiet NaN the host path produced
-    for (const int p : st.unobserved) stats_err[p] = std::nan("");
-  sum->num_tracks = Np;
-  sum->num_selected_grid = s->h_counters[0];
-  sum->num_selected = s->h_counters[1];
-  sum->seconds = now_s() - t0;
-  return TMI_BA_OK;
-}
-
-int32_t tmi_ba_select_good_tracks(const tmi_ba_problem* P, int32_t device,
-                                  int32_t long_track_length_threshold,
-                                  int32_t image_grid_cell_size_pixels,
-                                  int32_t min_num_optimized_tracks_per_view,
-                                  const uint8_t* view_mask, uint8_t* selected,
-                                  int32_t* stats_len, double* stats_err, tmi_ba_select_summary* sum) {
-  if (!P || !sum) return TMI_BA_ERR_INVALID_ARGUMENT;
-  memset(sum, 0, sizeof(*sum));
-  const double t0 = now_s();
-  tmi_ba_options O;
-  tmi_ba_options_init(&O);
-  O.device = device;
-  tmi_ba_solver* s = new tmi_ba_solver();
-  int rc = create_impl(s, P, &O, 0, 1, /*light=*/true);
-  if (rc == TMI_BA_OK)
-    rc = tmi_ba_solver_select_good_tracks(s, long_track_length_threshold, image_grid_cell_size_pixels,
-                                          min_num_optimized_tracks_per_view, view_mask, selected,
-                                          stats_len, stats_err, sum);
-  else
-    g_last_error = s->error;
-  tmi_ba_solver_destroy(s);
-  sum->seconds = now_s() - t0;
-  return rc;
-}
-
-// ---- batched two-view bundle adjustment ------------------------------
-int32_t tmi_ba_adjust_two_views(tmi_ba_two_view_batch* Bh, int32_t point_dof, int32_t max_num_iterations,
-                                int32_t device, int8_t* pair_termination, int32_t* pair_iterations,
-                                double* pair_initial_cost, double* pair_final_cost,
-                                tmi_ba_track_batch_summary* sum) {
-  if (!Bh || !sum) return TMI_BA_ERR_INVALID_ARGUMENT;
-  memset(sum, 0, sizeof(*sum));
-  if ((point_dof != 3 && point_dof != 4) || Bh->num_pairs < 0 || max_num_iterations < 0)
-    return TMI_BA_ERR_INVALID_ARGUMENT;
-  const int P = Bh->num_pairs;
-  if (P > 0 && (!Bh->extrinsics1 || !Bh->extrinsics2 || !Bh->model1 || !Bh->model2 || !Bh->intrinsics1 ||
-                !Bh->intrinsics2 || !Bh->correspondence_ptr))
-    return TMI_BA_ERR_INVALID_ARGUMENT;
-  const double t0 = now_s();
-  const int64_t N = P ? Bh->correspondence_ptr[P] : 0;
-  for (int p = 0; p < P; ++p) {
-    if (Bh->correspondence_ptr[p + 1] < Bh->correspondence_ptr[p] || Bh->model1[p] < 0 || Bh->model1[p] > 4 ||
-        Bh->model2[p] < 0 || Bh->model2[p] > 4)
-      return TMI_BA_ERR_INVALID_ARGUMENT;
-  }
-  if (N > 0 && (!Bh->features1 || !Bh->features2 || !Bh->points)) return TMI_BA_ERR_INVALID_ARGUMENT;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    g_last_error = "no HIP device visible (the device path has no CPU fallback)";
-    return TMI_BA_ERR_NO_DEVICE;
-  }
-  if (device >= ndev) return TMI_BA_ERR_INVALID_ARGUMENT;
-  if (P == 0) return TMI_BA_OK;
-  OneShot sc;
-  OneShot* s = &sc;  // (TMI_HIP reports into s->error)
-  const int rc = [&]() -> int {
-    int rc = s->open(device);
-    if (rc) return rc;
-    std::vector<unsigned char> c1((size_t)P, 1), c2((size_t)P, 1);
-    if (Bh->constant_intrinsics1) c1.assign(Bh->constant_intrinsics1, Bh->constant_intrinsics1 + P);
-    if (Bh->constant_intrinsics2) c2.assign(Bh->constant_intrinsics2, Bh->constant_intrinsics2 + P);
-    TwoViewBatch B;
-    memset(&B, 0, sizeof(B));
-    B.num_pairs = P;
-    double *d_e1, *d_f1, *d_f2;
-    int *d_m1, *d_m2;
-    unsigned char *d_c1, *d_c2;
-    long long* d_cptr;
-    const size_t Nn = (size_t)std::max<int64_t>(N, 1);
-    TMI_HIP(s->upload(&d_e1, Bh->extrinsics1, (size_t)6 * P));
-    TMI_HIP(s->upload(&B.ext2, (const double*)Bh->extrinsics2, (size_t)6 * P));
-    TMI_HIP(s->upload(&d_m1, Bh->model1, (size_t)P));
-    TMI_HIP(s->upload(&d_m2, Bh->model2, (size_t)P));
-    TMI_HIP(s->upload(&B.intr1, (const double*)Bh->intrinsics1, (size_t)10 * P));
-    TMI_HIP(s->upload(&B.intr2, (const double*)Bh->intrinsics2, (size_t)10 * P));
-    TMI_HIP(s->upload(&d_c1, (const unsigned char*)c1.data(), (size_t)P));
-    TMI_HIP(s->upload(&d_c2, (const unsigned char*)c2.data(), (size_t)P));
-    TMI_HIP(s->upload(&d_cptr, (const long long*)Bh->correspondence_ptr, (size_t)P + 1));
-    TMI_HIP(s->upload(&d_f1, Bh->features1, (size_t)2 * N));
-    TMI_HIP(s->upload(&d_f2, Bh->features2, (size_t)2 * N));
-    TMI_HIP(s->upload(&B.points, (const double*)Bh->points, (size_t)4 * N));
-    TMI_HIP(s->alloc(&B.points_c, 4 * Nn));
-    TMI_HIP(s->alloc(&B.scale_p, 4 * Nn));
-    B.ext1 = d_e1; B.model1 = d_m1; B.model2 = d_m2; B.const1 = d_c1; B.const2 = d_c2; B.corr_ptr = d_cptr;
-    B.feat1 = d_f1; B.feat2 = d_f2;
-    SmallLmOut d;
-    if ((rc = s->alloc_outputs(&d, (size_t)P))) return rc;
-    const SmallLmArgs L = ceres_default_lm_args(max_num_iterations, TMI_BA_LOSS_TRIVIAL, 0.0);
-    TwoViewArgs A;  // (two_view_lm_kernel keeps its own argument layout: two_view_kernels.h)
-    A.point_dof = point_dof;
-    A.max_num_iterations = L.max_num_iterations;
-    A.jacobi_scaling = L.jacobi_scaling;
-    A.function_tolerance = L.function_tolerance;
-    A.gradient_tolerance = L.gradient_tolerance;
-    A.parameter_tolerance = L.parameter_tolerance;
-    A.initial_radius = L.initial_radius;
-    A.max_radius = L.max_radius;
-    A.min_radius = L.min_radius;
-    A.min_relative_decrease = L.min_relative_decrease;
-    A.lm_lo = L.lm_lo;
-    A.lm_hi = L.lm_hi;
-    A.max_num_consecutive_invalid_steps = L.max_num_consecutive_invalid_steps;
-    std::vector<signed char> term;
-    rc = run_small_lm(s, s->stream, d, (size_t)P, nullptr, [&] {
-      if (point_dof == 3)
-        hipLaunchKernelGGL(two_view_lm_kernel<3>, dim3((P + 3) / 4), dim3(256), 0, s->stream, B, A, d.term, d.iters,
-                           d.c0, d.c1, (const long long*)nullptr);
-      else
-        hipLaunchKernelGGL(two_view_lm_kernel<4>, dim3((P + 3) / 4), dim3(256), 0, s->stream, B, A, d.term, d.iters,
-                           d.c0, d.c1, (const long long*)nullptr);
-    }, ItemArrays{pair_termination, pair_iterations, pair_initial_cost, pair_final_cost}, sum, &sum->num_tracks, &term);
-    if (rc) return rc;
-    std::vector<double> e2((size_t)6 * P), k1((size_t)10 * P), k2((size_t)10 * P), pts((size_t)4 * N);
-    TMI_HIP(hipMemcpyAsync(e2.data(), B.ext2, e2.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    TMI_HIP(hipMemcpyAsync(k1.data(), B.intr1, k1.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    TMI_HIP(hipMemcpyAsync(k2.data(), B.intr2, k2.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    if (N) TMI_HIP(hipMemcpyAsync(pts.data(), B.points, pts.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    TMI_HIP(hipStreamSynchronize(s->stream));
-    for (int p = 0; p < P; ++p) {
-      if (term[p] != 0 && term[p] != 1) continue;  // IsSolutionUsable: write back
-      for (int a = 0; a < 6; ++a) Bh->extrinsics2[(size_t)6 * p + a] = e2[(size_t)6 * p + a];
-      Bh->intrinsics1[(size_t)10 * p] = k1[(size_t)10 * p];
-      Bh->intrinsics2[(size_t)10 * p] = k2[(size_t)10 * p];
-      for (int64_t q = Bh->correspondence_ptr[p]; q < Bh->correspondence_ptr[p + 1]; ++q)
-        for (int a = 0; a < 4; ++a) Bh->points[4 * q + a] = pts[4 * q + a];
-    }
-    return TMI_BA_OK;
-  }();
-  if (rc) g_last_error = s->error;
-  sum->seconds = now_s() - t0;
-  return rc;
-}
-
-// ---- batched two-view verification BA: triangulate, adjust, filter (two_view_verify_kernels.h) ----
-void tmi_ba_two_view_verification_options_init(tmi_ba_two_view_verification_options* o) {
-  if (!o) return;
-  o->min_num_inlier_matches = 30;
-  o->triangulation_max_reprojection_error = 15.0;
-  o->min_triangulation_angle_degrees = 4.0;
-  o->final_max_reprojection_error = 5.0;
-  o->bundle_adjustment = 1;
-}
-
-int32_t tmi_ba_verify_two_views(tmi_ba_two_view_batch* Bh, const tmi_ba_two_view_verification_options* vo,
-                                int32_t point_dof, int32_t max_num_iterations, int32_t device,
-                                int8_t* correspondence_status, int8_t* pair_status, int32_t* pair_num_verified,
-                                int8_t* pair_termination, int32_t* pair_iterations, double* pair_initial_cost,
-                                double* pair_final_cost, tmi_ba_two_view_verification_summary* sum) {
-  if (!Bh || !vo || !sum) return TMI_BA_ERR_INVALID_ARGUMENT;
-  memset(sum, 0, sizeof(*sum));
-  if ((point_dof != 3 && point_dof != 4) || Bh->num_pairs < 0 || max_num_iterations < 0 ||
-      vo->min_num_inlier_matches < 0)
-    return TMI_BA_ERR_INVALID_ARGUMENT;
-  const int P = Bh->num_pairs;
-  if (P > 0 && (!Bh->extrinsics1 || !Bh->extrinsics2 || !Bh->model1 || !Bh->model2 || !Bh->intrinsics1 ||
-                !Bh->intrinsics2 || !Bh->correspondence_ptr))
-    return TMI_BA_ERR_INVALID_ARGUMENT;
-  const double t0 = now_s();
-  const int64_t N = P ? Bh->correspondence_ptr[P] : 0;
-  if (P > 0 && Bh->correspondence_ptr[0] < 0) return TMI_BA_ERR_INVALID_ARGUMENT;
-  for (int p = 0; p < P; ++p) {
-    if (Bh->correspondence_ptr[p + 1] < Bh->correspondence_ptr[p] || Bh->model1[p] < 0 || Bh->model1[p] > 4 ||
-        Bh->model2[p] < 0 || Bh->model2[p] > 4)
-      return TMI_BA_ERR_INVALID_ARGUMENT;
-  }
-  if (N > 0 && (!Bh->features1 || !Bh->features2 || !Bh->points)) return TMI_BA_ERR_INVALID_ARGUMENT;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    g_last_error = "no HIP device visible (the device path has no CPU fallback)";
-    return TMI_BA_ERR_NO_DEVICE;
-  }
-  if (device >= ndev) return TMI_BA_ERR_INVALID_ARGUMENT;
-  sum->num_pairs = P;
-  if (P == 0) return TMI_BA_OK;
-  OneShot sc;
-  OneShot* s = &sc;  // (TMI_HIP reports into s->error)
-  const int rc = [&]() -> int {
-    int rc = s->open(device);
-    if (rc) return rc;
-    std::vector<unsigned char> c1((size_t)P, 1), c2((size_t)P, 1);
-    if (Bh->constant_intrinsics1) c1.assign(Bh->constant_intrinsics1, Bh->constant_intrinsics1 + P);
-    if (Bh->constant_intrinsics2) c2.assign(Bh->constant_intrinsics2, Bh->constant_intrinsics2 + P);
-    TwoViewBatch B;  // the caller's correspondences: what the triangulation reads
-    memset(&B, 0, sizeof(B));
-    B.num_pairs = P;
-    double *d_e1, *d_f1, *d_f2;
-    int *d_m1, *d_m2;
-    unsigned char *d_c1, *d_c2;
-    long long* d_cptr;
-    const size_t Nn = (size_t)std::max<int64_t>(N, 1);
-    TMI_HIP(s->upload(&d_e1, Bh->extrinsics1, (size_t)6 * P));
-    TMI_HIP(s->upload(&B.ext2, (const double*)Bh->extrinsics2, (size_t)6 * P));
-    TMI_HIP(s->upload(&d_m1, Bh->model1, (size_t)P));
-    TMI_HIP(s->upload(&d_m2, Bh->model2, (size_t)P));
-    TMI_HIP(s->upload(&B.intr1, (const double*)Bh->intrinsics1, (size_t)10 * P));
-    TMI_HIP(s->upload(&B.intr2, (const double*)Bh->intrinsics2, (size_t)10 * P));
-    TMI_HIP(s->upload(&d_c1, (const unsigned char*)c1.data(), (size_t)P));
-    TMI_HIP(s->upload(&d_c2, (const unsigned char*)c2.data(), (size_t)P));
-    TMI_HIP(s->upload(&d_cptr, (const long long*)Bh->correspondence_ptr, (size_t)P + 1));
-    TMI_HIP(s->upload(&d_f1, Bh->features1, (size_t)2 * N));
-    TMI_HIP(s->upload(&d_f2, Bh->features2, (size_t)2 * N));
-    B.ext1 = d_e1; B.model1 = d_m1; B.model2 = d_m2; B.const1 = d_c1; B.const2 = d_c2; B.corr_ptr = d_cptr;
-    B.feat1 = d_f1; B.feat2 = d_f2;
-    TwoViewVerifyBuffers O;
-    TMI_HIP(s->alloc(&O.feat1_c, 2 * Nn));
-    TMI_HIP(s->alloc(&O.feat2_c, 2 * Nn));
-    TMI_HIP(s->alloc(&O.points_c, 4 * Nn));
-    TMI_HIP(s->alloc(&O.orig, Nn));
-    TMI_HIP(s->alloc(&O.corr_end, (size_t)P));
-    TMI_HIP(s->alloc(&O.points_out, 4 * Nn));
-    TMI_HIP(s->alloc(&O.corr_status, Nn));
-    TMI_HIP(s->alloc(&O.pair_status, (size_t)P));
-    TMI_HIP(s->alloc(&O.pair_count, (size_t)P));
-    TMI_HIP(hipMemsetAsync(O.corr_status, 0xff, Nn, s->stream));
-    TwoViewBatch C = B;  // the compacted survivors: what the solve and the last filter read
-    C.feat1 = O.feat1_c;
-    C.feat2 = O.feat2_c;
-    C.points = O.points_c;
-    TMI_HIP(s->alloc(&C.points_c, 4 * Nn));
-    TMI_HIP(s->alloc(&C.scale_p, 4 * Nn));
-    SmallLmOut d;
-    if ((rc = s->alloc_outputs(&d, (size_t)P))) return rc;
-    const SmallLmArgs L = ceres_default_lm_args(max_num_iterations, TMI_BA_LOSS_TRIVIAL, 0.0);
-    TwoViewArgs A;  // (as tmi_ba_adjust_two_views fills it)
-    A.point_dof = point_dof;
-    A.max_num_iterations = L.max_num_iterations;
-    A.jacobi_scaling = L.jacobi_scaling;
-    A.function_tolerance = L.function_tolerance;
-    A.gradient_tolerance = L.gradient_tolerance;
-    A.parameter_tolerance = L.parameter_tolerance;
-    A.initial_radius = L.initial_radius;
-    A.max_radius = L.max_radius;
-    A.min_radius = L.min_radius;
-    A.min_relative_decrease = L.min_relative_decrease;
-    A.lm_lo = L.lm_lo;
-    A.lm_hi = L.lm_hi;
-    A.max_num_consecutive_invalid_steps = L.max_num_consecutive_invalid_steps;
-    TwoViewVerifyArgs V;
-    V.min_matches = vo->min_num_inlier_matches;
-    V.cos_min = std::cos(vo->min_triangulation_angle_degrees * (M_PI / 180.0));
-    V.tri_max_sq = vo->triangulation_max_reprojection_error * vo->triangulation_max_reprojection_error;
-    V.final_max_sq = vo->final_max_reprojection_error * vo->final_max_reprojection_error;
-    const bool ba = vo->bundle_adjustment != 0;
-    // between the launches: the split of kernel_seconds (created last of all that can fail here; destroyed on every
-    // way out below)
-    hipEvent_t e_0 = nullptr, e_tri = nullptr, e_lm = nullptr;
-    {
-      hipError_t ee = hipEventCreate(&e_0);
-      if (ee == hipSuccess) ee = hipEventCreate(&e_tri);
-      if (ee == hipSuccess) ee = hipEventCreate(&e_lm);
-      if (ee != hipSuccess) {
-        if (e_0) hipEventDestroy(e_0);
-        if (e_tri) hipEventDestroy(e_tri);
-        TMI_HIP(ee);
-      }
-    }
-    tmi_ba_track_batch_summary lm_sum;
-    memset(&lm_sum, 0, sizeof(lm_sum));
-    int64_t num_solved = 0;
-    const dim3 grid((P + 3) / 4), block(256);
-    rc = run_small_lm(s, s->stream, d, (size_t)P, nullptr, [&] {
-      hipEventRecord(e_0, s->stream);
-      hipLaunchKernelGGL(two_view_triangulate_kernel, grid, block, 0, s->stream, B, V, O);
-      hipEventRecord(e_tri, s->stream);
-      if (!ba) return;
-      if (point_dof == 3)
-        hipLaunchKernelGGL(two_view_lm_kernel<3>, grid, block, 0, s->stream, C, A, d.term, d.iters, d.c0, d.c1,
-                           (const long long*)O.corr_end);
-      else
-        hipLaunchKernelGGL(two_view_lm_kernel<4>, grid, block, 0, s->stream, C, A, d.term, d.iters, d.c0, d.c1,
-                           (const long long*)O.corr_end);
-      hipEventRecord(e_lm, s->stream);
-      hipLaunchKernelGGL(two_view_accept_kernel, grid, block, 0, s->stream, C, V, O, (const signed char*)d.term);
-    }, ItemArrays{pair_termination, pair_iterations, pair_initial_cost, pair_final_cost}, &lm_sum, &num_solved);
-    float ms_tri = 0.f, ms_lm = 0.f;
-    if (rc == TMI_BA_OK) {
-      hipEventElapsedTime(&ms_tri, e_0, e_tri);
-      if (ba) hipEventElapsedTime(&ms_lm, e_tri, e_lm);
-    }
-    hipEventDestroy(e_0);
-    hipEventDestroy(e_tri);
-    hipEventDestroy(e_lm);
-    if (rc) return rc;
-    sum->kernel_seconds = lm_sum.kernel_seconds;
-    sum->triangulate_kernel_seconds = 1e-3 * ms_tri;
-    sum->solve_kernel_seconds = 1e-3 * ms_lm;
-    sum->accept_kernel_seconds = ba ? std::max(0.0, sum->kernel_seconds - 1e-3 * (ms_tri + ms_lm)) : 0.0;
-    sum->total_iterations = lm_sum.total_iterations;
-    std::vector<double> e2((size_t)6 * P), k1((size_t)10 * P), k2((size_t)10 * P), pts((size_t)4 * N);
-    std::vector<signed char> cst((size_t)N), pst((size_t)P);
-    std::vector<int> cnt((size_t)P);
-    TMI_HIP(hipMemcpyAsync(e2.data(), B.ext2, e2.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    TMI_HIP(hipMemcpyAsync(k1.data(), B.intr1, k1.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    TMI_HIP(hipMemcpyAsync(k2.data(), B.intr2, k2.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    TMI_HIP(hipMemcpyAsync(pst.data(), O.pair_status, (size_t)P, hipMemcpyDeviceToHost, s->stream));
-    TMI_HIP(hipMemcpyAsync(cnt.data(), O.pair_count, (size_t)P * sizeof(int), hipMemcpyDeviceToHost, s->stream));
-    if (N) {
-      TMI_HIP(hipMemcpyAsync(pts.data(), O.points_out, pts.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-      TMI_HIP(hipMemcpyAsync(cst.data(), O.corr_status, (size_t)N, hipMemcpyDeviceToHost, s->stream));
-    }
-    TMI_HIP(hipStreamSynchronize(s->stream));
-    int64_t* const pair_counter[5] = {&sum->num_pairs_verified, &sum->num_pairs_too_few_matches,
-                                      &sum->num_pairs_too_few_triangulated, &sum->num_pairs_failed_ba,
-                                      &sum->num_pairs_too_few_verified};
-    int64_t* const corr_counter[5] = {&sum->num_verified, &sum->num_bad_triangulation_angles,
-                                      &sum->num_failed_triangulations, &sum->num_bad_reprojection_errors,
-                                      &sum->num_bad_final_reprojection_errors};
-    for (int p = 0; p < P; ++p) {
-      const int st = pst[p];
-      ++*pair_counter[st];
-      if (pair_status) pair_status[p] = (int8_t)st;
-      if (pair_num_verified) pair_num_verified[p] = cnt[p];
-      if (ba && (st == 0 || st == 4)) {  // :316-321 run before the last test of VerifyMatches
-        for (int a = 0; a < 6; ++a) Bh->extrinsics2[(size_t)6 * p + a] = e2[(size_t)6 * p + a];
-        Bh->intrinsics1[(size_t)10 * p] = k1[(size_t)10 * p];
-        Bh->intrinsics2[(size_t)10 * p] = k2[(size_t)10 * p];
-      }
-    }
-    for (int64_t q = 0; q < N; ++q) {
-      const int st = cst[q];
-      if (correspondence_status) correspondence_status[q] = (int8_t)st;
-      if (st < 0) continue;
-      ++sum->num_correspondences;
-      ++*corr_counter[st];
-      if (st == 0 || st == 4)
-        for (int a = 0; a < 4; ++a) Bh->points[4 * q + a] = pts[4 * q + a];
-    }
-    return TMI_BA_OK;
-  }();
-  if (rc) g_last_error = s->error;
-  sum->seconds = now_s() - t0;
-  return rc;
-}
 
 int32_t tmi_ba_structure_stats(const tmi_ba_problem* P, int32_t rank, int32_t world, int64_t out[12]) {
   return tmi_ba_structure_stats_for(P, rank, world, /*forms_S=*/1, out);
