@@ -842,6 +842,91 @@ int32_t tmi_ba_optimize_relative_positions(tmi_ba_relative_position_batch* batch
                                            double* pair_cost, int32_t* pair_num_in_front,
                                            tmi_ba_track_batch_summary* summary);
 
+/* ---- the view-pair filters of the global pipeline's edge stage -------------------------------
+ * The view table and edge list of tmi_ba_relative_position_batch with a TwoViewInfo per edge.  No view pairs itself
+ * and no unordered pair appears twice (the reference's edges are keys of a map). */
+typedef struct tmi_ba_view_pair_batch {
+  int32_t num_views;
+  const double*  view_rotation;   /* [3 * num_views] angle-axis, world to camera; for the translation filter
+                                     NULL = pair_position2 is already in the global frame                    */
+  int32_t num_pairs;
+  const int32_t* pair_view1;      /* [num_pairs] */
+  const int32_t* pair_view2;
+  const double*  pair_rotation2;  /* [3 * num_pairs] TwoViewInfo::rotation_2 (orientation filter only)       */
+  const double*  pair_position2;  /* [3 * num_pairs] TwoViewInfo::position_2 (translation filter only)       */
+} tmi_ba_view_pair_batch;
+
+/* FilterViewPairsFromRelativeTranslation, the 1DSfM filter of Wilson and Snavely
+ * (filter_view_pairs_from_relative_translation.cc; called at global_reconstruction_estimator.cc:392).
+ *   1. :68-85    t_e = AngleAxisRotatePoint(-view_rotation[view1], position_2), Ceres' formula with its small-angle
+ *                branch; skipped when view_rotation is NULL.
+ *   2. :180-195  the mean over the edges and the sum of squared deviations / (E - 1), by a reduction of fixed shape.
+ *                E < 2 leaves the variance undefined: TMI_BA_ERR_INVALID_ARGUMENT unless the axes are given.
+ *   3. :216-221  axes_given != 0: the caller's axes as they are (unit norm is the caller's business).  Otherwise
+ *                num_iterations axes are drawn on the host from `seed`: three normal deviates with mean mean[k] and
+ *                standard deviation variance[k] -- the reference passes the variance where RandGaussian takes a
+ *                standard deviation, and so does this call -- then divided by their norm (left alone if that is 0).
+ *                The generator is the engine's own and deterministic in `seed`: state = seed, every 64-bit word is
+ *                one splitmix64 step (Steele, Lea and Flood 2014), u = ((word >> 11) + 0.5) 2^-53, and deviates come
+ *                in Box-Muller pairs sqrt(-2 ln u1) (cos, sin)(2 pi u2), cosine first; component k of axis i is
+ *                deviate 3 i + k (the unused half of the last pair is dropped).  It does not equal
+ *                std::normal_distribution.  The axes used are written to `axes` when that is not NULL.
+ *   4.           per iteration and edge p = t.x a.x + t.y a.y + t.z a.z, left to right, never contracted into FMA.
+ *   5. :114-163  OrderTranslationsFromProjections on the directed graph: p > 0 is view1 -> view2, otherwise
+ *                view2 -> view1 (a zero projection is an edge of weight 0 in the reversed direction and counts as an
+ *                incoming node); weight |p|; a view's initial incoming / outgoing weight is the sequential sum over
+ *                its edges in ascending edge index.  Then one step per view with an edge (:90-110): a remaining
+ *                view without remaining incoming nodes if there is one -- THE ONE WITH THE SMALLEST INDEX, where the
+ *                reference takes the first its hash map yields -- else the remaining view with the largest
+ *                (outgoing_weight + 1.0) / (incoming_weight + 1.0), TIES TO THE SMALLEST INDEX.  The chosen view
+ *                gets the step's number as its order; every remaining neighbour loses the edge's weight from the
+ *                matching sum, and an incoming node where the edge pointed at it.  Views without edges: order -1.
+ *   6. :233-251  d = order[view2] - order[view1]; (d < 0 && p > 0) || (d > 0 && p < 0) contributes |p|.
+ *                pair_bad_weight is the sum of the contributions IN ASCENDING ITERATION ORDER from zero (the
+ *                reference adds in thread-completion order).
+ *   7. :294-304  pair_removed = pair_bad_weight > translation_projection_tolerance * num_iterations.
+ * One workgroup per iteration on the device, all iterations in one launch.
+ * TMI_BA_ERR_INVALID_ARGUMENT, before the device is looked for: a null batch, options or summary, a missing array,
+ * a view index out of range, view1 == view2, a repeated unordered pair, num_iterations < 1, a non-finite rotation,
+ * position or given axis, axes_given without axes.  num_pairs == 0: OK, nothing written.
+ * Every output may be NULL: pair_removed [num_pairs], pair_bad_weight [num_pairs], rotated_translation
+ * [3 * num_pairs], iteration_order [num_iterations * num_views]. */
+typedef struct tmi_ba_translation_filter_options {
+  int32_t  num_iterations;                    /* 48 (the reference recommends more than 40)  */
+  double   translation_projection_tolerance;  /* 0.08, tau of the paper                      */
+  uint64_t seed;                              /* 0                                           */
+} tmi_ba_translation_filter_options;
+void tmi_ba_translation_filter_options_init(tmi_ba_translation_filter_options* options);
+
+typedef struct tmi_ba_view_pair_filter_summary {
+  int32_t num_pairs;
+  int32_t num_pairs_removed;
+  int32_t num_iterations;      /* 0 for the orientation filter                          */
+  int32_t num_views_ordered;   /* views with at least one edge; 0 for the orientation filter */
+  double  seconds;
+  double  kernel_seconds;
+} tmi_ba_view_pair_filter_summary;
+
+int32_t tmi_ba_filter_view_pairs_from_relative_translation(const tmi_ba_view_pair_batch* batch,
+                                                           const tmi_ba_translation_filter_options* options,
+                                                           double* axes, int32_t axes_given, int32_t device,
+                                                           uint8_t* pair_removed, double* pair_bad_weight,
+                                                           double* rotated_translation, int32_t* iteration_order,
+                                                           tmi_ba_view_pair_filter_summary* summary);
+
+/* FilterViewPairsFromOrientation (filter_view_pairs_from_orientation.cc:55-122; called at
+ * global_reconstruction_estimator.cc:360).  Per edge loop = R(-rotation_2) (R(orientation2) R(-orientation1))
+ * (:60-63), removed when the squared rotation angle of loop exceeds the squared threshold in radians (:64-67,
+ * :80-84).  The reference takes the angle as the norm of RotationMatrixToAngleAxis(loop); only that norm is used, and
+ * it is computed here from the matrix as atan2(|skew part| / 2, (trace - 1) / 2), in [0, pi].  pair_angle: radians.
+ * A view without an orientation (:94-103) has no counterpart in a dense table: the host shim removes such edges.
+ * One thread per edge, one launch.  TMI_BA_ERR_INVALID_ARGUMENT as above, and for a negative or NaN threshold (the
+ * reference CHECK_GEs it).  pair_removed and pair_angle [num_pairs] may be NULL. */
+int32_t tmi_ba_filter_view_pairs_from_orientation(const tmi_ba_view_pair_batch* batch,
+                                                  double max_relative_rotation_difference_degrees, int32_t device,
+                                                  uint8_t* pair_removed, double* pair_angle,
+                                                  tmi_ba_view_pair_filter_summary* summary);
+
 /* Test hook: FNV-1a checksums of the static structure arrays resident in HBM -- built in HBM by
  * sort / scan kernels (one rank, no shared intrinsics blocks; TMI_BA_HOST_SETUP=1 disables) or on
  * host threads otherwise.  out[0] = 1 when the device built it; the other slots are documented at

@@ -1,0 +1,42 @@
+"""The view-pair filter shim (theiasfm_amd/host/view_pair_filter_ops.cc) through
+tests/cpp/test_view_pair_filter_shim.cc, compiled here with g++ -Wall -Werror into pytest's tmp_path.  Without a
+device the program checks that both calls leave the edge vector unchanged and return 0; with one (-m gpu) it checks
+the id mapping in ascending order, the missing-orientation rule and the erasure against the C ABI."""
+import os
+import subprocess
+import sys
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import __graft_entry__ as entry  # noqa: E402
+
+LIB = os.path.join(ROOT, "theiasfm_amd", "lib")
+
+
+def _compile(tmp_path):
+    entry.build_engine()
+    exe = str(tmp_path / "test_view_pair_filter_shim")
+    cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-pthread", "-I" + os.path.join(ROOT, "include"), "-o", exe,
+           os.path.join(ROOT, "tests", "cpp", "test_view_pair_filter_shim.cc"),
+           os.path.join(ROOT, "theiasfm_amd", "host", "view_pair_filter_ops.cc"),
+           "-L" + LIB, "-ltheia_mi355_ba", "-Wl,-rpath," + LIB, "-Wl,-rpath,/opt/rocm/lib",
+           "-Wl,-rpath-link,/opt/rocm/lib"]
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr
+    return exe
+
+
+def test_view_pair_filter_shim(tmp_path):
+    """Whatever the machine has: without a device no change and a return of 0, with one the full comparison."""
+    p = subprocess.run([_compile(tmp_path)], capture_output=True, text=True, timeout=600)
+    print(p.stdout, p.stderr)
+    assert p.returncode == 0 and "OK" in p.stdout, p.stdout + p.stderr
+
+
+@pytest.mark.gpu
+def test_view_pair_filter_shim_on_the_device(tmp_path):
+    p = subprocess.run([_compile(tmp_path), "--need-device"], capture_output=True, text=True, timeout=600)
+    print(p.stdout, p.stderr)
+    assert p.returncode == 0 and "view-pair filter shim: OK" in p.stdout, p.stdout + p.stderr

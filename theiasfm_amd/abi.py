@@ -324,6 +324,54 @@ class CRelativePositionBatch(C.Structure):
     ]
 
 
+class CViewPairBatch(C.Structure):
+    """tmi_ba_view_pair_batch (the view-pair filters)."""
+    _fields_ = [
+        ("num_views", C.c_int32),
+        ("view_rotation", C.POINTER(C.c_double)),
+        ("num_pairs", C.c_int32),
+        ("pair_view1", C.POINTER(C.c_int32)),
+        ("pair_view2", C.POINTER(C.c_int32)),
+        ("pair_rotation2", C.POINTER(C.c_double)),
+        ("pair_position2", C.POINTER(C.c_double)),
+    ]
+
+
+class CTranslationFilterOptions(C.Structure):
+    """tmi_ba_translation_filter_options (FilterViewPairsFromRelativeTranslationOptions,
+    filter_view_pairs_from_relative_translation.h:48-65, the rng replaced by a seed)."""
+    _fields_ = [
+        ("num_iterations", C.c_int32),
+        ("translation_projection_tolerance", C.c_double),
+        ("seed", C.c_uint64),
+    ]
+
+
+def translation_filter_options(**overrides) -> CTranslationFilterOptions:
+    """The reference's defaults; mirrors tmi_ba_translation_filter_options_init."""
+    o = CTranslationFilterOptions()
+    o.num_iterations = 48
+    o.translation_projection_tolerance = 0.08
+    o.seed = 0
+    for k, v in overrides.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
+class CViewPairFilterSummary(C.Structure):
+    """tmi_ba_view_pair_filter_summary."""
+    _fields_ = [
+        ("num_pairs", C.c_int32),
+        ("num_pairs_removed", C.c_int32),
+        ("num_iterations", C.c_int32),
+        ("num_views_ordered", C.c_int32),
+        ("seconds", C.c_double),
+        ("kernel_seconds", C.c_double),
+    ]
+
+
 class CSelectSummary(C.Structure):
     _fields_ = [
         ("num_tracks", C.c_int64),
@@ -712,4 +760,50 @@ class RelativePositionBatch:
         b.features1 = _ptr(self.features1, C.c_double)
         b.features2 = _ptr(self.features2, C.c_double)
         b.position2 = _ptr(self.position2, C.c_double)
+        return b
+
+
+@dataclass
+class ViewPairBatch:
+    """A view table and an edge list with a TwoViewInfo per edge (``tmi_ba_view_pair_batch``), for the view-pair
+    filters.  view_rotation None: pair_position2 is already in the global frame (translation filter only)."""
+
+    view_rotation: np.ndarray          # [V, 3] angle-axis, world to camera, or None
+    pair_view1: np.ndarray             # [P] int32
+    pair_view2: np.ndarray
+    pair_rotation2: np.ndarray = None  # [P, 3] TwoViewInfo::rotation_2 (zeros when not given)
+    pair_position2: np.ndarray = None  # [P, 3] TwoViewInfo::position_2 (zeros when not given)
+    num_views: int = None              # given with view_rotation None; else the rows of view_rotation
+
+    def __post_init__(self):
+        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
+        self.pair_view1 = np.ascontiguousarray(self.pair_view1, dtype=np.int32)
+        self.pair_view2 = np.ascontiguousarray(self.pair_view2, dtype=np.int32)
+        n = self.pair_view1.shape[0]
+        if self.view_rotation is not None:
+            self.view_rotation = f64(self.view_rotation).reshape(-1, 3)
+            self.num_views = self.view_rotation.shape[0]
+        elif self.num_views is None:
+            self.num_views = int(max(self.pair_view1.max(initial=-1), self.pair_view2.max(initial=-1))) + 1
+        self.pair_rotation2 = f64(np.zeros((n, 3)) if self.pair_rotation2 is None else self.pair_rotation2).reshape(-1, 3)
+        self.pair_position2 = f64(np.zeros((n, 3)) if self.pair_position2 is None else self.pair_position2).reshape(-1, 3)
+
+    @property
+    def num_pairs(self) -> int:
+        return self.pair_view1.shape[0]
+
+    def copy(self) -> "ViewPairBatch":
+        return ViewPairBatch(None if self.view_rotation is None else self.view_rotation.copy(), self.pair_view1.copy(),
+                             self.pair_view2.copy(), self.pair_rotation2.copy(), self.pair_position2.copy(),
+                             self.num_views)
+
+    def as_c(self) -> CViewPairBatch:
+        b = CViewPairBatch()
+        b.num_views = self.num_views
+        b.view_rotation = _ptr(self.view_rotation, C.c_double)
+        b.num_pairs = self.num_pairs
+        b.pair_view1 = _ptr(self.pair_view1, C.c_int32)
+        b.pair_view2 = _ptr(self.pair_view2, C.c_int32)
+        b.pair_rotation2 = _ptr(self.pair_rotation2, C.c_double)
+        b.pair_position2 = _ptr(self.pair_position2, C.c_double)
         return b

@@ -1352,4 +1352,288 @@ int32_t tmi_ba_verify_two_views(tmi_ba_two_view_batch* Bh, const tmi_ba_two_view
     return TMI_BA_OK;
   });
 }
+
+// ---- the view-pair filters (view_pair_filter_kernels.h) --------------------------------------
+}  // extern "C"
+namespace {
+bool all_finite(const double* x, size_t n) {
+  for (size_t i = 0; i < n; ++i)
+    if (!std::isfinite(x[i])) return false;
+  return true;
+}
+
+// What both filters ask of a batch; `pair_values` is the per-edge array the call reads.  null: fine.
+const char* check_view_pair_batch(const tmi_ba_view_pair_batch* B, bool need_rotation, const double* pair_values) {
+  const int V = B->num_views, E = B->num_pairs;
+  if (V < 0 || E < 0) return "view pairs: negative size";
+  if (need_rotation && V > 0 && !B->view_rotation) return "view pairs: missing view_rotation";
+  if (E > 0 && (!B->pair_view1 || !B->pair_view2 || !pair_values)) return "view pairs: missing array";
+  if (E > (1 << 30)) return "view pairs: more than 2^30 pairs";
+  std::vector<uint64_t> keys((size_t)E);
+  for (int e = 0; e < E; ++e) {
+    const int a = B->pair_view1[e], b = B->pair_view2[e];
+    if (a < 0 || a >= V || b < 0 || b >= V) return "view pairs: view index out of range";
+    if (a == b) return "view pairs: a view paired with itself";
+    keys[e] = ((uint64_t)std::min(a, b) << 32) | (uint64_t)std::max(a, b);
+  }
+  std::sort(keys.begin(), keys.end());
+  if (std::adjacent_find(keys.begin(), keys.end()) != keys.end()) return "view pairs: an unordered pair appears twice";
+  if (B->view_rotation && !all_finite(B->view_rotation, (size_t)3 * V)) return "view pairs: non-finite view_rotation";
+  if (!all_finite(pair_values, (size_t)3 * E)) return "view pairs: non-finite pair value";
+  return nullptr;
+}
+
+// Pinned host memory of one call, freed on every way out.
+struct PinnedWords {
+  void* p = nullptr;
+  PinnedWords() = default;
+  PinnedWords(const PinnedWords&) = delete;
+  PinnedWords& operator=(const PinnedWords&) = delete;
+  hipError_t alloc(size_t bytes) { return hipHostMalloc(&p, bytes, hipHostMallocDefault); }
+  ~PinnedWords() {
+    if (p) hipHostFree(p);
+  }
+};
+
+// The axis generator documented at tmi_ba_filter_view_pairs_from_relative_translation.
+struct AxisDeviates {
+  uint64_t state;
+  double spare = 0.0;
+  bool has_spare = false;
+  explicit AxisDeviates(uint64_t seed) : state(seed) {}
+  double uniform() {
+    uint64_t z = (state += 0x9e3779b97f4a7c15ULL);
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ULL;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebULL;
+    z ^= z >> 31;
+    return ((double)(z >> 11) + 0.5) * (1.0 / 9007199254740992.0);
+  }
+  double normal() {
+    if (has_spare) {
+      has_spare = false;
+      return spare;
+    }
+    const double u1 = uniform(), u2 = uniform();
+    const double r = std::sqrt(-2.0 * std::log(u1)), a = 2.0 * M_PI * u2;
+    spare = r * std::sin(a);
+    has_spare = true;
+    return r * std::cos(a);
+  }
+};
+
+// The view count up to which mfas_order_kernel keeps its state in LDS (TMI_BA_1DSFM_LDS_VIEWS lowers it: a
+// diagnostic knob, so that a small graph reaches the global-memory path).
+int mfas_lds_view_cap() {
+  int cap = kMfasLdsViews;
+  if (const char* e = getenv("TMI_BA_1DSFM_LDS_VIEWS")) cap = std::max(0, std::min(cap, atoi(e)));
+  return cap;
+}
+}  // namespace
+extern "C" {
+
+void tmi_ba_translation_filter_options_init(tmi_ba_translation_filter_options* o) {
+  if (!o) return;
+  o->num_iterations = 48;  // filter_view_pairs_from_relative_translation.h:59-64
+  o->translation_projection_tolerance = 0.08;
+  o->seed = 0;
+}
+
+int32_t tmi_ba_filter_view_pairs_from_relative_translation(const tmi_ba_view_pair_batch* Bh,
+                                                           const tmi_ba_translation_filter_options* opt, double* axes,
+                                                           int32_t axes_given, int32_t device, uint8_t* pair_removed,
+                                                           double* pair_bad_weight, double* rotated_translation,
+                                                           int32_t* iteration_order,
+                                                           tmi_ba_view_pair_filter_summary* sum) {
+  if (!Bh || !opt || !sum) return bad_argument("translation filter: null batch, options or summary");
+  memset(sum, 0, sizeof(*sum));
+  const double t0 = now_s();
+  // argument errors before the device is touched
+  if (const char* why = check_view_pair_batch(Bh, false, Bh->pair_position2)) return bad_argument(why);
+  const int V = Bh->num_views, E = Bh->num_pairs, K = opt->num_iterations;
+  if (K < 1) return bad_argument("translation filter: num_iterations < 1");
+  if (axes_given && !axes) return bad_argument("translation filter: axes_given without axes");
+  if (axes_given && !all_finite(axes, (size_t)3 * K)) return bad_argument("translation filter: non-finite axis");
+  if (!std::isfinite(opt->translation_projection_tolerance))
+    return bad_argument("translation filter: non-finite tolerance");
+  if (!axes_given && E == 1) return bad_argument("translation filter: the variance of one translation is undefined");
+  if ((int64_t)K * V > INT32_MAX) return bad_argument("translation filter: num_iterations * num_views exceeds 2^31");
+  // the CSR of the undirected graph: both rows of an edge in ascending edge index
+  std::vector<int> row_ptr((size_t)V + 1, 0);
+  std::vector<int2> row((size_t)2 * E);
+  int ordered = 0;
+  if (E > 0) {
+    for (int e = 0; e < E; ++e) {
+      row_ptr[(size_t)Bh->pair_view1[e] + 1]++;
+      row_ptr[(size_t)Bh->pair_view2[e] + 1]++;
+    }
+    for (int v = 0; v < V; ++v) {
+      ordered += row_ptr[(size_t)v + 1] > 0;
+      row_ptr[(size_t)v + 1] += row_ptr[v];
+    }
+    std::vector<int> fill(row_ptr.begin(), row_ptr.end() - 1);
+    for (int e = 0; e < E; ++e) {
+      const int a = Bh->pair_view1[e], b = Bh->pair_view2[e];
+      row[(size_t)fill[a]++] = make_int2(b, e << 1);
+      row[(size_t)fill[b]++] = make_int2(a, (e << 1) | 1);
+    }
+  }
+  return one_shot_batch(device, "translation filter: no such device", E, t0, sum, [&](OneShot* s) -> int {
+    ViewPairGraph G;
+    memset(&G, 0, sizeof(G));
+    G.num_views = V;
+    G.num_pairs = E;
+    int *d_v1, *d_v2, *d_ptr, *d_order, *d_counter;
+    int2* d_row;
+    double *d_pos, *d_t, *d_rot = nullptr, *d_axes, *d_contrib, *d_weight, *d_moments;
+    unsigned char *d_flag, *d_state = nullptr;
+    TMI_HIP(s->upload(&d_v1, (const int*)Bh->pair_view1, (size_t)E));
+    TMI_HIP(s->upload(&d_v2, (const int*)Bh->pair_view2, (size_t)E));
+    TMI_HIP(s->upload(&d_ptr, row_ptr.data(), row_ptr.size()));
+    TMI_HIP(s->upload(&d_row, row.data(), row.size()));
+    TMI_HIP(s->upload(&d_pos, Bh->pair_position2, (size_t)3 * E));
+    d_t = d_pos;
+    if (Bh->view_rotation) {
+      TMI_HIP(s->upload(&d_rot, Bh->view_rotation, (size_t)3 * V));
+      TMI_HIP(s->alloc(&d_t, (size_t)3 * E));
+    }
+    TMI_HIP(s->alloc(&d_axes, (size_t)3 * K));
+    TMI_HIP(s->alloc(&d_contrib, (size_t)K * E));
+    TMI_HIP(s->alloc(&d_order, (size_t)K * V));
+    TMI_HIP(s->alloc(&d_weight, (size_t)E));
+    TMI_HIP(s->alloc(&d_flag, (size_t)E));
+    TMI_HIP(s->alloc(&d_moments, 6));
+    TMI_HIP(s->alloc(&d_counter, 1));
+    const bool lds = V <= mfas_lds_view_cap();
+    const size_t state_stride = (((size_t)V + 1) & ~(size_t)1) * 20;
+    if (!lds) TMI_HIP(s->alloc(&d_state, state_stride * K));
+    PinnedWords pinned;  // [0..6) the moments, then the count of removed pairs
+    TMI_HIP(pinned.alloc(8 * sizeof(double)));
+    double* h_moments = static_cast<double*>(pinned.p);
+    int* h_counter = reinterpret_cast<int*>(h_moments + 6);
+    G.pair_view1 = d_v1;
+    G.pair_view2 = d_v2;
+    G.translation = d_t;
+    G.row_ptr = d_ptr;
+    G.row = d_row;
+    StreamTimer timer(s->stream);  // rotate + moments; order_timer below: order + sum (the host draws in between)
+    TMI_HIP(timer.status);
+    const dim3 edge_grid((E + 255) / 256), block(256);
+    TMI_HIP(timer.mark());
+    if (d_rot) hipLaunchKernelGGL(rotate_translations_kernel, edge_grid, block, 0, s->stream, E, d_rot, d_v1, d_pos, d_t);
+    std::vector<double> axes_h((size_t)3 * K);
+    if (axes_given) {
+      TMI_HIP(timer.mark());
+      std::copy(axes, axes + (size_t)3 * K, axes_h.begin());
+    } else {
+      hipLaunchKernelGGL(translation_moments_kernel, dim3(1), block, 0, s->stream, E, d_t, d_moments);
+      TMI_HIP(timer.mark());
+      TMI_HIP(hipGetLastError());
+      TMI_HIP(hipMemcpyAsync(h_moments, d_moments, 6 * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+      TMI_HIP(hipStreamSynchronize(s->stream));
+      // :216-221 -- the variance goes where RandGaussian takes a standard deviation, as in the reference
+      AxisDeviates rng(opt->seed);
+      for (int i = 0; i < K; ++i) {
+        double a[3];
+        for (int k = 0; k < 3; ++k) a[k] = h_moments[k] + h_moments[3 + k] * rng.normal();
+        const double n = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
+        for (int k = 0; k < 3; ++k) axes_h[(size_t)3 * i + k] = n > 0.0 ? a[k] / n : a[k];
+      }
+      if (!all_finite(axes_h.data(), axes_h.size())) {
+        s->error = "translation filter: the drawn axes are not finite (translations too large?)";
+        return TMI_BA_ERR_INVALID_ARGUMENT;
+      }
+    }
+    TMI_HIP(hipMemcpyAsync(d_axes, axes_h.data(), axes_h.size() * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    TMI_HIP(hipMemsetAsync(d_counter, 0, sizeof(int), s->stream));
+    StreamTimer order_timer(s->stream);
+    TMI_HIP(order_timer.status);
+    TMI_HIP(order_timer.mark());
+    if (lds) {
+      static bool attr_set = false;
+      if (!attr_set) {
+        TMI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&mfas_order_kernel<true>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)mfas_lds_bytes(kMfasLdsViews)));
+        attr_set = true;
+      }
+      hipLaunchKernelGGL(mfas_order_kernel<true>, dim3(K), dim3(kMfasThreads), mfas_lds_bytes(V), s->stream, G, d_axes,
+                         ordered, d_state, d_order, d_contrib);
+    } else {
+      hipLaunchKernelGGL(mfas_order_kernel<false>, dim3(K), dim3(kMfasThreads), kMfasLdsHeader, s->stream, G, d_axes,
+                         ordered, d_state, d_order, d_contrib);
+    }
+    const double threshold = opt->translation_projection_tolerance * (double)K;
+    hipLaunchKernelGGL(bad_weight_sum_kernel, edge_grid, block, 0, s->stream, E, K, d_contrib, threshold, d_flag,
+                       d_weight, d_counter);
+    TMI_HIP(order_timer.mark());
+    const hipError_t le = hipGetLastError();
+    hipError_t ce = hipMemcpyAsync(h_counter, d_counter, sizeof(int), hipMemcpyDeviceToHost, s->stream);
+    if (ce == hipSuccess && pair_removed) ce = hipMemcpyAsync(pair_removed, d_flag, (size_t)E, hipMemcpyDeviceToHost, s->stream);
+    if (ce == hipSuccess && pair_bad_weight)
+      ce = hipMemcpyAsync(pair_bad_weight, d_weight, (size_t)E * sizeof(double), hipMemcpyDeviceToHost, s->stream);
+    if (ce == hipSuccess && rotated_translation)
+      ce = hipMemcpyAsync(rotated_translation, d_t, (size_t)3 * E * sizeof(double), hipMemcpyDeviceToHost, s->stream);
+    if (ce == hipSuccess && iteration_order)
+      ce = hipMemcpyAsync(iteration_order, d_order, (size_t)K * V * sizeof(int), hipMemcpyDeviceToHost, s->stream);
+    const hipError_t se = hipStreamSynchronize(s->stream);
+    TMI_HIP(le);
+    TMI_HIP(ce);
+    TMI_HIP(se);
+    if (axes) std::copy(axes_h.begin(), axes_h.end(), axes);
+    sum->num_pairs = E;
+    sum->num_pairs_removed = *h_counter;
+    sum->num_iterations = K;
+    sum->num_views_ordered = ordered;
+    sum->kernel_seconds = timer.seconds(0, 1) + order_timer.seconds();
+    return TMI_BA_OK;
+  });
+}
+
+int32_t tmi_ba_filter_view_pairs_from_orientation(const tmi_ba_view_pair_batch* Bh,
+                                                  double max_relative_rotation_difference_degrees, int32_t device,
+                                                  uint8_t* pair_removed, double* pair_angle,
+                                                  tmi_ba_view_pair_filter_summary* sum) {
+  if (!Bh || !sum) return bad_argument("orientation filter: null batch or summary");
+  memset(sum, 0, sizeof(*sum));
+  const double t0 = now_s();
+  if (const char* why = check_view_pair_batch(Bh, true, Bh->pair_rotation2)) return bad_argument(why);
+  if (!(max_relative_rotation_difference_degrees >= 0.0))  // filter_view_pairs_from_orientation.cc:77
+    return bad_argument("orientation filter: negative threshold");
+  const int V = Bh->num_views, E = Bh->num_pairs;
+  const double max_rad = max_relative_rotation_difference_degrees * (M_PI / 180.0);  // :80-84
+  return one_shot_batch(device, "orientation filter: no such device", E, t0, sum, [&](OneShot* s) -> int {
+    int *d_v1, *d_v2, *d_counter;
+    double *d_rot, *d_rot2, *d_angle;
+    unsigned char* d_flag;
+    TMI_HIP(s->upload(&d_rot, Bh->view_rotation, (size_t)3 * V));
+    TMI_HIP(s->upload(&d_v1, (const int*)Bh->pair_view1, (size_t)E));
+    TMI_HIP(s->upload(&d_v2, (const int*)Bh->pair_view2, (size_t)E));
+    TMI_HIP(s->upload(&d_rot2, Bh->pair_rotation2, (size_t)3 * E));
+    TMI_HIP(s->alloc(&d_angle, (size_t)E));
+    TMI_HIP(s->alloc(&d_flag, (size_t)E));
+    TMI_HIP(s->alloc(&d_counter, 1));
+    PinnedWords pinned;
+    TMI_HIP(pinned.alloc(sizeof(int)));
+    int* h_counter = static_cast<int*>(pinned.p);
+    TMI_HIP(hipMemsetAsync(d_counter, 0, sizeof(int), s->stream));
+    StreamTimer timer(s->stream);
+    TMI_HIP(timer.status);
+    TMI_HIP(timer.mark());
+    hipLaunchKernelGGL(orientation_filter_kernel, dim3((E + 255) / 256), dim3(256), 0, s->stream, E, d_rot, d_v1, d_v2,
+                       d_rot2, max_rad * max_rad, d_flag, d_angle, d_counter);
+    TMI_HIP(timer.mark());
+    const hipError_t le = hipGetLastError();
+    hipError_t ce = hipMemcpyAsync(h_counter, d_counter, sizeof(int), hipMemcpyDeviceToHost, s->stream);
+    if (ce == hipSuccess && pair_removed) ce = hipMemcpyAsync(pair_removed, d_flag, (size_t)E, hipMemcpyDeviceToHost, s->stream);
+    if (ce == hipSuccess && pair_angle)
+      ce = hipMemcpyAsync(pair_angle, d_angle, (size_t)E * sizeof(double), hipMemcpyDeviceToHost, s->stream);
+    const hipError_t se = hipStreamSynchronize(s->stream);
+    TMI_HIP(le);
+    TMI_HIP(ce);
+    TMI_HIP(se);
+    sum->num_pairs = E;
+    sum->num_pairs_removed = *h_counter;
+    sum->kernel_seconds = timer.seconds();
+    return TMI_BA_OK;
+  });
+}
 }  // extern "C"

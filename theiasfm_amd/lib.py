@@ -34,6 +34,8 @@ EXPORTS = (
     "tmi_ba_solver_select_good_tracks", "tmi_ba_select_good_tracks",
     "tmi_ba_adjust_two_views", "tmi_ba_adjust_two_views_angular", "tmi_ba_optimize_relative_positions",
     "tmi_ba_two_view_verification_options_init", "tmi_ba_verify_two_views",
+    "tmi_ba_translation_filter_options_init", "tmi_ba_filter_view_pairs_from_relative_translation",
+    "tmi_ba_filter_view_pairs_from_orientation",
     "tmi_ba_solver_structure_checksums",
     "tmi_ba_solver_operator_info",
 )
@@ -150,6 +152,15 @@ def load():
                                                      C.c_void_p, C.c_void_p, C.c_void_p,
                                                      C.POINTER(abi.CTrackBatchSummary)]
     L.tmi_ba_optimize_relative_positions.restype = C.c_int32
+    PB, PFS = C.POINTER(abi.CViewPairBatch), C.POINTER(abi.CViewPairFilterSummary)
+    L.tmi_ba_translation_filter_options_init.argtypes = [C.POINTER(abi.CTranslationFilterOptions)]
+    L.tmi_ba_translation_filter_options_init.restype = None
+    L.tmi_ba_filter_view_pairs_from_relative_translation.argtypes = [
+        PB, C.POINTER(abi.CTranslationFilterOptions), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+        C.c_void_p, C.c_void_p, PFS]
+    L.tmi_ba_filter_view_pairs_from_relative_translation.restype = C.c_int32
+    L.tmi_ba_filter_view_pairs_from_orientation.argtypes = [PB, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, PFS]
+    L.tmi_ba_filter_view_pairs_from_orientation.restype = C.c_int32
     L.tmi_ba_solver_structure_checksums.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     L.tmi_ba_solver_structure_checksums.restype = C.c_int32
     L.tmi_ba_solver_operator_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
@@ -397,6 +408,51 @@ def optimize_relative_positions(batch: abi.RelativePositionBatch, device: int = 
     if st != 0:
         raise EngineError(st, "tmi_ba_optimize_relative_positions")
     return status, iters, cost, front, ts
+
+
+def filter_view_pairs_from_relative_translation(batch: abi.ViewPairBatch, options=None, axes=None, device: int = -1):
+    """The 1DSfM filter (FilterViewPairsFromRelativeTranslation) on the device.  options: a
+    CTranslationFilterOptions (default: the reference's).  axes: [num_iterations, 3] projection axes to use as they
+    are, or None: the engine draws them from options.seed.
+    Returns (removed [P] uint8, bad_weight [P], rotated_translation [P, 3], iteration_order [iterations, V] int32,
+    axes [iterations, 3] as used, CViewPairFilterSummary)."""
+    L = load()
+    o = options if options is not None else abi.translation_filter_options()
+    K, n, V = max(int(o.num_iterations), 0), batch.num_pairs, batch.num_views
+    given = axes is not None
+    ax = np.ascontiguousarray(axes, dtype=np.float64).reshape(-1, 3).copy() if given else np.zeros((K, 3))
+    if given and ax.shape[0] != K:
+        raise ValueError("axes must hold options.num_iterations rows")
+    cb = batch.as_c()
+    removed = np.zeros(n, dtype=np.uint8)
+    weight = np.zeros(n)
+    rotated = np.zeros((n, 3))
+    order = np.full((K, V), -1, dtype=np.int32)
+    fs = abi.CViewPairFilterSummary()
+    st = L.tmi_ba_filter_view_pairs_from_relative_translation(
+        C.byref(cb), C.byref(o), ax.ctypes.data, 1 if given else 0, int(device), removed.ctypes.data,
+        weight.ctypes.data, rotated.ctypes.data, order.ctypes.data, C.byref(fs))
+    if st != 0:
+        raise EngineError(st, "tmi_ba_filter_view_pairs_from_relative_translation")
+    return removed, weight, rotated, order, ax, fs
+
+
+def filter_view_pairs_from_orientation(batch: abi.ViewPairBatch, max_relative_rotation_difference_degrees: float,
+                                       device: int = -1):
+    """FilterViewPairsFromOrientation on the device.
+    Returns (removed [P] uint8, angle [P] in radians, CViewPairFilterSummary)."""
+    L = load()
+    cb = batch.as_c()
+    n = batch.num_pairs
+    removed = np.zeros(n, dtype=np.uint8)
+    angle = np.zeros(n)
+    fs = abi.CViewPairFilterSummary()
+    st = L.tmi_ba_filter_view_pairs_from_orientation(C.byref(cb), float(max_relative_rotation_difference_degrees),
+                                                     int(device), removed.ctypes.data, angle.ctypes.data,
+                                                     C.byref(fs))
+    if st != 0:
+        raise EngineError(st, "tmi_ba_filter_view_pairs_from_orientation")
+    return removed, angle, fs
 
 
 class Solver:

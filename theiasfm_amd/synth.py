@@ -653,3 +653,53 @@ def make_relative_position_batch(n_pairs: int, seed: int, *, min_corr: int = 30,
     truth = np.einsum("nij,nj->ni", Rm[v1], d / np.linalg.norm(d, axis=1, keepdims=True))
     batch = abi.RelativePositionBatch(aa, v1, v2, ptr, f1, f2, None, model if models else None, K if models else None)
     return batch, truth
+
+
+def make_view_pair_batch(num_views: int, num_valid: int, num_invalid: int, seed: int):
+    """A view graph after the recipe of filter_view_pairs_from_relative_translation_test.cc:59-150 with a numpy
+    generator: view 0 at the origin with identity orientation, the others with angle-axis orientation and position
+    uniform in [-1, 1]^3; a skeletal path (i - 1, i), random extra valid edges (view1 < view2) up to num_valid, then
+    num_invalid edges whose rotation_2 has ones added and whose position_2 is a random unit vector.  A valid edge has
+    rotation_2 = AngleAxis(R2 R1^T) and position_2 = R1 (c2 - c1) / |c2 - c1| (:71-93).
+    Returns (abi.ViewPairBatch, positions [V, 3]); the first num_valid edges are the valid ones."""
+    rng = np.random.default_rng(seed)
+    V = int(num_views)
+    if num_valid < V - 1 or num_valid + num_invalid > V * (V - 1) // 2:
+        raise ValueError("make_view_pair_batch: the edge counts do not fit the view count")
+    aa = rng.uniform(-1.0, 1.0, (V, 3))
+    pos = rng.uniform(-1.0, 1.0, (V, 3))
+    aa[0] = 0.0
+    pos[0] = 0.0
+    Rm = Rotation.from_rotvec(aa).as_matrix()
+
+    def info(a, b):
+        d = pos[b] - pos[a]
+        return Rotation.from_matrix(Rm[b] @ Rm[a].T).as_rotvec(), Rm[a] @ (d / np.linalg.norm(d))
+
+    edges, taken, rot2, pos2 = [], set(), [], []
+    for i in range(1, V):
+        edges.append((i - 1, i))
+        taken.add((i - 1, i))
+    while len(edges) < num_valid:
+        a, b = (int(x) for x in rng.choice(V, 2, replace=False))
+        if a > b or (a, b) in taken:
+            continue
+        edges.append((a, b))
+        taken.add((a, b))
+    for a, b in edges:
+        r, t = info(a, b)
+        rot2.append(r)
+        pos2.append(t)
+    while len(edges) < num_valid + num_invalid:
+        a, b = int(rng.integers(0, V)), int(rng.integers(0, V))
+        if a >= b or (a, b) in taken:
+            continue
+        edges.append((a, b))
+        taken.add((a, b))
+        r, _ = info(a, b)
+        t = rng.uniform(-1.0, 1.0, 3)
+        rot2.append(r + 1.0)
+        pos2.append(t / np.linalg.norm(t))
+    e = np.asarray(edges, dtype=np.int32).reshape(-1, 2)
+    return abi.ViewPairBatch(aa, e[:, 0], e[:, 1], np.asarray(rot2).reshape(-1, 3), np.asarray(pos2).reshape(-1, 3)), pos
+
