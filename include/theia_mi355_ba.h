@@ -927,6 +927,95 @@ int32_t tmi_ba_filter_view_pairs_from_orientation(const tmi_ba_view_pair_batch* 
                                                   uint8_t* pair_removed, double* pair_angle,
                                                   tmi_ba_view_pair_filter_summary* summary);
 
+/* ---- RobustRotationEstimator: global orientations from relative rotations ---------------------
+ * reference: robust_rotation_estimator.cc:66-282 (GlobalRotationEstimatorType::ROBUST_L1L2, the default; Chatterjee and
+ * Govindu, ICCV 2013) with math/l1_solver.h:120-178 and math/rotation.cc:122-132.  The orientations every view-pair
+ * call above takes come out of this one.
+ * The batch is an edge list on a dense view table.  UNLIKE tmi_ba_view_pair_batch the same unordered pair may occur
+ * more than once and in either direction (AddRelativeRotationConstraint, robust_rotation_estimator.h:93-103). */
+typedef struct tmi_ba_relative_rotation_batch {
+  int32_t num_views;
+  int32_t num_pairs;
+  const int32_t* pair_view1;     /* [num_pairs] */
+  const int32_t* pair_view2;
+  const double*  pair_rotation;  /* [3 * num_pairs] angle-axis R_12 = R_2 R_1^T (TwoViewInfo::rotation_2) */
+} tmi_ba_relative_rotation_batch;
+
+/* RobustRotationEstimator::Options (robust_rotation_estimator.h:63-82) with the reference's defaults. */
+typedef struct tmi_ba_robust_rotation_options {
+  int32_t max_num_l1_iterations;            /* 5; 0 skips the L1 phase       */
+  double  l1_step_convergence_threshold;    /* 1e-3                          */
+  int32_t max_num_irls_iterations;          /* 100; 0 skips the IRLS phase   */
+  double  irls_step_convergence_threshold;  /* 1e-3                          */
+  double  irls_loss_parameter_sigma;        /* 5 degrees in radians          */
+} tmi_ba_robust_rotation_options;
+void tmi_ba_robust_rotation_options_init(tmi_ba_robust_rotation_options* options);
+
+typedef struct tmi_ba_robust_rotation_summary {
+  int32_t num_views;
+  int32_t num_pairs;
+  int32_t num_l1_iterations;      /* outer L1 iterations run                                   */
+  int32_t num_admm_iterations;    /* ADMM iterations over all of them                          */
+  int32_t num_irls_iterations;
+  int32_t l1_converged;           /* the L1 phase stopped at its step threshold                */
+  int32_t irls_converged;         /* the IRLS phase stopped at its step threshold              */
+  int32_t num_factorizations;     /* dense Cholesky factorisations of order num_views - 1      */
+  double  seconds;
+  double  kernel_seconds;         /* device time; the sum of the three below                   */
+  double  factor_seconds;         /* Laplacian assembly + factorisation                        */
+  double  substitution_seconds;   /* forward / backward substitution                           */
+  double  graph_seconds;          /* the per-edge and per-view kernels and their reductions    */
+} tmi_ba_robust_rotation_summary;
+
+/* EstimateRotations on the device.  view_rotation [3 * num_views] holds the initial orientations (angle-axis, world to
+ * camera) and receives the result; view `fixed_view` keeps its value (the reference holds fixed whichever view its hash
+ * map yields first).
+ *   1. :101-147  A has a -I3 block at view1 and a +I3 block at view2 of every edge, without the fixed view's columns.
+ *                Free view v has column v - (v > fixed_view); n = num_views - 1.  The IRLS weights are one scalar per
+ *                edge, so A^T W A = L_w (x) I3 with L_w the weighted graph Laplacian without the fixed view's row and
+ *                column: every solve is ONE dense symmetric positive definite system of order n with three right-hand
+ *                sides, factored by the blocked Cholesky of the exact camera solve.  Parallel edges add into L_w in
+ *                ascending edge index.
+ *   2. :256-272  r_e = MultiplyRotations(-o[view2], MultiplyRotations(rotation_e, o[view1])), MultiplyRotations
+ *                (math/rotation.cc:122-132) being Ceres' AngleAxisToRotationMatrix on both, the matrix product and Ceres'
+ *                RotationMatrixToAngleAxis (through the quaternion, as Ceres 1.x).
+ *   3. :149-171  L1 phase: up to max_num_l1_iterations outer iterations of (L1Solver::Solve on b = r, step 4, step 2),
+ *                stopping at average step <= l1_step_convergence_threshold.  The ADMM budget is 5 in the first outer
+ *                iteration and doubles with every further one.  L_1 (unit weights) is factored once for the phase.
+ *      l1_solver.h:120-178, per Solve: z = u = 0; per iteration x = (A^T A)^-1 A^T (b + z - u); Ax_hat = alpha A x +
+ *                (1 - alpha)(z + b); z_old = z; z = Shrinkage(Ax_hat - b + u, 1 / rho); u += Ax_hat - z - b; stop when
+ *                |A x - z - b| < sqrt(3 E) 1e-4 + 1e-2 max(|A x|, |z|, |b|) and |rho A^T (z - z_old)| <
+ *                sqrt(3 n) 1e-4 + 1e-2 |rho A^T u|.  rho = alpha = 1, the tolerances 1e-4 and 1e-2: the reference's
+ *                constants, not options.
+ *   4. :240-252, :274-282  o[v] = MultiplyRotations(o[v], step[v]) for the free views; the average step is the mean of
+ *                |step[v]| over them.
+ *   5. :173-236  IRLS phase: up to max_num_irls_iterations iterations of w_e = sigma / (|r_e|^2 + sigma^2)^2, one
+ *                factorisation of L_w, step = L_w^-1 A^T W r, step 4, step 2, stopping at average step <
+ *                irls_step_convergence_threshold (strictly).
+ *   6.           Fixed orders: edges in the caller's order; every per-view sum over the view's edges from zero in
+ *                ascending edge index; every sum over the edges or the views by a reduction of fixed shape (a binary
+ *                tree over blocks of 256, the block sums strided over 256 accumulators in ascending order, the same
+ *                tree again).  The result is the same bits from call to call.
+ * The loops run on the host; every kernel is a plain grid launch.  A non-positive pivot: TMI_BA_ERR_LINEAR_SOLVER.
+ * n is capped at 11000 (the dense matrix, 8 n^2 bytes, stays under 1 GB; the environment variable
+ * TMI_BA_ROTATION_MAX_ORDER lowers the cap, a diagnostic knob): TMI_BA_ERR_UNSUPPORTED above it, before anything is
+ * allocated.  A sparse factorisation for larger graphs is not provided.
+ * TMI_BA_ERR_INVALID_ARGUMENT, before the device is looked for: a null batch, options, view_rotation or summary, a
+ * missing array, num_pairs == 0 (the reference CHECK_GTs it), a view index out of range, view1 == view2, fixed_view out
+ * of range, a non-finite orientation or relative rotation, a threshold or sigma that is not positive and finite, a
+ * negative iteration count, and a view that the edges do not connect to fixed_view (L_w would be singular; the
+ * reference's callers pass the largest connected component).
+ * On every failure view_rotation and the optional outputs are left as they were.  Optional outputs (each may be NULL):
+ * pair_residual [3 * num_pairs] the final r; l1_admm_iterations / l1_average_step [max_num_l1_iterations] per outer L1
+ * iteration run; irls_average_step / irls_squared_residual [max_num_irls_iterations] the average step and |r|^2 after
+ * every IRLS iteration run. */
+int32_t tmi_ba_estimate_global_rotations_robust(const tmi_ba_relative_rotation_batch* batch,
+                                                const tmi_ba_robust_rotation_options* options, int32_t fixed_view,
+                                                int32_t device, double* view_rotation, double* pair_residual,
+                                                int32_t* l1_admm_iterations, double* l1_average_step,
+                                                double* irls_average_step, double* irls_squared_residual,
+                                                tmi_ba_robust_rotation_summary* summary);
+
 /* Test hook: FNV-1a checksums of the static structure arrays resident in HBM -- built in HBM by
  * sort / scan kernels (one rank, no shared intrinsics blocks; TMI_BA_HOST_SETUP=1 disables) or on
  * host threads otherwise.  out[0] = 1 when the device built it; the other slots are documented at

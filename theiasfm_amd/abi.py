@@ -372,6 +372,62 @@ class CViewPairFilterSummary(C.Structure):
     ]
 
 
+class CRelativeRotationBatch(C.Structure):
+    """tmi_ba_relative_rotation_batch (the rotation estimator)."""
+    _fields_ = [
+        ("num_views", C.c_int32),
+        ("num_pairs", C.c_int32),
+        ("pair_view1", C.POINTER(C.c_int32)),
+        ("pair_view2", C.POINTER(C.c_int32)),
+        ("pair_rotation", C.POINTER(C.c_double)),
+    ]
+
+
+class CRobustRotationOptions(C.Structure):
+    """tmi_ba_robust_rotation_options (RobustRotationEstimator::Options, robust_rotation_estimator.h:63-82)."""
+    _fields_ = [
+        ("max_num_l1_iterations", C.c_int32),
+        ("l1_step_convergence_threshold", C.c_double),
+        ("max_num_irls_iterations", C.c_int32),
+        ("irls_step_convergence_threshold", C.c_double),
+        ("irls_loss_parameter_sigma", C.c_double),
+    ]
+
+
+def robust_rotation_options(**overrides) -> CRobustRotationOptions:
+    """The reference's defaults; mirrors tmi_ba_robust_rotation_options_init."""
+    o = CRobustRotationOptions()
+    o.max_num_l1_iterations = 5
+    o.l1_step_convergence_threshold = 0.001
+    o.max_num_irls_iterations = 100
+    o.irls_step_convergence_threshold = 0.001
+    o.irls_loss_parameter_sigma = 5.0 * (np.pi / 180.0)
+    for k, v in overrides.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
+class CRobustRotationSummary(C.Structure):
+    """tmi_ba_robust_rotation_summary."""
+    _fields_ = [
+        ("num_views", C.c_int32),
+        ("num_pairs", C.c_int32),
+        ("num_l1_iterations", C.c_int32),
+        ("num_admm_iterations", C.c_int32),
+        ("num_irls_iterations", C.c_int32),
+        ("l1_converged", C.c_int32),
+        ("irls_converged", C.c_int32),
+        ("num_factorizations", C.c_int32),
+        ("seconds", C.c_double),
+        ("kernel_seconds", C.c_double),
+        ("factor_seconds", C.c_double),
+        ("substitution_seconds", C.c_double),
+        ("graph_seconds", C.c_double),
+    ]
+
+
 class CSelectSummary(C.Structure):
     _fields_ = [
         ("num_tracks", C.c_int64),
@@ -806,4 +862,34 @@ class ViewPairBatch:
         b.pair_view2 = _ptr(self.pair_view2, C.c_int32)
         b.pair_rotation2 = _ptr(self.pair_rotation2, C.c_double)
         b.pair_position2 = _ptr(self.pair_position2, C.c_double)
+        return b
+
+
+@dataclass
+class RelativeRotationBatch:
+    """An edge list with a relative rotation per edge on a dense view table (``tmi_ba_relative_rotation_batch``), for
+    the rotation estimator.  The same unordered pair may occur more than once and in either direction."""
+
+    num_views: int
+    pair_view1: np.ndarray     # [P] int32
+    pair_view2: np.ndarray
+    pair_rotation: np.ndarray  # [P, 3] angle-axis R_12 = R_2 R_1^T (TwoViewInfo::rotation_2)
+
+    def __post_init__(self):
+        self.num_views = int(self.num_views)
+        self.pair_view1 = np.ascontiguousarray(self.pair_view1, dtype=np.int32)
+        self.pair_view2 = np.ascontiguousarray(self.pair_view2, dtype=np.int32)
+        self.pair_rotation = np.ascontiguousarray(self.pair_rotation, dtype=np.float64).reshape(-1, 3)
+
+    @property
+    def num_pairs(self) -> int:
+        return self.pair_view1.shape[0]
+
+    def as_c(self) -> CRelativeRotationBatch:
+        b = CRelativeRotationBatch()
+        b.num_views = self.num_views
+        b.num_pairs = self.num_pairs
+        b.pair_view1 = _ptr(self.pair_view1, C.c_int32)
+        b.pair_view2 = _ptr(self.pair_view2, C.c_int32)
+        b.pair_rotation = _ptr(self.pair_rotation, C.c_double)
         return b

@@ -185,11 +185,12 @@ __global__ __launch_bounds__(256) void chol_syrk_kernel(double* __restrict__ A, 
 //   backward: x_k = L_kk^-T y_k;  y[j] -= L[panel, j]^T x_k for the columns left of the panel
 // `in` is the working vector (never written inside the panel's own range), `out` receives the solved
 // panel entries -- so no workgroup reads what another one writes.
-template <bool FWD>
+// NRHS right-hand sides in one pass: in / out are [n][NRHS]; every right-hand side sees the arithmetic of NRHS = 1.
+template <bool FWD, int NRHS = 1>
 __global__ __launch_bounds__(256) void chol_subst_kernel(const double* __restrict__ A, int n, int k0,
                                                          double* __restrict__ in, double* __restrict__ out) {
   __shared__ double L[kTile][kTilePitch];
-  __shared__ double xs[kTile];
+  __shared__ double xs[kTile * NRHS];
   const int nb = min(kTile, n - k0);
   for (int e = threadIdx.x; e < kTile * kTile; e += 256) {
     const int r = e / kTile, c = e - r * kTile;
@@ -198,45 +199,65 @@ __global__ __launch_bounds__(256) void chol_subst_kernel(const double* __restric
   __syncthreads();
   if (threadIdx.x < 64) {
     const int lane = threadIdx.x;
-    double wv = lane < nb ? in[k0 + lane] : 0.0;
+    double wv[NRHS];
+#pragma unroll
+    for (int k = 0; k < NRHS; ++k) wv[k] = lane < nb ? in[(size_t)(k0 + lane) * NRHS + k] : 0.0;
     if (FWD) {
       for (int c = 0; c < nb; ++c) {
-        const double xc = __shfl(wv, c, 64) / L[c][c];
-        if (lane == c) wv = xc;
-        if (lane > c) wv -= L[lane][c] * xc;
+#pragma unroll
+        for (int k = 0; k < NRHS; ++k) {
+          const double xc = __shfl(wv[k], c, 64) / L[c][c];
+          if (lane == c) wv[k] = xc;
+          if (lane > c) wv[k] -= L[lane][c] * xc;
+        }
       }
     } else {
       for (int c = nb - 1; c >= 0; --c) {
-        const double xc = __shfl(wv, c, 64) / L[c][c];
-        if (lane == c) wv = xc;
-        if (lane < c) wv -= L[c][lane] * xc;
+#pragma unroll
+        for (int k = 0; k < NRHS; ++k) {
+          const double xc = __shfl(wv[k], c, 64) / L[c][c];
+          if (lane == c) wv[k] = xc;
+          if (lane < c) wv[k] -= L[c][lane] * xc;
+        }
       }
     }
-    xs[lane] = wv;
-    if (blockIdx.x == 0 && lane < nb) out[k0 + lane] = wv;
+#pragma unroll
+    for (int k = 0; k < NRHS; ++k) {
+      xs[lane * NRHS + k] = wv[k];
+      if (blockIdx.x == 0 && lane < nb) out[(size_t)(k0 + lane) * NRHS + k] = wv[k];
+    }
   }
   __syncthreads();
+  double t[NRHS];
+#pragma unroll
+  for (int k = 0; k < NRHS; ++k) t[k] = 0.0;
   if (FWD) {
     const int i = k0 + nb + blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const double* row = A + (size_t)i * n + k0;
-    double t = 0.0;
-    for (int c = 0; c < nb; ++c) t += row[c] * xs[c];
-    in[i] -= t;
+    for (int c = 0; c < nb; ++c) {
+      const double a = row[c];
+#pragma unroll
+      for (int k = 0; k < NRHS; ++k) t[k] += a * xs[c * NRHS + k];
+    }
+#pragma unroll
+    for (int k = 0; k < NRHS; ++k) in[(size_t)i * NRHS + k] -= t[k];
   } else {
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (j >= k0) return;
-    double t = 0.0;
-    for (int c = 0; c < nb; ++c) t += A[(size_t)(k0 + c) * n + j] * xs[c];
-    in[j] -= t;
+    for (int c = 0; c < nb; ++c) {
+      const double a = A[(size_t)(k0 + c) * n + j];
+#pragma unroll
+      for (int k = 0; k < NRHS; ++k) t[k] += a * xs[c * NRHS + k];
+    }
+#pragma unroll
+    for (int k = 0; k < NRHS; ++k) in[(size_t)j * NRHS + k] -= t[k];
   }
 }
 
-// A (n x n, symmetric, row major) is overwritten by its Cholesky factor (lower);
-// x <- A^-1 b.  *flag is set when a pivot is not positive.  tmp: n doubles of scratch.
-// diag: kPanel * (n rounded up to kPanel) doubles of scratch for the factored diagonal blocks.
-inline void dense_cholesky_solve(double* A, int n, const double* b, double* x, double* tmp, double* diag, int* flag,
-                                 hipStream_t st) {
+// A (n x n, symmetric, row major) is overwritten by its Cholesky factor (lower).  *flag is set when a pivot is not
+// positive.  diag: kPanel * (n rounded up to kPanel) doubles of scratch for the factored diagonal blocks.
+inline void dense_cholesky_factor(double* A, int n, double* diag, int* flag, hipStream_t st) {
   auto panel = [&](int k0) {  // factor columns [k0, k0 + kPanel) given all earlier updates
     const int nb = (n - k0 < kPanel) ? n - k0 : kPanel;
     const int rem = n - k0 - nb;
@@ -258,16 +279,28 @@ inline void dense_cholesky_solve(double* A, int n, const double* b, double* x, d
     hipLaunchKernelGGL(chol_syrk_kernel, dim3(nt, nt), dim3(256), 0, st, A, n, k0, kTile, k2, n);
   }
   hipLaunchKernelGGL(chol_diag_store_kernel, dim3((n * kPanel + 255) / 256), dim3(256), 0, st, A, n, diag);
-  // forward on x (working) -> tmp (solved y), backward on tmp (working) -> x
-  hipMemcpyAsync(x, b, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st);
+}
+
+// x <- A^-1 w for NRHS right-hand sides ([n][NRHS]) given the factor in A: forward on w (working, overwritten) -> tmp
+// (the solved y), backward on tmp (working) -> x.  tmp: n * NRHS doubles of scratch.
+template <int NRHS = 1>
+inline void dense_cholesky_substitute(const double* A, int n, double* w, double* x, double* tmp, hipStream_t st) {
   for (int k0 = 0; k0 < n; k0 += kTile) {
     const int nb = (n - k0 < kTile) ? n - k0 : kTile;
     const int rem = n - k0 - nb;
-    hipLaunchKernelGGL(chol_subst_kernel<true>, dim3(1 + (rem + 255) / 256), dim3(256), 0, st, A, n, k0, x, tmp);
+    hipLaunchKernelGGL((chol_subst_kernel<true, NRHS>), dim3(1 + (rem + 255) / 256), dim3(256), 0, st, A, n, k0, w, tmp);
   }
   const int last = ((n - 1) / kTile) * kTile;
   for (int k0 = last; k0 >= 0; k0 -= kTile)
-    hipLaunchKernelGGL(chol_subst_kernel<false>, dim3(1 + (k0 + 255) / 256), dim3(256), 0, st, A, n, k0, tmp, x);
+    hipLaunchKernelGGL((chol_subst_kernel<false, NRHS>), dim3(1 + (k0 + 255) / 256), dim3(256), 0, st, A, n, k0, tmp, x);
+}
+
+// Factor, then x <- A^-1 b (x serves as the forward substitution's working vector).
+inline void dense_cholesky_solve(double* A, int n, const double* b, double* x, double* tmp, double* diag, int* flag,
+                                 hipStream_t st) {
+  dense_cholesky_factor(A, n, diag, flag, st);
+  hipMemcpyAsync(x, b, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st);
+  dense_cholesky_substitute<1>(A, n, x, x, tmp, st);
 }
 
 }  // namespace tmi

@@ -40,6 +40,7 @@
 #include "two_view_verify_kernels.h"
 #include "view_kernels.h"
 #include "view_pair_filter_kernels.h"
+#include "rotation_kernels.h"
 #include "select_kernels.h"
 #include "structure_gpu.h"
 #include <hipcub/hipcub.hpp>

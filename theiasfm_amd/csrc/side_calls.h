@@ -59,7 +59,7 @@ struct OneShot {
 // mark b once the stream has been synchronised (0 where the runtime cannot tell).  The events are destroyed on every
 // way out.
 struct StreamTimer {
-  static constexpr int kMaxMarks = 3;
+  static constexpr int kMaxMarks = 4;
   hipStream_t stream;
   hipEvent_t ev[kMaxMarks] = {};
   hipError_t status = hipSuccess;  // of creating the events: TMI_HIP(timer.status) before the first mark
@@ -1633,6 +1633,327 @@ int32_t tmi_ba_filter_view_pairs_from_orientation(const tmi_ba_view_pair_batch* 
     sum->num_pairs = E;
     sum->num_pairs_removed = *h_counter;
     sum->kernel_seconds = timer.seconds();
+    return TMI_BA_OK;
+  });
+}
+}  // extern "C"
+
+// ---- RobustRotationEstimator (rotation_kernels.h) ----------------------------------------------
+namespace {
+// The largest order n = V - 1 the call takes (TMI_BA_ROTATION_MAX_ORDER lowers it: a diagnostic knob, so that a small
+// graph reaches the refusal).
+int rotation_order_cap() {
+  int cap = kRotationMaxOrder;
+  if (const char* e = getenv("TMI_BA_ROTATION_MAX_ORDER")) cap = std::max(0, std::min(cap, atoi(e)));
+  return cap;
+}
+
+// What the rotation estimator asks of its arguments; null: fine.
+const char* check_rotation_arguments(const tmi_ba_relative_rotation_batch* B, const tmi_ba_robust_rotation_options* o,
+                                     int fixed_view, const double* view_rotation) {
+  const int V = B->num_views, E = B->num_pairs;
+  if (V < 0 || E < 0) return "robust rotations: negative size";
+  if (E == 0) return "robust rotations: no relative rotation (the reference CHECK_GTs the number of constraints)";
+  if (!B->pair_view1 || !B->pair_view2 || !B->pair_rotation) return "robust rotations: missing array";
+  if (fixed_view < 0 || fixed_view >= V) return "robust rotations: fixed_view out of range";
+  if (!(o->l1_step_convergence_threshold > 0.0) || !std::isfinite(o->l1_step_convergence_threshold) ||
+      !(o->irls_step_convergence_threshold > 0.0) || !std::isfinite(o->irls_step_convergence_threshold))
+    return "robust rotations: a step threshold that is not positive and finite";
+  if (!(o->irls_loss_parameter_sigma > 0.0) || !std::isfinite(o->irls_loss_parameter_sigma))
+    return "robust rotations: sigma is not positive and finite";
+  if (o->max_num_l1_iterations < 0 || o->max_num_irls_iterations < 0)
+    return "robust rotations: negative iteration count";
+  // union-find: every view must reach fixed_view
+  std::vector<int> parent((size_t)V);
+  for (int v = 0; v < V; ++v) parent[v] = v;
+  auto find = [&](int v) {
+    while (parent[v] != v) v = parent[v] = parent[parent[v]];
+    return v;
+  };
+  for (int e = 0; e < E; ++e) {
+    const int a = B->pair_view1[e], b = B->pair_view2[e];
+    if (a < 0 || a >= V || b < 0 || b >= V) return "robust rotations: view index out of range";
+    if (a == b) return "robust rotations: a view paired with itself";
+    const int ra = find(a), rb = find(b);
+    if (ra != rb) parent[std::max(ra, rb)] = std::min(ra, rb);
+  }
+  if (!all_finite(view_rotation, (size_t)3 * V)) return "robust rotations: non-finite view_rotation";
+  if (!all_finite(B->pair_rotation, (size_t)3 * E)) return "robust rotations: non-finite pair_rotation";
+  const int root = find(fixed_view);
+  for (int v = 0; v < V; ++v)
+    if (find(v) != root) return "robust rotations: a view is not connected to fixed_view";
+  return nullptr;
+}
+}  // namespace
+extern "C" {
+
+void tmi_ba_robust_rotation_options_init(tmi_ba_robust_rotation_options* o) {
+  if (!o) return;
+  o->max_num_l1_iterations = 5;  // robust_rotation_estimator.h:63-82
+  o->l1_step_convergence_threshold = 0.001;
+  o->max_num_irls_iterations = 100;
+  o->irls_step_convergence_threshold = 0.001;
+  o->irls_loss_parameter_sigma = 5.0 * (M_PI / 180.0);
+}
+
+int32_t tmi_ba_estimate_global_rotations_robust(const tmi_ba_relative_rotation_batch* Bh,
+                                                const tmi_ba_robust_rotation_options* opt, int32_t fixed_view,
+                                                int32_t device, double* view_rotation, double* pair_residual,
+                                                int32_t* l1_admm_iterations, double* l1_average_step,
+                                                double* irls_average_step, double* irls_squared_residual,
+                                                tmi_ba_robust_rotation_summary* sum) {
+  if (!Bh || !opt || !view_rotation || !sum)
+    return bad_argument("robust rotations: null batch, options, view_rotation or summary");
+  memset(sum, 0, sizeof(*sum));
+  const double t0 = now_s();
+  // argument errors before the device is touched
+  if (const char* why = check_rotation_arguments(Bh, opt, fixed_view, view_rotation)) return bad_argument(why);
+  const int V = Bh->num_views, E = Bh->num_pairs, n = V - 1;
+  if (n > rotation_order_cap()) {
+    g_last_error = "robust rotations: num_views - 1 exceeds the dense solver's cap (see the header)";
+    return TMI_BA_ERR_UNSUPPORTED;
+  }
+  if (E > (1 << 30)) return bad_argument("robust rotations: more than 2^30 pairs");
+  // the CSR of the undirected graph in ascending edge index, and per free view the entries with a free neighbour
+  // sorted by (neighbour, edge) for the Laplacian
+  auto column_of = [&](int v) { return v == fixed_view ? -1 : v - (v > fixed_view); };
+  std::vector<int> row_ptr((size_t)V + 1, 0), lap_ptr((size_t)n + 1, 0);
+  std::vector<int2> row((size_t)2 * E), lap_row;
+  for (int e = 0; e < E; ++e) {
+    row_ptr[(size_t)Bh->pair_view1[e] + 1]++;
+    row_ptr[(size_t)Bh->pair_view2[e] + 1]++;
+  }
+  for (int v = 0; v < V; ++v) row_ptr[(size_t)v + 1] += row_ptr[v];
+  {
+    std::vector<int> fill(row_ptr.begin(), row_ptr.end() - 1);
+    for (int e = 0; e < E; ++e) {
+      const int a = Bh->pair_view1[e], b = Bh->pair_view2[e];
+      row[(size_t)fill[a]++] = make_int2(b, e << 1);
+      row[(size_t)fill[b]++] = make_int2(a, (e << 1) | 1);
+    }
+    lap_row.reserve((size_t)2 * E);
+    for (int c = 0; c < n; ++c) {
+      const int v = c + (c >= fixed_view);
+      const size_t first = lap_row.size();
+      for (int r = row_ptr[v]; r < row_ptr[(size_t)v + 1]; ++r) {
+        const int nc = column_of(row[r].x);
+        if (nc >= 0) lap_row.push_back(make_int2(nc, row[r].y >> 1));
+      }
+      std::sort(lap_row.begin() + first, lap_row.end(),
+                [](const int2& p, const int2& q) { return p.x != q.x ? p.x < q.x : p.y < q.y; });
+      lap_ptr[(size_t)c + 1] = (int)lap_row.size();
+    }
+  }
+  const int L1 = opt->max_num_l1_iterations, IR = opt->max_num_irls_iterations;
+  std::vector<int> admm_trace;
+  std::vector<double> l1_trace, irls_trace, irls_sq_trace;
+  return one_shot_batch(device, "robust rotations: no such device", E, t0, sum, [&](OneShot* s) -> int {
+    RotationGraph G;
+    memset(&G, 0, sizeof(G));
+    G.num_views = V;
+    G.num_pairs = E;
+    G.fixed_view = fixed_view;
+    int *d_v1, *d_v2, *d_ptr, *d_lptr, *d_flag;
+    int2 *d_row, *d_lrow;
+    double *d_rel, *d_o, *d_r, *d_w, *d_z, *d_u, *d_dz, *d_rhs, *d_tmp, *d_x, *d_diag_w, *d_A, *d_cdiag, *d_part, *d_norms;
+    TMI_HIP(s->upload(&d_v1, (const int*)Bh->pair_view1, (size_t)E));
+    TMI_HIP(s->upload(&d_v2, (const int*)Bh->pair_view2, (size_t)E));
+    TMI_HIP(s->upload(&d_ptr, row_ptr.data(), row_ptr.size()));
+    TMI_HIP(s->upload(&d_row, row.data(), row.size()));
+    TMI_HIP(s->upload(&d_lptr, lap_ptr.data(), lap_ptr.size()));
+    TMI_HIP(s->upload(&d_lrow, lap_row.data(), lap_row.size()));
+    TMI_HIP(s->upload(&d_rel, Bh->pair_rotation, (size_t)3 * E));
+    TMI_HIP(s->upload(&d_o, (const double*)view_rotation, (size_t)3 * V));
+    TMI_HIP(s->alloc(&d_r, (size_t)3 * E));
+    TMI_HIP(s->alloc(&d_w, (size_t)E));
+    TMI_HIP(s->alloc(&d_z, (size_t)3 * E));
+    TMI_HIP(s->alloc(&d_u, (size_t)3 * E));
+    TMI_HIP(s->alloc(&d_dz, (size_t)3 * E));
+    TMI_HIP(s->alloc(&d_rhs, (size_t)3 * n));
+    TMI_HIP(s->alloc(&d_tmp, (size_t)3 * n));
+    TMI_HIP(s->alloc(&d_x, (size_t)3 * n));
+    TMI_HIP(s->alloc(&d_diag_w, (size_t)n));
+    TMI_HIP(s->alloc(&d_A, (size_t)n * n));
+    TMI_HIP(s->alloc(&d_cdiag, (size_t)kPanel * ((size_t)(n + kPanel - 1) / kPanel) * kPanel));
+    const int nbE = (E + 255) / 256, nbV = (n + 255) / 256;
+    TMI_HIP(s->alloc(&d_part, (size_t)4 * nbE + (size_t)3 * nbV));
+    TMI_HIP(s->alloc(&d_norms, 8));
+    TMI_HIP(s->alloc(&d_flag, 1));
+    double *p_r = d_part, *p_ax = p_r + nbE, *p_z = p_ax + nbE, *p_rr = p_z + nbE, *p_s = p_rr + nbE, *p_t = p_s + nbV,
+           *p_step = p_t + nbV;
+    PinnedWords pinned;  // [0..5) the ADMM norms or (|r|^2, the step sum), then the pivot flag
+    TMI_HIP(pinned.alloc(8 * sizeof(double)));
+    double* h_norms = static_cast<double*>(pinned.p);
+    int* h_flag = reinterpret_cast<int*>(h_norms + 6);
+    G.pair_view1 = d_v1;
+    G.pair_view2 = d_v2;
+    G.relative = d_rel;
+    G.row_ptr = d_ptr;
+    G.row = d_row;
+    G.lap_ptr = d_lptr;
+    G.lap_row = d_lrow;
+    TMI_HIP(hipMemsetAsync(d_flag, 0, sizeof(int), s->stream));
+    hipStream_t st = s->stream;
+    const dim3 edge_grid(nbE), view_grid(nbV), block(256);
+    const double sigma = opt->irls_loss_parameter_sigma;
+    // device time in three classes; every section ends in a fetch(), which synchronises
+    StreamTimer timer(st, StreamTimer::kMaxMarks);
+    TMI_HIP(timer.status);
+    enum { kFactor = 0, kSubst = 1, kGraph = 2 };
+    double seconds[3] = {0.0, 0.0, 0.0};
+    int section[3] = {kGraph, kGraph, kGraph};  // what runs between marks 0-1, 1-2 and 2-3
+    // the sums of `count` quantities into h_norms, and the pivot flag, then the time of the marked sections
+    auto fetch = [&](const ReduceJobs& jobs, int count) -> int {
+      hipLaunchKernelGGL(reduce_partials_kernel, dim3(count), block, 0, st, jobs, d_norms);
+      TMI_HIP(timer.mark());
+      const hipError_t le = hipGetLastError();
+      hipError_t ce = hipMemcpyAsync(h_norms, d_norms, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, st);
+      if (ce == hipSuccess) ce = hipMemcpyAsync(h_flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, st);
+      const hipError_t se = hipStreamSynchronize(st);
+      TMI_HIP(le);
+      TMI_HIP(ce);
+      TMI_HIP(se);
+      for (int m = 0; m + 1 < timer.marked; ++m) seconds[section[m]] += timer.seconds(m, m + 1);
+      timer.marked = 0;
+      return TMI_BA_OK;
+    };
+    auto assemble_and_factor = [&](const double* w, const double* diag_w) {
+      hipLaunchKernelGGL(laplacian_assemble_kernel, dim3(n), block, 0, st, G, n, w, diag_w, d_A);
+      dense_cholesky_factor(d_A, n, d_cdiag, d_flag, st);
+      sum->num_factorizations++;
+    };
+    auto residuals = [&]() {
+      hipLaunchKernelGGL(rotation_residual_kernel, edge_grid, block, 0, st, G, d_o, sigma, d_r, d_w, p_rr);
+    };
+    const char* pivot = "robust rotations: a pivot of the Laplacian's Cholesky factorisation is not positive";
+    ReduceJobs jobs;
+    memset(&jobs, 0, sizeof(jobs));
+    int rc;
+
+    // ---- ComputeResiduals, and the factorisation of the L1 phase (:149-155) ----
+    TMI_HIP(timer.mark());
+    if (L1 > 0) assemble_and_factor(nullptr, nullptr);
+    TMI_HIP(timer.mark());
+    section[0] = kFactor;
+    section[1] = kGraph;
+    residuals();
+    jobs.part[0] = p_rr;
+    jobs.count[0] = nbE;
+    if ((rc = fetch(jobs, 1))) return rc;
+    if (*h_flag) {
+      s->error = pivot;
+      return TMI_BA_ERR_LINEAR_SOLVER;
+    }
+    double r_sq = h_norms[0];
+
+    // ---- SolveL1Regression (:156-169) ----
+    const double rho = 1.0, alpha = 1.0, abs_tol = 1e-4, rel_tol = 1e-2;  // l1_solver.h:89-98
+    const double primal_abs = std::sqrt(3.0 * (double)E) * abs_tol, dual_abs = std::sqrt(3.0 * (double)n) * abs_tol;
+    int budget = 5;
+    for (int outer = 0; outer < L1; ++outer) {
+      const double rhs_norm = std::sqrt(r_sq);
+      TMI_HIP(timer.mark());
+      TMI_HIP(hipMemsetAsync(d_z, 0, (size_t)3 * E * sizeof(double), st));
+      TMI_HIP(hipMemsetAsync(d_u, 0, (size_t)3 * E * sizeof(double), st));
+      TMI_HIP(hipMemsetAsync(d_dz, 0, (size_t)3 * E * sizeof(double), st));
+      hipLaunchKernelGGL(admm_view_kernel, view_grid, block, 0, st, G, n, rho, d_r, d_z, d_u, d_dz, d_rhs, p_s, p_t);
+      int ran = 0;
+      for (int it = 0; it < budget; ++it) {
+        TMI_HIP(timer.mark());  // (the first iteration's second mark: the section before it is the set-up above)
+        section[0] = kGraph;
+        section[timer.marked - 1] = kSubst;
+        section[timer.marked] = kGraph;
+        dense_cholesky_substitute<3>(d_A, n, d_rhs, d_x, d_tmp, st);
+        TMI_HIP(timer.mark());
+        hipLaunchKernelGGL(admm_edge_kernel, edge_grid, block, 0, st, G, rho, alpha, d_x, d_r, d_z, d_u, d_dz, p_r, p_ax,
+                           p_z);
+        hipLaunchKernelGGL(admm_view_kernel, view_grid, block, 0, st, G, n, rho, d_r, d_z, d_u, d_dz, d_rhs, p_s, p_t);
+        const double* parts[5] = {p_r, p_ax, p_z, p_s, p_t};
+        for (int q = 0; q < 5; ++q) {
+          jobs.part[q] = parts[q];
+          jobs.count[q] = q < 3 ? nbE : nbV;
+        }
+        if ((rc = fetch(jobs, 5))) return rc;
+        ++ran;
+        const double r_norm = std::sqrt(h_norms[0]), s_norm = std::sqrt(h_norms[3]);
+        const double max_norm = std::max({std::sqrt(h_norms[1]), std::sqrt(h_norms[2]), rhs_norm});
+        const double primal_eps = primal_abs + rel_tol * max_norm;
+        const double dual_eps = dual_abs + rel_tol * std::sqrt(h_norms[4]);
+        if (r_norm < primal_eps && s_norm < dual_eps) break;
+      }
+      // UpdateGlobalRotations, ComputeResiduals, ComputeAverageStepSize
+      TMI_HIP(timer.mark());
+      hipLaunchKernelGGL(rotation_update_kernel, view_grid, block, 0, st, n, fixed_view, d_x, d_o, p_step);
+      residuals();
+      section[0] = kGraph;
+      jobs.part[0] = p_rr;
+      jobs.count[0] = nbE;
+      jobs.part[1] = p_step;
+      jobs.count[1] = nbV;
+      if ((rc = fetch(jobs, 2))) return rc;
+      r_sq = h_norms[0];
+      const double avg = h_norms[1] / (double)n;
+      admm_trace.push_back(ran);
+      l1_trace.push_back(avg);
+      sum->num_l1_iterations++;
+      sum->num_admm_iterations += ran;
+      if (avg <= opt->l1_step_convergence_threshold) {
+        sum->l1_converged = 1;
+        break;
+      }
+      budget *= 2;
+    }
+
+    // ---- SolveIRLS (:189-234) ----
+    for (int it = 0; it < IR; ++it) {
+      TMI_HIP(timer.mark());
+      hipLaunchKernelGGL(irls_rhs_kernel, view_grid, block, 0, st, G, n, d_w, d_r, d_rhs, d_diag_w);
+      assemble_and_factor(d_w, d_diag_w);
+      TMI_HIP(timer.mark());
+      dense_cholesky_substitute<3>(d_A, n, d_rhs, d_x, d_tmp, st);
+      TMI_HIP(timer.mark());
+      section[0] = kFactor;
+      section[1] = kSubst;
+      section[2] = kGraph;
+      hipLaunchKernelGGL(rotation_update_kernel, view_grid, block, 0, st, n, fixed_view, d_x, d_o, p_step);
+      residuals();
+      jobs.part[0] = p_rr;
+      jobs.count[0] = nbE;
+      jobs.part[1] = p_step;
+      jobs.count[1] = nbV;
+      if ((rc = fetch(jobs, 2))) return rc;
+      if (*h_flag) {
+        s->error = pivot;
+        return TMI_BA_ERR_LINEAR_SOLVER;
+      }
+      r_sq = h_norms[0];
+      const double avg = h_norms[1] / (double)n;
+      irls_trace.push_back(avg);
+      irls_sq_trace.push_back(r_sq);
+      sum->num_irls_iterations++;
+      if (avg < opt->irls_step_convergence_threshold) {
+        sum->irls_converged = 1;
+        break;
+      }
+    }
+
+    // the results, only now: a failure above leaves the caller's arrays as they were
+    std::vector<double> o_h((size_t)3 * V), r_h(pair_residual ? (size_t)3 * E : 0);
+    TMI_HIP(hipMemcpyAsync(o_h.data(), d_o, o_h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (pair_residual) TMI_HIP(hipMemcpyAsync(r_h.data(), d_r, r_h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    TMI_HIP(hipStreamSynchronize(st));
+    std::copy(o_h.begin(), o_h.end(), view_rotation);
+    if (pair_residual) std::copy(r_h.begin(), r_h.end(), pair_residual);
+    if (l1_admm_iterations) std::copy(admm_trace.begin(), admm_trace.end(), l1_admm_iterations);
+    if (l1_average_step) std::copy(l1_trace.begin(), l1_trace.end(), l1_average_step);
+    if (irls_average_step) std::copy(irls_trace.begin(), irls_trace.end(), irls_average_step);
+    if (irls_squared_residual) std::copy(irls_sq_trace.begin(), irls_sq_trace.end(), irls_squared_residual);
+    sum->num_views = V;
+    sum->num_pairs = E;
+    sum->factor_seconds = seconds[kFactor];
+    sum->substitution_seconds = seconds[kSubst];
+    sum->graph_seconds = seconds[kGraph];
+    sum->kernel_seconds = seconds[kFactor] + seconds[kSubst] + seconds[kGraph];
     return TMI_BA_OK;
   });
 }

@@ -36,6 +36,7 @@ EXPORTS = (
     "tmi_ba_two_view_verification_options_init", "tmi_ba_verify_two_views",
     "tmi_ba_translation_filter_options_init", "tmi_ba_filter_view_pairs_from_relative_translation",
     "tmi_ba_filter_view_pairs_from_orientation",
+    "tmi_ba_robust_rotation_options_init", "tmi_ba_estimate_global_rotations_robust",
     "tmi_ba_solver_structure_checksums",
     "tmi_ba_solver_operator_info",
 )
@@ -161,6 +162,13 @@ def load():
     L.tmi_ba_filter_view_pairs_from_relative_translation.restype = C.c_int32
     L.tmi_ba_filter_view_pairs_from_orientation.argtypes = [PB, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, PFS]
     L.tmi_ba_filter_view_pairs_from_orientation.restype = C.c_int32
+    RO = C.POINTER(abi.CRobustRotationOptions)
+    L.tmi_ba_robust_rotation_options_init.argtypes = [RO]
+    L.tmi_ba_robust_rotation_options_init.restype = None
+    L.tmi_ba_estimate_global_rotations_robust.argtypes = [
+        C.POINTER(abi.CRelativeRotationBatch), RO, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+        C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(abi.CRobustRotationSummary)]
+    L.tmi_ba_estimate_global_rotations_robust.restype = C.c_int32
     L.tmi_ba_solver_structure_checksums.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     L.tmi_ba_solver_structure_checksums.restype = C.c_int32
     L.tmi_ba_solver_operator_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
@@ -453,6 +461,33 @@ def filter_view_pairs_from_orientation(batch: abi.ViewPairBatch, max_relative_ro
     if st != 0:
         raise EngineError(st, "tmi_ba_filter_view_pairs_from_orientation")
     return removed, angle, fs
+
+
+def estimate_global_rotations_robust(batch: abi.RelativeRotationBatch, view_rotation, fixed_view: int = 0, options=None,
+                                     device: int = -1):
+    """RobustRotationEstimator::EstimateRotations on the device.  view_rotation [V, 3]: the initial orientations (not
+    modified).  options: a CRobustRotationOptions (default: the reference's).
+    Returns a dict: rotations [V, 3], residuals [P, 3], admm_iterations (per outer L1 iteration run), l1_steps,
+    irls_steps, irls_sq_residuals, summary (CRobustRotationSummary).  Raises EngineError on any failure."""
+    L = load()
+    o = options if options is not None else abi.robust_rotation_options()
+    rot = np.array(view_rotation, dtype=np.float64).reshape(-1, 3)
+    if rot.shape[0] != batch.num_views:
+        raise ValueError("view_rotation must hold batch.num_views rows")
+    n1, n2 = max(int(o.max_num_l1_iterations), 0), max(int(o.max_num_irls_iterations), 0)
+    res = np.zeros((batch.num_pairs, 3))
+    admm = np.zeros(max(n1, 1), dtype=np.int32)
+    l1_steps, irls_steps, irls_sq = np.zeros(max(n1, 1)), np.zeros(max(n2, 1)), np.zeros(max(n2, 1))
+    cb = batch.as_c()
+    rs = abi.CRobustRotationSummary()
+    st = L.tmi_ba_estimate_global_rotations_robust(
+        C.byref(cb), C.byref(o), int(fixed_view), int(device), rot.ctypes.data, res.ctypes.data, admm.ctypes.data,
+        l1_steps.ctypes.data, irls_steps.ctypes.data, irls_sq.ctypes.data, C.byref(rs))
+    if st != 0:
+        raise EngineError(st, "tmi_ba_estimate_global_rotations_robust")
+    k1, k2 = rs.num_l1_iterations, rs.num_irls_iterations
+    return dict(rotations=rot, residuals=res, admm_iterations=[int(x) for x in admm[:k1]], l1_steps=list(l1_steps[:k1]),
+                irls_steps=list(irls_steps[:k2]), irls_sq_residuals=list(irls_sq[:k2]), summary=rs)
 
 
 class Solver:
