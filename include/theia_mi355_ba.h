@@ -1016,6 +1016,80 @@ int32_t tmi_ba_estimate_global_rotations_robust(const tmi_ba_relative_rotation_b
                                                 double* irls_average_step, double* irls_squared_residual,
                                                 tmi_ba_robust_rotation_summary* summary);
 
+/* ---- LeastUnsquaredDeviationPositionEstimator: camera positions from orientations and directions ----
+ * reference: least_unsquared_deviation_position_estimator.cc:75-212 (GlobalPositionEstimatorType::
+ * LEAST_UNSQUARED_DEVIATION; Ozyesil and Singer, CVPR 2015) with math/constrained_l1_solver.cc:49-187; called at
+ * global_reconstruction_estimator.cc EstimatePosition, after the rotation estimator and the view-pair filters above.
+ * The estimator builds ConstrainedL1Solver with DEFAULT options (its own Options are only CHECKed), so the defaults
+ * below are constrained_l1_solver.h:64-74. */
+typedef struct tmi_ba_lud_position_options {
+  int32_t max_num_iterations;   /* 1000 */
+  double  rho;                  /* 10   */
+  double  alpha;                /* 1.2  */
+  double  absolute_tolerance;   /* 1e-4 */
+  double  relative_tolerance;   /* 1e-2 */
+} tmi_ba_lud_position_options;
+void tmi_ba_lud_position_options_init(tmi_ba_lud_position_options* options);
+
+typedef struct tmi_ba_lud_position_summary {
+  int32_t num_views;
+  int32_t num_pairs;
+  int32_t num_admm_iterations;
+  int32_t converged;              /* both stopping tests held before max_num_iterations ran out    */
+  int32_t num_factorizations;     /* dense Cholesky factorisations of order 3 (num_views - 1): 1    */
+  double  seconds;
+  double  kernel_seconds;         /* device time; the sum of the three below                        */
+  double  factor_seconds;         /* directions, assembly of S and its factorisation                */
+  double  substitution_seconds;   /* forward / backward substitution                                */
+  double  graph_seconds;          /* the per-edge and per-view kernels and their reductions         */
+} tmi_ba_lud_position_summary;
+
+/* EstimatePositions on the device.  The batch is tmi_ba_view_pair_batch: view_rotation (or NULL: pair_position2 is
+ * already in the global frame), pair_view1 / pair_view2 and pair_position2; pair_rotation2 is not read.
+ * view_position [3 * num_views] receives the positions; view `fixed_view` is at 0 (the reference holds fixed whichever
+ * view its hash map yields first).
+ *   1. :56-63, :177-181  t_e = R(view_rotation[view1])^T position_2 with R Ceres' AngleAxisToRotationMatrix (not
+ *                AngleAxisRotatePoint): (R^T p)[k] = (R(0, k) p0 + R(1, k) p1) + R(2, k) p2.
+ *   2. :154-212, :90-97  The unknowns are the positions of the n = num_views - 1 free views -- free view v has columns
+ *                3 (v - (v > fixed_view)) + c -- then one scale s_e per edge, column 3 n + e.  Rows 3 e + c:
+ *                p[view2] - p[view1] - s_e t_e; rows 3 E + e: s_e.  b = [0 (3 E); 1 (E)].
+ *   3.           With d_e = |t_e|^2 + 1 = (t0 t0 + t1 t1) + t2 t2 + 1 and W_e = I3 - t_e t_e^T / d_e, eliminating the
+ *                scales from A^T A leaves S of order 3 n: the diagonal block of view v is the sum of W_e over its edges in
+ *                ascending edge index, block (view1, view2) of an edge is -W_e, the fixed view's rows and columns are
+ *                absent.  S is positive definite exactly when every view reaches fixed_view.  It is factored ONCE by the
+ *                blocked Cholesky of the exact camera solve.  With q = A^T (b + z - u) = [q_p; q_s] the solve is
+ *                p = S^-1 (q_p with t_e (q_s[e] / d_e) subtracted at view1 and added at view2) and
+ *                s_e = (q_s[e] + t_e . (p[view2] - p[view1])) / d_e.  The reference factors the whole sparse matrix of
+ *                order 3 n + E with Eigen / CHOLMOD; the two differ only in rounding.
+ *   4. constrained_l1_solver.cc:112-170  z = u = 0; per iteration x = (A^T A)^-1 A^T (b + z - u) (step 3);
+ *                Ax_hat = alpha A x + (1 - alpha)(z + b); z_old = z; z = ModifiedShrinkage(Ax_hat - b + u, 1 / rho), the
+ *                first 3 E rows by the shrinkage of l1_solver.h, the last E rows by max(., 0); u += Ax_hat - z - b; stop
+ *                when, strictly, |A x - z - b| < sqrt(4 E) absolute_tolerance + relative_tolerance max(|A x|, |z|, |b|)
+ *                and |rho A^T (z - z_old)| < sqrt(3 n + E) absolute_tolerance + relative_tolerance |rho A^T u|.  The
+ *                result is the x of the last iteration run.
+ *   5.           Fixed orders: edges in the caller's order; every per-view sum over the view's edges from zero in
+ *                ascending edge index; every norm by a reduction of fixed shape (a binary tree over blocks of 256, the
+ *                block sums strided over 256 accumulators in ascending order, the same tree again); for the two norms
+ *                of A^T products the edges' block sums (the scale entries) come before the views' (the position entries)
+ *                in that second stage.  No expression is contracted into FMA.  The result is the same bits from call to
+ *                call.
+ * The loop runs on the host; every kernel is a plain grid launch.  A non-positive pivot: TMI_BA_ERR_LINEAR_SOLVER.
+ * 3 n is capped at 11000, i.e. 3667 views (the cap and the knob TMI_BA_ROTATION_MAX_ORDER of the rotation estimator):
+ * TMI_BA_ERR_UNSUPPORTED above it, before anything of the views' size is allocated, on the host (the connectivity
+ * check included: a graph above the cap is refused whether connected or not) or on the device.
+ * TMI_BA_ERR_INVALID_ARGUMENT, before the device is looked for: a null batch, options, view_position or summary, a
+ * missing array, num_pairs == 0, a view index out of range, view1 == view2, a repeated unordered pair, fixed_view out of
+ * range, a non-finite rotation or position_2, rho, alpha or a tolerance that is not positive and finite,
+ * max_num_iterations < 1 (the reference CHECK_GTs it), and a view that the edges do not connect to fixed_view.
+ * On every failure view_position and the optional outputs are left as they were.  Optional outputs (each may be NULL):
+ * pair_scale [num_pairs] the final s_e; pair_residual [3 * num_pairs] the final A x of the L1 rows; admm_r_norm /
+ * admm_s_norm [max_num_iterations] the two norms of every iteration run. */
+int32_t tmi_ba_estimate_global_positions_lud(const tmi_ba_view_pair_batch* batch,
+                                             const tmi_ba_lud_position_options* options, int32_t fixed_view,
+                                             int32_t device, double* view_position, double* pair_scale,
+                                             double* pair_residual, double* admm_r_norm, double* admm_s_norm,
+                                             tmi_ba_lud_position_summary* summary);
+
 /* Test hook: FNV-1a checksums of the static structure arrays resident in HBM -- built in HBM by
  * sort / scan kernels (one rank, no shared intrinsics blocks; TMI_BA_HOST_SETUP=1 disables) or on
  * host threads otherwise.  out[0] = 1 when the device built it; the other slots are documented at

@@ -428,6 +428,48 @@ class CRobustRotationSummary(C.Structure):
     ]
 
 
+class CLudPositionOptions(C.Structure):
+    """tmi_ba_lud_position_options (ConstrainedL1Solver::Options, math/constrained_l1_solver.h:64-74)."""
+    _fields_ = [
+        ("max_num_iterations", C.c_int32),
+        ("rho", C.c_double),
+        ("alpha", C.c_double),
+        ("absolute_tolerance", C.c_double),
+        ("relative_tolerance", C.c_double),
+    ]
+
+
+def lud_position_options(**overrides) -> CLudPositionOptions:
+    """The reference's defaults; mirrors tmi_ba_lud_position_options_init."""
+    o = CLudPositionOptions()
+    o.max_num_iterations = 1000
+    o.rho = 10.0
+    o.alpha = 1.2
+    o.absolute_tolerance = 1e-4
+    o.relative_tolerance = 1e-2
+    for k, v in overrides.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
+class CLudPositionSummary(C.Structure):
+    """tmi_ba_lud_position_summary."""
+    _fields_ = [
+        ("num_views", C.c_int32),
+        ("num_pairs", C.c_int32),
+        ("num_admm_iterations", C.c_int32),
+        ("converged", C.c_int32),
+        ("num_factorizations", C.c_int32),
+        ("seconds", C.c_double),
+        ("kernel_seconds", C.c_double),
+        ("factor_seconds", C.c_double),
+        ("substitution_seconds", C.c_double),
+        ("graph_seconds", C.c_double),
+    ]
+
+
 class CSelectSummary(C.Structure):
     _fields_ = [
         ("num_tracks", C.c_int64),

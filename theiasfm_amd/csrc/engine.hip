@@ -41,6 +41,7 @@
 #include "view_kernels.h"
 #include "view_pair_filter_kernels.h"
 #include "rotation_kernels.h"
+#include "position_kernels.h"
 #include "select_kernels.h"
 #include "structure_gpu.h"
 #include <hipcub/hipcub.hpp>

@@ -1648,6 +1648,53 @@ int rotation_order_cap() {
   return cap;
 }
 
+// The CSR of the undirected graph in ascending edge index -- row: (neighbour, edge << 1 | (this view is the edge's
+// view2)) -- and per free view (column c = v - (v > fixed_view)) the entries with a free neighbour sorted by
+// (neighbour's column, edge), for the matrix assembly of the rotation and the position estimator.
+struct EdgeRows {
+  std::vector<int> row_ptr;   // [V + 1]
+  std::vector<int2> row;      // [2 E]
+  std::vector<int> lap_ptr;   // [n + 1]
+  std::vector<int2> lap_row;  // [<= 2 E]
+};
+
+EdgeRows build_edge_rows(int V, int E, const int32_t* view1, const int32_t* view2, int fixed_view) {
+  const int n = V - 1;
+  EdgeRows rows;
+  std::vector<int>& row_ptr = rows.row_ptr;
+  std::vector<int>& lap_ptr = rows.lap_ptr;
+  std::vector<int2>& row = rows.row;
+  std::vector<int2>& lap_row = rows.lap_row;
+  auto column_of = [&](int v) { return v == fixed_view ? -1 : v - (v > fixed_view); };
+  row_ptr.assign((size_t)V + 1, 0);
+  lap_ptr.assign((size_t)n + 1, 0);
+  row.resize((size_t)2 * E);
+  for (int e = 0; e < E; ++e) {
+    row_ptr[(size_t)view1[e] + 1]++;
+    row_ptr[(size_t)view2[e] + 1]++;
+  }
+  for (int v = 0; v < V; ++v) row_ptr[(size_t)v + 1] += row_ptr[v];
+  std::vector<int> fill(row_ptr.begin(), row_ptr.end() - 1);
+  for (int e = 0; e < E; ++e) {
+    const int a = view1[e], b = view2[e];
+    row[(size_t)fill[a]++] = make_int2(b, e << 1);
+    row[(size_t)fill[b]++] = make_int2(a, (e << 1) | 1);
+  }
+  lap_row.reserve((size_t)2 * E);
+  for (int c = 0; c < n; ++c) {
+    const int v = c + (c >= fixed_view);
+    const size_t first = lap_row.size();
+    for (int r = row_ptr[v]; r < row_ptr[(size_t)v + 1]; ++r) {
+      const int nc = column_of(row[r].x);
+      if (nc >= 0) lap_row.push_back(make_int2(nc, row[r].y >> 1));
+    }
+    std::sort(lap_row.begin() + first, lap_row.end(),
+              [](const int2& p, const int2& q) { return p.x != q.x ? p.x < q.x : p.y < q.y; });
+    lap_ptr[(size_t)c + 1] = (int)lap_row.size();
+  }
+  return rows;
+}
+
 // What the rotation estimator asks of its arguments; null: fine.
 const char* check_rotation_arguments(const tmi_ba_relative_rotation_batch* B, const tmi_ba_robust_rotation_options* o,
                                      int fixed_view, const double* view_rotation) {
@@ -1714,36 +1761,7 @@ int32_t tmi_ba_estimate_global_rotations_robust(const tmi_ba_relative_rotation_b
     return TMI_BA_ERR_UNSUPPORTED;
   }
   if (E > (1 << 30)) return bad_argument("robust rotations: more than 2^30 pairs");
-  // the CSR of the undirected graph in ascending edge index, and per free view the entries with a free neighbour
-  // sorted by (neighbour, edge) for the Laplacian
-  auto column_of = [&](int v) { return v == fixed_view ? -1 : v - (v > fixed_view); };
-  std::vector<int> row_ptr((size_t)V + 1, 0), lap_ptr((size_t)n + 1, 0);
-  std::vector<int2> row((size_t)2 * E), lap_row;
-  for (int e = 0; e < E; ++e) {
-    row_ptr[(size_t)Bh->pair_view1[e] + 1]++;
-    row_ptr[(size_t)Bh->pair_view2[e] + 1]++;
-  }
-  for (int v = 0; v < V; ++v) row_ptr[(size_t)v + 1] += row_ptr[v];
-  {
-    std::vector<int> fill(row_ptr.begin(), row_ptr.end() - 1);
-    for (int e = 0; e < E; ++e) {
-      const int a = Bh->pair_view1[e], b = Bh->pair_view2[e];
-      row[(size_t)fill[a]++] = make_int2(b, e << 1);
-      row[(size_t)fill[b]++] = make_int2(a, (e << 1) | 1);
-    }
-    lap_row.reserve((size_t)2 * E);
-    for (int c = 0; c < n; ++c) {
-      const int v = c + (c >= fixed_view);
-      const size_t first = lap_row.size();
-      for (int r = row_ptr[v]; r < row_ptr[(size_t)v + 1]; ++r) {
-        const int nc = column_of(row[r].x);
-        if (nc >= 0) lap_row.push_back(make_int2(nc, row[r].y >> 1));
-      }
-      std::sort(lap_row.begin() + first, lap_row.end(),
-                [](const int2& p, const int2& q) { return p.x != q.x ? p.x < q.x : p.y < q.y; });
-      lap_ptr[(size_t)c + 1] = (int)lap_row.size();
-    }
-  }
+  const EdgeRows rows = build_edge_rows(V, E, Bh->pair_view1, Bh->pair_view2, fixed_view);
   const int L1 = opt->max_num_l1_iterations, IR = opt->max_num_irls_iterations;
   std::vector<int> admm_trace;
   std::vector<double> l1_trace, irls_trace, irls_sq_trace;
@@ -1758,10 +1776,10 @@ int32_t tmi_ba_estimate_global_rotations_robust(const tmi_ba_relative_rotation_b
     double *d_rel, *d_o, *d_r, *d_w, *d_z, *d_u, *d_dz, *d_rhs, *d_tmp, *d_x, *d_diag_w, *d_A, *d_cdiag, *d_part, *d_norms;
     TMI_HIP(s->upload(&d_v1, (const int*)Bh->pair_view1, (size_t)E));
     TMI_HIP(s->upload(&d_v2, (const int*)Bh->pair_view2, (size_t)E));
-    TMI_HIP(s->upload(&d_ptr, row_ptr.data(), row_ptr.size()));
-    TMI_HIP(s->upload(&d_row, row.data(), row.size()));
-    TMI_HIP(s->upload(&d_lptr, lap_ptr.data(), lap_ptr.size()));
-    TMI_HIP(s->upload(&d_lrow, lap_row.data(), lap_row.size()));
+    TMI_HIP(s->upload(&d_ptr, rows.row_ptr.data(), rows.row_ptr.size()));
+    TMI_HIP(s->upload(&d_row, rows.row.data(), rows.row.size()));
+    TMI_HIP(s->upload(&d_lptr, rows.lap_ptr.data(), rows.lap_ptr.size()));
+    TMI_HIP(s->upload(&d_lrow, rows.lap_row.data(), rows.lap_row.size()));
     TMI_HIP(s->upload(&d_rel, Bh->pair_rotation, (size_t)3 * E));
     TMI_HIP(s->upload(&d_o, (const double*)view_rotation, (size_t)3 * V));
     TMI_HIP(s->alloc(&d_r, (size_t)3 * E));
@@ -1954,6 +1972,229 @@ int32_t tmi_ba_estimate_global_rotations_robust(const tmi_ba_relative_rotation_b
     sum->substitution_seconds = seconds[kSubst];
     sum->graph_seconds = seconds[kGraph];
     sum->kernel_seconds = seconds[kFactor] + seconds[kSubst] + seconds[kGraph];
+    return TMI_BA_OK;
+  });
+}
+}  // extern "C"
+
+// ---- LeastUnsquaredDeviationPositionEstimator (position_kernels.h) ------------------------------
+namespace {
+// What the position estimator asks of its arguments beyond check_view_pair_batch, the connection to fixed_view apart;
+// null: fine.  Nothing is allocated here.
+const char* check_lud_arguments(const tmi_ba_view_pair_batch* B, const tmi_ba_lud_position_options* o, int fixed_view) {
+  if (B->num_pairs == 0) return "LUD positions: no view pair";
+  if (fixed_view < 0 || fixed_view >= B->num_views) return "LUD positions: fixed_view out of range";
+  for (const double x : {o->rho, o->alpha, o->absolute_tolerance, o->relative_tolerance})
+    if (!(x > 0.0) || !std::isfinite(x)) return "LUD positions: rho, alpha or a tolerance that is not positive and finite";
+  if (o->max_num_iterations < 1) return "LUD positions: max_num_iterations < 1 (the reference CHECK_GTs it)";
+  return nullptr;
+}
+
+// Union-find over the (checked) edges: does every view reach fixed_view?
+bool every_view_reaches(const tmi_ba_view_pair_batch* B, int fixed_view) {
+  const int V = B->num_views, E = B->num_pairs;
+  std::vector<int> parent((size_t)V);
+  for (int v = 0; v < V; ++v) parent[v] = v;
+  auto find = [&](int v) {
+    while (parent[v] != v) v = parent[v] = parent[parent[v]];
+    return v;
+  };
+  for (int e = 0; e < E; ++e) {
+    const int ra = find(B->pair_view1[e]), rb = find(B->pair_view2[e]);
+    if (ra != rb) parent[std::max(ra, rb)] = std::min(ra, rb);
+  }
+  const int root = find(fixed_view);
+  for (int v = 0; v < V; ++v)
+    if (find(v) != root) return false;
+  return true;
+}
+}  // namespace
+extern "C" {
+
+void tmi_ba_lud_position_options_init(tmi_ba_lud_position_options* o) {
+  if (!o) return;
+  o->max_num_iterations = 1000;  // math/constrained_l1_solver.h:64-74
+  o->rho = 10.0;
+  o->alpha = 1.2;
+  o->absolute_tolerance = 1e-4;
+  o->relative_tolerance = 1e-2;
+}
+
+int32_t tmi_ba_estimate_global_positions_lud(const tmi_ba_view_pair_batch* Bh, const tmi_ba_lud_position_options* opt,
+                                             int32_t fixed_view, int32_t device, double* view_position,
+                                             double* pair_scale, double* pair_residual, double* admm_r_norm,
+                                             double* admm_s_norm, tmi_ba_lud_position_summary* sum) {
+  if (!Bh || !opt || !view_position || !sum)
+    return bad_argument("LUD positions: null batch, options, view_position or summary");
+  memset(sum, 0, sizeof(*sum));
+  const double t0 = now_s();
+  // argument errors before the device is touched
+  if (const char* why = check_view_pair_batch(Bh, false, Bh->pair_position2)) return bad_argument(why);
+  if (const char* why = check_lud_arguments(Bh, opt, fixed_view)) return bad_argument(why);
+  const int V = Bh->num_views, E = Bh->num_pairs, n = V - 1;
+  // the cap before anything of the views' size is allocated, the union-find included
+  if ((int64_t)3 * n > rotation_order_cap()) {
+    g_last_error = "LUD positions: 3 (num_views - 1) exceeds the dense solver's cap (see the header)";
+    return TMI_BA_ERR_UNSUPPORTED;
+  }
+  const int N = 3 * n;  // (<= the cap)
+  if (!every_view_reaches(Bh, fixed_view)) return bad_argument("LUD positions: a view is not connected to fixed_view");
+  const EdgeRows rows = build_edge_rows(V, E, Bh->pair_view1, Bh->pair_view2, fixed_view);
+  const int max_it = opt->max_num_iterations;
+  const double rho = opt->rho, alpha = opt->alpha;
+  std::vector<double> r_trace, s_trace;
+  return one_shot_batch(device, "LUD positions: no such device", E, t0, sum, [&](OneShot* s) -> int {
+    PositionGraph G;
+    memset(&G, 0, sizeof(G));
+    G.num_views = V;
+    G.num_pairs = E;
+    G.fixed_view = fixed_view;
+    int *d_v1, *d_v2, *d_ptr, *d_lptr, *d_flag;
+    int2 *d_row, *d_lrow;
+    double *d_pos, *d_t, *d_rot = nullptr, *d_qs, *d_z, *d_u, *d_dz, *d_scale, *d_ax, *d_rhs, *d_tmp, *d_p, *d_S, *d_cdiag, *d_part,
+        *d_norms;
+    TMI_HIP(s->upload(&d_v1, (const int*)Bh->pair_view1, (size_t)E));
+    TMI_HIP(s->upload(&d_v2, (const int*)Bh->pair_view2, (size_t)E));
+    TMI_HIP(s->upload(&d_ptr, rows.row_ptr.data(), rows.row_ptr.size()));
+    TMI_HIP(s->upload(&d_row, rows.row.data(), rows.row.size()));
+    TMI_HIP(s->upload(&d_lptr, rows.lap_ptr.data(), rows.lap_ptr.size()));
+    TMI_HIP(s->upload(&d_lrow, rows.lap_row.data(), rows.lap_row.size()));
+    TMI_HIP(s->upload(&d_pos, Bh->pair_position2, (size_t)3 * E));
+    d_t = d_pos;
+    if (Bh->view_rotation) {
+      TMI_HIP(s->upload(&d_rot, Bh->view_rotation, (size_t)3 * V));
+      TMI_HIP(s->alloc(&d_t, (size_t)3 * E));
+    }
+    const std::vector<double> ones((size_t)E, 1.0);  // the scale entries of A^T b
+    TMI_HIP(s->upload(&d_qs, ones.data(), ones.size()));
+    TMI_HIP(s->alloc(&d_z, (size_t)4 * E));
+    TMI_HIP(s->alloc(&d_u, (size_t)4 * E));
+    TMI_HIP(s->alloc(&d_dz, (size_t)4 * E));
+    TMI_HIP(s->alloc(&d_scale, (size_t)E));
+    TMI_HIP(s->alloc(&d_ax, (size_t)3 * E));
+    TMI_HIP(s->alloc(&d_rhs, (size_t)N));
+    TMI_HIP(s->alloc(&d_tmp, (size_t)N));
+    TMI_HIP(s->alloc(&d_p, (size_t)N));
+    TMI_HIP(s->alloc(&d_S, (size_t)N * N));
+    TMI_HIP(s->alloc(&d_cdiag, (size_t)kPanel * ((size_t)(N + kPanel - 1) / kPanel) * kPanel));
+    const int nbE = (E + 255) / 256, nbV = (n + 255) / 256;
+    // the blocks' parts: |A x - z - b|^2, |A x|^2, |z|^2 [nbE each], then |rho A^T dz|^2 and |rho A^T u|^2, each the
+    // edges' parts [nbE] followed by the views' [nbV] and reduced as one quantity
+    TMI_HIP(s->alloc(&d_part, (size_t)5 * nbE + (size_t)2 * nbV));
+    TMI_HIP(s->alloc(&d_norms, 8));
+    TMI_HIP(s->alloc(&d_flag, 1));
+    double *p_r = d_part, *p_ax = p_r + nbE, *p_z = p_ax + nbE, *p_s = p_z + nbE, *p_t = p_s + nbE + nbV;
+    PinnedWords pinned;  // [0..5) the ADMM norms, then the pivot flag
+    TMI_HIP(pinned.alloc(8 * sizeof(double)));
+    double* h_norms = static_cast<double*>(pinned.p);
+    int* h_flag = reinterpret_cast<int*>(h_norms + 6);
+    G.pair_view1 = d_v1;
+    G.pair_view2 = d_v2;
+    G.t = d_t;
+    G.row_ptr = d_ptr;
+    G.row = d_row;
+    G.lap_ptr = d_lptr;
+    G.lap_row = d_lrow;
+    hipStream_t st = s->stream;
+    const dim3 edge_grid(nbE), view_grid(nbV), block(256);
+    TMI_HIP(hipMemsetAsync(d_flag, 0, sizeof(int), st));
+    TMI_HIP(hipMemsetAsync(d_z, 0, (size_t)4 * E * sizeof(double), st));
+    TMI_HIP(hipMemsetAsync(d_u, 0, (size_t)4 * E * sizeof(double), st));
+    TMI_HIP(hipMemsetAsync(d_dz, 0, (size_t)4 * E * sizeof(double), st));
+    ReduceJobs jobs;
+    memset(&jobs, 0, sizeof(jobs));
+    const double* parts[5] = {p_r, p_ax, p_z, p_s, p_t};
+    for (int q = 0; q < 5; ++q) {
+      jobs.part[q] = parts[q];
+      jobs.count[q] = q < 3 ? nbE : nbE + nbV;
+    }
+    // device time in three classes: marks 0-1 the set-up (first iteration only) or the substitution, 1-2 the graph
+    // kernels; every iteration ends in a synchronisation
+    StreamTimer timer(st, 3);
+    TMI_HIP(timer.status);
+    double factor_seconds = 0.0, subst_seconds = 0.0, graph_seconds = 0.0;
+
+    // ---- the directions, S and its factor, and the right-hand side of the first solve: A^T b ----
+    TMI_HIP(timer.mark());
+    if (Bh->view_rotation) hipLaunchKernelGGL(lud_direction_kernel, edge_grid, block, 0, st, E, d_rot, d_v1, d_pos, d_t);
+    hipLaunchKernelGGL(lud_assemble_kernel, dim3(n), block, 0, st, G, N, d_S);
+    dense_cholesky_factor(d_S, N, d_cdiag, d_flag, st);
+    sum->num_factorizations = 1;
+    TMI_HIP(timer.mark());
+    hipLaunchKernelGGL(lud_view_kernel, view_grid, block, 0, st, G, n, rho, d_qs, d_z, d_u, d_dz, d_rhs, p_s + nbE,
+                       p_t + nbE);
+    TMI_HIP(timer.mark());
+    {
+      const hipError_t le = hipGetLastError();
+      const hipError_t ce = hipMemcpyAsync(h_flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, st);
+      const hipError_t se = hipStreamSynchronize(st);
+      TMI_HIP(le);
+      TMI_HIP(ce);
+      TMI_HIP(se);
+    }
+    factor_seconds += timer.seconds(0, 1);
+    graph_seconds += timer.seconds(1, 2);
+    if (*h_flag) {
+      s->error = "LUD positions: a pivot of the Cholesky factorisation of S is not positive";
+      return TMI_BA_ERR_LINEAR_SOLVER;
+    }
+
+    // ---- ConstrainedL1Solver::Solve (:112-170) ----
+    const double rhs_norm = std::sqrt((double)E);  // |b|
+    const double primal_abs = std::sqrt(4.0 * (double)E) * opt->absolute_tolerance;
+    const double dual_abs = std::sqrt(3.0 * (double)n + (double)E) * opt->absolute_tolerance;
+    for (int it = 0; it < max_it; ++it) {
+      timer.marked = 0;
+      TMI_HIP(timer.mark());
+      dense_cholesky_substitute<1>(d_S, N, d_rhs, d_p, d_tmp, st);
+      TMI_HIP(timer.mark());
+      hipLaunchKernelGGL(lud_edge_kernel, edge_grid, block, 0, st, G, rho, alpha, d_p, d_qs, d_z, d_u, d_dz, d_scale,
+                         d_ax, p_r, p_ax, p_z, p_s, p_t);
+      hipLaunchKernelGGL(lud_view_kernel, view_grid, block, 0, st, G, n, rho, d_qs, d_z, d_u, d_dz, d_rhs, p_s + nbE,
+                         p_t + nbE);
+      hipLaunchKernelGGL(reduce_partials_kernel, dim3(5), block, 0, st, jobs, d_norms);
+      TMI_HIP(timer.mark());
+      const hipError_t le = hipGetLastError();
+      hipError_t ce = hipMemcpyAsync(h_norms, d_norms, 5 * sizeof(double), hipMemcpyDeviceToHost, st);
+      if (ce == hipSuccess) ce = hipMemcpyAsync(h_flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, st);
+      const hipError_t se = hipStreamSynchronize(st);
+      TMI_HIP(le);
+      TMI_HIP(ce);
+      TMI_HIP(se);
+      subst_seconds += timer.seconds(0, 1);
+      graph_seconds += timer.seconds(1, 2);
+      sum->num_admm_iterations++;
+      const double r_norm = std::sqrt(h_norms[0]), s_norm = std::sqrt(h_norms[3]);
+      const double max_norm = std::max({std::sqrt(h_norms[1]), std::sqrt(h_norms[2]), rhs_norm});
+      const double primal_eps = primal_abs + opt->relative_tolerance * max_norm;
+      const double dual_eps = dual_abs + opt->relative_tolerance * std::sqrt(h_norms[4]);
+      r_trace.push_back(r_norm);
+      s_trace.push_back(s_norm);
+      if (r_norm < primal_eps && s_norm < dual_eps) {
+        sum->converged = 1;
+        break;
+      }
+    }
+
+    // the results, only now: a failure above leaves the caller's arrays as they were
+    std::vector<double> p_h((size_t)N), scale_h(pair_scale ? (size_t)E : 0), ax_h(pair_residual ? (size_t)3 * E : 0);
+    TMI_HIP(hipMemcpyAsync(p_h.data(), d_p, p_h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (pair_scale) TMI_HIP(hipMemcpyAsync(scale_h.data(), d_scale, scale_h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (pair_residual) TMI_HIP(hipMemcpyAsync(ax_h.data(), d_ax, ax_h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    TMI_HIP(hipStreamSynchronize(st));
+    for (int v = 0; v < V; ++v)
+      for (int k = 0; k < 3; ++k)
+        view_position[(size_t)3 * v + k] = v == fixed_view ? 0.0 : p_h[(size_t)3 * (v - (v > fixed_view)) + k];
+    if (pair_scale) std::copy(scale_h.begin(), scale_h.end(), pair_scale);
+    if (pair_residual) std::copy(ax_h.begin(), ax_h.end(), pair_residual);
+    if (admm_r_norm) std::copy(r_trace.begin(), r_trace.end(), admm_r_norm);
+    if (admm_s_norm) std::copy(s_trace.begin(), s_trace.end(), admm_s_norm);
+    sum->num_views = V;
+    sum->num_pairs = E;
+    sum->factor_seconds = factor_seconds;
+    sum->substitution_seconds = subst_seconds;
+    sum->graph_seconds = graph_seconds;
+    sum->kernel_seconds = factor_seconds + subst_seconds + graph_seconds;
     return TMI_BA_OK;
   });
 }

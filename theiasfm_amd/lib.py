@@ -37,6 +37,7 @@ EXPORTS = (
     "tmi_ba_translation_filter_options_init", "tmi_ba_filter_view_pairs_from_relative_translation",
     "tmi_ba_filter_view_pairs_from_orientation",
     "tmi_ba_robust_rotation_options_init", "tmi_ba_estimate_global_rotations_robust",
+    "tmi_ba_lud_position_options_init", "tmi_ba_estimate_global_positions_lud",
     "tmi_ba_solver_structure_checksums",
     "tmi_ba_solver_operator_info",
 )
@@ -169,6 +170,13 @@ def load():
         C.POINTER(abi.CRelativeRotationBatch), RO, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
         C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(abi.CRobustRotationSummary)]
     L.tmi_ba_estimate_global_rotations_robust.restype = C.c_int32
+    LO = C.POINTER(abi.CLudPositionOptions)
+    L.tmi_ba_lud_position_options_init.argtypes = [LO]
+    L.tmi_ba_lud_position_options_init.restype = None
+    L.tmi_ba_estimate_global_positions_lud.argtypes = [
+        PB, LO, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+        C.POINTER(abi.CLudPositionSummary)]
+    L.tmi_ba_estimate_global_positions_lud.restype = C.c_int32
     L.tmi_ba_solver_structure_checksums.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     L.tmi_ba_solver_structure_checksums.restype = C.c_int32
     L.tmi_ba_solver_operator_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
@@ -488,6 +496,30 @@ def estimate_global_rotations_robust(batch: abi.RelativeRotationBatch, view_rota
     k1, k2 = rs.num_l1_iterations, rs.num_irls_iterations
     return dict(rotations=rot, residuals=res, admm_iterations=[int(x) for x in admm[:k1]], l1_steps=list(l1_steps[:k1]),
                 irls_steps=list(irls_steps[:k2]), irls_sq_residuals=list(irls_sq[:k2]), summary=rs)
+
+
+def estimate_global_positions_lud(batch: abi.ViewPairBatch, fixed_view: int = 0, options=None, device: int = -1):
+    """LeastUnsquaredDeviationPositionEstimator::EstimatePositions on the device.  batch.view_rotation None:
+    batch.pair_position2 is already in the global frame.  options: a CLudPositionOptions (default: the reference's).
+    Returns a dict: positions [V, 3] (the fixed view at 0), scales [P], residuals [P, 3] (the final A x of the L1 rows),
+    r_norms, s_norms (per ADMM iteration run), summary (CLudPositionSummary).  Raises EngineError on any failure."""
+    L = load()
+    o = options if options is not None else abi.lud_position_options()
+    k = max(int(o.max_num_iterations), 1)
+    pos = np.zeros((batch.num_views, 3))
+    scales = np.zeros(batch.num_pairs)
+    res = np.zeros((batch.num_pairs, 3))
+    r_norms, s_norms = np.zeros(k), np.zeros(k)
+    cb = batch.as_c()
+    ps = abi.CLudPositionSummary()
+    st = L.tmi_ba_estimate_global_positions_lud(
+        C.byref(cb), C.byref(o), int(fixed_view), int(device), pos.ctypes.data, scales.ctypes.data, res.ctypes.data,
+        r_norms.ctypes.data, s_norms.ctypes.data, C.byref(ps))
+    if st != 0:
+        raise EngineError(st, "tmi_ba_estimate_global_positions_lud")
+    ran = ps.num_admm_iterations
+    return dict(positions=pos, scales=scales, residuals=res, r_norms=r_norms[:ran].copy(), s_norms=s_norms[:ran].copy(),
+                summary=ps)
 
 
 class Solver:
