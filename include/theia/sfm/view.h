@@ -8,6 +8,14 @@
 #include "theia/sfm/feature.h"
 #include "theia/sfm/types.h"
 namespace theia {
+// reference: sfm/camera_intrinsics_prior.h -- of the priors only the focal length's, which
+// DoesViewHaveKnownIntrinsics (localize_view_to_reconstruction.cc:55-58) reads.
+struct CameraIntrinsicsPrior {
+  struct FocalLength {
+    bool is_set = false;
+    double value[1] = {0.0};
+  } focal_length;
+};
 class View {
  public:
   View() : name_(""), is_estimated_(false) {}
@@ -20,6 +28,8 @@ class View {
   bool IsEstimated() const { return is_estimated_; }
   const class Camera& Camera() const { return camera_; }
   class Camera* MutableCamera() { return &camera_; }
+  const struct CameraIntrinsicsPrior& CameraIntrinsicsPrior() const { return camera_intrinsics_prior_; }
+  struct CameraIntrinsicsPrior* MutableCameraIntrinsicsPrior() { return &camera_intrinsics_prior_; }
   int NumFeatures() const { return static_cast<int>(features_.size()); }
   std::vector<TrackId> TrackIds() const {
     std::vector<TrackId> ids;
@@ -47,6 +57,7 @@ class View {
   std::string name_;
   bool is_estimated_;
   class Camera camera_;
+  struct CameraIntrinsicsPrior camera_intrinsics_prior_;
   std::unordered_map<TrackId, Feature> features_;
 };
 }  // namespace theia

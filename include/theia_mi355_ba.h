@@ -1090,6 +1090,106 @@ int32_t tmi_ba_estimate_global_positions_lud(const tmi_ba_view_pair_batch* batch
                                              double* pair_residual, double* admm_r_norm, double* admm_s_norm,
                                              tmi_ba_lud_position_summary* summary);
 
+/* ---- batched LocalizeViewToReconstruction: P3P RANSAC for many candidate views ------------------
+ * reference: LocalizeViewToReconstruction (localize_view_to_reconstruction.cc:213-257), the inner loop of the
+ * incremental and hybrid pipelines (incremental_reconstruction_estimator.cc:219-233), on its CALIBRATED path:
+ * EstimateCameraPose with known intrinsics and without assume_known_orientation (:185-198),
+ * EstimateCalibratedAbsolutePose with RansacType::RANSAC (estimate_calibrated_absolute_pose.cc:58-110),
+ * SampleConsensusEstimator::Estimate (sample_consensus_estimator.h:246-344) with InlierSupport, and PoseFromThreePoints
+ * (perspective_three_point.cc).  Not provided: P4Pf (unknown focal length), the known-orientation position solver,
+ * use_mle, use_Tdd_test, PROSAC, LMED and exhaustive sampling.
+ * The problem holds the candidate views as cameras; EVERY point of the problem counts as an estimated track; view_mask
+ * [num_cameras] selects the candidates (NULL = all); the input extrinsics of a selected view are ignored.
+ * view_error_threshold [num_cameras] is RansacParameters::error_thresh per view: the SQUARED threshold in normalised
+ * coordinates (:188-191), i.e. (ComputeResolutionScaledThreshold(pixels, width, height) / focal_length)^2, which the
+ * caller computes because tmi_ba_problem has no image size.  Per selected view, in this order:
+ *   1. Correspondences: the view's observations in ascending observation index, numbered 0..n-1; the feature is
+ *      Camera::PixelToNormalizedCoordinates(pixel).hnormalized() (as step 2 of tmi_ba_estimate_tracks, all five
+ *      models), the world point is point.hnormalized().  n < min_num_inliers (:141-145)        -> status 1.
+ *      (Also n < 3: the reference's sampler refuses to initialise.)
+ *   2. The sample of iteration i.  samples_given != 0: the caller's samples[3 (max_iterations v + i) + k], v the camera
+ *      index.  Otherwise deterministic in `seed` and stateless: word c = 3 (v 2^32 + i) + k (mod 2^64) of the splitmix64
+ *      stream from state `seed` (the generator documented at tmi_ba_filter_view_pairs_from_relative_translation: the
+ *      state after c + 1 steps is seed + (c + 1) gamma and the word is the output mix of that state),
+ *      u = ((word >> 11) + 0.5) 2^-53, j_k = min(k + floor(u (n - k)), n - 1), then the three swaps of a partial
+ *      Fisher-Yates on the identity permutation, swap(a[k], a[j_k]) for k = 0, 1, 2; the sample is a[0..2].
+ *      THE SAMPLE SEQUENCES ARE NOT THE REFERENCE'S: its RandomSampler carries its permutation from one iteration to the
+ *      next and draws from another generator.
+ *   3. P3P as PoseFromThreePoints writes it: the collinearity test (< 1e-6), the swap when intermediate_image_point[2]
+ *      > 0, the quartic in cos(theta), cot(alpha) and the back-substitution with its sign rules, then position = -R^T t.
+ *      The reference takes the roots from the companion matrix and back-substitutes THE REAL PART OF EVERY ONE OF THE FOUR
+ *      ROOTS, complex ones included; so does this call: four solutions per sample, in ascending real part (a conjugate
+ *      pair gives the same pose twice).  The roots come from Ferrari's factorisation through a positive root of the
+ *      resolvent cubic found by bisection, with two Newton steps on every real root.  A leading coefficient of exactly
+ *      0 gives no model (DEVIATION: the reference would drop the degree).
+ *   4. The cost of a solution: the correspondences whose squared reprojection error
+ *      |hnormalized(R (X - c)) - feature|^2 is not below the threshold (a NaN error is an outlier), the three sampled
+ *      ones included.
+ *   5. The replay in ascending (iteration, solution) order, exactly the loop at sample_consensus_estimator.h:276-330: a
+ *      solution becomes the best on cost < best_cost, strictly; inlier_ratio < 3 / n skips the update of the bound;
+ *      max_iterations = min(ComputeMaxIterations(3, inlier_ratio, log(failure_probability)), max_iterations) with the
+ *      reference's formula (its - epsilon, its inlier_ratio == 1 case, its clamp between min_iterations and
+ *      max_iterations); the initial bound comes from min_inlier_ratio when that is positive (:268-274); a sample without
+ *      a model still counts as an iteration; the loop ends when the iteration counter reaches the current bound.
+ *      Iterations are evaluated on the device in chunks of chunk_iterations (0: max(min_iterations, 64)); what a chunk
+ *      evaluated beyond the end of the loop is discarded, so THE RESULT DOES NOT DEPEND ON chunk_iterations.
+ *   6. Final (:332-341): the inlier mask of the best model, num_inliers its count, confidence =
+ *      1 - (1 - (num_inliers / n)^3)^num_iterations.  No solution in any iteration -> status 2 (DEVIATION: the reference
+ *      goes on with an uninitialised model).  num_inliers < min_num_inliers (:239) -> status 3.
+ *   7. Otherwise the view is localised: problem->extrinsics of the view becomes the position and the orientation as
+ *      Camera::SetOrientationFromRotationMatrix sets it (Ceres' RotationMatrixToAngleAxis).  With bundle_adjust_view the
+ *      batched view adjustment (tmi_ba_adjust_views with ba_options) then runs on exactly the localised views, on the
+ *      data already on the device; a view whose adjustment is not usable gets status 4 and keeps its RANSAC pose (the
+ *      reference has set the pose and SetEstimated(true) by then, :247-252, and returns false).  Otherwise status 0.
+ * view_status: -1 not selected, 0..4 as above.  Every per-view output [num_cameras] may be NULL.  view_best_iteration /
+ * view_best_solution: the (iteration, solution) of the best model, -1 without one.  obs_inlier [num_observations]
+ * (optional): 1 for the inliers of the best model of an attempted view, 0 elsewhere.  hypothesis_cost
+ * [num_selected * max_iterations * 4] (optional, for tests; selected views in ascending camera index): the cost of every
+ * replayed hypothesis, -1 for no model or not replayed.
+ * With samples_given the whole table [3 * max_iterations * num_cameras] is uploaded, the rows of views that are not
+ * attempted included (12 bytes per camera and iteration).
+ * ComputeMaxIterations and the confidence are evaluated on the host (log and pow of the C library); steps 2 to 6 use
+ * + - * / and sqrt only and are never contracted into FMA.
+ * TMI_BA_ERR_INVALID_ARGUMENT, before the device (ba_options->device) is looked for: a null problem, options, ba_options
+ * or summary, a missing array, a bad index or intrinsics group, the CHECKs of the SampleConsensusEstimator constructor
+ * (an error threshold of an attempted view that is not positive, min_inlier_ratio outside [0, 1], failure_probability
+ * outside (0, 1), max_iterations < min_iterations), a negative count, max_iterations above 2^20, samples_given without
+ * samples, and a sample of an attempted view with a repeated or out-of-range index. */
+typedef struct tmi_ba_localization_options {
+  double   failure_probability;  /* 0.01 (sample_consensus_estimator.h:57-65)                                  */
+  double   min_inlier_ratio;     /* 0                                                                          */
+  int32_t  min_iterations;       /* 100                                                                        */
+  int32_t  max_iterations;       /* 1000; the reference's struct default is INT_MAX, its estimators set
+                                    ransac_max_iterations                                                      */
+  int32_t  min_num_inliers;      /* 30 (localize_view_to_reconstruction.h:71)                                  */
+  int32_t  bundle_adjust_view;   /* 1                                                                          */
+  int32_t  chunk_iterations;     /* 0 = the engine's choice                                                    */
+  uint64_t seed;                 /* 0                                                                          */
+} tmi_ba_localization_options;
+void tmi_ba_localization_options_init(tmi_ba_localization_options* options);
+
+typedef struct tmi_ba_localization_summary {
+  int32_t num_views;                    /* selected views                                   */
+  int32_t num_localized;                /* status 0                                         */
+  int32_t num_too_few_correspondences;  /* status 1                                         */
+  int32_t num_no_model;                 /* status 2                                         */
+  int32_t num_too_few_inliers;          /* status 3                                         */
+  int32_t num_failed_ba;                /* status 4                                         */
+  int32_t num_chunks;                   /* chunks of iterations evaluated                   */
+  int64_t total_iterations;             /* RANSAC iterations over the attempted views       */
+  double  seconds;
+  double  kernel_seconds;               /* the RANSAC launches, first to last (the per-chunk read-back of the done flags
+                                           included), plus the view adjustment's           */
+} tmi_ba_localization_summary;
+
+int32_t tmi_ba_localize_views(tmi_ba_problem* problem, const tmi_ba_localization_options* options,
+                              const tmi_ba_options* ba_options, const uint8_t* view_mask,
+                              const double* view_error_threshold, const int32_t* samples, int32_t samples_given,
+                              int8_t* view_status, int32_t* view_num_correspondences, int32_t* view_num_inliers,
+                              int32_t* view_num_iterations, int32_t* view_best_iteration, int32_t* view_best_solution,
+                              double* view_confidence, uint8_t* obs_inlier, int32_t* hypothesis_cost,
+                              tmi_ba_localization_summary* summary);
+
 /* Test hook: FNV-1a checksums of the static structure arrays resident in HBM -- built in HBM by
  * sort / scan kernels (one rank, no shared intrinsics blocks; TMI_BA_HOST_SETUP=1 disables) or on
  * host threads otherwise.  out[0] = 1 when the device built it; the other slots are documented at

@@ -470,6 +470,55 @@ class CLudPositionSummary(C.Structure):
     ]
 
 
+class CLocalizationOptions(C.Structure):
+    """tmi_ba_localization_options (RansacParameters, sample_consensus_estimator.h:57-65, and
+    LocalizeViewToReconstructionOptions, localize_view_to_reconstruction.h:48-72)."""
+    _fields_ = [
+        ("failure_probability", C.c_double),
+        ("min_inlier_ratio", C.c_double),
+        ("min_iterations", C.c_int32),
+        ("max_iterations", C.c_int32),
+        ("min_num_inliers", C.c_int32),
+        ("bundle_adjust_view", C.c_int32),
+        ("chunk_iterations", C.c_int32),
+        ("seed", C.c_uint64),
+    ]
+
+
+def localization_options(**overrides) -> CLocalizationOptions:
+    """The defaults of tmi_ba_localization_options_init."""
+    o = CLocalizationOptions()
+    o.failure_probability = 0.01
+    o.min_inlier_ratio = 0.0
+    o.min_iterations = 100
+    o.max_iterations = 1000
+    o.min_num_inliers = 30
+    o.bundle_adjust_view = 1
+    o.chunk_iterations = 0
+    o.seed = 0
+    for k, v in overrides.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
+class CLocalizationSummary(C.Structure):
+    """tmi_ba_localization_summary."""
+    _fields_ = [
+        ("num_views", C.c_int32),
+        ("num_localized", C.c_int32),
+        ("num_too_few_correspondences", C.c_int32),
+        ("num_no_model", C.c_int32),
+        ("num_too_few_inliers", C.c_int32),
+        ("num_failed_ba", C.c_int32),
+        ("num_chunks", C.c_int32),
+        ("total_iterations", C.c_int64),
+        ("seconds", C.c_double),
+        ("kernel_seconds", C.c_double),
+    ]
+
+
 class CSelectSummary(C.Structure):
     _fields_ = [
         ("num_tracks", C.c_int64),

@@ -19,6 +19,7 @@
 #include <cstdio>
 #include <cstring>
 #include <functional>
+#include <limits>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -42,6 +43,7 @@
 #include "view_pair_filter_kernels.h"
 #include "rotation_kernels.h"
 #include "position_kernels.h"
+#include "localize_kernels.h"
 #include "select_kernels.h"
 #include "structure_gpu.h"
 #include <hipcub/hipcub.hpp>

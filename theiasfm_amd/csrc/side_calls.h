@@ -2198,4 +2198,338 @@ int32_t tmi_ba_estimate_global_positions_lud(const tmi_ba_view_pair_batch* Bh, c
     return TMI_BA_OK;
   });
 }
+
+// ---- batched LocalizeViewToReconstruction: P3P RANSAC (localize_kernels.h) ---------------------
+void tmi_ba_localization_options_init(tmi_ba_localization_options* o) {
+  if (!o) return;
+  o->failure_probability = 0.01;  // sample_consensus_estimator.h:57-65
+  o->min_inlier_ratio = 0.0;
+  o->min_iterations = 100;
+  o->max_iterations = 1000;       // (the reference's struct default is INT_MAX; the estimators set ransac_max_iterations)
+  o->min_num_inliers = 30;        // localize_view_to_reconstruction.h:71
+  o->bundle_adjust_view = 1;
+  o->chunk_iterations = 0;
+  o->seed = 0;
+}
+}  // extern "C"
+namespace {
+// SampleConsensusEstimator::ComputeMaxIterations (sample_consensus_estimator.h:215-243) for a sample of three, without
+// the T(d,d) test.
+int localize_max_iterations(double inlier_ratio, double log_failure_prob, int min_iterations, int max_iterations) {
+  if (inlier_ratio == 1.0) return min_iterations;
+  const double log_prob = std::log(1.0 - std::pow(inlier_ratio, 3.0)) - std::numeric_limits<double>::epsilon();
+  const double num_iterations = log_failure_prob / log_prob;
+  return (int)std::max((double)min_iterations, std::min(num_iterations, (double)max_iterations));
+}
+}  // namespace
+extern "C" {
+
+int32_t tmi_ba_localize_views(tmi_ba_problem* P, const tmi_ba_localization_options* L, const tmi_ba_options* O,
+                              const uint8_t* view_mask, const double* view_error_threshold, const int32_t* samples,
+                              int32_t samples_given, int8_t* view_status, int32_t* view_num_correspondences,
+                              int32_t* view_num_inliers, int32_t* view_num_iterations, int32_t* view_best_iteration,
+                              int32_t* view_best_solution, double* view_confidence, uint8_t* obs_inlier,
+                              int32_t* hypothesis_cost, tmi_ba_localization_summary* sum) {
+  if (!P || !L || !O || !sum) return bad_argument("localize views: null problem, options or summary");
+  memset(sum, 0, sizeof(*sum));
+  const double t0 = now_s();
+  // argument errors before the device is looked for
+  const int Nc = P->num_cameras, G = P->num_groups, Np = P->num_points;
+  const int64_t No = P->num_observations;
+  if (Nc < 0 || G < 0 || Np < 0 || No < 0) return bad_argument("localize views: negative size");
+  if ((Nc && (!P->extrinsics || !P->camera_group)) || (G && (!P->group_model || !P->group_offset)) ||
+      (Np && !P->points) || (No && (!P->obs_camera || !P->obs_point || !P->obs_xy)))
+    return bad_argument("localize views: missing array");
+  if (No >= (int64_t)0x7fffffffLL) return bad_argument("localize views: more than 2^31 observations");
+  // the CHECKs of the SampleConsensusEstimator constructor (sample_consensus_estimator.h:191-197)
+  if (!(L->failure_probability > 0.0 && L->failure_probability < 1.0))
+    return bad_argument("localize views: failure_probability must be in (0, 1)");
+  if (!(L->min_inlier_ratio >= 0.0 && L->min_inlier_ratio <= 1.0))
+    return bad_argument("localize views: min_inlier_ratio must be in [0, 1]");
+  if (L->min_iterations < 0 || L->max_iterations < L->min_iterations)
+    return bad_argument("localize views: max_iterations < min_iterations, or a negative count");
+  if (L->max_iterations > kLocalizeMaxIterations) return bad_argument("localize views: max_iterations above 2^20");
+  if (L->chunk_iterations < 0) return bad_argument("localize views: negative chunk_iterations");
+  if (samples_given && !samples) return bad_argument("localize views: samples_given without samples");
+  const int n_intr = G ? P->group_offset[G] : 0;
+  if (n_intr && !P->intrinsics) return bad_argument("localize views: missing intrinsics");
+  std::vector<uint32_t> grp_free((size_t)G, 0);
+  for (int g = 0; g < G; ++g) {
+    const int o = P->group_offset[g], nk = P->group_offset[g + 1] - o;
+    if (P->group_model[g] < 0 || P->group_model[g] > 4 || nk != tmi_ba_intrinsics_size(P->group_model[g]) || o < 0)
+      return bad_argument("localize views: bad intrinsics group");
+    for (int j = 0; j < nk; ++j)
+      if (!P->intrinsics_constant || !P->intrinsics_constant[o + j]) grp_free[g] |= 1u << j;
+  }
+  std::vector<int4> cam((size_t)Nc);
+  for (int c = 0; c < Nc; ++c) {
+    const int g = P->camera_group[c];
+    if (g < 0 || g >= G) return bad_argument("localize views: bad camera group");
+    const int o = P->group_offset[g];
+    cam[c] = view_cam_record(P->camera_flags ? P->camera_flags[c] : 0, P->group_model[g], o,
+                             P->group_offset[g + 1] - o, grp_free[g]);
+  }
+  std::vector<long long> optr((size_t)Nc + 1, 0);
+  for (int64_t i = 0; i < No; ++i) {
+    const int c = P->obs_camera[i], p = P->obs_point[i];
+    if (c < 0 || c >= Nc || p < 0 || p >= Np) return bad_argument("localize views: bad observation index");
+    optr[(size_t)c + 1]++;
+  }
+  for (int c = 0; c < Nc; ++c) optr[(size_t)c + 1] += optr[c];
+  // the selected views; attempted: enough correspondences for min_num_inliers (:141-145) and for a sample (the
+  // reference's sampler refuses fewer than three)
+  const int K = L->max_iterations;
+  const int need = std::max(L->min_num_inliers, 3);
+  std::vector<int> selected, sel_view;       // camera indices; sel_view: the attempted ones, the device's slots
+  std::vector<int> sel_rank;                 // rank of a device slot among the selected views
+  for (int c = 0; c < Nc; ++c) {
+    if (view_mask && !view_mask[c]) continue;
+    const long long n = optr[(size_t)c + 1] - optr[c];
+    if (n >= need) {
+      if (!view_error_threshold) return bad_argument("localize views: missing view_error_threshold");
+      if (!(view_error_threshold[c] > 0.0)) return bad_argument("localize views: error threshold must be positive");
+      if (samples_given)
+        for (int64_t i = 0; i < K; ++i) {
+          const int32_t* t = samples + 3 * ((int64_t)K * c + i);
+          if (t[0] < 0 || t[1] < 0 || t[2] < 0 || t[0] >= n || t[1] >= n || t[2] >= n || t[0] == t[1] || t[0] == t[2] ||
+              t[1] == t[2])
+            return bad_argument("localize views: a sample with a repeated or out-of-range index");
+        }
+      sel_view.push_back(c);
+      sel_rank.push_back((int)selected.size());
+    }
+    selected.push_back(c);
+  }
+  const int num_selected = (int)selected.size(), S = (int)sel_view.size();
+  // nothing below fails on an argument: preset the outputs
+  for (int c = 0; c < Nc; ++c) {
+    const bool sel = !view_mask || view_mask[c];
+    const long long n = optr[(size_t)c + 1] - optr[c];
+    if (view_status) view_status[c] = (int8_t)(sel ? 1 : -1);
+    if (view_num_correspondences) view_num_correspondences[c] = sel ? (int32_t)n : 0;
+    if (view_num_inliers) view_num_inliers[c] = 0;
+    if (view_num_iterations) view_num_iterations[c] = 0;
+    if (view_best_iteration) view_best_iteration[c] = -1;
+    if (view_best_solution) view_best_solution[c] = -1;
+    if (view_confidence) view_confidence[c] = 0.0;
+  }
+  if (obs_inlier && No) memset(obs_inlier, 0, (size_t)No);
+  if (hypothesis_cost)
+    std::fill(hypothesis_cost, hypothesis_cost + (size_t)num_selected * (size_t)K * 4, -1);
+  sum->num_views = num_selected;
+  sum->num_too_few_correspondences = num_selected - S;
+  // the attempted views' observations in view-major order, ascending observation index inside a view (the gather of
+  // tmi_ba_adjust_views, which the adjustment below then runs on)
+  std::vector<uint8_t> attempted((size_t)Nc, 0);
+  for (const int c : sel_view) attempted[c] = 1;
+  std::vector<long long> vptr((size_t)Nc + 1, 0);
+  for (int c = 0; c < Nc; ++c) vptr[(size_t)c + 1] = vptr[c] + (attempted[c] ? optr[(size_t)c + 1] - optr[c] : 0);
+  const size_t M = (size_t)vptr[Nc];
+  std::vector<unsigned long long> keys(M);
+  std::vector<int> slot_pt(M);
+  std::vector<int64_t> slot_obs(M);
+  std::vector<double> xy(2 * M);
+  if (M) {
+    std::vector<long long> fill(vptr.begin(), vptr.end() - 1);
+    for (int64_t i = 0; i < No; ++i) {
+      const int c = P->obs_camera[i];
+      if (!attempted[c]) continue;
+      const size_t o = (size_t)fill[c]++;
+      keys[o] = ((unsigned long long)(unsigned)c << 32) | (unsigned long long)o;
+      slot_pt[o] = P->obs_point[i];
+      slot_obs[o] = i;
+      xy[2 * o] = P->obs_xy[2 * i];
+      xy[2 * o + 1] = P->obs_xy[2 * i + 1];
+    }
+  }
+  // ComputeMaxIterations per view and inlier count, with the host's log and pow
+  const double log_failure_prob = std::log(L->failure_probability);
+  std::vector<long long> sel_ptr((size_t)S + 1, 0);
+  std::vector<double> thresh((size_t)S);
+  std::vector<int> bound(M + (size_t)S);
+  std::vector<LocalizeState> state((size_t)S);
+  int initial_bound = K;
+  if (L->min_inlier_ratio > 0.0)
+    initial_bound = std::min(localize_max_iterations(L->min_inlier_ratio, log_failure_prob, L->min_iterations, K), K);
+  for (int s = 0; s < S; ++s) {
+    const int c = sel_view[s];
+    const int n = (int)(vptr[(size_t)c + 1] - vptr[c]);
+    sel_ptr[s] = vptr[c];
+    sel_ptr[(size_t)s + 1] = vptr[(size_t)c + 1];
+    thresh[s] = view_error_threshold[c];
+    int* row = bound.data() + vptr[c] + s;
+    for (int k = 0; k <= n; ++k)
+      row[k] = k < 3 ? K : localize_max_iterations((double)k / (double)n, log_failure_prob, L->min_iterations, K);
+    LocalizeState& st = state[s];
+    memset(&st, 0, sizeof(st));
+    st.best_cost = INT32_MAX;
+    st.best_iteration = st.best_solution = -1;
+    st.max_iterations = initial_bound;
+    st.done = initial_bound <= 0;
+  }
+  // the engine's choice of chunk: the common case -- the run stops at min_iterations -- is a single chunk
+  int chunk = L->chunk_iterations ? L->chunk_iterations : std::max(L->min_iterations, 64);
+  chunk = std::max(1, std::min(chunk, std::max(K, 1)));
+  const int max_chunks = (K + chunk - 1) / chunk;
+  return one_shot_batch(O->device, "localize views: no such device", S, t0, sum, [&](OneShot* s) -> int {
+    const hipStream_t stream = s->stream;
+    ViewBatch VB;
+    memset(&VB, 0, sizeof(VB));
+    LocalizeBatch B;
+    memset(&B, 0, sizeof(B));
+    int4* d_cam;
+    long long *d_vptr, *d_sel_ptr;
+    unsigned long long* d_keys;
+    int *d_slot_pt, *d_sel_view, *d_bound, *d_active, *d_samples = nullptr, *d_num_inliers;
+    double *d_xy, *d_pts, *d_thresh, *d_pose_out;
+    unsigned char* d_slot_inlier;
+    signed char* d_status;
+    TMI_HIP(s->upload(&VB.ext, (const double*)P->extrinsics, (size_t)6 * Nc));
+    TMI_HIP(s->upload(&VB.intr, (const double*)P->intrinsics, (size_t)n_intr));
+    TMI_HIP(s->upload(&d_cam, cam.data(), cam.size()));
+    TMI_HIP(s->upload(&d_vptr, vptr.data(), vptr.size()));
+    TMI_HIP(s->upload(&d_keys, keys.data(), keys.size()));
+    TMI_HIP(s->upload(&d_slot_pt, slot_pt.data(), slot_pt.size()));
+    TMI_HIP(s->upload(&d_xy, xy.data(), xy.size()));
+    TMI_HIP(s->upload(&d_pts, (const double*)P->points, (size_t)4 * Np));
+    TMI_HIP(s->upload(&d_sel_view, sel_view.data(), sel_view.size()));
+    TMI_HIP(s->upload(&d_sel_ptr, sel_ptr.data(), sel_ptr.size()));
+    TMI_HIP(s->upload(&d_thresh, thresh.data(), thresh.size()));
+    TMI_HIP(s->upload(&d_bound, bound.data(), bound.size()));
+    TMI_HIP(s->upload(&B.state, state.data(), state.size()));
+    if (samples_given) TMI_HIP(s->upload(&d_samples, (const int*)samples, (size_t)3 * K * Nc));
+    TMI_HIP(s->alloc(&B.fx, M));
+    TMI_HIP(s->alloc(&B.fy, M));
+    TMI_HIP(s->alloc(&B.wx, M));
+    TMI_HIP(s->alloc(&B.wy, M));
+    TMI_HIP(s->alloc(&B.wz, M));
+    TMI_HIP(s->alloc(&d_active, (size_t)S));
+    TMI_HIP(s->alloc(&B.poses, (size_t)S * chunk * 48));
+    TMI_HIP(s->alloc(&B.num_solutions, (size_t)S * chunk));
+    TMI_HIP(s->alloc(&B.cost, (size_t)S * chunk * 4));
+    TMI_HIP(s->alloc(&d_slot_inlier, M));
+    TMI_HIP(s->alloc(&d_num_inliers, (size_t)S));
+    TMI_HIP(s->alloc(&d_status, (size_t)S));
+    TMI_HIP(s->alloc(&d_pose_out, (size_t)6 * S));
+    if (hypothesis_cost) {
+      TMI_HIP(s->alloc(&B.hypothesis_cost, (size_t)S * K * 4));
+      TMI_HIP(hipMemsetAsync(B.hypothesis_cost, 0xff, std::max<size_t>((size_t)S * K * 4, 1) * sizeof(int), stream));
+    }
+    B.num_selected = S;
+    B.max_iterations = K;
+    B.chunk = chunk;
+    B.seed = L->seed;
+    B.sel_view = d_sel_view;
+    B.sel_ptr = d_sel_ptr;
+    B.threshold = d_thresh;
+    B.samples = d_samples;
+    B.bound_table = d_bound;
+    B.active = d_active;
+    StreamTimer timer(stream);
+    TMI_HIP(timer.status);
+    TMI_HIP(timer.mark());
+    hipLaunchKernelGGL(localize_prepare_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, stream, (long long)M,
+                       d_keys, d_slot_pt, d_xy, d_pts, d_cam, VB.intr, B);
+    // the chunk loop: bounded by ceil(max_iterations / chunk) whatever the device reports
+    std::vector<int> active;
+    int chunks_run = 0;
+    for (int ch = 0; ch < max_chunks; ++ch) {
+      active.clear();
+      for (int v = 0; v < S; ++v)
+        if (!state[v].done) active.push_back(v);
+      if (active.empty()) break;
+      TMI_HIP(hipMemcpyAsync(d_active, active.data(), active.size() * sizeof(int), hipMemcpyHostToDevice, stream));
+      B.num_active = (int)active.size();
+      B.chunk_start = ch * chunk;
+      const long long items = (long long)B.num_active * chunk;
+      hipLaunchKernelGGL(localize_hypothesis_kernel, dim3((unsigned)((items + 63) / 64)), dim3(64), 0, stream, B);
+      hipLaunchKernelGGL(localize_score_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, stream, B);
+      hipLaunchKernelGGL(localize_replay_kernel, dim3((unsigned)((B.num_active + 63) / 64)), dim3(64), 0, stream, B);
+      TMI_HIP(hipGetLastError());
+      TMI_HIP(hipMemcpyAsync(state.data(), B.state, state.size() * sizeof(LocalizeState), hipMemcpyDeviceToHost, stream));
+      TMI_HIP(hipStreamSynchronize(stream));  // (also: `active` is free to change)
+      ++chunks_run;
+    }
+    hipLaunchKernelGGL(localize_final_kernel, dim3(S), dim3(64), 0, stream, B, (int)L->min_num_inliers, d_slot_inlier,
+                       d_num_inliers, d_status, d_pose_out, VB.ext);
+    TMI_HIP(timer.mark());
+    TMI_HIP(hipGetLastError());
+    std::vector<signed char> status_h((size_t)S);
+    std::vector<int> inliers_h((size_t)S);
+    std::vector<unsigned char> slot_inlier_h(obs_inlier ? M : 0);
+    std::vector<int> hyp_h(hypothesis_cost ? (size_t)S * K * 4 : 0);
+    TMI_HIP(hipMemcpyAsync(status_h.data(), d_status, (size_t)S, hipMemcpyDeviceToHost, stream));
+    TMI_HIP(hipMemcpyAsync(inliers_h.data(), d_num_inliers, (size_t)S * sizeof(int), hipMemcpyDeviceToHost, stream));
+    if (!slot_inlier_h.empty())
+      TMI_HIP(hipMemcpyAsync(slot_inlier_h.data(), d_slot_inlier, M, hipMemcpyDeviceToHost, stream));
+    if (!hyp_h.empty())
+      TMI_HIP(hipMemcpyAsync(hyp_h.data(), B.hypothesis_cost, hyp_h.size() * sizeof(int), hipMemcpyDeviceToHost, stream));
+    TMI_HIP(hipStreamSynchronize(stream));
+    sum->kernel_seconds = timer.seconds();
+    sum->num_chunks = chunks_run;
+    // BundleAdjustView on exactly the localised views, on the data already uploaded
+    std::vector<uint8_t> localised((size_t)Nc, 0);
+    int num_localised = 0;
+    for (int v = 0; v < S; ++v)
+      if (status_h[v] == 0) {
+        localised[sel_view[v]] = 1;
+        ++num_localised;
+      }
+    if (L->bundle_adjust_view && num_localised) {
+      std::vector<int> chain_ptr, chain_views;
+      build_view_chains(Nc, cam, P->camera_group, G, vptr, localised.data(), &chain_ptr, &chain_views);
+      VB.cam = d_cam;
+      VB.vptr = d_vptr;
+      VB.keys = d_keys;
+      VB.slot_pt = d_slot_pt;
+      VB.obs_xy = d_xy;
+      VB.pts = d_pts;
+      std::vector<int8_t> term((size_t)Nc, -1);
+      tmi_ba_view_batch_summary vs;
+      memset(&vs, 0, sizeof(vs));
+      const int rc = run_view_batch(s, VB, O, Nc, cam, chain_ptr, chain_views, {term.data(), nullptr, nullptr, nullptr},
+                                    &vs);
+      if (rc) return rc;
+      sum->kernel_seconds += vs.kernel_seconds;
+      for (int v = 0; v < S; ++v)
+        if (status_h[v] == 0 && term[sel_view[v]] != 0 && term[sel_view[v]] != 1) status_h[v] = 4;
+      if (n_intr) {
+        // (the kernel wrote back exactly the usable views' free intrinsics)
+        TMI_HIP(hipMemcpyAsync(P->intrinsics, VB.intr, (size_t)n_intr * sizeof(double), hipMemcpyDeviceToHost, stream));
+      }
+    }
+    std::vector<double> ext_h((size_t)6 * Nc);
+    TMI_HIP(hipMemcpyAsync(ext_h.data(), VB.ext, ext_h.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+    TMI_HIP(hipStreamSynchronize(stream));
+    for (int v = 0; v < S; ++v) {
+      const int c = sel_view[v];
+      const int n = (int)(sel_ptr[(size_t)v + 1] - sel_ptr[v]);
+      const int code = status_h[v];
+      const LocalizeState& st = state[v];
+      if (code == 0 || code == 4) std::copy(ext_h.begin() + 6 * (size_t)c, ext_h.begin() + 6 * (size_t)c + 6, P->extrinsics + 6 * (size_t)c);
+      switch (code) {
+        case 0: sum->num_localized++; break;
+        case 2: sum->num_no_model++; break;
+        case 3: sum->num_too_few_inliers++; break;
+        default: sum->num_failed_ba++; break;
+      }
+      sum->total_iterations += st.num_iterations;
+      if (view_status) view_status[c] = (int8_t)code;
+      if (view_num_inliers) view_num_inliers[c] = inliers_h[v];
+      if (view_num_iterations) view_num_iterations[c] = st.num_iterations;
+      if (view_best_iteration) view_best_iteration[c] = st.best_iteration;
+      if (view_best_solution) view_best_solution[c] = st.best_solution;
+      if (view_confidence) {
+        const double ratio = (double)inliers_h[v] / (double)n;  // :336-340
+        view_confidence[c] = 1.0 - std::pow(1.0 - std::pow(ratio, 3.0), (double)st.num_iterations);
+      }
+      if (obs_inlier)
+        for (long long o = sel_ptr[v]; o < sel_ptr[(size_t)v + 1]; ++o) obs_inlier[slot_obs[(size_t)o]] = slot_inlier_h[(size_t)o];
+      if (hypothesis_cost)
+        std::copy(hyp_h.begin() + (size_t)v * K * 4, hyp_h.begin() + ((size_t)v + 1) * K * 4,
+                  hypothesis_cost + (size_t)sel_rank[v] * K * 4);
+    }
+    return TMI_BA_OK;
+  });
+}
 }  // extern "C"

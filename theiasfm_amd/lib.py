@@ -38,6 +38,7 @@ EXPORTS = (
     "tmi_ba_filter_view_pairs_from_orientation",
     "tmi_ba_robust_rotation_options_init", "tmi_ba_estimate_global_rotations_robust",
     "tmi_ba_lud_position_options_init", "tmi_ba_estimate_global_positions_lud",
+    "tmi_ba_localization_options_init", "tmi_ba_localize_views",
     "tmi_ba_solver_structure_checksums",
     "tmi_ba_solver_operator_info",
 )
@@ -177,6 +178,12 @@ def load():
         PB, LO, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
         C.POINTER(abi.CLudPositionSummary)]
     L.tmi_ba_estimate_global_positions_lud.restype = C.c_int32
+    ZO = C.POINTER(abi.CLocalizationOptions)
+    L.tmi_ba_localization_options_init.argtypes = [ZO]
+    L.tmi_ba_localization_options_init.restype = None
+    L.tmi_ba_localize_views.argtypes = [P, ZO, O, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 9 + [
+        C.POINTER(abi.CLocalizationSummary)]
+    L.tmi_ba_localize_views.restype = C.c_int32
     L.tmi_ba_solver_structure_checksums.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     L.tmi_ba_solver_structure_checksums.restype = C.c_int32
     L.tmi_ba_solver_operator_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
@@ -520,6 +527,50 @@ def estimate_global_positions_lud(batch: abi.ViewPairBatch, fixed_view: int = 0,
     ran = ps.num_admm_iterations
     return dict(positions=pos, scales=scales, residuals=res, r_norms=r_norms[:ran].copy(), s_norms=s_norms[:ran].copy(),
                 summary=ps)
+
+
+def localize_views(problem: abi.Problem, view_error_threshold, options=None, ba_options=None, view_mask=None,
+                   samples=None, want_hypothesis_cost: bool = False):
+    """Batched LocalizeViewToReconstruction (calibrated path: P3P RANSAC, then the batched BundleAdjustView) over the
+    views view_mask selects (None = all).  view_error_threshold [Nc]: the squared threshold in normalised coordinates.
+    samples: optional [Nc, max_iterations, 3] int32 sample table (otherwise drawn from options.seed).
+    problem.extrinsics (and, with the adjustment, free intrinsics) are updated in place for the localised views.
+    Returns a dict: status [Nc] int8, num_correspondences, num_inliers, num_iterations, best_iteration, best_solution
+    [Nc] int32, confidence [Nc], obs_inlier [No] uint8, hypothesis_cost [num_selected, max_iterations, 4] int32 or
+    None, summary (CLocalizationSummary).  Raises EngineError on any failure."""
+    L = load()
+    o = options if options is not None else abi.localization_options()
+    bo = ba_options if ba_options is not None else abi.default_options()
+    nc = problem.num_cameras
+    vm = None if view_mask is None else np.ascontiguousarray(view_mask, dtype=np.uint8)
+    if vm is not None and vm.shape != (nc,):
+        raise ValueError(f"view_mask must have num_cameras = {nc} entries")
+    th = None if view_error_threshold is None else np.ascontiguousarray(view_error_threshold, dtype=np.float64)
+    if th is not None and th.shape != (nc,):
+        raise ValueError(f"view_error_threshold must have num_cameras = {nc} entries")
+    k = max(int(o.max_iterations), 0)
+    sm = None
+    if samples is not None:
+        sm = np.ascontiguousarray(samples, dtype=np.int32)
+        if sm.shape != (nc, k, 3):
+            raise ValueError(f"samples must have shape (num_cameras, max_iterations, 3) = ({nc}, {k}, 3)")
+    nsel = nc if vm is None else int(np.count_nonzero(vm))
+    status = np.full(nc, -1, dtype=np.int8)
+    i32 = [np.zeros(nc, dtype=np.int32) for _ in range(5)]
+    conf = np.zeros(nc)
+    inl = np.zeros(problem.num_observations, dtype=np.uint8)
+    hyp = np.full((nsel, min(k, 1 << 20), 4), -1, dtype=np.int32) if want_hypothesis_cost else None
+    cp = problem.as_c()
+    zs = abi.CLocalizationSummary()
+    ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+    st = L.tmi_ba_localize_views(C.byref(cp), C.byref(o), C.byref(bo), ptr(vm), ptr(th), ptr(sm),
+                                 0 if sm is None else 1, status.ctypes.data, *[a.ctypes.data for a in i32],
+                                 conf.ctypes.data, inl.ctypes.data, ptr(hyp), C.byref(zs))
+    if st != 0:
+        raise EngineError(st, "tmi_ba_localize_views")
+    return dict(status=status, num_correspondences=i32[0], num_inliers=i32[1], num_iterations=i32[2],
+                best_iteration=i32[3], best_solution=i32[4], confidence=conf, obs_inlier=inl, hypothesis_cost=hyp,
+                summary=zs)
 
 
 class Solver:

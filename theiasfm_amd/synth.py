@@ -703,3 +703,59 @@ def make_view_pair_batch(num_views: int, num_valid: int, num_invalid: int, seed:
     e = np.asarray(edges, dtype=np.int32).reshape(-1, 2)
     return abi.ViewPairBatch(aa, e[:, 0], e[:, 1], np.asarray(rot2).reshape(-1, 3), np.asarray(pos2).reshape(-1, 3)), pos
 
+
+
+def make_localization_batch(num_views: int, num_correspondences, seed: int, *, inlier_ratio=1.0, pixel_noise=0.5,
+                            num_points: int = 0, models=None, threshold_pixels: float = 4.0,
+                            image_size=(1000, 800)) -> Problem:
+    """Candidate views to localise against a fixed point cloud (tmi_ba_localize_views): a cloud uniform in a cube of
+    side 4 around the origin, V views on a sphere of radius about 8 looking at it with known poses (focal lengths
+    700..900 pixels, principal point (500, 400)), view v observing num_correspondences[v] distinct points (a scalar
+    serves every view).  A fraction inlier_ratio[v] of a view's observations are the projections with Gaussian noise of
+    pixel_noise[v] pixels; the others are outliers, uniform over the image.  models: optional camera model per view
+    (default PINHOLE without distortion).  Every view has an intrinsics group of its own, all intrinsics constant.
+    The extrinsics of the returned problem are zero (the call ignores them); meta holds `true_extrinsics` [V, 6],
+    `obs_is_inlier` [No] and `error_threshold` [V], the squared threshold in normalised coordinates for
+    threshold_pixels on a `image_size` image (ComputeResolutionScaledThreshold / focal length, squared)."""
+    rng = np.random.default_rng(seed)
+    V = int(num_views)
+    ncorr = np.broadcast_to(np.asarray(num_correspondences, dtype=np.int64), (V,)).copy()
+    ratio = np.broadcast_to(np.asarray(inlier_ratio, dtype=np.float64), (V,))
+    noise = np.broadcast_to(np.asarray(pixel_noise, dtype=np.float64), (V,))
+    Np = int(num_points) if num_points else int(max(ncorr.max(initial=1), 4))
+    if ncorr.max(initial=0) > Np:
+        raise ValueError("make_localization_batch: a view observes more points than there are")
+    X = rng.uniform(-2.0, 2.0, (Np, 3))
+    d = rng.normal(size=(V, 3))
+    Cpos = d / np.linalg.norm(d, axis=1, keepdims=True) * rng.uniform(7.0, 9.0, (V, 1))
+    aa = _look_at(Cpos, 0.3 * rng.normal(size=(V, 3)))
+    f = rng.uniform(700.0, 900.0, V)
+    model = np.zeros(V, dtype=np.int32) if models is None else np.asarray(models, dtype=np.int32)
+    K = _model_intrinsics(model, f)
+    if models is None:
+        K[:, 5:] = 0.0
+    sizes = np.asarray([abi.INTRINSICS_SIZE[m] for m in model], dtype=np.int32)
+    offset = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+    intr = np.concatenate([K[v, :sizes[v]] for v in range(V)]) if V else np.zeros(0)
+    cam = np.repeat(np.arange(V, dtype=np.int32), ncorr)
+    pt = np.concatenate([rng.permutation(Np)[:n] for n in ncorr]).astype(np.int32) if V else np.zeros(0, np.int32)
+    # interleave the views' observations so that a view's are not contiguous in the caller's arrays
+    order = rng.permutation(cam.shape[0])
+    cam, pt = cam[order], pt[order]
+    prob = Problem(np.concatenate([Cpos, aa], 1), np.arange(V, dtype=np.int32), np.zeros(V, np.uint8), model, offset,
+                   intr, np.ones(intr.shape[0], np.uint8), np.concatenate([X, np.ones((Np, 1))], 1),
+                   np.zeros(Np, np.uint8), cam, pt, np.zeros((cam.shape[0], 2)))
+    px = project(prob) + rng.normal(size=(cam.shape[0], 2)) * noise[cam][:, None]
+    is_inlier = np.ones(cam.shape[0], dtype=bool)
+    for v in range(V):
+        idx = np.nonzero(cam == v)[0]
+        n_out = int(round((1.0 - ratio[v]) * idx.shape[0]))
+        out = idx[rng.permutation(idx.shape[0])[:n_out]]
+        is_inlier[out] = False
+        px[out] = rng.uniform(0.0, 1.0, (n_out, 2)) * np.asarray(image_size, dtype=np.float64)
+    prob.obs_xy[:] = px
+    prob.meta["true_extrinsics"] = prob.extrinsics.copy()
+    prob.meta["obs_is_inlier"] = is_inlier
+    prob.meta["error_threshold"] = (threshold_pixels * max(image_size) / 1024.0 / f) ** 2
+    prob.extrinsics[:] = 0.0
+    return prob
