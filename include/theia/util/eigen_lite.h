@@ -4,8 +4,10 @@
 // Eigen-free shim keeps the same spelling so host code ports verbatim.
 #ifndef THEIA_MI355_EIGEN_LITE_H_
 #define THEIA_MI355_EIGEN_LITE_H_
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <vector>
 namespace Eigen {
 template <typename T, int N>
 struct LiteVector {
@@ -27,6 +29,47 @@ struct LiteVector {
   static constexpr int size() { return N; }
   static LiteVector Zero() { return LiteVector(); }
 };
+// The smallest dynamic float vector the descriptor interface needs (keypoints_and_descriptors.h stores
+// std::vector<Eigen::VectorXf>): size, element access, data, Constant / Zero, squaredNorm / norm and normalize.
+class LiteVectorXf {
+ public:
+  LiteVectorXf() {}
+  explicit LiteVectorXf(int n) : v_(static_cast<size_t>(n), 0.f) {}
+  static LiteVectorXf Constant(int n, float value) {
+    LiteVectorXf r(n);
+    for (float& x : r.v_) x = value;
+    return r;
+  }
+  static LiteVectorXf Zero(int n) { return LiteVectorXf(n); }
+  int size() const { return static_cast<int>(v_.size()); }
+  void resize(int n) { v_.resize(static_cast<size_t>(n)); }
+  float& operator[](int i) { return v_[static_cast<size_t>(i)]; }
+  const float& operator[](int i) const { return v_[static_cast<size_t>(i)]; }
+  float& operator()(int i) { return v_[static_cast<size_t>(i)]; }
+  const float& operator()(int i) const { return v_[static_cast<size_t>(i)]; }
+  float* data() { return v_.data(); }
+  const float* data() const { return v_.data(); }
+  float squaredNorm() const {
+    float s = 0.f;
+    for (const float x : v_) s += x * x;
+    return s;
+  }
+  float norm() const { return std::sqrt(squaredNorm()); }
+  void normalize() {
+    const float n = norm();
+    if (n > 0.f)
+      for (float& x : v_) x /= n;
+  }
+  LiteVectorXf normalized() const {
+    LiteVectorXf r(*this);
+    r.normalize();
+    return r;
+  }
+
+ private:
+  std::vector<float> v_;
+};
+typedef LiteVectorXf VectorXf;
 typedef LiteVector<double, 2> Vector2d;
 typedef LiteVector<double, 3> Vector3d;
 typedef LiteVector<double, 4> Vector4d;

@@ -44,7 +44,8 @@ typedef enum tmi_ba_status {
   TMI_BA_ERR_UNSUPPORTED = 5,      /* problem shape the device path lacks    */
   TMI_BA_ERR_EVALUATION_FAILED = 6,/* residual undefined at the start point  */
   TMI_BA_ERR_LINEAR_SOLVER = 7,    /* reduced system could not be solved     */
-  TMI_BA_ERR_COLLECTIVE = 8        /* the all-reduce callback reported error */
+  TMI_BA_ERR_COLLECTIVE = 8,       /* the all-reduce callback reported error */
+  TMI_BA_ERR_CAPACITY = 9          /* an output array of the caller is too small (tmi_ba_match_features) */
 } tmi_ba_status;
 
 /* ---- enums mirrored from the reference ---------------------------------- */
@@ -1189,6 +1190,69 @@ int32_t tmi_ba_localize_views(tmi_ba_problem* problem, const tmi_ba_localization
                               int32_t* view_num_iterations, int32_t* view_best_iteration, int32_t* view_best_solution,
                               double* view_confidence, uint8_t* obs_inlier, int32_t* hypothesis_cost,
                               tmi_ba_localization_summary* summary);
+
+/* ---- batched BruteForceFeatureMatcher: exact squared-L2 descriptor matching for many image pairs ---
+ * reference: BruteForceFeatureMatcher::MatchImagePair (brute_force_feature_matcher.cc:49-117) with IntersectMatches
+ * (feature_matcher_utils.cc:48-71) and the defaults of FeatureMatcherOptions (feature_matcher_options.h:45-71).  Not
+ * provided: cascade hashing, geometric verification, the databases.  A one-shot call without a tmi_ba_problem; THE
+ * DESCRIPTORS AND DISTANCES ARE fp32 (the one exception to this header's fp64 rule), as the reference's are.
+ * Image m owns the descriptor rows image_begin[m] .. image_begin[m + 1] - 1 of `descriptors` [rows x dim, row-major];
+ * every image goes to the device once however many pairs name it.  Per pair (image1, image2), N1 and N2 rows:
+ *   1. Distance, in fp32: acc = 0; for k = 0 .. dim-1 ascending: t = a[k] - b[k]; acc = acc + t * t -- every
+ *      subtraction, multiplication and addition rounded on its own (no FMA, no reassociation), subnormals kept.  This is
+ *      the reference's (a - b).squaredNorm() with the summation order fixed (Eigen leaves it open).  d(a, b) == d(b, a).
+ *   2. Forward pass: for every row i of image 1 the best and the second-best column of image 2 under the total order
+ *      (distance, then LOWER COLUMN INDEX; the reference's partial_sort leaves ties open).  A NaN distance never wins.
+ *   3. Ratio test as the reference types it (:58-59, :79): ratio_sq = (double)(float)(lowes_ratio * lowes_ratio), the
+ *      product formed in fp32; row i passes when (double)d0 < ratio_sq * (double)d1.  Without use_lowes_ratio every row
+ *      passes if N2 >= 1.  With it and N2 < 2 no row passes (DEVIATION: the reference reads past the end there).
+ *   4. pair_num_forward = the rows that passed.  Fewer than min_num_feature_matches (:84-86): status 1, no matches.
+ *   5. With keep_only_symmetric_matches the same pass with the roles swapped; the forward match (i, j) survives when
+ *      the reverse pass kept a match for row j of image 2 whose best column is i.  Then the count is tested against
+ *      min_num_feature_matches again (:116): fewer -> status 1, no matches.  (The reverse pass of a pair that failed
+ *      step 4 is still computed; nothing of it is visible.)
+ *   6. Otherwise status 0 and the matches in ascending feature1 index: (feature1, feature2, distance), the distance the
+ *      fp32 value of the forward pass.
+ * Empty images, N = 1, a pair of an image with itself and duplicate descriptors follow from these rules.  Non-finite
+ * descriptor values are the caller's error and are not validated.
+ * Outputs: pair_status [num_pairs] (0 ok, 1 too few matches), pair_num_forward [num_pairs], pair_match_begin
+ * [num_pairs + 1] (int64; the matches of pair p are pair_match_begin[p] .. pair_match_begin[p + 1] - 1), and
+ * match_feature1 / match_feature2 / match_distance [match_capacity].  When match_capacity is smaller than the total,
+ * the call returns TMI_BA_ERR_CAPACITY with the needed total in summary->num_matches; the three per-pair arrays are
+ * filled all the same and the match arrays are unspecified, so the caller can size them and call again.
+ * Pairs are processed in chunks of consecutive pairs whose work memory (34 bytes per descriptor row and direction: the
+ * neighbour triple, two flags, the scan and the compacted match) stays within a fixed budget; pairs_per_chunk > 0 sets
+ * the number of pairs of a chunk instead.
+ * THE RESULT DOES NOT DEPEND ON THE CHUNKING, nor on anything else about how the device is driven: steps 1 to 6 leave
+ * nothing open.
+ * TMI_BA_ERR_INVALID_ARGUMENT, before the device (options->device) is looked for: a null options or summary, a missing
+ * array, a negative count, dim < 1, image_begin that does not start at 0 or decreases, an image index out of range,
+ * a negative min_num_feature_matches or pairs_per_chunk, an image of 2^31 - 1 rows or more.  TMI_BA_ERR_UNSUPPORTED:
+ * a single pair whose rows exceed what a chunk can index (2^31 - 1 over both directions). */
+typedef struct tmi_ba_match_options {
+  int32_t use_lowes_ratio;              /* 1                                        */
+  float   lowes_ratio;                  /* 0.8f                                     */
+  int32_t keep_only_symmetric_matches;  /* 1                                        */
+  int32_t min_num_feature_matches;      /* 30                                       */
+  int32_t device;                       /* -1 = the current device                  */
+  int32_t pairs_per_chunk;              /* 0 = from the work-memory budget          */
+} tmi_ba_match_options;
+void tmi_ba_match_options_init(tmi_ba_match_options* options);
+
+typedef struct tmi_ba_match_summary {
+  int64_t num_matches;           /* over all pairs (the needed match_capacity)                                   */
+  int64_t distance_evaluations;  /* N1 N2 per pair and direction                                                  */
+  int32_t num_pairs_ok;          /* status 0                                                                      */
+  int32_t num_chunks;
+  double  kernel_seconds;        /* the chunks' launches, first to last of each chunk                             */
+  double  total_seconds;
+} tmi_ba_match_summary;
+
+int32_t tmi_ba_match_features(const tmi_ba_match_options* options, int32_t num_images, const int64_t* image_begin,
+                              const float* descriptors, int32_t dim, int32_t num_pairs, const int32_t* pair_image1,
+                              const int32_t* pair_image2, int64_t match_capacity, int8_t* pair_status,
+                              int32_t* pair_num_forward, int64_t* pair_match_begin, int32_t* match_feature1,
+                              int32_t* match_feature2, float* match_distance, tmi_ba_match_summary* summary);
 
 /* Test hook: FNV-1a checksums of the static structure arrays resident in HBM -- built in HBM by
  * sort / scan kernels (one rank, no shared intrinsics blocks; TMI_BA_HOST_SETUP=1 disables) or on

@@ -54,10 +54,12 @@ KERNEL_CLASS_NAMES = (
 
 ERR_INVALID_ARGUMENT = 1
 ERR_UNSUPPORTED = 5
+ERR_CAPACITY = 9
 
 STATUS_NAMES = {
     0: "OK", 1: "INVALID_ARGUMENT", 2: "NO_DEVICE", 3: "DEVICE", 4: "OUT_OF_MEMORY",
     5: "UNSUPPORTED", 6: "EVALUATION_FAILED", 7: "LINEAR_SOLVER", 8: "COLLECTIVE",
+    9: "CAPACITY",
 }
 
 
@@ -516,6 +518,46 @@ class CLocalizationSummary(C.Structure):
         ("total_iterations", C.c_int64),
         ("seconds", C.c_double),
         ("kernel_seconds", C.c_double),
+    ]
+
+
+class CMatchOptions(C.Structure):
+    """tmi_ba_match_options (FeatureMatcherOptions, feature_matcher_options.h:45-71)."""
+    _fields_ = [
+        ("use_lowes_ratio", C.c_int32),
+        ("lowes_ratio", C.c_float),
+        ("keep_only_symmetric_matches", C.c_int32),
+        ("min_num_feature_matches", C.c_int32),
+        ("device", C.c_int32),
+        ("pairs_per_chunk", C.c_int32),
+    ]
+
+
+def match_options(**overrides) -> CMatchOptions:
+    """The defaults of tmi_ba_match_options_init."""
+    o = CMatchOptions()
+    o.use_lowes_ratio = 1
+    o.lowes_ratio = 0.8
+    o.keep_only_symmetric_matches = 1
+    o.min_num_feature_matches = 30
+    o.device = -1
+    o.pairs_per_chunk = 0
+    for k, v in overrides.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
+class CMatchSummary(C.Structure):
+    """tmi_ba_match_summary."""
+    _fields_ = [
+        ("num_matches", C.c_int64),
+        ("distance_evaluations", C.c_int64),
+        ("num_pairs_ok", C.c_int32),
+        ("num_chunks", C.c_int32),
+        ("kernel_seconds", C.c_double),
+        ("total_seconds", C.c_double),
     ]
 
 

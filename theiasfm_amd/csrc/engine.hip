@@ -44,6 +44,7 @@
 #include "rotation_kernels.h"
 #include "position_kernels.h"
 #include "localize_kernels.h"
+#include "match_kernels.h"
 #include "select_kernels.h"
 #include "structure_gpu.h"
 #include <hipcub/hipcub.hpp>
@@ -1354,6 +1355,7 @@ const char* tmi_ba_status_string(int32_t st) {
     case TMI_BA_ERR_EVALUATION_FAILED: return "residual evaluation failed at the start point";
     case TMI_BA_ERR_LINEAR_SOLVER: return "linear solver failure";
     case TMI_BA_ERR_COLLECTIVE: return "collective failure";
+    case TMI_BA_ERR_CAPACITY: return "output capacity too small";
     default: return "unknown status";
   }
 }

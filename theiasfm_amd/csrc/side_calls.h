@@ -2532,4 +2532,252 @@ int32_t tmi_ba_localize_views(tmi_ba_problem* P, const tmi_ba_localization_optio
     return TMI_BA_OK;
   });
 }
+
+// ---- batched BruteForceFeatureMatcher: exact squared-L2 matching (match_kernels.h) -------------
+void tmi_ba_match_options_init(tmi_ba_match_options* o) {
+  if (!o) return;
+  o->use_lowes_ratio = 1;  // feature_matcher_options.h:45-71
+  o->lowes_ratio = 0.8f;
+  o->keep_only_symmetric_matches = 1;
+  o->min_num_feature_matches = 30;
+  o->device = -1;
+  o->pairs_per_chunk = 0;
+}
+}  // extern "C"
+namespace {
+// Work memory of a chunk of pairs, per descriptor row and direction: the nearest-neighbour triple (12), the two flags
+// (2), the scan's input and output (8) and the compacted matches (12).
+constexpr long long kMatchRowBytes = 34;
+constexpr long long kMatchWorkBudgetBytes = 64ll << 20;
+constexpr long long kMatchMaxChunkRows = 0x7ffffff0ll;
+
+// Page-locked host memory of one call, freed on every way out.
+struct PinnedBuffer {
+  void* p = nullptr;
+  PinnedBuffer() {}
+  PinnedBuffer(const PinnedBuffer&) = delete;
+  PinnedBuffer& operator=(const PinnedBuffer&) = delete;
+  hipError_t alloc(size_t bytes) { return hipHostMalloc(&p, std::max<size_t>(bytes, 16), hipHostMallocDefault); }
+  ~PinnedBuffer() {
+    if (p) hipHostFree(p);
+  }
+};
+// one_shot_batch writes the call's time to sum->seconds; tmi_ba_match_summary calls that field total_seconds and is
+// filled after the capacity check, so the scaffold gets this stand-in.
+struct MatchSeconds {
+  double seconds;
+};
+}  // namespace
+extern "C" {
+
+int32_t tmi_ba_match_features(const tmi_ba_match_options* M, int32_t num_images, const int64_t* image_begin,
+                              const float* descriptors, int32_t dim, int32_t num_pairs, const int32_t* pair_image1,
+                              const int32_t* pair_image2, int64_t match_capacity, int8_t* pair_status,
+                              int32_t* pair_num_forward, int64_t* pair_match_begin, int32_t* match_feature1,
+                              int32_t* match_feature2, float* match_distance, tmi_ba_match_summary* sum) {
+  if (!M || !sum) return bad_argument("match features: null options or summary");
+  memset(sum, 0, sizeof(*sum));
+  const double t0 = now_s();
+  // argument errors before the device is looked for
+  if (num_images < 0 || num_pairs < 0 || match_capacity < 0) return bad_argument("match features: negative count");
+  if (dim < 1) return bad_argument("match features: dim < 1");
+  if (!image_begin) return bad_argument("match features: missing image_begin");
+  if (M->min_num_feature_matches < 0 || M->pairs_per_chunk < 0)
+    return bad_argument("match features: negative min_num_feature_matches or pairs_per_chunk");
+  if (image_begin[0] != 0) return bad_argument("match features: image_begin must start at 0");
+  for (int m = 0; m < num_images; ++m) {
+    if (image_begin[m + 1] < image_begin[m]) return bad_argument("match features: image_begin decreases");
+    if (image_begin[m + 1] - image_begin[m] >= 0x7fffffffLL) return bad_argument("match features: an image of 2^31 rows");
+  }
+  const int64_t total_rows = image_begin[num_images];
+  if (total_rows && !descriptors) return bad_argument("match features: missing descriptors");
+  if (num_pairs && (!pair_image1 || !pair_image2 || !pair_status || !pair_num_forward))
+    return bad_argument("match features: missing pair array");
+  if (!pair_match_begin) return bad_argument("match features: missing pair_match_begin");
+  if (match_capacity && (!match_feature1 || !match_feature2 || !match_distance))
+    return bad_argument("match features: missing match array");
+  for (int p = 0; p < num_pairs; ++p)
+    if (pair_image1[p] < 0 || pair_image1[p] >= num_images || pair_image2[p] < 0 || pair_image2[p] >= num_images)
+      return bad_argument("match features: image index out of range");
+  const bool symmetric = M->keep_only_symmetric_matches != 0;
+  const int min_matches = M->min_num_feature_matches;
+  const float ratio_f = M->lowes_ratio * M->lowes_ratio;  // formed in fp32 (brute_force_feature_matcher.cc:58-59)
+  const double ratio_sq = (double)ratio_f;
+  // the chunks of consecutive pairs
+  auto rows_of = [&](int p) -> long long {
+    const long long n1 = image_begin[pair_image1[p] + 1] - image_begin[pair_image1[p]];
+    const long long n2 = image_begin[pair_image2[p] + 1] - image_begin[pair_image2[p]];
+    return n1 + (symmetric ? n2 : 0);
+  };
+  std::vector<int> chunk_begin(1, 0);
+  long long max_rows = 0;
+  int max_pairs = 0;
+  for (int p = 0; p < num_pairs;) {
+    long long rows = 0;
+    int q = p;
+    while (q < num_pairs) {
+      const long long r = rows_of(q);
+      if (r > kMatchMaxChunkRows) {
+        g_last_error = "match features: a pair with more than 2^31 rows over its directions";
+        return TMI_BA_ERR_UNSUPPORTED;
+      }
+      if (q > p) {
+        if (M->pairs_per_chunk ? q - p >= M->pairs_per_chunk : (rows + r) * kMatchRowBytes > kMatchWorkBudgetBytes) break;
+        if (rows + r > kMatchMaxChunkRows) break;
+      }
+      rows += r;
+      ++q;
+    }
+    max_rows = std::max(max_rows, rows);
+    max_pairs = std::max(max_pairs, q - p);
+    chunk_begin.push_back(q);
+    p = q;
+  }
+  for (int p = 0; p < num_pairs; ++p) {
+    const long long n1 = image_begin[pair_image1[p] + 1] - image_begin[pair_image1[p]];
+    const long long n2 = image_begin[pair_image2[p] + 1] - image_begin[pair_image2[p]];
+    sum->distance_evaluations += n1 * n2 * (symmetric ? 2 : 1);
+  }
+  pair_match_begin[0] = 0;
+  MatchSeconds secs = {0.0};
+  const int rc = one_shot_batch(M->device, "match features: no such device", num_pairs, t0, &secs, [&](OneShot* s) -> int {
+    const hipStream_t stream = s->stream;
+    float* d_desc;
+    TMI_HIP(s->upload(&d_desc, descriptors, (size_t)total_rows * (size_t)dim));
+    const size_t R = (size_t)max_rows;
+    MatchNn nn;
+    MatchTask* d_tasks;
+    int2* d_blocks;
+    int *d_fwd_task, *d_pair_counts, *d_flag, *d_scan, *d_counts;
+    MatchRecord* d_out;
+    unsigned char *d_pass, *d_keep;
+    const size_t max_blocks = (R + kMatchTile - 1) / kMatchTile + 2 * (size_t)max_pairs;
+    TMI_HIP(s->alloc(&nn.best_d, R));
+    TMI_HIP(s->alloc(&nn.best_i, R));
+    TMI_HIP(s->alloc(&nn.second_d, R));
+    TMI_HIP(s->alloc(&d_tasks, 2 * (size_t)max_pairs));
+    TMI_HIP(s->alloc(&d_blocks, max_blocks));
+    TMI_HIP(s->alloc(&d_fwd_task, (size_t)max_pairs));
+    TMI_HIP(s->alloc(&d_pair_counts, 2 * (size_t)max_pairs));
+    TMI_HIP(s->alloc(&d_pass, R));
+    TMI_HIP(s->alloc(&d_keep, R));
+    TMI_HIP(s->alloc(&d_flag, R + 1));
+    TMI_HIP(s->alloc(&d_scan, R + 1));
+    TMI_HIP(s->alloc(&d_counts, 4 * (size_t)max_pairs + 1));
+    TMI_HIP(s->alloc(&d_out, R));
+    size_t scan_bytes = 0;
+    TMI_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, d_flag, d_scan, (int)(R + 1), stream));
+    unsigned char* d_scan_tmp;
+    TMI_HIP(s->alloc(&d_scan_tmp, std::max<size_t>(scan_bytes, 16)));
+    PinnedBuffer h_counts_buf, h_out_buf;
+    TMI_HIP(h_counts_buf.alloc((4 * (size_t)max_pairs + 1) * sizeof(int)));
+    TMI_HIP(h_out_buf.alloc(R * sizeof(MatchRecord)));
+    const int* h_counts = (const int*)h_counts_buf.p;
+    const size_t lds = match_lds_bytes(dim);
+    const bool staged = dim <= kMatchMaxStagedDim;
+    int64_t total = 0;
+    std::vector<MatchTask> tasks;
+    std::vector<int2> blocks;
+    std::vector<int> fwd_task;
+    for (size_t c = 0; c + 1 < chunk_begin.size(); ++c) {
+      const int p0 = chunk_begin[c], np = chunk_begin[c + 1] - p0;
+      tasks.clear();
+      blocks.clear();
+      fwd_task.clear();
+      long long rows = 0;
+      for (int p = 0; p < np; ++p) {
+        const int i1 = pair_image1[p0 + p], i2 = pair_image2[p0 + p];
+        const int n1 = (int)(image_begin[i1 + 1] - image_begin[i1]), n2 = (int)(image_begin[i2 + 1] - image_begin[i2]);
+        MatchTask f = {image_begin[i1], image_begin[i2], n1, n2, (int)rows, p, 1, symmetric ? (int)(rows + n1) : -1};
+        fwd_task.push_back((int)tasks.size());
+        tasks.push_back(f);
+        rows += n1;
+        if (symmetric) {
+          MatchTask r = {image_begin[i2], image_begin[i1], n2, n1, (int)rows, p, 0, f.out_base};
+          tasks.push_back(r);
+          rows += n2;
+        }
+      }
+      for (size_t t = 0; t < tasks.size(); ++t)
+        for (int b = 0; b * kMatchTile < tasks[t].n_rows; ++b) blocks.push_back(make_int2((int)t, b));
+      const int num_rows = (int)rows, num_tasks = (int)tasks.size();
+      if (blocks.size() > max_blocks || (size_t)num_rows > R) {  // (the plan above bounds both)
+        s->error = "match features: chunk plan exceeded";
+        return TMI_BA_ERR_DEVICE;
+      }
+      TMI_HIP(hipMemcpyAsync(d_tasks, tasks.data(), tasks.size() * sizeof(MatchTask), hipMemcpyHostToDevice, stream));
+      if (!blocks.empty())
+        TMI_HIP(hipMemcpyAsync(d_blocks, blocks.data(), blocks.size() * sizeof(int2), hipMemcpyHostToDevice, stream));
+      TMI_HIP(hipMemcpyAsync(d_fwd_task, fwd_task.data(), fwd_task.size() * sizeof(int), hipMemcpyHostToDevice, stream));
+      TMI_HIP(hipMemsetAsync(d_pair_counts, 0, 2 * (size_t)np * sizeof(int), stream));
+      int* d_num_forward = d_pair_counts;
+      int* d_num_kept = d_pair_counts + np;
+      StreamTimer timer(stream);
+      TMI_HIP(timer.status);
+      TMI_HIP(timer.mark());
+      const unsigned row_grid = (unsigned)((num_rows + 255) / 256);
+      if (!blocks.empty()) {
+        if (staged)
+          hipLaunchKernelGGL(match_nn_kernel<true>, dim3((unsigned)blocks.size()), dim3(256), lds, stream, d_desc, (int)dim,
+                             d_tasks, d_blocks, nn);
+        else
+          hipLaunchKernelGGL(match_nn_kernel<false>, dim3((unsigned)blocks.size()), dim3(256), lds, stream, d_desc, (int)dim,
+                             d_tasks, d_blocks, nn);
+      }
+      if (num_rows) {
+        hipLaunchKernelGGL(match_ratio_kernel, dim3(row_grid), dim3(256), 0, stream, d_tasks, num_tasks, num_rows, nn,
+                           (int)(M->use_lowes_ratio != 0), ratio_sq, d_pass, d_num_forward);
+        hipLaunchKernelGGL(match_symmetric_kernel, dim3(row_grid), dim3(256), 0, stream, d_tasks, num_tasks, num_rows, nn,
+                           d_pass, d_num_forward, (int)symmetric, min_matches, d_keep, d_num_kept);
+      }
+      hipLaunchKernelGGL(match_flag_kernel, dim3((unsigned)(num_rows / 256 + 1)), dim3(256), 0, stream, d_tasks, num_tasks,
+                         num_rows, d_keep, d_num_kept, min_matches, d_flag);
+      TMI_HIP(hipcub::DeviceScan::ExclusiveSum(d_scan_tmp, scan_bytes, d_flag, d_scan, num_rows + 1, stream));
+      if (num_rows)
+        hipLaunchKernelGGL(match_compact_kernel, dim3(row_grid), dim3(256), 0, stream, d_tasks, num_tasks, num_rows, nn,
+                           d_flag, d_scan, d_out);
+      hipLaunchKernelGGL(match_pair_kernel, dim3((unsigned)(np / 256 + 1)), dim3(256), 0, stream, d_tasks, d_fwd_task, np,
+                         num_rows, d_num_forward, d_num_kept, min_matches, d_scan, d_counts);
+      TMI_HIP(timer.mark());
+      TMI_HIP(hipGetLastError());
+      // the counts, then exactly the chunk's matches
+      TMI_HIP(hipMemcpyAsync(h_counts_buf.p, d_counts, (4 * (size_t)np + 1) * sizeof(int), hipMemcpyDeviceToHost, stream));
+      TMI_HIP(hipStreamSynchronize(stream));  // (also: tasks, blocks and fwd_task are free to change)
+      sum->kernel_seconds += timer.seconds();
+      const int chunk_total = h_counts[4 * np];
+      if (chunk_total < 0 || chunk_total > num_rows) {
+        s->error = "match features: the device reported an impossible match count";
+        return TMI_BA_ERR_DEVICE;
+      }
+      for (int p = 0; p < np; ++p) {
+        pair_status[p0 + p] = (int8_t)h_counts[4 * p];
+        pair_num_forward[p0 + p] = h_counts[4 * p + 1];
+        pair_match_begin[p0 + p] = total + h_counts[4 * p + 2];
+        if (h_counts[4 * p] == 0) sum->num_pairs_ok++;
+      }
+      if (chunk_total && total + chunk_total <= match_capacity) {
+        const size_t n = (size_t)chunk_total;
+        TMI_HIP(hipMemcpyAsync(h_out_buf.p, d_out, n * sizeof(MatchRecord), hipMemcpyDeviceToHost, stream));
+        TMI_HIP(hipStreamSynchronize(stream));
+        const MatchRecord* rec = (const MatchRecord*)h_out_buf.p;
+        for (size_t i = 0; i < n; ++i) {
+          match_feature1[total + i] = rec[i].feature1;
+          match_feature2[total + i] = rec[i].feature2;
+          match_distance[total + i] = rec[i].distance;
+        }
+      }
+      total += chunk_total;
+      pair_match_begin[p0 + np] = total;
+      sum->num_chunks++;
+    }
+    sum->num_matches = total;
+    return TMI_BA_OK;
+  });
+  sum->total_seconds = now_s() - t0;
+  if (rc == TMI_BA_OK && sum->num_matches > match_capacity) {
+    g_last_error = "match features: match_capacity is smaller than the number of matches (summary->num_matches)";
+    return TMI_BA_ERR_CAPACITY;
+  }
+  return rc;
+}
 }  // extern "C"

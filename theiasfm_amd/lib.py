@@ -39,6 +39,7 @@ EXPORTS = (
     "tmi_ba_robust_rotation_options_init", "tmi_ba_estimate_global_rotations_robust",
     "tmi_ba_lud_position_options_init", "tmi_ba_estimate_global_positions_lud",
     "tmi_ba_localization_options_init", "tmi_ba_localize_views",
+    "tmi_ba_match_options_init", "tmi_ba_match_features",
     "tmi_ba_solver_structure_checksums",
     "tmi_ba_solver_operator_info",
 )
@@ -184,6 +185,12 @@ def load():
     L.tmi_ba_localize_views.argtypes = [P, ZO, O, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 9 + [
         C.POINTER(abi.CLocalizationSummary)]
     L.tmi_ba_localize_views.restype = C.c_int32
+    MO = C.POINTER(abi.CMatchOptions)
+    L.tmi_ba_match_options_init.argtypes = [MO]
+    L.tmi_ba_match_options_init.restype = None
+    L.tmi_ba_match_features.argtypes = [MO, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                        C.c_void_p, C.c_int64] + [C.c_void_p] * 6 + [C.POINTER(abi.CMatchSummary)]
+    L.tmi_ba_match_features.restype = C.c_int32
     L.tmi_ba_solver_structure_checksums.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     L.tmi_ba_solver_structure_checksums.restype = C.c_int32
     L.tmi_ba_solver_operator_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
@@ -571,6 +578,53 @@ def localize_views(problem: abi.Problem, view_error_threshold, options=None, ba_
     return dict(status=status, num_correspondences=i32[0], num_inliers=i32[1], num_iterations=i32[2],
                 best_iteration=i32[3], best_solution=i32[4], confidence=conf, obs_inlier=inl, hypothesis_cost=hyp,
                 summary=zs)
+
+
+def match_features(image_begin, descriptors, pair_image1, pair_image2, options=None, match_capacity=None):
+    """Batched BruteForceFeatureMatcher (exact fp32 squared-L2 matching, ratio test, symmetric intersection) over the
+    image pairs (pair_image1[p], pair_image2[p]).  image_begin [num_images + 1] int64 row offsets into descriptors
+    [rows, dim] float32.  match_capacity: None sizes the match arrays for the most the options allow (the rows of
+    image 1 over the pairs); a number is passed through, and a capacity that is too small comes back as `status` ==
+    abi.ERR_CAPACITY with the per-pair arrays filled and summary.num_matches the needed total.
+    Returns a dict: status (the call's), pair_status [P] int8, pair_num_forward [P] int32, pair_match_begin [P + 1]
+    int64, feature1 / feature2 [total] int32, distance [total] float32, summary (CMatchSummary).  Raises EngineError
+    on any other failure."""
+    L = load()
+    o = options if options is not None else abi.match_options()
+    ib = np.ascontiguousarray(image_begin, dtype=np.int64)
+    desc = np.ascontiguousarray(descriptors, dtype=np.float32)
+    if ib.ndim != 1 or ib.shape[0] < 1:
+        raise ValueError("image_begin must have num_images + 1 entries")
+    if desc.ndim != 2:
+        raise ValueError("descriptors must be [rows, dim]")
+    p1 = np.ascontiguousarray(pair_image1, dtype=np.int32)
+    p2 = np.ascontiguousarray(pair_image2, dtype=np.int32)
+    if p1.ndim != 1 or p1.shape != p2.shape:
+        raise ValueError("pair_image1 and pair_image2 must be one-dimensional and of one length")
+    if desc.shape[0] != int(ib[-1]):
+        raise ValueError("descriptors must have image_begin[-1] rows")
+    num_images, num_pairs = ib.shape[0] - 1, p1.shape[0]
+    if match_capacity is None:
+        ok = (p1 >= 0) & (p1 < num_images)
+        n1 = np.diff(ib)[p1[ok]] if num_images else np.zeros(0, np.int64)
+        cap = int(np.maximum(n1, 0).sum())
+    else:
+        cap = int(match_capacity)
+    status = np.zeros(num_pairs, dtype=np.int8)
+    nfwd = np.zeros(num_pairs, dtype=np.int32)
+    begin = np.zeros(num_pairs + 1, dtype=np.int64)
+    f1 = np.zeros(max(cap, 0), dtype=np.int32)
+    f2 = np.zeros(max(cap, 0), dtype=np.int32)
+    dist = np.zeros(max(cap, 0), dtype=np.float32)
+    ms = abi.CMatchSummary()
+    st = L.tmi_ba_match_features(C.byref(o), num_images, ib.ctypes.data, desc.ctypes.data, desc.shape[1], num_pairs,
+                                 p1.ctypes.data, p2.ctypes.data, cap, status.ctypes.data, nfwd.ctypes.data,
+                                 begin.ctypes.data, f1.ctypes.data, f2.ctypes.data, dist.ctypes.data, C.byref(ms))
+    if st not in (0, abi.ERR_CAPACITY):
+        raise EngineError(st, "tmi_ba_match_features")
+    n = 0 if st else int(begin[-1])
+    return dict(status=st, pair_status=status, pair_num_forward=nfwd, pair_match_begin=begin, feature1=f1[:n],
+                feature2=f2[:n], distance=dist[:n], summary=ms)
 
 
 class Solver:

@@ -759,3 +759,71 @@ def make_localization_batch(num_views: int, num_correspondences, seed: int, *, i
     prob.meta["error_threshold"] = (threshold_pixels * max(image_size) / 1024.0 / f) ** 2
     prob.extrinsics[:] = 0.0
     return prob
+
+
+def make_matching_batch(num_images: int, num_descriptors, dim: int, seed: int, *, match_share: float = 0.5,
+                        noise: float = 0.05, num_duplicates: int = 0, num_ties: int = 0, integer: bool = False,
+                        pool_size: int = 0):
+    """Descriptors for tmi_ba_match_features: a pool of pool_size (0: max(num_descriptors)) unit-norm "scene"
+    descriptors; image m holds num_descriptors[m] rows (a scalar serves every image), of which a share match_share are
+    pool descriptors (the first ones of the pool, cyclically, so that they recur across images) with Gaussian noise of
+    `noise` per element and the others are random; the rows of an image are shuffled.  integer: values are whole
+    numbers 0..255 instead (every fp32 operation on them is exact for dim <= 258).
+    num_duplicates: in every image with at least two rows, that many rows are overwritten with copies of other rows of
+    the same image: for a query that is nearest to such a row, best == second in every bit.
+    num_ties: that many rows q of image 0 are queries with two equally near columns in every other image m with at
+    least two rows: rows lo and hi of image m become copies of q with element 0 moved by -e and +e (e = 1 where
+    integer, else 2^-6; element 0 of q is first rounded so that both are exact), so d(q, lo) == d(q, hi) == e^2.
+    Returns (image_begin int64 [num_images + 1], descriptors float32 [rows, dim], meta) with meta['duplicate_rows'] a
+    list of (image, row, source row) and meta['tie_rows'] a list of (q, image, lo, hi)."""
+    rng = np.random.default_rng(seed)
+    n = np.broadcast_to(np.asarray(num_descriptors, dtype=np.int64), (int(num_images),)).copy()
+    begin = np.concatenate([[0], np.cumsum(n)]).astype(np.int64)
+    pool_n = int(pool_size) if pool_size else int(n.max(initial=0))
+
+    def draw(k):
+        if integer:
+            return rng.integers(0, 256, (k, dim)).astype(np.float32)
+        x = rng.normal(size=(k, dim))
+        return (x / np.maximum(np.linalg.norm(x, axis=1, keepdims=True), 1e-12)).astype(np.float32)
+
+    pool = draw(pool_n)
+    parts, dups, ties = [], [], []
+    for m in range(int(num_images)):
+        k = int(n[m])
+        shared = int(round(match_share * k))
+        a = pool[np.arange(shared) % max(pool_n, 1)].copy() if pool_n else pool[:0].copy()
+        if integer:
+            a = np.clip(a + np.rint(rng.normal(size=a.shape) * noise * 255.0), 0, 255).astype(np.float32)
+        else:
+            a = (a + rng.normal(size=a.shape).astype(np.float32) * np.float32(noise)).astype(np.float32)
+        rows = np.concatenate([a, draw(k - shared)], 0)[rng.permutation(k)] if k else np.zeros((0, dim), np.float32)
+        parts.append(rows)
+    used = [set() for _ in range(int(num_images))]
+    e = np.float32(1.0 if integer else 2.0 ** -6)
+    for q in range(min(int(num_ties), int(n[0]) if num_images else 0)):
+        base = parts[0][q]
+        base[0] = np.float32(min(max(base[0], 1.0), 254.0)) if integer else np.float32(np.round(base[0] * 32.0) / 32.0)
+        used[0].add(q)
+        for m in range(1, int(num_images)):
+            free = [r for r in range(int(n[m])) if r not in used[m]]
+            if len(free) < 2:
+                continue
+            lo, hi = (int(v) for v in rng.choice(free, 2, replace=False))
+            parts[m][lo] = base
+            parts[m][hi] = base
+            parts[m][lo, 0] = base[0] - e
+            parts[m][hi, 0] = base[0] + e
+            used[m].update((lo, hi))
+            ties.append((q, m, lo, hi))
+    for m in range(int(num_images)):
+        for _ in range(int(num_duplicates)):
+            free = [r for r in range(int(n[m])) if r not in used[m]]
+            if len(free) < 2:
+                break
+            src, dst = (int(v) for v in rng.choice(free, 2, replace=False))
+            parts[m][dst] = parts[m][src]
+            used[m].update((src, dst))
+            dups.append((m, dst, src))
+    desc = np.concatenate(parts, 0) if parts else np.zeros((0, dim), np.float32)
+    return begin, np.ascontiguousarray(desc, dtype=np.float32), {"duplicate_rows": dups, "tie_rows": ties}
