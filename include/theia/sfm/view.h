@@ -8,13 +8,20 @@
 #include "theia/sfm/feature.h"
 #include "theia/sfm/types.h"
 namespace theia {
-// reference: sfm/camera_intrinsics_prior.h -- of the priors only the focal length's, which
-// DoesViewHaveKnownIntrinsics (localize_view_to_reconstruction.cc:55-58) reads.
+// reference: sfm/camera_intrinsics_prior.h -- of the priors the focal length's, which DoesViewHaveKnownIntrinsics
+// (localize_view_to_reconstruction.cc:55-58) and EstimateTwoViewInfo read, and the image size and the principal
+// point, from which EstimateTwoViewInfo centres the pixels and scales its threshold.
 struct CameraIntrinsicsPrior {
+  int image_width = 0;
+  int image_height = 0;
   struct FocalLength {
     bool is_set = false;
     double value[1] = {0.0};
   } focal_length;
+  struct PrincipalPoint {
+    bool is_set = false;
+    double value[2] = {0.0, 0.0};
+  } principal_point;
 };
 class View {
  public:

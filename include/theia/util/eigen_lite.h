@@ -69,6 +69,17 @@ class LiteVectorXf {
  private:
   std::vector<float> v_;
 };
+// A 3x3 double matrix, column-major as Eigen's default, with element access and data().
+struct LiteMatrix3d {
+  double m[9];
+  LiteMatrix3d() { for (int i = 0; i < 9; ++i) m[i] = 0.0; }
+  double& operator()(int r, int c) { return m[r + 3 * c]; }
+  const double& operator()(int r, int c) const { return m[r + 3 * c]; }
+  double* data() { return m; }
+  const double* data() const { return m; }
+  static LiteMatrix3d Zero() { return LiteMatrix3d(); }
+};
+typedef LiteMatrix3d Matrix3d;
 typedef LiteVectorXf VectorXf;
 typedef LiteVector<double, 2> Vector2d;
 typedef LiteVector<double, 3> Vector3d;

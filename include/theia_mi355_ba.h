@@ -739,8 +739,9 @@ int32_t tmi_ba_adjust_two_views(tmi_ba_two_view_batch* batch, int32_t point_dof,
  * indices.  That mode is NOT a path of the reference (which calls this function only to adjust): it is an extension
  * for staging the steps and for tests.
  * One wavefront per pair in three launches (triangulate, solve, accept); a pair's result does not depend on the rest
- * of the batch.  Out of scope: the RANSAC of EstimateTwoViewInfo (:128-134), guided matching (:157-168)
- * and the homography inlier count (:124). */
+ * of the batch.  The RANSAC of EstimateTwoViewInfo (:128-134) that precedes this step is provided for the UNCALIBRATED
+ * branch (tmi_ba_estimate_uncalibrated_relative_poses below), not for the calibrated (five-point) one.  Out of scope
+ * (DESIGN 9): guided matching (:157-168) and the homography inlier count (:124). */
 typedef struct tmi_ba_two_view_verification_options {
   int32_t min_num_inlier_matches;               /* 30   (two_view_match_geometric_verification.h:59-92) */
   double triangulation_max_reprojection_error;  /* 15.0 */
@@ -1253,6 +1254,115 @@ int32_t tmi_ba_match_features(const tmi_ba_match_options* options, int32_t num_i
                               const int32_t* pair_image2, int64_t match_capacity, int8_t* pair_status,
                               int32_t* pair_num_forward, int64_t* pair_match_begin, int32_t* match_feature1,
                               int32_t* match_feature2, float* match_distance, tmi_ba_match_summary* summary);
+
+/* ---- batched EstimateUncalibratedRelativePose: eight-point RANSAC for many uncalibrated view pairs -------
+ * reference: the UNCALIBRATED branch of EstimateTwoViewInfo (estimate_twoview_info.cc:202-248), which the reference's
+ * application runs for every view without an EXIF focal length: EstimateUncalibratedRelativePose with
+ * RansacType::RANSAC (estimators/estimate_uncalibrated_relative_pose.cc:67-172) and
+ * SampleConsensusEstimator::Estimate with InlierSupport (solvers/sample_consensus_estimator.h:246-344).  Not provided:
+ * the calibrated (five-point) branch, PROSAC, LMED and exhaustive sampling, use_mle, use_Tdd_test, guided matching.
+ * A one-shot call without a tmi_ba_problem.  Pair p owns the correspondences pair_offset[p] .. pair_offset[p + 1] - 1,
+ * numbered 0..n-1; feature1 / feature2 [2 per correspondence] are CENTRED pixels: the principal point removed and NO
+ * focal division, as NormalizeFeatures leaves them when a focal prior is missing (estimate_twoview_info.cc:82-85).
+ * pair_error_threshold [num_pairs] is RansacParameters::error_thresh per pair, the SQUARED threshold in pixels^2
+ * (:220-221: the product of the two resolution-scaled thresholds), computed by the caller.  pair_mask [num_pairs]
+ * selects the pairs (NULL = all).  Per selected pair, in this order:
+ *   1. n < 8 (the sampler refuses to initialise)                                                   -> status 1.
+ *   2. The sample of iteration i.  samples_given != 0: the caller's samples[8 (max_iterations p + i) + k].  Otherwise
+ *      deterministic in `seed` and stateless, as step 2 of tmi_ba_localize_views with 3 replaced by 8: word
+ *      c = 8 (q 2^32 + i) + k (mod 2^64) of the splitmix64 stream from state `seed`, q = pair_stream[p] (EXTENSION; NULL:
+ *      q = p), u = ((word >> 11) + 0.5) 2^-53, j_k = min(k + floor(u (n - k)), n - 1), then the eight swaps of a partial
+ *      Fisher-Yates on the identity permutation, swap(a[k], a[j_k]) for k = 0..7; the sample is a[0..7].
+ *      THE SAMPLE SEQUENCES ARE NOT THE REFERENCE'S (its RandomSampler carries its permutation along and draws from
+ *      another generator).
+ *   3. NormalizedEightPointFundamentalMatrix on the eight points (eight_point_fundamental_matrix.cc:54-113,
+ *      pose/util.cc:82-115): per image the centroid (sums in sample order, / 8), rms = sqrt(sum((dx^2 + dy^2)) / 8),
+ *      nf = sqrt(2) / rms, T = [nf 0 -nf cx; 0 nf -nf cy; 0 0 1]; the 8x9 rows
+ *      (x2 x1, x2 y1, x2, y2 x1, y2 y1, y2, x1, y1, 1) of the normalised points; the kernel by elimination with FULL
+ *      pivoting; the transpose (so that F(i, j) = f[3 i + j]); the nearest rank-2 matrix by a 3x3 SVD; F = T2^T F T1.
+ *      What Eigen leaves open is fixed: the pivot is the entry of largest magnitude, ties go to the lowest (row,
+ *      column); the rank counts the pivots with |pivot| > 8 DBL_EPSILON |largest pivot| (FullPivLU's default threshold
+ *      for an 8x9 matrix) and a rank other than 8 gives NO MODEL; the kernel vector (back-substitution from 1 in the last
+ *      permuted column, each sum in ascending column order) is normalised to unit length with its largest-magnitude entry
+ *      (the first among equals) positive.  Every 3x3 SVD of this call is a one-sided Jacobi iteration on the columns:
+ *      10 sweeps over the column pairs (0,1), (0,2), (1,2), a pair with a zero inner product skipped, then the columns
+ *      sorted by descending squared norm with a stable network (a tie keeps the lower column first).  The rank-2 matrix
+ *      is the sum of the two leading sigma_j u_j v_j^T.
+ *   4. FocalLengthsFromFundamentalMatrix (fundamental_matrix_util.cc:57-133): the epipoles are the right null vectors of
+ *      F and F^T, each formed as the cross product of two rows (of F, of F^T) with the largest squared norm among
+ *      r0 x r1, r0 x r2, r1 x r2 (the first among equals), NOT normalised: the focal lengths depend on neither their
+ *      length nor their sign.  epipole.x() == 0 for either gives no model.  The two in-plane rotations need no atan2, sin
+ *      or cos: cos = e_x / r, sin = -e_y / r, r = sqrt(e_x^2 + e_y^2).  Then the factorised matrix and the two
+ *      quotients in the reference's association.  A negative square gives no model; so does a NaN square (DEVIATION:
+ *      the reference's `< 0` lets NaN through).
+ *   5. EssentialMatrixFromFundamentalMatrix, E = diag(f2, f2, 1) F diag(f1, f1, 1), then GetBestPoseFromEssentialMatrix
+ *      (essential_matrix_utils.cc:57-148) on the eight sampled correspondences divided by the two focal lengths: the
+ *      SVD; with both determinant sign fixes applied the third columns of U and V are the cross products of their first
+ *      two, and are formed so; rotation1 = U d V^T, rotation2 = U d^T V^T, translation = U.col(2).normalized(); the four
+ *      candidates (R1, -R1^T t), (R1, R1^T t), (R2, -R2^T t), (R2, R2^T t) in the reference's order;
+ *      IsTriangulatedPointInFrontOfCameras (triangulation.cc:216-232) per point; the FIRST candidate with the largest
+ *      count wins (std::max_element).  Any count is accepted (:122-127).  (Which of the two SVD sign conventions a
+ *      library picks permutes the four candidates; the winner differs only between candidates of equal count.)
+ *   6. The cost of the ONE model of a sample: the correspondences (the eight sampled ones included) for which the
+ *      cheirality test on the focal-normalised pair fails, or the SquaredSampsonDistance (pose/util.cc:56-68) of the
+ *      CENTRED pixels under F is not below the threshold, or that distance is NaN.
+ *   7. The replay is step 5 of tmi_ba_localize_views with a sample size of 8 and one model per sample: strict <;
+ *      inlier_ratio < 8 / n skips the update of the bound; ComputeMaxIterations(8, ...) from a host-made table; a sample
+ *      without a model counts as an iteration; THE RESULT DOES NOT DEPEND ON chunk_iterations (0: max(min_iterations,
+ *      64)).
+ *   8. Final: the inlier mask of the best model, num_inliers, confidence = 1 - (1 - (num_inliers / n)^8)^num_iterations
+ *      (host); no model in any iteration -> status 2; otherwise status 0 and the model: fundamental_matrix [9]
+ *      column-major as the reference stores it (as estimated: no scale is imposed), the focal lengths, the rotation as
+ *      angle-axis (Ceres' RotationMatrixToAngleAxis, the routine tmi_ba_localize_views uses) and the position.
+ * pair_status: -1 not selected, 0, 1, 2.  Every per-pair output [num_pairs] ([9 / 3 num_pairs]) may be NULL.
+ * corr_inlier [pair_offset[num_pairs]] (optional): 1 for the inliers of the best model, 0 elsewhere.  hypothesis_cost
+ * [num_selected * max_iterations] (optional, for tests; selected pairs in ascending index): the cost of every replayed
+ * hypothesis, -1 for no model or not replayed.
+ * ComputeMaxIterations and the confidence are evaluated on the host (log and pow of the C library); steps 3 to 6 use
+ * + - * / and sqrt only and are never contracted into FMA.
+ * TMI_BA_ERR_INVALID_ARGUMENT, before the device (options->device) is looked for: a null options or summary, a missing
+ * array, a negative count, pair_offset that does not start at 0 or decreases, the CHECKs of the
+ * SampleConsensusEstimator constructor (an error threshold of an attempted pair that is not positive, min_inlier_ratio
+ * outside [0, 1], failure_probability outside (0, 1), max_iterations < min_iterations), max_iterations above 2^20, a
+ * negative chunk_iterations, 2^31 - 1 correspondences or more, samples_given without samples, and a sample of an
+ * attempted pair with a repeated or out-of-range index. */
+typedef struct tmi_ba_two_view_ransac_options {
+  double   failure_probability;  /* 0.01 (sample_consensus_estimator.h:57-65; EstimateTwoViewInfo sets
+                                    1 - expected_ransac_confidence, estimate_twoview_info.h:69)                  */
+  double   min_inlier_ratio;     /* 0                                                                          */
+  int32_t  min_iterations;       /* 10   (EstimateTwoViewInfoOptions, estimate_twoview_info.h:70)              */
+  int32_t  max_iterations;       /* 1000 (estimate_twoview_info.h:71)                                          */
+  int32_t  chunk_iterations;     /* 0 = the engine's choice                                                    */
+  int32_t  device;               /* -1 = the current device                                                    */
+  uint64_t seed;                 /* 0                                                                          */
+} tmi_ba_two_view_ransac_options;
+void tmi_ba_two_view_ransac_options_init(tmi_ba_two_view_ransac_options* options);
+
+typedef struct tmi_ba_two_view_ransac_summary {
+  int32_t num_pairs;                    /* selected pairs                                   */
+  int32_t num_estimated;                /* status 0                                         */
+  int32_t num_too_few_correspondences;  /* status 1                                         */
+  int32_t num_no_model;                 /* status 2                                         */
+  int32_t num_chunks;                   /* chunks of iterations evaluated                   */
+  int32_t reserved;
+  int64_t total_iterations;             /* RANSAC iterations over the attempted pairs       */
+  int64_t total_scores;                 /* correspondences times iterations replayed        */
+  double  seconds;
+  double  kernel_seconds;               /* the launches, first to last (the per-chunk read-back of the done flags
+                                           included)                                        */
+  double  hypothesis_seconds;           /* of kernel_seconds: the hypothesis launches,      */
+  double  score_seconds;                /* the scoring launches                             */
+  double  replay_seconds;               /* and the replay launches                          */
+} tmi_ba_two_view_ransac_summary;
+
+int32_t tmi_ba_estimate_uncalibrated_relative_poses(
+    const tmi_ba_two_view_ransac_options* options, int32_t num_pairs, const int64_t* pair_offset,
+    const double* feature1, const double* feature2, const double* pair_error_threshold, const uint8_t* pair_mask,
+    const uint32_t* pair_stream, const int32_t* samples, int32_t samples_given, int8_t* pair_status,
+    int32_t* pair_num_correspondences, int32_t* pair_num_inliers, int32_t* pair_num_iterations,
+    int32_t* pair_best_iteration, double* pair_confidence, double* fundamental_matrix, double* focal_length1,
+    double* focal_length2, double* rotation, double* position, uint8_t* corr_inlier, int32_t* hypothesis_cost,
+    tmi_ba_two_view_ransac_summary* summary);
 
 /* Test hook: FNV-1a checksums of the static structure arrays resident in HBM -- built in HBM by
  * sort / scan kernels (one rank, no shared intrinsics blocks; TMI_BA_HOST_SETUP=1 disables) or on

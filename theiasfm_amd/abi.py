@@ -521,6 +521,56 @@ class CLocalizationSummary(C.Structure):
     ]
 
 
+class CTwoViewRansacOptions(C.Structure):
+    """tmi_ba_two_view_ransac_options (RansacParameters, sample_consensus_estimator.h:57-65, with the iteration counts of
+    EstimateTwoViewInfoOptions, estimate_twoview_info.h:69-71)."""
+    _fields_ = [
+        ("failure_probability", C.c_double),
+        ("min_inlier_ratio", C.c_double),
+        ("min_iterations", C.c_int32),
+        ("max_iterations", C.c_int32),
+        ("chunk_iterations", C.c_int32),
+        ("device", C.c_int32),
+        ("seed", C.c_uint64),
+    ]
+
+
+def two_view_ransac_options(**overrides) -> CTwoViewRansacOptions:
+    """The defaults of tmi_ba_two_view_ransac_options_init."""
+    o = CTwoViewRansacOptions()
+    o.failure_probability = 0.01
+    o.min_inlier_ratio = 0.0
+    o.min_iterations = 10
+    o.max_iterations = 1000
+    o.chunk_iterations = 0
+    o.device = -1
+    o.seed = 0
+    for k, v in overrides.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
+class CTwoViewRansacSummary(C.Structure):
+    """tmi_ba_two_view_ransac_summary."""
+    _fields_ = [
+        ("num_pairs", C.c_int32),
+        ("num_estimated", C.c_int32),
+        ("num_too_few_correspondences", C.c_int32),
+        ("num_no_model", C.c_int32),
+        ("num_chunks", C.c_int32),
+        ("reserved", C.c_int32),
+        ("total_iterations", C.c_int64),
+        ("total_scores", C.c_int64),
+        ("seconds", C.c_double),
+        ("kernel_seconds", C.c_double),
+        ("hypothesis_seconds", C.c_double),
+        ("score_seconds", C.c_double),
+        ("replay_seconds", C.c_double),
+    ]
+
+
 class CMatchOptions(C.Structure):
     """tmi_ba_match_options (FeatureMatcherOptions, feature_matcher_options.h:45-71)."""
     _fields_ = [

@@ -2781,3 +2781,278 @@ int32_t tmi_ba_match_features(const tmi_ba_match_options* M, int32_t num_images,
   return rc;
 }
 }  // extern "C"
+
+// ---- batched EstimateUncalibratedRelativePose: eight-point RANSAC (two_view_ransac_kernels.h) ----
+extern "C" {
+void tmi_ba_two_view_ransac_options_init(tmi_ba_two_view_ransac_options* o) {
+  if (!o) return;
+  o->failure_probability = 0.01;  // sample_consensus_estimator.h:57-65
+  o->min_inlier_ratio = 0.0;
+  o->min_iterations = 10;         // estimate_twoview_info.h:70
+  o->max_iterations = 1000;       // estimate_twoview_info.h:71
+  o->chunk_iterations = 0;
+  o->device = -1;
+  o->seed = 0;
+}
+}  // extern "C"
+namespace {
+// SampleConsensusEstimator::ComputeMaxIterations (sample_consensus_estimator.h:215-243) for a sample of eight, without
+// the T(d,d) test.
+int two_view_max_iterations(double inlier_ratio, double log_failure_prob, int min_iterations, int max_iterations) {
+  if (inlier_ratio == 1.0) return min_iterations;
+  const double log_prob = std::log(1.0 - std::pow(inlier_ratio, 8.0)) - std::numeric_limits<double>::epsilon();
+  const double num_iterations = log_failure_prob / log_prob;
+  return (int)std::max((double)min_iterations, std::min(num_iterations, (double)max_iterations));
+}
+}  // namespace
+extern "C" {
+
+int32_t tmi_ba_estimate_uncalibrated_relative_poses(
+    const tmi_ba_two_view_ransac_options* L, int32_t num_pairs, const int64_t* pair_offset, const double* feature1,
+    const double* feature2, const double* pair_error_threshold, const uint8_t* pair_mask, const uint32_t* pair_stream,
+    const int32_t* samples, int32_t samples_given, int8_t* pair_status, int32_t* pair_num_correspondences,
+    int32_t* pair_num_inliers, int32_t* pair_num_iterations, int32_t* pair_best_iteration, double* pair_confidence,
+    double* fundamental_matrix, double* focal_length1, double* focal_length2, double* rotation, double* position,
+    uint8_t* corr_inlier, int32_t* hypothesis_cost, tmi_ba_two_view_ransac_summary* sum) {
+  if (!L || !sum) return bad_argument("uncalibrated relative poses: null options or summary");
+  memset(sum, 0, sizeof(*sum));
+  const double t0 = now_s();
+  // argument errors before the device is looked for
+  const int Npair = num_pairs;
+  if (Npair < 0) return bad_argument("uncalibrated relative poses: negative size");
+  if (!pair_offset) return bad_argument("uncalibrated relative poses: missing array");
+  if (pair_offset[0] != 0) return bad_argument("uncalibrated relative poses: pair_offset must start at 0");
+  for (int p = 0; p < Npair; ++p)
+    if (pair_offset[p + 1] < pair_offset[p]) return bad_argument("uncalibrated relative poses: pair_offset decreases");
+  const int64_t total = pair_offset[Npair];
+  if (total >= (int64_t)0x7fffffffLL) return bad_argument("uncalibrated relative poses: more than 2^31 correspondences");
+  if (total && (!feature1 || !feature2)) return bad_argument("uncalibrated relative poses: missing array");
+  // the CHECKs of the SampleConsensusEstimator constructor (sample_consensus_estimator.h:191-197)
+  if (!(L->failure_probability > 0.0 && L->failure_probability < 1.0))
+    return bad_argument("uncalibrated relative poses: failure_probability must be in (0, 1)");
+  if (!(L->min_inlier_ratio >= 0.0 && L->min_inlier_ratio <= 1.0))
+    return bad_argument("uncalibrated relative poses: min_inlier_ratio must be in [0, 1]");
+  if (L->min_iterations < 0 || L->max_iterations < L->min_iterations)
+    return bad_argument("uncalibrated relative poses: max_iterations < min_iterations, or a negative count");
+  if (L->max_iterations > kLocalizeMaxIterations)
+    return bad_argument("uncalibrated relative poses: max_iterations above 2^20");
+  if (L->chunk_iterations < 0) return bad_argument("uncalibrated relative poses: negative chunk_iterations");
+  if (samples_given && !samples) return bad_argument("uncalibrated relative poses: samples_given without samples");
+  const int K = L->max_iterations;
+  std::vector<int> selected, sel_pair, sel_rank;  // sel_pair: the attempted ones, the device's slots
+  for (int p = 0; p < Npair; ++p) {
+    if (pair_mask && !pair_mask[p]) continue;
+    const int64_t n = pair_offset[p + 1] - pair_offset[p];
+    if (n >= 8) {
+      if (!pair_error_threshold) return bad_argument("uncalibrated relative poses: missing pair_error_threshold");
+      if (!(pair_error_threshold[p] > 0.0))
+        return bad_argument("uncalibrated relative poses: error threshold must be positive");
+      if (samples_given)
+        for (int64_t i = 0; i < K; ++i) {
+          const int32_t* t = samples + 8 * ((int64_t)K * p + i);
+          for (int a = 0; a < 8; ++a) {
+            bool bad = t[a] < 0 || t[a] >= n;
+            for (int b = 0; b < a; ++b) bad = bad || t[a] == t[b];
+            if (bad) return bad_argument("uncalibrated relative poses: a sample with a repeated or out-of-range index");
+          }
+        }
+      sel_pair.push_back(p);
+      sel_rank.push_back((int)selected.size());
+    }
+    selected.push_back(p);
+  }
+  const int num_selected = (int)selected.size(), S = (int)sel_pair.size();
+  // nothing below fails on an argument: preset the outputs
+  for (int p = 0; p < Npair; ++p) {
+    const bool sel = !pair_mask || pair_mask[p];
+    if (pair_status) pair_status[p] = (int8_t)(sel ? 1 : -1);
+    if (pair_num_correspondences) pair_num_correspondences[p] = sel ? (int32_t)(pair_offset[p + 1] - pair_offset[p]) : 0;
+    if (pair_num_inliers) pair_num_inliers[p] = 0;
+    if (pair_num_iterations) pair_num_iterations[p] = 0;
+    if (pair_best_iteration) pair_best_iteration[p] = -1;
+    if (pair_confidence) pair_confidence[p] = 0.0;
+    if (fundamental_matrix) std::fill(fundamental_matrix + 9 * (size_t)p, fundamental_matrix + 9 * (size_t)p + 9, 0.0);
+    if (focal_length1) focal_length1[p] = 0.0;
+    if (focal_length2) focal_length2[p] = 0.0;
+    if (rotation) std::fill(rotation + 3 * (size_t)p, rotation + 3 * (size_t)p + 3, 0.0);
+    if (position) std::fill(position + 3 * (size_t)p, position + 3 * (size_t)p + 3, 0.0);
+  }
+  if (corr_inlier && total) memset(corr_inlier, 0, (size_t)total);
+  if (hypothesis_cost) std::fill(hypothesis_cost, hypothesis_cost + (size_t)num_selected * (size_t)K, -1);
+  sum->num_pairs = num_selected;
+  sum->num_too_few_correspondences = num_selected - S;
+  // the attempted pairs' correspondences, pair-major, structure of arrays
+  std::vector<long long> sel_ptr((size_t)S + 1, 0);
+  for (int s = 0; s < S; ++s) sel_ptr[(size_t)s + 1] = sel_ptr[s] + (pair_offset[sel_pair[s] + 1] - pair_offset[sel_pair[s]]);
+  const size_t M = (size_t)sel_ptr[S];
+  std::vector<double> xs(4 * std::max<size_t>(M, 1));
+  double *hx1 = xs.data(), *hy1 = hx1 + M, *hx2 = hy1 + M, *hy2 = hx2 + M;
+  std::vector<double> thresh((size_t)S);
+  std::vector<unsigned> stream_id((size_t)S);
+  for (int s = 0; s < S; ++s) {
+    const int p = sel_pair[s];
+    const int64_t o0 = pair_offset[p];
+    const int n = (int)(pair_offset[p + 1] - o0);
+    for (int m = 0; m < n; ++m) {
+      const size_t o = (size_t)sel_ptr[s] + m;
+      hx1[o] = feature1[2 * (o0 + m)];
+      hy1[o] = feature1[2 * (o0 + m) + 1];
+      hx2[o] = feature2[2 * (o0 + m)];
+      hy2[o] = feature2[2 * (o0 + m) + 1];
+    }
+    thresh[s] = pair_error_threshold[p];
+    stream_id[s] = pair_stream ? pair_stream[p] : (unsigned)p;
+  }
+  // ComputeMaxIterations per pair and inlier count, with the host's log and pow
+  const double log_failure_prob = std::log(L->failure_probability);
+  std::vector<int> bound(M + (size_t)S);
+  std::vector<TwoViewRansacState> state((size_t)S);
+  int initial_bound = K;
+  if (L->min_inlier_ratio > 0.0)
+    initial_bound = std::min(two_view_max_iterations(L->min_inlier_ratio, log_failure_prob, L->min_iterations, K), K);
+  for (int s = 0; s < S; ++s) {
+    const int n = (int)(sel_ptr[(size_t)s + 1] - sel_ptr[s]);
+    int* row = bound.data() + sel_ptr[s] + s;
+    for (int k = 0; k <= n; ++k)
+      row[k] = k < 8 ? K : two_view_max_iterations((double)k / (double)n, log_failure_prob, L->min_iterations, K);
+    TwoViewRansacState& st = state[s];
+    memset(&st, 0, sizeof(st));
+    st.best_cost = INT32_MAX;
+    st.best_iteration = -1;
+    st.max_iterations = initial_bound;
+    st.done = initial_bound <= 0;
+  }
+  // the engine's choice of chunk: the common case -- the run stops at min_iterations -- is a single chunk
+  int chunk = L->chunk_iterations ? L->chunk_iterations : std::max(L->min_iterations, 64);
+  chunk = std::max(1, std::min(chunk, std::max(K, 1)));
+  const int max_chunks = (K + chunk - 1) / chunk;
+  return one_shot_batch(L->device, "uncalibrated relative poses: no such device", S, t0, sum, [&](OneShot* s) -> int {
+    const hipStream_t stream = s->stream;
+    TwoViewRansacBatch B;
+    memset(&B, 0, sizeof(B));
+    double *d_xs, *d_thresh, *d_model_out;
+    long long* d_sel_ptr;
+    unsigned* d_stream_id;
+    int *d_sel_pair, *d_bound, *d_active, *d_samples = nullptr, *d_num_inliers;
+    unsigned char* d_slot_inlier;
+    signed char* d_status;
+    TMI_HIP(s->upload(&d_xs, (const double*)xs.data(), xs.size()));
+    TMI_HIP(s->upload(&d_sel_pair, (const int*)sel_pair.data(), sel_pair.size()));
+    TMI_HIP(s->upload(&d_stream_id, (const unsigned*)stream_id.data(), stream_id.size()));
+    TMI_HIP(s->upload(&d_sel_ptr, (const long long*)sel_ptr.data(), sel_ptr.size()));
+    TMI_HIP(s->upload(&d_thresh, (const double*)thresh.data(), thresh.size()));
+    TMI_HIP(s->upload(&d_bound, (const int*)bound.data(), bound.size()));
+    TMI_HIP(s->upload(&B.state, (const TwoViewRansacState*)state.data(), state.size()));
+    if (samples_given) TMI_HIP(s->upload(&d_samples, (const int*)samples, (size_t)8 * K * Npair));
+    TMI_HIP(s->alloc(&d_active, (size_t)S));
+    TMI_HIP(s->alloc(&B.models, (size_t)S * chunk * kTwoViewModel));
+    TMI_HIP(s->alloc(&B.has_model, (size_t)S * chunk));
+    TMI_HIP(s->alloc(&B.cost, (size_t)S * chunk));
+    TMI_HIP(s->alloc(&d_slot_inlier, M));
+    TMI_HIP(s->alloc(&d_num_inliers, (size_t)S));
+    TMI_HIP(s->alloc(&d_status, (size_t)S));
+    TMI_HIP(s->alloc(&d_model_out, (size_t)17 * S));
+    if (hypothesis_cost) {
+      TMI_HIP(s->alloc(&B.hypothesis_cost, (size_t)S * K));
+      TMI_HIP(hipMemsetAsync(B.hypothesis_cost, 0xff, std::max<size_t>((size_t)S * K, 1) * sizeof(int), stream));
+    }
+    B.num_selected = S;
+    B.max_iterations = K;
+    B.chunk = chunk;
+    B.seed = L->seed;
+    B.sel_pair = d_sel_pair;
+    B.sel_stream = d_stream_id;
+    B.sel_ptr = d_sel_ptr;
+    B.threshold = d_thresh;
+    B.samples = d_samples;
+    B.bound_table = d_bound;
+    B.x1 = d_xs;
+    B.y1 = d_xs + M;
+    B.x2 = d_xs + 2 * M;
+    B.y2 = d_xs + 3 * M;
+    B.active = d_active;
+    StreamTimer timer(stream);
+    TMI_HIP(timer.status);
+    TMI_HIP(timer.mark());
+    // the chunk loop: bounded by ceil(max_iterations / chunk) whatever the device reports
+    std::vector<int> active;
+    int chunks_run = 0;
+    for (int ch = 0; ch < max_chunks; ++ch) {
+      active.clear();
+      for (int v = 0; v < S; ++v)
+        if (!state[v].done) active.push_back(v);
+      if (active.empty()) break;
+      TMI_HIP(hipMemcpyAsync(d_active, active.data(), active.size() * sizeof(int), hipMemcpyHostToDevice, stream));
+      B.num_active = (int)active.size();
+      B.chunk_start = ch * chunk;
+      const long long items = (long long)B.num_active * chunk;
+      StreamTimer phase(stream, 4);
+      TMI_HIP(phase.status);
+      TMI_HIP(phase.mark());
+      hipLaunchKernelGGL(two_view_hypothesis_kernel, dim3((unsigned)((items + 63) / 64)), dim3(64), 0, stream, B);
+      TMI_HIP(phase.mark());
+      hipLaunchKernelGGL(two_view_score_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, stream, B);
+      TMI_HIP(phase.mark());
+      hipLaunchKernelGGL(two_view_replay_kernel, dim3((unsigned)((B.num_active + 63) / 64)), dim3(64), 0, stream, B);
+      TMI_HIP(phase.mark());
+      TMI_HIP(hipGetLastError());
+      TMI_HIP(hipMemcpyAsync(state.data(), B.state, state.size() * sizeof(TwoViewRansacState), hipMemcpyDeviceToHost,
+                             stream));
+      TMI_HIP(hipStreamSynchronize(stream));  // (also: `active` is free to change)
+      sum->hypothesis_seconds += phase.seconds(0, 1);
+      sum->score_seconds += phase.seconds(1, 2);
+      sum->replay_seconds += phase.seconds(2, 3);
+      ++chunks_run;
+    }
+    hipLaunchKernelGGL(two_view_final_kernel, dim3(S), dim3(64), 0, stream, B, d_slot_inlier, d_num_inliers, d_status,
+                       d_model_out);
+    TMI_HIP(timer.mark());
+    TMI_HIP(hipGetLastError());
+    std::vector<signed char> status_h((size_t)S);
+    std::vector<int> inliers_h((size_t)S);
+    std::vector<double> model_h((size_t)17 * S);
+    std::vector<unsigned char> slot_inlier_h(corr_inlier ? M : 0);
+    std::vector<int> hyp_h(hypothesis_cost ? (size_t)S * K : 0);
+    TMI_HIP(hipMemcpyAsync(status_h.data(), d_status, (size_t)S, hipMemcpyDeviceToHost, stream));
+    TMI_HIP(hipMemcpyAsync(inliers_h.data(), d_num_inliers, (size_t)S * sizeof(int), hipMemcpyDeviceToHost, stream));
+    TMI_HIP(hipMemcpyAsync(model_h.data(), d_model_out, model_h.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (!slot_inlier_h.empty())
+      TMI_HIP(hipMemcpyAsync(slot_inlier_h.data(), d_slot_inlier, M, hipMemcpyDeviceToHost, stream));
+    if (!hyp_h.empty())
+      TMI_HIP(hipMemcpyAsync(hyp_h.data(), B.hypothesis_cost, hyp_h.size() * sizeof(int), hipMemcpyDeviceToHost, stream));
+    TMI_HIP(hipStreamSynchronize(stream));
+    sum->kernel_seconds = timer.seconds();
+    sum->num_chunks = chunks_run;
+    for (int v = 0; v < S; ++v) {
+      const int p = sel_pair[v];
+      const int n = (int)(sel_ptr[(size_t)v + 1] - sel_ptr[v]);
+      const int code = status_h[v];
+      const TwoViewRansacState& st = state[v];
+      const double* mo = model_h.data() + 17 * (size_t)v;
+      if (code == 0) sum->num_estimated++; else sum->num_no_model++;
+      sum->total_iterations += st.num_iterations;
+      sum->total_scores += (int64_t)st.num_iterations * n;
+      if (pair_status) pair_status[p] = (int8_t)code;
+      if (pair_num_inliers) pair_num_inliers[p] = inliers_h[v];
+      if (pair_num_iterations) pair_num_iterations[p] = st.num_iterations;
+      if (pair_best_iteration) pair_best_iteration[p] = st.best_iteration;
+      if (pair_confidence) {
+        const double ratio = (double)inliers_h[v] / (double)n;  // sample_consensus_estimator.h:336-340
+        pair_confidence[p] = 1.0 - std::pow(1.0 - std::pow(ratio, 8.0), (double)st.num_iterations);
+      }
+      if (fundamental_matrix) std::copy(mo, mo + 9, fundamental_matrix + 9 * (size_t)p);
+      if (focal_length1) focal_length1[p] = mo[9];
+      if (focal_length2) focal_length2[p] = mo[10];
+      if (rotation) std::copy(mo + 11, mo + 14, rotation + 3 * (size_t)p);
+      if (position) std::copy(mo + 14, mo + 17, position + 3 * (size_t)p);
+      if (corr_inlier)
+        std::copy(slot_inlier_h.begin() + (size_t)sel_ptr[v], slot_inlier_h.begin() + (size_t)sel_ptr[(size_t)v + 1],
+                  corr_inlier + pair_offset[p]);
+      if (hypothesis_cost)
+        std::copy(hyp_h.begin() + (size_t)v * K, hyp_h.begin() + ((size_t)v + 1) * K,
+                  hypothesis_cost + (size_t)sel_rank[v] * K);
+    }
+    return TMI_BA_OK;
+  });
+}
+}  // extern "C"

@@ -827,3 +827,69 @@ def make_matching_batch(num_images: int, num_descriptors, dim: int, seed: int, *
             dups.append((m, dst, src))
     desc = np.concatenate(parts, 0) if parts else np.zeros((0, dim), np.float32)
     return begin, np.ascontiguousarray(desc, dtype=np.float32), {"duplicate_rows": dups, "tie_rows": ties}
+
+
+def make_uncalibrated_pair_batch(num_pairs: int, num_correspondences, seed: int, *, inlier_ratio=1.0, pixel_noise=0.5,
+                                 focal_range=(800.0, 1600.0), image_half_size=(512.0, 384.0), parallel_axes=()):
+    """View pairs for tmi_ba_estimate_uncalibrated_relative_poses: two pinhole views with DIFFERENT focal lengths drawn
+    from focal_range and NON-PARALLEL optical axes that do not meet (view 2 is turned about x and y and moved along all
+    three axes; otherwise the focal lengths are not recoverable from F), scene points in front of both views and inside
+    both images, CENTRED pixels (principal point (0, 0)) with Gaussian pixel_noise, and outliers (a share
+    1 - inlier_ratio of every pair, exactly round(...) of them) uniform in the two images.  num_correspondences and
+    inlier_ratio: a scalar or one value per pair.  parallel_axes: pair indices whose view 2 is NOT turned (the degenerate configuration).
+    Returns a dict: pair_offset [P + 1] int64, feature1 / feature2 [N, 2], is_inlier [N] bool, focal_length1 /
+    focal_length2 [P], rotation [P, 3] (angle-axis of view 2), position [P, 3] (unit norm), fundamental_matrix
+    [P, 3, 3] (x2^T F x1 = 0, unit Frobenius norm), points [N, 3] (in view 1's frame)."""
+    rng = np.random.default_rng(seed)
+    n = np.broadcast_to(np.asarray(num_correspondences, dtype=np.int64), (int(num_pairs),)).copy()
+    ratio = np.broadcast_to(np.asarray(inlier_ratio, dtype=np.float64), (int(num_pairs),))
+    ptr = np.concatenate([[0], np.cumsum(n)]).astype(np.int64)
+    N = int(ptr[-1])
+    f1 = np.zeros((N, 2))
+    f2 = np.zeros((N, 2))
+    X = np.zeros((N, 3))
+    inl = np.zeros(N, dtype=bool)
+    fl1 = rng.uniform(focal_range[0], focal_range[1], num_pairs)
+    fl2 = rng.uniform(focal_range[0], focal_range[1], num_pairs)
+    rot = np.zeros((num_pairs, 3))
+    pos = np.zeros((num_pairs, 3))
+    Fm = np.zeros((num_pairs, 3, 3))
+    hw, hh = image_half_size
+    for p in range(int(num_pairs)):
+        sign = rng.choice([-1.0, 1.0], 2)
+        aa = np.array([sign[0] * rng.uniform(0.08, 0.2), -rng.uniform(0.15, 0.35), rng.uniform(-0.1, 0.1)])
+        if p in parallel_axes:
+            aa[:] = 0.0
+        c = np.array([rng.uniform(0.8, 1.4), sign[1] * rng.uniform(0.3, 0.6), rng.uniform(-0.3, 0.3)])
+        R = Rotation.from_rotvec(aa).as_matrix()
+        rot[p] = aa
+        pos[p] = c / np.linalg.norm(c)
+        tx = np.array([[0, -c[2], c[1]], [c[2], 0, -c[0]], [-c[1], c[0], 0]])
+        E = R @ tx.T  # x2^T E x1 = 0 for x2 ~ R (X - c): E = [t]_x R with t = -R c, i.e. R [c]_x^T
+        Fp = np.diag([1 / fl2[p], 1 / fl2[p], 1.0]) @ E @ np.diag([1 / fl1[p], 1 / fl1[p], 1.0])
+        Fm[p] = Fp / np.linalg.norm(Fp)
+        k = int(n[p])
+        got = 0
+        a, b = int(ptr[p]), int(ptr[p + 1])
+        while got < k:
+            m = 4 * (k - got) + 16
+            depth = rng.uniform(4.0, 9.0, m)
+            Y = np.stack([rng.uniform(-hw, hw, m) / fl1[p] * depth, rng.uniform(-hh, hh, m) / fl1[p] * depth, depth], 1)
+            q = (Y - c) @ R.T
+            u2 = fl2[p] * q[:, :2] / q[:, 2:3]
+            ok = (q[:, 2] > 1.0) & (np.abs(u2[:, 0]) < hw) & (np.abs(u2[:, 1]) < hh)
+            take = np.nonzero(ok)[0][:k - got]
+            X[a + got:a + got + take.size] = Y[take]
+            f1[a + got:a + got + take.size] = fl1[p] * Y[take, :2] / Y[take, 2:3]
+            f2[a + got:a + got + take.size] = u2[take]
+            got += take.size
+        f1[a:b] += pixel_noise * rng.normal(size=(k, 2))
+        f2[a:b] += pixel_noise * rng.normal(size=(k, 2))
+        n_out = int(round((1.0 - float(ratio[p])) * k))
+        out = rng.permutation(k)[:n_out]
+        inl[a:b] = True
+        inl[a + out] = False
+        f1[a + out] = rng.uniform([-hw, -hh], [hw, hh], (n_out, 2))
+        f2[a + out] = rng.uniform([-hw, -hh], [hw, hh], (n_out, 2))
+    return dict(pair_offset=ptr, feature1=f1, feature2=f2, is_inlier=inl, focal_length1=fl1, focal_length2=fl2,
+                rotation=rot, position=pos, fundamental_matrix=Fm, points=X)
