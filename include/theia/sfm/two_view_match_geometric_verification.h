@@ -5,9 +5,9 @@
 // reprojection error, update the TwoViewInfo.  Implemented on the C ABI (tmi_ba_verify_two_views, where the steps are
 // listed line by line); the batched form runs many pairs in ONE call, one wavefront per pair.
 //
-// The RANSAC of EstimateTwoViewInfo (:128-134) that runs before this step exists for the UNCALIBRATED branch
-// (theia/sfm/estimate_twoview_info.h on tmi_ba_estimate_uncalibrated_relative_poses); its
-// calibrated (five-point) branch does not.  Out of scope: guided matching (:157-168) and the
+// The RANSAC of EstimateTwoViewInfo (:128-134) that runs before this step exists for both branches
+// (theia/sfm/estimate_twoview_info.h on tmi_ba_estimate_uncalibrated_relative_poses and, with inlier-count scoring,
+// tmi_ba_estimate_calibrated_relative_poses; DESIGN.md sections 8.10 and 8.11).  Out of scope: guided matching (:157-168) and the
 // homography inlier count (:124).  The caller hands over what VerifyMatches has once those ran: the two cameras
 // (SetupCameras :56-68) and the pair's correspondences.
 #ifndef THEIA_MI355_TWO_VIEW_MATCH_GEOMETRIC_VERIFICATION_H_

@@ -739,9 +739,10 @@ int32_t tmi_ba_adjust_two_views(tmi_ba_two_view_batch* batch, int32_t point_dof,
  * indices.  That mode is NOT a path of the reference (which calls this function only to adjust): it is an extension
  * for staging the steps and for tests.
  * One wavefront per pair in three launches (triangulate, solve, accept); a pair's result does not depend on the rest
- * of the batch.  The RANSAC of EstimateTwoViewInfo (:128-134) that precedes this step is provided for the UNCALIBRATED
- * branch (tmi_ba_estimate_uncalibrated_relative_poses below), not for the calibrated (five-point) one.  Out of scope
- * (DESIGN 9): guided matching (:157-168) and the homography inlier count (:124). */
+ * of the batch.  The RANSAC of EstimateTwoViewInfo (:128-134) that precedes this step is provided for both branches:
+ * tmi_ba_estimate_uncalibrated_relative_poses (eight-point) and tmi_ba_estimate_calibrated_relative_poses (five-point,
+ * inlier-count scoring; MLESAC scoring is not provided) below.  Out of scope: guided matching (:157-168)
+ * and the homography inlier count (:124). */
 typedef struct tmi_ba_two_view_verification_options {
   int32_t min_num_inlier_matches;               /* 30   (two_view_match_geometric_verification.h:59-92) */
   double triangulation_max_reprojection_error;  /* 15.0 */
@@ -1259,8 +1260,9 @@ int32_t tmi_ba_match_features(const tmi_ba_match_options* options, int32_t num_i
  * reference: the UNCALIBRATED branch of EstimateTwoViewInfo (estimate_twoview_info.cc:202-248), which the reference's
  * application runs for every view without an EXIF focal length: EstimateUncalibratedRelativePose with
  * RansacType::RANSAC (estimators/estimate_uncalibrated_relative_pose.cc:67-172) and
- * SampleConsensusEstimator::Estimate with InlierSupport (solvers/sample_consensus_estimator.h:246-344).  Not provided:
- * the calibrated (five-point) branch, PROSAC, LMED and exhaustive sampling, use_mle, use_Tdd_test, guided matching.
+ * SampleConsensusEstimator::Estimate with InlierSupport (solvers/sample_consensus_estimator.h:246-344).  The calibrated
+ * (five-point) branch is tmi_ba_estimate_calibrated_relative_poses further down.  Not provided: PROSAC, LMED and
+ * exhaustive sampling, use_mle, use_Tdd_test, guided matching.
  * A one-shot call without a tmi_ba_problem.  Pair p owns the correspondences pair_offset[p] .. pair_offset[p + 1] - 1,
  * numbered 0..n-1; feature1 / feature2 [2 per correspondence] are CENTRED pixels: the principal point removed and NO
  * focal division, as NormalizeFeatures leaves them when a focal prior is missing (estimate_twoview_info.cc:82-85).
@@ -1362,6 +1364,70 @@ int32_t tmi_ba_estimate_uncalibrated_relative_poses(
     int32_t* pair_num_correspondences, int32_t* pair_num_inliers, int32_t* pair_num_iterations,
     int32_t* pair_best_iteration, double* pair_confidence, double* fundamental_matrix, double* focal_length1,
     double* focal_length2, double* rotation, double* position, uint8_t* corr_inlier, int32_t* hypothesis_cost,
+    tmi_ba_two_view_ransac_summary* summary);
+
+/* ---- batched EstimateRelativePose: five-point RANSAC for many calibrated view pairs ----------------------
+ * reference: the CALIBRATED branch of EstimateTwoViewInfo (estimate_twoview_info.cc:127-200), taken whenever both views
+ * carry a focal-length prior: EstimateRelativePose with RansacType::RANSAC (estimators/estimate_relative_pose.cc:59-144)
+ * over FivePointRelativePose (pose/five_point_relative_pose.cc:212-299, the MINIMAL path) and
+ * SampleConsensusEstimator::Estimate with InlierSupport.  Not provided: PROSAC, LMED and exhaustive sampling, use_mle
+ * (MLESAC scoring), use_Tdd_test, the non-minimal (SVD) path of the solver.
+ * A one-shot call shaped like tmi_ba_estimate_uncalibrated_relative_poses, whose options, summary, pair_offset,
+ * pair_mask, pair_stream, samples / samples_given, integer outputs and corr_inlier it shares.  What differs:
+ * feature1 / feature2 are NORMALISED coordinates, the principal point removed and the result divided by the focal
+ * length, as NormalizeFeatures leaves them when both priors are set (estimate_twoview_info.cc:67-100);
+ * pair_error_threshold is RansacParameters::error_thresh in those units (:160-162), computed by the caller; the model
+ * is essential_matrix [9] (column-major, as the reference stores it; unit Frobenius norm), rotation [3] (angle-axis),
+ * position [3]; pair_best_solution says which of a sample's models won; there are no focal-length outputs.  Per
+ * selected pair, in this order:
+ *   1. n < 5                                                                                       -> status 1.
+ *   2. The sample of iteration i: step 2 of the uncalibrated call with 8 replaced by 5 (samples[5 (max_iterations p +
+ *      i) + k]; word c = 5 (q 2^32 + i) + k; five swaps).
+ *   3. FivePointRelativePose on the five points:
+ *      a. The 5x9 rows (x2 x1, y2 x1, x1, x2 y1, y2 y1, y1, x2, y2, 1) (:227-236).  The kernel by elimination with FULL
+ *         pivoting under the eight-point call's rules: the pivot is the entry of largest magnitude, strict >, ties to the
+ *         lowest (row, column); the rank counts the pivots with |pivot| > 5 DBL_EPSILON |largest pivot|; a rank other
+ *         than 5 gives NO MODEL.  The basis is FullPivLU::kernel()'s: one vector per free permuted column, that column
+ *         1, the other free columns 0, back-substitution with each sum in ascending column order, NOT normalised.
+ *      b. The 10x20 constraint matrix exactly as :65-206 expand it, their association order kept, no FMA contraction.
+ *      c. C[:, :10] X = C[:, 10:] by elimination with full pivoting of the augmented matrix under the same rules, then
+ *         back-substitution (ascending column order).  DEVIATION: a rank below 10 at 10 DBL_EPSILON gives NO MODEL (the
+ *         reference solves whatever the rank).
+ *      d. The action matrix (:271-279) and its REAL eigenvalues by one fixed algorithm: reduction to Hessenberg form
+ *         by stabilised elementary similarity transformations (EISPACK elmhes: the pivot of column m - 1 is the entry
+ *         of largest magnitude among rows m.., strict >, the first among equals), no balancing, then the Francis
+ *         double-shift QR iteration to the real Schur form (EISPACK hqr: a subdiagonal entry e is negligible when
+ *         |e| + s == s for s the sum of its two diagonal neighbours' magnitudes, or the matrix' norm where that is 0;
+ *         exceptional shifts at sweeps 10 and 20).  A block that has not split after 30 sweeps gives NO MODEL; every
+ *         loop has a fixed bound.  A root is real exactly where the Schur form leaves a 1x1 block, or a 2x2 block whose
+ *         discriminant is >= 0 (the reference's imag() != 0 test).
+ *      e. Per real eigenvalue, in ASCENDING order (equal ones in the order of their diagonal position; the reference's
+ *         order is whatever Eigen returns, and matters only between models of equal cost): the null vector of
+ *         A - lambda I by NINE steps of the same elimination, the tenth permuted entry set to 1.  DEVIATION: the rank
+ *         test (10 DBL_EPSILON) covers the nine pivots; the tenth is the root's own rounding residual and is taken as
+ *         zero.  Rank < 9 gives no model for that root.  The last four entries are the coordinates over the kernel
+ *         basis; the 9-vector null_space x tail (:293-294) is scaled to unit norm with its largest-magnitude entry
+ *         (the first among equals) positive.
+ *   4. GetBestPoseFromEssentialMatrix on the five sampled correspondences: step 5 of the uncalibrated call (the same 3x3
+ *      Jacobi SVD, candidates, cheirality vote, first of the largest) without focal division.  A model is kept only with
+ *      at least 4 points in front (estimate_relative_pose.cc:94-104).  A sample yields 0 to 10 models in 10 slots, in
+ *      the order of 3e.
+ *   5. The cost of a model (:111-121): the correspondences for which the cheirality test fails, or the
+ *      SquaredSampsonDistance under E is not below the threshold, or that distance is NaN.
+ *   6. The replay is step 5 of tmi_ba_localize_views (many models per sample, ascending (iteration, slot), strict <)
+ *      with a sample size of 5 and 10 slots; THE RESULT DOES NOT DEPEND ON chunk_iterations.
+ *   7. Final: the inlier mask of the best model, confidence = 1 - (1 - (num_inliers / n)^5)^num_iterations (host); no
+ *      model in any iteration -> status 2.
+ * hypothesis_cost [num_selected * max_iterations * 10] (optional, for tests): -1 for an empty slot or not replayed.
+ * Steps 3 to 5 use + - * / sqrt and fabs only and are never contracted into FMA.  The argument errors and their order
+ * relative to the device check are those of the uncalibrated call, with 5 in place of 8. */
+int32_t tmi_ba_estimate_calibrated_relative_poses(
+    const tmi_ba_two_view_ransac_options* options, int32_t num_pairs, const int64_t* pair_offset,
+    const double* feature1, const double* feature2, const double* pair_error_threshold, const uint8_t* pair_mask,
+    const uint32_t* pair_stream, const int32_t* samples, int32_t samples_given, int8_t* pair_status,
+    int32_t* pair_num_correspondences, int32_t* pair_num_inliers, int32_t* pair_num_iterations,
+    int32_t* pair_best_iteration, int32_t* pair_best_solution, double* pair_confidence, double* essential_matrix,
+    double* rotation, double* position, uint8_t* corr_inlier, int32_t* hypothesis_cost,
     tmi_ba_two_view_ransac_summary* summary);
 
 /* Test hook: FNV-1a checksums of the static structure arrays resident in HBM -- built in HBM by

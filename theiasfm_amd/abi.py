@@ -552,6 +552,9 @@ def two_view_ransac_options(**overrides) -> CTwoViewRansacOptions:
     return o
 
 
+CALIBRATED_SLOTS = 10  # models per sample of tmi_ba_estimate_calibrated_relative_poses (the stride of its hypothesis_cost)
+
+
 class CTwoViewRansacSummary(C.Structure):
     """tmi_ba_two_view_ransac_summary."""
     _fields_ = [

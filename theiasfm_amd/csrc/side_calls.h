@@ -2796,64 +2796,72 @@ void tmi_ba_two_view_ransac_options_init(tmi_ba_two_view_ransac_options* o) {
 }
 }  // extern "C"
 namespace {
-// SampleConsensusEstimator::ComputeMaxIterations (sample_consensus_estimator.h:215-243) for a sample of eight, without
-// the T(d,d) test.
-int two_view_max_iterations(double inlier_ratio, double log_failure_prob, int min_iterations, int max_iterations) {
+// SampleConsensusEstimator::ComputeMaxIterations (sample_consensus_estimator.h:215-243) for a sample of sample_size,
+// without the T(d,d) test.
+int two_view_max_iterations(double inlier_ratio, double log_failure_prob, int min_iterations, int max_iterations,
+                            int sample_size) {
   if (inlier_ratio == 1.0) return min_iterations;
-  const double log_prob = std::log(1.0 - std::pow(inlier_ratio, 8.0)) - std::numeric_limits<double>::epsilon();
+  const double log_prob =
+      std::log(1.0 - std::pow(inlier_ratio, (double)sample_size)) - std::numeric_limits<double>::epsilon();
   const double num_iterations = log_failure_prob / log_prob;
   return (int)std::max((double)min_iterations, std::min(num_iterations, (double)max_iterations));
 }
-}  // namespace
-extern "C" {
 
-int32_t tmi_ba_estimate_uncalibrated_relative_poses(
+// The host loop the two RANSAC calls over view pairs share.  Calibrated == false: the eight-point call (a sample of 8,
+// one model per sample, model_a = the fundamental matrix, focal lengths out).  Calibrated == true: the five-point call
+// (a sample of 5, kCalibSlots models per sample, model_a = the essential matrix, pair_best_solution out).
+template <bool Calibrated>
+int32_t two_view_ransac_call(
     const tmi_ba_two_view_ransac_options* L, int32_t num_pairs, const int64_t* pair_offset, const double* feature1,
     const double* feature2, const double* pair_error_threshold, const uint8_t* pair_mask, const uint32_t* pair_stream,
     const int32_t* samples, int32_t samples_given, int8_t* pair_status, int32_t* pair_num_correspondences,
-    int32_t* pair_num_inliers, int32_t* pair_num_iterations, int32_t* pair_best_iteration, double* pair_confidence,
-    double* fundamental_matrix, double* focal_length1, double* focal_length2, double* rotation, double* position,
-    uint8_t* corr_inlier, int32_t* hypothesis_cost, tmi_ba_two_view_ransac_summary* sum) {
-  if (!L || !sum) return bad_argument("uncalibrated relative poses: null options or summary");
+    int32_t* pair_num_inliers, int32_t* pair_num_iterations, int32_t* pair_best_iteration, int32_t* pair_best_solution,
+    double* pair_confidence, double* fundamental_matrix, double* focal_length1, double* focal_length2, double* rotation,
+    double* position, uint8_t* corr_inlier, int32_t* hypothesis_cost, tmi_ba_two_view_ransac_summary* sum) {
+  constexpr int kSample = Calibrated ? 5 : 8;
+  constexpr int kSlots = Calibrated ? kCalibSlots : 1;
+  const std::string what = Calibrated ? "calibrated relative poses" : "uncalibrated relative poses";
+  auto bad = [&](const char* why) { return bad_argument((what + ": " + why).c_str()); };
+  if (!L || !sum) return bad("null options or summary");
   memset(sum, 0, sizeof(*sum));
   const double t0 = now_s();
   // argument errors before the device is looked for
   const int Npair = num_pairs;
-  if (Npair < 0) return bad_argument("uncalibrated relative poses: negative size");
-  if (!pair_offset) return bad_argument("uncalibrated relative poses: missing array");
-  if (pair_offset[0] != 0) return bad_argument("uncalibrated relative poses: pair_offset must start at 0");
+  if (Npair < 0) return bad("negative size");
+  if (!pair_offset) return bad("missing array");
+  if (pair_offset[0] != 0) return bad("pair_offset must start at 0");
   for (int p = 0; p < Npair; ++p)
-    if (pair_offset[p + 1] < pair_offset[p]) return bad_argument("uncalibrated relative poses: pair_offset decreases");
+    if (pair_offset[p + 1] < pair_offset[p]) return bad("pair_offset decreases");
   const int64_t total = pair_offset[Npair];
-  if (total >= (int64_t)0x7fffffffLL) return bad_argument("uncalibrated relative poses: more than 2^31 correspondences");
-  if (total && (!feature1 || !feature2)) return bad_argument("uncalibrated relative poses: missing array");
+  if (total >= (int64_t)0x7fffffffLL) return bad("more than 2^31 correspondences");
+  if (total && (!feature1 || !feature2)) return bad("missing array");
   // the CHECKs of the SampleConsensusEstimator constructor (sample_consensus_estimator.h:191-197)
   if (!(L->failure_probability > 0.0 && L->failure_probability < 1.0))
-    return bad_argument("uncalibrated relative poses: failure_probability must be in (0, 1)");
+    return bad("failure_probability must be in (0, 1)");
   if (!(L->min_inlier_ratio >= 0.0 && L->min_inlier_ratio <= 1.0))
-    return bad_argument("uncalibrated relative poses: min_inlier_ratio must be in [0, 1]");
+    return bad("min_inlier_ratio must be in [0, 1]");
   if (L->min_iterations < 0 || L->max_iterations < L->min_iterations)
-    return bad_argument("uncalibrated relative poses: max_iterations < min_iterations, or a negative count");
+    return bad("max_iterations < min_iterations, or a negative count");
   if (L->max_iterations > kLocalizeMaxIterations)
-    return bad_argument("uncalibrated relative poses: max_iterations above 2^20");
-  if (L->chunk_iterations < 0) return bad_argument("uncalibrated relative poses: negative chunk_iterations");
-  if (samples_given && !samples) return bad_argument("uncalibrated relative poses: samples_given without samples");
+    return bad("max_iterations above 2^20");
+  if (L->chunk_iterations < 0) return bad("negative chunk_iterations");
+  if (samples_given && !samples) return bad("samples_given without samples");
   const int K = L->max_iterations;
   std::vector<int> selected, sel_pair, sel_rank;  // sel_pair: the attempted ones, the device's slots
   for (int p = 0; p < Npair; ++p) {
     if (pair_mask && !pair_mask[p]) continue;
     const int64_t n = pair_offset[p + 1] - pair_offset[p];
-    if (n >= 8) {
-      if (!pair_error_threshold) return bad_argument("uncalibrated relative poses: missing pair_error_threshold");
+    if (n >= kSample) {
+      if (!pair_error_threshold) return bad("missing pair_error_threshold");
       if (!(pair_error_threshold[p] > 0.0))
-        return bad_argument("uncalibrated relative poses: error threshold must be positive");
+        return bad("error threshold must be positive");
       if (samples_given)
         for (int64_t i = 0; i < K; ++i) {
-          const int32_t* t = samples + 8 * ((int64_t)K * p + i);
-          for (int a = 0; a < 8; ++a) {
-            bool bad = t[a] < 0 || t[a] >= n;
-            for (int b = 0; b < a; ++b) bad = bad || t[a] == t[b];
-            if (bad) return bad_argument("uncalibrated relative poses: a sample with a repeated or out-of-range index");
+          const int32_t* t = samples + kSample * ((int64_t)K * p + i);
+          for (int a = 0; a < kSample; ++a) {
+            bool wrong = t[a] < 0 || t[a] >= n;
+            for (int b = 0; b < a; ++b) wrong = wrong || t[a] == t[b];
+            if (wrong) return bad("a sample with a repeated or out-of-range index");
           }
         }
       sel_pair.push_back(p);
@@ -2870,6 +2878,7 @@ int32_t tmi_ba_estimate_uncalibrated_relative_poses(
     if (pair_num_inliers) pair_num_inliers[p] = 0;
     if (pair_num_iterations) pair_num_iterations[p] = 0;
     if (pair_best_iteration) pair_best_iteration[p] = -1;
+    if (pair_best_solution) pair_best_solution[p] = -1;
     if (pair_confidence) pair_confidence[p] = 0.0;
     if (fundamental_matrix) std::fill(fundamental_matrix + 9 * (size_t)p, fundamental_matrix + 9 * (size_t)p + 9, 0.0);
     if (focal_length1) focal_length1[p] = 0.0;
@@ -2878,7 +2887,7 @@ int32_t tmi_ba_estimate_uncalibrated_relative_poses(
     if (position) std::fill(position + 3 * (size_t)p, position + 3 * (size_t)p + 3, 0.0);
   }
   if (corr_inlier && total) memset(corr_inlier, 0, (size_t)total);
-  if (hypothesis_cost) std::fill(hypothesis_cost, hypothesis_cost + (size_t)num_selected * (size_t)K, -1);
+  if (hypothesis_cost) std::fill(hypothesis_cost, hypothesis_cost + (size_t)num_selected * (size_t)K * kSlots, -1);
   sum->num_pairs = num_selected;
   sum->num_too_few_correspondences = num_selected - S;
   // the attempted pairs' correspondences, pair-major, structure of arrays
@@ -2909,16 +2918,19 @@ int32_t tmi_ba_estimate_uncalibrated_relative_poses(
   std::vector<TwoViewRansacState> state((size_t)S);
   int initial_bound = K;
   if (L->min_inlier_ratio > 0.0)
-    initial_bound = std::min(two_view_max_iterations(L->min_inlier_ratio, log_failure_prob, L->min_iterations, K), K);
+    initial_bound =
+        std::min(two_view_max_iterations(L->min_inlier_ratio, log_failure_prob, L->min_iterations, K, kSample), K);
   for (int s = 0; s < S; ++s) {
     const int n = (int)(sel_ptr[(size_t)s + 1] - sel_ptr[s]);
     int* row = bound.data() + sel_ptr[s] + s;
     for (int k = 0; k <= n; ++k)
-      row[k] = k < 8 ? K : two_view_max_iterations((double)k / (double)n, log_failure_prob, L->min_iterations, K);
+      row[k] = k < kSample ? K
+                           : two_view_max_iterations((double)k / (double)n, log_failure_prob, L->min_iterations, K, kSample);
     TwoViewRansacState& st = state[s];
     memset(&st, 0, sizeof(st));
     st.best_cost = INT32_MAX;
     st.best_iteration = -1;
+    st.best_solution = -1;
     st.max_iterations = initial_bound;
     st.done = initial_bound <= 0;
   }
@@ -2926,7 +2938,8 @@ int32_t tmi_ba_estimate_uncalibrated_relative_poses(
   int chunk = L->chunk_iterations ? L->chunk_iterations : std::max(L->min_iterations, 64);
   chunk = std::max(1, std::min(chunk, std::max(K, 1)));
   const int max_chunks = (K + chunk - 1) / chunk;
-  return one_shot_batch(L->device, "uncalibrated relative poses: no such device", S, t0, sum, [&](OneShot* s) -> int {
+  const std::string no_device = what + ": no such device";
+  return one_shot_batch(L->device, no_device.c_str(), S, t0, sum, [&](OneShot* s) -> int {
     const hipStream_t stream = s->stream;
     TwoViewRansacBatch B;
     memset(&B, 0, sizeof(B));
@@ -2943,18 +2956,18 @@ int32_t tmi_ba_estimate_uncalibrated_relative_poses(
     TMI_HIP(s->upload(&d_thresh, (const double*)thresh.data(), thresh.size()));
     TMI_HIP(s->upload(&d_bound, (const int*)bound.data(), bound.size()));
     TMI_HIP(s->upload(&B.state, (const TwoViewRansacState*)state.data(), state.size()));
-    if (samples_given) TMI_HIP(s->upload(&d_samples, (const int*)samples, (size_t)8 * K * Npair));
+    if (samples_given) TMI_HIP(s->upload(&d_samples, (const int*)samples, (size_t)kSample * K * Npair));
     TMI_HIP(s->alloc(&d_active, (size_t)S));
-    TMI_HIP(s->alloc(&B.models, (size_t)S * chunk * kTwoViewModel));
-    TMI_HIP(s->alloc(&B.has_model, (size_t)S * chunk));
-    TMI_HIP(s->alloc(&B.cost, (size_t)S * chunk));
+    TMI_HIP(s->alloc(&B.models, (size_t)S * chunk * kSlots * kTwoViewModel));
+    TMI_HIP(s->alloc(&B.has_model, (size_t)S * chunk * kSlots));
+    TMI_HIP(s->alloc(&B.cost, (size_t)S * chunk * kSlots));
     TMI_HIP(s->alloc(&d_slot_inlier, M));
     TMI_HIP(s->alloc(&d_num_inliers, (size_t)S));
     TMI_HIP(s->alloc(&d_status, (size_t)S));
     TMI_HIP(s->alloc(&d_model_out, (size_t)17 * S));
     if (hypothesis_cost) {
-      TMI_HIP(s->alloc(&B.hypothesis_cost, (size_t)S * K));
-      TMI_HIP(hipMemsetAsync(B.hypothesis_cost, 0xff, std::max<size_t>((size_t)S * K, 1) * sizeof(int), stream));
+      TMI_HIP(s->alloc(&B.hypothesis_cost, (size_t)S * K * kSlots));
+      TMI_HIP(hipMemsetAsync(B.hypothesis_cost, 0xff, std::max<size_t>((size_t)S * K * kSlots, 1) * sizeof(int), stream));
     }
     B.num_selected = S;
     B.max_iterations = K;
@@ -2989,11 +3002,21 @@ int32_t tmi_ba_estimate_uncalibrated_relative_poses(
       StreamTimer phase(stream, 4);
       TMI_HIP(phase.status);
       TMI_HIP(phase.mark());
-      hipLaunchKernelGGL(two_view_hypothesis_kernel, dim3((unsigned)((items + 63) / 64)), dim3(64), 0, stream, B);
+      if (Calibrated)
+        hipLaunchKernelGGL(calibrated_hypothesis_kernel, dim3((unsigned)((items + kCalibThreads - 1) / kCalibThreads)),
+                           dim3(kCalibThreads), 0, stream, B);
+      else
+        hipLaunchKernelGGL(two_view_hypothesis_kernel, dim3((unsigned)((items + 63) / 64)), dim3(64), 0, stream, B);
       TMI_HIP(phase.mark());
-      hipLaunchKernelGGL(two_view_score_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, stream, B);
+      if (Calibrated)
+        hipLaunchKernelGGL(calibrated_score_kernel, dim3((unsigned)((items * kCalibSlots + 3) / 4)), dim3(256), 0, stream, B);
+      else
+        hipLaunchKernelGGL(two_view_score_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, stream, B);
       TMI_HIP(phase.mark());
-      hipLaunchKernelGGL(two_view_replay_kernel, dim3((unsigned)((B.num_active + 63) / 64)), dim3(64), 0, stream, B);
+      if (Calibrated)
+        hipLaunchKernelGGL(calibrated_replay_kernel, dim3((unsigned)((B.num_active + 63) / 64)), dim3(64), 0, stream, B);
+      else
+        hipLaunchKernelGGL(two_view_replay_kernel, dim3((unsigned)((B.num_active + 63) / 64)), dim3(64), 0, stream, B);
       TMI_HIP(phase.mark());
       TMI_HIP(hipGetLastError());
       TMI_HIP(hipMemcpyAsync(state.data(), B.state, state.size() * sizeof(TwoViewRansacState), hipMemcpyDeviceToHost,
@@ -3012,7 +3035,8 @@ int32_t tmi_ba_estimate_uncalibrated_relative_poses(
     std::vector<int> inliers_h((size_t)S);
     std::vector<double> model_h((size_t)17 * S);
     std::vector<unsigned char> slot_inlier_h(corr_inlier ? M : 0);
-    std::vector<int> hyp_h(hypothesis_cost ? (size_t)S * K : 0);
+    const size_t KS = (size_t)K * kSlots;
+    std::vector<int> hyp_h(hypothesis_cost ? (size_t)S * KS : 0);
     TMI_HIP(hipMemcpyAsync(status_h.data(), d_status, (size_t)S, hipMemcpyDeviceToHost, stream));
     TMI_HIP(hipMemcpyAsync(inliers_h.data(), d_num_inliers, (size_t)S * sizeof(int), hipMemcpyDeviceToHost, stream));
     TMI_HIP(hipMemcpyAsync(model_h.data(), d_model_out, model_h.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
@@ -3036,9 +3060,10 @@ int32_t tmi_ba_estimate_uncalibrated_relative_poses(
       if (pair_num_inliers) pair_num_inliers[p] = inliers_h[v];
       if (pair_num_iterations) pair_num_iterations[p] = st.num_iterations;
       if (pair_best_iteration) pair_best_iteration[p] = st.best_iteration;
+      if (pair_best_solution) pair_best_solution[p] = st.best_solution;
       if (pair_confidence) {
         const double ratio = (double)inliers_h[v] / (double)n;  // sample_consensus_estimator.h:336-340
-        pair_confidence[p] = 1.0 - std::pow(1.0 - std::pow(ratio, 8.0), (double)st.num_iterations);
+        pair_confidence[p] = 1.0 - std::pow(1.0 - std::pow(ratio, (double)kSample), (double)st.num_iterations);
       }
       if (fundamental_matrix) std::copy(mo, mo + 9, fundamental_matrix + 9 * (size_t)p);
       if (focal_length1) focal_length1[p] = mo[9];
@@ -3049,10 +3074,41 @@ int32_t tmi_ba_estimate_uncalibrated_relative_poses(
         std::copy(slot_inlier_h.begin() + (size_t)sel_ptr[v], slot_inlier_h.begin() + (size_t)sel_ptr[(size_t)v + 1],
                   corr_inlier + pair_offset[p]);
       if (hypothesis_cost)
-        std::copy(hyp_h.begin() + (size_t)v * K, hyp_h.begin() + ((size_t)v + 1) * K,
-                  hypothesis_cost + (size_t)sel_rank[v] * K);
+        std::copy(hyp_h.begin() + (size_t)v * KS, hyp_h.begin() + ((size_t)v + 1) * KS,
+                  hypothesis_cost + (size_t)sel_rank[v] * KS);
     }
     return TMI_BA_OK;
   });
+}
+}  // namespace
+extern "C" {
+
+int32_t tmi_ba_estimate_uncalibrated_relative_poses(
+    const tmi_ba_two_view_ransac_options* L, int32_t num_pairs, const int64_t* pair_offset, const double* feature1,
+    const double* feature2, const double* pair_error_threshold, const uint8_t* pair_mask, const uint32_t* pair_stream,
+    const int32_t* samples, int32_t samples_given, int8_t* pair_status, int32_t* pair_num_correspondences,
+    int32_t* pair_num_inliers, int32_t* pair_num_iterations, int32_t* pair_best_iteration, double* pair_confidence,
+    double* fundamental_matrix, double* focal_length1, double* focal_length2, double* rotation, double* position,
+    uint8_t* corr_inlier, int32_t* hypothesis_cost, tmi_ba_two_view_ransac_summary* sum) {
+  return two_view_ransac_call<false>(L, num_pairs, pair_offset, feature1, feature2, pair_error_threshold, pair_mask,
+                                     pair_stream, samples, samples_given, pair_status, pair_num_correspondences,
+                                     pair_num_inliers, pair_num_iterations, pair_best_iteration, nullptr, pair_confidence,
+                                     fundamental_matrix, focal_length1, focal_length2, rotation, position, corr_inlier,
+                                     hypothesis_cost, sum);
+}
+
+// ---- batched EstimateRelativePose: five-point RANSAC (two_view_calibrated_kernels.h) ----
+int32_t tmi_ba_estimate_calibrated_relative_poses(
+    const tmi_ba_two_view_ransac_options* L, int32_t num_pairs, const int64_t* pair_offset, const double* feature1,
+    const double* feature2, const double* pair_error_threshold, const uint8_t* pair_mask, const uint32_t* pair_stream,
+    const int32_t* samples, int32_t samples_given, int8_t* pair_status, int32_t* pair_num_correspondences,
+    int32_t* pair_num_inliers, int32_t* pair_num_iterations, int32_t* pair_best_iteration, int32_t* pair_best_solution,
+    double* pair_confidence, double* essential_matrix, double* rotation, double* position, uint8_t* corr_inlier,
+    int32_t* hypothesis_cost, tmi_ba_two_view_ransac_summary* sum) {
+  return two_view_ransac_call<true>(L, num_pairs, pair_offset, feature1, feature2, pair_error_threshold, pair_mask,
+                                    pair_stream, samples, samples_given, pair_status, pair_num_correspondences,
+                                    pair_num_inliers, pair_num_iterations, pair_best_iteration, pair_best_solution,
+                                    pair_confidence, essential_matrix, nullptr, nullptr, rotation, position, corr_inlier,
+                                    hypothesis_cost, sum);
 }
 }  // extern "C"

@@ -39,7 +39,8 @@ struct TwoViewRansacState {
   int max_iterations;   // the loop bound, only ever lowered
   int num_iterations;   // iterations replayed
   int done;
-  int pad[3];
+  int best_solution;    // -1 (the calibrated call's slot of the best model; unused by the eight-point call)
+  int pad[2];
   double model[kTwoViewModel];
 };
 
@@ -163,7 +164,7 @@ __device__ __forceinline__ void two_view_normalization(const double x[8], const 
       vb[r_] = t_;                                \
     }                                             \
   }
-__device__ __forceinline__ void two_view_jacobi_svd(double a0[3], double a1[3], double a2[3], double v0[3], double v1[3],
+__host__ __device__ __forceinline__ void two_view_jacobi_svd(double a0[3], double a1[3], double a2[3], double v0[3], double v1[3],
                                                     double v2[3]) {
 #pragma clang fp contract(off)
   v0[0] = 1.0; v0[1] = 0.0; v0[2] = 0.0;
@@ -207,7 +208,7 @@ __device__ __forceinline__ void two_view_null_vector(const double r0[3], const d
 
 // The two expressions of IsTriangulatedPointInFrontOfCameras (triangulation.cc:216-232) for the normalised pair
 // (u1, v1), (u2, v2) under rotation R (row-major) and position p; in front when both are > 0.
-__device__ __forceinline__ void two_view_cheirality(const double* __restrict__ R, double px, double py, double pz, double u1,
+__host__ __device__ __forceinline__ void two_view_cheirality(const double* __restrict__ R, double px, double py, double pz, double u1,
                                                     double v1, double u2, double v2, double* e1, double* e2) {
 #pragma clang fp contract(off)
   const double d0 = (R[0] * u2 + R[3] * v2) + R[6];

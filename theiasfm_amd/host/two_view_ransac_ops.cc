@@ -1,13 +1,16 @@
-// Host shim of theia::EstimateUncalibratedRelativePose and of the uncalibrated branch of theia::EstimateTwoViewInfo
-// (reference estimate_uncalibrated_relative_pose.cc:153-170, estimate_twoview_info.cc:202-285) on the C ABI: the pairs'
-// pixels are centred, the squared threshold is computed per pair, RANSAC runs for all pairs in one
-// tmi_ba_estimate_uncalibrated_relative_poses call and the results are written back.
+// Host shim of theia::EstimateUncalibratedRelativePose, theia::EstimateRelativePose and theia::EstimateTwoViewInfo
+// (reference estimate_uncalibrated_relative_pose.cc:153-170, estimate_relative_pose.cc:129-144,
+// estimate_twoview_info.cc:67-285) on the C ABI: the pairs' pixels are centred (and, for a calibrated pair, divided by
+// the focal priors), the squared threshold is computed per pair, RANSAC runs for all pairs of a kind in one
+// tmi_ba_estimate_uncalibrated_relative_poses / tmi_ba_estimate_calibrated_relative_poses call and the results are
+// written back.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <vector>
 
 #include "theia/sfm/estimate_twoview_info.h"
+#include "theia/sfm/estimators/estimate_relative_pose.h"
 #include "theia/sfm/estimators/estimate_uncalibrated_relative_pose.h"
 #include "theia_mi355_ba.h"
 
@@ -50,15 +53,16 @@ void RotationMatrix(const double aa[3], Eigen::Matrix3d* R) {
 
 struct PairResult {
   bool ok = false;
-  UncalibratedRelativePose pose;
+  UncalibratedRelativePose pose;  // fundamental_matrix holds E for a calibrated pair (focal lengths 0)
   double rotation_angle_axis[3] = {0, 0, 0};
   RansacSummary summary;
 };
 
-// All pairs in one device call.  centred[p]: the pair's centred correspondences; thresholds: squared, pixels^2.
-bool RunBatch(const std::vector<const std::vector<FeatureCorrespondence>*>& centred, const std::vector<double>& thresholds,
-              const std::vector<uint32_t>& streams, const tmi_ba_two_view_ransac_options& options,
-              std::vector<PairResult>* results) {
+// All pairs of one kind in one device call.  centred[p]: the pair's centred (calibrated: normalised) correspondences;
+// thresholds: squared, in the correspondences' units.
+bool RunBatch(bool calibrated, const std::vector<const std::vector<FeatureCorrespondence>*>& centred,
+              const std::vector<double>& thresholds, const std::vector<uint32_t>& streams,
+              const tmi_ba_two_view_ransac_options& options, std::vector<PairResult>* results) {
   const int P = static_cast<int>(centred.size());
   results->assign(P, PairResult());
   std::vector<int64_t> offset(P + 1, 0);
@@ -79,12 +83,19 @@ bool RunBatch(const std::vector<const std::vector<FeatureCorrespondence>*>& cent
       rot(3 * static_cast<size_t>(P) + 1), pos(3 * static_cast<size_t>(P) + 1);
   std::vector<uint8_t> inlier(static_cast<size_t>(offset[P]) + 1, 0);
   tmi_ba_two_view_ransac_summary summary;
-  const int rc = tmi_ba_estimate_uncalibrated_relative_poses(
-      &options, P, offset.data(), f1.data(), f2.data(), thresholds.data(), nullptr, streams.data(), nullptr, 0,
-      status.data(), nullptr, nullptr, iterations.data(), nullptr, confidence.data(), F.data(), fl1.data(), fl2.data(),
-      rot.data(), pos.data(), inlier.data(), nullptr, &summary);
+  const int rc =
+      calibrated
+          ? tmi_ba_estimate_calibrated_relative_poses(
+                &options, P, offset.data(), f1.data(), f2.data(), thresholds.data(), nullptr, streams.data(), nullptr, 0,
+                status.data(), nullptr, nullptr, iterations.data(), nullptr, nullptr, confidence.data(), F.data(),
+                rot.data(), pos.data(), inlier.data(), nullptr, &summary)
+          : tmi_ba_estimate_uncalibrated_relative_poses(
+                &options, P, offset.data(), f1.data(), f2.data(), thresholds.data(), nullptr, streams.data(), nullptr, 0,
+                status.data(), nullptr, nullptr, iterations.data(), nullptr, confidence.data(), F.data(), fl1.data(),
+                fl2.data(), rot.data(), pos.data(), inlier.data(), nullptr, &summary);
   if (rc != TMI_BA_OK) {
-    std::fprintf(stderr, "[theia::EstimateUncalibratedRelativePose] device call failed: %s\n", tmi_ba_last_error());
+    std::fprintf(stderr, "[theia::%s] device call failed: %s\n",
+                 calibrated ? "EstimateRelativePose" : "EstimateUncalibratedRelativePose", tmi_ba_last_error());
     return false;
   }
   for (int p = 0; p < P; ++p) {
@@ -134,10 +145,32 @@ bool EstimateUncalibratedRelativePose(const RansacParameters& ransac_params, con
   DeviceOptions(ransac_params.failure_probability, ransac_params.min_inlier_ratio, ransac_params.min_iterations,
                 ransac_params.max_iterations, ransac_params.seed, -1, &o);
   std::vector<PairResult> results;
-  if (!RunBatch({&centered_correspondences}, {ransac_params.error_thresh}, {0u}, o, &results)) return false;
+  if (!RunBatch(false, {&centered_correspondences}, {ransac_params.error_thresh}, {0u}, o, &results)) return false;
   if (ransac_summary != nullptr) *ransac_summary = results[0].summary;
   if (!results[0].ok) return false;
   *relative_pose = results[0].pose;
+  return true;
+}
+
+bool EstimateRelativePose(const RansacParameters& ransac_params, const RansacType& ransac_type,
+                          const std::vector<FeatureCorrespondence>& normalized_correspondences,
+                          RelativePose* relative_pose, RansacSummary* ransac_summary) {
+  if (ransac_type != RansacType::RANSAC || ransac_params.use_mle || ransac_params.use_Tdd_test) {
+    std::fprintf(stderr, "[theia::EstimateRelativePose] unsupported: only RansacType::RANSAC without use_mle and "
+                         "use_Tdd_test is provided\n");
+    return false;
+  }
+  if (relative_pose == nullptr) return false;
+  tmi_ba_two_view_ransac_options o;
+  DeviceOptions(ransac_params.failure_probability, ransac_params.min_inlier_ratio, ransac_params.min_iterations,
+                ransac_params.max_iterations, ransac_params.seed, -1, &o);
+  std::vector<PairResult> results;
+  if (!RunBatch(true, {&normalized_correspondences}, {ransac_params.error_thresh}, {0u}, o, &results)) return false;
+  if (ransac_summary != nullptr) *ransac_summary = results[0].summary;
+  if (!results[0].ok) return false;
+  relative_pose->essential_matrix = results[0].pose.fundamental_matrix;
+  relative_pose->rotation = results[0].pose.rotation;
+  relative_pose->position = results[0].pose.position;
   return true;
 }
 
@@ -148,62 +181,70 @@ std::vector<bool> EstimateTwoViewInfos(const EstimateTwoViewInfoOptions& options
     std::fprintf(stderr, "[theia::EstimateTwoViewInfo] unsupported: only RansacType::RANSAC is provided\n");
     return success;
   }
-  std::vector<size_t> which;  // the uncalibrated pairs
-  std::vector<std::vector<FeatureCorrespondence>> centred;
-  std::vector<double> thresholds;
-  std::vector<uint32_t> streams;
+  // one device call per kind of pair: [0] uncalibrated (eight-point), [1] calibrated (five-point)
+  std::vector<size_t> which[2];
+  std::vector<std::vector<FeatureCorrespondence>> centred[2];
+  std::vector<double> thresholds[2];
+  std::vector<uint32_t> streams[2];
   for (size_t k = 0; k < problems.size(); ++k) {
     const TwoViewInfoProblem& q = problems[k];
     if (q.intrinsics1 == nullptr || q.intrinsics2 == nullptr || q.correspondences == nullptr ||
         q.twoview_info == nullptr || q.inlier_indices == nullptr)
       continue;
-    if (q.intrinsics1->focal_length.is_set && q.intrinsics2->focal_length.is_set) {
-      std::fprintf(stderr, "[theia::EstimateTwoViewInfo] pair %zu: both focal lengths are known; the calibrated "
-                           "(five-point) branch is not provided, the pair is left alone\n", k);
+    const bool calibrated = q.intrinsics1->focal_length.is_set && q.intrinsics2->focal_length.is_set;
+    if (calibrated && options.use_mle) {
+      std::fprintf(stderr, "[theia::EstimateTwoViewInfo] pair %zu: both focal lengths are known and options.use_mle is "
+                           "set; MLESAC scoring is not provided (set use_mle = false for inlier-count scoring), the "
+                           "pair is left alone\n", k);
       continue;
     }
     q.inlier_indices->clear();  // estimate_twoview_info.cc:260
     double pp1[2], pp2[2];
     PrincipalPoint(*q.intrinsics1, pp1);
     PrincipalPoint(*q.intrinsics2, pp2);
+    // NormalizeFeatures (:67-100) for a PINHOLE camera set from the priors: the focal division only with both priors
+    const double fl1 = calibrated ? q.intrinsics1->focal_length.value[0] : 1.0;
+    const double fl2 = calibrated ? q.intrinsics2->focal_length.value[0] : 1.0;
     std::vector<FeatureCorrespondence> c(q.correspondences->size());
     for (size_t i = 0; i < c.size(); ++i) {
       const FeatureCorrespondence& in = (*q.correspondences)[i];
-      c[i].feature1 = Feature(in.feature1.x() - pp1[0], in.feature1.y() - pp1[1]);
-      c[i].feature2 = Feature(in.feature2.x() - pp2[0], in.feature2.y() - pp2[1]);
+      c[i].feature1 = Feature((in.feature1.x() - pp1[0]) / fl1, (in.feature1.y() - pp1[1]) / fl1);
+      c[i].feature2 = Feature((in.feature2.x() - pp2[0]) / fl2, (in.feature2.y() - pp2[1]) / fl2);
     }
-    centred.push_back(std::move(c));
+    centred[calibrated].push_back(std::move(c));
     const double t1 = ResolutionScaledThreshold(options.max_sampson_error_pixels, q.intrinsics1->image_width,
                                                 q.intrinsics1->image_height);
     const double t2 = ResolutionScaledThreshold(options.max_sampson_error_pixels, q.intrinsics2->image_width,
                                                 q.intrinsics2->image_height);
-    thresholds.push_back(t1 * t2);  // :220-221
-    streams.push_back(q.stream_id);
-    which.push_back(k);
+    thresholds[calibrated].push_back(calibrated ? t1 * t2 / (fl1 * fl2) : t1 * t2);  // :160-162, :220-221
+    streams[calibrated].push_back(q.stream_id);
+    which[calibrated].push_back(k);
   }
-  if (which.empty()) return success;
   tmi_ba_two_view_ransac_options o;
   DeviceOptions(1.0 - options.expected_ransac_confidence, 0.0, options.min_ransac_iterations,
                 options.max_ransac_iterations, options.seed, options.device, &o);
-  std::vector<const std::vector<FeatureCorrespondence>*> ptrs;
-  for (const auto& c : centred) ptrs.push_back(&c);
-  std::vector<PairResult> results;
-  if (!RunBatch(ptrs, thresholds, streams, o, &results)) return success;
-  for (size_t j = 0; j < which.size(); ++j) {
-    const PairResult& r = results[j];
-    if (!r.ok) continue;
-    const TwoViewInfoProblem& q = problems[which[j]];
-    TwoViewInfo* info = q.twoview_info;
-    for (int i = 0; i < 3; ++i) {
-      info->rotation_2[i] = r.rotation_angle_axis[i];
-      info->position_2[i] = r.pose.position[i];
+  for (int calibrated = 0; calibrated < 2; ++calibrated) {
+    if (which[calibrated].empty()) continue;
+    std::vector<const std::vector<FeatureCorrespondence>*> ptrs;
+    for (const auto& c : centred[calibrated]) ptrs.push_back(&c);
+    std::vector<PairResult> results;
+    if (!RunBatch(calibrated != 0, ptrs, thresholds[calibrated], streams[calibrated], o, &results)) continue;
+    for (size_t j = 0; j < which[calibrated].size(); ++j) {
+      const PairResult& r = results[j];
+      if (!r.ok) continue;
+      const TwoViewInfoProblem& q = problems[which[calibrated][j]];
+      TwoViewInfo* info = q.twoview_info;
+      for (int i = 0; i < 3; ++i) {
+        info->rotation_2[i] = r.rotation_angle_axis[i];
+        info->position_2[i] = r.pose.position[i];
+      }
+      info->focal_length_1 = calibrated ? q.intrinsics1->focal_length.value[0] : r.pose.focal_length1;  // :180-181
+      info->focal_length_2 = calibrated ? q.intrinsics2->focal_length.value[0] : r.pose.focal_length2;
+      info->num_verified_matches = static_cast<int>(r.summary.inliers.size());
+      info->visibility_score = 0;  // of the (still empty) *inlier_indices: :183-186, :243-245
+      *q.inlier_indices = r.summary.inliers;
+      success[which[calibrated][j]] = true;
     }
-    info->focal_length_1 = r.pose.focal_length1;
-    info->focal_length_2 = r.pose.focal_length2;
-    info->num_verified_matches = static_cast<int>(r.summary.inliers.size());
-    info->visibility_score = 0;  // of the (still empty) *inlier_indices: :243-245
-    *q.inlier_indices = r.summary.inliers;
-    success[which[j]] = true;
   }
   return success;
 }

@@ -893,3 +893,27 @@ def make_uncalibrated_pair_batch(num_pairs: int, num_correspondences, seed: int,
         f2[a + out] = rng.uniform([-hw, -hh], [hw, hh], (n_out, 2))
     return dict(pair_offset=ptr, feature1=f1, feature2=f2, is_inlier=inl, focal_length1=fl1, focal_length2=fl2,
                 rotation=rot, position=pos, fundamental_matrix=Fm, points=X)
+
+
+def make_calibrated_pair_batch(num_pairs: int, num_correspondences, seed: int, *, inlier_ratio=1.0, pixel_noise=0.5,
+                               focal_range=(800.0, 1600.0), image_half_size=(512.0, 384.0)):
+    """View pairs for tmi_ba_estimate_calibrated_relative_poses: the scenes of make_uncalibrated_pair_batch (same
+    arguments, same random stream) with every feature divided by its view's focal length, i.e. NORMALISED coordinates
+    with pixel_noise / focal of noise.  Returns that dict with feature1 / feature2 normalised, plus pixel1 / pixel2 (the
+    centred pixels) and essential_matrix [P, 3, 3] (x2^T E x1 = 0, unit Frobenius norm)."""
+    b = make_uncalibrated_pair_batch(num_pairs, num_correspondences, seed, inlier_ratio=inlier_ratio,
+                                     pixel_noise=pixel_noise, focal_range=focal_range, image_half_size=image_half_size)
+    ptr = b["pair_offset"]
+    n = np.diff(ptr)
+    b["pixel1"], b["pixel2"] = b["feature1"], b["feature2"]
+    b["feature1"] = b["pixel1"] / np.repeat(b["focal_length1"], n)[:, None]
+    b["feature2"] = b["pixel2"] / np.repeat(b["focal_length2"], n)[:, None]
+    E = np.zeros((int(num_pairs), 3, 3))
+    for p in range(int(num_pairs)):
+        R = Rotation.from_rotvec(b["rotation"][p]).as_matrix()
+        c = b["position"][p]
+        tx = np.array([[0, -c[2], c[1]], [c[2], 0, -c[0]], [-c[1], c[0], 0]])
+        Ep = R @ tx.T
+        E[p] = Ep / np.linalg.norm(Ep)
+    b["essential_matrix"] = E
+    return b
