@@ -1448,7 +1448,11 @@ int32_t tmi_ba_solver_structure_checksums(tmi_ba_solver* solver, uint64_t out[24
  *          TRIVIAL-loss problem with unit aspect ratio and zero skew the camera block is formed from the point block, the
  *          normalised image point, the track and the view instead of stored (TMI_BA_COMPACT_PLANES=0 switches it off)
  *          bit 1: the handle may linearise the candidate of a trial step speculatively instead of taking its trial cost
- *          (TMI_BA_SPECULATIVE_LINEARIZE=0 switches it off)                                                             */
+ *          (TMI_BA_SPECULATIVE_LINEARIZE=0 switches it off)
+ *          bit 2: back-substitution can take y_p and the model cost change from the per-track sums the PCG solve's
+ *          matrix-free products left instead of sweeping the observations again (one rank, the one-sweep product, no
+ *          shared intrinsics blocks; TMI_BA_BACKSUB_FROM_PRODUCTS=0 switches it off)
+ *          bits 8..: LM iterations of the handle's last solve that took that path                                       */
 int32_t tmi_ba_solver_operator_info(tmi_ba_solver* solver, int32_t out[8]);
 
 /* Host-only: statistics of the static structure the engine would build for

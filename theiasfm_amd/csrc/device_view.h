@@ -175,6 +175,10 @@ struct DeviceView {
   double* dotbuf;   // [Nrb] per-block partial dot products of the product kernels
   int* ticket;      // [4][kTicketStride] arrival counters of the "last workgroup finishes the reduction" kernels
   int* pcg_done;    // set by pcg_step once PCG has stopped: pcg_p, enqueued behind it, returns at once
+  // back-substitution from the products' per-track sums (back_combine_kernel, kernels.h): pcg_step leaves the step length
+  // of PCG iteration it in alpha_hist[it - 1] while it <= alpha_cap (null / 0: the handle has no planes for the sums)
+  double* alpha_hist;
+  int alpha_cap;
 };
 
 // The buffers of DeviceView that the COMPACT linearize writes and a later kernel of the same linearisation reads
@@ -232,7 +236,7 @@ enum {
   SC_SS = 1,        // sum of squared raw residuals
   SC_CAND_COST = 2,
   SC_CAND_SS = 3,
-  SC_MCC = 4,       // model cost change
+  SC_MCC = 4,       // model cost change: the camera-side scalars of back_combine_kernel (update_cameras_kernel leaves them)
   SC_STEP_SQ = 5,
   SC_XNORM_SQ = 6,
   SC_GMAX = 7,

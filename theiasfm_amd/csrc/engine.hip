@@ -111,14 +111,19 @@ struct Launch {
   // the one-sweep matrix-free product of mf_chunks.h (no shared intrinsics blocks)
   // xs_ready: DeviceView::xs already holds x with the position entries scaled (pcg_init / pcg_p leave it for cg_p)
   // ev_a / ev_b (may be null): HIP events that take the start of the first and the end of the last kernel of the product
+  // sk (may be null): planes [DP][Np_pad] the product leaves every track's sum_i Jp_i^T (A_i x) in (back_combine)
   void (*mf_product)(const DeviceView&, const mfc::View&, hipStream_t, RedLayout, const double*, double*, double, double,
-                     double, int, int dot, int xs_ready, hipEvent_t ev_a, hipEvent_t ev_b, const int* guard);
+                     double, int, int dot, int xs_ready, hipEvent_t ev_a, hipEvent_t ev_b, const int* guard, double* sk);
   void (*pcg_step)(const DeviceView&, hipStream_t, const double* b, int it, int nb, double eta, int min_it,
                    int max_it, const double* red8, HostMirror* mirror, unsigned long long seq, const int* guard);
   void (*pcg_a)(const DeviceView&, hipStream_t, int, int);
   void (*pcg_b2)(const DeviceView&, hipStream_t, const double*, int, int, double*);
   void (*back_substitute)(const DeviceView&, hipStream_t, int, double*, double* sums);
-  void (*update_cameras)(const DeviceView&, hipStream_t, double* out, double* prep_c);
+  // (want_mcc: + the camera-side scalars of back_combine's model cost change)
+  void (*update_cameras)(const DeviceView&, hipStream_t, double* out, double* prep_c, RedLayout, double ir, double lo, double hi,
+                         int want_mcc);
+  // back_substitute from the K planes of per-track sums the products of this PCG solve left (kernels.h, back_combine_kernel)
+  void (*back_combine)(const DeviceView&, hipStream_t, const double* sk, int K, int nb, double* partial, double* sums);
   void (*pcg_init)(const DeviceView&, hipStream_t, const double* b, int nb);
   void (*pcg_persistent)(const DeviceView&, hipStream_t, int grid, const ppcg::Args&);
   void (*dense_gather)(const DeviceView&, hipStream_t, const double*, double*, int);
@@ -326,7 +331,7 @@ Launch make_launch(bool fp32) {
   };
   L.mf_product = [](const DeviceView& v, const mfc::View& m0, hipStream_t st, RedLayout R, const double* x, double* y,
                     double ir, double lo, double hi, int add_diag, int dot, int xs_ready, hipEvent_t ev_a, hipEvent_t ev_b,
-                    const int* guard) {
+                    const int* guard, double* sk) {
     if (!v.Nrb) return;
     mfc::View m = m0;
     m.guard = guard;
@@ -339,19 +344,19 @@ Launch make_launch(bool fp32) {
       if constexpr (D == 9) {
         if (m.n_items && v.compact == 2) {
           hipExtLaunchKernelGGL((mfc::product_kernel<D, DP, true, 2>), dim3(m.n_items), dim3(mfc::kThreads), 0, st, ev_a, nullptr, 0, v,
-                                m, (const double*)v.xs);
+                                m, (const double*)v.xs, sk);
           cp_done = true;
         } else if (m.n_items && v.compact) {
           hipExtLaunchKernelGGL((mfc::product_kernel<D, DP, true, 1>), dim3(m.n_items), dim3(mfc::kThreads), 0, st, ev_a, nullptr, 0, v,
-                                m, (const double*)v.xs);
+                                m, (const double*)v.xs, sk);
           cp_done = true;
         }
       }
       if (m.n_items && !cp_done)
         hipExtLaunchKernelGGL((mfc::product_kernel<D, DP, true>), dim3(m.n_items), dim3(mfc::kThreads), 0, st, ev_a, nullptr, 0, v, m,
-                              (const double*)v.xs);
+                              (const double*)v.xs, sk);
     } else if (m.n_items) {
-      hipExtLaunchKernelGGL((mfc::product_kernel<D, DP, false>), dim3(m.n_items), dim3(mfc::kThreads), 0, st, ev_a, nullptr, 0, v, m, x);
+      hipExtLaunchKernelGGL((mfc::product_kernel<D, DP, false>), dim3(m.n_items), dim3(mfc::kThreads), 0, st, ev_a, nullptr, 0, v, m, x, sk);
     }
     hipExtLaunchKernelGGL((mfc::reduce_kernel<D>), dim3(8 * ((v.Nrb + 7) / 8)), dim3(256), 0, st, m.n_items ? nullptr : ev_a, ev_b, 0,
                           v, m, R, x, y, ir, lo, hi, add_diag, dot);
@@ -367,12 +372,17 @@ Launch make_launch(bool fp32) {
     //  the candidate points and their step / norm sums come out of this launch too: no update_points launch)
     hipLaunchKernelGGL((back_substitute_kernel<D, DP, SH>), dim3(nb), dim3(256), 0, st, v, nb, partial, sums);
   };
-  L.update_cameras = [](const DeviceView& v, hipStream_t st, double* out, double* prep_c) {
+  L.update_cameras = [](const DeviceView& v, hipStream_t st, double* out, double* prep_c, RedLayout R, double ir, double lo,
+                        double hi, int want_mcc) {
     const int n = v.Nc + (SH ? v.Nrb - v.Ncam_rb : 0);
-    hipLaunchKernelGGL((update_cameras_kernel<D, SH>), dim3((std::max(n, 1) + 255) / 256), dim3(256), 0, st, v, out, prep_c);
+    hipLaunchKernelGGL((update_cameras_kernel<D, SH>), dim3((std::max(n, 1) + 255) / 256), dim3(256), 0, st, v, out, prep_c, R,
+                       ir, lo, hi, SH ? 0 : want_mcc);
     // shared intrinsics: a view's record needs its group's candidate, written by another thread
     if (SH && v.Nc)
       hipLaunchKernelGGL(camera_prepare_kernel, dim3((v.Nc + 255) / 256), dim3(256), 0, st, v, v.ext_c, v.intr_c, prep_c);
+  };
+  L.back_combine = [](const DeviceView& v, hipStream_t st, const double* sk, int K, int nb, double* partial, double* sums) {
+    hipLaunchKernelGGL((back_combine_kernel<D, DP>), dim3(nb), dim3(256), 0, st, v, sk, K, nb, partial, sums);
   };
   L.pcg_init = [](const DeviceView& v, hipStream_t st, const double* b, int nb) {
     hipLaunchKernelGGL((pcg_init_kernel<D>), dim3(nb), dim3(kPcgStepThreads), 0, st, v, b, nb);
@@ -485,7 +495,7 @@ __global__ void flag_to_scalar_kernel(const int* __restrict__ flag, double* __re
 struct tmi_ba_solver {
   Structure st;
   Launch launch;
-  DeviceView v;
+  DeviceView v = {};
   RedLayout RL;
   int DP = 4;
   int device = 0;
@@ -534,6 +544,17 @@ struct tmi_ba_solver {
   bool spec_ready = false, spec_off = false;
   bool spec_swapped = false;  // DeviceView currently holds the second set (whose pm_A has room for compact planes only)
   LinearisationSet spec_set = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  // Back-substitution from the products' per-track sums (kernels.h, back_combine_kernel): on an eligible LM iteration
+  // (solve) every product of the PCG solve also stores s_k = W^T p_k per track, and y_p, the candidate points and the
+  // model cost change come from a per-track combine of those planes instead of back_substitute's sweep over the
+  // observations.  TMI_BA_BACKSUB_FROM_PRODUCTS=0: always the sweep.  The kBspCap planes ([DP][Np_pad] each) are allocated
+  // at the first eligible iteration; bsp_off: that failed, the sweep for the life of the handle.
+  bool bsp_env = true;
+  bool bsp_ready = false, bsp_off = false;
+  double* d_sk = nullptr;     // [kBspCap][DP][Np_pad]
+  bool bsp_live = false;      // the products of the current PCG solve store their sums
+  int bsp_K = 0;              // > 0: the solve ended with y_c = sum of K recorded steps -- the planes stand for the sweep
+  int bsp_used = 0;           // LM iterations of the last solve() that took the combine (operator_info)
   bool implicit = false;      // S is never formed (schur_mode)
   bool adaptive = false;     // schur_mode auto on one rank: both operators are resident and every LM iteration
                               // takes the cheaper one for the PCG length it expects (see solve)
@@ -740,6 +761,32 @@ bool ensure_speculative_set(tmi_ba_solver* s) {
   for (int i = 0; i < 6; ++i) s->allocs.push_back((void*)p[i]);
   s->spec_set = LinearisationSet{p[0], p[1], p[2], p[3], p[4], p[5]};
   s->spec_ready = true;
+  return true;
+}
+
+// The planes of per-track sums of back_combine_kernel: a PCG solve that ends before its first residual reset
+// (residual_reset_period = 10) has at most nine products, so nine planes cover every solve the path can serve at all
+// (the PCG lengths of the headline workload: profiles/backsub_from_products_summary.md); 216 MB at Venice size (1 M
+// tracks) beside ~1.3 GB of observation planes.  Allocated on first use; false: the allocation failed
+// (the sticky HIP error is cleared and the handle keeps the sweep for its life, as ensure_speculative_set does).
+constexpr int kBspCap = 9;
+bool ensure_backsub_planes(tmi_ba_solver* s) {
+  if (s->bsp_ready) return true;
+  if (s->bsp_off) return false;
+  const size_t n = (size_t)kBspCap * (size_t)s->DP * std::max<size_t>((size_t)s->st.Np_pad, 1);
+  double *p = nullptr, *a = nullptr;
+  if (hipMalloc((void**)&p, n * sizeof(double)) != hipSuccess || hipMalloc((void**)&a, kBspCap * sizeof(double)) != hipSuccess) {
+    (void)hipGetLastError();
+    if (p) (void)hipFree(p);
+    s->bsp_off = true;
+    return false;
+  }
+  s->allocs.push_back((void*)p);
+  s->allocs.push_back((void*)a);
+  s->d_sk = p;
+  s->v.alpha_hist = a;
+  s->v.alpha_cap = kBspCap;
+  s->bsp_ready = true;
   return true;
 }
 
@@ -2332,6 +2379,8 @@ static int create_impl(tmi_ba_solver* s, const tmi_ba_problem* P, const tmi_ba_o
     s->compact_robust = !(env && env[0] == '0');
     env = getenv("TMI_BA_SPECULATIVE_LINEARIZE");
     s->spec_env = !(env && env[0] == '0');
+    env = getenv("TMI_BA_BACKSUB_FROM_PRODUCTS");
+    s->bsp_env = !(env && env[0] == '0');
   }
   v.direct_diag = 0;
   {
@@ -2606,7 +2655,8 @@ static void prepare_cameras(tmi_ba_solver* s, const double* ext, const double* i
 // returns TMI_BA_OK; *usable = 0 for LINEAR_SOLVER_FAILURE
 // q = S x: explicit (symmetric block SpMV on the formed Schur complement) or implicit
 // (two passes over the observations; the reduced vector is all-reduced across ranks)
-static int apply_schur(tmi_ba_solver* s, const double* x, double* y, int dot = 0, int xs_ready = 0, const int* guard = nullptr) {
+static int apply_schur(tmi_ba_solver* s, const double* x, double* y, int dot = 0, int xs_ready = 0, const int* guard = nullptr,
+                       double* sk = nullptr) {
   DeviceView& v = s->v;
   const int n = v.Nrb * v.D;
   if (!s->implicit_now) {
@@ -2620,7 +2670,7 @@ static int apply_schur(tmi_ba_solver* s, const double* x, double* y, int dot = 0
     const int add_diag = (s->st.world <= 1 || s->st.rank == 0) ? 1 : 0;
     if (s->mf_ok)
       s->launch.mf_product(v, s->mf, s->stream, s->RL, x, y, s->cur_inv_radius, O->min_lm_diagonal, O->max_lm_diagonal,
-                           add_diag, dot, xs_ready, t.start(), t.stop(), guard);
+                           add_diag, dot, xs_ready, t.start(), t.stop(), guard, sk);
     else
       s->launch.implicit_spmv(v, s->stream, s->RL, x, y, s->d_pm_u, s->d_cm_t, s->cur_inv_radius,
                               O->min_lm_diagonal, O->max_lm_diagonal, add_diag, s->nblocks_tracks, dot);
@@ -2909,8 +2959,12 @@ static int solve_reduced_pcg(tmi_ba_solver* s, const tmi_ba_options* O, int* usa
   bool xs_valid = !s->cl_active;
   // One fused iteration: product (+ p.q) -> [all-reduce] -> pcg_step, which publishes to slot (it & 1) of the host mirror.
   // guard != null: the kernels return at once when the previous step's stopping test held (DeviceView::pcg_done).
+  // (bsp_live: product it_ also leaves the tracks' W^T p in plane it_ - 1, solve())
+  s->bsp_K = 0;
+  const bool sk_on = s->bsp_live && fused && s->implicit_now && s->mf_ok && s->st.world == 1;
   auto enqueue_step = [&](int it_, const int* guard, unsigned long long* seq_out) -> int {
-    const int rcs = apply_schur(s, v.cg_p, v.cg_q, /*dot=*/1, xs_valid ? 1 : 0, guard);
+    double* sk = (sk_on && it_ <= kBspCap) ? s->d_sk + (size_t)(it_ - 1) * s->DP * (size_t)v.Np_pad : nullptr;
+    const int rcs = apply_schur(s, v.cg_p, v.cg_q, /*dot=*/1, xs_valid ? 1 : 0, guard, sk);
     if (rcs) return rcs;
     xs_valid = true;  // (pcg_step leaves the scaled copy of the next p)
     Timed t(s, TMI_BA_K_PCG_VECTOR);
@@ -3028,6 +3082,11 @@ static int solve_reduced_pcg(tmi_ba_solver* s, const tmi_ba_options* O, int* usa
   }
   void_speculation();
   *iters += it;
+  // y_c = sum_{k <= it} alpha_k p_k with every s_k stored: PCG started from x = 0, every iteration was a fused step (no
+  // residual-reset iteration, whose kernels record nothing) and the last one moved x (p.q > 0, no failure)
+  if (sk_on && *usable && it >= 1 && it <= kBspCap && it < 10 && !s->h_flags[FL_PCG_FAIL] && s->h_scal[SC_PQ] > 0.0 &&
+      std::isfinite(s->h_scal[SC_PQ]))
+    s->bsp_K = it;
   return TMI_BA_OK;
 }
 
@@ -3535,7 +3594,7 @@ int32_t tmi_ba_solver_solve(tmi_ba_solver* s, const tmi_ba_options* O, tmi_ba_su
   double xnorm_cam_sq = 0.0, xnorm_pts_sq = 0.0;
   {
     Timed t(s, TMI_BA_K_UPDATE_COST);
-    s->launch.update_cameras(v, stream, v.scal + SC_STEP_SQ, v.prep_c);  // y = 0: copies + |x|
+    s->launch.update_cameras(v, stream, v.scal + SC_STEP_SQ, v.prep_c, RL, 0.0, 0.0, 0.0, 0);  // y = 0: copies + |x|
     hipLaunchKernelGGL(points_norm_kernel, dim3(nbp), dim3(256), 0, stream, v, v.pts, nbp, v.partial, d_sc);
   }
   CK(do_allreduce(s, d_sc, 8));
@@ -3554,6 +3613,7 @@ int32_t tmi_ba_solver_solve(tmi_ba_solver* s, const tmi_ba_options* O, tmi_ba_su
   const char* why = "maximum number of iterations reached";
   int64_t pcg_iters = 0;
   s->n_implicit_iterations = 0;
+  s->bsp_used = 0;
   bool need_gradient_check = true;  // after the first build and after every accepted step
   bool inner_enabled = O->use_inner_iterations != 0;
   bool time_up = false;
@@ -3652,6 +3712,16 @@ int32_t tmi_ba_solver_solve(tmi_ba_solver* s, const tmi_ba_options* O, tmi_ba_su
         }
       }
       const int64_t before = pcg_iters;
+      // back-substitution from the products' sums: one rank, the one-sweep product, no clusters, and a forecast (the
+      // previous iteration's PCG length, what schur_mode auto prices with) the planes cover -- a longer solve would pay
+      // for stores nobody reads; update_cameras needs three rows of dotbuf for the camera-side scalars
+      // Not with the IDENTITY preconditioner: sum |u|^2 rests on PCG's recurrence residual, and without a preconditioner
+      // that residual drifts far enough from b - S y_c to move the model cost change by ~1e-8 relative (measured:
+      // tests/test_gpu_compact_planes.py, identity_preconditioner, where two operators must agree to 1e-10).
+      s->bsp_live = s->bsp_env && st.world == 1 && s->implicit_now && s->mf_ok && !st.has_shared && !s->cl_active &&
+                    O->preconditioner_type != TMI_BA_PRECOND_IDENTITY &&
+                    last_pcg_len <= kBspCap && 3 * ((std::max(st.Nc, 1) + 255) / 256) <= st.Nrb + 8 && ensure_backsub_planes(s);
+      s->bsp_K = 0;
       if (s->cl_active && s->cl_failed) {
         usable = 0;  // the tridiagonal preconditioner could not be factored, scaled or not: the linear solve fails (Ceres)
       } else {
@@ -3707,15 +3777,23 @@ int32_t tmi_ba_solver_solve(tmi_ba_solver* s, const tmi_ba_options* O, tmi_ba_su
     bool cand_invalid = false;
     int spec_compact = 0;  // != 0: the candidate was linearised into the second set (DeviceView::compact of that set)
     if (usable) {
+      const bool combine = iterative && s->bsp_live && s->bsp_K > 0;
       {
         // candidate cameras + their prepared records (+ the scaled copy of y_c back_substitute gathers: first)
         Timed t(s, TMI_BA_K_UPDATE_COST);
-        s->launch.update_cameras(v, stream, v.scal + SC_STEP_SQ, v.prep_c);
+        s->launch.update_cameras(v, stream, v.scal + SC_STEP_SQ, v.prep_c, RL, inv_radius, O->min_lm_diagonal,
+                                 O->max_lm_diagonal, combine ? 1 : 0);
       }
       {
-        // y_p, the model cost change, the candidate points and their share of |step|^2, |x+|^2: d_sc[0..2]
+        // y_p, the model cost change, the candidate points and their share of |step|^2, |x+|^2: d_sc[0..2] -- from the
+        // planes the products of this solve left where they stand for the sweep (solve_reduced_pcg, bsp_K)
         Timed t(s, TMI_BA_K_BACK_SUBSTITUTE);
-        s->launch.back_substitute(v, stream, nbs, v.partial, d_sc + 0);
+        if (combine) {
+          s->launch.back_combine(v, stream, s->d_sk, s->bsp_K, nbp, v.partial, d_sc + 0);
+          s->bsp_used++;
+        } else {
+          s->launch.back_substitute(v, stream, nbs, v.partial, d_sc + 0);
+        }
       }
       // d_sc: [mcc, step_sq_points, |x+|^2 points, cand_cost, cand_ss, invalid votes, singular
       //        track votes, time-limit votes]
@@ -4027,6 +4105,11 @@ int32_t tmi_ba_solver_operator_info(tmi_ba_solver* s, int32_t out[8]) {
   if (s->spec_env && !s->spec_off && s->compact_env && s->v.drop_pos && s->v.uniform_pinhole_default && s->mf_ok && s->direct_ok &&
       s->st.D == 9 && s->v.cp_trk != nullptr && !s->v.planes_fp32 && !s->cluster_blocks)
     out[7] |= 2;
+  // bit 2: back-substitution from the products' per-track sums is available to this handle (the switch is on, one rank, the
+  // one-sweep product, no shared intrinsics blocks, the planes have not failed to allocate); bits 8..: the LM iterations of
+  // the last solve() that took it (the others ran back_substitute's sweep)
+  if (s->bsp_env && !s->bsp_off && s->mf_ok && !s->st.has_shared && s->st.world == 1) out[7] |= 4;
+  out[7] |= (int32_t)std::min(s->bsp_used, (1 << 22)) << 8;
   return TMI_BA_OK;
 }
 

@@ -2919,6 +2919,8 @@ __global__ __launch_bounds__(kPcgStepThreads) void pcg_step_kernel(DeviceView v,
     };
     set(SC_PQ, pq);
     set(SC_ALPHA, alpha);
+    // y_c = sum_k alpha_k p_k: the step lengths back_combine_kernel weighs the products' per-track sums with
+    if (ok && v.alpha_hist && it <= v.alpha_cap) v.alpha_hist[it - 1] = alpha;
     if (ok && !isfinite(alpha)) {
       v.flags[FL_PCG_FAIL] = 1;
       pubf[FL_PCG_FAIL] = 1;
@@ -3363,6 +3365,98 @@ __global__ __launch_bounds__(256) void back_substitute_kernel(DeviceView v, int 
 }
 
 // ------------------------------------------------------------------------------
+// back_substitute without the sweep (kernel class 8; one rank, the one-sweep matrix-free product, PCG from x = 0 without a
+// residual-reset iteration): everything back_substitute_kernel takes from the observations is linear in y_c but sum |u|^2,
+// and PCG has already applied that linear map to every direction, y_c = sum_k alpha_k p_k.  Product k left
+// s_k = sum_i Jp_i^T (A_i p_k) of every track in plane k of sk (mfc::product_kernel: the w ahead of its track solve, in
+// the same scaled system as the Jp planes -- s_k itself, not L^-1 s_k; V_d^-1 is loaded for y_p anyway), so
+//   c = W^T y_c = sum_k alpha_k s_k   (k ascending),   w = g_p - c,   y_p = V_d^-1 w     as before, and
+//   sum_i u_i.r_i = y_c.g_c,
+//   sum_i |u_i|^2 = y_c^T U y_c = y_c.(b - r_K) - y_c^T D_c y_c + sum_tracks c^T V_d^-1 c
+// from S = U + D_c - W V_d^-1 W^T and r_K = b - S y_c (the recurrence residual PCG ended with: the identity holds to PCG's
+// own round-off, which also carries its Q-based stopping test, pcg_step_kernel).  The camera-side scalars are
+// update_cameras_kernel's (v.scal[SC_MCC], that launch runs first); this kernel adds them once, in a fixed place.
+// One lane per track; sums as back_substitute_kernel leaves them.
+// ------------------------------------------------------------------------------
+template <int D, int DP>
+__global__ __launch_bounds__(256) void back_combine_kernel(DeviceView v, const double* __restrict__ sk, int K, int nblocks,
+                                                           double* partial, double* __restrict__ sums) {
+  constexpr int NS = sym_size(DP);
+  const int lp = blockIdx.x * 256 + threadIdx.x;
+  double acc[3] = {0.0, 0.0, 0.0};
+  if (blockIdx.x == 0 && threadIdx.x == 0) acc[0] = v.scal[SC_MCC];
+  if (lp < v.Np_pad) {
+    const size_t NP = (size_t)v.Np_pad;
+    const int k = v.pt_k[lp];
+    double ypv[DP];
+#pragma unroll
+    for (int a = 0; a < DP; ++a) ypv[a] = 0.0;
+    if (k > 0) {
+      double c[DP], w[DP];
+#pragma unroll
+      for (int a = 0; a < DP; ++a) c[a] = 0.0;
+      for (int q = 0; q < K; ++q) {
+        const double al = v.alpha_hist[q];
+        const double* s = sk + (size_t)q * DP * NP + lp;
+#pragma unroll
+        for (int a = 0; a < DP; ++a) c[a] += al * __builtin_nontemporal_load(s + (size_t)a * NP);
+      }
+#pragma unroll
+      for (int a = 0; a < DP; ++a) w[a] = v.gp[(size_t)a * NP + lp] - c[a];
+      double Vi[NS], Vr[NS], yp[DP];
+#pragma unroll
+      for (int i = 0; i < NS; ++i) {
+        Vi[i] = v.Vinv[(size_t)i * NP + lp];
+        Vr[i] = v.Vraw[(size_t)i * NP + lp];
+      }
+      double cvc = 0.0;
+#pragma unroll
+      for (int a = 0; a < DP; ++a) {
+        double t = 0.0, tc = 0.0;
+#pragma unroll
+        for (int b = 0; b < DP; ++b) {
+          const double vi = Vi[a <= b ? sym_idx(a, b, DP) : sym_idx(b, a, DP)];
+          t += vi * w[b];
+          tc += vi * c[b];
+        }
+        yp[a] = t;
+        ypv[a] = t;
+        v.yp[(size_t)a * NP + lp] = t;
+        cvc += c[a] * tc;
+      }
+      double lin = 0.0, quad = 0.0;
+#pragma unroll
+      for (int a = 0; a < DP; ++a) {
+        lin += yp[a] * w[a];
+        double t = 0.0;
+#pragma unroll
+        for (int b = 0; b < DP; ++b) t += Vr[a <= b ? sym_idx(a, b, DP) : sym_idx(b, a, DP)] * yp[b];
+        quad += yp[a] * t;
+      }
+      acc[0] += lin - 0.5 * quad - 0.5 * cvc;
+    }
+    // the candidate point and the tracks' share of |step|^2 and |x+|^2, as back_substitute_kernel
+    const bool live = k > 0 && !v.pt_const[lp];
+    const double2 x01 = *reinterpret_cast<const double2*>(v.pts + (size_t)lp * 4);
+    const double2 x23 = *reinterpret_cast<const double2*>(v.pts + (size_t)lp * 4 + 2);
+    double x[4] = {x01.x, x01.y, x23.x, x23.y};
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+      if (live && a < DP) {
+        const double d = -ypv[a < DP ? a : 0] * v.scale_p[(size_t)lp * DP + (a < DP ? a : 0)];
+        x[a] += d;
+        acc[1] += d * d;
+      }
+      if (live) acc[2] += x[a] * x[a];
+    }
+    *reinterpret_cast<double2*>(v.pts_c + (size_t)lp * 4) = make_double2(x[0], x[1]);
+    *reinterpret_cast<double2*>(v.pts_c + (size_t)lp * 4 + 2) = make_double2(x[2], x[3]);
+  }
+  // sums[0] = model cost change, sums[1] = |step|^2 over the points, sums[2] = |x+|^2 over the points
+  block_sum_finish<3>(acc, partial, nblocks, v.ticket + 2 * kTicketStride, sums);
+}
+
+// ------------------------------------------------------------------------------
 // update (kernel class 9): candidate = x - scale .* y on the free coordinates.
 // Points: by back_substitute_kernel, where y_p is in registers (partial sums [step^2, |x+|^2] for the tracks).
 // Cameras: update_cameras_kernel (the camera part is replicated on every rank).
@@ -3389,14 +3483,18 @@ __global__ __launch_bounds__(256) void points_norm_kernel(DeviceView v, const do
 // thread also writes the candidate's prepared record (camera_models.h), saving the separate
 // camera_prepare launch.  Column of parameter bit a inside its block = popcount of the lower free bits
 // (rb_cols is filled in increasing bit order, structure.cpp).
+// want_mcc (no shared intrinsics blocks; 3 gridDim.x <= Nrb + 8 entries of dotbuf): the camera-side scalars of the model
+// cost change for back_combine_kernel, v.scal[SC_MCC] = y_c.g_c - (y_c.(b - r_K) - y_c^T D_c y_c) / 2 with b = g~ and
+// r_K = cg_r, the residual PCG ended with, and D_c the clamped diagonal reduce_kernel adds (mf_chunks.h).
 template <int D, bool SH>
 __global__ __launch_bounds__(256) void update_cameras_kernel(DeviceView v, double* __restrict__ out,
-                                                             double* __restrict__ prep_c) {
-  __shared__ double uc_sh[2][4];
+                                                             double* __restrict__ prep_c, RedLayout L, double inv_radius,
+                                                             double lm_lo, double lm_hi, int want_mcc) {
+  __shared__ double uc_sh[3][4];
   __shared__ int uc_last;
   const int c = blockIdx.x * 256 + threadIdx.x;
   const int n_groups_sh = v.Nrb - v.Ncam_rb;
-  double step = 0.0, xn = 0.0;
+  double step = 0.0, xn = 0.0, mcc = 0.0;
   if (c < v.Nc) {
     const unsigned mask = v.cam_mask[c];
     const int rb = v.cam_rb[c];
@@ -3440,7 +3538,19 @@ __global__ __launch_bounds__(256) void update_cameras_kernel(DeviceView v, doubl
         for (int j = 0; j < 10; ++j) xn += K[j] * K[j];
     }
     if (!SH) prepare_camera_record(e, K, rec.z, v.scale_cam + (size_t)c * 16, prep_c + (size_t)c * kPrepStride);
-    if (!SH && v.drop_pos && rb >= 0) {
+    if (!SH && want_mcc && rb >= 0) {
+      // (identity rows, rb_cols < 0: y = 0, nothing to add)
+#pragma unroll
+      for (int a = 0; a < D; ++a) {
+        const size_t i = (size_t)rb * D + a;
+        if (v.rb_cols[i] >= 0) {
+          const double y = v.yc[i];
+          const double dc = fmin(fmax(v.red[L.udiag + i], lm_lo), lm_hi) * inv_radius;
+          mcc += y * v.red[L.gc + i] - 0.5 * (y * (v.red[L.gt + i] - v.cg_r[i]) - dc * y * y);
+        }
+      }
+    }
+    if (!SH && v.drop_pos && rb >= 0 && !want_mcc) {  // (want_mcc: back_combine follows, which gathers nothing)
       // drop_pos: the copy of y_c back_substitute gathers, position entries times the column scales (round 6:
       // pos_scale_kernel's job -- this launch runs BEFORE back_substitute and owns the view's block anyway)
       bool cpx = false;
@@ -3477,16 +3587,18 @@ __global__ __launch_bounds__(256) void update_cameras_kernel(DeviceView v, doubl
       xn += x * x;
     }
   }
-  const double s0 = wave_sum(step), s1 = wave_sum(xn);
+  const double s0 = wave_sum(step), s1 = wave_sum(xn), s2 = wave_sum(mcc);
   if ((threadIdx.x & 63) == 0) {
     uc_sh[0][threadIdx.x >> 6] = s0;
     uc_sh[1][threadIdx.x >> 6] = s1;
+    uc_sh[2][threadIdx.x >> 6] = s2;
   }
   __syncthreads();
   if (threadIdx.x == 0) {
     const int nb = (int)gridDim.x;
     st_agent(&v.dotbuf[blockIdx.x], uc_sh[0][0] + uc_sh[0][1] + uc_sh[0][2] + uc_sh[0][3]);
     st_agent(&v.dotbuf[nb + blockIdx.x], uc_sh[1][0] + uc_sh[1][1] + uc_sh[1][2] + uc_sh[1][3]);
+    if (want_mcc) st_agent(&v.dotbuf[2 * nb + blockIdx.x], uc_sh[2][0] + uc_sh[2][1] + uc_sh[2][2] + uc_sh[2][3]);
     uc_last = take_ticket(v.ticket + 2 * kTicketStride, nb) ? 1 : 0;
   }
   __syncthreads();
@@ -3500,6 +3612,11 @@ __global__ __launch_bounds__(256) void update_cameras_kernel(DeviceView v, doubl
     }
     out[0] = t0;
     out[1] = t1;
+    if (want_mcc) {
+      double t2 = 0.0;
+      for (int i = 0; i < nb; ++i) t2 += ld_agent(&v.dotbuf[2 * nb + i]);
+      v.scal[SC_MCC] = t2;
+    }
   }
 }
 

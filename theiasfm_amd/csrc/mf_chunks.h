@@ -299,6 +299,13 @@ __device__ __forceinline__ double2 mf_stream_load(const double2* p) {
   return make_double2(t.x, t.y);
 }
 #define MF_STREAM_LOAD(p) mf_stream_load(p)
+// s = sum_i Jp_i^T (A_i x) of track lp -- the w the track solve is about to take -- into plane a of sk ([DP][Np_pad]):
+// written once, read once by back_combine_kernel (kernels.h) after the solve, so it bypasses the caches like the rows
+template <int DP>
+__device__ __forceinline__ void mf_store_sk(double* __restrict__ sk, size_t NP, size_t lp, const double (&s)[DP]) {
+#pragma unroll
+  for (int a = 0; a < DP; ++a) __builtin_nontemporal_store(s[a], sk + (size_t)a * NP + lp);
+}
 // DROP: the position columns of the A planes are not stored (DeviceView::drop_pos); x is then the vector with the position
 // entries of every block already times the block's column scales (pos_scale_kernel), reduce_kernel applies the scales
 // to the position entries of the sums.
@@ -306,8 +313,13 @@ __device__ __forceinline__ double2 mf_stream_load(const double2* p) {
 // [kappa | eta | a0 a1 a2] of every view (compact_forward), the sums are the moments compact_backward maps back
 // (reduce_kernel).  Same units, runs, slots and summation orders as the full planes.
 // (CP == 2: a robust loss -- pm_A holds [C p_n | r^2 .] per observation, 32 bytes)
+// sk (may be null): the product also leaves every track's s = sum_i Jp_i^T (A_i x) in the planes sk[DP][Np_pad] -- the
+// per-track sums back-substitution would otherwise sweep the observations again for (back_combine_kernel, kernels.h).
+// A kernel argument, not a field of View: PCG passes another plane with every product.  A guarded launch that
+// returns at once stores nothing.
 template <int D, int DP, bool DROP, int CP = 0>
-__global__ __launch_bounds__(kThreads, 2) void product_kernel(DeviceView v, View m, const double* __restrict__ x) {
+__global__ __launch_bounds__(kThreads, 2) void product_kernel(DeviceView v, View m, const double* __restrict__ x,
+                                                              double* __restrict__ sk) {
   static_assert(!CP || (DROP && D == 9), "compact planes: the 9-wide PINHOLE block without stored position columns");
   constexpr size_t CPT = CP == 2 ? 256 : 128;  // doubles of a 64-observation tile of the compact pm_A
   constexpr int A0 = DROP ? 3 : 0;  // first stored column of the A planes
@@ -395,6 +407,7 @@ __global__ __launch_bounds__(kThreads, 2) void product_kernel(DeviceView v, View
       }
 #pragma unroll
       for (int a = 0; a < DP; ++a) wv[a] = group_sum(wv[a], ultra ? 2 : 1);
+      if (sk && j0 == 0 && k > 0) mf_store_sk<DP>(sk, (size_t)v.Np_pad, (size_t)lp, wv);  // (every lane holds the sum)
       if (k > 0) {
         double z[DP];
         track_solve<DP>(v, lp, wv, z);
@@ -694,6 +707,8 @@ __global__ __launch_bounds__(kThreads, 2) void product_kernel(DeviceView v, View
 #pragma unroll
           for (int a = 0; a < DP; ++a) wt[a] += (sl >= s_lo && sl < s_hi) ? wp[sl][a] : 0.0;
       }
+      // (the track L^-1 was loaded for, load_linv: slice w of a pack; a cut slice: the first of the L lanes of a track)
+      if (sk && lane < nt) mf_store_sk<DP>(sk, (size_t)v.Np_pad, (size_t)(d0.w + w) * 64 + tl, wt);
       // z = L^-T (L^-1 w)   (Linv planes: sym_idx(a, b), a <= b, holds L^-1(b, a))
 #pragma unroll
       for (int bb = 0; bb < DP; ++bb) {

@@ -919,7 +919,11 @@ class Solver:
             raise EngineError(st, "tmi_ba_solver_operator_info")
         return dict(one_sweep_product=bool(out[0]), position_columns_formed=bool(out[1]), direct_camera_side=bool(out[2]),
                     adaptive=bool(out[3]), implicit=bool(out[4]), break_even=int(out[5]), cluster_handle=bool(out[6]),
-                    compact_planes=bool(out[7] & 1), speculative_linearize=bool(out[7] & 2))
+                    compact_planes=bool(out[7] & 1), speculative_linearize=bool(out[7] & 2),
+                    # back-substitution from the products' per-track sums (TMI_BA_BACKSUB_FROM_PRODUCTS): available to
+                    # this handle / LM iterations of the last solve() that took it instead of the observation sweep
+                    back_substitute_from_products=bool(out[7] & 4),
+                    back_substitute_from_products_iterations=int(out[7]) >> 8)
 
     @property
     def stream(self) -> int:
