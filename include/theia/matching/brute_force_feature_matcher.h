@@ -5,7 +5,8 @@
 // Provided: MatchImagePair (private in the reference, reached there through FeatureMatcher::MatchImages), a batched
 // MatchImagePairs that equals the single calls in order, and the step of FeatureMatcher::MatchImages that turns the
 // matches into pixel correspondences (feature_matcher.cc:170-180).  Not rebuilt: AddImage / MatchImages, the features
-// and matches databases, threading, cascade hashing, and geometric verification -- with
+// and matches databases, threading, and geometric verification (cascade hashing is
+// theia/matching/cascade_hashing_feature_matcher.h) -- with
 // options.perform_geometric_verification the constructor says so once on stderr and the matches come back
 // unverified; BundleAdjustRelativePose (theia/sfm/two_view_match_geometric_verification.h) takes the correspondences.
 #ifndef THEIA_MI355_MATCHING_BRUTE_FORCE_FEATURE_MATCHER_H_

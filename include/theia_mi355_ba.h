@@ -1196,7 +1196,7 @@ int32_t tmi_ba_localize_views(tmi_ba_problem* problem, const tmi_ba_localization
 /* ---- batched BruteForceFeatureMatcher: exact squared-L2 descriptor matching for many image pairs ---
  * reference: BruteForceFeatureMatcher::MatchImagePair (brute_force_feature_matcher.cc:49-117) with IntersectMatches
  * (feature_matcher_utils.cc:48-71) and the defaults of FeatureMatcherOptions (feature_matcher_options.h:45-71).  Not
- * provided: cascade hashing, geometric verification, the databases.  A one-shot call without a tmi_ba_problem; THE
+ * provided: geometric verification, the databases (cascade hashing: tmi_ba_match_features_cascade below).  A one-shot call without a tmi_ba_problem; THE
  * DESCRIPTORS AND DISTANCES ARE fp32 (the one exception to this header's fp64 rule), as the reference's are.
  * Image m owns the descriptor rows image_begin[m] .. image_begin[m + 1] - 1 of `descriptors` [rows x dim, row-major];
  * every image goes to the device once however many pairs name it.  Per pair (image1, image2), N1 and N2 rows:
@@ -1255,6 +1255,80 @@ int32_t tmi_ba_match_features(const tmi_ba_match_options* options, int32_t num_i
                               const int32_t* pair_image2, int64_t match_capacity, int8_t* pair_status,
                               int32_t* pair_num_forward, int64_t* pair_match_begin, int32_t* match_feature1,
                               int32_t* match_feature2, float* match_distance, tmi_ba_match_summary* summary);
+
+/* ---- batched CascadeHashingFeatureMatcher: hashed shortlists, exact distances on eleven columns per row ----
+ * reference: CascadeHasher (cascade_hasher.cc:55-277; Cheng et al., CVPR 2014) and
+ * CascadeHashingFeatureMatcher::MatchImagePair (cascade_hashing_feature_matcher.cc:130-166), the matcher the
+ * reference's applications run by default (--matching_strategy=CASCADE_HASHING).  Not provided: the LRU cache of hashed
+ * images (a call hashes every image once), AddImage(s), geometric verification, the databases.  A one-shot call
+ * without a tmi_ba_problem; descriptors, projections and distances are fp32.  The images, the pairs, the outputs and
+ * the TMI_BA_ERR_CAPACITY protocol are those of tmi_ba_match_features.
+ * `projections` [188 x dim, row-major] is an INPUT (the reference draws it from a clock-seeded generator, so there is
+ * nothing reproducible to restate; theia::CascadeHashingFeatureMatcher draws it from a seed): rows 0..127 are the
+ * primary projection (kHashCodeSize 128), row 128 + 10 g + k is bit k of bucket group g (kNumBucketGroups 6,
+ * kNumBucketBits 10; cascade_hasher.h:52-58).
+ *   1. Mean (:55-62), per image with N >= 1 rows, in fp32: for every dimension k, m = 0; for i = 0 .. N-1 ascending:
+ *      m = m + x[i][k]; then m = m / (float)N.
+ *   2. Projection (:94-117), per row and projection row r, in fp32: t[k] = x[k] - m[k]; acc = 0; for k ascending:
+ *      acc = acc + P[r][k] * t[k] -- every operation rounded on its own (no FMA), subnormals kept.  The bit is acc > 0.
+ *      Code bit j is the bit of row j; the bucket id of group g is the sum over k of bit(128 + 10 g + k) << (9 - k).
+ *      DEVIATION of the kind of step 1 of tmi_ba_match_features: Eigen leaves the summation order of its
+ *      matrix-vector product open; this fixes it.
+ *   3. Candidates of row i of image 1 in image 2 (:206-226): column c is a candidate of group g when
+ *      bucket2[c][g] == bucket1[i][g].  total = the number of (c, g) incidences, duplicates counted.  total <= 10: the
+ *      row has no match (the reference's `<= kNumTopCandidates`).
+ *   4. Shortlist (:228-260): among the UNIQUE candidates the 11 smallest under the total order (Hamming distance of
+ *      the 128-bit codes, first group g in which c is a candidate, column index c), all of them if there are fewer.
+ *      This is exactly the reference's walk over its Hamming bins in insertion order with the buckets filled in
+ *      ascending index: a bin holds its columns in the order they were first met, i.e. by (first group, column), and
+ *      the walk stops once it holds more than ten.  total > 10 implies at least two unique candidates (a column
+ *      counts at most six times), so the reference's partial_sort(begin, begin + 2, end) is always in range.
+ *   5. Exact distances of the shortlisted columns by step 1 of tmi_ba_match_features (the same bits: (b - a)^2 equals
+ *      (a - b)^2); the best and the second best under (distance, then lower column), which is std::pair<float, int>'s
+ *      own operator<.
+ *   6. Ratio test as the reference types it (:180, :268-271, cascade_hashing_feature_matcher.cc:144-145):
+ *      sq = (double)lowes_ratio * (double)lowes_ratio, or 1.0 without use_lowes_ratio; the row is dropped when
+ *      (double)d0 > (double)d1 * sq.  (NOT step 3 of tmi_ba_match_features: `>` against `<`, the square in double.)
+ *   7. Counts and intersection (cascade_hashing_feature_matcher.cc:152-165): steps 4 to 6 of tmi_ba_match_features --
+ *      the forward count against min_num_feature_matches, with keep_only_symmetric_matches the reverse pass and
+ *      IntersectMatches, the count again, the matches in ascending feature1 with the forward d0.
+ *   8. An empty image has no hash and no matches (:144-146, :175-177); its pairs' rows are not counted as skipped.
+ * THE RESULT DOES NOT DEPEND ON THE CHUNKING, the grid, the thread mapping or the physical order of a bucket: steps 1
+ * to 8 leave nothing open.
+ * Test outputs, each may be null: image_hash [rows x 4 uint32: code bit j is bit j % 32 of word j / 32] and
+ * image_bucket_ids [rows x 6 uint16].
+ * summary: distance_evaluations counts the exact distances of step 5 only; candidates_examined the incidences
+ * (`total`) of the rows that were not skipped and rows_skipped the rows that failed step 3, both over every pass that
+ * is computed (the reverse pass whenever keep_only_symmetric_matches is set); kernel_seconds includes the hashing.
+ * TMI_BA_ERR_INVALID_ARGUMENT as for tmi_ba_match_features, and for a null `projections`. */
+typedef struct tmi_ba_cascade_match_options {
+  int32_t use_lowes_ratio;              /* 1                                        */
+  float   lowes_ratio;                  /* 0.8f                                     */
+  int32_t keep_only_symmetric_matches;  /* 1                                        */
+  int32_t min_num_feature_matches;      /* 30                                       */
+  int32_t device;                       /* -1 = the current device                  */
+  int32_t pairs_per_chunk;              /* 0 = from the work-memory budget          */
+} tmi_ba_cascade_match_options;
+void tmi_ba_cascade_match_options_init(tmi_ba_cascade_match_options* options);
+
+typedef struct tmi_ba_cascade_match_summary {
+  int64_t num_matches;           /* over all pairs (the needed match_capacity)                                   */
+  int64_t distance_evaluations;  /* exact distances (step 5)                                                      */
+  int32_t num_pairs_ok;          /* status 0                                                                      */
+  int32_t num_chunks;
+  double  kernel_seconds;        /* the hashing launches plus the chunks' launches, first to last of each        */
+  double  total_seconds;
+  int64_t candidates_examined;   /* candidate incidences of the rows that were not skipped                       */
+  int64_t rows_skipped;          /* rows with total <= 10                                                         */
+} tmi_ba_cascade_match_summary;
+
+int32_t tmi_ba_match_features_cascade(const tmi_ba_cascade_match_options* options, int32_t num_images,
+                                      const int64_t* image_begin, const float* descriptors, int32_t dim,
+                                      const float* projections, int32_t num_pairs, const int32_t* pair_image1,
+                                      const int32_t* pair_image2, int64_t match_capacity, int8_t* pair_status,
+                                      int32_t* pair_num_forward, int64_t* pair_match_begin, int32_t* match_feature1,
+                                      int32_t* match_feature2, float* match_distance, uint32_t* image_hash,
+                                      uint16_t* image_bucket_ids, tmi_ba_cascade_match_summary* summary);
 
 /* ---- batched EstimateUncalibratedRelativePose: eight-point RANSAC for many uncalibrated view pairs -------
  * reference: the UNCALIBRATED branch of EstimateTwoViewInfo (estimate_twoview_info.cc:202-248), which the reference's

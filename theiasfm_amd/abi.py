@@ -614,6 +614,35 @@ class CMatchSummary(C.Structure):
     ]
 
 
+class CCascadeMatchOptions(C.Structure):
+    """tmi_ba_cascade_match_options: the fields and defaults of tmi_ba_match_options."""
+    _fields_ = list(CMatchOptions._fields_)
+
+
+def cascade_match_options(**overrides) -> CCascadeMatchOptions:
+    """The defaults of tmi_ba_cascade_match_options_init."""
+    o = CCascadeMatchOptions()
+    o.use_lowes_ratio = 1
+    o.lowes_ratio = 0.8
+    o.keep_only_symmetric_matches = 1
+    o.min_num_feature_matches = 30
+    o.device = -1
+    o.pairs_per_chunk = 0
+    for k, v in overrides.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
+class CCascadeMatchSummary(C.Structure):
+    """tmi_ba_cascade_match_summary."""
+    _fields_ = list(CMatchSummary._fields_) + [
+        ("candidates_examined", C.c_int64),
+        ("rows_skipped", C.c_int64),
+    ]
+
+
 class CSelectSummary(C.Structure):
     _fields_ = [
         ("num_tracks", C.c_int64),

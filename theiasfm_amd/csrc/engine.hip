@@ -45,6 +45,7 @@
 #include "position_kernels.h"
 #include "localize_kernels.h"
 #include "match_kernels.h"
+#include "cascade_match_kernels.h"
 #include "two_view_ransac_kernels.h"
 #include "two_view_calibrated_kernels.h"
 #include "select_kernels.h"

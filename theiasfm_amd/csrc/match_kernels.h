@@ -193,6 +193,10 @@ __device__ __forceinline__ int match_task_of_row(const MatchTask* __restrict__ t
 }
 
 // Ratio test of every row of the chunk, both directions: pass[row]; the forward rows of a pair are counted.
+// Cascade == false: step 3 of tmi_ba_match_features.  Cascade == true: step 6 of tmi_ba_match_features_cascade, the
+// expression cascade_hasher.cc:268-271 types (ratio_sq is 1.0 without the ratio test; a row that was not skipped has
+// at least two shortlisted columns).
+template <bool Cascade>
 __global__ __launch_bounds__(256) void match_ratio_kernel(const MatchTask* __restrict__ tasks, int num_tasks,
                                                           int num_rows, MatchNn nn, int use_ratio, double ratio_sq,
                                                           unsigned char* __restrict__ pass,
@@ -205,7 +209,11 @@ __global__ __launch_bounds__(256) void match_ratio_kernel(const MatchTask* __res
   // a row that never saw a column that compares (no columns, or every distance NaN) still holds kMatchNoColumn, which
   // fails the upper bound here; match_symmetric_kernel's `back` index relies on pass[row] implying 0 <= bi < n_cols
   bool ok = bi >= 0 && bi < T.n_cols;
-  if (ok && use_ratio) ok = T.n_cols >= 2 && (double)nn.best_d[row] < ratio_sq * (double)nn.second_d[row];
+  if (Cascade) {
+    if (ok) ok = !((double)nn.best_d[row] > (double)nn.second_d[row] * ratio_sq);
+  } else {
+    if (ok && use_ratio) ok = T.n_cols >= 2 && (double)nn.best_d[row] < ratio_sq * (double)nn.second_d[row];
+  }
   pass[row] = ok;
   if (ok && T.forward) atomicAdd(&pair_num_forward[T.pair], 1);
 }

@@ -2567,42 +2567,51 @@ struct PinnedBuffer {
 struct MatchSeconds {
   double seconds;
 };
-}  // namespace
-extern "C" {
 
-int32_t tmi_ba_match_features(const tmi_ba_match_options* M, int32_t num_images, const int64_t* image_begin,
-                              const float* descriptors, int32_t dim, int32_t num_pairs, const int32_t* pair_image1,
-                              const int32_t* pair_image2, int64_t match_capacity, int8_t* pair_status,
-                              int32_t* pair_num_forward, int64_t* pair_match_begin, int32_t* match_feature1,
-                              int32_t* match_feature2, float* match_distance, tmi_ba_match_summary* sum) {
-  if (!M || !sum) return bad_argument("match features: null options or summary");
+// The call the two matchers share.  Cascade == false: tmi_ba_match_features (match_nn_kernel gives every row its
+// neighbour triple).  Cascade == true: tmi_ba_match_features_cascade (the images are hashed once, then
+// cascade_candidates_kernel gives the triple; projections, image_hash and image_bucket_ids are its alone).  The chunk
+// plan, the finish kernels and the read-back are one code.
+template <bool Cascade, class Options, class Summary>
+int32_t match_features_call(const Options* M, int32_t num_images, const int64_t* image_begin, const float* descriptors,
+                            int32_t dim, const float* projections, int32_t num_pairs, const int32_t* pair_image1,
+                            const int32_t* pair_image2, int64_t match_capacity, int8_t* pair_status,
+                            int32_t* pair_num_forward, int64_t* pair_match_begin, int32_t* match_feature1,
+                            int32_t* match_feature2, float* match_distance, uint32_t* image_hash,
+                            uint16_t* image_bucket_ids, Summary* sum) {
+  const std::string what = Cascade ? "cascade match features" : "match features";
+  auto bad = [&](const char* why) { return bad_argument((what + ": " + why).c_str()); };
+  if (!M || !sum) return bad("null options or summary");
   memset(sum, 0, sizeof(*sum));
   const double t0 = now_s();
   // argument errors before the device is looked for
-  if (num_images < 0 || num_pairs < 0 || match_capacity < 0) return bad_argument("match features: negative count");
-  if (dim < 1) return bad_argument("match features: dim < 1");
-  if (!image_begin) return bad_argument("match features: missing image_begin");
+  if (num_images < 0 || num_pairs < 0 || match_capacity < 0) return bad("negative count");
+  if (dim < 1) return bad("dim < 1");
+  if (!image_begin) return bad("missing image_begin");
   if (M->min_num_feature_matches < 0 || M->pairs_per_chunk < 0)
-    return bad_argument("match features: negative min_num_feature_matches or pairs_per_chunk");
-  if (image_begin[0] != 0) return bad_argument("match features: image_begin must start at 0");
+    return bad("negative min_num_feature_matches or pairs_per_chunk");
+  if (Cascade && !projections) return bad("missing projections");
+  if (image_begin[0] != 0) return bad("image_begin must start at 0");
   for (int m = 0; m < num_images; ++m) {
-    if (image_begin[m + 1] < image_begin[m]) return bad_argument("match features: image_begin decreases");
-    if (image_begin[m + 1] - image_begin[m] >= 0x7fffffffLL) return bad_argument("match features: an image of 2^31 rows");
+    if (image_begin[m + 1] < image_begin[m]) return bad("image_begin decreases");
+    if (image_begin[m + 1] - image_begin[m] >= 0x7fffffffLL) return bad("an image of 2^31 rows");
   }
   const int64_t total_rows = image_begin[num_images];
-  if (total_rows && !descriptors) return bad_argument("match features: missing descriptors");
+  if (total_rows && !descriptors) return bad("missing descriptors");
   if (num_pairs && (!pair_image1 || !pair_image2 || !pair_status || !pair_num_forward))
-    return bad_argument("match features: missing pair array");
-  if (!pair_match_begin) return bad_argument("match features: missing pair_match_begin");
+    return bad("missing pair array");
+  if (!pair_match_begin) return bad("missing pair_match_begin");
   if (match_capacity && (!match_feature1 || !match_feature2 || !match_distance))
-    return bad_argument("match features: missing match array");
+    return bad("missing match array");
   for (int p = 0; p < num_pairs; ++p)
     if (pair_image1[p] < 0 || pair_image1[p] >= num_images || pair_image2[p] < 0 || pair_image2[p] >= num_images)
-      return bad_argument("match features: image index out of range");
+      return bad("image index out of range");
   const bool symmetric = M->keep_only_symmetric_matches != 0;
   const int min_matches = M->min_num_feature_matches;
   const float ratio_f = M->lowes_ratio * M->lowes_ratio;  // formed in fp32 (brute_force_feature_matcher.cc:58-59)
-  const double ratio_sq = (double)ratio_f;
+  // cascade: formed in double, 1.0 without the ratio test (cascade_hasher.cc:180, cascade_hashing_feature_matcher.cc:144)
+  const double ratio_sq = !Cascade ? (double)ratio_f
+                          : M->use_lowes_ratio ? (double)M->lowes_ratio * (double)M->lowes_ratio : 1.0;
   // the chunks of consecutive pairs
   auto rows_of = [&](int p) -> long long {
     const long long n1 = image_begin[pair_image1[p] + 1] - image_begin[pair_image1[p]];
@@ -2618,7 +2627,7 @@ int32_t tmi_ba_match_features(const tmi_ba_match_options* M, int32_t num_images,
     while (q < num_pairs) {
       const long long r = rows_of(q);
       if (r > kMatchMaxChunkRows) {
-        g_last_error = "match features: a pair with more than 2^31 rows over its directions";
+        g_last_error = what + ": a pair with more than 2^31 rows over its directions";
         return TMI_BA_ERR_UNSUPPORTED;
       }
       if (q > p) {
@@ -2633,17 +2642,67 @@ int32_t tmi_ba_match_features(const tmi_ba_match_options* M, int32_t num_images,
     chunk_begin.push_back(q);
     p = q;
   }
-  for (int p = 0; p < num_pairs; ++p) {
-    const long long n1 = image_begin[pair_image1[p] + 1] - image_begin[pair_image1[p]];
-    const long long n2 = image_begin[pair_image2[p] + 1] - image_begin[pair_image2[p]];
-    sum->distance_evaluations += n1 * n2 * (symmetric ? 2 : 1);
-  }
+  if constexpr (!Cascade)
+    for (int p = 0; p < num_pairs; ++p) {
+      const long long n1 = image_begin[pair_image1[p] + 1] - image_begin[pair_image1[p]];
+      const long long n2 = image_begin[pair_image2[p] + 1] - image_begin[pair_image2[p]];
+      sum->distance_evaluations += n1 * n2 * (symmetric ? 2 : 1);
+    }
   pair_match_begin[0] = 0;
   MatchSeconds secs = {0.0};
-  const int rc = one_shot_batch(M->device, "match features: no such device", num_pairs, t0, &secs, [&](OneShot* s) -> int {
+  const std::string no_device = what + ": no such device";
+  const int rc = one_shot_batch(M->device, no_device.c_str(), num_pairs, t0, &secs, [&](OneShot* s) -> int {
     const hipStream_t stream = s->stream;
     float* d_desc;
     TMI_HIP(s->upload(&d_desc, descriptors, (size_t)total_rows * (size_t)dim));
+    // cascade: every image is hashed once, however many pairs name it
+    CascadeRecord* d_rec = nullptr;
+    int *d_bucket_begin = nullptr, *d_bucket_rows = nullptr, *d_task_image = nullptr;
+    unsigned long long* d_counters = nullptr;
+    std::vector<int> task_image;
+    if constexpr (Cascade) {
+      float *d_proj, *d_mean;
+      long long* d_image_begin;
+      int2* d_hash_blocks;
+      std::vector<long long> begin_h(image_begin, image_begin + num_images + 1);
+      std::vector<int2> hash_blocks;
+      for (int m = 0; m < num_images; ++m)
+        for (long long r = 0; r * kCascadeHashRows < begin_h[m + 1] - begin_h[m]; ++r) hash_blocks.push_back(make_int2(m, (int)r));
+      TMI_HIP(s->upload(&d_proj, projections, (size_t)kCascadeProjRows * (size_t)dim));
+      TMI_HIP(s->upload(&d_image_begin, begin_h.data(), begin_h.size()));
+      TMI_HIP(s->upload(&d_hash_blocks, hash_blocks.data(), hash_blocks.size()));
+      TMI_HIP(s->alloc(&d_mean, (size_t)num_images * (size_t)dim));
+      TMI_HIP(s->alloc(&d_rec, (size_t)total_rows));
+      TMI_HIP(s->alloc(&d_bucket_begin, (size_t)num_images * kCascadeGroups * (kCascadeBuckets + 1)));
+      TMI_HIP(s->alloc(&d_bucket_rows, (size_t)kCascadeGroups * (size_t)total_rows));
+      TMI_HIP(s->alloc(&d_task_image, 2 * (size_t)max_pairs));
+      TMI_HIP(s->alloc(&d_counters, 4 * (size_t)kCascadeCounterShards));
+      TMI_HIP(hipMemsetAsync(d_counters, 0, 4 * (size_t)kCascadeCounterShards * sizeof(unsigned long long), stream));
+      StreamTimer timer(stream);
+      TMI_HIP(timer.status);
+      TMI_HIP(timer.mark());
+      if (num_images) {
+        const long long cells = (long long)num_images * dim;
+        hipLaunchKernelGGL(cascade_mean_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, d_desc, (int)dim,
+                           d_image_begin, (int)num_images, d_mean);
+        if (!hash_blocks.empty())
+          hipLaunchKernelGGL(cascade_hash_kernel, dim3((unsigned)hash_blocks.size()), dim3(256), 0, stream, d_desc, (int)dim,
+                             d_proj, d_mean, d_image_begin, d_hash_blocks, d_rec);
+        hipLaunchKernelGGL(cascade_bucket_kernel, dim3((unsigned)num_images * kCascadeGroups), dim3(256), 0, stream, d_rec,
+                           d_image_begin, d_bucket_begin, d_bucket_rows);
+      }
+      TMI_HIP(timer.mark());
+      TMI_HIP(hipGetLastError());
+      std::vector<CascadeRecord> rec_h((image_hash || image_bucket_ids) ? (size_t)total_rows : 0);
+      if (!rec_h.empty())
+        TMI_HIP(hipMemcpyAsync(rec_h.data(), d_rec, rec_h.size() * sizeof(CascadeRecord), hipMemcpyDeviceToHost, stream));
+      TMI_HIP(hipStreamSynchronize(stream));  // (also: begin_h and hash_blocks are free to go)
+      sum->kernel_seconds += timer.seconds();
+      for (size_t r = 0; r < rec_h.size(); ++r) {
+        if (image_hash) std::copy(rec_h[r].code, rec_h[r].code + 4, image_hash + 4 * r);
+        if (image_bucket_ids) std::copy(rec_h[r].ids, rec_h[r].ids + kCascadeGroups, image_bucket_ids + kCascadeGroups * r);
+      }
+    }
     const size_t R = (size_t)max_rows;
     MatchNn nn;
     MatchTask* d_tasks;
@@ -2684,6 +2743,7 @@ int32_t tmi_ba_match_features(const tmi_ba_match_options* M, int32_t num_images,
       tasks.clear();
       blocks.clear();
       fwd_task.clear();
+      task_image.clear();
       long long rows = 0;
       for (int p = 0; p < np; ++p) {
         const int i1 = pair_image1[p0 + p], i2 = pair_image2[p0 + p];
@@ -2691,23 +2751,28 @@ int32_t tmi_ba_match_features(const tmi_ba_match_options* M, int32_t num_images,
         MatchTask f = {image_begin[i1], image_begin[i2], n1, n2, (int)rows, p, 1, symmetric ? (int)(rows + n1) : -1};
         fwd_task.push_back((int)tasks.size());
         tasks.push_back(f);
+        task_image.push_back(i2);  // the image whose buckets the task's rows look into
         rows += n1;
         if (symmetric) {
           MatchTask r = {image_begin[i2], image_begin[i1], n2, n1, (int)rows, p, 0, f.out_base};
           tasks.push_back(r);
+          task_image.push_back(i1);
           rows += n2;
         }
       }
-      for (size_t t = 0; t < tasks.size(); ++t)
-        for (int b = 0; b * kMatchTile < tasks[t].n_rows; ++b) blocks.push_back(make_int2((int)t, b));
+      if constexpr (!Cascade)
+        for (size_t t = 0; t < tasks.size(); ++t)
+          for (int b = 0; b * kMatchTile < tasks[t].n_rows; ++b) blocks.push_back(make_int2((int)t, b));
       const int num_rows = (int)rows, num_tasks = (int)tasks.size();
       if (blocks.size() > max_blocks || (size_t)num_rows > R) {  // (the plan above bounds both)
-        s->error = "match features: chunk plan exceeded";
+        s->error = what + ": chunk plan exceeded";
         return TMI_BA_ERR_DEVICE;
       }
       TMI_HIP(hipMemcpyAsync(d_tasks, tasks.data(), tasks.size() * sizeof(MatchTask), hipMemcpyHostToDevice, stream));
       if (!blocks.empty())
         TMI_HIP(hipMemcpyAsync(d_blocks, blocks.data(), blocks.size() * sizeof(int2), hipMemcpyHostToDevice, stream));
+      if constexpr (Cascade)
+        TMI_HIP(hipMemcpyAsync(d_task_image, task_image.data(), task_image.size() * sizeof(int), hipMemcpyHostToDevice, stream));
       TMI_HIP(hipMemcpyAsync(d_fwd_task, fwd_task.data(), fwd_task.size() * sizeof(int), hipMemcpyHostToDevice, stream));
       TMI_HIP(hipMemsetAsync(d_pair_counts, 0, 2 * (size_t)np * sizeof(int), stream));
       int* d_num_forward = d_pair_counts;
@@ -2716,7 +2781,12 @@ int32_t tmi_ba_match_features(const tmi_ba_match_options* M, int32_t num_images,
       TMI_HIP(timer.status);
       TMI_HIP(timer.mark());
       const unsigned row_grid = (unsigned)((num_rows + 255) / 256);
-      if (!blocks.empty()) {
+      if constexpr (Cascade) {
+        if (num_rows)
+          hipLaunchKernelGGL(cascade_candidates_kernel, dim3((unsigned)((num_rows + 3) / 4)), dim3(256), 0, stream, d_desc,
+                             (int)dim, d_tasks, d_task_image, num_tasks, num_rows, d_rec, d_bucket_begin, d_bucket_rows, nn,
+                             d_counters);
+      } else if (!blocks.empty()) {
         if (staged)
           hipLaunchKernelGGL(match_nn_kernel<true>, dim3((unsigned)blocks.size()), dim3(256), lds, stream, d_desc, (int)dim,
                              d_tasks, d_blocks, nn);
@@ -2725,7 +2795,7 @@ int32_t tmi_ba_match_features(const tmi_ba_match_options* M, int32_t num_images,
                              d_tasks, d_blocks, nn);
       }
       if (num_rows) {
-        hipLaunchKernelGGL(match_ratio_kernel, dim3(row_grid), dim3(256), 0, stream, d_tasks, num_tasks, num_rows, nn,
+        hipLaunchKernelGGL(match_ratio_kernel<Cascade>, dim3(row_grid), dim3(256), 0, stream, d_tasks, num_tasks, num_rows, nn,
                            (int)(M->use_lowes_ratio != 0), ratio_sq, d_pass, d_num_forward);
         hipLaunchKernelGGL(match_symmetric_kernel, dim3(row_grid), dim3(256), 0, stream, d_tasks, num_tasks, num_rows, nn,
                            d_pass, d_num_forward, (int)symmetric, min_matches, d_keep, d_num_kept);
@@ -2746,7 +2816,7 @@ int32_t tmi_ba_match_features(const tmi_ba_match_options* M, int32_t num_images,
       sum->kernel_seconds += timer.seconds();
       const int chunk_total = h_counts[4 * np];
       if (chunk_total < 0 || chunk_total > num_rows) {
-        s->error = "match features: the device reported an impossible match count";
+        s->error = what + ": the device reported an impossible match count";
         return TMI_BA_ERR_DEVICE;
       }
       for (int p = 0; p < np; ++p) {
@@ -2771,14 +2841,60 @@ int32_t tmi_ba_match_features(const tmi_ba_match_options* M, int32_t num_images,
       sum->num_chunks++;
     }
     sum->num_matches = total;
+    if constexpr (Cascade) {
+      unsigned long long counters_h[4 * kCascadeCounterShards];
+      TMI_HIP(hipMemcpyAsync(counters_h, d_counters, sizeof(counters_h), hipMemcpyDeviceToHost, stream));
+      TMI_HIP(hipStreamSynchronize(stream));
+      for (int i = 0; i < kCascadeCounterShards; ++i) {
+        sum->candidates_examined += (int64_t)counters_h[4 * i];
+        sum->distance_evaluations += (int64_t)counters_h[4 * i + 1];
+        sum->rows_skipped += (int64_t)counters_h[4 * i + 2];
+      }
+    }
     return TMI_BA_OK;
   });
   sum->total_seconds = now_s() - t0;
   if (rc == TMI_BA_OK && sum->num_matches > match_capacity) {
-    g_last_error = "match features: match_capacity is smaller than the number of matches (summary->num_matches)";
+    g_last_error = what + ": match_capacity is smaller than the number of matches (summary->num_matches)";
     return TMI_BA_ERR_CAPACITY;
   }
   return rc;
+}
+}  // namespace
+extern "C" {
+
+int32_t tmi_ba_match_features(const tmi_ba_match_options* M, int32_t num_images, const int64_t* image_begin,
+                              const float* descriptors, int32_t dim, int32_t num_pairs, const int32_t* pair_image1,
+                              const int32_t* pair_image2, int64_t match_capacity, int8_t* pair_status,
+                              int32_t* pair_num_forward, int64_t* pair_match_begin, int32_t* match_feature1,
+                              int32_t* match_feature2, float* match_distance, tmi_ba_match_summary* sum) {
+  return match_features_call<false>(M, num_images, image_begin, descriptors, dim, nullptr, num_pairs, pair_image1,
+                                    pair_image2, match_capacity, pair_status, pair_num_forward, pair_match_begin,
+                                    match_feature1, match_feature2, match_distance, nullptr, nullptr, sum);
+}
+
+// ---- batched CascadeHashingFeatureMatcher (cascade_match_kernels.h) ----------------------------
+void tmi_ba_cascade_match_options_init(tmi_ba_cascade_match_options* o) {
+  if (!o) return;
+  o->use_lowes_ratio = 1;  // feature_matcher_options.h:45-71
+  o->lowes_ratio = 0.8f;
+  o->keep_only_symmetric_matches = 1;
+  o->min_num_feature_matches = 30;
+  o->device = -1;
+  o->pairs_per_chunk = 0;
+}
+
+int32_t tmi_ba_match_features_cascade(const tmi_ba_cascade_match_options* options, int32_t num_images,
+                                      const int64_t* image_begin, const float* descriptors, int32_t dim,
+                                      const float* projections, int32_t num_pairs, const int32_t* pair_image1,
+                                      const int32_t* pair_image2, int64_t match_capacity, int8_t* pair_status,
+                                      int32_t* pair_num_forward, int64_t* pair_match_begin, int32_t* match_feature1,
+                                      int32_t* match_feature2, float* match_distance, uint32_t* image_hash,
+                                      uint16_t* image_bucket_ids, tmi_ba_cascade_match_summary* summary) {
+  return match_features_call<true>(options, num_images, image_begin, descriptors, dim, projections, num_pairs,
+                                   pair_image1, pair_image2, match_capacity, pair_status, pair_num_forward,
+                                   pair_match_begin, match_feature1, match_feature2, match_distance, image_hash,
+                                   image_bucket_ids, summary);
 }
 }  // extern "C"
 

@@ -40,6 +40,7 @@ EXPORTS = (
     "tmi_ba_lud_position_options_init", "tmi_ba_estimate_global_positions_lud",
     "tmi_ba_localization_options_init", "tmi_ba_localize_views",
     "tmi_ba_match_options_init", "tmi_ba_match_features",
+    "tmi_ba_cascade_match_options_init", "tmi_ba_match_features_cascade",
     "tmi_ba_two_view_ransac_options_init", "tmi_ba_estimate_uncalibrated_relative_poses",
     "tmi_ba_estimate_calibrated_relative_poses",
     "tmi_ba_solver_structure_checksums",
@@ -193,6 +194,13 @@ def load():
     L.tmi_ba_match_features.argtypes = [MO, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                         C.c_void_p, C.c_int64] + [C.c_void_p] * 6 + [C.POINTER(abi.CMatchSummary)]
     L.tmi_ba_match_features.restype = C.c_int32
+    KO = C.POINTER(abi.CCascadeMatchOptions)
+    L.tmi_ba_cascade_match_options_init.argtypes = [KO]
+    L.tmi_ba_cascade_match_options_init.restype = None
+    L.tmi_ba_match_features_cascade.argtypes = [KO, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                                C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 8 + [
+        C.POINTER(abi.CCascadeMatchSummary)]
+    L.tmi_ba_match_features_cascade.restype = C.c_int32
     RO = C.POINTER(abi.CTwoViewRansacOptions)
     L.tmi_ba_two_view_ransac_options_init.argtypes = [RO]
     L.tmi_ba_two_view_ransac_options_init.restype = None
@@ -591,17 +599,11 @@ def localize_views(problem: abi.Problem, view_error_threshold, options=None, ba_
                 summary=zs)
 
 
-def match_features(image_begin, descriptors, pair_image1, pair_image2, options=None, match_capacity=None):
-    """Batched BruteForceFeatureMatcher (exact fp32 squared-L2 matching, ratio test, symmetric intersection) over the
-    image pairs (pair_image1[p], pair_image2[p]).  image_begin [num_images + 1] int64 row offsets into descriptors
-    [rows, dim] float32.  match_capacity: None sizes the match arrays for the most the options allow (the rows of
-    image 1 over the pairs); a number is passed through, and a capacity that is too small comes back as `status` ==
-    abi.ERR_CAPACITY with the per-pair arrays filled and summary.num_matches the needed total.
-    Returns a dict: status (the call's), pair_status [P] int8, pair_num_forward [P] int32, pair_match_begin [P + 1]
-    int64, feature1 / feature2 [total] int32, distance [total] float32, summary (CMatchSummary).  Raises EngineError
-    on any other failure."""
+def _match_call(entry, summary_type, default_options, image_begin, descriptors, projections, pair_image1, pair_image2,
+                options, match_capacity, want_hash):
+    """The wrapper tmi_ba_match_features and tmi_ba_match_features_cascade share (projections is None for the first)."""
     L = load()
-    o = options if options is not None else abi.match_options()
+    o = options if options is not None else default_options()
     ib = np.ascontiguousarray(image_begin, dtype=np.int64)
     desc = np.ascontiguousarray(descriptors, dtype=np.float32)
     if ib.ndim != 1 or ib.shape[0] < 1:
@@ -627,15 +629,54 @@ def match_features(image_begin, descriptors, pair_image1, pair_image2, options=N
     f1 = np.zeros(max(cap, 0), dtype=np.int32)
     f2 = np.zeros(max(cap, 0), dtype=np.int32)
     dist = np.zeros(max(cap, 0), dtype=np.float32)
-    ms = abi.CMatchSummary()
-    st = L.tmi_ba_match_features(C.byref(o), num_images, ib.ctypes.data, desc.ctypes.data, desc.shape[1], num_pairs,
-                                 p1.ctypes.data, p2.ctypes.data, cap, status.ctypes.data, nfwd.ctypes.data,
-                                 begin.ctypes.data, f1.ctypes.data, f2.ctypes.data, dist.ctypes.data, C.byref(ms))
+    ms = summary_type()
+    extra = {}
+    if projections is None:
+        st = L.tmi_ba_match_features(C.byref(o), num_images, ib.ctypes.data, desc.ctypes.data, desc.shape[1], num_pairs,
+                                     p1.ctypes.data, p2.ctypes.data, cap, status.ctypes.data, nfwd.ctypes.data,
+                                     begin.ctypes.data, f1.ctypes.data, f2.ctypes.data, dist.ctypes.data, C.byref(ms))
+    else:
+        proj = np.ascontiguousarray(projections, dtype=np.float32)
+        if proj.shape != (188, desc.shape[1]):
+            raise ValueError("projections must be [188, dim]")
+        code = np.zeros((desc.shape[0], 4), dtype=np.uint32) if want_hash else None
+        ids = np.zeros((desc.shape[0], 6), dtype=np.uint16) if want_hash else None
+        st = L.tmi_ba_match_features_cascade(
+            C.byref(o), num_images, ib.ctypes.data, desc.ctypes.data, desc.shape[1], proj.ctypes.data, num_pairs,
+            p1.ctypes.data, p2.ctypes.data, cap, status.ctypes.data, nfwd.ctypes.data, begin.ctypes.data, f1.ctypes.data,
+            f2.ctypes.data, dist.ctypes.data, code.ctypes.data if want_hash else None,
+            ids.ctypes.data if want_hash else None, C.byref(ms))
+        extra = dict(image_hash=code, image_bucket_ids=ids)
     if st not in (0, abi.ERR_CAPACITY):
-        raise EngineError(st, "tmi_ba_match_features")
+        raise EngineError(st, entry)
     n = 0 if st else int(begin[-1])
     return dict(status=st, pair_status=status, pair_num_forward=nfwd, pair_match_begin=begin, feature1=f1[:n],
-                feature2=f2[:n], distance=dist[:n], summary=ms)
+                feature2=f2[:n], distance=dist[:n], summary=ms, **extra)
+
+
+def match_features(image_begin, descriptors, pair_image1, pair_image2, options=None, match_capacity=None):
+    """Batched BruteForceFeatureMatcher (exact fp32 squared-L2 matching, ratio test, symmetric intersection) over the
+    image pairs (pair_image1[p], pair_image2[p]).  image_begin [num_images + 1] int64 row offsets into descriptors
+    [rows, dim] float32.  match_capacity: None sizes the match arrays for the most the options allow (the rows of
+    image 1 over the pairs); a number is passed through, and a capacity that is too small comes back as `status` ==
+    abi.ERR_CAPACITY with the per-pair arrays filled and summary.num_matches the needed total.
+    Returns a dict: status (the call's), pair_status [P] int8, pair_num_forward [P] int32, pair_match_begin [P + 1]
+    int64, feature1 / feature2 [total] int32, distance [total] float32, summary (CMatchSummary).  Raises EngineError
+    on any other failure."""
+    return _match_call("tmi_ba_match_features", abi.CMatchSummary, abi.match_options, image_begin, descriptors, None,
+                       pair_image1, pair_image2, options, match_capacity, False)
+
+
+def match_features_cascade(image_begin, descriptors, projections, pair_image1, pair_image2, options=None,
+                           match_capacity=None, want_hash=False):
+    """Batched CascadeHashingFeatureMatcher (tmi_ba_match_features_cascade): the arguments and the returned dict of
+    match_features, plus projections [188, dim] float32 (rows 0..127 the primary projection, row 128 + 10 g + k bit k
+    of bucket group g; synth.cascade_projections draws them) and options from abi.cascade_match_options().
+    want_hash adds image_hash [rows, 4] uint32 and image_bucket_ids [rows, 6] uint16 (None otherwise).  summary is a
+    CCascadeMatchSummary."""
+    return _match_call("tmi_ba_match_features_cascade", abi.CCascadeMatchSummary, abi.cascade_match_options,
+                       image_begin, descriptors, projections, pair_image1, pair_image2, options, match_capacity,
+                       bool(want_hash))
 
 
 def estimate_uncalibrated_relative_poses(pair_offset, feature1, feature2, pair_error_threshold, options=None,

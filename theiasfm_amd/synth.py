@@ -829,6 +829,54 @@ def make_matching_batch(num_images: int, num_descriptors, dim: int, seed: int, *
     return begin, np.ascontiguousarray(desc, dtype=np.float32), {"duplicate_rows": dups, "tie_rows": ties}
 
 
+def _mt19937_normals(seed: int, count: int) -> np.ndarray:
+    """count draws of std::normal_distribution<double>(0, 1), a FRESH distribution per draw, from std::mt19937(seed),
+    as libstdc++ computes them: the Marsaglia polar method on x = 2 u - 1 with u = generate_canonical<double, 53> (two
+    32-bit words, low word first), returning y * sqrt(-2 log(r2) / r2) of the pair's SECOND coordinate and dropping
+    the saved one with the distribution."""
+    bits = np.random.MT19937()
+    state = bits.state
+    key = np.zeros(624, dtype=np.uint32)
+    key[0] = seed & 0xFFFFFFFF
+    for i in range(1, 624):
+        key[i] = (1812433253 * (int(key[i - 1]) ^ (int(key[i - 1]) >> 30)) + i) & 0xFFFFFFFF
+    state["state"]["key"] = key
+    state["state"]["pos"] = 624
+    bits.state = state
+    out = np.empty(count, dtype=np.float64)
+
+    def canonical():
+        lo = int(bits.random_raw())
+        hi = int(bits.random_raw())
+        r = (lo + hi * 4294967296.0) / 18446744073709551616.0
+        return r if r < 1.0 else float(np.nextafter(1.0, 0.0))
+
+    for i in range(count):
+        while True:
+            x = 2.0 * canonical() - 1.0
+            y = 2.0 * canonical() - 1.0
+            r2 = x * x + y * y
+            if not (r2 > 1.0 or r2 == 0.0):
+                break
+        out[i] = y * np.sqrt(-2.0 * np.log(r2) / r2)
+    return out
+
+
+CASCADE_DEFAULT_SEED = 20140623  # theia::CascadeHashingFeatureMatcher's default seed
+
+
+def cascade_projections(dim: int, seed: int = CASCADE_DEFAULT_SEED, *, zero_secondary: bool = False) -> np.ndarray:
+    """The projections of tmi_ba_match_features_cascade, [188, dim] float32, as theia::CascadeHashingFeatureMatcher
+    draws them from `seed`: std::mt19937(seed), a fresh std::normal_distribution<double>(0, 1) per draw cast to float,
+    the primary projection's 128 rows first, then bit k of group g at row 128 + 10 g + k, each row in ascending
+    dimension (CascadeHasher::Initialize).  zero_secondary: rows 128.. are all zero, so that every row of every image
+    falls into bucket 0 of every group (a test input)."""
+    p = _mt19937_normals(int(seed), 188 * int(dim)).astype(np.float32).reshape(188, int(dim))
+    if zero_secondary:
+        p[128:] = 0.0
+    return np.ascontiguousarray(p)
+
+
 def make_uncalibrated_pair_batch(num_pairs: int, num_correspondences, seed: int, *, inlier_ratio=1.0, pixel_noise=0.5,
                                  focal_range=(800.0, 1600.0), image_half_size=(512.0, 384.0), parallel_axes=()):
     """View pairs for tmi_ba_estimate_uncalibrated_relative_poses: two pinhole views with DIFFERENT focal lengths drawn
