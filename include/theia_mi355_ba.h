@@ -1330,6 +1330,79 @@ int32_t tmi_ba_match_features_cascade(const tmi_ba_cascade_match_options* option
                                       int32_t* match_feature2, float* match_distance, uint32_t* image_hash,
                                       uint16_t* image_bucket_ids, tmi_ba_cascade_match_summary* summary);
 
+/* ---- TrackBuilder: the tracks of a reconstruction from the verified matches of all view pairs, by union-find ----
+ * reference: TrackBuilder (track_builder.cc:53-151) on ConnectedComponents<uint64_t> (connected_components.h:87-162),
+ * driven from reconstruction_builder.cc:173,358,432-439 with the defaults of reconstruction_builder.h:81-85
+ * (min_track_length 2, max_track_length 50).  Not provided: ViewGraph components, ReconstructionBuilder, the feature
+ * and match databases, a resident form, coordinates as keys (theia::TrackBuilder owns the Feature-to-index map).  A
+ * one-shot call without a tmi_ba_problem, all integers.
+ * Input: E = num_edges correspondences; edge e joins the endpoints 2e and 2e + 1 of endpoint_view / endpoint_feature
+ * [2E].  endpoint_feature is a feature index LOCAL TO ITS VIEW: the same index in two views names two features.
+ *   1. Nodes (track_builder.cc:70-74, :133-151).  A node is a distinct (view, feature); its id is the rank of its first
+ *      appearance among the 2E endpoints in ascending endpoint index -- the order of the reference's FindOrInsert ids.
+ *   2. The components of the unconstrained graph: the partition union-find gives with no size cap.
+ *   3. The cap (connected_components.h:87-108).  A component of at most max_track_length nodes is one set: the
+ *      reference's loop never refuses a merge inside it, because the sizes of two of its parts sum to at most its
+ *      size.  A larger component is REPLAYED: its edges in ascending edge index; an edge finds both roots and is skipped
+ *      when they are equal or size1 + size2 > max_track_length (:94-97), otherwise the sets are united.  Only the
+ *      partition matters, not which root survives (:101-107).  Components never interact in the reference's loop (a
+ *      root's size and id change only by edges of its own component), so the replay per component gives exactly the
+ *      reference's partition for its edge order.
+ *   4. Labels and small sets.  A set's label is its smallest node id.  A set of fewer than min_track_length nodes is
+ *      dropped and counted in num_small_tracks, before step 5 as in the reference (track_builder.cc:98).  DEVIATION: a
+ *      set of one node is always dropped (and counted): with min_track_length <= 1 the reference reaches AddTrack with
+ *      one observation and aborts (:121).
+ *   5. Consistency (:107-119).  Among the nodes of an emitted set with the same view the lowest node id is kept, the
+ *      others are counted in num_inconsistent_features.  DEVIATION: the reference keeps whichever its unordered_set
+ *      iterates first.
+ *   6. Output: the tracks in ascending label, a track's observations in ascending node id, as a CSR: track_begin
+ *      [num_tracks + 1], obs_view / obs_feature [num_observations].  DEVIATION: the reference's order is its
+ *      unordered_map's.
+ * THE RESULT DOES NOT DEPEND ON HOW THE DEVICE IS DRIVEN: steps 1 to 6 leave nothing open, so whatever the grid, the
+ * arrival order of atomics or any chunking, the outputs are the same bytes.
+ * Capacity, the protocol of tmi_ba_match_features: track_begin has room for track_capacity + 1 entries, obs_view and
+ * obs_feature for obs_capacity.  With either too small the call returns TMI_BA_ERR_CAPACITY, writes none of the three
+ * and leaves the needed totals in summary->num_tracks and summary->num_observations (every other summary field and
+ * the two test outputs are filled as well).
+ * Test outputs, each may be null: endpoint_node [2E], the node id of every endpoint, and endpoint_label [2E], the label
+ * of its final set, whether that set was emitted or dropped.
+ * summary: num_sets = num_tracks + num_small_tracks; num_replayed_edges the edges of the oversize components;
+ * kernel_seconds the device time of the four phases, phase_seconds: nodes / components / cap / output, each from a pair
+ * of events around launches that are queued anyway.
+ * TMI_BA_ERR_INVALID_ARGUMENT, before the device is looked for and with every output untouched: null options or
+ * summary, a missing array (endpoint_view / endpoint_feature when E > 0, track_begin, obs_view / obs_feature when
+ * obs_capacity > 0), a negative count, E >= 2^30, max_track_length < 1 (the reference's CHECK_GT,
+ * connected_components.h:77), min_track_length < 1, an edge whose two endpoints have the same view (the reference's
+ * CHECK_NE, track_builder.cc:66).  E = 0: TMI_BA_OK, zero tracks, track_begin[0] = 0.  Without a device:
+ * TMI_BA_ERR_NO_DEVICE.  A loop bound reached on the device (never, by the argument in track_build_kernels.h):
+ * TMI_BA_ERR_DEVICE. */
+typedef struct tmi_ba_track_build_options {
+  int32_t min_track_length;  /* 2                          */
+  int32_t max_track_length;  /* 50                         */
+  int32_t device;            /* -1 = the current device    */
+} tmi_ba_track_build_options;
+void tmi_ba_track_build_options_init(tmi_ba_track_build_options* options);
+
+typedef struct tmi_ba_track_build_summary {
+  int64_t num_nodes;
+  int64_t num_components;
+  int64_t num_oversize_components;
+  int64_t num_replayed_edges;
+  int64_t num_sets;
+  int64_t num_tracks;                 /* the needed track_capacity */
+  int64_t num_observations;           /* the needed obs_capacity   */
+  int64_t num_small_tracks;
+  int64_t num_inconsistent_features;
+  double  seconds;
+  double  kernel_seconds;
+  double  phase_seconds[4];           /* nodes, components, cap, output */
+} tmi_ba_track_build_summary;
+
+int32_t tmi_ba_build_tracks(const tmi_ba_track_build_options* options, int64_t num_edges,
+                            const uint32_t* endpoint_view, const uint32_t* endpoint_feature, int64_t track_capacity,
+                            int64_t obs_capacity, int64_t* track_begin, uint32_t* obs_view, uint32_t* obs_feature,
+                            uint32_t* endpoint_node, uint32_t* endpoint_label, tmi_ba_track_build_summary* summary);
+
 /* ---- batched EstimateUncalibratedRelativePose: eight-point RANSAC for many uncalibrated view pairs -------
  * reference: the UNCALIBRATED branch of EstimateTwoViewInfo (estimate_twoview_info.cc:202-248), which the reference's
  * application runs for every view without an EXIF focal length: EstimateUncalibratedRelativePose with

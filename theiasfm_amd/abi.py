@@ -643,6 +643,46 @@ class CCascadeMatchSummary(C.Structure):
     ]
 
 
+class CTrackBuildOptions(C.Structure):
+    """tmi_ba_track_build_options."""
+    _fields_ = [
+        ("min_track_length", C.c_int32),
+        ("max_track_length", C.c_int32),
+        ("device", C.c_int32),
+    ]
+
+
+def track_build_options(**overrides) -> CTrackBuildOptions:
+    """The defaults of tmi_ba_track_build_options_init."""
+    o = CTrackBuildOptions()
+    o.min_track_length = 2
+    o.max_track_length = 50
+    o.device = -1
+    for k, v in overrides.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
+class CTrackBuildSummary(C.Structure):
+    """tmi_ba_track_build_summary."""
+    _fields_ = [
+        ("num_nodes", C.c_int64),
+        ("num_components", C.c_int64),
+        ("num_oversize_components", C.c_int64),
+        ("num_replayed_edges", C.c_int64),
+        ("num_sets", C.c_int64),
+        ("num_tracks", C.c_int64),
+        ("num_observations", C.c_int64),
+        ("num_small_tracks", C.c_int64),
+        ("num_inconsistent_features", C.c_int64),
+        ("seconds", C.c_double),
+        ("kernel_seconds", C.c_double),
+        ("phase_seconds", C.c_double * 4),
+    ]
+
+
 class CSelectSummary(C.Structure):
     _fields_ = [
         ("num_tracks", C.c_int64),

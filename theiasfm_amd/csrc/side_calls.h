@@ -2898,6 +2898,331 @@ int32_t tmi_ba_match_features_cascade(const tmi_ba_cascade_match_options* option
 }
 }  // extern "C"
 
+// ---- TrackBuilder: tracks from matches by union-find (track_build_kernels.h) -------------------
+namespace {
+// Stable radix sort of (key, value) pairs on bits [0, end_bit) and an exclusive sum, each with work memory of the
+// call's own.
+template <class K>
+int tb_sort_pairs(OneShot* s, const K* key_in, K* key_out, const unsigned* value_in, unsigned* value_out, size_t n,
+                  int end_bit) {
+  size_t bytes = 0;
+  unsigned char* tmp = nullptr;
+  TMI_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, key_in, key_out, value_in, value_out, (int)n, 0, end_bit, s->stream));
+  TMI_HIP(s->alloc(&tmp, std::max<size_t>(bytes, 16)));
+  TMI_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, bytes, key_in, key_out, value_in, value_out, (int)n, 0, end_bit, s->stream));
+  return TMI_BA_OK;
+}
+
+int tb_exclusive_sum(OneShot* s, const unsigned* in, unsigned* out, size_t n) {
+  size_t bytes = 0;
+  unsigned char* tmp = nullptr;
+  TMI_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in, out, (int)n, s->stream));
+  TMI_HIP(s->alloc(&tmp, std::max<size_t>(bytes, 16)));
+  TMI_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, bytes, in, out, (int)n, s->stream));
+  return TMI_BA_OK;
+}
+
+// The bits that hold every value below n (at least one).
+int tb_bits(unsigned n) {
+  int bits = 1;
+  while (bits < 32 && (1ull << bits) < n) ++bits;
+  return bits;
+}
+
+#define TMI_TB(call)                  \
+  do {                                \
+    const int rc_ = (call);           \
+    if (rc_ != TMI_BA_OK) return rc_; \
+  } while (0)
+}  // namespace
+extern "C" {
+
+void tmi_ba_track_build_options_init(tmi_ba_track_build_options* o) {
+  if (!o) return;
+  o->min_track_length = 2;  // reconstruction_builder.h:81-85
+  o->max_track_length = 50;
+  o->device = -1;
+}
+
+int32_t tmi_ba_build_tracks(const tmi_ba_track_build_options* O, int64_t num_edges, const uint32_t* endpoint_view,
+                            const uint32_t* endpoint_feature, int64_t track_capacity, int64_t obs_capacity,
+                            int64_t* track_begin, uint32_t* obs_view, uint32_t* obs_feature, uint32_t* endpoint_node,
+                            uint32_t* endpoint_label, tmi_ba_track_build_summary* sum) {
+  if (!O || !sum) return bad_argument("build tracks: null options or summary");
+  memset(sum, 0, sizeof(*sum));
+  const double t0 = now_s();
+  // argument errors before the device is looked for
+  if (num_edges < 0 || track_capacity < 0 || obs_capacity < 0) return bad_argument("build tracks: negative count");
+  if (num_edges >= (1ll << 30)) return bad_argument("build tracks: 2^30 edges or more");
+  if (O->max_track_length < 1) return bad_argument("build tracks: max_track_length < 1");
+  if (O->min_track_length < 1) return bad_argument("build tracks: min_track_length < 1");
+  if (num_edges && (!endpoint_view || !endpoint_feature)) return bad_argument("build tracks: missing endpoint array");
+  if (!track_begin) return bad_argument("build tracks: missing track_begin");
+  if (obs_capacity && (!obs_view || !obs_feature)) return bad_argument("build tracks: missing observation array");
+  for (int64_t e = 0; e < num_edges; ++e)
+    if (endpoint_view[2 * e] == endpoint_view[2 * e + 1])
+      return bad_argument("build tracks: an edge joins two features of the same view");
+  const long long E = num_edges, N2 = 2 * E;
+  const unsigned cap = (unsigned)O->max_track_length;
+  const unsigned min_length = (unsigned)std::max(O->min_track_length, 2);  // a set of one node is always dropped
+  bool too_small = false;
+  const int rc = one_shot_batch(O->device, "build tracks: no such device", (int)E, t0, sum, [&](OneShot* s) -> int {
+    const hipStream_t stream = s->stream;
+    auto grid = [](long long n) { return dim3((unsigned)((n + 255) / 256)); };
+    StreamTimer nodes_timer(stream), components_timer(stream), cap_timer(stream, 4), output_timer(stream, 4);
+    TMI_HIP(nodes_timer.status);
+    TMI_HIP(components_timer.status);
+    TMI_HIP(cap_timer.status);
+    TMI_HIP(output_timer.status);
+    unsigned long long* d_counters;
+    TMI_HIP(s->alloc(&d_counters, (size_t)kTbCounters));
+    TMI_HIP(hipMemsetAsync(d_counters, 0, kTbCounters * sizeof(unsigned long long), stream));
+    unsigned long long counters[kTbCounters];
+    auto read_counters = [&]() -> int {
+      TMI_HIP(hipMemcpyAsync(counters, d_counters, sizeof(counters), hipMemcpyDeviceToHost, stream));
+      TMI_HIP(hipStreamSynchronize(stream));
+      if (counters[kTbError]) {
+        s->error = "build tracks: a device loop reached its bound";
+        return TMI_BA_ERR_DEVICE;
+      }
+      return TMI_BA_OK;
+    };
+
+    // step 1: node ids
+    unsigned *d_view, *d_feature, *d_index, *d_index_sorted, *d_head, *d_first, *d_heads_before, *d_firsts_before;
+    unsigned *d_run_node, *d_node_view, *d_node_feature, *d_endpoint_node;
+    unsigned long long *d_key, *d_key_sorted;
+    TMI_HIP(s->upload(&d_view, endpoint_view, (size_t)N2));
+    TMI_HIP(s->upload(&d_feature, endpoint_feature, (size_t)N2));
+    TMI_HIP(s->alloc(&d_key, (size_t)N2));
+    TMI_HIP(s->alloc(&d_key_sorted, (size_t)N2));
+    TMI_HIP(s->alloc(&d_index, (size_t)N2));
+    TMI_HIP(s->alloc(&d_index_sorted, (size_t)N2));
+    TMI_HIP(s->alloc(&d_head, (size_t)N2 + 1));
+    TMI_HIP(s->alloc(&d_first, (size_t)N2 + 1));
+    TMI_HIP(s->alloc(&d_heads_before, (size_t)N2 + 1));
+    TMI_HIP(s->alloc(&d_firsts_before, (size_t)N2 + 1));
+    TMI_HIP(s->alloc(&d_run_node, (size_t)N2));
+    TMI_HIP(s->alloc(&d_node_view, (size_t)N2));
+    TMI_HIP(s->alloc(&d_node_feature, (size_t)N2));
+    TMI_HIP(s->alloc(&d_endpoint_node, (size_t)N2));
+    TMI_HIP(hipMemsetAsync(d_head, 0, ((size_t)N2 + 1) * sizeof(unsigned), stream));
+    TMI_HIP(hipMemsetAsync(d_first, 0, ((size_t)N2 + 1) * sizeof(unsigned), stream));
+    TMI_HIP(nodes_timer.mark());
+    hipLaunchKernelGGL(tb_keys_kernel, grid(N2), dim3(256), 0, stream, d_view, d_feature, N2, d_key, d_index);
+    TMI_TB(tb_sort_pairs(s, d_key, d_key_sorted, d_index, d_index_sorted, (size_t)N2, 64));
+    hipLaunchKernelGGL(tb_run_heads_kernel, grid(N2), dim3(256), 0, stream, d_key_sorted, d_index_sorted, N2, d_head, d_first);
+    TMI_TB(tb_exclusive_sum(s, d_head, d_heads_before, (size_t)N2 + 1));
+    TMI_TB(tb_exclusive_sum(s, d_first, d_firsts_before, (size_t)N2 + 1));
+    hipLaunchKernelGGL(tb_run_nodes_kernel, grid(N2), dim3(256), 0, stream, d_key_sorted, d_index_sorted, d_head,
+                       d_heads_before, d_firsts_before, N2, d_run_node, d_node_view, d_node_feature);
+    hipLaunchKernelGGL(tb_endpoint_nodes_kernel, grid(N2), dim3(256), 0, stream, d_index_sorted, d_head, d_heads_before,
+                       d_run_node, N2, d_endpoint_node);
+    TMI_HIP(nodes_timer.mark());
+    TMI_HIP(hipGetLastError());
+    unsigned num_nodes = 0;
+    TMI_HIP(hipMemcpyAsync(&num_nodes, d_firsts_before + N2, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+    TMI_HIP(hipStreamSynchronize(stream));
+    if (num_nodes < 2 || (long long)num_nodes > N2) {
+      s->error = "build tracks: the device reported an impossible node count";
+      return TMI_BA_ERR_DEVICE;
+    }
+    const size_t N = num_nodes;
+    const int node_bits = tb_bits(num_nodes);
+    sum->num_nodes = num_nodes;
+    sum->phase_seconds[0] = nodes_timer.seconds();
+
+    // step 2: the components of the unconstrained graph and their sizes
+    unsigned *d_parent, *d_component, *d_size, *d_iota;
+    TMI_HIP(s->alloc(&d_parent, N));
+    TMI_HIP(s->alloc(&d_iota, N));
+    TMI_HIP(s->alloc(&d_component, N));
+    TMI_HIP(s->alloc(&d_size, N));
+    TMI_HIP(hipMemsetAsync(d_size, 0, N * sizeof(unsigned), stream));
+    TMI_HIP(components_timer.mark());
+    hipLaunchKernelGGL(tb_iota_kernel, grid(N), dim3(256), 0, stream, d_parent, num_nodes);
+    hipLaunchKernelGGL(tb_iota_kernel, grid(N), dim3(256), 0, stream, d_iota, num_nodes);  // the sorts' values
+    hipLaunchKernelGGL(tb_union_kernel, grid(E), dim3(256), 0, stream, d_endpoint_node, E, num_nodes, d_parent, d_counters);
+    hipLaunchKernelGGL(tb_flatten_kernel, grid(N), dim3(256), 0, stream, d_parent, num_nodes, d_component, d_counters);
+    hipLaunchKernelGGL(tb_sizes_kernel, grid(N), dim3(256), 0, stream, d_component, num_nodes, d_size);
+    hipLaunchKernelGGL(tb_component_stats_kernel, grid(N), dim3(256), 0, stream, d_component, d_size, num_nodes, cap,
+                       d_counters);
+    TMI_HIP(components_timer.mark());
+    TMI_HIP(hipGetLastError());
+    TMI_TB(read_counters());
+    sum->num_components = (int64_t)counters[kTbComponents];
+    sum->num_oversize_components = (int64_t)counters[kTbOversize];
+    sum->phase_seconds[1] = components_timer.seconds();
+    const unsigned num_oversize = (unsigned)counters[kTbOversize];
+    if (counters[kTbComponents] > N || counters[kTbOversize] > counters[kTbComponents]) {
+      s->error = "build tracks: the device reported an impossible component count";
+      return TMI_BA_ERR_DEVICE;
+    }
+
+    // nodes sorted by (label, node id): for the replay by component, for the output by final label
+    auto sort_nodes_by = [&](const unsigned* label, unsigned** sorted_label, unsigned** sorted_node) -> int {
+      TMI_HIP(s->alloc(sorted_label, N));
+      TMI_HIP(s->alloc(sorted_node, N));
+      return tb_sort_pairs(s, label, *sorted_label, d_iota, *sorted_node, N, node_bits);
+    };
+
+    // step 3: the cap.  Without an oversize component the components are the final sets.
+    unsigned *d_final = d_component, *d_set_size = d_size, *d_out_label = nullptr, *d_out_node = nullptr;
+    unsigned *d_flag, *d_before;  // flags over the nodes and their sums, used by one step at a time
+    TMI_HIP(s->alloc(&d_flag, N + 1));
+    TMI_HIP(s->alloc(&d_before, N + 1));
+    if (num_oversize) {
+      unsigned *d_edge_flag, *d_edge_before, *d_edge_count, *d_by_component, *d_by_component_node, *d_position;
+      unsigned *d_list_node_begin, *d_list_num_nodes, *d_list_num_edges, *d_list_edge_begin, *d_work_parent, *d_work_size;
+      const size_t K = num_oversize;
+      TMI_HIP(s->alloc(&d_edge_flag, (size_t)E + 1));
+      TMI_HIP(s->alloc(&d_edge_before, (size_t)E + 1));
+      TMI_HIP(s->alloc(&d_edge_count, N));
+      TMI_HIP(s->alloc(&d_position, N));
+      TMI_HIP(s->alloc(&d_list_node_begin, K));
+      TMI_HIP(s->alloc(&d_list_num_nodes, K));
+      TMI_HIP(s->alloc(&d_list_num_edges, K + 1));
+      TMI_HIP(s->alloc(&d_list_edge_begin, K + 1));
+      TMI_HIP(s->alloc(&d_work_parent, N));
+      TMI_HIP(s->alloc(&d_work_size, N));
+      TMI_HIP(s->alloc(&d_final, N));
+      TMI_HIP(s->alloc(&d_set_size, N));
+      TMI_HIP(hipMemsetAsync(d_edge_flag, 0, ((size_t)E + 1) * sizeof(unsigned), stream));
+      TMI_HIP(hipMemsetAsync(d_edge_count, 0, N * sizeof(unsigned), stream));
+      TMI_HIP(hipMemsetAsync(d_flag, 0, (N + 1) * sizeof(unsigned), stream));
+      TMI_HIP(hipMemsetAsync(d_list_num_edges, 0, (K + 1) * sizeof(unsigned), stream));
+      TMI_HIP(hipMemsetAsync(d_set_size, 0, N * sizeof(unsigned), stream));
+      TMI_HIP(cap_timer.mark());
+      hipLaunchKernelGGL(tb_replay_edges_kernel, grid(E), dim3(256), 0, stream, d_endpoint_node, d_component, d_size, E, cap,
+                         d_edge_flag, d_edge_count);
+      TMI_TB(tb_exclusive_sum(s, d_edge_flag, d_edge_before, (size_t)E + 1));
+      TMI_TB(sort_nodes_by(d_component, &d_by_component, &d_by_component_node));
+      hipLaunchKernelGGL(tb_component_heads_kernel, grid(N), dim3(256), 0, stream, d_by_component, d_by_component_node,
+                         d_size, num_nodes, cap, d_position, d_flag);
+      TMI_TB(tb_exclusive_sum(s, d_flag, d_before, N + 1));
+      hipLaunchKernelGGL(tb_component_list_kernel, grid(N), dim3(256), 0, stream, d_by_component, d_flag, d_before, d_size,
+                         d_edge_count, num_nodes, d_list_node_begin, d_list_num_nodes, d_list_num_edges);
+      TMI_TB(tb_exclusive_sum(s, d_list_num_edges, d_list_edge_begin, K + 1));
+      TMI_HIP(cap_timer.mark());
+      TMI_HIP(hipGetLastError());
+      unsigned num_replayed = 0, listed = 0;
+      TMI_HIP(hipMemcpyAsync(&num_replayed, d_edge_before + E, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+      TMI_HIP(hipMemcpyAsync(&listed, d_before + N, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+      TMI_HIP(hipStreamSynchronize(stream));
+      if (listed != num_oversize || num_replayed < 1 || (long long)num_replayed > E) {
+        s->error = "build tracks: the device reported an impossible replay plan";
+        return TMI_BA_ERR_DEVICE;
+      }
+      sum->num_replayed_edges = num_replayed;
+      unsigned *d_replay_key, *d_replay_edge, *d_replay_key_sorted, *d_replay_edge_sorted;
+      TMI_HIP(s->alloc(&d_replay_key, (size_t)num_replayed));
+      TMI_HIP(s->alloc(&d_replay_edge, (size_t)num_replayed));
+      TMI_HIP(s->alloc(&d_replay_key_sorted, (size_t)num_replayed));
+      TMI_HIP(s->alloc(&d_replay_edge_sorted, (size_t)num_replayed));
+      TMI_HIP(hipMemcpyAsync(d_final, d_component, N * sizeof(unsigned), hipMemcpyDeviceToDevice, stream));
+      TMI_HIP(cap_timer.mark());
+      hipLaunchKernelGGL(tb_replay_compact_kernel, grid(E), dim3(256), 0, stream, d_endpoint_node, d_component, d_edge_flag,
+                         d_edge_before, E, d_replay_key, d_replay_edge);
+      // stable: the edges of a component stay in ascending edge index
+      TMI_TB(tb_sort_pairs(s, d_replay_key, d_replay_key_sorted, d_replay_edge, d_replay_edge_sorted, (size_t)num_replayed,
+                           node_bits));
+      hipLaunchKernelGGL(tb_iota_kernel, grid(N), dim3(256), 0, stream, d_work_parent, num_nodes);
+      TMI_HIP(hipMemsetD32Async((hipDeviceptr_t)d_work_size, 1, N, stream));
+      hipLaunchKernelGGL(tb_replay_kernel, dim3((unsigned)((K + 63) / 64)), dim3(64), 0, stream, d_list_node_begin,
+                         d_list_num_nodes, d_list_edge_begin, num_oversize, d_replay_edge_sorted, d_endpoint_node, d_position,
+                         d_by_component_node, cap, d_work_parent, d_work_size, d_final, d_counters);
+      hipLaunchKernelGGL(tb_sizes_kernel, grid(N), dim3(256), 0, stream, d_final, num_nodes, d_set_size);
+      TMI_HIP(cap_timer.mark());
+      TMI_HIP(hipGetLastError());
+      TMI_HIP(output_timer.mark());
+      TMI_TB(sort_nodes_by(d_final, &d_out_label, &d_out_node));
+    } else {
+      TMI_HIP(output_timer.mark());
+      TMI_TB(sort_nodes_by(d_component, &d_out_label, &d_out_node));
+    }
+
+    // steps 4 to 6: small sets, consistency, the CSR
+    unsigned long long *d_view_key, *d_view_key_sorted;
+    unsigned *d_by_view_node, *d_keep, *d_obs_flag, *d_obs_before;
+    TMI_HIP(s->alloc(&d_view_key, N));
+    TMI_HIP(s->alloc(&d_view_key_sorted, N));
+    TMI_HIP(s->alloc(&d_by_view_node, N));
+    TMI_HIP(s->alloc(&d_keep, N));
+    TMI_HIP(s->alloc(&d_obs_flag, N + 1));
+    TMI_HIP(s->alloc(&d_obs_before, N + 1));
+    TMI_HIP(hipMemsetAsync(d_obs_flag, 0, (N + 1) * sizeof(unsigned), stream));
+    TMI_HIP(hipMemsetAsync(d_flag, 0, (N + 1) * sizeof(unsigned), stream));
+    hipLaunchKernelGGL(tb_view_keys_kernel, grid(N), dim3(256), 0, stream, d_final, d_node_view, num_nodes, d_view_key);
+    TMI_TB(tb_sort_pairs(s, d_view_key, d_view_key_sorted, d_iota, d_by_view_node, N, 32 + node_bits));
+    hipLaunchKernelGGL(tb_keep_kernel, grid(N), dim3(256), 0, stream, d_view_key_sorted, d_by_view_node, d_set_size,
+                       num_nodes, min_length, d_keep, d_counters);
+    hipLaunchKernelGGL(tb_output_flags_kernel, grid(N), dim3(256), 0, stream, d_out_label, d_out_node, d_set_size, d_keep,
+                       num_nodes, min_length, d_obs_flag, d_flag, d_counters);
+    TMI_TB(tb_exclusive_sum(s, d_obs_flag, d_obs_before, N + 1));
+    TMI_TB(tb_exclusive_sum(s, d_flag, d_before, N + 1));
+    TMI_HIP(output_timer.mark());
+    TMI_HIP(hipGetLastError());
+    unsigned num_obs = 0, num_tracks = 0;
+    TMI_HIP(hipMemcpyAsync(&num_obs, d_obs_before + N, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+    TMI_HIP(hipMemcpyAsync(&num_tracks, d_before + N, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+    TMI_TB(read_counters());
+    if (num_oversize) sum->phase_seconds[2] = cap_timer.seconds(0, 1) + cap_timer.seconds(2, 3);
+    sum->num_sets = (int64_t)counters[kTbSets];
+    sum->num_small_tracks = (int64_t)counters[kTbSmall];
+    sum->num_inconsistent_features = (int64_t)counters[kTbInconsistent];
+    sum->num_tracks = num_tracks;
+    sum->num_observations = num_obs;
+    if (num_obs > num_nodes || (unsigned long long)num_tracks + counters[kTbSmall] != counters[kTbSets] ||
+        counters[kTbInconsistent] + num_obs > N) {
+      s->error = "build tracks: the device reported impossible totals";
+      return TMI_BA_ERR_DEVICE;
+    }
+    too_small = (int64_t)num_tracks > track_capacity || (int64_t)num_obs > obs_capacity;
+    long long* d_track_begin = nullptr;
+    unsigned *d_obs_view = nullptr, *d_obs_feature = nullptr, *d_endpoint_label = nullptr;
+    TMI_HIP(output_timer.mark());
+    if (!too_small) {
+      TMI_HIP(s->alloc(&d_track_begin, (size_t)num_tracks + 1));
+      TMI_HIP(s->alloc(&d_obs_view, (size_t)num_obs));
+      TMI_HIP(s->alloc(&d_obs_feature, (size_t)num_obs));
+      hipLaunchKernelGGL(tb_emit_kernel, grid((long long)N + 1), dim3(256), 0, stream, d_out_node, d_obs_flag, d_obs_before,
+                         d_flag, d_before, d_node_view, d_node_feature, num_nodes, d_track_begin, d_obs_view, d_obs_feature);
+    }
+    if (endpoint_label) {
+      TMI_HIP(s->alloc(&d_endpoint_label, (size_t)N2));
+      hipLaunchKernelGGL(tb_endpoint_labels_kernel, grid(N2), dim3(256), 0, stream, d_endpoint_node, d_final, N2,
+                         d_endpoint_label);
+    }
+    TMI_HIP(output_timer.mark());
+    TMI_HIP(hipGetLastError());
+    if (!too_small) {
+      static_assert(sizeof(long long) == sizeof(int64_t), "track_begin is read back as it is");
+      TMI_HIP(hipMemcpyAsync(track_begin, d_track_begin, ((size_t)num_tracks + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+      if (num_obs) {
+        TMI_HIP(hipMemcpyAsync(obs_view, d_obs_view, (size_t)num_obs * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        TMI_HIP(hipMemcpyAsync(obs_feature, d_obs_feature, (size_t)num_obs * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+      }
+    }
+    if (endpoint_node)
+      TMI_HIP(hipMemcpyAsync(endpoint_node, d_endpoint_node, (size_t)N2 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    if (endpoint_label)
+      TMI_HIP(hipMemcpyAsync(endpoint_label, d_endpoint_label, (size_t)N2 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    TMI_HIP(hipStreamSynchronize(stream));
+    sum->phase_seconds[3] = output_timer.seconds(0, 1) + output_timer.seconds(2, 3);
+    sum->kernel_seconds = sum->phase_seconds[0] + sum->phase_seconds[1] + sum->phase_seconds[2] + sum->phase_seconds[3];
+    return TMI_BA_OK;
+  });
+  if (rc == TMI_BA_OK && E == 0) track_begin[0] = 0;
+  sum->seconds = now_s() - t0;
+  if (rc == TMI_BA_OK && too_small) {
+    g_last_error = "build tracks: track_capacity or obs_capacity is too small (summary->num_tracks, num_observations)";
+    return TMI_BA_ERR_CAPACITY;
+  }
+  return rc;
+}
+#undef TMI_TB
+}  // extern "C"
+
 // ---- batched EstimateUncalibratedRelativePose: eight-point RANSAC (two_view_ransac_kernels.h) ----
 extern "C" {
 void tmi_ba_two_view_ransac_options_init(tmi_ba_two_view_ransac_options* o) {

@@ -41,6 +41,7 @@ EXPORTS = (
     "tmi_ba_localization_options_init", "tmi_ba_localize_views",
     "tmi_ba_match_options_init", "tmi_ba_match_features",
     "tmi_ba_cascade_match_options_init", "tmi_ba_match_features_cascade",
+    "tmi_ba_track_build_options_init", "tmi_ba_build_tracks",
     "tmi_ba_two_view_ransac_options_init", "tmi_ba_estimate_uncalibrated_relative_poses",
     "tmi_ba_estimate_calibrated_relative_poses",
     "tmi_ba_solver_structure_checksums",
@@ -201,6 +202,12 @@ def load():
                                                 C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 8 + [
         C.POINTER(abi.CCascadeMatchSummary)]
     L.tmi_ba_match_features_cascade.restype = C.c_int32
+    TO = C.POINTER(abi.CTrackBuildOptions)
+    L.tmi_ba_track_build_options_init.argtypes = [TO]
+    L.tmi_ba_track_build_options_init.restype = None
+    L.tmi_ba_build_tracks.argtypes = [TO, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 5 + [
+        C.POINTER(abi.CTrackBuildSummary)]
+    L.tmi_ba_build_tracks.restype = C.c_int32
     RO = C.POINTER(abi.CTwoViewRansacOptions)
     L.tmi_ba_two_view_ransac_options_init.argtypes = [RO]
     L.tmi_ba_two_view_ransac_options_init.restype = None
@@ -677,6 +684,42 @@ def match_features_cascade(image_begin, descriptors, projections, pair_image1, p
     return _match_call("tmi_ba_match_features_cascade", abi.CCascadeMatchSummary, abi.cascade_match_options,
                        image_begin, descriptors, projections, pair_image1, pair_image2, options, match_capacity,
                        bool(want_hash))
+
+
+def build_tracks(endpoint_view, endpoint_feature, options=None, track_capacity=None, obs_capacity=None,
+                 want_nodes=False):
+    """TrackBuilder on the device (tmi_ba_build_tracks): the tracks of the correspondences whose edge e joins the
+    endpoints 2e and 2e + 1 of endpoint_view / endpoint_feature [2E] uint32 (a feature index is local to its view).
+    options: abi.track_build_options().  track_capacity / obs_capacity: None sizes the outputs for the most there can
+    be (E tracks, 2E observations); a number is passed through, and a capacity that is too small comes back as
+    `status` == abi.ERR_CAPACITY with empty outputs and the needed totals in summary.num_tracks / num_observations.
+    Returns a dict: status, track_begin [num_tracks + 1] int64, obs_view / obs_feature [num_observations] uint32,
+    summary (CTrackBuildSummary) and, with want_nodes, endpoint_node / endpoint_label [2E] uint32 (None otherwise).
+    Raises EngineError on any other failure."""
+    L = load()
+    o = options if options is not None else abi.track_build_options()
+    ev = np.ascontiguousarray(endpoint_view, dtype=np.uint32)
+    ef = np.ascontiguousarray(endpoint_feature, dtype=np.uint32)
+    if ev.ndim != 1 or ev.shape != ef.shape or ev.shape[0] % 2:
+        raise ValueError("endpoint_view and endpoint_feature must be [2E]")
+    E = ev.shape[0] // 2
+    tcap = E if track_capacity is None else int(track_capacity)
+    ocap = 2 * E if obs_capacity is None else int(obs_capacity)
+    begin = np.zeros(max(tcap, 0) + 1, dtype=np.int64)
+    ov = np.zeros(max(ocap, 0), dtype=np.uint32)
+    of = np.zeros(max(ocap, 0), dtype=np.uint32)
+    node = np.zeros(2 * E, dtype=np.uint32) if want_nodes else None
+    label = np.zeros(2 * E, dtype=np.uint32) if want_nodes else None
+    ts = abi.CTrackBuildSummary()
+    st = L.tmi_ba_build_tracks(C.byref(o), E, ev.ctypes.data, ef.ctypes.data, tcap, ocap, begin.ctypes.data,
+                               ov.ctypes.data, of.ctypes.data, node.ctypes.data if want_nodes else None,
+                               label.ctypes.data if want_nodes else None, C.byref(ts))
+    if st not in (0, abi.ERR_CAPACITY):
+        raise EngineError(st, "tmi_ba_build_tracks")
+    nt = 0 if st else int(ts.num_tracks)
+    no = 0 if st else int(ts.num_observations)
+    return dict(status=st, track_begin=begin[:nt + 1], obs_view=ov[:no], obs_feature=of[:no], endpoint_node=node,
+                endpoint_label=label, summary=ts)
 
 
 def estimate_uncalibrated_relative_poses(pair_offset, feature1, feature2, pair_error_threshold, options=None,
