@@ -1093,6 +1093,123 @@ int32_t tmi_ba_estimate_global_positions_lud(const tmi_ba_view_pair_batch* batch
                                              double* pair_residual, double* admm_r_norm, double* admm_s_norm,
                                              tmi_ba_lud_position_summary* summary);
 
+/* ---- NonlinearPositionEstimator: camera positions by Levenberg-Marquardt on the direction error ----
+ * reference: nonlinear_position_estimator.cc:86-214 (GlobalPositionEstimatorType::NONLINEAR, the default of
+ * ReconstructionEstimatorOptions, reconstruction_estimator_options.h:90; Wilson and Snavely, ECCV 2014) with
+ * pairwise_translation_error.h:63-88 and Ceres 1.14's TrustRegionMinimizer, LevenbergMarquardtStrategy, HuberLoss and
+ * Corrector.  max_num_iterations and robust_loss_width are NonlinearPositionEstimator::Options
+ * (nonlinear_position_estimator.h:70-72); the trust-region fields are Ceres' Solver::Options defaults, which the
+ * reference leaves alone. */
+typedef struct tmi_ba_nonlinear_position_options {
+  int32_t  max_num_iterations;                 /* 400; 0: the start is evaluated and returned              */
+  double   robust_loss_width;                  /* 0.1, HuberLoss                                            */
+  int32_t  positions_given;                    /* 0; != 0: view_position holds the start (EXTENSION)        */
+  uint64_t seed;                               /* 0; of the random start                                    */
+  int32_t  jacobi_scaling;                     /* 1                                                         */
+  int32_t  max_num_consecutive_invalid_steps;  /* 5                                                         */
+  double   function_tolerance;                 /* 1e-6                                                      */
+  double   gradient_tolerance;                 /* 1e-10                                                     */
+  double   parameter_tolerance;                /* 1e-8                                                      */
+  double   initial_trust_region_radius;        /* 1e4                                                       */
+  double   max_trust_region_radius;            /* 1e16                                                      */
+  double   min_trust_region_radius;            /* 1e-32                                                     */
+  double   min_relative_decrease;              /* 1e-3                                                      */
+  double   min_lm_diagonal;                    /* 1e-6                                                      */
+  double   max_lm_diagonal;                    /* 1e32                                                      */
+} tmi_ba_nonlinear_position_options;
+void tmi_ba_nonlinear_position_options_init(tmi_ba_nonlinear_position_options* options);
+
+typedef struct tmi_ba_nonlinear_position_summary {
+  int32_t num_views;
+  int32_t num_pairs;
+  int32_t num_iterations;           /* LM iterations run (one ended by the gradient test is not counted)       */
+  int32_t num_successful_steps;
+  int32_t num_unsuccessful_steps;   /* rejected and invalid steps                                              */
+  int32_t num_factorizations;       /* dense Cholesky factorisations of order 3 (num_views - 1)                */
+  int32_t termination;              /* 0 CONVERGENCE, 1 NO_CONVERGENCE, 2 FAILURE                              */
+  int32_t usable;                   /* Summary::IsSolutionUsable(): termination != FAILURE                     */
+  double  initial_cost;
+  double  final_cost;
+  double  seconds;
+  double  kernel_seconds;           /* device time; the sum of the three below                                 */
+  double  factor_seconds;           /* the damped copy of the normal matrix and its factorisation              */
+  double  substitution_seconds;     /* forward / backward substitution                                         */
+  double  graph_seconds;            /* directions, per-edge and per-view kernels, assembly, the reductions     */
+} tmi_ba_nonlinear_position_summary;
+
+/* EstimatePositions on the device.  The batch is tmi_ba_view_pair_batch: view_rotation (or NULL: pair_position2 is
+ * already in the global frame), pair_view1 / pair_view2 and pair_position2; pair_rotation2 is not read.
+ * view_position [3 * num_views] is in/out: the start when options->positions_given, the result afterwards; view
+ * `fixed_view` is at 0.
+ *   1. :59-66, :196-199  t_e = R(view_rotation[view1])^T position_2, step 1 of tmi_ba_estimate_global_positions_lud and
+ *                its kernel.
+ *   2. :164-180  The start.  positions_given: the caller's view_position.  Otherwise component k of view v is
+ *                100 (2 u - 1) with u = ((word >> 11) + 0.5) 2^-53 and word = word 3 v + k of the splitmix64 stream from
+ *                state `seed` (word c is the output mix of seed + (c + 1) 0x9e3779b97f4a7c15, the generator documented
+ *                at the translation filter).  DEVIATION: not the reference's stream (100 RandVector3d() of its
+ *                mt19937).  :131-132  view `fixed_view` is set to 0 and held constant; DEVIATION: the reference fixes
+ *                whichever view its hash map yields first.  Free view v has columns 3 (v - (v > fixed_view)) + k;
+ *                n = num_views - 1.
+ *   3. pairwise_translation_error.h:63-88 (weight 1)  d = p[view2] - p[view1], norm = sqrt((d0 d0 + d1 d1) + d2 d2),
+ *                norm = 1 where norm < 1e-12; u = d / norm; r = u - t_e.  The Jacobian with respect to p[view2] is what
+ *                the reference's dual numbers give, J = (I - u u^T) / norm, and J = I on the small-norm branch (the
+ *                derivative of the discarded norm is discarded with it); with respect to p[view1] it is -J.
+ *   4. :201-207  HuberLoss(a = robust_loss_width) on s = (r0 r0 + r1 r1) + r2 r2 (ceres/loss_function.cc): s <= a^2:
+ *                rho = s, rho' = 1, rho'' = 0; otherwise rho = 2 a sqrt(s) - a^2, rho' = max(DBL_MIN, a / sqrt(s)),
+ *                rho'' = -rho' / (2 s).  Ceres' Corrector (corrector.cc), as the engine's robust path applies it: where
+ *                s = 0 or rho'' <= 0 (the shortcut) r~ = sqrt(rho') r and J~ = sqrt(rho') J; otherwise
+ *                alpha = 1 - sqrt(1 + 2 s rho'' / rho'), r~ = sqrt(rho') / (1 - alpha) r and
+ *                J~ = sqrt(rho') (J - (alpha / s) r (r^T J)).  Triggs' correction would have alpha in [0, 1) for
+ *                rho'' < 0 and clamp it below 1; Ceres takes alpha = 0 there instead, which is the shortcut.  HuberLoss
+ *                never leaves it (rho'' <= 0 on both branches), so the shortcut is all the kernels carry.
+ *                cost = sum of rho(s) / 2 over the edges.
+ *   5.           The normal equations of order 3 n: with B_e = J~^T J~ and q_e = J~^T r~ the diagonal blocks of view1 and
+ *                view2 get +B_e, block (view1, view2) is -B_e, the gradient gets +q_e at view2 and -q_e at view1; the
+ *                fixed view's rows and columns are absent.  Jacobi scaling (jacobi_scaling != 0): column i is scaled
+ *                by 1 / (1 + sqrt(the diagonal entry i at the start)), once.
+ *   6.           Ceres 1.14's TrustRegionMinimizer with the Levenberg-Marquardt strategy, the rules of
+ *                tmi_ba_solver_solve: per iteration (A + D) y = g with D_ii = clamp(A_ii, min_lm_diagonal,
+ *                max_lm_diagonal) / radius by ONE dense Cholesky factorisation and one substitution, step = -scale y;
+ *                a non-positive pivot or a model cost change -(J~ step) . (r~ + J~ step / 2) that is not positive is an
+ *                invalid step (max_num_consecutive_invalid_steps in a row: FAILURE), which divides the radius by the
+ *                decrease factor (2, doubling with every step in a row that is not accepted); then the parameter
+ *                tolerance |step| <= parameter_tolerance (|x| + parameter_tolerance) and the function tolerance
+ *                |cost change| <= function_tolerance cost end the solve with CONVERGENCE before the step is taken; a step
+ *                with cost change / model cost change > min_relative_decrease is accepted, the radius divided by
+ *                max(1/3, 1 - (2 rho - 1)^3) and capped at max_trust_region_radius; any other is rejected as an invalid
+ *                one shrinks.  A radius below min_trust_region_radius and, after the first linearisation and after
+ *                every accepted step, max |gradient| <= gradient_tolerance are CONVERGENCE.  A rejected or invalid step
+ *                re-factors the kept normal matrix with the new diagonal; nothing is evaluated or assembled again.
+ *   7.           Fixed orders: edges in the caller's order; every per-view sum from zero in ascending edge index;
+ *                every scalar (cost, model cost change, the squared norms of the step and of x over their 3 n entries) by
+ *                the reduction of fixed shape of step 5 of the LUD call; no expression is contracted into FMA and no
+ *                atomic is used.  The result is the same bits from call to call.
+ * The loop runs on the host; every kernel is a plain grid launch.  The call returns TMI_BA_OK whenever the solve ran:
+ * summary->termination says how it ended and summary->usable is IsSolutionUsable (:161); view_position receives the
+ * last accepted point in every case.
+ * DEVIATIONS beyond steps 2: the linear solve is always the exact dense factorisation -- the reference takes
+ * SPARSE_NORMAL_CHOLESKY up to 1000 views, the same step up to rounding, and CGNR with JACOBI above, an inexact step
+ * (:139-157).  3 n is capped as in the rotation and the LUD call (11000, the knob TMI_BA_ROTATION_MAX_ORDER):
+ * TMI_BA_ERR_UNSUPPORTED above it, before anything of that size is allocated.  The point-to-camera constraints
+ * (min_num_points_per_view > 0, :216-361) are not provided: the reference's default and its application flag are 0.
+ * TMI_BA_ERR_INVALID_ARGUMENT, before the device is looked for: a null batch, options, view_position or summary, a
+ * missing array, num_pairs == 0, a view index out of range, view1 == view2, a repeated unordered pair, fixed_view out of
+ * range, a non-finite rotation or position_2, robust_loss_width that is not positive and finite (:93),
+ * max_num_iterations < 0, a radius, tolerance or LM diagonal bound that is negative or NaN, an initial radius of 0,
+ * positions_given with a non-finite position, and a view that the edges do not connect to fixed_view.
+ * On every failure view_position and the optional outputs are left as they were.  Optional outputs (each may be NULL):
+ * initial_position [3 * num_views] the start (the fixed view at 0); iteration_cost, iteration_radius and
+ * iteration_step_accepted [max_num_iterations + 1]: entry 0 the initial cost, the initial radius and 1, entry k the cost
+ * and the radius after iteration k and its outcome -- 1 accepted, 0 rejected, -1 invalid, 2 / 3 ended by the parameter /
+ * the function tolerance; pair_residual [3 * num_pairs] the r of step 3 at the result. */
+int32_t tmi_ba_estimate_global_positions_nonlinear(const tmi_ba_view_pair_batch* batch,
+                                                   const tmi_ba_nonlinear_position_options* options,
+                                                   int32_t fixed_view, int32_t device, double* view_position,
+                                                   double* initial_position, double* iteration_cost,
+                                                   double* iteration_radius, int32_t* iteration_step_accepted,
+                                                   double* pair_residual,
+                                                   tmi_ba_nonlinear_position_summary* summary);
+
 /* ---- batched LocalizeViewToReconstruction: P3P RANSAC for many candidate views ------------------
  * reference: LocalizeViewToReconstruction (localize_view_to_reconstruction.cc:213-257), the inner loop of the
  * incremental and hybrid pipelines (incremental_reconstruction_estimator.cc:219-233), on its CALIBRATED path:

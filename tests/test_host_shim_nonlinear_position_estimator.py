@@ -1,0 +1,44 @@
+"""The nonlinear position estimator shim (theiasfm_amd/host/nonlinear_position_ops.cc) through
+tests/cpp/test_nonlinear_position_estimator_shim.cc, compiled here with g++ -Wall -Werror into pytest's tmp_path.  The
+program checks the options' defaults against the reference's and every refusal (false, nothing written) on any machine;
+without a device that the call returns false and leaves the position map unchanged; with one (-m gpu) the reference's
+4-view scene within its bound, the id mapping in ascending order against the C ABI called directly, the views without a
+kept pair and the smallest id at the origin."""
+import os
+import subprocess
+import sys
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import __graft_entry__ as entry  # noqa: E402
+
+LIB = os.path.join(ROOT, "theiasfm_amd", "lib")
+
+
+def _compile(tmp_path):
+    entry.build_engine()
+    exe = str(tmp_path / "test_nonlinear_position_estimator_shim")
+    cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-pthread", "-I" + os.path.join(ROOT, "include"), "-o", exe,
+           os.path.join(ROOT, "tests", "cpp", "test_nonlinear_position_estimator_shim.cc"),
+           os.path.join(ROOT, "theiasfm_amd", "host", "nonlinear_position_ops.cc"),
+           "-L" + LIB, "-ltheia_mi355_ba", "-Wl,-rpath," + LIB, "-Wl,-rpath,/opt/rocm/lib",
+           "-Wl,-rpath-link,/opt/rocm/lib"]
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr
+    return exe
+
+
+def test_nonlinear_position_estimator_shim(tmp_path):
+    """Whatever the machine has: without a device false and an unchanged map, with one the full comparison."""
+    p = subprocess.run([_compile(tmp_path)], capture_output=True, text=True, timeout=600)
+    print(p.stdout, p.stderr)
+    assert p.returncode == 0 and "OK" in p.stdout, p.stdout + p.stderr
+
+
+@pytest.mark.gpu
+def test_nonlinear_position_estimator_shim_on_the_device(tmp_path):
+    p = subprocess.run([_compile(tmp_path), "--need-device"], capture_output=True, text=True, timeout=600)
+    print(p.stdout, p.stderr)
+    assert p.returncode == 0 and "nonlinear position estimator shim: OK" in p.stdout, p.stdout + p.stderr

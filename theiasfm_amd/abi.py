@@ -472,6 +472,74 @@ class CLudPositionSummary(C.Structure):
     ]
 
 
+class CNonlinearPositionOptions(C.Structure):
+    """tmi_ba_nonlinear_position_options (NonlinearPositionEstimator::Options, nonlinear_position_estimator.h:63-82, the
+    rng replaced by a seed, and the trust-region fields of ceres::Solver::Options)."""
+    _fields_ = [
+        ("max_num_iterations", C.c_int32),
+        ("robust_loss_width", C.c_double),
+        ("positions_given", C.c_int32),
+        ("seed", C.c_uint64),
+        ("jacobi_scaling", C.c_int32),
+        ("max_num_consecutive_invalid_steps", C.c_int32),
+        ("function_tolerance", C.c_double),
+        ("gradient_tolerance", C.c_double),
+        ("parameter_tolerance", C.c_double),
+        ("initial_trust_region_radius", C.c_double),
+        ("max_trust_region_radius", C.c_double),
+        ("min_trust_region_radius", C.c_double),
+        ("min_relative_decrease", C.c_double),
+        ("min_lm_diagonal", C.c_double),
+        ("max_lm_diagonal", C.c_double),
+    ]
+
+
+def nonlinear_position_options(**overrides) -> CNonlinearPositionOptions:
+    """The reference's and Ceres' defaults; mirrors tmi_ba_nonlinear_position_options_init."""
+    o = CNonlinearPositionOptions()
+    o.max_num_iterations = 400
+    o.robust_loss_width = 0.1
+    o.positions_given = 0
+    o.seed = 0
+    o.jacobi_scaling = 1
+    o.max_num_consecutive_invalid_steps = 5
+    o.function_tolerance = 1e-6
+    o.gradient_tolerance = 1e-10
+    o.parameter_tolerance = 1e-8
+    o.initial_trust_region_radius = 1e4
+    o.max_trust_region_radius = 1e16
+    o.min_trust_region_radius = 1e-32
+    o.min_relative_decrease = 1e-3
+    o.min_lm_diagonal = 1e-6
+    o.max_lm_diagonal = 1e32
+    for k, v in overrides.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
+class CNonlinearPositionSummary(C.Structure):
+    """tmi_ba_nonlinear_position_summary."""
+    _fields_ = [
+        ("num_views", C.c_int32),
+        ("num_pairs", C.c_int32),
+        ("num_iterations", C.c_int32),
+        ("num_successful_steps", C.c_int32),
+        ("num_unsuccessful_steps", C.c_int32),
+        ("num_factorizations", C.c_int32),
+        ("termination", C.c_int32),
+        ("usable", C.c_int32),
+        ("initial_cost", C.c_double),
+        ("final_cost", C.c_double),
+        ("seconds", C.c_double),
+        ("kernel_seconds", C.c_double),
+        ("factor_seconds", C.c_double),
+        ("substitution_seconds", C.c_double),
+        ("graph_seconds", C.c_double),
+    ]
+
+
 class CLocalizationOptions(C.Structure):
     """tmi_ba_localization_options (RansacParameters, sample_consensus_estimator.h:57-65, and
     LocalizeViewToReconstructionOptions, localize_view_to_reconstruction.h:48-72)."""

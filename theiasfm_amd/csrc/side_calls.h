@@ -2198,6 +2198,344 @@ int32_t tmi_ba_estimate_global_positions_lud(const tmi_ba_view_pair_batch* Bh, c
     return TMI_BA_OK;
   });
 }
+}  // extern "C"
+
+// ---- NonlinearPositionEstimator (position_nonlinear_kernels.h) ----------------------------------
+namespace {
+// What the nonlinear position estimator asks of its arguments beyond check_view_pair_batch, the connection to fixed_view
+// apart; null: fine.  Nothing is allocated here.
+const char* check_nonlinear_position_arguments(const tmi_ba_view_pair_batch* B,
+                                               const tmi_ba_nonlinear_position_options* o, int fixed_view,
+                                               const double* view_position) {
+  if (B->num_pairs == 0) return "nonlinear positions: no view pair";
+  if (fixed_view < 0 || fixed_view >= B->num_views) return "nonlinear positions: fixed_view out of range";
+  if (!(o->robust_loss_width > 0.0) || !std::isfinite(o->robust_loss_width))
+    return "nonlinear positions: robust_loss_width is not positive and finite (the reference CHECK_GTs it)";
+  if (o->max_num_iterations < 0) return "nonlinear positions: max_num_iterations < 0";
+  for (const double x : {o->function_tolerance, o->gradient_tolerance, o->parameter_tolerance,
+                         o->initial_trust_region_radius, o->max_trust_region_radius, o->min_trust_region_radius,
+                         o->min_relative_decrease, o->min_lm_diagonal, o->max_lm_diagonal})
+    if (!(x >= 0.0)) return "nonlinear positions: a radius, tolerance or LM diagonal bound that is negative or NaN";
+  if (!(o->initial_trust_region_radius > 0.0)) return "nonlinear positions: initial_trust_region_radius is 0";
+  if (o->positions_given && !all_finite(view_position, (size_t)3 * B->num_views))
+    return "nonlinear positions: positions_given with a non-finite position";
+  return nullptr;
+}
+
+// Component k of view v of the random start: 100 (2 u - 1), u from word 3 v + k of the splitmix64 stream of `seed`.
+double nonlinear_position_start(uint64_t seed, int v, int k) {
+  uint64_t z = seed + ((uint64_t)3 * (uint64_t)v + (uint64_t)k + 1) * 0x9e3779b97f4a7c15ULL;
+  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ULL;
+  z = (z ^ (z >> 27)) * 0x94d049bb133111ebULL;
+  z ^= z >> 31;
+  const double u = ((double)(z >> 11) + 0.5) * (1.0 / 9007199254740992.0);
+  const double centred = 2.0 * u - 1.0;
+  return 100.0 * centred;
+}
+}  // namespace
+extern "C" {
+
+void tmi_ba_nonlinear_position_options_init(tmi_ba_nonlinear_position_options* o) {
+  if (!o) return;
+  const SmallLmArgs A = ceres_default_lm_args(400, TMI_BA_LOSS_HUBER, 0.1);  // nonlinear_position_estimator.h:70-72
+  o->max_num_iterations = A.max_num_iterations;
+  o->robust_loss_width = A.loss_width;
+  o->positions_given = 0;
+  o->seed = 0;
+  o->jacobi_scaling = A.jacobi_scaling;
+  o->max_num_consecutive_invalid_steps = A.max_num_consecutive_invalid_steps;
+  o->function_tolerance = A.function_tolerance;
+  o->gradient_tolerance = A.gradient_tolerance;
+  o->parameter_tolerance = A.parameter_tolerance;
+  o->initial_trust_region_radius = A.initial_radius;
+  o->max_trust_region_radius = A.max_radius;
+  o->min_trust_region_radius = A.min_radius;
+  o->min_relative_decrease = A.min_relative_decrease;
+  o->min_lm_diagonal = A.lm_lo;
+  o->max_lm_diagonal = A.lm_hi;
+}
+
+int32_t tmi_ba_estimate_global_positions_nonlinear(const tmi_ba_view_pair_batch* Bh,
+                                                   const tmi_ba_nonlinear_position_options* opt, int32_t fixed_view,
+                                                   int32_t device, double* view_position, double* initial_position,
+                                                   double* iteration_cost, double* iteration_radius,
+                                                   int32_t* iteration_step_accepted, double* pair_residual,
+                                                   tmi_ba_nonlinear_position_summary* sum) {
+  if (!Bh || !opt || !view_position || !sum)
+    return bad_argument("nonlinear positions: null batch, options, view_position or summary");
+  memset(sum, 0, sizeof(*sum));
+  sum->termination = 2;
+  const double t0 = now_s();
+  // argument errors before the device is touched
+  if (const char* why = check_view_pair_batch(Bh, false, Bh->pair_position2)) return bad_argument(why);
+  if (const char* why = check_nonlinear_position_arguments(Bh, opt, fixed_view, view_position)) return bad_argument(why);
+  const int V = Bh->num_views, E = Bh->num_pairs, n = V - 1;
+  // the cap before anything of the views' size is allocated, the union-find included
+  if ((int64_t)3 * n > rotation_order_cap()) {
+    g_last_error = "nonlinear positions: 3 (num_views - 1) exceeds the dense solver's cap (see the header)";
+    return TMI_BA_ERR_UNSUPPORTED;
+  }
+  const int N = 3 * n;  // (<= the cap)
+  if (!every_view_reaches(Bh, fixed_view))
+    return bad_argument("nonlinear positions: a view is not connected to fixed_view");
+  const EdgeRows rows = build_edge_rows(V, E, Bh->pair_view1, Bh->pair_view2, fixed_view);
+  // the start: x [n][3] over the free views
+  std::vector<double> start((size_t)3 * V);
+  for (int v = 0; v < V; ++v)
+    for (int k = 0; k < 3; ++k)
+      start[(size_t)3 * v + k] = v == fixed_view ? 0.0
+                                 : opt->positions_given ? view_position[(size_t)3 * v + k]
+                                                        : nonlinear_position_start(opt->seed, v, k);
+  std::vector<double> x_h((size_t)N);
+  for (int v = 0; v < V; ++v)
+    if (v != fixed_view) std::copy(start.begin() + 3 * v, start.begin() + 3 * v + 3, x_h.begin() + 3 * (v - (v > fixed_view)));
+  const int max_it = opt->max_num_iterations;
+  const double width = opt->robust_loss_width;
+  std::vector<double> cost_trace, radius_trace;
+  std::vector<int32_t> outcome_trace;
+  return one_shot_batch(device, "nonlinear positions: no such device", E, t0, sum, [&](OneShot* s) -> int {
+    PositionGraph G;
+    memset(&G, 0, sizeof(G));
+    G.num_views = V;
+    G.num_pairs = E;
+    G.fixed_view = fixed_view;
+    int *d_v1, *d_v2, *d_ptr, *d_lptr, *d_flag;
+    int2 *d_row, *d_lrow;
+    double *d_pos, *d_t, *d_rot = nullptr, *d_x, *d_cand, *d_step, *d_y, *d_rhs, *d_tmp, *d_scale, *d_diag, *d_g, *d_gabs,
+        *d_rec, *d_res, *d_M, *d_A, *d_cdiag, *d_part, *d_norms;
+    TMI_HIP(s->upload(&d_v1, (const int*)Bh->pair_view1, (size_t)E));
+    TMI_HIP(s->upload(&d_v2, (const int*)Bh->pair_view2, (size_t)E));
+    TMI_HIP(s->upload(&d_ptr, rows.row_ptr.data(), rows.row_ptr.size()));
+    TMI_HIP(s->upload(&d_row, rows.row.data(), rows.row.size()));
+    TMI_HIP(s->upload(&d_lptr, rows.lap_ptr.data(), rows.lap_ptr.size()));
+    TMI_HIP(s->upload(&d_lrow, rows.lap_row.data(), rows.lap_row.size()));
+    TMI_HIP(s->upload(&d_pos, Bh->pair_position2, (size_t)3 * E));
+    d_t = d_pos;
+    if (Bh->view_rotation) {
+      TMI_HIP(s->upload(&d_rot, Bh->view_rotation, (size_t)3 * V));
+      TMI_HIP(s->alloc(&d_t, (size_t)3 * E));
+    }
+    TMI_HIP(s->upload(&d_x, x_h.data(), x_h.size()));
+    const std::vector<double> ones((size_t)N, 1.0);  // the scales without jacobi_scaling
+    TMI_HIP(s->upload(&d_scale, ones.data(), ones.size()));
+    TMI_HIP(s->alloc(&d_cand, (size_t)N));
+    TMI_HIP(s->alloc(&d_step, (size_t)N));
+    TMI_HIP(s->alloc(&d_y, (size_t)N));
+    TMI_HIP(s->alloc(&d_rhs, (size_t)N));
+    TMI_HIP(s->alloc(&d_tmp, (size_t)N));
+    TMI_HIP(s->alloc(&d_diag, (size_t)N));
+    TMI_HIP(s->alloc(&d_g, (size_t)N));
+    TMI_HIP(s->alloc(&d_gabs, (size_t)N));
+    TMI_HIP(s->alloc(&d_rec, (size_t)9 * E));
+    TMI_HIP(s->alloc(&d_res, (size_t)3 * E));
+    TMI_HIP(s->alloc(&d_M, (size_t)N * N));  // the assembled normal matrix, kept across rejected steps
+    TMI_HIP(s->alloc(&d_A, (size_t)N * N));  // its damped copy, overwritten by the factor
+    TMI_HIP(s->alloc(&d_cdiag, (size_t)kPanel * ((size_t)(N + kPanel - 1) / kPanel) * kPanel));
+    const int nbE = (E + 255) / 256, nbN = (N + 255) / 256, nbV = (n + 255) / 256;
+    // the blocks' parts: the cost and the model cost change [nbE each], |step|^2 and |candidate|^2 [nbN each]
+    TMI_HIP(s->alloc(&d_part, (size_t)2 * nbE + (size_t)2 * nbN));
+    TMI_HIP(s->alloc(&d_norms, 8));
+    TMI_HIP(s->alloc(&d_flag, 1));
+    double *p_cost = d_part, *p_mcc = p_cost + nbE, *p_step = p_mcc + nbE, *p_x = p_step + nbN;
+    PinnedWords pinned;  // [0..5) cost, model cost change, |step|^2, |candidate|^2, max |gradient|; then the pivot flag
+    TMI_HIP(pinned.alloc(8 * sizeof(double)));
+    double* h_norms = static_cast<double*>(pinned.p);
+    int* h_flag = reinterpret_cast<int*>(h_norms + 6);
+    G.pair_view1 = d_v1;
+    G.pair_view2 = d_v2;
+    G.t = d_t;
+    G.row_ptr = d_ptr;
+    G.row = d_row;
+    G.lap_ptr = d_lptr;
+    G.lap_row = d_lrow;
+    hipStream_t st = s->stream;
+    const dim3 edge_grid(nbE), entry_grid(nbN), view_grid(nbV), block(256);
+    TMI_HIP(hipMemsetAsync(d_flag, 0, sizeof(int), st));
+    TMI_HIP(hipMemsetAsync(d_y, 0, (size_t)N * sizeof(double), st));
+    ReduceJobs jobs;
+    memset(&jobs, 0, sizeof(jobs));
+    const double* parts[4] = {p_cost, p_mcc, p_step, p_x};
+    for (int q = 0; q < 4; ++q) {
+      jobs.part[q] = parts[q];
+      jobs.count[q] = q < 2 ? nbE : nbN;
+    }
+    // device time in three classes.  An iteration's marks: 0-1 the damped copy and the factorisation, 1-2 the
+    // substitution, 2-3 the step, the candidate and the reductions; a linearisation with its assembly has a timer of
+    // its own, read after the next synchronisation.
+    StreamTimer timer(st, 4), lin_timer(st, 2);
+    TMI_HIP(timer.status);
+    TMI_HIP(lin_timer.status);
+    double factor_seconds = 0.0, subst_seconds = 0.0, graph_seconds = 0.0;
+    bool lin_pending = false;
+    // the sums of the first `count` quantities and max |gradient| into h_norms, and the pivot flag
+    auto fetch = [&](int count) -> int {
+      hipLaunchKernelGGL(reduce_partials_kernel, dim3(count), block, 0, st, jobs, d_norms);
+      hipLaunchKernelGGL(nlp_absmax_kernel, dim3(1), block, 0, st, N, d_gabs, d_norms + 4);
+      if (timer.marked > 0) TMI_HIP(timer.mark());
+      const hipError_t le = hipGetLastError();
+      hipError_t ce = hipMemcpyAsync(h_norms, d_norms, 5 * sizeof(double), hipMemcpyDeviceToHost, st);
+      if (ce == hipSuccess) ce = hipMemcpyAsync(h_flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, st);
+      const hipError_t se = hipStreamSynchronize(st);
+      TMI_HIP(le);
+      TMI_HIP(ce);
+      TMI_HIP(se);
+      if (lin_pending) graph_seconds += lin_timer.seconds();
+      lin_pending = false;
+      return TMI_BA_OK;
+    };
+    // records, residuals and the cost parts at d_x, then M, its diagonal and the gradient
+    bool scaled = !opt->jacobi_scaling;
+    auto linearize = [&]() -> int {
+      lin_timer.marked = 0;
+      TMI_HIP(lin_timer.mark());
+      hipLaunchKernelGGL(nlp_edge_kernel<true>, edge_grid, block, 0, st, G, width, d_x, nullptr, d_rec, d_res, p_cost,
+                         nullptr);
+      if (!scaled) hipLaunchKernelGGL(nlp_scale_kernel, view_grid, block, 0, st, G, n, d_rec, d_scale);
+      scaled = true;
+      hipLaunchKernelGGL(nlp_assemble_kernel, dim3(n), block, 0, st, G, N, d_rec, d_scale, d_M, d_diag, d_g, d_gabs);
+      TMI_HIP(lin_timer.mark());
+      lin_pending = true;
+      return TMI_BA_OK;
+    };
+    int rc;
+
+    // ---- the directions, the first linearisation, its cost and |x| (the step kernel on y = 0) ----
+    if (Bh->view_rotation) hipLaunchKernelGGL(lud_direction_kernel, edge_grid, block, 0, st, E, d_rot, d_v1, d_pos, d_t);
+    if ((rc = linearize())) return rc;
+    hipLaunchKernelGGL(nlp_step_kernel, entry_grid, block, 0, st, N, d_x, d_scale, d_y, d_step, d_cand, p_step, p_x);
+    TMI_HIP(hipMemsetAsync(p_mcc, 0, (size_t)nbE * sizeof(double), st));
+    if ((rc = fetch(4))) return rc;
+    double cost = h_norms[0], x_norm = std::sqrt(h_norms[3]);
+    sum->initial_cost = cost;
+
+    // ---- TrustRegionMinimizer with the Levenberg-Marquardt strategy: the rules of tmi_ba_solver_solve ----
+    double radius = opt->initial_trust_region_radius, decrease_factor = 2.0;
+    int invalid_run = 0, iter = 0, termination = 1;
+    bool need_gradient_check = true;
+    cost_trace.push_back(cost);
+    radius_trace.push_back(radius);
+    outcome_trace.push_back(1);
+    auto record = [&](int outcome) {
+      cost_trace.push_back(cost);
+      radius_trace.push_back(radius);
+      outcome_trace.push_back(outcome);
+    };
+    for (;;) {
+      if (iter >= max_it) break;
+      ++iter;
+      timer.marked = 0;
+      TMI_HIP(timer.mark());
+      hipLaunchKernelGGL(nlp_copy_lower_kernel, dim3(N), block, 0, st, N, d_M, d_A);
+      hipLaunchKernelGGL(nlp_lm_diagonal_kernel, entry_grid, block, 0, st, N, d_diag, opt->min_lm_diagonal,
+                         opt->max_lm_diagonal, radius, d_A);
+      dense_cholesky_factor(d_A, N, d_cdiag, d_flag, st);
+      sum->num_factorizations++;
+      TMI_HIP(timer.mark());
+      TMI_HIP(hipMemcpyAsync(d_rhs, d_g, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, st));
+      dense_cholesky_substitute<1>(d_A, N, d_rhs, d_y, d_tmp, st);
+      TMI_HIP(timer.mark());
+      hipLaunchKernelGGL(nlp_step_kernel, entry_grid, block, 0, st, N, d_x, d_scale, d_y, d_step, d_cand, p_step, p_x);
+      hipLaunchKernelGGL(nlp_edge_kernel<false>, edge_grid, block, 0, st, G, width, d_cand, d_step, d_rec, nullptr,
+                         p_cost, p_mcc);
+      if ((rc = fetch(4))) return rc;
+      factor_seconds += timer.seconds(0, 1);
+      subst_seconds += timer.seconds(1, 2);
+      graph_seconds += timer.seconds(2, 3);
+      bool usable = true;
+      if (*h_flag) {  // a non-positive pivot: the linear solve failed, an invalid step as in Ceres
+        usable = false;
+        TMI_HIP(hipMemsetAsync(d_flag, 0, sizeof(int), st));
+      }
+      if (need_gradient_check) {
+        need_gradient_check = false;
+        if (!(h_norms[4] > opt->gradient_tolerance)) {
+          termination = 0;
+          --iter;
+          break;
+        }
+      }
+      const double cand_cost = h_norms[0], model_cost_change = h_norms[1], step_sq = h_norms[2], cand_x_sq = h_norms[3];
+      if (!(model_cost_change > 0.0)) usable = false;
+      if (!usable) {
+        // HandleInvalidStep
+        sum->num_unsuccessful_steps++;
+        if (++invalid_run >= opt->max_num_consecutive_invalid_steps) {
+          record(-1);
+          termination = 2;
+          break;
+        }
+        radius /= decrease_factor;
+        decrease_factor *= 2.0;
+        record(-1);
+        if (radius < opt->min_trust_region_radius) {
+          termination = 0;
+          break;
+        }
+        continue;
+      }
+      invalid_run = 0;
+      if (std::sqrt(step_sq) <= opt->parameter_tolerance * (x_norm + opt->parameter_tolerance)) {
+        record(2);
+        termination = 0;
+        break;
+      }
+      const double cost_change = cost - cand_cost;
+      if (std::fabs(cost_change) <= opt->function_tolerance * cost) {
+        record(3);
+        termination = 0;
+        break;
+      }
+      const double relative_decrease = cost_change / model_cost_change;
+      if (relative_decrease > opt->min_relative_decrease) {  // IsStepSuccessful
+        std::swap(d_x, d_cand);
+        cost = cand_cost;
+        x_norm = std::sqrt(cand_x_sq);
+        sum->num_successful_steps++;
+        radius = radius / std::fmax(1.0 / 3.0, 1.0 - std::pow(2.0 * relative_decrease - 1.0, 3));
+        radius = std::fmin(opt->max_trust_region_radius, radius);
+        decrease_factor = 2.0;
+        if ((rc = linearize())) return rc;
+        need_gradient_check = true;
+        record(1);
+      } else {
+        sum->num_unsuccessful_steps++;
+        radius /= decrease_factor;
+        decrease_factor *= 2.0;
+        record(0);
+      }
+      if (radius < opt->min_trust_region_radius) {
+        termination = 0;
+        break;
+      }
+    }
+
+    // the results, only now: a failure above leaves the caller's arrays as they were
+    std::vector<double> res_h(pair_residual ? (size_t)3 * E : 0);
+    TMI_HIP(hipMemcpyAsync(x_h.data(), d_x, x_h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (pair_residual) TMI_HIP(hipMemcpyAsync(res_h.data(), d_res, res_h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    TMI_HIP(hipStreamSynchronize(st));
+    if (lin_pending) graph_seconds += lin_timer.seconds();
+    for (int v = 0; v < V; ++v)
+      for (int k = 0; k < 3; ++k)
+        view_position[(size_t)3 * v + k] = v == fixed_view ? 0.0 : x_h[(size_t)3 * (v - (v > fixed_view)) + k];
+    if (initial_position) std::copy(start.begin(), start.end(), initial_position);
+    if (pair_residual) std::copy(res_h.begin(), res_h.end(), pair_residual);
+    if (iteration_cost) std::copy(cost_trace.begin(), cost_trace.end(), iteration_cost);
+    if (iteration_radius) std::copy(radius_trace.begin(), radius_trace.end(), iteration_radius);
+    if (iteration_step_accepted) std::copy(outcome_trace.begin(), outcome_trace.end(), iteration_step_accepted);
+    sum->num_views = V;
+    sum->num_pairs = E;
+    sum->num_iterations = iter;
+    sum->termination = termination;
+    sum->usable = termination != 2;
+    sum->final_cost = cost;
+    sum->factor_seconds = factor_seconds;
+    sum->substitution_seconds = subst_seconds;
+    sum->graph_seconds = graph_seconds;
+    sum->kernel_seconds = factor_seconds + subst_seconds + graph_seconds;
+    return TMI_BA_OK;
+  });
+}
 
 // ---- batched LocalizeViewToReconstruction: P3P RANSAC (localize_kernels.h) ---------------------
 void tmi_ba_localization_options_init(tmi_ba_localization_options* o) {

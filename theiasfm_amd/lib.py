@@ -38,6 +38,7 @@ EXPORTS = (
     "tmi_ba_filter_view_pairs_from_orientation",
     "tmi_ba_robust_rotation_options_init", "tmi_ba_estimate_global_rotations_robust",
     "tmi_ba_lud_position_options_init", "tmi_ba_estimate_global_positions_lud",
+    "tmi_ba_nonlinear_position_options_init", "tmi_ba_estimate_global_positions_nonlinear",
     "tmi_ba_localization_options_init", "tmi_ba_localize_views",
     "tmi_ba_match_options_init", "tmi_ba_match_features",
     "tmi_ba_cascade_match_options_init", "tmi_ba_match_features_cascade",
@@ -183,6 +184,13 @@ def load():
         PB, LO, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
         C.POINTER(abi.CLudPositionSummary)]
     L.tmi_ba_estimate_global_positions_lud.restype = C.c_int32
+    NO = C.POINTER(abi.CNonlinearPositionOptions)
+    L.tmi_ba_nonlinear_position_options_init.argtypes = [NO]
+    L.tmi_ba_nonlinear_position_options_init.restype = None
+    L.tmi_ba_estimate_global_positions_nonlinear.argtypes = [
+        PB, NO, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+        C.POINTER(abi.CNonlinearPositionSummary)]
+    L.tmi_ba_estimate_global_positions_nonlinear.restype = C.c_int32
     ZO = C.POINTER(abi.CLocalizationOptions)
     L.tmi_ba_localization_options_init.argtypes = [ZO]
     L.tmi_ba_localization_options_init.restype = None
@@ -560,6 +568,37 @@ def estimate_global_positions_lud(batch: abi.ViewPairBatch, fixed_view: int = 0,
     ran = ps.num_admm_iterations
     return dict(positions=pos, scales=scales, residuals=res, r_norms=r_norms[:ran].copy(), s_norms=s_norms[:ran].copy(),
                 summary=ps)
+
+
+def estimate_global_positions_nonlinear(batch: abi.ViewPairBatch, fixed_view: int = 0, options=None, device: int = -1,
+                                        start=None):
+    """NonlinearPositionEstimator::EstimatePositions on the device.  batch.view_rotation None: batch.pair_position2 is
+    already in the global frame.  options: a CNonlinearPositionOptions (default: the reference's).  start [V, 3]: the
+    positions to start from, required exactly when options.positions_given (not modified).
+    Returns a dict: positions [V, 3] (the fixed view at 0), initial_positions [V, 3], residuals [P, 3], costs, radii and
+    outcomes (entry 0 the start, then one per iteration run: 1 accepted, 0 rejected, -1 invalid, 2 / 3 ended by the
+    parameter / function tolerance), summary (CNonlinearPositionSummary).  Raises EngineError on any failure."""
+    L = load()
+    o = options if options is not None else abi.nonlinear_position_options()
+    if bool(o.positions_given) != (start is not None):
+        raise ValueError("start goes with options.positions_given")
+    k = max(int(o.max_num_iterations), 0) + 1
+    pos = np.zeros((batch.num_views, 3)) if start is None else np.array(start, dtype=np.float64).reshape(-1, 3)
+    if pos.shape[0] != batch.num_views:
+        raise ValueError("start must hold batch.num_views rows")
+    initial = np.zeros((batch.num_views, 3))
+    res = np.zeros((batch.num_pairs, 3))
+    costs, radii, outcomes = np.zeros(k), np.zeros(k), np.zeros(k, dtype=np.int32)
+    cb = batch.as_c()
+    ps = abi.CNonlinearPositionSummary()
+    st = L.tmi_ba_estimate_global_positions_nonlinear(
+        C.byref(cb), C.byref(o), int(fixed_view), int(device), pos.ctypes.data, initial.ctypes.data, costs.ctypes.data,
+        radii.ctypes.data, outcomes.ctypes.data, res.ctypes.data, C.byref(ps))
+    if st != 0:
+        raise EngineError(st, "tmi_ba_estimate_global_positions_nonlinear")
+    ran = ps.num_iterations + 1
+    return dict(positions=pos, initial_positions=initial, residuals=res, costs=costs[:ran].copy(),
+                radii=radii[:ran].copy(), outcomes=outcomes[:ran].copy(), summary=ps)
 
 
 def localize_views(problem: abi.Problem, view_error_threshold, options=None, ba_options=None, view_mask=None,
