@@ -1,25 +1,16 @@
 // Batched LocalizeViewToReconstruction, calibrated path (localize_view_to_reconstruction.cc:185-198): RANSAC over P3P
-// for many candidate views at once, as a chunked evaluate-then-replay loop (the loop itself is the host's,
-// side_calls.h).  Per call one preparation launch, per chunk of iterations three launches, one final launch:
+// for many candidate views at once, on the chunked evaluate-then-replay scaffold of ransac_core.h (the loop itself is
+// the host's, side_calls.h).  What is this call's own: one preparation launch, the problem the scaffold's three
+// per-chunk kernels are instantiated with, one final launch:
 //
 //   localize_prepare_kernel     one thread per correspondence: the normalised feature
 //                               (PixelToNormalizedCoordinates(pixel).hnormalized(), pixel_to_camera) and the world
 //                               point (point.hnormalized()), structure of arrays in view-major order
-//   localize_hypothesis_kernel  one thread per (active view, iteration of the chunk): the sample, PoseFromThreePoints
-//                               (perspective_three_point.cc) and position = -R^T t: four poses or none
-//   localize_score_kernel       one wavefront per (active view, iteration): the lanes stride over the view's
-//                               correspondences, all four poses are scored per load, the four integer costs come out
-//                               of a wave reduction of fixed shape
-//   localize_replay_kernel      one thread per active view: SampleConsensusEstimator::Estimate's loop
-//                               (sample_consensus_estimator.h:276-330) over the chunk's costs in (iteration, solution)
-//                               order -- best model, max_iterations, the done flag
+//   LocalizeProblem             a sample of three, PoseFromThreePoints (perspective_three_point.cc) and position =
+//                               -R^T t: four poses or none; one wavefront scores all four poses of an iteration per load
+//                               of a correspondence; the squared reprojection error against the threshold
 //   localize_final_kernel       one wavefront per selected view: the best model's inlier mask and count (:332-341),
 //                               the status, and the pose into the extrinsics of a localised view
-//
-// A view's outcome depends only on the ORDER in which its integer costs are replayed, never on the chunk length:
-// iterations at or beyond the view's current max_iterations are not evaluated, those evaluated beyond the point where
-// the replay stops are discarded.  ComputeMaxIterations is a host-made table over the inlier count (log and pow of the
-// host's libm, so that a CPU model gets the same integers).
 //
 // The arithmetic of the hypothesis, scoring and final kernels is never contracted into FMA (#pragma clang fp
 // contract(off) in every body) and uses only + - * / and sqrt, which round correctly: a CPU model that evaluates the
@@ -28,55 +19,24 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "ransac_core.h"
 #include "rotation_kernels.h"
 #include "track_estimate_kernels.h"
+#include "vec3.h"
 
 namespace tmi {
 
-constexpr int kLocalizeMaxIterations = 1 << 20;
 constexpr int kQuarticBisections = 200;  // of the resolvent cubic; stops early at neighbouring doubles
 
-// Per selected view: what the replay carries from chunk to chunk.
-struct LocalizeState {
-  int best_cost;        // INT_MAX: no model yet
-  int best_iteration;   // -1
-  int best_solution;    // -1
-  int max_iterations;   // the loop bound, only ever lowered
-  int num_iterations;   // iterations replayed
-  int done;
-  int pad[2];
-  double pose[12];      // the best model: R row-major, then the position
-};
-
-struct LocalizeBatch {
-  int num_selected;
-  int max_iterations;             // the options' value: the stride of samples and hypothesis_cost
-  int chunk;
-  int chunk_start;
-  unsigned long long seed;
-  // static per call
-  const int* sel_view;            // [num_selected] camera index
-  const long long* sel_ptr;       // [num_selected + 1] the view's correspondences in the arrays below
-  const double* threshold;        // [num_selected]
-  const int* samples;             // caller's table [3 max_iterations num_cameras], or null
-  const int* bound_table;         // ComputeMaxIterations per inlier count: view s, count k at sel_ptr[s] + s + k
-  double *fx, *fy, *wx, *wy, *wz; // [M] prepared correspondences
-  // per chunk
-  const int* active;              // [num_active] selected-view slots still running
-  int num_active;
-  double* poses;                  // [num_active chunk 4 12]
-  int* num_solutions;             // [num_active chunk] 0 or 4
-  int* cost;                      // [num_active chunk 4]
-  LocalizeState* state;           // [num_selected]
-  int* hypothesis_cost;           // [num_selected max_iterations 4] or null
-};
+// The correspondence planes of RansacBatch: the normalised feature, then the world point.
+enum { kLocFx, kLocFy, kLocWx, kLocWy, kLocWz };
 
 __global__ __launch_bounds__(256) void localize_prepare_kernel(long long M, const unsigned long long* __restrict__ keys,
                                                                const int* __restrict__ slot_pt,
                                                                const double* __restrict__ obs_xy,
                                                                const double* __restrict__ pts,
                                                                const int4* __restrict__ cam,
-                                                               const double* __restrict__ intr, LocalizeBatch B) {
+                                                               const double* __restrict__ intr, RansacBatch B) {
   const long long o = (long long)blockIdx.x * 256 + threadIdx.x;
   if (o >= M) return;
   const int c = (int)(keys[o] >> 32);
@@ -88,57 +48,13 @@ __global__ __launch_bounds__(256) void localize_prepare_kernel(long long M, cons
   double u[3];
   pixel_to_camera(rec.x, K, px, u);
   const double* X = pts + 4 * (long long)slot_pt[o];
-  B.fx[o] = u[0];
-  B.fy[o] = u[1];
-  B.wx[o] = X[0] / X[3];
-  B.wy[o] = X[1] / X[3];
-  B.wz[o] = X[2] / X[3];
+  B.plane[kLocFx][o] = u[0];
+  B.plane[kLocFy][o] = u[1];
+  B.plane[kLocWx][o] = X[0] / X[3];
+  B.plane[kLocWy][o] = X[1] / X[3];
+  B.plane[kLocWz][o] = X[2] / X[3];
 }
 
-// Word c of the splitmix64 stream from state `seed`: the output mix of seed + (c + 1) gamma.
-__device__ __forceinline__ unsigned long long splitmix64_word(unsigned long long seed, unsigned long long c) {
-  unsigned long long z = seed + (c + 1ull) * 0x9e3779b97f4a7c15ull;
-  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-  return z ^ (z >> 31);
-}
-
-// The sample of iteration i of camera v among n correspondences: three swaps of a partial Fisher-Yates on the identity.
-__device__ __forceinline__ void localize_sample(unsigned long long seed, int v, int i, int n, int s[3]) {
-#pragma clang fp contract(off)
-  int j[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const unsigned long long c = 3ull * (((unsigned long long)(unsigned)v << 32) + (unsigned long long)i) + k;
-    const double u = ((double)(splitmix64_word(seed, c) >> 11) + 0.5) * (1.0 / 9007199254740992.0);
-    int jk = k + (int)(u * (double)(n - k));
-    j[k] = jk < n - 1 ? jk : n - 1;  // (u < 1, so the product is below n - k; the clamp costs nothing)
-  }
-  // the three swaps on the identity, without the array: position 0 is final after the first swap, position 1 after the
-  // second; before the third, position j >= 2 holds what the second swap put there, else what the first did, else j
-  const int cur1 = j[0] == 1 ? 0 : 1;
-  s[0] = j[0];
-  s[1] = j[1] == 1 ? cur1 : (j[1] == j[0] ? 0 : j[1]);
-  s[2] = j[2] == j[1] ? cur1 : (j[2] == j[0] ? 0 : j[2]);
-}
-
-__host__ __device__ __forceinline__ void cross3(const double a[3], const double b[3], double c[3]) {
-#pragma clang fp contract(off)
-  c[0] = a[1] * b[2] - a[2] * b[1];
-  c[1] = a[2] * b[0] - a[0] * b[2];
-  c[2] = a[0] * b[1] - a[1] * b[0];
-}
-__host__ __device__ __forceinline__ double dot3(const double a[3], const double b[3]) {
-#pragma clang fp contract(off)
-  return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2];
-}
-__host__ __device__ __forceinline__ void normalize3(double a[3]) {
-#pragma clang fp contract(off)
-  const double n = sqrt(dot3(a, a));
-  a[0] = a[0] / n;
-  a[1] = a[1] / n;
-  a[2] = a[2] / n;
-}
 // rows: tx = f0, tz = (f0 x f1) normalised, ty = tz x tx
 __device__ __forceinline__ void p3p_frame(const double f0[3], const double f1[3], double T[9]) {
 #pragma clang fp contract(off)
@@ -345,40 +261,6 @@ __device__ bool p3p_poses(const double feat[3][2], const double Xw[3][3], double
   return true;
 }
 
-// (register-heavy fp64: a launch of its own, like the ray code of the two-view verification)
-__global__ __launch_bounds__(64) void localize_hypothesis_kernel(LocalizeBatch B) {
-  const long long id = (long long)blockIdx.x * 64 + threadIdx.x;
-  if (id >= (long long)B.num_active * B.chunk) return;
-  const int a = (int)(id / B.chunk), j = (int)(id % B.chunk);
-  const int s = B.active[a];
-  const int i = B.chunk_start + j;
-  B.num_solutions[id] = 0;
-  if (i >= B.state[s].max_iterations) return;
-  const long long o0 = B.sel_ptr[s];
-  const int n = (int)(B.sel_ptr[s + 1] - o0);
-  const int v = B.sel_view[s];
-  int smp[3];
-  if (B.samples) {
-    const int* t = B.samples + 3 * ((long long)B.max_iterations * v + i);
-    smp[0] = t[0];
-    smp[1] = t[1];
-    smp[2] = t[2];
-  } else {
-    localize_sample(B.seed, v, i, n, smp);
-  }
-  double feat[3][2], X[3][3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const long long o = o0 + smp[k];
-    feat[k][0] = B.fx[o];
-    feat[k][1] = B.fy[o];
-    X[k][0] = B.wx[o];
-    X[k][1] = B.wy[o];
-    X[k][2] = B.wz[o];
-  }
-  if (p3p_poses(feat, X, B.poses + 48 * id)) B.num_solutions[id] = 4;
-}
-
 // 1 where the squared reprojection error |hnormalized(R (X - c)) - feature|^2 is not below the threshold (NaN included)
 __device__ __forceinline__ int localize_outlier(const double* __restrict__ P, double X, double Y, double Z, double fx,
                                                 double fy, double thresh) {
@@ -391,83 +273,29 @@ __device__ __forceinline__ int localize_outlier(const double* __restrict__ P, do
   return (du * du + dv * dv) < thresh ? 0 : 1;
 }
 
-__global__ __launch_bounds__(256) void localize_score_kernel(LocalizeBatch B) {
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int lane = threadIdx.x & 63;
-  const long long id = (long long)blockIdx.x * 4 + wave;
-  if (id >= (long long)B.num_active * B.chunk) return;
-  if (B.num_solutions[id] == 0) return;
-  const int s = B.active[(int)(id / B.chunk)];
-  const long long o0 = B.sel_ptr[s];
-  const int n = (int)(B.sel_ptr[s + 1] - o0);
-  const double thresh = B.threshold[s];
-  const double* __restrict__ P = B.poses + 48 * id;
-  int c0 = 0, c1 = 0, c2 = 0, c3 = 0;
-  for (int m = lane; m < n; m += 64) {
-    const long long o = o0 + m;
-    const double X = B.wx[o], Y = B.wy[o], Z = B.wz[o], fx = B.fx[o], fy = B.fy[o];
-    c0 += localize_outlier(P, X, Y, Z, fx, fy, thresh);
-    c1 += localize_outlier(P + 12, X, Y, Z, fx, fy, thresh);
-    c2 += localize_outlier(P + 24, X, Y, Z, fx, fy, thresh);
-    c3 += localize_outlier(P + 36, X, Y, Z, fx, fy, thresh);
-  }
+struct LocalizeProblem {
+  static constexpr int kSample = 3, kSlots = 4, kModel = 12, kScoreSlots = 4, kPlanes = 5, kThreads = 64, kSlab = 0;
+  // four poses or none, so the four flags are equal
+  __device__ static void models(const double pts[kPlanes][kSample], double*, double* __restrict__ poses, int* has) {
+    double feat[3][2], X[3][3];
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    c0 += __shfl_xor(c0, off, 64);
-    c1 += __shfl_xor(c1, off, 64);
-    c2 += __shfl_xor(c2, off, 64);
-    c3 += __shfl_xor(c3, off, 64);
-  }
-  if (lane == 0) *reinterpret_cast<int4*>(B.cost + 4 * id) = make_int4(c0, c1, c2, c3);
-}
-
-__global__ __launch_bounds__(64) void localize_replay_kernel(LocalizeBatch B) {
-  const int a = blockIdx.x * 64 + threadIdx.x;
-  if (a >= B.num_active) return;
-  const int s = B.active[a];
-  LocalizeState st = B.state[s];
-  const long long o0 = B.sel_ptr[s];
-  const int n = (int)(B.sel_ptr[s + 1] - o0);
-  const int* __restrict__ bound = B.bound_table + o0 + s;
-  int best_j = -1;
-  for (int j = 0; j < B.chunk; ++j) {
-    const int i = B.chunk_start + j;
-    if (i >= st.max_iterations) break;
-    const long long id = (long long)a * B.chunk + j;
-    const bool model = B.num_solutions[id] != 0;
-    int4 c = make_int4(-1, -1, -1, -1);
-    if (model) {
-      c = *reinterpret_cast<const int4*>(B.cost + 4 * id);
-      const int ck[4] = {c.x, c.y, c.z, c.w};
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        if (ck[k] < st.best_cost) {
-          st.best_cost = ck[k];
-          st.best_iteration = i;
-          st.best_solution = k;
-          best_j = j;
-          const int inliers = n - ck[k];
-          if (inliers < 3) continue;  // inlier_ratio < 3 / n
-          const int m = bound[inliers];
-          if (m < st.max_iterations) st.max_iterations = m;
-        }
-      }
+    for (int k = 0; k < 3; ++k) {
+      feat[k][0] = pts[kLocFx][k];
+      feat[k][1] = pts[kLocFy][k];
+      X[k][0] = pts[kLocWx][k];
+      X[k][1] = pts[kLocWy][k];
+      X[k][2] = pts[kLocWz][k];
     }
-    if (B.hypothesis_cost) *reinterpret_cast<int4*>(B.hypothesis_cost + 4 * ((long long)s * B.max_iterations + i)) = c;
-    st.num_iterations = i + 1;
+    if (p3p_poses(feat, X, poses)) has[0] = has[1] = has[2] = has[3] = 1;
   }
-  if (st.num_iterations >= st.max_iterations) st.done = 1;
-  if (best_j >= 0) {
-    const double* P = B.poses + 48 * ((long long)a * B.chunk + best_j) + 12 * st.best_solution;
-#pragma unroll
-    for (int q = 0; q < 12; ++q) st.pose[q] = P[q];
+  __device__ __forceinline__ static int outlier(const double* __restrict__ P, const double x[kPlanes], double thresh) {
+    return localize_outlier(P, x[kLocWx], x[kLocWy], x[kLocWz], x[kLocFx], x[kLocFy], thresh);
   }
-  B.state[s] = st;
-}
+};
 
 // One wavefront per selected view.  status: 2 no model, 3 fewer than min_num_inliers inliers, 0 localised (the pose
 // goes to ext: position, then Ceres' RotationMatrixToAngleAxis of R).
-__global__ __launch_bounds__(64) void localize_final_kernel(LocalizeBatch B, int min_num_inliers,
+__global__ __launch_bounds__(64) void localize_final_kernel(RansacBatch B, int min_num_inliers,
                                                             unsigned char* __restrict__ slot_inlier,
                                                             int* __restrict__ num_inliers,
                                                             signed char* __restrict__ status, double* __restrict__ pose_out,
@@ -475,30 +303,10 @@ __global__ __launch_bounds__(64) void localize_final_kernel(LocalizeBatch B, int
 #pragma clang fp contract(off)
   const int s = blockIdx.x;
   const int lane = threadIdx.x;
-  const LocalizeState* st = B.state + s;
-  const long long o0 = B.sel_ptr[s];
-  const int n = (int)(B.sel_ptr[s + 1] - o0);
-  if (st->best_iteration < 0) {
-    for (int m = lane; m < n; m += 64) slot_inlier[o0 + m] = 0;
-    if (lane == 0) {
-      num_inliers[s] = 0;
-      status[s] = 2;
-    }
-    return;
-  }
-  const double thresh = B.threshold[s];
-  const double* P = st->pose;
-  int count = 0;
-  for (int m = lane; m < n; m += 64) {
-    const long long o = o0 + m;
-    const int out = localize_outlier(P, B.wx[o], B.wy[o], B.wz[o], B.fx[o], B.fy[o], thresh);
-    slot_inlier[o] = (unsigned char)(1 - out);
-    count += 1 - out;
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) count += __shfl_xor(count, off, 64);
+  const int count = ransac_final_inliers<LocalizeProblem>(B, s, lane, slot_inlier, num_inliers, status);
+  if (count < 0) return;
+  const double* P = B.state[s].model;
   if (lane == 0) {
-    num_inliers[s] = count;
     const int code = count < min_num_inliers ? 3 : 0;
     status[s] = (signed char)code;
     double Rc[9], aa[3];  // column-major for rotation_matrix_to_angle_axis
@@ -515,7 +323,7 @@ __global__ __launch_bounds__(64) void localize_final_kernel(LocalizeBatch B, int
     po[4] = aa[1];
     po[5] = aa[2];
     if (code == 0) {
-      double* e = ext + 6 * (long long)B.sel_view[s];
+      double* e = ext + 6 * (long long)B.sel_item[s];
 #pragma unroll
       for (int q = 0; q < 6; ++q) e[q] = po[q];
     }

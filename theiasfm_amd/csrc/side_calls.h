@@ -2537,6 +2537,217 @@ int32_t tmi_ba_estimate_global_positions_nonlinear(const tmi_ba_view_pair_batch*
   });
 }
 
+}  // extern "C"
+
+// ---- the sample-consensus scaffold of the batched RANSAC calls (ransac_core.h) -----------------
+namespace {
+// SampleConsensusEstimator::ComputeMaxIterations (sample_consensus_estimator.h:215-243) for a sample of sample_size,
+// without the T(d,d) test.
+int ransac_max_iterations(double inlier_ratio, double log_failure_prob, int min_iterations, int max_iterations,
+                          double sample_size) {
+  if (inlier_ratio == 1.0) return min_iterations;
+  const double log_prob = std::log(1.0 - std::pow(inlier_ratio, sample_size)) - std::numeric_limits<double>::epsilon();
+  const double num_iterations = log_failure_prob / log_prob;
+  return (int)std::max((double)min_iterations, std::min(num_iterations, (double)max_iterations));
+}
+
+// The CHECKs of the SampleConsensusEstimator constructor (sample_consensus_estimator.h:191-197) and the limits of the
+// chunked loop, on either options struct.  Null: nothing is wrong; else the message, for the call to prefix.
+template <class Options>
+const char* ransac_options_error(const Options* L, const int32_t* samples, int32_t samples_given) {
+  if (!(L->failure_probability > 0.0 && L->failure_probability < 1.0)) return "failure_probability must be in (0, 1)";
+  if (!(L->min_inlier_ratio >= 0.0 && L->min_inlier_ratio <= 1.0)) return "min_inlier_ratio must be in [0, 1]";
+  if (L->min_iterations < 0 || L->max_iterations < L->min_iterations)
+    return "max_iterations < min_iterations, or a negative count";
+  if (L->max_iterations > kRansacMaxIterations) return "max_iterations above 2^20";
+  if (L->chunk_iterations < 0) return "negative chunk_iterations";
+  if (samples_given && !samples) return "samples_given without samples";
+  return nullptr;
+}
+
+// The caller's per-item arrays (each may be null).
+struct RansacItemArrays {
+  int8_t* status;
+  int32_t *num_inliers, *num_iterations, *best_iteration, *best_solution;
+  double* confidence;
+};
+
+// One call's host half of the chunked evaluate-then-replay loop over S attempted items (a view, a view pair) with M
+// correspondences in all: plan(), upload<P>() and chunks<P>(), then the call's final kernel into d_status,
+// d_num_inliers and d_slot_inlier, then read_back() and item_results() per item.  P is the problem of ransac_core.h.
+struct RansacRun {
+  std::vector<long long> sel_ptr;  // [S + 1] the call fills this before plan()
+  int S = 0, K = 0, chunk = 1, chunks_run = 0;
+  size_t M = 0;
+  double sample_size = 0.0;
+  std::vector<int> bound;
+  std::vector<RansacState> state;
+  RansacBatch B;
+  int* d_active = nullptr;
+  unsigned char* d_slot_inlier = nullptr;
+  int* d_num_inliers = nullptr;
+  signed char* d_status = nullptr;
+  std::vector<signed char> status;
+  std::vector<int> num_inliers;
+  std::vector<unsigned char> slot_inlier;
+
+  // ComputeMaxIterations per item and inlier count with the host's log and pow, the initial bound from
+  // min_inlier_ratio, the states and the chunk length.
+  template <class Options>
+  void plan(const Options* L, int sample) {
+    S = (int)sel_ptr.size() - 1;
+    K = L->max_iterations;
+    M = (size_t)sel_ptr[S];
+    sample_size = (double)sample;
+    const double log_failure_prob = std::log(L->failure_probability);
+    bound.resize(M + (size_t)S);
+    state.resize((size_t)S);
+    int initial_bound = K;
+    if (L->min_inlier_ratio > 0.0)
+      initial_bound =
+          std::min(ransac_max_iterations(L->min_inlier_ratio, log_failure_prob, L->min_iterations, K, sample_size), K);
+    for (int s = 0; s < S; ++s) {
+      const int n = (int)(sel_ptr[(size_t)s + 1] - sel_ptr[s]);
+      int* row = bound.data() + sel_ptr[s] + s;
+      for (int k = 0; k <= n; ++k)
+        row[k] = k < sample ? K
+                            : ransac_max_iterations((double)k / (double)n, log_failure_prob, L->min_iterations, K, sample_size);
+      RansacState& st = state[s];
+      memset(&st, 0, sizeof(st));
+      st.best_cost = INT32_MAX;
+      st.best_iteration = st.best_solution = -1;
+      st.max_iterations = initial_bound;
+      st.done = initial_bound <= 0;
+    }
+    // the engine's choice of chunk: the common case -- the run stops at min_iterations -- is a single chunk
+    chunk = L->chunk_iterations ? L->chunk_iterations : std::max(L->min_iterations, 64);
+    chunk = std::max(1, std::min(chunk, std::max(K, 1)));
+  }
+
+  // Everything of B but the correspondence planes, and the final kernel's outputs.  samples: the caller's table of
+  // num_items rows, or null.
+  template <class P>
+  int upload(OneShot* s, uint64_t seed, const std::vector<int>& sel_item, const std::vector<unsigned>& sel_stream,
+             const std::vector<double>& thresh, const int32_t* samples, size_t num_items, bool want_hypothesis_cost) {
+    memset(&B, 0, sizeof(B));
+    const size_t slots = (size_t)S * chunk * P::kSlots, hyp = (size_t)S * K * P::kSlots;
+    int *d_sel_item, *d_bound, *d_samples = nullptr;
+    unsigned* d_sel_stream;
+    long long* d_sel_ptr;
+    double* d_thresh;
+    TMI_HIP(s->upload(&d_sel_item, sel_item.data(), sel_item.size()));
+    TMI_HIP(s->upload(&d_sel_stream, sel_stream.data(), sel_stream.size()));
+    TMI_HIP(s->upload(&d_sel_ptr, (const long long*)sel_ptr.data(), sel_ptr.size()));
+    TMI_HIP(s->upload(&d_thresh, thresh.data(), thresh.size()));
+    TMI_HIP(s->upload(&d_bound, (const int*)bound.data(), bound.size()));
+    TMI_HIP(s->upload(&B.state, (const RansacState*)state.data(), state.size()));
+    if (samples) TMI_HIP(s->upload(&d_samples, (const int*)samples, (size_t)P::kSample * K * num_items));
+    TMI_HIP(s->alloc(&d_active, (size_t)S));
+    TMI_HIP(s->alloc(&B.models, slots * P::kModel));
+    TMI_HIP(s->alloc(&B.has_model, slots));
+    TMI_HIP(s->alloc(&B.cost, slots));
+    TMI_HIP(s->alloc(&d_slot_inlier, M));
+    TMI_HIP(s->alloc(&d_num_inliers, (size_t)S));
+    TMI_HIP(s->alloc(&d_status, (size_t)S));
+    if (want_hypothesis_cost) {
+      TMI_HIP(s->alloc(&B.hypothesis_cost, hyp));
+      TMI_HIP(hipMemsetAsync(B.hypothesis_cost, 0xff, std::max<size_t>(hyp, 1) * sizeof(int), s->stream));
+    }
+    B.num_selected = S;
+    B.max_iterations = K;
+    B.chunk = chunk;
+    B.seed = seed;
+    B.sel_item = d_sel_item;
+    B.sel_stream = d_sel_stream;
+    B.sel_ptr = d_sel_ptr;
+    B.threshold = d_thresh;
+    B.samples = d_samples;
+    B.bound_table = d_bound;
+    B.active = d_active;
+    return TMI_BA_OK;
+  }
+
+  // The chunk loop: bounded by ceil(max_iterations / chunk) whatever the device reports.  phases (or null): the
+  // summary that has fields for the device time of the three launches.
+  template <class P>
+  int chunks(OneShot* s, tmi_ba_two_view_ransac_summary* phases) {
+    const hipStream_t stream = s->stream;
+    std::vector<int> active;
+    const int max_chunks = (K + chunk - 1) / chunk;
+    for (int ch = 0; ch < max_chunks; ++ch) {
+      active.clear();
+      for (int v = 0; v < S; ++v)
+        if (!state[v].done) active.push_back(v);
+      if (active.empty()) break;
+      TMI_HIP(hipMemcpyAsync(d_active, active.data(), active.size() * sizeof(int), hipMemcpyHostToDevice, stream));
+      B.num_active = (int)active.size();
+      B.chunk_start = ch * chunk;
+      const long long items = (long long)B.num_active * chunk;
+      StreamTimer phase(stream, phases ? 4 : 0);
+      TMI_HIP(phase.status);
+      if (phases) TMI_HIP(phase.mark());
+      hipLaunchKernelGGL(ransac_hypothesis_kernel<P>, dim3((unsigned)((items + P::kThreads - 1) / P::kThreads)),
+                         dim3(P::kThreads), 0, stream, B);
+      if (phases) TMI_HIP(phase.mark());
+      hipLaunchKernelGGL(ransac_score_kernel<P>, dim3((unsigned)((items * (P::kSlots / P::kScoreSlots) + 3) / 4)),
+                         dim3(256), 0, stream, B);
+      if (phases) TMI_HIP(phase.mark());
+      hipLaunchKernelGGL(ransac_replay_kernel<P>, dim3((unsigned)((B.num_active + 63) / 64)), dim3(64), 0, stream, B);
+      if (phases) TMI_HIP(phase.mark());
+      TMI_HIP(hipGetLastError());
+      TMI_HIP(hipMemcpyAsync(state.data(), B.state, state.size() * sizeof(RansacState), hipMemcpyDeviceToHost, stream));
+      TMI_HIP(hipStreamSynchronize(stream));  // (also: `active` is free to change)
+      if (phases) {
+        phases->hypothesis_seconds += phase.seconds(0, 1);
+        phases->score_seconds += phase.seconds(1, 2);
+        phases->replay_seconds += phase.seconds(2, 3);
+      }
+      ++chunks_run;
+    }
+    return TMI_BA_OK;
+  }
+
+  // After the final kernel: the statuses, the inlier counts and (want_mask) the inlier mask come to the host, the
+  // stream is synchronised, and the costs of attempted item v go to row sel_rank[v] of the caller's hypothesis_cost.
+  int read_back(OneShot* s, bool want_mask, int slots, const std::vector<int>& sel_rank, int32_t* hypothesis_cost) {
+    const hipStream_t stream = s->stream;
+    const size_t KS = (size_t)K * slots;
+    status.resize((size_t)S);
+    num_inliers.resize((size_t)S);
+    slot_inlier.resize(want_mask ? M : 0);
+    std::vector<int> hyp_h(hypothesis_cost ? (size_t)S * KS : 0);
+    TMI_HIP(hipMemcpyAsync(status.data(), d_status, (size_t)S, hipMemcpyDeviceToHost, stream));
+    TMI_HIP(hipMemcpyAsync(num_inliers.data(), d_num_inliers, (size_t)S * sizeof(int), hipMemcpyDeviceToHost, stream));
+    if (!slot_inlier.empty())
+      TMI_HIP(hipMemcpyAsync(slot_inlier.data(), d_slot_inlier, M, hipMemcpyDeviceToHost, stream));
+    if (!hyp_h.empty())
+      TMI_HIP(hipMemcpyAsync(hyp_h.data(), B.hypothesis_cost, hyp_h.size() * sizeof(int), hipMemcpyDeviceToHost, stream));
+    TMI_HIP(hipStreamSynchronize(stream));
+    if (hypothesis_cost)
+      for (int v = 0; v < S; ++v)
+        std::copy(hyp_h.begin() + (size_t)v * KS, hyp_h.begin() + ((size_t)v + 1) * KS,
+                  hypothesis_cost + (size_t)sel_rank[v] * KS);
+    return TMI_BA_OK;
+  }
+
+  // Attempted item v with status `code` into entry `item` of the caller's arrays.
+  void item_results(int v, int item, int code, const RansacItemArrays& out) const {
+    const RansacState& st = state[v];
+    if (out.status) out.status[item] = (int8_t)code;
+    if (out.num_inliers) out.num_inliers[item] = num_inliers[v];
+    if (out.num_iterations) out.num_iterations[item] = st.num_iterations;
+    if (out.best_iteration) out.best_iteration[item] = st.best_iteration;
+    if (out.best_solution) out.best_solution[item] = st.best_solution;
+    if (out.confidence) {
+      const int n = (int)(sel_ptr[(size_t)v + 1] - sel_ptr[v]);
+      const double ratio = (double)num_inliers[v] / (double)n;  // sample_consensus_estimator.h:336-340
+      out.confidence[item] = 1.0 - std::pow(1.0 - std::pow(ratio, sample_size), (double)st.num_iterations);
+    }
+  }
+};
+}  // namespace
+
+extern "C" {
 // ---- batched LocalizeViewToReconstruction: P3P RANSAC (localize_kernels.h) ---------------------
 void tmi_ba_localization_options_init(tmi_ba_localization_options* o) {
   if (!o) return;
@@ -2549,18 +2760,6 @@ void tmi_ba_localization_options_init(tmi_ba_localization_options* o) {
   o->chunk_iterations = 0;
   o->seed = 0;
 }
-}  // extern "C"
-namespace {
-// SampleConsensusEstimator::ComputeMaxIterations (sample_consensus_estimator.h:215-243) for a sample of three, without
-// the T(d,d) test.
-int localize_max_iterations(double inlier_ratio, double log_failure_prob, int min_iterations, int max_iterations) {
-  if (inlier_ratio == 1.0) return min_iterations;
-  const double log_prob = std::log(1.0 - std::pow(inlier_ratio, 3.0)) - std::numeric_limits<double>::epsilon();
-  const double num_iterations = log_failure_prob / log_prob;
-  return (int)std::max((double)min_iterations, std::min(num_iterations, (double)max_iterations));
-}
-}  // namespace
-extern "C" {
 
 int32_t tmi_ba_localize_views(tmi_ba_problem* P, const tmi_ba_localization_options* L, const tmi_ba_options* O,
                               const uint8_t* view_mask, const double* view_error_threshold, const int32_t* samples,
@@ -2579,16 +2778,8 @@ int32_t tmi_ba_localize_views(tmi_ba_problem* P, const tmi_ba_localization_optio
       (Np && !P->points) || (No && (!P->obs_camera || !P->obs_point || !P->obs_xy)))
     return bad_argument("localize views: missing array");
   if (No >= (int64_t)0x7fffffffLL) return bad_argument("localize views: more than 2^31 observations");
-  // the CHECKs of the SampleConsensusEstimator constructor (sample_consensus_estimator.h:191-197)
-  if (!(L->failure_probability > 0.0 && L->failure_probability < 1.0))
-    return bad_argument("localize views: failure_probability must be in (0, 1)");
-  if (!(L->min_inlier_ratio >= 0.0 && L->min_inlier_ratio <= 1.0))
-    return bad_argument("localize views: min_inlier_ratio must be in [0, 1]");
-  if (L->min_iterations < 0 || L->max_iterations < L->min_iterations)
-    return bad_argument("localize views: max_iterations < min_iterations, or a negative count");
-  if (L->max_iterations > kLocalizeMaxIterations) return bad_argument("localize views: max_iterations above 2^20");
-  if (L->chunk_iterations < 0) return bad_argument("localize views: negative chunk_iterations");
-  if (samples_given && !samples) return bad_argument("localize views: samples_given without samples");
+  if (const char* why = ransac_options_error(L, samples, samples_given))
+    return bad_argument((std::string("localize views: ") + why).c_str());
   const int n_intr = G ? P->group_offset[G] : 0;
   if (n_intr && !P->intrinsics) return bad_argument("localize views: missing intrinsics");
   std::vector<uint32_t> grp_free((size_t)G, 0);
@@ -2680,48 +2871,26 @@ int32_t tmi_ba_localize_views(tmi_ba_problem* P, const tmi_ba_localization_optio
       xy[2 * o + 1] = P->obs_xy[2 * i + 1];
     }
   }
-  // ComputeMaxIterations per view and inlier count, with the host's log and pow
-  const double log_failure_prob = std::log(L->failure_probability);
-  std::vector<long long> sel_ptr((size_t)S + 1, 0);
+  RansacRun run;
+  run.sel_ptr.assign((size_t)S + 1, 0);
   std::vector<double> thresh((size_t)S);
-  std::vector<int> bound(M + (size_t)S);
-  std::vector<LocalizeState> state((size_t)S);
-  int initial_bound = K;
-  if (L->min_inlier_ratio > 0.0)
-    initial_bound = std::min(localize_max_iterations(L->min_inlier_ratio, log_failure_prob, L->min_iterations, K), K);
   for (int s = 0; s < S; ++s) {
     const int c = sel_view[s];
-    const int n = (int)(vptr[(size_t)c + 1] - vptr[c]);
-    sel_ptr[s] = vptr[c];
-    sel_ptr[(size_t)s + 1] = vptr[(size_t)c + 1];
+    run.sel_ptr[s] = vptr[c];
+    run.sel_ptr[(size_t)s + 1] = vptr[(size_t)c + 1];
     thresh[s] = view_error_threshold[c];
-    int* row = bound.data() + vptr[c] + s;
-    for (int k = 0; k <= n; ++k)
-      row[k] = k < 3 ? K : localize_max_iterations((double)k / (double)n, log_failure_prob, L->min_iterations, K);
-    LocalizeState& st = state[s];
-    memset(&st, 0, sizeof(st));
-    st.best_cost = INT32_MAX;
-    st.best_iteration = st.best_solution = -1;
-    st.max_iterations = initial_bound;
-    st.done = initial_bound <= 0;
   }
-  // the engine's choice of chunk: the common case -- the run stops at min_iterations -- is a single chunk
-  int chunk = L->chunk_iterations ? L->chunk_iterations : std::max(L->min_iterations, 64);
-  chunk = std::max(1, std::min(chunk, std::max(K, 1)));
-  const int max_chunks = (K + chunk - 1) / chunk;
+  run.plan(L, LocalizeProblem::kSample);
+  const std::vector<unsigned> sel_stream(sel_view.begin(), sel_view.end());  // a view's sample stream is its camera index
   return one_shot_batch(O->device, "localize views: no such device", S, t0, sum, [&](OneShot* s) -> int {
     const hipStream_t stream = s->stream;
     ViewBatch VB;
     memset(&VB, 0, sizeof(VB));
-    LocalizeBatch B;
-    memset(&B, 0, sizeof(B));
     int4* d_cam;
-    long long *d_vptr, *d_sel_ptr;
+    long long* d_vptr;
     unsigned long long* d_keys;
-    int *d_slot_pt, *d_sel_view, *d_bound, *d_active, *d_samples = nullptr, *d_num_inliers;
-    double *d_xy, *d_pts, *d_thresh, *d_pose_out;
-    unsigned char* d_slot_inlier;
-    signed char* d_status;
+    int* d_slot_pt;
+    double *d_xy, *d_pts, *d_pose_out;
     TMI_HIP(s->upload(&VB.ext, (const double*)P->extrinsics, (size_t)6 * Nc));
     TMI_HIP(s->upload(&VB.intr, (const double*)P->intrinsics, (size_t)n_intr));
     TMI_HIP(s->upload(&d_cam, cam.data(), cam.size()));
@@ -2730,86 +2899,31 @@ int32_t tmi_ba_localize_views(tmi_ba_problem* P, const tmi_ba_localization_optio
     TMI_HIP(s->upload(&d_slot_pt, slot_pt.data(), slot_pt.size()));
     TMI_HIP(s->upload(&d_xy, xy.data(), xy.size()));
     TMI_HIP(s->upload(&d_pts, (const double*)P->points, (size_t)4 * Np));
-    TMI_HIP(s->upload(&d_sel_view, sel_view.data(), sel_view.size()));
-    TMI_HIP(s->upload(&d_sel_ptr, sel_ptr.data(), sel_ptr.size()));
-    TMI_HIP(s->upload(&d_thresh, thresh.data(), thresh.size()));
-    TMI_HIP(s->upload(&d_bound, bound.data(), bound.size()));
-    TMI_HIP(s->upload(&B.state, state.data(), state.size()));
-    if (samples_given) TMI_HIP(s->upload(&d_samples, (const int*)samples, (size_t)3 * K * Nc));
-    TMI_HIP(s->alloc(&B.fx, M));
-    TMI_HIP(s->alloc(&B.fy, M));
-    TMI_HIP(s->alloc(&B.wx, M));
-    TMI_HIP(s->alloc(&B.wy, M));
-    TMI_HIP(s->alloc(&B.wz, M));
-    TMI_HIP(s->alloc(&d_active, (size_t)S));
-    TMI_HIP(s->alloc(&B.poses, (size_t)S * chunk * 48));
-    TMI_HIP(s->alloc(&B.num_solutions, (size_t)S * chunk));
-    TMI_HIP(s->alloc(&B.cost, (size_t)S * chunk * 4));
-    TMI_HIP(s->alloc(&d_slot_inlier, M));
-    TMI_HIP(s->alloc(&d_num_inliers, (size_t)S));
-    TMI_HIP(s->alloc(&d_status, (size_t)S));
+    if (const int rc = run.upload<LocalizeProblem>(s, L->seed, sel_view, sel_stream, thresh,
+                                                   samples_given ? samples : nullptr, (size_t)Nc, hypothesis_cost != nullptr))
+      return rc;
+    RansacBatch& B = run.B;
+    for (int q = 0; q < LocalizeProblem::kPlanes; ++q) TMI_HIP(s->alloc(&B.plane[q], M));
     TMI_HIP(s->alloc(&d_pose_out, (size_t)6 * S));
-    if (hypothesis_cost) {
-      TMI_HIP(s->alloc(&B.hypothesis_cost, (size_t)S * K * 4));
-      TMI_HIP(hipMemsetAsync(B.hypothesis_cost, 0xff, std::max<size_t>((size_t)S * K * 4, 1) * sizeof(int), stream));
-    }
-    B.num_selected = S;
-    B.max_iterations = K;
-    B.chunk = chunk;
-    B.seed = L->seed;
-    B.sel_view = d_sel_view;
-    B.sel_ptr = d_sel_ptr;
-    B.threshold = d_thresh;
-    B.samples = d_samples;
-    B.bound_table = d_bound;
-    B.active = d_active;
     StreamTimer timer(stream);
     TMI_HIP(timer.status);
     TMI_HIP(timer.mark());
     hipLaunchKernelGGL(localize_prepare_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, stream, (long long)M,
                        d_keys, d_slot_pt, d_xy, d_pts, d_cam, VB.intr, B);
-    // the chunk loop: bounded by ceil(max_iterations / chunk) whatever the device reports
-    std::vector<int> active;
-    int chunks_run = 0;
-    for (int ch = 0; ch < max_chunks; ++ch) {
-      active.clear();
-      for (int v = 0; v < S; ++v)
-        if (!state[v].done) active.push_back(v);
-      if (active.empty()) break;
-      TMI_HIP(hipMemcpyAsync(d_active, active.data(), active.size() * sizeof(int), hipMemcpyHostToDevice, stream));
-      B.num_active = (int)active.size();
-      B.chunk_start = ch * chunk;
-      const long long items = (long long)B.num_active * chunk;
-      hipLaunchKernelGGL(localize_hypothesis_kernel, dim3((unsigned)((items + 63) / 64)), dim3(64), 0, stream, B);
-      hipLaunchKernelGGL(localize_score_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, stream, B);
-      hipLaunchKernelGGL(localize_replay_kernel, dim3((unsigned)((B.num_active + 63) / 64)), dim3(64), 0, stream, B);
-      TMI_HIP(hipGetLastError());
-      TMI_HIP(hipMemcpyAsync(state.data(), B.state, state.size() * sizeof(LocalizeState), hipMemcpyDeviceToHost, stream));
-      TMI_HIP(hipStreamSynchronize(stream));  // (also: `active` is free to change)
-      ++chunks_run;
-    }
-    hipLaunchKernelGGL(localize_final_kernel, dim3(S), dim3(64), 0, stream, B, (int)L->min_num_inliers, d_slot_inlier,
-                       d_num_inliers, d_status, d_pose_out, VB.ext);
+    if (const int rc = run.chunks<LocalizeProblem>(s, nullptr)) return rc;
+    hipLaunchKernelGGL(localize_final_kernel, dim3(S), dim3(64), 0, stream, B, (int)L->min_num_inliers,
+                       run.d_slot_inlier, run.d_num_inliers, run.d_status, d_pose_out, VB.ext);
     TMI_HIP(timer.mark());
     TMI_HIP(hipGetLastError());
-    std::vector<signed char> status_h((size_t)S);
-    std::vector<int> inliers_h((size_t)S);
-    std::vector<unsigned char> slot_inlier_h(obs_inlier ? M : 0);
-    std::vector<int> hyp_h(hypothesis_cost ? (size_t)S * K * 4 : 0);
-    TMI_HIP(hipMemcpyAsync(status_h.data(), d_status, (size_t)S, hipMemcpyDeviceToHost, stream));
-    TMI_HIP(hipMemcpyAsync(inliers_h.data(), d_num_inliers, (size_t)S * sizeof(int), hipMemcpyDeviceToHost, stream));
-    if (!slot_inlier_h.empty())
-      TMI_HIP(hipMemcpyAsync(slot_inlier_h.data(), d_slot_inlier, M, hipMemcpyDeviceToHost, stream));
-    if (!hyp_h.empty())
-      TMI_HIP(hipMemcpyAsync(hyp_h.data(), B.hypothesis_cost, hyp_h.size() * sizeof(int), hipMemcpyDeviceToHost, stream));
-    TMI_HIP(hipStreamSynchronize(stream));
+    if (const int rc = run.read_back(s, obs_inlier != nullptr, LocalizeProblem::kSlots, sel_rank, hypothesis_cost))
+      return rc;
     sum->kernel_seconds = timer.seconds();
-    sum->num_chunks = chunks_run;
+    sum->num_chunks = run.chunks_run;
     // BundleAdjustView on exactly the localised views, on the data already uploaded
     std::vector<uint8_t> localised((size_t)Nc, 0);
     int num_localised = 0;
     for (int v = 0; v < S; ++v)
-      if (status_h[v] == 0) {
+      if (run.status[v] == 0) {
         localised[sel_view[v]] = 1;
         ++num_localised;
       }
@@ -2830,7 +2944,7 @@ int32_t tmi_ba_localize_views(tmi_ba_problem* P, const tmi_ba_localization_optio
       if (rc) return rc;
       sum->kernel_seconds += vs.kernel_seconds;
       for (int v = 0; v < S; ++v)
-        if (status_h[v] == 0 && term[sel_view[v]] != 0 && term[sel_view[v]] != 1) status_h[v] = 4;
+        if (run.status[v] == 0 && term[sel_view[v]] != 0 && term[sel_view[v]] != 1) run.status[v] = 4;
       if (n_intr) {
         // (the kernel wrote back exactly the usable views' free intrinsics)
         TMI_HIP(hipMemcpyAsync(P->intrinsics, VB.intr, (size_t)n_intr * sizeof(double), hipMemcpyDeviceToHost, stream));
@@ -2839,11 +2953,11 @@ int32_t tmi_ba_localize_views(tmi_ba_problem* P, const tmi_ba_localization_optio
     std::vector<double> ext_h((size_t)6 * Nc);
     TMI_HIP(hipMemcpyAsync(ext_h.data(), VB.ext, ext_h.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
     TMI_HIP(hipStreamSynchronize(stream));
+    const RansacItemArrays out = {view_status,         view_num_inliers,   view_num_iterations,
+                                  view_best_iteration, view_best_solution, view_confidence};
     for (int v = 0; v < S; ++v) {
       const int c = sel_view[v];
-      const int n = (int)(sel_ptr[(size_t)v + 1] - sel_ptr[v]);
-      const int code = status_h[v];
-      const LocalizeState& st = state[v];
+      const int code = run.status[v];
       if (code == 0 || code == 4) std::copy(ext_h.begin() + 6 * (size_t)c, ext_h.begin() + 6 * (size_t)c + 6, P->extrinsics + 6 * (size_t)c);
       switch (code) {
         case 0: sum->num_localized++; break;
@@ -2851,21 +2965,11 @@ int32_t tmi_ba_localize_views(tmi_ba_problem* P, const tmi_ba_localization_optio
         case 3: sum->num_too_few_inliers++; break;
         default: sum->num_failed_ba++; break;
       }
-      sum->total_iterations += st.num_iterations;
-      if (view_status) view_status[c] = (int8_t)code;
-      if (view_num_inliers) view_num_inliers[c] = inliers_h[v];
-      if (view_num_iterations) view_num_iterations[c] = st.num_iterations;
-      if (view_best_iteration) view_best_iteration[c] = st.best_iteration;
-      if (view_best_solution) view_best_solution[c] = st.best_solution;
-      if (view_confidence) {
-        const double ratio = (double)inliers_h[v] / (double)n;  // :336-340
-        view_confidence[c] = 1.0 - std::pow(1.0 - std::pow(ratio, 3.0), (double)st.num_iterations);
-      }
+      sum->total_iterations += run.state[v].num_iterations;
+      run.item_results(v, c, code, out);
       if (obs_inlier)
-        for (long long o = sel_ptr[v]; o < sel_ptr[(size_t)v + 1]; ++o) obs_inlier[slot_obs[(size_t)o]] = slot_inlier_h[(size_t)o];
-      if (hypothesis_cost)
-        std::copy(hyp_h.begin() + (size_t)v * K * 4, hyp_h.begin() + ((size_t)v + 1) * K * 4,
-                  hypothesis_cost + (size_t)sel_rank[v] * K * 4);
+        for (long long o = run.sel_ptr[v]; o < run.sel_ptr[(size_t)v + 1]; ++o)
+          obs_inlier[slot_obs[(size_t)o]] = run.slot_inlier[(size_t)o];
     }
     return TMI_BA_OK;
   });
@@ -3575,31 +3679,18 @@ void tmi_ba_two_view_ransac_options_init(tmi_ba_two_view_ransac_options* o) {
 }
 }  // extern "C"
 namespace {
-// SampleConsensusEstimator::ComputeMaxIterations (sample_consensus_estimator.h:215-243) for a sample of sample_size,
-// without the T(d,d) test.
-int two_view_max_iterations(double inlier_ratio, double log_failure_prob, int min_iterations, int max_iterations,
-                            int sample_size) {
-  if (inlier_ratio == 1.0) return min_iterations;
-  const double log_prob =
-      std::log(1.0 - std::pow(inlier_ratio, (double)sample_size)) - std::numeric_limits<double>::epsilon();
-  const double num_iterations = log_failure_prob / log_prob;
-  return (int)std::max((double)min_iterations, std::min(num_iterations, (double)max_iterations));
-}
-
-// The host loop the two RANSAC calls over view pairs share.  Calibrated == false: the eight-point call (a sample of 8,
-// one model per sample, model_a = the fundamental matrix, focal lengths out).  Calibrated == true: the five-point call
-// (a sample of 5, kCalibSlots models per sample, model_a = the essential matrix, pair_best_solution out).
-template <bool Calibrated>
+// What the two RANSAC calls over view pairs share beyond the scaffold.  P = EightPointProblem: model_a = the
+// fundamental matrix, focal lengths out.  P = FivePointProblem: model_a = the essential matrix, pair_best_solution out.
+template <class P>
 int32_t two_view_ransac_call(
-    const tmi_ba_two_view_ransac_options* L, int32_t num_pairs, const int64_t* pair_offset, const double* feature1,
+    const char* name, const tmi_ba_two_view_ransac_options* L, int32_t num_pairs, const int64_t* pair_offset, const double* feature1,
     const double* feature2, const double* pair_error_threshold, const uint8_t* pair_mask, const uint32_t* pair_stream,
     const int32_t* samples, int32_t samples_given, int8_t* pair_status, int32_t* pair_num_correspondences,
     int32_t* pair_num_inliers, int32_t* pair_num_iterations, int32_t* pair_best_iteration, int32_t* pair_best_solution,
     double* pair_confidence, double* fundamental_matrix, double* focal_length1, double* focal_length2, double* rotation,
     double* position, uint8_t* corr_inlier, int32_t* hypothesis_cost, tmi_ba_two_view_ransac_summary* sum) {
-  constexpr int kSample = Calibrated ? 5 : 8;
-  constexpr int kSlots = Calibrated ? kCalibSlots : 1;
-  const std::string what = Calibrated ? "calibrated relative poses" : "uncalibrated relative poses";
+  constexpr int kSample = P::kSample, kSlots = P::kSlots;
+  const std::string what = name;
   auto bad = [&](const char* why) { return bad_argument((what + ": " + why).c_str()); };
   if (!L || !sum) return bad("null options or summary");
   memset(sum, 0, sizeof(*sum));
@@ -3614,17 +3705,7 @@ int32_t two_view_ransac_call(
   const int64_t total = pair_offset[Npair];
   if (total >= (int64_t)0x7fffffffLL) return bad("more than 2^31 correspondences");
   if (total && (!feature1 || !feature2)) return bad("missing array");
-  // the CHECKs of the SampleConsensusEstimator constructor (sample_consensus_estimator.h:191-197)
-  if (!(L->failure_probability > 0.0 && L->failure_probability < 1.0))
-    return bad("failure_probability must be in (0, 1)");
-  if (!(L->min_inlier_ratio >= 0.0 && L->min_inlier_ratio <= 1.0))
-    return bad("min_inlier_ratio must be in [0, 1]");
-  if (L->min_iterations < 0 || L->max_iterations < L->min_iterations)
-    return bad("max_iterations < min_iterations, or a negative count");
-  if (L->max_iterations > kLocalizeMaxIterations)
-    return bad("max_iterations above 2^20");
-  if (L->chunk_iterations < 0) return bad("negative chunk_iterations");
-  if (samples_given && !samples) return bad("samples_given without samples");
+  if (const char* why = ransac_options_error(L, samples, samples_given)) return bad(why);
   const int K = L->max_iterations;
   std::vector<int> selected, sel_pair, sel_rank;  // sel_pair: the attempted ones, the device's slots
   for (int p = 0; p < Npair; ++p) {
@@ -3670,7 +3751,9 @@ int32_t two_view_ransac_call(
   sum->num_pairs = num_selected;
   sum->num_too_few_correspondences = num_selected - S;
   // the attempted pairs' correspondences, pair-major, structure of arrays
-  std::vector<long long> sel_ptr((size_t)S + 1, 0);
+  RansacRun run;
+  std::vector<long long>& sel_ptr = run.sel_ptr;
+  sel_ptr.assign((size_t)S + 1, 0);
   for (int s = 0; s < S; ++s) sel_ptr[(size_t)s + 1] = sel_ptr[s] + (pair_offset[sel_pair[s] + 1] - pair_offset[sel_pair[s]]);
   const size_t M = (size_t)sel_ptr[S];
   std::vector<double> xs(4 * std::max<size_t>(M, 1));
@@ -3691,170 +3774,51 @@ int32_t two_view_ransac_call(
     thresh[s] = pair_error_threshold[p];
     stream_id[s] = pair_stream ? pair_stream[p] : (unsigned)p;
   }
-  // ComputeMaxIterations per pair and inlier count, with the host's log and pow
-  const double log_failure_prob = std::log(L->failure_probability);
-  std::vector<int> bound(M + (size_t)S);
-  std::vector<TwoViewRansacState> state((size_t)S);
-  int initial_bound = K;
-  if (L->min_inlier_ratio > 0.0)
-    initial_bound =
-        std::min(two_view_max_iterations(L->min_inlier_ratio, log_failure_prob, L->min_iterations, K, kSample), K);
-  for (int s = 0; s < S; ++s) {
-    const int n = (int)(sel_ptr[(size_t)s + 1] - sel_ptr[s]);
-    int* row = bound.data() + sel_ptr[s] + s;
-    for (int k = 0; k <= n; ++k)
-      row[k] = k < kSample ? K
-                           : two_view_max_iterations((double)k / (double)n, log_failure_prob, L->min_iterations, K, kSample);
-    TwoViewRansacState& st = state[s];
-    memset(&st, 0, sizeof(st));
-    st.best_cost = INT32_MAX;
-    st.best_iteration = -1;
-    st.best_solution = -1;
-    st.max_iterations = initial_bound;
-    st.done = initial_bound <= 0;
-  }
-  // the engine's choice of chunk: the common case -- the run stops at min_iterations -- is a single chunk
-  int chunk = L->chunk_iterations ? L->chunk_iterations : std::max(L->min_iterations, 64);
-  chunk = std::max(1, std::min(chunk, std::max(K, 1)));
-  const int max_chunks = (K + chunk - 1) / chunk;
+  run.plan(L, kSample);
   const std::string no_device = what + ": no such device";
   return one_shot_batch(L->device, no_device.c_str(), S, t0, sum, [&](OneShot* s) -> int {
     const hipStream_t stream = s->stream;
-    TwoViewRansacBatch B;
-    memset(&B, 0, sizeof(B));
-    double *d_xs, *d_thresh, *d_model_out;
-    long long* d_sel_ptr;
-    unsigned* d_stream_id;
-    int *d_sel_pair, *d_bound, *d_active, *d_samples = nullptr, *d_num_inliers;
-    unsigned char* d_slot_inlier;
-    signed char* d_status;
+    double *d_xs, *d_model_out;
     TMI_HIP(s->upload(&d_xs, (const double*)xs.data(), xs.size()));
-    TMI_HIP(s->upload(&d_sel_pair, (const int*)sel_pair.data(), sel_pair.size()));
-    TMI_HIP(s->upload(&d_stream_id, (const unsigned*)stream_id.data(), stream_id.size()));
-    TMI_HIP(s->upload(&d_sel_ptr, (const long long*)sel_ptr.data(), sel_ptr.size()));
-    TMI_HIP(s->upload(&d_thresh, (const double*)thresh.data(), thresh.size()));
-    TMI_HIP(s->upload(&d_bound, (const int*)bound.data(), bound.size()));
-    TMI_HIP(s->upload(&B.state, (const TwoViewRansacState*)state.data(), state.size()));
-    if (samples_given) TMI_HIP(s->upload(&d_samples, (const int*)samples, (size_t)kSample * K * Npair));
-    TMI_HIP(s->alloc(&d_active, (size_t)S));
-    TMI_HIP(s->alloc(&B.models, (size_t)S * chunk * kSlots * kTwoViewModel));
-    TMI_HIP(s->alloc(&B.has_model, (size_t)S * chunk * kSlots));
-    TMI_HIP(s->alloc(&B.cost, (size_t)S * chunk * kSlots));
-    TMI_HIP(s->alloc(&d_slot_inlier, M));
-    TMI_HIP(s->alloc(&d_num_inliers, (size_t)S));
-    TMI_HIP(s->alloc(&d_status, (size_t)S));
+    if (const int rc = run.upload<P>(s, L->seed, sel_pair, stream_id, thresh, samples_given ? samples : nullptr,
+                                     (size_t)Npair, hypothesis_cost != nullptr))
+      return rc;
+    RansacBatch& B = run.B;
+    for (int q = 0; q < P::kPlanes; ++q) B.plane[q] = d_xs + q * M;  // x1, y1, x2, y2
     TMI_HIP(s->alloc(&d_model_out, (size_t)17 * S));
-    if (hypothesis_cost) {
-      TMI_HIP(s->alloc(&B.hypothesis_cost, (size_t)S * K * kSlots));
-      TMI_HIP(hipMemsetAsync(B.hypothesis_cost, 0xff, std::max<size_t>((size_t)S * K * kSlots, 1) * sizeof(int), stream));
-    }
-    B.num_selected = S;
-    B.max_iterations = K;
-    B.chunk = chunk;
-    B.seed = L->seed;
-    B.sel_pair = d_sel_pair;
-    B.sel_stream = d_stream_id;
-    B.sel_ptr = d_sel_ptr;
-    B.threshold = d_thresh;
-    B.samples = d_samples;
-    B.bound_table = d_bound;
-    B.x1 = d_xs;
-    B.y1 = d_xs + M;
-    B.x2 = d_xs + 2 * M;
-    B.y2 = d_xs + 3 * M;
-    B.active = d_active;
     StreamTimer timer(stream);
     TMI_HIP(timer.status);
     TMI_HIP(timer.mark());
-    // the chunk loop: bounded by ceil(max_iterations / chunk) whatever the device reports
-    std::vector<int> active;
-    int chunks_run = 0;
-    for (int ch = 0; ch < max_chunks; ++ch) {
-      active.clear();
-      for (int v = 0; v < S; ++v)
-        if (!state[v].done) active.push_back(v);
-      if (active.empty()) break;
-      TMI_HIP(hipMemcpyAsync(d_active, active.data(), active.size() * sizeof(int), hipMemcpyHostToDevice, stream));
-      B.num_active = (int)active.size();
-      B.chunk_start = ch * chunk;
-      const long long items = (long long)B.num_active * chunk;
-      StreamTimer phase(stream, 4);
-      TMI_HIP(phase.status);
-      TMI_HIP(phase.mark());
-      if (Calibrated)
-        hipLaunchKernelGGL(calibrated_hypothesis_kernel, dim3((unsigned)((items + kCalibThreads - 1) / kCalibThreads)),
-                           dim3(kCalibThreads), 0, stream, B);
-      else
-        hipLaunchKernelGGL(two_view_hypothesis_kernel, dim3((unsigned)((items + 63) / 64)), dim3(64), 0, stream, B);
-      TMI_HIP(phase.mark());
-      if (Calibrated)
-        hipLaunchKernelGGL(calibrated_score_kernel, dim3((unsigned)((items * kCalibSlots + 3) / 4)), dim3(256), 0, stream, B);
-      else
-        hipLaunchKernelGGL(two_view_score_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, stream, B);
-      TMI_HIP(phase.mark());
-      if (Calibrated)
-        hipLaunchKernelGGL(calibrated_replay_kernel, dim3((unsigned)((B.num_active + 63) / 64)), dim3(64), 0, stream, B);
-      else
-        hipLaunchKernelGGL(two_view_replay_kernel, dim3((unsigned)((B.num_active + 63) / 64)), dim3(64), 0, stream, B);
-      TMI_HIP(phase.mark());
-      TMI_HIP(hipGetLastError());
-      TMI_HIP(hipMemcpyAsync(state.data(), B.state, state.size() * sizeof(TwoViewRansacState), hipMemcpyDeviceToHost,
-                             stream));
-      TMI_HIP(hipStreamSynchronize(stream));  // (also: `active` is free to change)
-      sum->hypothesis_seconds += phase.seconds(0, 1);
-      sum->score_seconds += phase.seconds(1, 2);
-      sum->replay_seconds += phase.seconds(2, 3);
-      ++chunks_run;
-    }
-    hipLaunchKernelGGL(two_view_final_kernel, dim3(S), dim3(64), 0, stream, B, d_slot_inlier, d_num_inliers, d_status,
-                       d_model_out);
+    if (const int rc = run.chunks<P>(s, sum)) return rc;
+    hipLaunchKernelGGL(two_view_final_kernel, dim3(S), dim3(64), 0, stream, B, run.d_slot_inlier, run.d_num_inliers,
+                       run.d_status, d_model_out);
     TMI_HIP(timer.mark());
     TMI_HIP(hipGetLastError());
-    std::vector<signed char> status_h((size_t)S);
-    std::vector<int> inliers_h((size_t)S);
     std::vector<double> model_h((size_t)17 * S);
-    std::vector<unsigned char> slot_inlier_h(corr_inlier ? M : 0);
-    const size_t KS = (size_t)K * kSlots;
-    std::vector<int> hyp_h(hypothesis_cost ? (size_t)S * KS : 0);
-    TMI_HIP(hipMemcpyAsync(status_h.data(), d_status, (size_t)S, hipMemcpyDeviceToHost, stream));
-    TMI_HIP(hipMemcpyAsync(inliers_h.data(), d_num_inliers, (size_t)S * sizeof(int), hipMemcpyDeviceToHost, stream));
     TMI_HIP(hipMemcpyAsync(model_h.data(), d_model_out, model_h.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-    if (!slot_inlier_h.empty())
-      TMI_HIP(hipMemcpyAsync(slot_inlier_h.data(), d_slot_inlier, M, hipMemcpyDeviceToHost, stream));
-    if (!hyp_h.empty())
-      TMI_HIP(hipMemcpyAsync(hyp_h.data(), B.hypothesis_cost, hyp_h.size() * sizeof(int), hipMemcpyDeviceToHost, stream));
-    TMI_HIP(hipStreamSynchronize(stream));
+    if (const int rc = run.read_back(s, corr_inlier != nullptr, kSlots, sel_rank, hypothesis_cost)) return rc;
     sum->kernel_seconds = timer.seconds();
-    sum->num_chunks = chunks_run;
+    sum->num_chunks = run.chunks_run;
+    const RansacItemArrays out = {pair_status,         pair_num_inliers,   pair_num_iterations,
+                                  pair_best_iteration, pair_best_solution, pair_confidence};
     for (int v = 0; v < S; ++v) {
       const int p = sel_pair[v];
       const int n = (int)(sel_ptr[(size_t)v + 1] - sel_ptr[v]);
-      const int code = status_h[v];
-      const TwoViewRansacState& st = state[v];
+      const int code = run.status[v];
+      const RansacState& st = run.state[v];
       const double* mo = model_h.data() + 17 * (size_t)v;
       if (code == 0) sum->num_estimated++; else sum->num_no_model++;
       sum->total_iterations += st.num_iterations;
       sum->total_scores += (int64_t)st.num_iterations * n;
-      if (pair_status) pair_status[p] = (int8_t)code;
-      if (pair_num_inliers) pair_num_inliers[p] = inliers_h[v];
-      if (pair_num_iterations) pair_num_iterations[p] = st.num_iterations;
-      if (pair_best_iteration) pair_best_iteration[p] = st.best_iteration;
-      if (pair_best_solution) pair_best_solution[p] = st.best_solution;
-      if (pair_confidence) {
-        const double ratio = (double)inliers_h[v] / (double)n;  // sample_consensus_estimator.h:336-340
-        pair_confidence[p] = 1.0 - std::pow(1.0 - std::pow(ratio, (double)kSample), (double)st.num_iterations);
-      }
+      run.item_results(v, p, code, out);
       if (fundamental_matrix) std::copy(mo, mo + 9, fundamental_matrix + 9 * (size_t)p);
       if (focal_length1) focal_length1[p] = mo[9];
       if (focal_length2) focal_length2[p] = mo[10];
       if (rotation) std::copy(mo + 11, mo + 14, rotation + 3 * (size_t)p);
       if (position) std::copy(mo + 14, mo + 17, position + 3 * (size_t)p);
       if (corr_inlier)
-        std::copy(slot_inlier_h.begin() + (size_t)sel_ptr[v], slot_inlier_h.begin() + (size_t)sel_ptr[(size_t)v + 1],
+        std::copy(run.slot_inlier.begin() + (size_t)sel_ptr[v], run.slot_inlier.begin() + (size_t)sel_ptr[(size_t)v + 1],
                   corr_inlier + pair_offset[p]);
-      if (hypothesis_cost)
-        std::copy(hyp_h.begin() + (size_t)v * KS, hyp_h.begin() + ((size_t)v + 1) * KS,
-                  hypothesis_cost + (size_t)sel_rank[v] * KS);
     }
     return TMI_BA_OK;
   });
@@ -3869,11 +3833,11 @@ int32_t tmi_ba_estimate_uncalibrated_relative_poses(
     int32_t* pair_num_inliers, int32_t* pair_num_iterations, int32_t* pair_best_iteration, double* pair_confidence,
     double* fundamental_matrix, double* focal_length1, double* focal_length2, double* rotation, double* position,
     uint8_t* corr_inlier, int32_t* hypothesis_cost, tmi_ba_two_view_ransac_summary* sum) {
-  return two_view_ransac_call<false>(L, num_pairs, pair_offset, feature1, feature2, pair_error_threshold, pair_mask,
-                                     pair_stream, samples, samples_given, pair_status, pair_num_correspondences,
-                                     pair_num_inliers, pair_num_iterations, pair_best_iteration, nullptr, pair_confidence,
-                                     fundamental_matrix, focal_length1, focal_length2, rotation, position, corr_inlier,
-                                     hypothesis_cost, sum);
+  return two_view_ransac_call<EightPointProblem>(
+      "uncalibrated relative poses", L, num_pairs, pair_offset, feature1, feature2, pair_error_threshold, pair_mask,
+      pair_stream, samples, samples_given, pair_status, pair_num_correspondences, pair_num_inliers, pair_num_iterations,
+      pair_best_iteration, nullptr, pair_confidence, fundamental_matrix, focal_length1, focal_length2, rotation, position,
+      corr_inlier, hypothesis_cost, sum);
 }
 
 // ---- batched EstimateRelativePose: five-point RANSAC (two_view_calibrated_kernels.h) ----
@@ -3884,10 +3848,10 @@ int32_t tmi_ba_estimate_calibrated_relative_poses(
     int32_t* pair_num_inliers, int32_t* pair_num_iterations, int32_t* pair_best_iteration, int32_t* pair_best_solution,
     double* pair_confidence, double* essential_matrix, double* rotation, double* position, uint8_t* corr_inlier,
     int32_t* hypothesis_cost, tmi_ba_two_view_ransac_summary* sum) {
-  return two_view_ransac_call<true>(L, num_pairs, pair_offset, feature1, feature2, pair_error_threshold, pair_mask,
-                                    pair_stream, samples, samples_given, pair_status, pair_num_correspondences,
-                                    pair_num_inliers, pair_num_iterations, pair_best_iteration, pair_best_solution,
-                                    pair_confidence, essential_matrix, nullptr, nullptr, rotation, position, corr_inlier,
-                                    hypothesis_cost, sum);
+  return two_view_ransac_call<FivePointProblem>(
+      "calibrated relative poses", L, num_pairs, pair_offset, feature1, feature2, pair_error_threshold, pair_mask,
+      pair_stream, samples, samples_given, pair_status, pair_num_correspondences, pair_num_inliers, pair_num_iterations,
+      pair_best_iteration, pair_best_solution, pair_confidence, essential_matrix, nullptr, nullptr, rotation, position,
+      corr_inlier, hypothesis_cost, sum);
 }
 }  // extern "C"

@@ -1,15 +1,12 @@
 // Batched EstimateRelativePose (estimators/estimate_relative_pose.cc:59-144): RANSAC over the minimal five-point
 // essential matrix (pose/five_point_relative_pose.cc:212-299) for many calibrated view pairs at once, on the chunked
-// evaluate-then-replay scaffold of two_view_ransac_kernels.h, whose batch and state records, outlier test and final
-// kernel it shares (a model is stored with focal lengths 1, so that the centred-pixel code scores normalised points
-// unchanged).  Per chunk of iterations three launches:
-//
-//   calibrated_hypothesis_kernel  one thread per (active pair, iteration of the chunk), 32 threads per workgroup: the
-//                                 sample, the 5x9 kernel, the 10x20 constraint matrix and its solve, the action
-//                                 matrix' real eigenvalues and their vectors, and per real root the decomposition of E
-//                                 with the cheirality vote over the five sampled points: 0 to 10 models in 10 slots
-//   calibrated_score_kernel       one wavefront per (active pair, iteration, slot); an empty slot returns at once
-//   calibrated_replay_kernel      one thread per active pair: the costs in ascending (iteration, slot) order, strict <
+// evaluate-then-replay scaffold of ransac_core.h, with the outlier test and the final kernel of
+// two_view_ransac_kernels.h (a model is stored with focal lengths 1, so that the centred-pixel code scores normalised
+// points unchanged).  What is this call's own is FivePointProblem, which the scaffold's three per-chunk kernels are
+// instantiated with: a sample of five, 32 hypotheses per workgroup; the 5x9 kernel, the 10x20 constraint matrix and its
+// solve, the action matrix' real eigenvalues and their vectors, and per real root the decomposition of E with the
+// cheirality vote over the five sampled points: 0 to 10 models in 10 slots, one wavefront scoring one slot (an empty
+// slot returns at once).
 //
 // A hypothesis' state (45, then 200, then 2 x 100 doubles) does not fit a thread's registers, and every pivot is
 // data-dependent, so each thread owns a slab of kCalibSlab doubles of LDS, element e of thread t at lds[e * 32 + t]: the
@@ -605,143 +602,13 @@ __host__ __device__ int calib_models(const double x1[5], const double y1[5], con
 }
 
 #ifdef __HIPCC__
-// The sample of iteration i of stream p among n >= 5 correspondences: two_view_sample with five swaps.
-__device__ __forceinline__ void calibrated_sample(unsigned long long seed, unsigned p, int i, int n, int s[5]) {
-#pragma clang fp contract(off)
-  int cur[5], epos[5], eval[5];
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    cur[k] = k;
-    epos[k] = -1;
-    eval[k] = 0;
+struct FivePointProblem : TwoViewOutlier {
+  static constexpr int kSample = 5, kSlots = kCalibSlots, kScoreSlots = 1, kThreads = kCalibThreads, kSlab = kCalibSlab;
+  __device__ static void models(const double pts[kPlanes][kSample], double* slab, double* __restrict__ models, int* has) {
+    const int count = calib_models<kCalibThreads>(pts[0], pts[1], pts[2], pts[3], slab, models);
+    for (int k = 0; k < count; ++k) has[k] = 1;
   }
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    const unsigned long long c = 5ull * (((unsigned long long)p << 32) + (unsigned long long)i) + k;
-    const double u = ((double)(splitmix64_word(seed, c) >> 11) + 0.5) * (1.0 / 9007199254740992.0);
-    int j = k + (int)(u * (double)(n - k));
-    j = j < n - 1 ? j : n - 1;
-    int v = j;
-#pragma unroll
-    for (int q = 0; q < 5; ++q) v = j == q ? cur[q] : v;
-#pragma unroll
-    for (int m = 0; m < 5; ++m)
-      if (m < k) v = epos[m] == j ? eval[m] : v;
-    const int old = cur[k];
-#pragma unroll
-    for (int q = 0; q < 5; ++q) cur[q] = j == q ? old : cur[q];
-    epos[k] = j >= 5 ? j : -1;
-    eval[k] = old;
-    cur[k] = v;
-  }
-#pragma unroll
-  for (int k = 0; k < 5; ++k) s[k] = cur[k];
-}
-
-// B.models [num_active chunk 10 kTwoViewModel], B.has_model and B.cost [num_active chunk 10], B.samples [5 ...].
-__global__ __launch_bounds__(kCalibThreads) void calibrated_hypothesis_kernel(TwoViewRansacBatch B) {
-  __shared__ double slab[kCalibSlab * kCalibThreads];
-  const long long id = (long long)blockIdx.x * kCalibThreads + threadIdx.x;
-  if (id >= (long long)B.num_active * B.chunk) return;
-  const int a = (int)(id / B.chunk), j = (int)(id % B.chunk);
-  const int s = B.active[a];
-  const int i = B.chunk_start + j;
-  int* has = B.has_model + kCalibSlots * id;
-#pragma unroll
-  for (int k = 0; k < kCalibSlots; ++k) has[k] = 0;
-  if (i >= B.state[s].max_iterations) return;
-  const long long o0 = B.sel_ptr[s];
-  const int n = (int)(B.sel_ptr[s + 1] - o0);
-  int smp[5];
-  if (B.samples) {
-    const int* t = B.samples + 5 * ((long long)B.max_iterations * B.sel_pair[s] + i);
-#pragma unroll
-    for (int k = 0; k < 5; ++k) smp[k] = t[k];
-  } else {
-    calibrated_sample(B.seed, B.sel_stream[s], i, n, smp);
-  }
-  double x1[5], y1[5], x2[5], y2[5];
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    const long long o = o0 + smp[k];
-    x1[k] = B.x1[o];
-    y1[k] = B.y1[o];
-    x2[k] = B.x2[o];
-    y2[k] = B.y2[o];
-  }
-  const int count = calib_models<kCalibThreads>(x1, y1, x2, y2, slab + threadIdx.x,
-                                                B.models + (long long)kCalibSlots * kTwoViewModel * id);
-  for (int k = 0; k < count; ++k) has[k] = 1;
-}
-
-__global__ __launch_bounds__(256) void calibrated_score_kernel(TwoViewRansacBatch B) {
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int lane = threadIdx.x & 63;
-  const long long id = (long long)blockIdx.x * 4 + wave;  // (active, iteration, slot)
-  if (id >= (long long)B.num_active * B.chunk * kCalibSlots) return;
-  if (B.has_model[id] == 0) return;
-  const int s = B.active[(int)(id / ((long long)B.chunk * kCalibSlots))];
-  const long long o0 = B.sel_ptr[s];
-  const int n = (int)(B.sel_ptr[s + 1] - o0);
-  const double thresh = B.threshold[s];
-  const double* __restrict__ m = B.models + kTwoViewModel * id;
-  int c = 0;
-  for (int q = lane; q < n; q += 64) {
-    const long long o = o0 + q;
-    c += two_view_outlier(m, B.x1[o], B.y1[o], B.x2[o], B.y2[o], thresh);
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
-  if (lane == 0) B.cost[id] = c;
-}
-
-// B.hypothesis_cost [num_selected max_iterations 10] or null.
-__global__ __launch_bounds__(64) void calibrated_replay_kernel(TwoViewRansacBatch B) {
-  const int a = blockIdx.x * 64 + threadIdx.x;
-  if (a >= B.num_active) return;
-  const int s = B.active[a];
-  TwoViewRansacState* sp = B.state + s;
-  int best_cost = sp->best_cost, best_iteration = sp->best_iteration, best_solution = sp->best_solution;
-  int max_iterations = sp->max_iterations, num_iterations = sp->num_iterations;
-  const long long o0 = B.sel_ptr[s];
-  const int n = (int)(B.sel_ptr[s + 1] - o0);
-  const int* __restrict__ bound = B.bound_table + o0 + s;
-  long long best_id = -1;
-  for (int j = 0; j < B.chunk; ++j) {
-    const int i = B.chunk_start + j;
-    if (i >= max_iterations) break;
-    for (int k = 0; k < kCalibSlots; ++k) {
-      const long long id = ((long long)a * B.chunk + j) * kCalibSlots + k;
-      int c = -1;
-      if (B.has_model[id] != 0) {
-        c = B.cost[id];
-        if (c < best_cost) {
-          best_cost = c;
-          best_iteration = i;
-          best_solution = k;
-          best_id = id;
-          const int inliers = n - c;
-          if (inliers >= 5) {  // (inlier_ratio < 5 / n skips the update of the bound)
-            const int m = bound[inliers];
-            if (m < max_iterations) max_iterations = m;
-          }
-        }
-      }
-      if (B.hypothesis_cost) B.hypothesis_cost[((long long)s * B.max_iterations + i) * kCalibSlots + k] = c;
-    }
-    num_iterations = i + 1;
-  }
-  sp->best_cost = best_cost;
-  sp->best_iteration = best_iteration;
-  sp->best_solution = best_solution;
-  sp->max_iterations = max_iterations;
-  sp->num_iterations = num_iterations;
-  if (num_iterations >= max_iterations) sp->done = 1;
-  if (best_id >= 0) {
-    const double* m = B.models + kTwoViewModel * best_id;
-    for (int q = 0; q < kTwoViewModel; ++q) sp->model[q] = m[q];
-  }
-}
+};
 #endif  // __HIPCC__
 
 }  // namespace tmi

@@ -1,18 +1,14 @@
 // Batched EstimateUncalibratedRelativePose (estimate_uncalibrated_relative_pose.cc:67-172): RANSAC over the normalised
 // eight-point fundamental matrix for many view pairs at once, on the chunked evaluate-then-replay scaffold of
-// localize_kernels.h (the loop itself is the host's, side_calls.h).  Per chunk of iterations three launches, one final:
+// ransac_core.h (the loop itself is the host's, side_calls.h).  What is this call's own: the problem the scaffold's
+// three per-chunk kernels are instantiated with, and one final launch:
 //
-//   two_view_hypothesis_kernel  one thread per (active pair, iteration of the chunk): the sample, the normalised
-//                               eight-point F (8x9 elimination with full pivoting IN LDS, one 3x3 Jacobi SVD), the focal
-//                               lengths from F, the essential matrix' decomposition (one 3x3 Jacobi SVD) and the
-//                               cheirality vote over the eight sampled points: one model (F, R, position, f1, f2) or none
-//   two_view_score_kernel       one wavefront per (active pair, iteration): the lanes stride over the pair's
-//                               correspondences, the model's 23 doubles are uniform, the integer cost comes out of a wave
-//                               reduction of fixed shape
-//   two_view_replay_kernel      one thread per active pair: SampleConsensusEstimator::Estimate's loop
-//                               (sample_consensus_estimator.h:276-330) over the chunk's costs in iteration order
-//   two_view_final_kernel       one wavefront per attempted pair: the best model's inlier mask and count, the status, the
-//                               model (F column-major, the rotation as angle-axis)
+//   EightPointProblem      a sample of eight; the normalised eight-point F (8x9 elimination with full pivoting IN LDS,
+//                          one 3x3 Jacobi SVD), the focal lengths from F, the essential matrix' decomposition (one 3x3
+//                          Jacobi SVD) and the cheirality vote over the eight sampled points: one model (F, R, position,
+//                          f1, f2) or none; cheirality and the squared Sampson distance against the threshold
+//   two_view_final_kernel  one wavefront per attempted pair: the best model's inlier mask and count, the status, the
+//                          model (F column-major, the rotation as angle-axis)
 //
 // The 8x9 constraint matrix does not fit one thread's registers beside the rest, so every thread owns an 9x9 slab of LDS
 // (rows 0..7 the matrix, row 8 the column permutation), element e of thread t at lds[e * 64 + t]: a wavefront's 64 lanes
@@ -26,81 +22,13 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "localize_kernels.h"
+#include "ransac_core.h"
+#include "rotation_kernels.h"
+#include "vec3.h"
 
 namespace tmi {
 
 constexpr int kTwoViewJacobiSweeps = 10;  // of the cyclic one-sided Jacobi iteration on a 3x3 matrix
-constexpr int kTwoViewModel = 24;         // doubles per model: F row-major, R row-major, position, f1, f2, pad
-
-struct TwoViewRansacState {
-  int best_cost;        // INT_MAX: no model yet
-  int best_iteration;   // -1
-  int max_iterations;   // the loop bound, only ever lowered
-  int num_iterations;   // iterations replayed
-  int done;
-  int best_solution;    // -1 (the calibrated call's slot of the best model; unused by the eight-point call)
-  int pad[2];
-  double model[kTwoViewModel];
-};
-
-struct TwoViewRansacBatch {
-  int num_selected;
-  int max_iterations;             // the options' value: the stride of samples and hypothesis_cost
-  int chunk;
-  int chunk_start;
-  unsigned long long seed;
-  // static per call
-  const int* sel_pair;            // [num_selected] pair index (the row of the caller's sample table)
-  const unsigned* sel_stream;     // [num_selected] the p of the sample stream
-  const long long* sel_ptr;       // [num_selected + 1] the pair's correspondences in the arrays below
-  const double* threshold;        // [num_selected]
-  const int* samples;             // caller's table [8 max_iterations num_pairs], or null
-  const int* bound_table;         // ComputeMaxIterations per inlier count: pair s, count k at sel_ptr[s] + s + k
-  const double *x1, *y1, *x2, *y2;  // [M] centred pixels
-  // per chunk
-  const int* active;              // [num_active] slots still running
-  int num_active;
-  double* models;                 // [num_active chunk kTwoViewModel]
-  int* has_model;                 // [num_active chunk] 0 or 1
-  int* cost;                      // [num_active chunk]
-  TwoViewRansacState* state;      // [num_selected]
-  int* hypothesis_cost;           // [num_selected max_iterations] or null
-};
-
-// The sample of iteration i of stream p among n >= 8 correspondences: eight swaps of a partial Fisher-Yates on the
-// identity.  cur[] holds positions 0..7, (epos, eval) what the swaps put at positions >= 8; every index is static.
-__device__ __forceinline__ void two_view_sample(unsigned long long seed, unsigned p, int i, int n, int s[8]) {
-#pragma clang fp contract(off)
-  int cur[8], epos[8], eval[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    cur[k] = k;
-    epos[k] = -1;
-    eval[k] = 0;
-  }
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const unsigned long long c = 8ull * (((unsigned long long)p << 32) + (unsigned long long)i) + k;
-    const double u = ((double)(splitmix64_word(seed, c) >> 11) + 0.5) * (1.0 / 9007199254740992.0);
-    int j = k + (int)(u * (double)(n - k));
-    j = j < n - 1 ? j : n - 1;
-    int v = j;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) v = j == q ? cur[q] : v;
-#pragma unroll
-    for (int m = 0; m < 8; ++m)
-      if (m < k) v = epos[m] == j ? eval[m] : v;
-    const int old = cur[k];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) cur[q] = j == q ? old : cur[q];
-    epos[k] = j >= 8 ? j : -1;
-    eval[k] = old;
-    cur[k] = v;
-  }
-#pragma unroll
-  for (int k = 0; k < 8; ++k) s[k] = cur[k];
-}
 
 // NormalizeImagePoints (pose/util.cc:82-115) on eight points: nf = sqrt(2) / rms, T = [nf 0 tx; 0 nf ty; 0 0 1].
 __device__ __forceinline__ void two_view_normalization(const double x[8], const double y[8], double* nf, double* tx,
@@ -442,37 +370,6 @@ __device__ bool two_view_model(const double x1[8], const double y1[8], const dou
 #undef TMI_TV_A
 }
 
-__global__ __launch_bounds__(64) void two_view_hypothesis_kernel(TwoViewRansacBatch B) {
-  __shared__ double slab[81 * 64];
-  const long long id = (long long)blockIdx.x * 64 + threadIdx.x;
-  if (id >= (long long)B.num_active * B.chunk) return;
-  const int a = (int)(id / B.chunk), j = (int)(id % B.chunk);
-  const int s = B.active[a];
-  const int i = B.chunk_start + j;
-  B.has_model[id] = 0;
-  if (i >= B.state[s].max_iterations) return;
-  const long long o0 = B.sel_ptr[s];
-  const int n = (int)(B.sel_ptr[s + 1] - o0);
-  int smp[8];
-  if (B.samples) {
-    const int* t = B.samples + 8 * ((long long)B.max_iterations * B.sel_pair[s] + i);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) smp[k] = t[k];
-  } else {
-    two_view_sample(B.seed, B.sel_stream[s], i, n, smp);
-  }
-  double x1[8], y1[8], x2[8], y2[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const long long o = o0 + smp[k];
-    x1[k] = B.x1[o];
-    y1[k] = B.y1[o];
-    x2[k] = B.x2[o];
-    y2[k] = B.y2[o];
-  }
-  if (two_view_model(x1, y1, x2, y2, slab + threadIdx.x, B.models + kTwoViewModel * id)) B.has_model[id] = 1;
-}
-
 // 1 where the correspondence is no inlier of the model: behind a camera, or a squared Sampson distance of the centred
 // pixels (pose/util.cc:56-68) that is not below the threshold (NaN included)
 __device__ __forceinline__ int two_view_outlier(const double* __restrict__ m, double x1, double y1, double x2, double y2,
@@ -491,105 +388,37 @@ __device__ __forceinline__ int two_view_outlier(const double* __restrict__ m, do
   return (ea > 0.0 && eb > 0.0 && err < thresh) ? 0 : 1;
 }
 
-__global__ __launch_bounds__(256) void two_view_score_kernel(TwoViewRansacBatch B) {
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int lane = threadIdx.x & 63;
-  const long long id = (long long)blockIdx.x * 4 + wave;
-  if (id >= (long long)B.num_active * B.chunk) return;
-  if (B.has_model[id] == 0) return;
-  const int s = B.active[(int)(id / B.chunk)];
-  const long long o0 = B.sel_ptr[s];
-  const int n = (int)(B.sel_ptr[s + 1] - o0);
-  const double thresh = B.threshold[s];
-  const double* __restrict__ m = B.models + kTwoViewModel * id;
-  int c = 0;
-  for (int q = lane; q < n; q += 64) {
-    const long long o = o0 + q;
-    c += two_view_outlier(m, B.x1[o], B.y1[o], B.x2[o], B.y2[o], thresh);
+// The correspondence planes of RansacBatch are x1, y1, x2, y2: centred pixels.
+struct TwoViewOutlier {
+  static constexpr int kModel = kTwoViewModel, kPlanes = 4;
+  __device__ __forceinline__ static int outlier(const double* __restrict__ m, const double x[kPlanes], double thresh) {
+    return two_view_outlier(m, x[0], x[1], x[2], x[3], thresh);
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
-  if (lane == 0) B.cost[id] = c;
-}
+};
 
-__global__ __launch_bounds__(64) void two_view_replay_kernel(TwoViewRansacBatch B) {
-  const int a = blockIdx.x * 64 + threadIdx.x;
-  if (a >= B.num_active) return;
-  const int s = B.active[a];
-  TwoViewRansacState* sp = B.state + s;
-  int best_cost = sp->best_cost, best_iteration = sp->best_iteration, max_iterations = sp->max_iterations;
-  int num_iterations = sp->num_iterations;
-  const long long o0 = B.sel_ptr[s];
-  const int n = (int)(B.sel_ptr[s + 1] - o0);
-  const int* __restrict__ bound = B.bound_table + o0 + s;
-  int best_j = -1;
-  for (int j = 0; j < B.chunk; ++j) {
-    const int i = B.chunk_start + j;
-    if (i >= max_iterations) break;
-    const long long id = (long long)a * B.chunk + j;
-    int c = -1;
-    if (B.has_model[id] != 0) {
-      c = B.cost[id];
-      if (c < best_cost) {
-        best_cost = c;
-        best_iteration = i;
-        best_j = j;
-        const int inliers = n - c;
-        if (inliers >= 8) {  // (inlier_ratio < 8 / n skips the update of the bound)
-          const int m = bound[inliers];
-          if (m < max_iterations) max_iterations = m;
-        }
-      }
-    }
-    if (B.hypothesis_cost) B.hypothesis_cost[(long long)s * B.max_iterations + i] = c;
-    num_iterations = i + 1;
+struct EightPointProblem : TwoViewOutlier {
+  static constexpr int kSample = 8, kSlots = 1, kScoreSlots = 1, kThreads = 64, kSlab = 81;
+  __device__ static void models(const double pts[kPlanes][kSample], double* slab, double* __restrict__ model, int* has) {
+    if (two_view_model(pts[0], pts[1], pts[2], pts[3], slab, model)) has[0] = 1;
   }
-  sp->best_cost = best_cost;
-  sp->best_iteration = best_iteration;
-  sp->max_iterations = max_iterations;
-  sp->num_iterations = num_iterations;
-  if (num_iterations >= max_iterations) sp->done = 1;
-  if (best_j >= 0) {
-    const double* m = B.models + kTwoViewModel * ((long long)a * B.chunk + best_j);
-    for (int q = 0; q < kTwoViewModel; ++q) sp->model[q] = m[q];
-  }
-}
+};
 
 // One wavefront per attempted pair.  status 2: no model.  model_out [num_selected 17]: F column-major, f1, f2, the
 // rotation as angle-axis (Ceres' RotationMatrixToAngleAxis), the position.
-__global__ __launch_bounds__(64) void two_view_final_kernel(TwoViewRansacBatch B, unsigned char* __restrict__ slot_inlier,
+__global__ __launch_bounds__(64) void two_view_final_kernel(RansacBatch B, unsigned char* __restrict__ slot_inlier,
                                                             int* __restrict__ num_inliers,
                                                             signed char* __restrict__ status,
                                                             double* __restrict__ model_out) {
 #pragma clang fp contract(off)
   const int s = blockIdx.x;
   const int lane = threadIdx.x;
-  const TwoViewRansacState* st = B.state + s;
-  const long long o0 = B.sel_ptr[s];
-  const int n = (int)(B.sel_ptr[s + 1] - o0);
   double* mo = model_out + 17 * s;
-  if (st->best_iteration < 0) {
-    for (int q = lane; q < n; q += 64) slot_inlier[o0 + q] = 0;
+  if (ransac_final_inliers<TwoViewOutlier>(B, s, lane, slot_inlier, num_inliers, status) < 0) {
     if (lane < 17) mo[lane] = 0.0;
-    if (lane == 0) {
-      num_inliers[s] = 0;
-      status[s] = 2;
-    }
     return;
   }
-  const double thresh = B.threshold[s];
-  const double* m = st->model;
-  int count = 0;
-  for (int q = lane; q < n; q += 64) {
-    const long long o = o0 + q;
-    const int out = two_view_outlier(m, B.x1[o], B.y1[o], B.x2[o], B.y2[o], thresh);
-    slot_inlier[o] = (unsigned char)(1 - out);
-    count += 1 - out;
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) count += __shfl_xor(count, off, 64);
+  const double* m = B.state[s].model;
   if (lane == 0) {
-    num_inliers[s] = count;
     status[s] = 0;
     double Rc[9], aa[3];  // column-major for rotation_matrix_to_angle_axis
 #pragma unroll
