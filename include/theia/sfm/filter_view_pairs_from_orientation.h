@@ -10,6 +10,7 @@
 
 #include "theia/sfm/twoview_info.h"
 #include "theia/sfm/types.h"
+#include "theia/sfm/view_graph/view_graph.h"
 #include "theia/util/eigen_lite.h"
 
 namespace theia {
@@ -21,5 +22,11 @@ namespace theia {
 int FilterViewPairsFromOrientation(const std::unordered_map<ViewId, Eigen::Vector3d>& orientations,
                                    double max_relative_rotation_difference_degrees,
                                    std::vector<std::pair<ViewIdPair, TwoViewInfo*>>* edges, int device = -1);
+
+// The reference's signature (filter_view_pairs_from_orientation.h:59-62): the call above on the graph's edges in
+// ascending ViewIdPair order, the flagged edges removed from the graph (theiasfm_amd/host/view_graph_ops.cc).
+void FilterViewPairsFromOrientation(const std::unordered_map<ViewId, Eigen::Vector3d>& orientations,
+                                    double max_relative_rotation_difference_degrees, ViewGraph* view_graph,
+                                    int device = -1);
 }  // namespace theia
 #endif

@@ -15,6 +15,7 @@
 
 #include "theia/sfm/twoview_info.h"
 #include "theia/sfm/types.h"
+#include "theia/sfm/view_graph/view_graph.h"
 #include "theia/util/eigen_lite.h"
 
 namespace theia {
@@ -45,5 +46,11 @@ struct FilterViewPairsFromRelativeTranslationOptions {
 int FilterViewPairsFromRelativeTranslation(const FilterViewPairsFromRelativeTranslationOptions& options,
                                            const std::unordered_map<ViewId, Eigen::Vector3d>& orientations,
                                            std::vector<std::pair<ViewIdPair, TwoViewInfo*>>* edges, int device = -1);
+
+// The reference's signature (filter_view_pairs_from_relative_translation.h:75-78): the call above on the graph's edges
+// in ascending ViewIdPair order, the flagged edges removed from the graph (theiasfm_amd/host/view_graph_ops.cc).
+void FilterViewPairsFromRelativeTranslation(const FilterViewPairsFromRelativeTranslationOptions& options,
+                                            const std::unordered_map<ViewId, Eigen::Vector3d>& orientations,
+                                            ViewGraph* view_graph, int device = -1);
 }  // namespace theia
 #endif

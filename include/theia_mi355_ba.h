@@ -1520,6 +1520,86 @@ int32_t tmi_ba_build_tracks(const tmi_ba_track_build_options* options, int64_t n
                             int64_t obs_capacity, int64_t* track_begin, uint32_t* obs_view, uint32_t* obs_feature,
                             uint32_t* endpoint_node, uint32_t* endpoint_label, tmi_ba_track_build_summary* summary);
 
+/* ---- the view-graph steps between the edge filters and the global solvers ---------------------
+ * reference: RemoveDisconnectedViewPairs (view_graph/remove_disconnected_view_pairs.cc:48-95; called after every
+ * filtering step, global_reconstruction_estimator.cc:312, 366, 398) and OrientationsFromMaximumSpanningTree
+ * (view_graph/orientations_from_maximum_spanning_tree.cc:109-180; the start RobustRotationEstimator is given,
+ * global_reconstruction_estimator.cc:326-334).  Both take tmi_ba_view_pair_batch; only num_views, num_pairs, pair_view1
+ * and pair_view2 are read, and pair_rotation2 by the orientations.  UNLIKE the filters a repeated unordered pair is
+ * accepted.  pair_mask [num_pairs]: 0 = the edge is not there (already filtered); NULL = every edge is alive.
+ *
+ * tmi_ba_largest_connected_component:
+ *   1. :52-59   Components over the alive edges.  view_label[v] is the smallest view index of v's component; a view
+ *               without an alive edge is a component of its own (the reference never sees such a view).
+ *   2. :61-69   The largest component is the one with the most views; AMONG EQUALS THE ONE WITH THE SMALLEST LABEL,
+ *               where the reference takes the first its hash map yields.  Only components with at least one edge
+ *               compete.  view_in_largest[v] = 1 for its views.
+ *   3. :71-86   pair_keep[e] = 1 exactly for the alive edges inside the largest component (the edges
+ *               RemoveView leaves in the graph).
+ *   With no alive edge there is no component to keep: view_in_largest and pair_keep are all 0, largest_label = -1 and
+ *   the call returns TMI_BA_OK (the reference's loops have nothing to remove).
+ * summary: num_components counts the components with at least one edge; num_pairs_removed the alive edges outside the
+ * largest component; num_views_removed the views of the OTHER components with at least one edge -- the size of the
+ * set the reference returns.  Outputs, each may be NULL: view_label [num_views] int32, view_in_largest [num_views],
+ * pair_keep [num_pairs].
+ *
+ * tmi_ba_orientations_from_maximum_spanning_tree, per call in this order:
+ *   1. :114-119 The largest component as above.
+ *   2. :121-136 The maximum spanning tree of that component by weight pair_num_verified_matches: exactly the tree the
+ *               reference's Kruskal gives.  Its std::sort over pair<int, pair<ViewId, ViewId>>
+ *               (math/graph/minimum_spanning_tree.h:83) is a total order, ascending (-num_verified_matches,
+ *               min(view1, view2), max(view1, view2)) (a repeated pair: then the edge index); under a total order the
+ *               minimum spanning tree is unique, and the device finds it by Boruvka rounds on the ranks of that order.
+ *   3. :152     The root.  root_view == -1: the smallest view index of the largest component.  A NAMED ROOT where the
+ *               reference takes mst.begin()->first of a hash set.  A root outside the largest component:
+ *               TMI_BA_ERR_INVALID_ARGUMENT, every output untouched.
+ *   4. :62-84   The root's orientation is 0.  Every other view of the tree gets ComputeOrientation from its tree
+ *               parent: Ceres' AngleAxisToRotationMatrix of the parent's orientation and of the edge's pair_rotation2,
+ *               R_rel R_parent when the parent is pair_view1 of the edge and R_rel^T R_parent when it is pair_view2,
+ *               Ceres' RotationMatrixToAngleAxis -- the conversion at every step, as in the reference.  A view's value
+ *               depends on its parent's alone, so the reference's heap order (:149-178) does not matter.
+ * Outputs, each may be NULL: view_orientation [3 * num_views] (views outside the tree ARE LEFT AS THEY WERE),
+ * view_parent, view_parent_pair, view_depth [num_views] int32 (-1 for the root's parent and parent pair and for every
+ * view outside the tree; the root's depth is 0), pair_in_tree [num_pairs].
+ * No alive edge: TMI_BA_OK, summary->usable = 0, num_tree_pairs = 0 and no array written (the reference returns false,
+ * minimum_spanning_tree.h:71-74).  Otherwise usable = 1 and num_tree_pairs = largest_num_views - 1.
+ *
+ * Both calls: all integer results go through integer atomics only, so two calls give the same bytes.
+ * TMI_BA_ERR_INVALID_ARGUMENT, before the device is looked for: a null batch or summary, a missing array, negative
+ * counts, a view index out of range, a pair of a view with itself, a negative num_verified_matches on an alive edge,
+ * root_view outside [-1, num_views).  Without a device: TMI_BA_ERR_NO_DEVICE.  A loop bound reached on the device, or a
+ * tree that does not span the component (never, by the argument in view_graph_kernels.h): TMI_BA_ERR_DEVICE.  ON EVERY
+ * FAILURE EVERY OUTPUT, THE SUMMARY INCLUDED, IS LEFT AS IT WAS. */
+typedef struct tmi_ba_view_graph_component_summary {
+  int32_t num_components;     /* components with at least one edge               */
+  int32_t largest_label;      /* -1: no alive edge                               */
+  int32_t largest_num_views;
+  int32_t num_pairs_kept;
+  int32_t num_pairs_removed;  /* alive edges outside the largest component       */
+  int32_t num_views_removed;  /* views of the other components with an edge      */
+  double  seconds;
+  double  kernel_seconds;
+} tmi_ba_view_graph_component_summary;
+
+typedef struct tmi_ba_spanning_tree_summary {
+  tmi_ba_view_graph_component_summary component;  /* seconds / kernel_seconds: of the whole call */
+  int32_t num_tree_pairs;
+  int32_t tree_depth;         /* the largest view_depth                          */
+  int32_t root_view;          /* -1 when not usable                              */
+  int32_t usable;             /* 0: no alive edge, nothing written               */
+} tmi_ba_spanning_tree_summary;
+
+int32_t tmi_ba_largest_connected_component(const tmi_ba_view_pair_batch* batch, const uint8_t* pair_mask,
+                                           int32_t device, int32_t* view_label, uint8_t* view_in_largest,
+                                           uint8_t* pair_keep, tmi_ba_view_graph_component_summary* summary);
+
+int32_t tmi_ba_orientations_from_maximum_spanning_tree(const tmi_ba_view_pair_batch* batch,
+                                                       const int32_t* pair_num_verified_matches,
+                                                       const uint8_t* pair_mask, int32_t root_view, int32_t device,
+                                                       double* view_orientation, int32_t* view_parent,
+                                                       int32_t* view_parent_pair, int32_t* view_depth,
+                                                       uint8_t* pair_in_tree, tmi_ba_spanning_tree_summary* summary);
+
 /* ---- batched EstimateUncalibratedRelativePose: eight-point RANSAC for many uncalibrated view pairs -------
  * reference: the UNCALIBRATED branch of EstimateTwoViewInfo (estimate_twoview_info.cc:202-248), which the reference's
  * application runs for every view without an EXIF focal length: EstimateUncalibratedRelativePose with

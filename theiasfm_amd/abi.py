@@ -374,6 +374,31 @@ class CViewPairFilterSummary(C.Structure):
     ]
 
 
+class CViewGraphComponentSummary(C.Structure):
+    """tmi_ba_view_graph_component_summary."""
+    _fields_ = [
+        ("num_components", C.c_int32),
+        ("largest_label", C.c_int32),
+        ("largest_num_views", C.c_int32),
+        ("num_pairs_kept", C.c_int32),
+        ("num_pairs_removed", C.c_int32),
+        ("num_views_removed", C.c_int32),
+        ("seconds", C.c_double),
+        ("kernel_seconds", C.c_double),
+    ]
+
+
+class CSpanningTreeSummary(C.Structure):
+    """tmi_ba_spanning_tree_summary."""
+    _fields_ = [
+        ("component", CViewGraphComponentSummary),
+        ("num_tree_pairs", C.c_int32),
+        ("tree_depth", C.c_int32),
+        ("root_view", C.c_int32),
+        ("usable", C.c_int32),
+    ]
+
+
 class CRelativeRotationBatch(C.Structure):
     """tmi_ba_relative_rotation_batch (the rotation estimator)."""
     _fields_ = [

@@ -3665,6 +3665,280 @@ int32_t tmi_ba_build_tracks(const tmi_ba_track_build_options* O, int64_t num_edg
 #undef TMI_TB
 }  // extern "C"
 
+// ---- the view-graph steps: largest component, MST orientations (view_graph_kernels.h) -----------
+namespace {
+// What both calls ask of the batch, the mask and (need_weights) the weights.  null: fine.
+const char* check_view_graph_arguments(const tmi_ba_view_pair_batch* B, const uint8_t* mask, bool need_weights,
+                                       const int32_t* weight) {
+  const int V = B->num_views, E = B->num_pairs;
+  if (V < 0 || E < 0) return "view graph: negative size";
+  if (E > 0 && (!B->pair_view1 || !B->pair_view2)) return "view graph: missing array";
+  if (need_weights && E > 0 && (!weight || !B->pair_rotation2)) return "view graph: missing array";
+  if (E > (1 << 30)) return "view graph: more than 2^30 pairs";
+  for (int e = 0; e < E; ++e) {
+    const int a = B->pair_view1[e], b = B->pair_view2[e];
+    if (a < 0 || a >= V || b < 0 || b >= V) return "view graph: view index out of range";
+    if (a == b) return "view graph: a view paired with itself";
+    if (need_weights && (!mask || mask[e]) && weight[e] < 0)
+      return "view graph: negative num_verified_matches on an alive edge";
+  }
+  return nullptr;
+}
+
+struct ViewGraphDevice {
+  int *view1, *view2;
+  unsigned char *mask, *keep;
+  unsigned *label, *size;
+  unsigned long long* counters;
+};
+
+#define TMI_VG(call)                  \
+  do {                                \
+    const int rc_ = (call);           \
+    if (rc_ != TMI_BA_OK) return rc_; \
+  } while (0)
+
+// Uploads the edges and queues steps 1 to 3 of tmi_ba_largest_connected_component: label [V], keep [E], counters.
+int vg_queue_components(OneShot* s, const tmi_ba_view_pair_batch* B, const uint8_t* mask, ViewGraphDevice* D,
+                        StreamTimer* timer) {
+  const int V = B->num_views, E = B->num_pairs;
+  const hipStream_t stream = s->stream;
+  auto grid = [](long long n) { return dim3((unsigned)((n + 255) / 256)); };
+  unsigned* d_parent;
+  D->mask = nullptr;
+  TMI_HIP(s->upload(&D->view1, (const int*)B->pair_view1, (size_t)E));
+  TMI_HIP(s->upload(&D->view2, (const int*)B->pair_view2, (size_t)E));
+  if (mask) TMI_HIP(s->upload(&D->mask, (const unsigned char*)mask, (size_t)E));
+  TMI_HIP(s->alloc(&D->keep, (size_t)E));
+  TMI_HIP(s->alloc(&d_parent, (size_t)V));
+  TMI_HIP(s->alloc(&D->label, (size_t)V));
+  TMI_HIP(s->alloc(&D->size, (size_t)V));
+  TMI_HIP(s->alloc(&D->counters, (size_t)kVgCounters));
+  TMI_HIP(hipMemsetAsync(D->size, 0, (size_t)V * sizeof(unsigned), stream));
+  TMI_HIP(hipMemsetAsync(D->counters, 0, kVgCounters * sizeof(unsigned long long), stream));
+  TMI_HIP(timer->mark());
+  hipLaunchKernelGGL(tb_iota_kernel, grid(V), dim3(256), 0, stream, d_parent, (unsigned)V);
+  hipLaunchKernelGGL(vg_union_kernel, grid(E), dim3(256), 0, stream, D->view1, D->view2, D->mask, E, (unsigned)V, d_parent,
+                     D->counters);
+  hipLaunchKernelGGL(tb_flatten_kernel, grid(V), dim3(256), 0, stream, d_parent, (unsigned)V, D->label, D->counters);
+  hipLaunchKernelGGL(tb_sizes_kernel, grid(V), dim3(256), 0, stream, D->label, (unsigned)V, D->size);
+  hipLaunchKernelGGL(vg_component_stats_kernel, grid(V), dim3(256), 0, stream, D->label, D->size, (unsigned)V, D->counters);
+  hipLaunchKernelGGL(vg_keep_kernel, grid(E), dim3(256), 0, stream, D->view1, D->mask, D->label, E, D->keep, D->counters);
+  return TMI_BA_OK;
+}
+
+// The component summary from the counters; false: the device reported impossible totals.
+bool vg_component_summary(const unsigned long long* c, int V, int E, tmi_ba_view_graph_component_summary* sum) {
+  const unsigned long long best = c[kVgBest];
+  const unsigned long long size = best >> 32, label = 0xffffffffull - (best & 0xffffffffull);
+  if (c[kVgAlive] > (unsigned long long)E || c[kVgKept] > c[kVgAlive] || c[kVgEdgeViews] > (unsigned long long)V ||
+      size > c[kVgEdgeViews] || (best && (label >= (unsigned long long)V || size < 2 || !c[kVgKept])) ||
+      (!best && (c[kVgAlive] || c[kVgComponents])))
+    return false;
+  sum->num_components = (int32_t)c[kVgComponents];
+  sum->largest_label = best ? (int32_t)label : -1;
+  sum->largest_num_views = (int32_t)size;
+  sum->num_pairs_kept = (int32_t)c[kVgKept];
+  sum->num_pairs_removed = (int32_t)(c[kVgAlive] - c[kVgKept]);
+  sum->num_views_removed = (int32_t)(c[kVgEdgeViews] - size);
+  return true;
+}
+}  // namespace
+extern "C" {
+
+int32_t tmi_ba_largest_connected_component(const tmi_ba_view_pair_batch* Bh, const uint8_t* pair_mask, int32_t device,
+                                           int32_t* view_label, uint8_t* view_in_largest, uint8_t* pair_keep,
+                                           tmi_ba_view_graph_component_summary* summary) {
+  if (!Bh || !summary) return bad_argument("largest component: null batch or summary");
+  const double t0 = now_s();
+  // argument errors before the device is looked for
+  if (const char* why = check_view_graph_arguments(Bh, pair_mask, false, nullptr)) return bad_argument(why);
+  const int V = Bh->num_views, E = Bh->num_pairs;
+  tmi_ba_view_graph_component_summary sum;  // the caller's is written on success only
+  memset(&sum, 0, sizeof(sum));
+  sum.largest_label = -1;
+  std::vector<int32_t> label_h((size_t)V);
+  std::vector<uint8_t> in_largest_h((size_t)V, 0), keep_h((size_t)E, 0);
+  for (int v = 0; v < V; ++v) label_h[v] = v;  // (E == 0: every view is its own component)
+  const int rc = one_shot_batch(device, "largest component: no such device", E, t0, &sum, [&](OneShot* s) -> int {
+    const hipStream_t stream = s->stream;
+    ViewGraphDevice D;
+    unsigned char* d_in_largest;
+    StreamTimer timer(stream);
+    TMI_HIP(timer.status);
+    TMI_HIP(s->alloc(&d_in_largest, (size_t)V));
+    TMI_VG(vg_queue_components(s, Bh, pair_mask, &D, &timer));
+    hipLaunchKernelGGL(vg_view_flags_kernel, dim3((V + 255) / 256), dim3(256), 0, stream, D.label, (unsigned)V, D.counters,
+                       d_in_largest);
+    TMI_HIP(timer.mark());
+    TMI_HIP(hipGetLastError());
+    unsigned long long counters[kVgCounters];
+    static_assert(sizeof(unsigned) == sizeof(int32_t), "labels are read back as they are");
+    TMI_HIP(hipMemcpyAsync(counters, D.counters, sizeof(counters), hipMemcpyDeviceToHost, stream));
+    TMI_HIP(hipMemcpyAsync(label_h.data(), D.label, (size_t)V * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    TMI_HIP(hipMemcpyAsync(in_largest_h.data(), d_in_largest, (size_t)V, hipMemcpyDeviceToHost, stream));
+    TMI_HIP(hipMemcpyAsync(keep_h.data(), D.keep, (size_t)E, hipMemcpyDeviceToHost, stream));
+    TMI_HIP(hipStreamSynchronize(stream));
+    if (counters[kVgError]) {
+      s->error = "largest component: a device loop reached its bound";
+      return TMI_BA_ERR_DEVICE;
+    }
+    if (!vg_component_summary(counters, V, E, &sum)) {
+      s->error = "largest component: the device reported impossible totals";
+      return TMI_BA_ERR_DEVICE;
+    }
+    sum.kernel_seconds = timer.seconds();
+    return TMI_BA_OK;
+  });
+  if (rc != TMI_BA_OK) return rc;
+  if (view_label) std::copy(label_h.begin(), label_h.end(), view_label);
+  if (view_in_largest) std::copy(in_largest_h.begin(), in_largest_h.end(), view_in_largest);
+  if (pair_keep) std::copy(keep_h.begin(), keep_h.end(), pair_keep);
+  sum.seconds = now_s() - t0;
+  *summary = sum;
+  return TMI_BA_OK;
+}
+
+int32_t tmi_ba_orientations_from_maximum_spanning_tree(const tmi_ba_view_pair_batch* Bh,
+                                                       const int32_t* pair_num_verified_matches,
+                                                       const uint8_t* pair_mask, int32_t root_view, int32_t device,
+                                                       double* view_orientation, int32_t* view_parent,
+                                                       int32_t* view_parent_pair, int32_t* view_depth,
+                                                       uint8_t* pair_in_tree, tmi_ba_spanning_tree_summary* summary) {
+  if (!Bh || !summary) return bad_argument("spanning tree: null batch or summary");
+  const double t0 = now_s();
+  // argument errors before the device is looked for
+  if (const char* why = check_view_graph_arguments(Bh, pair_mask, true, pair_num_verified_matches)) return bad_argument(why);
+  const int V = Bh->num_views, E = Bh->num_pairs;
+  if (root_view < -1 || root_view >= V) return bad_argument("spanning tree: root_view outside [-1, num_views)");
+  tmi_ba_spanning_tree_summary sum;  // the caller's is written on success only
+  memset(&sum, 0, sizeof(sum));
+  sum.component.largest_label = -1;
+  sum.root_view = -1;
+  std::vector<double> orientation_h;
+  std::vector<int32_t> parent_h, parent_pair_h, depth_h;
+  std::vector<uint8_t> in_tree_h;
+  const int rc = one_shot_batch(device, "spanning tree: no such device", E, t0, &sum.component, [&](OneShot* s) -> int {
+    const hipStream_t stream = s->stream;
+    auto grid = [](long long n) { return dim3((unsigned)((n + 255) / 256)); };
+    ViewGraphDevice D;
+    StreamTimer timer(stream);
+    TMI_HIP(timer.status);
+    int *d_weight, *d_tree;  // d_tree [5 V]: parent, parent pair, depth, the two frontiers
+    unsigned *d_index, *d_by_pair, *d_weight_key, *d_weight_key_sorted, *d_edge_of_rank, *d_comp, *d_hook, *d_best;
+    unsigned *d_degree, *d_row_ptr, *d_cursor;
+    unsigned long long *d_pair_key, *d_pair_key_sorted;
+    unsigned char* d_in_tree;
+    int2* d_row;
+    double *d_relative, *d_orientation;
+    const size_t Vs = (size_t)V, Es = (size_t)E;
+    TMI_HIP(s->upload(&d_weight, (const int*)pair_num_verified_matches, Es));
+    TMI_HIP(s->upload(&d_relative, Bh->pair_rotation2, 3 * Es));
+    TMI_HIP(s->alloc(&d_pair_key, Es));
+    TMI_HIP(s->alloc(&d_pair_key_sorted, Es));
+    TMI_HIP(s->alloc(&d_index, Es));
+    TMI_HIP(s->alloc(&d_by_pair, Es));
+    TMI_HIP(s->alloc(&d_weight_key, Es));
+    TMI_HIP(s->alloc(&d_weight_key_sorted, Es));
+    TMI_HIP(s->alloc(&d_edge_of_rank, Es));
+    TMI_HIP(s->alloc(&d_in_tree, Es));
+    TMI_HIP(s->alloc(&d_row, 2 * Es));  // (a tree has fewer edges than views; the flags can never exceed E)
+    TMI_HIP(s->alloc(&d_comp, Vs));
+    TMI_HIP(s->alloc(&d_hook, Vs));
+    TMI_HIP(s->alloc(&d_best, Vs));
+    TMI_HIP(s->alloc(&d_degree, Vs + 1));
+    TMI_HIP(s->alloc(&d_row_ptr, Vs + 1));
+    TMI_HIP(s->alloc(&d_cursor, Vs + 1));
+    TMI_HIP(s->alloc(&d_tree, 5 * Vs));
+    TMI_HIP(s->alloc(&d_orientation, 3 * Vs));
+    TMI_HIP(hipMemsetAsync(d_in_tree, 0, Es, stream));
+    TMI_HIP(hipMemsetAsync(d_degree, 0, (Vs + 1) * sizeof(unsigned), stream));
+    TMI_HIP(hipMemsetAsync(d_tree, 0xff, 3 * Vs * sizeof(int), stream));
+    TMI_HIP(hipMemsetAsync(d_orientation, 0, 3 * Vs * sizeof(double), stream));
+    // step 1
+    TMI_VG(vg_queue_components(s, Bh, pair_mask, &D, &timer));
+    // step 2: the ranks of the reference's order, then the Boruvka rounds
+    hipLaunchKernelGGL(vg_pair_keys_kernel, grid(E), dim3(256), 0, stream, D.view1, D.view2, E, d_pair_key, d_index);
+    TMI_VG(tb_sort_pairs(s, d_pair_key, d_pair_key_sorted, d_index, d_by_pair, Es, 32 + tb_bits((unsigned)V)));
+    hipLaunchKernelGGL(vg_weight_keys_kernel, grid(E), dim3(256), 0, stream, d_by_pair, d_weight, D.keep, E, d_weight_key);
+    TMI_VG(tb_sort_pairs(s, d_weight_key, d_weight_key_sorted, d_by_pair, d_edge_of_rank, Es, 32));
+    hipLaunchKernelGGL(tb_iota_kernel, grid(V), dim3(256), 0, stream, d_comp, (unsigned)V);
+    int rounds = 1;  // ceil(log2 V) + 1
+    while ((1ll << (rounds - 1)) < (long long)V) ++rounds;
+    for (int round = 0; round < rounds; ++round) {
+      TMI_HIP(hipMemsetAsync(d_best, 0xff, Vs * sizeof(unsigned), stream));
+      hipLaunchKernelGGL(vg_min_edge_kernel, grid(E), dim3(256), 0, stream, d_edge_of_rank, D.keep, D.view1, D.view2, d_comp,
+                         E, d_best);
+      hipLaunchKernelGGL(vg_hook_kernel, grid(V), dim3(256), 0, stream, d_edge_of_rank, D.view1, D.view2, d_comp, d_best,
+                         (unsigned)V, d_hook, d_in_tree);
+      hipLaunchKernelGGL(tb_flatten_kernel, grid(V), dim3(256), 0, stream, d_hook, (unsigned)V, d_comp, D.counters);
+    }
+    // steps 3 and 4: the tree's CSR and the walk from the root
+    hipLaunchKernelGGL(vg_tree_degree_kernel, grid(E), dim3(256), 0, stream, d_in_tree, D.view1, D.view2, E, d_degree,
+                       D.counters);
+    TMI_VG(tb_exclusive_sum(s, d_degree, d_row_ptr, Vs + 1));
+    TMI_HIP(hipMemcpyAsync(d_cursor, d_row_ptr, (Vs + 1) * sizeof(unsigned), hipMemcpyDeviceToDevice, stream));
+    hipLaunchKernelGGL(vg_tree_fill_kernel, grid(E), dim3(256), 0, stream, d_in_tree, D.view1, D.view2, E, d_cursor, d_row);
+    hipLaunchKernelGGL(vg_root_kernel, dim3(1), dim3(kVgRootThreads), 0, stream, V, (int)root_view, D.label, d_row_ptr,
+                       d_row, d_relative, d_orientation, d_tree, D.counters);
+    TMI_HIP(timer.mark());
+    TMI_HIP(hipGetLastError());
+    unsigned long long counters[kVgCounters];
+    orientation_h.resize(3 * Vs);
+    parent_h.resize(Vs);
+    parent_pair_h.resize(Vs);
+    depth_h.resize(Vs);
+    in_tree_h.resize(Es);
+    TMI_HIP(hipMemcpyAsync(counters, D.counters, sizeof(counters), hipMemcpyDeviceToHost, stream));
+    TMI_HIP(hipMemcpyAsync(orientation_h.data(), d_orientation, 3 * Vs * sizeof(double), hipMemcpyDeviceToHost, stream));
+    TMI_HIP(hipMemcpyAsync(parent_h.data(), d_tree, Vs * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    TMI_HIP(hipMemcpyAsync(parent_pair_h.data(), d_tree + Vs, Vs * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    TMI_HIP(hipMemcpyAsync(depth_h.data(), d_tree + 2 * Vs, Vs * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    TMI_HIP(hipMemcpyAsync(in_tree_h.data(), d_in_tree, Es, hipMemcpyDeviceToHost, stream));
+    TMI_HIP(hipStreamSynchronize(stream));
+    if (counters[kVgError]) {
+      s->error = "spanning tree: a device loop reached its bound";
+      return TMI_BA_ERR_DEVICE;
+    }
+    if (!vg_component_summary(counters, V, E, &sum.component)) {
+      s->error = "spanning tree: the device reported impossible totals";
+      return TMI_BA_ERR_DEVICE;
+    }
+    if (counters[kVgBadRoot]) {
+      s->error = "spanning tree: root_view is outside the largest component";
+      return TMI_BA_ERR_INVALID_ARGUMENT;
+    }
+    if (counters[kVgBest]) {
+      const unsigned long long views = (unsigned long long)sum.component.largest_num_views;
+      if (counters[kVgTreePairs] + 1 != views || counters[kVgReached] != views || counters[kVgDepth] >= views ||
+          counters[kVgRoot] >= (unsigned long long)V) {
+        s->error = "spanning tree: the device's tree does not span the largest component";
+        return TMI_BA_ERR_DEVICE;
+      }
+      sum.usable = 1;
+      sum.num_tree_pairs = (int32_t)counters[kVgTreePairs];
+      sum.tree_depth = (int32_t)counters[kVgDepth];
+      sum.root_view = (int32_t)counters[kVgRoot];
+    }
+    sum.component.kernel_seconds = timer.seconds();
+    return TMI_BA_OK;
+  });
+  if (rc != TMI_BA_OK) return rc;
+  if (sum.usable) {
+    for (int v = 0; v < V && view_orientation; ++v)
+      if (depth_h[v] >= 0) std::copy(&orientation_h[3 * (size_t)v], &orientation_h[3 * (size_t)v] + 3, view_orientation + 3 * (size_t)v);
+    if (view_parent) std::copy(parent_h.begin(), parent_h.end(), view_parent);
+    if (view_parent_pair) std::copy(parent_pair_h.begin(), parent_pair_h.end(), view_parent_pair);
+    if (view_depth) std::copy(depth_h.begin(), depth_h.end(), view_depth);
+    if (pair_in_tree) std::copy(in_tree_h.begin(), in_tree_h.end(), pair_in_tree);
+  }
+  sum.component.seconds = now_s() - t0;
+  *summary = sum;
+  return TMI_BA_OK;
+}
+#undef TMI_VG
+}  // extern "C"
+
 // ---- batched EstimateUncalibratedRelativePose: eight-point RANSAC (two_view_ransac_kernels.h) ----
 extern "C" {
 void tmi_ba_two_view_ransac_options_init(tmi_ba_two_view_ransac_options* o) {

@@ -36,6 +36,7 @@ EXPORTS = (
     "tmi_ba_two_view_verification_options_init", "tmi_ba_verify_two_views",
     "tmi_ba_translation_filter_options_init", "tmi_ba_filter_view_pairs_from_relative_translation",
     "tmi_ba_filter_view_pairs_from_orientation",
+    "tmi_ba_largest_connected_component", "tmi_ba_orientations_from_maximum_spanning_tree",
     "tmi_ba_robust_rotation_options_init", "tmi_ba_estimate_global_rotations_robust",
     "tmi_ba_lud_position_options_init", "tmi_ba_estimate_global_positions_lud",
     "tmi_ba_nonlinear_position_options_init", "tmi_ba_estimate_global_positions_nonlinear",
@@ -170,6 +171,13 @@ def load():
     L.tmi_ba_filter_view_pairs_from_relative_translation.restype = C.c_int32
     L.tmi_ba_filter_view_pairs_from_orientation.argtypes = [PB, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, PFS]
     L.tmi_ba_filter_view_pairs_from_orientation.restype = C.c_int32
+    L.tmi_ba_largest_connected_component.argtypes = [PB, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.POINTER(abi.CViewGraphComponentSummary)]
+    L.tmi_ba_largest_connected_component.restype = C.c_int32
+    L.tmi_ba_orientations_from_maximum_spanning_tree.argtypes = [
+        PB, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+        C.POINTER(abi.CSpanningTreeSummary)]
+    L.tmi_ba_orientations_from_maximum_spanning_tree.restype = C.c_int32
     RO = C.POINTER(abi.CRobustRotationOptions)
     L.tmi_ba_robust_rotation_options_init.argtypes = [RO]
     L.tmi_ba_robust_rotation_options_init.restype = None
@@ -517,6 +525,61 @@ def filter_view_pairs_from_orientation(batch: abi.ViewPairBatch, max_relative_ro
     if st != 0:
         raise EngineError(st, "tmi_ba_filter_view_pairs_from_orientation")
     return removed, angle, fs
+
+
+def _mask_pointer(pair_mask, n):
+    if pair_mask is None:
+        return None, None
+    m = np.ascontiguousarray(pair_mask, dtype=np.uint8)
+    if m.shape != (n,):
+        raise ValueError("pair_mask must hold one entry per pair")
+    return m, m.ctypes.data
+
+
+def largest_connected_component(batch: abi.ViewPairBatch, pair_mask=None, device: int = -1):
+    """The component step of RemoveDisconnectedViewPairs on the device.  pair_mask [P]: 0 = the edge is not there.
+    Returns (view_label [V] int32, view_in_largest [V] uint8, pair_keep [P] uint8, CViewGraphComponentSummary)."""
+    L = load()
+    cb = batch.as_c()
+    n, V = batch.num_pairs, batch.num_views
+    mask, mask_p = _mask_pointer(pair_mask, n)
+    label = np.full(V, -1, dtype=np.int32)
+    in_largest = np.zeros(V, dtype=np.uint8)
+    keep = np.zeros(n, dtype=np.uint8)
+    cs = abi.CViewGraphComponentSummary()
+    st = L.tmi_ba_largest_connected_component(C.byref(cb), mask_p, int(device), label.ctypes.data,
+                                              in_largest.ctypes.data, keep.ctypes.data, C.byref(cs))
+    if st != 0:
+        raise EngineError(st, "tmi_ba_largest_connected_component")
+    return label, in_largest, keep, cs
+
+
+def orientations_from_maximum_spanning_tree(batch: abi.ViewPairBatch, pair_num_verified_matches, pair_mask=None,
+                                            root_view: int = -1, device: int = -1, view_orientation=None):
+    """OrientationsFromMaximumSpanningTree on the device (batch.pair_rotation2 holds the relative rotations).
+    view_orientation [V, 3]: the values the views outside the tree keep (default: NaN).
+    Returns a dict: orientation [V, 3], parent, parent_pair, depth [V] int32, in_tree [P] uint8, summary
+    (CSpanningTreeSummary).  Raises EngineError on any failure."""
+    L = load()
+    cb = batch.as_c()
+    n, V = batch.num_pairs, batch.num_views
+    mask, mask_p = _mask_pointer(pair_mask, n)
+    w = np.ascontiguousarray(pair_num_verified_matches, dtype=np.int32)
+    if w.shape != (n,):
+        raise ValueError("pair_num_verified_matches must hold one entry per pair")
+    o = np.full((V, 3), np.nan) if view_orientation is None else \
+        np.ascontiguousarray(view_orientation, dtype=np.float64).reshape(V, 3).copy()
+    parent = np.full(V, -1, dtype=np.int32)
+    parent_pair = np.full(V, -1, dtype=np.int32)
+    depth = np.full(V, -1, dtype=np.int32)
+    in_tree = np.zeros(n, dtype=np.uint8)
+    ts = abi.CSpanningTreeSummary()
+    st = L.tmi_ba_orientations_from_maximum_spanning_tree(
+        C.byref(cb), w.ctypes.data, mask_p, int(root_view), int(device), o.ctypes.data, parent.ctypes.data,
+        parent_pair.ctypes.data, depth.ctypes.data, in_tree.ctypes.data, C.byref(ts))
+    if st != 0:
+        raise EngineError(st, "tmi_ba_orientations_from_maximum_spanning_tree")
+    return dict(orientation=o, parent=parent, parent_pair=parent_pair, depth=depth, in_tree=in_tree, summary=ts)
 
 
 def estimate_global_rotations_robust(batch: abi.RelativeRotationBatch, view_rotation, fixed_view: int = 0, options=None,
