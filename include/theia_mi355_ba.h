@@ -1210,6 +1210,109 @@ int32_t tmi_ba_estimate_global_positions_nonlinear(const tmi_ba_view_pair_batch*
                                                    double* pair_residual,
                                                    tmi_ba_nonlinear_position_summary* summary);
 
+/* ---- NonlinearRotationEstimator: global orientations by Levenberg-Marquardt on the relative rotation error ----
+ * reference: nonlinear_rotation_estimator.cc:49-100 (GlobalRotationEstimatorType::NONLINEAR,
+ * global_reconstruction_estimator.cc:335-339, hybrid_reconstruction_estimator.cc:329-334) with
+ * pairwise_rotation_error.h:65-95 and Ceres 1.14's TrustRegionMinimizer, LevenbergMarquardtStrategy, SoftLOneLoss,
+ * Corrector and rotation.h.  robust_loss_width is the constructor's (nonlinear_rotation_estimator.h, default 0.1),
+ * max_num_iterations is :94; the trust-region fields are Ceres' Solver::Options defaults, which the reference leaves
+ * alone. */
+typedef struct tmi_ba_nonlinear_rotation_options {
+  int32_t  max_num_iterations;                 /* 200; 0: the start is evaluated and returned              */
+  double   robust_loss_width;                  /* 0.1, SoftLOneLoss                                         */
+  int32_t  fixed_view;                         /* -1: no view is held, the reference's problem; >= 0: that
+                                                  view is held constant (EXTENSION)                         */
+  int32_t  jacobi_scaling;                     /* 1                                                         */
+  int32_t  max_num_consecutive_invalid_steps;  /* 5                                                         */
+  double   function_tolerance;                 /* 1e-6                                                      */
+  double   gradient_tolerance;                 /* 1e-10                                                     */
+  double   parameter_tolerance;                /* 1e-8                                                      */
+  double   initial_trust_region_radius;        /* 1e4                                                       */
+  double   max_trust_region_radius;            /* 1e16                                                      */
+  double   min_trust_region_radius;            /* 1e-32                                                     */
+  double   min_relative_decrease;              /* 1e-3                                                      */
+  double   min_lm_diagonal;                    /* 1e-6                                                      */
+  double   max_lm_diagonal;                    /* 1e32                                                      */
+} tmi_ba_nonlinear_rotation_options;
+void tmi_ba_nonlinear_rotation_options_init(tmi_ba_nonlinear_rotation_options* options);
+
+typedef struct tmi_ba_nonlinear_rotation_summary {
+  int32_t num_views;                /* views in the problem: marked, with an edge that is used                 */
+  int32_t num_pairs;                /* edges used: both views marked                                           */
+  int32_t num_iterations;           /* LM iterations run (one ended by the gradient test is not counted)       */
+  int32_t num_successful_steps;
+  int32_t num_unsuccessful_steps;   /* rejected and invalid steps                                              */
+  int32_t num_factorizations;       /* dense Cholesky factorisations of order 3 (free views)                   */
+  int32_t termination;              /* 0 CONVERGENCE, 1 NO_CONVERGENCE, 2 FAILURE                              */
+  int32_t usable;                   /* Summary::IsSolutionUsable(): termination != FAILURE                     */
+  double  initial_cost;
+  double  final_cost;
+  double  seconds;
+  double  kernel_seconds;           /* device time; the sum of the three below                                 */
+  double  factor_seconds;           /* the damped copy of the normal matrix and its factorisation              */
+  double  substitution_seconds;     /* forward / backward substitution                                         */
+  double  graph_seconds;            /* per-edge and per-view kernels, assembly, the reductions                 */
+} tmi_ba_nonlinear_rotation_summary;
+
+/* EstimateRotations on the device.  The batch is tmi_ba_view_pair_batch: num_views, pair_view1 / pair_view2 and
+ * pair_rotation2 are read; the batch's view_rotation and pair_position2 are not.  view_rotation [3 * num_views],
+ * angle-axis, is in/out and always the start: the reference refuses to run without an initialisation (:53-57).
+ * view_given [num_views] (NULL: every view) marks the views that have one, the keys of the reference's map.
+ *   1. :69-88    The problem.  An edge with an unmarked view is skipped (:76-80); the edges used keep the caller's order
+ *                (DEVIATION: the reference walks its hash map).  The views of the problem are the marked views with an
+ *                edge that is used, in ascending index; every other view is never written.  options->fixed_view = -1 is
+ *                the reference's problem: every such view is free and nothing holds the gauge, the three-dimensional
+ *                null space of the normal matrix is lifted by the LM diagonal alone.  fixed_view >= 0 (EXTENSION) holds
+ *                that view constant and removes its rows and columns; a held view that is not in the problem holds
+ *                nothing.  n = the number of free views, column c is the c-th of them.
+ *   2. pairwise_rotation_error.h:65-95 (weight 1)  With R1, R2, Rrel = AngleAxisToRotationMatrix of x[view1], x[view2]
+ *                and rotation_2, r = RotationMatrixToAngleAxis(R2 R1^T Rrel^T).  The 3 x 6 Jacobian is what forward-mode
+ *                dual numbers give through Ceres' rotation.h, every branch taken on the values as the Jets take it:
+ *                theta^2 > DBL_EPSILON or the first-order matrix I + [x] in AngleAxisToRotationMatrix (an exactly zero
+ *                rotation, which the spanning tree's root carries, has the non-zero derivatives of [x]); trace >= 0 or
+ *                the largest diagonal entry (first of equals) in RotationMatrixToQuaternion; sin^2 > 0 or k = 2, and
+ *                atan2(-sin, -cos) for a negative scalar part, in QuaternionToAngleAxis.  Jet division is by the inverse
+ *                of the divisor's value, sqrt' = 1 / (2 sqrt), atan2(g, f)' = (f g' - g f') / (f^2 + g^2).
+ *   3. :66-67    SoftLOneLoss(a = robust_loss_width) on s = (r0 r0 + r1 r1) + r2 r2 (ceres/loss_function.cc), b = a^2:
+ *                rho = 2 b (sqrt(1 + s / b) - 1), rho' = max(DBL_MIN, 1 / sqrt(1 + s / b)),
+ *                rho'' = -1 / (2 b (1 + s / b)^(3/2)).  Ceres' Corrector takes the shortcut r~ = sqrt(rho') r,
+ *                J~ = sqrt(rho') J where s = 0 or rho'' <= 0 (step 4 of tmi_ba_estimate_global_positions_nonlinear gives
+ *                the other case); SoftLOneLoss has rho'' < 0 everywhere, so the shortcut is all the kernels carry.
+ *                cost = sum of rho(s) / 2 over the edges used.
+ *   4.           The normal equations of order 3 n: with J1~, J2~ the halves of J~ for view1 and view2 -- independent, not
+ *                +-J as in the position call -- the diagonal block of view1 gets J1~^T J1~, that of view2 J2~^T J2~, block
+ *                (view1, view2) J1~^T J2~ and the gradient J1~^T r~ at view1, J2~^T r~ at view2; a held view's rows and
+ *                columns are absent.  Jacobi scaling as in step 5 of the position call.
+ *   5.           Steps 6 and 7 of tmi_ba_estimate_global_positions_nonlinear word for word: the kept normal matrix and a
+ *                damped copy factored per trial radius, the invalid / rejected / accepted step rules, the three
+ *                tolerances, the fixed orders (edges in the caller's order, per-view sums in ascending edge index, every
+ *                scalar by the reduction of fixed shape), no FMA contraction, no atomics, the same bits from call to call.
+ *                The code is shared.
+ * The loop runs on the host; every kernel is a plain grid launch.  TMI_BA_OK whenever the solve ran; summary->termination
+ * says how it ended; view_rotation receives the last accepted point in every case (a held view's and every view's outside
+ * the problem bit for bit as given).  Marked views but no edge between two of them: TMI_BA_OK, an empty problem, nothing
+ * written (the reference solves an empty problem and returns true).
+ * THE GAUGE.  With fixed_view = -1 the result is defined up to one rotation applied to every view of a connected
+ * component, and rounding in the gradient's gauge component is amplified by up to radius / A_ii: two correct
+ * implementations agree in the loop rotations R2 R1^T, the residuals, the costs and the radii, not in view_rotation itself.
+ * DEVIATIONS beyond step 1: the linear solve is always the dense factorisation (the reference: SPARSE_NORMAL_CHOLESKY, the
+ * same step up to rounding); 3 n is capped as in the position call (11000, the knob TMI_BA_ROTATION_MAX_ORDER):
+ * TMI_BA_ERR_UNSUPPORTED above it, before anything of that size is allocated.
+ * TMI_BA_ERR_INVALID_ARGUMENT, before the device is looked for: the reference's two refusals (its `false`) -- num_pairs == 0
+ * or no marked view -- and a null batch, options, view_rotation or summary, a missing array, a view index out of range,
+ * view1 == view2, a repeated unordered pair, a non-finite rotation_2 or marked view_rotation, fixed_view outside
+ * [-1, num_views) or unmarked, robust_loss_width that is not positive and finite, max_num_iterations < 0, a radius,
+ * tolerance or LM diagonal bound that is negative or NaN, an initial radius of 0.
+ * On every failure view_rotation and the optional outputs are left as they were.  Optional outputs (each may be NULL):
+ * iteration_cost, iteration_radius and iteration_step_accepted [max_num_iterations + 1] as in the position call;
+ * pair_residual [3 * num_pairs] the r of step 2 at the result, 0 for a skipped edge. */
+int32_t tmi_ba_estimate_global_rotations_nonlinear(const tmi_ba_view_pair_batch* batch,
+                                                   const tmi_ba_nonlinear_rotation_options* options,
+                                                   const uint8_t* view_given, int32_t device, double* view_rotation,
+                                                   double* iteration_cost, double* iteration_radius,
+                                                   int32_t* iteration_step_accepted, double* pair_residual,
+                                                   tmi_ba_nonlinear_rotation_summary* summary);
+
 /* ---- batched LocalizeViewToReconstruction: P3P RANSAC for many candidate views ------------------
  * reference: LocalizeViewToReconstruction (localize_view_to_reconstruction.cc:213-257), the inner loop of the
  * incremental and hybrid pipelines (incremental_reconstruction_estimator.cc:219-233), on its CALIBRATED path:

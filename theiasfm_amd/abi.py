@@ -565,6 +565,56 @@ class CNonlinearPositionSummary(C.Structure):
     ]
 
 
+class CNonlinearRotationOptions(C.Structure):
+    """tmi_ba_nonlinear_rotation_options (NonlinearRotationEstimator's loss width and iteration limit, fixed_view, and the
+    trust-region fields of ceres::Solver::Options)."""
+    _fields_ = [
+        ("max_num_iterations", C.c_int32),
+        ("robust_loss_width", C.c_double),
+        ("fixed_view", C.c_int32),
+        ("jacobi_scaling", C.c_int32),
+        ("max_num_consecutive_invalid_steps", C.c_int32),
+        ("function_tolerance", C.c_double),
+        ("gradient_tolerance", C.c_double),
+        ("parameter_tolerance", C.c_double),
+        ("initial_trust_region_radius", C.c_double),
+        ("max_trust_region_radius", C.c_double),
+        ("min_trust_region_radius", C.c_double),
+        ("min_relative_decrease", C.c_double),
+        ("min_lm_diagonal", C.c_double),
+        ("max_lm_diagonal", C.c_double),
+    ]
+
+
+def nonlinear_rotation_options(**overrides) -> CNonlinearRotationOptions:
+    """The reference's and Ceres' defaults; mirrors tmi_ba_nonlinear_rotation_options_init."""
+    o = CNonlinearRotationOptions()
+    o.max_num_iterations = 200
+    o.robust_loss_width = 0.1
+    o.fixed_view = -1
+    o.jacobi_scaling = 1
+    o.max_num_consecutive_invalid_steps = 5
+    o.function_tolerance = 1e-6
+    o.gradient_tolerance = 1e-10
+    o.parameter_tolerance = 1e-8
+    o.initial_trust_region_radius = 1e4
+    o.max_trust_region_radius = 1e16
+    o.min_trust_region_radius = 1e-32
+    o.min_relative_decrease = 1e-3
+    o.min_lm_diagonal = 1e-6
+    o.max_lm_diagonal = 1e32
+    for k, v in overrides.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
+class CNonlinearRotationSummary(C.Structure):
+    """tmi_ba_nonlinear_rotation_summary."""
+    _fields_ = list(CNonlinearPositionSummary._fields_)
+
+
 class CLocalizationOptions(C.Structure):
     """tmi_ba_localization_options (RansacParameters, sample_consensus_estimator.h:57-65, and
     LocalizeViewToReconstructionOptions, localize_view_to_reconstruction.h:48-72)."""

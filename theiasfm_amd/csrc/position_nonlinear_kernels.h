@@ -31,6 +31,10 @@
 //                         and |candidate|^2.
 // nlp_absmax_kernel       one workgroup: max |unscaled gradient| (a maximum does not depend on the order).
 // Sums: rot::block_sum and reduce_partials_kernel (rotation_kernels.h), a reduction of fixed shape.
+// nlp_scale_kernel and nlp_assemble_kernel are templates on a policy that says where an edge's record holds the entries
+// of the blocks and of the gradient (nlp::PositionBlocks here: the walks, the orders and the arithmetic above); the
+// nonlinear rotation estimator instantiates them, and uses the other kernels as they are, with nlr::RotationBlocks
+// (rotation_nonlinear_kernels.h).  G.fixed_view = G.num_views means that no view is fixed (that estimator's case).
 //
 // Every kernel is a plain grid launch; nothing waits on another workgroup and no atomic is used.  The loop stays on the
 // host (side_calls.h).  The arithmetic written here is never contracted into FMA (#pragma clang fp contract(off) in every
@@ -85,6 +89,28 @@ __device__ __forceinline__ void load_position(const double* __restrict__ x, int 
 #pragma unroll
   for (int k = 0; k < 3; ++k) p[k] = c >= 0 ? x[3 * c + k] : 0.0;
 }
+
+// What nlp_scale_kernel and nlp_assemble_kernel read from an edge's record, for this estimator: the Jacobian with respect
+// to p[view1] is -J~, so one symmetric B_e serves the diagonal blocks of both views and, negated, the block between them.
+// `row_is_view2`: the view whose rows are assembled is the edge's view2.  (nlr::RotationBlocks, rotation_nonlinear_kernels.h,
+// is the other policy: two independent Jacobian halves.)
+struct PositionBlocks {
+  // entry (i, j) of the edge's part of the row view's diagonal block
+  static __device__ __forceinline__ double diag(const double* __restrict__ rec, size_t E, size_t e, bool, int i, int j) {
+    return rec[(size_t)sym_plane(i, j) * E + e];
+  }
+  // entry (i, j) of the edge's part of block (row view, neighbour), before finish_off
+  static __device__ __forceinline__ double off(const double* __restrict__ rec, size_t E, size_t e, bool, int i, int j) {
+    return rec[(size_t)sym_plane(i, j) * E + e];
+  }
+  static __device__ __forceinline__ double finish_off(double x) { return -x; }
+  // entry k of the edge's part of the row view's gradient
+  static __device__ __forceinline__ double grad(const double* __restrict__ rec, size_t E, size_t e, bool row_is_view2,
+                                                int k) {
+    const double q = rec[(size_t)(6 + k) * E + e];
+    return row_is_view2 ? q : -q;
+  }
+};
 
 }  // namespace nlp
 
@@ -141,6 +167,7 @@ __global__ __launch_bounds__(256) void nlp_edge_kernel(PositionGraph G, double w
   }
 }
 
+template <class Blocks>
 __global__ __launch_bounds__(256) void nlp_scale_kernel(PositionGraph G, int n, const double* __restrict__ rec,
                                                         double* __restrict__ scale) {
 #pragma clang fp contract(off)
@@ -150,10 +177,11 @@ __global__ __launch_bounds__(256) void nlp_scale_kernel(PositionGraph G, int n, 
   const int v = rot::view_of(c, G.fixed_view);
   double d0 = 0.0, d1 = 0.0, d2 = 0.0;
   for (int r = G.row_ptr[v]; r < G.row_ptr[v + 1]; ++r) {
-    const size_t e = (size_t)(G.row[r].y >> 1);
-    d0 += rec[0 * E + e];
-    d1 += rec[3 * E + e];
-    d2 += rec[5 * E + e];
+    const int code = G.row[r].y;
+    const size_t e = (size_t)(code >> 1);
+    d0 += Blocks::diag(rec, E, e, code & 1, 0, 0);
+    d1 += Blocks::diag(rec, E, e, code & 1, 1, 1);
+    d2 += Blocks::diag(rec, E, e, code & 1, 2, 2);
   }
   scale[3 * c] = 1.0 / (1.0 + sqrt(d0));
   scale[3 * c + 1] = 1.0 / (1.0 + sqrt(d1));
@@ -162,6 +190,7 @@ __global__ __launch_bounds__(256) void nlp_scale_kernel(PositionGraph G, int n, 
 
 // blockIdx.x = the free view's column c; M is N x N row major, N = 3 n.  diag [N]: the scaled diagonal of M; g [N]: the
 // scaled gradient; gabs [N]: |the unscaled gradient|.
+template <class Blocks>
 __global__ __launch_bounds__(256) void nlp_assemble_kernel(PositionGraph G, int N, const double* __restrict__ rec,
                                                            const double* __restrict__ scale, double* __restrict__ M,
                                                            double* __restrict__ diag, double* __restrict__ g,
@@ -181,21 +210,22 @@ __global__ __launch_bounds__(256) void nlp_assemble_kernel(PositionGraph G, int 
     const int2 ent = G.lap_row[r];
     if (ent.x >= c) continue;                              // the other triangle
     if (r > r0 && G.lap_row[r - 1].x == ent.x) continue;  // not the first of its neighbour's run
-    double sum[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    const int row_view = rot::view_of(c, G.fixed_view);
+    double sum[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     for (int q = r; q < r1; ++q) {
       const int2 nxt = G.lap_row[q];
       if (nxt.x != ent.x) break;
+      const bool row_is_view2 = G.pair_view2[nxt.y] == row_view;
 #pragma unroll
-      for (int k = 0; k < 6; ++k) sum[k] += rec[k * E + (size_t)nxt.y];
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) sum[3 * i + j] += Blocks::off(rec, E, (size_t)nxt.y, row_is_view2, i, j);
     }
 #pragma unroll
     for (int i = 0; i < 3; ++i)
 #pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        const int a = i < j ? i : j, b = i < j ? j : i;
-        const int k = a == 0 ? b : (a == 1 ? 2 + b : 5);  // (constants after unrolling)
-        rows[(size_t)i * N + 3 * ent.x + j] = -((sum[k] * scale[3 * c + i]) * scale[3 * ent.x + j]);
-      }
+      for (int j = 0; j < 3; ++j)
+        rows[(size_t)i * N + 3 * ent.x + j] = Blocks::finish_off((sum[3 * i + j] * scale[3 * c + i]) * scale[3 * ent.x + j]);
   }
   if (threadIdx.x < 9) {
     const int v = rot::view_of(c, G.fixed_view);
@@ -204,9 +234,11 @@ __global__ __launch_bounds__(256) void nlp_assemble_kernel(PositionGraph G, int 
       // the lower triangle of the diagonal block: (0,0) (1,0) (1,1) (2,0) (2,1) (2,2)
       const int i = threadIdx.x < 1 ? 0 : (threadIdx.x < 3 ? 1 : 2);
       const int j = threadIdx.x - (i * (i + 1)) / 2;
-      const size_t plane = (size_t)nlp::sym_plane(i, j);
       double sum = 0.0;
-      for (int r = row_begin; r < row_end; ++r) sum += rec[plane * E + (size_t)(G.row[r].y >> 1)];
+      for (int r = row_begin; r < row_end; ++r) {
+        const int code = G.row[r].y;
+        sum += Blocks::diag(rec, E, (size_t)(code >> 1), code & 1, i, j);
+      }
       const double a = (sum * scale[3 * c + i]) * scale[3 * c + j];
       rows[(size_t)i * N + 3 * c + j] = a;
       if (i == j) diag[3 * c + i] = a;
@@ -215,8 +247,7 @@ __global__ __launch_bounds__(256) void nlp_assemble_kernel(PositionGraph G, int 
       double sum = 0.0;
       for (int r = row_begin; r < row_end; ++r) {
         const int code = G.row[r].y;
-        const double q = rec[(size_t)(6 + k) * E + (size_t)(code >> 1)];
-        sum += (code & 1) ? q : -q;
+        sum += Blocks::grad(rec, E, (size_t)(code >> 1), code & 1, k);
       }
       g[3 * c + k] = sum * scale[3 * c + k];
       gabs[3 * c + k] = fabs(sum);

@@ -1658,8 +1658,9 @@ struct EdgeRows {
   std::vector<int2> lap_row;  // [<= 2 E]
 };
 
+// fixed_view = V: no view is fixed and every view has a column (the nonlinear rotation estimator's gauge-free problem).
 EdgeRows build_edge_rows(int V, int E, const int32_t* view1, const int32_t* view2, int fixed_view) {
-  const int n = V - 1;
+  const int n = fixed_view < V ? V - 1 : V;
   EdgeRows rows;
   std::vector<int>& row_ptr = rows.row_ptr;
   std::vector<int>& lap_ptr = rows.lap_ptr;
@@ -2202,6 +2203,237 @@ int32_t tmi_ba_estimate_global_positions_lud(const tmi_ba_view_pair_batch* Bh, c
 
 // ---- NonlinearPositionEstimator (position_nonlinear_kernels.h) ----------------------------------
 namespace {
+// The device memory of the Levenberg-Marquardt loop on dense normal equations of order N over E edges that the nonlinear
+// position and rotation estimators share (normal_lm_solve), and the traces it leaves.
+struct NormalLm {
+  int N = 0, nbE = 0, nbN = 0;
+  double *x, *cand, *step, *y, *rhs, *tmp, *scale, *diag, *g, *gabs, *M, *A, *cdiag, *part, *norms;
+  int* flag;
+  double *p_cost, *p_mcc, *p_step, *p_x;  // the blocks' parts: cost and model cost change [nbE], |step|^2, |x|^2 [nbN]
+  std::vector<double> cost_trace, radius_trace;
+  std::vector<int32_t> outcome_trace;
+  int alloc(OneShot* s, int N_, int E) {
+    N = N_;
+    nbE = (E + 255) / 256;
+    nbN = (N + 255) / 256;
+    TMI_HIP(s->alloc(&x, (size_t)N));
+    const std::vector<double> ones((size_t)N, 1.0);  // the scales without jacobi_scaling
+    TMI_HIP(s->upload(&scale, ones.data(), ones.size()));
+    TMI_HIP(hipStreamSynchronize(s->stream));  // (ones goes out of scope)
+    TMI_HIP(s->alloc(&cand, (size_t)N));
+    TMI_HIP(s->alloc(&step, (size_t)N));
+    TMI_HIP(s->alloc(&y, (size_t)N));
+    TMI_HIP(s->alloc(&rhs, (size_t)N));
+    TMI_HIP(s->alloc(&tmp, (size_t)N));
+    TMI_HIP(s->alloc(&diag, (size_t)N));
+    TMI_HIP(s->alloc(&g, (size_t)N));
+    TMI_HIP(s->alloc(&gabs, (size_t)N));
+    TMI_HIP(s->alloc(&M, (size_t)N * N));  // the assembled normal matrix, kept across rejected steps
+    TMI_HIP(s->alloc(&A, (size_t)N * N));  // its damped copy, overwritten by the factor
+    TMI_HIP(s->alloc(&cdiag, (size_t)kPanel * ((size_t)(N + kPanel - 1) / kPanel) * kPanel));
+    TMI_HIP(s->alloc(&part, (size_t)2 * nbE + (size_t)2 * nbN));
+    TMI_HIP(s->alloc(&norms, 8));
+    TMI_HIP(s->alloc(&flag, 1));
+    p_cost = part;
+    p_mcc = p_cost + nbE;
+    p_step = p_mcc + nbE;
+    p_x = p_step + nbN;
+    return TMI_BA_OK;
+  }
+};
+
+// Ceres 1.14's TrustRegionMinimizer with the Levenberg-Marquardt strategy on the dense normal equations, the rules of
+// tmi_ba_solver_solve (steps 6 and 7 of tmi_ba_estimate_global_positions_nonlinear).  x_h [N] is the start and receives
+// the last accepted point.  linearize(first_scaled) queues, at L.x: the records, the residuals and the cost parts
+// (L.p_cost), the Jacobi scales into L.scale where first_scaled, then L.M, L.diag, L.g and L.gabs.  candidate() queues, at
+// L.cand with L.step: the cost parts and the parts of the model cost change (L.p_mcc).  Opt has the trust-region fields of
+// tmi_ba_nonlinear_position_options; Sum the counters and times of tmi_ba_nonlinear_position_summary.
+template <class Opt, class Sum, class Linearize, class Candidate>
+int normal_lm_solve(OneShot* s, const Opt* opt, Sum* sum, NormalLm& L, std::vector<double>& x_h, Linearize linearize_at,
+                    Candidate candidate_at) {
+  const int N = L.N, nbE = L.nbE, nbN = L.nbN, max_it = opt->max_num_iterations;
+  double*& d_x = L.x;
+  double*& d_cand = L.cand;
+  double *d_step = L.step, *d_y = L.y, *d_rhs = L.rhs, *d_tmp = L.tmp, *d_scale = L.scale, *d_diag = L.diag, *d_g = L.g,
+         *d_gabs = L.gabs, *d_M = L.M, *d_A = L.A, *d_cdiag = L.cdiag, *d_norms = L.norms;
+  int* d_flag = L.flag;
+  double *p_cost = L.p_cost, *p_mcc = L.p_mcc, *p_step = L.p_step, *p_x = L.p_x;
+  std::vector<double>&cost_trace = L.cost_trace, &radius_trace = L.radius_trace;
+  std::vector<int32_t>& outcome_trace = L.outcome_trace;
+  hipStream_t st = s->stream;
+  const dim3 entry_grid(nbN), block(256);
+  TMI_HIP(hipMemcpyAsync(d_x, x_h.data(), (size_t)N * sizeof(double), hipMemcpyHostToDevice, st));
+  PinnedWords pinned;  // [0..5) cost, model cost change, |step|^2, |candidate|^2, max |gradient|; then the pivot flag
+  TMI_HIP(pinned.alloc(8 * sizeof(double)));
+  double* h_norms = static_cast<double*>(pinned.p);
+  int* h_flag = reinterpret_cast<int*>(h_norms + 6);
+  TMI_HIP(hipMemsetAsync(d_flag, 0, sizeof(int), st));
+  TMI_HIP(hipMemsetAsync(d_y, 0, (size_t)N * sizeof(double), st));
+  ReduceJobs jobs;
+  memset(&jobs, 0, sizeof(jobs));
+  const double* parts[4] = {p_cost, p_mcc, p_step, p_x};
+  for (int q = 0; q < 4; ++q) {
+    jobs.part[q] = parts[q];
+    jobs.count[q] = q < 2 ? nbE : nbN;
+  }
+  // device time in three classes.  An iteration's marks: 0-1 the damped copy and the factorisation, 1-2 the
+  // substitution, 2-3 the step, the candidate and the reductions; a linearisation with its assembly has a timer of
+  // its own, read after the next synchronisation.
+  StreamTimer timer(st, 4), lin_timer(st, 2);
+  TMI_HIP(timer.status);
+  TMI_HIP(lin_timer.status);
+  double factor_seconds = 0.0, subst_seconds = 0.0, graph_seconds = 0.0;
+  bool lin_pending = false;
+  // the sums of the first `count` quantities and max |gradient| into h_norms, and the pivot flag
+  auto fetch = [&](int count) -> int {
+    hipLaunchKernelGGL(reduce_partials_kernel, dim3(count), block, 0, st, jobs, d_norms);
+    hipLaunchKernelGGL(nlp_absmax_kernel, dim3(1), block, 0, st, N, d_gabs, d_norms + 4);
+    if (timer.marked > 0) TMI_HIP(timer.mark());
+    const hipError_t le = hipGetLastError();
+    hipError_t ce = hipMemcpyAsync(h_norms, d_norms, 5 * sizeof(double), hipMemcpyDeviceToHost, st);
+    if (ce == hipSuccess) ce = hipMemcpyAsync(h_flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, st);
+    const hipError_t se = hipStreamSynchronize(st);
+    TMI_HIP(le);
+    TMI_HIP(ce);
+    TMI_HIP(se);
+    if (lin_pending) graph_seconds += lin_timer.seconds();
+    lin_pending = false;
+    return TMI_BA_OK;
+  };
+  // records, residuals and the cost parts at d_x, then M, its diagonal and the gradient
+  bool scaled = !opt->jacobi_scaling;
+  auto linearize = [&]() -> int {
+    lin_timer.marked = 0;
+    TMI_HIP(lin_timer.mark());
+    linearize_at(!scaled);
+    scaled = true;
+    TMI_HIP(lin_timer.mark());
+    lin_pending = true;
+    return TMI_BA_OK;
+  };
+  int rc;
+
+  // ---- the first linearisation, its cost and |x| (the step kernel on y = 0) ----
+  if ((rc = linearize())) return rc;
+  hipLaunchKernelGGL(nlp_step_kernel, entry_grid, block, 0, st, N, d_x, d_scale, d_y, d_step, d_cand, p_step, p_x);
+  TMI_HIP(hipMemsetAsync(p_mcc, 0, (size_t)nbE * sizeof(double), st));
+  if ((rc = fetch(4))) return rc;
+  double cost = h_norms[0], x_norm = std::sqrt(h_norms[3]);
+  sum->initial_cost = cost;
+
+  double radius = opt->initial_trust_region_radius, decrease_factor = 2.0;
+  int invalid_run = 0, iter = 0, termination = 1;
+  bool need_gradient_check = true;
+  cost_trace.push_back(cost);
+  radius_trace.push_back(radius);
+  outcome_trace.push_back(1);
+  auto record = [&](int outcome) {
+    cost_trace.push_back(cost);
+    radius_trace.push_back(radius);
+    outcome_trace.push_back(outcome);
+  };
+  for (;;) {
+    if (iter >= max_it) break;
+    ++iter;
+    timer.marked = 0;
+    TMI_HIP(timer.mark());
+    hipLaunchKernelGGL(nlp_copy_lower_kernel, dim3(N), block, 0, st, N, d_M, d_A);
+    hipLaunchKernelGGL(nlp_lm_diagonal_kernel, entry_grid, block, 0, st, N, d_diag, opt->min_lm_diagonal,
+                       opt->max_lm_diagonal, radius, d_A);
+    dense_cholesky_factor(d_A, N, d_cdiag, d_flag, st);
+    sum->num_factorizations++;
+    TMI_HIP(timer.mark());
+    TMI_HIP(hipMemcpyAsync(d_rhs, d_g, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, st));
+    dense_cholesky_substitute<1>(d_A, N, d_rhs, d_y, d_tmp, st);
+    TMI_HIP(timer.mark());
+    hipLaunchKernelGGL(nlp_step_kernel, entry_grid, block, 0, st, N, d_x, d_scale, d_y, d_step, d_cand, p_step, p_x);
+    candidate_at();
+    if ((rc = fetch(4))) return rc;
+    factor_seconds += timer.seconds(0, 1);
+    subst_seconds += timer.seconds(1, 2);
+    graph_seconds += timer.seconds(2, 3);
+    bool usable = true;
+    if (*h_flag) {  // a non-positive pivot: the linear solve failed, an invalid step as in Ceres
+      usable = false;
+      TMI_HIP(hipMemsetAsync(d_flag, 0, sizeof(int), st));
+    }
+    if (need_gradient_check) {
+      need_gradient_check = false;
+      if (!(h_norms[4] > opt->gradient_tolerance)) {
+        termination = 0;
+        --iter;
+        break;
+      }
+    }
+    const double cand_cost = h_norms[0], model_cost_change = h_norms[1], step_sq = h_norms[2], cand_x_sq = h_norms[3];
+    if (!(model_cost_change > 0.0)) usable = false;
+    if (!usable) {
+      // HandleInvalidStep
+      sum->num_unsuccessful_steps++;
+      if (++invalid_run >= opt->max_num_consecutive_invalid_steps) {
+        record(-1);
+        termination = 2;
+        break;
+      }
+      radius /= decrease_factor;
+      decrease_factor *= 2.0;
+      record(-1);
+      if (radius < opt->min_trust_region_radius) {
+        termination = 0;
+        break;
+      }
+      continue;
+    }
+    invalid_run = 0;
+    if (std::sqrt(step_sq) <= opt->parameter_tolerance * (x_norm + opt->parameter_tolerance)) {
+      record(2);
+      termination = 0;
+      break;
+    }
+    const double cost_change = cost - cand_cost;
+    if (std::fabs(cost_change) <= opt->function_tolerance * cost) {
+      record(3);
+      termination = 0;
+      break;
+    }
+    const double relative_decrease = cost_change / model_cost_change;
+    if (relative_decrease > opt->min_relative_decrease) {  // IsStepSuccessful
+      std::swap(d_x, d_cand);
+      cost = cand_cost;
+      x_norm = std::sqrt(cand_x_sq);
+      sum->num_successful_steps++;
+      radius = radius / std::fmax(1.0 / 3.0, 1.0 - std::pow(2.0 * relative_decrease - 1.0, 3));
+      radius = std::fmin(opt->max_trust_region_radius, radius);
+      decrease_factor = 2.0;
+      if ((rc = linearize())) return rc;
+      need_gradient_check = true;
+      record(1);
+    } else {
+      sum->num_unsuccessful_steps++;
+      radius /= decrease_factor;
+      decrease_factor *= 2.0;
+      record(0);
+    }
+    if (radius < opt->min_trust_region_radius) {
+      termination = 0;
+      break;
+    }
+  }
+
+  TMI_HIP(hipMemcpyAsync(x_h.data(), d_x, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
+  TMI_HIP(hipStreamSynchronize(st));
+  if (lin_pending) graph_seconds += lin_timer.seconds();
+  sum->num_iterations = iter;
+  sum->termination = termination;
+  sum->usable = termination != 2;
+  sum->final_cost = cost;
+  sum->factor_seconds = factor_seconds;
+  sum->substitution_seconds = subst_seconds;
+  sum->graph_seconds = graph_seconds;
+  sum->kernel_seconds = factor_seconds + subst_seconds + graph_seconds;
+  return TMI_BA_OK;
+}
+
 // What the nonlinear position estimator asks of its arguments beyond check_view_pair_batch, the connection to fixed_view
 // apart; null: fine.  Nothing is allocated here.
 const char* check_nonlinear_position_arguments(const tmi_ba_view_pair_batch* B,
@@ -2289,20 +2521,16 @@ int32_t tmi_ba_estimate_global_positions_nonlinear(const tmi_ba_view_pair_batch*
   std::vector<double> x_h((size_t)N);
   for (int v = 0; v < V; ++v)
     if (v != fixed_view) std::copy(start.begin() + 3 * v, start.begin() + 3 * v + 3, x_h.begin() + 3 * (v - (v > fixed_view)));
-  const int max_it = opt->max_num_iterations;
   const double width = opt->robust_loss_width;
-  std::vector<double> cost_trace, radius_trace;
-  std::vector<int32_t> outcome_trace;
   return one_shot_batch(device, "nonlinear positions: no such device", E, t0, sum, [&](OneShot* s) -> int {
     PositionGraph G;
     memset(&G, 0, sizeof(G));
     G.num_views = V;
     G.num_pairs = E;
     G.fixed_view = fixed_view;
-    int *d_v1, *d_v2, *d_ptr, *d_lptr, *d_flag;
+    int *d_v1, *d_v2, *d_ptr, *d_lptr;
     int2 *d_row, *d_lrow;
-    double *d_pos, *d_t, *d_rot = nullptr, *d_x, *d_cand, *d_step, *d_y, *d_rhs, *d_tmp, *d_scale, *d_diag, *d_g, *d_gabs,
-        *d_rec, *d_res, *d_M, *d_A, *d_cdiag, *d_part, *d_norms;
+    double *d_pos, *d_t, *d_rot = nullptr, *d_rec, *d_res;
     TMI_HIP(s->upload(&d_v1, (const int*)Bh->pair_view1, (size_t)E));
     TMI_HIP(s->upload(&d_v2, (const int*)Bh->pair_view2, (size_t)E));
     TMI_HIP(s->upload(&d_ptr, rows.row_ptr.data(), rows.row_ptr.size()));
@@ -2315,32 +2543,8 @@ int32_t tmi_ba_estimate_global_positions_nonlinear(const tmi_ba_view_pair_batch*
       TMI_HIP(s->upload(&d_rot, Bh->view_rotation, (size_t)3 * V));
       TMI_HIP(s->alloc(&d_t, (size_t)3 * E));
     }
-    TMI_HIP(s->upload(&d_x, x_h.data(), x_h.size()));
-    const std::vector<double> ones((size_t)N, 1.0);  // the scales without jacobi_scaling
-    TMI_HIP(s->upload(&d_scale, ones.data(), ones.size()));
-    TMI_HIP(s->alloc(&d_cand, (size_t)N));
-    TMI_HIP(s->alloc(&d_step, (size_t)N));
-    TMI_HIP(s->alloc(&d_y, (size_t)N));
-    TMI_HIP(s->alloc(&d_rhs, (size_t)N));
-    TMI_HIP(s->alloc(&d_tmp, (size_t)N));
-    TMI_HIP(s->alloc(&d_diag, (size_t)N));
-    TMI_HIP(s->alloc(&d_g, (size_t)N));
-    TMI_HIP(s->alloc(&d_gabs, (size_t)N));
     TMI_HIP(s->alloc(&d_rec, (size_t)9 * E));
     TMI_HIP(s->alloc(&d_res, (size_t)3 * E));
-    TMI_HIP(s->alloc(&d_M, (size_t)N * N));  // the assembled normal matrix, kept across rejected steps
-    TMI_HIP(s->alloc(&d_A, (size_t)N * N));  // its damped copy, overwritten by the factor
-    TMI_HIP(s->alloc(&d_cdiag, (size_t)kPanel * ((size_t)(N + kPanel - 1) / kPanel) * kPanel));
-    const int nbE = (E + 255) / 256, nbN = (N + 255) / 256, nbV = (n + 255) / 256;
-    // the blocks' parts: the cost and the model cost change [nbE each], |step|^2 and |candidate|^2 [nbN each]
-    TMI_HIP(s->alloc(&d_part, (size_t)2 * nbE + (size_t)2 * nbN));
-    TMI_HIP(s->alloc(&d_norms, 8));
-    TMI_HIP(s->alloc(&d_flag, 1));
-    double *p_cost = d_part, *p_mcc = p_cost + nbE, *p_step = p_mcc + nbE, *p_x = p_step + nbN;
-    PinnedWords pinned;  // [0..5) cost, model cost change, |step|^2, |candidate|^2, max |gradient|; then the pivot flag
-    TMI_HIP(pinned.alloc(8 * sizeof(double)));
-    double* h_norms = static_cast<double*>(pinned.p);
-    int* h_flag = reinterpret_cast<int*>(h_norms + 6);
     G.pair_view1 = d_v1;
     G.pair_view2 = d_v2;
     G.t = d_t;
@@ -2348,173 +2552,36 @@ int32_t tmi_ba_estimate_global_positions_nonlinear(const tmi_ba_view_pair_batch*
     G.row = d_row;
     G.lap_ptr = d_lptr;
     G.lap_row = d_lrow;
-    hipStream_t st = s->stream;
-    const dim3 edge_grid(nbE), entry_grid(nbN), view_grid(nbV), block(256);
-    TMI_HIP(hipMemsetAsync(d_flag, 0, sizeof(int), st));
-    TMI_HIP(hipMemsetAsync(d_y, 0, (size_t)N * sizeof(double), st));
-    ReduceJobs jobs;
-    memset(&jobs, 0, sizeof(jobs));
-    const double* parts[4] = {p_cost, p_mcc, p_step, p_x};
-    for (int q = 0; q < 4; ++q) {
-      jobs.part[q] = parts[q];
-      jobs.count[q] = q < 2 ? nbE : nbN;
-    }
-    // device time in three classes.  An iteration's marks: 0-1 the damped copy and the factorisation, 1-2 the
-    // substitution, 2-3 the step, the candidate and the reductions; a linearisation with its assembly has a timer of
-    // its own, read after the next synchronisation.
-    StreamTimer timer(st, 4), lin_timer(st, 2);
-    TMI_HIP(timer.status);
-    TMI_HIP(lin_timer.status);
-    double factor_seconds = 0.0, subst_seconds = 0.0, graph_seconds = 0.0;
-    bool lin_pending = false;
-    // the sums of the first `count` quantities and max |gradient| into h_norms, and the pivot flag
-    auto fetch = [&](int count) -> int {
-      hipLaunchKernelGGL(reduce_partials_kernel, dim3(count), block, 0, st, jobs, d_norms);
-      hipLaunchKernelGGL(nlp_absmax_kernel, dim3(1), block, 0, st, N, d_gabs, d_norms + 4);
-      if (timer.marked > 0) TMI_HIP(timer.mark());
-      const hipError_t le = hipGetLastError();
-      hipError_t ce = hipMemcpyAsync(h_norms, d_norms, 5 * sizeof(double), hipMemcpyDeviceToHost, st);
-      if (ce == hipSuccess) ce = hipMemcpyAsync(h_flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, st);
-      const hipError_t se = hipStreamSynchronize(st);
-      TMI_HIP(le);
-      TMI_HIP(ce);
-      TMI_HIP(se);
-      if (lin_pending) graph_seconds += lin_timer.seconds();
-      lin_pending = false;
-      return TMI_BA_OK;
-    };
-    // records, residuals and the cost parts at d_x, then M, its diagonal and the gradient
-    bool scaled = !opt->jacobi_scaling;
-    auto linearize = [&]() -> int {
-      lin_timer.marked = 0;
-      TMI_HIP(lin_timer.mark());
-      hipLaunchKernelGGL(nlp_edge_kernel<true>, edge_grid, block, 0, st, G, width, d_x, nullptr, d_rec, d_res, p_cost,
-                         nullptr);
-      if (!scaled) hipLaunchKernelGGL(nlp_scale_kernel, view_grid, block, 0, st, G, n, d_rec, d_scale);
-      scaled = true;
-      hipLaunchKernelGGL(nlp_assemble_kernel, dim3(n), block, 0, st, G, N, d_rec, d_scale, d_M, d_diag, d_g, d_gabs);
-      TMI_HIP(lin_timer.mark());
-      lin_pending = true;
-      return TMI_BA_OK;
-    };
+    NormalLm L;
     int rc;
-
-    // ---- the directions, the first linearisation, its cost and |x| (the step kernel on y = 0) ----
+    if ((rc = L.alloc(s, N, E))) return rc;
+    hipStream_t st = s->stream;
+    const dim3 edge_grid(L.nbE), view_grid((n + 255) / 256), block(256);
+    // the directions, then the loop
     if (Bh->view_rotation) hipLaunchKernelGGL(lud_direction_kernel, edge_grid, block, 0, st, E, d_rot, d_v1, d_pos, d_t);
-    if ((rc = linearize())) return rc;
-    hipLaunchKernelGGL(nlp_step_kernel, entry_grid, block, 0, st, N, d_x, d_scale, d_y, d_step, d_cand, p_step, p_x);
-    TMI_HIP(hipMemsetAsync(p_mcc, 0, (size_t)nbE * sizeof(double), st));
-    if ((rc = fetch(4))) return rc;
-    double cost = h_norms[0], x_norm = std::sqrt(h_norms[3]);
-    sum->initial_cost = cost;
-
-    // ---- TrustRegionMinimizer with the Levenberg-Marquardt strategy: the rules of tmi_ba_solver_solve ----
-    double radius = opt->initial_trust_region_radius, decrease_factor = 2.0;
-    int invalid_run = 0, iter = 0, termination = 1;
-    bool need_gradient_check = true;
-    cost_trace.push_back(cost);
-    radius_trace.push_back(radius);
-    outcome_trace.push_back(1);
-    auto record = [&](int outcome) {
-      cost_trace.push_back(cost);
-      radius_trace.push_back(radius);
-      outcome_trace.push_back(outcome);
-    };
-    for (;;) {
-      if (iter >= max_it) break;
-      ++iter;
-      timer.marked = 0;
-      TMI_HIP(timer.mark());
-      hipLaunchKernelGGL(nlp_copy_lower_kernel, dim3(N), block, 0, st, N, d_M, d_A);
-      hipLaunchKernelGGL(nlp_lm_diagonal_kernel, entry_grid, block, 0, st, N, d_diag, opt->min_lm_diagonal,
-                         opt->max_lm_diagonal, radius, d_A);
-      dense_cholesky_factor(d_A, N, d_cdiag, d_flag, st);
-      sum->num_factorizations++;
-      TMI_HIP(timer.mark());
-      TMI_HIP(hipMemcpyAsync(d_rhs, d_g, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, st));
-      dense_cholesky_substitute<1>(d_A, N, d_rhs, d_y, d_tmp, st);
-      TMI_HIP(timer.mark());
-      hipLaunchKernelGGL(nlp_step_kernel, entry_grid, block, 0, st, N, d_x, d_scale, d_y, d_step, d_cand, p_step, p_x);
-      hipLaunchKernelGGL(nlp_edge_kernel<false>, edge_grid, block, 0, st, G, width, d_cand, d_step, d_rec, nullptr,
-                         p_cost, p_mcc);
-      if ((rc = fetch(4))) return rc;
-      factor_seconds += timer.seconds(0, 1);
-      subst_seconds += timer.seconds(1, 2);
-      graph_seconds += timer.seconds(2, 3);
-      bool usable = true;
-      if (*h_flag) {  // a non-positive pivot: the linear solve failed, an invalid step as in Ceres
-        usable = false;
-        TMI_HIP(hipMemsetAsync(d_flag, 0, sizeof(int), st));
-      }
-      if (need_gradient_check) {
-        need_gradient_check = false;
-        if (!(h_norms[4] > opt->gradient_tolerance)) {
-          termination = 0;
-          --iter;
-          break;
-        }
-      }
-      const double cand_cost = h_norms[0], model_cost_change = h_norms[1], step_sq = h_norms[2], cand_x_sq = h_norms[3];
-      if (!(model_cost_change > 0.0)) usable = false;
-      if (!usable) {
-        // HandleInvalidStep
-        sum->num_unsuccessful_steps++;
-        if (++invalid_run >= opt->max_num_consecutive_invalid_steps) {
-          record(-1);
-          termination = 2;
-          break;
-        }
-        radius /= decrease_factor;
-        decrease_factor *= 2.0;
-        record(-1);
-        if (radius < opt->min_trust_region_radius) {
-          termination = 0;
-          break;
-        }
-        continue;
-      }
-      invalid_run = 0;
-      if (std::sqrt(step_sq) <= opt->parameter_tolerance * (x_norm + opt->parameter_tolerance)) {
-        record(2);
-        termination = 0;
-        break;
-      }
-      const double cost_change = cost - cand_cost;
-      if (std::fabs(cost_change) <= opt->function_tolerance * cost) {
-        record(3);
-        termination = 0;
-        break;
-      }
-      const double relative_decrease = cost_change / model_cost_change;
-      if (relative_decrease > opt->min_relative_decrease) {  // IsStepSuccessful
-        std::swap(d_x, d_cand);
-        cost = cand_cost;
-        x_norm = std::sqrt(cand_x_sq);
-        sum->num_successful_steps++;
-        radius = radius / std::fmax(1.0 / 3.0, 1.0 - std::pow(2.0 * relative_decrease - 1.0, 3));
-        radius = std::fmin(opt->max_trust_region_radius, radius);
-        decrease_factor = 2.0;
-        if ((rc = linearize())) return rc;
-        need_gradient_check = true;
-        record(1);
-      } else {
-        sum->num_unsuccessful_steps++;
-        radius /= decrease_factor;
-        decrease_factor *= 2.0;
-        record(0);
-      }
-      if (radius < opt->min_trust_region_radius) {
-        termination = 0;
-        break;
-      }
-    }
-
-    // the results, only now: a failure above leaves the caller's arrays as they were
+    rc = normal_lm_solve(
+        s, opt, sum, L, x_h,
+        [&](bool first_scaled) {
+          hipLaunchKernelGGL(nlp_edge_kernel<true>, edge_grid, block, 0, st, G, width, L.x, nullptr, d_rec, d_res,
+                             L.p_cost, nullptr);
+          if (first_scaled)
+            hipLaunchKernelGGL(nlp_scale_kernel<nlp::PositionBlocks>, view_grid, block, 0, st, G, n, d_rec, L.scale);
+          hipLaunchKernelGGL(nlp_assemble_kernel<nlp::PositionBlocks>, dim3(n), block, 0, st, G, N, d_rec, L.scale, L.M,
+                             L.diag, L.g, L.gabs);
+        },
+        [&]() {
+          hipLaunchKernelGGL(nlp_edge_kernel<false>, edge_grid, block, 0, st, G, width, L.cand, L.step, d_rec, nullptr,
+                             L.p_cost, L.p_mcc);
+        });
+    if (rc) return rc;
+    const std::vector<double>&cost_trace = L.cost_trace, &radius_trace = L.radius_trace;
+    const std::vector<int32_t>& outcome_trace = L.outcome_trace;
     std::vector<double> res_h(pair_residual ? (size_t)3 * E : 0);
-    TMI_HIP(hipMemcpyAsync(x_h.data(), d_x, x_h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (pair_residual) TMI_HIP(hipMemcpyAsync(res_h.data(), d_res, res_h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    TMI_HIP(hipStreamSynchronize(st));
-    if (lin_pending) graph_seconds += lin_timer.seconds();
+    if (pair_residual) {
+      TMI_HIP(hipMemcpyAsync(res_h.data(), d_res, res_h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+      TMI_HIP(hipStreamSynchronize(st));
+    }
+    // the results, only now: a failure above leaves the caller's arrays as they were
     for (int v = 0; v < V; ++v)
       for (int k = 0; k < 3; ++k)
         view_position[(size_t)3 * v + k] = v == fixed_view ? 0.0 : x_h[(size_t)3 * (v - (v > fixed_view)) + k];
@@ -2525,14 +2592,174 @@ int32_t tmi_ba_estimate_global_positions_nonlinear(const tmi_ba_view_pair_batch*
     if (iteration_step_accepted) std::copy(outcome_trace.begin(), outcome_trace.end(), iteration_step_accepted);
     sum->num_views = V;
     sum->num_pairs = E;
-    sum->num_iterations = iter;
-    sum->termination = termination;
-    sum->usable = termination != 2;
-    sum->final_cost = cost;
-    sum->factor_seconds = factor_seconds;
-    sum->substitution_seconds = subst_seconds;
-    sum->graph_seconds = graph_seconds;
-    sum->kernel_seconds = factor_seconds + subst_seconds + graph_seconds;
+    return TMI_BA_OK;
+  });
+}
+
+// ---- NonlinearRotationEstimator (rotation_nonlinear_kernels.h) ----------------------------------
+void tmi_ba_nonlinear_rotation_options_init(tmi_ba_nonlinear_rotation_options* o) {
+  if (!o) return;
+  // nonlinear_rotation_estimator.h (width 0.1), nonlinear_rotation_estimator.cc:94 (200 iterations)
+  const SmallLmArgs A = ceres_default_lm_args(200, TMI_BA_LOSS_SOFTLONE, 0.1);
+  o->max_num_iterations = A.max_num_iterations;
+  o->robust_loss_width = A.loss_width;
+  o->fixed_view = -1;
+  o->jacobi_scaling = A.jacobi_scaling;
+  o->max_num_consecutive_invalid_steps = A.max_num_consecutive_invalid_steps;
+  o->function_tolerance = A.function_tolerance;
+  o->gradient_tolerance = A.gradient_tolerance;
+  o->parameter_tolerance = A.parameter_tolerance;
+  o->initial_trust_region_radius = A.initial_radius;
+  o->max_trust_region_radius = A.max_radius;
+  o->min_trust_region_radius = A.min_radius;
+  o->min_relative_decrease = A.min_relative_decrease;
+  o->min_lm_diagonal = A.lm_lo;
+  o->max_lm_diagonal = A.lm_hi;
+}
+
+int32_t tmi_ba_estimate_global_rotations_nonlinear(const tmi_ba_view_pair_batch* Bh,
+                                                   const tmi_ba_nonlinear_rotation_options* opt,
+                                                   const uint8_t* view_given, int32_t device, double* view_rotation,
+                                                   double* iteration_cost, double* iteration_radius,
+                                                   int32_t* iteration_step_accepted, double* pair_residual,
+                                                   tmi_ba_nonlinear_rotation_summary* sum) {
+  if (!Bh || !opt || !view_rotation || !sum)
+    return bad_argument("nonlinear rotations: null batch, options, view_rotation or summary");
+  memset(sum, 0, sizeof(*sum));
+  sum->termination = 2;
+  const double t0 = now_s();
+  // argument errors before the device is touched; the batch's own view_rotation is not this call's
+  tmi_ba_view_pair_batch checked = *Bh;
+  checked.view_rotation = nullptr;
+  if (const char* why = check_view_pair_batch(&checked, false, Bh->pair_rotation2)) return bad_argument(why);
+  const int V = Bh->num_views, E_all = Bh->num_pairs, fixed_view = opt->fixed_view;
+  // the reference's two refusals (nonlinear_rotation_estimator.cc:53-62)
+  if (E_all == 0) return bad_argument("nonlinear rotations: no relative rotation constraint");
+  int num_given = 0;
+  for (int v = 0; v < V; ++v) num_given += !view_given || view_given[v];
+  if (num_given == 0) return bad_argument("nonlinear rotations: no view has an initialisation");
+  if (fixed_view < -1 || fixed_view >= V) return bad_argument("nonlinear rotations: fixed_view out of range");
+  if (fixed_view >= 0 && view_given && !view_given[fixed_view])
+    return bad_argument("nonlinear rotations: fixed_view has no initialisation");
+  if (!(opt->robust_loss_width > 0.0) || !std::isfinite(opt->robust_loss_width))
+    return bad_argument("nonlinear rotations: robust_loss_width is not positive and finite");
+  if (opt->max_num_iterations < 0) return bad_argument("nonlinear rotations: max_num_iterations < 0");
+  for (const double x : {opt->function_tolerance, opt->gradient_tolerance, opt->parameter_tolerance,
+                         opt->initial_trust_region_radius, opt->max_trust_region_radius, opt->min_trust_region_radius,
+                         opt->min_relative_decrease, opt->min_lm_diagonal, opt->max_lm_diagonal})
+    if (!(x >= 0.0)) return bad_argument("nonlinear rotations: a radius, tolerance or LM diagonal bound that is negative or NaN");
+  if (!(opt->initial_trust_region_radius > 0.0)) return bad_argument("nonlinear rotations: initial_trust_region_radius is 0");
+  for (int v = 0; v < V; ++v)
+    if ((!view_given || view_given[v]) && !all_finite(view_rotation + (size_t)3 * v, 3))
+      return bad_argument("nonlinear rotations: a marked view with a non-finite rotation");
+  // the problem: the edges between marked views in the caller's order, and the marked views with such an edge
+  std::vector<int> edge_of;  // [E] the caller's index of edge e of the problem
+  std::vector<int> view_index((size_t)V, -1), view_of;
+  for (int e = 0; e < E_all; ++e) {
+    const int a = Bh->pair_view1[e], b = Bh->pair_view2[e];
+    if (view_given && (!view_given[a] || !view_given[b])) continue;
+    edge_of.push_back(e);
+    view_index[a] = view_index[b] = 0;
+  }
+  for (int v = 0; v < V; ++v)
+    if (view_index[v] == 0) {
+      view_index[v] = (int)view_of.size();
+      view_of.push_back(v);
+    }
+  const int E = (int)edge_of.size(), Vp = (int)view_of.size();
+  // the held view's index in the problem; Vp: no view is held
+  const int held = fixed_view >= 0 && view_index[fixed_view] >= 0 ? view_index[fixed_view] : Vp;
+  const int n = held < Vp ? Vp - 1 : Vp;
+  // the cap before anything of the views' size is allocated
+  if ((int64_t)3 * n > rotation_order_cap()) {
+    g_last_error = "nonlinear rotations: 3 (free views) exceeds the dense solver's cap (see the header)";
+    return TMI_BA_ERR_UNSUPPORTED;
+  }
+  const int N = 3 * n;  // (<= the cap)
+  std::vector<int32_t> v1((size_t)E), v2((size_t)E);
+  std::vector<double> rel((size_t)3 * E), x_h((size_t)N), held_h(3, 0.0);
+  for (int e = 0; e < E; ++e) {
+    v1[e] = view_index[Bh->pair_view1[edge_of[e]]];
+    v2[e] = view_index[Bh->pair_view2[edge_of[e]]];
+    std::copy(Bh->pair_rotation2 + (size_t)3 * edge_of[e], Bh->pair_rotation2 + (size_t)3 * edge_of[e] + 3,
+              rel.begin() + (size_t)3 * e);
+  }
+  auto column_of = [&](int p) { return p == held ? -1 : p - (p > held); };
+  for (int p = 0; p < Vp; ++p) {
+    const double* src = view_rotation + (size_t)3 * view_of[p];
+    std::copy(src, src + 3, p == held ? held_h.begin() : x_h.begin() + (size_t)3 * column_of(p));
+  }
+  const EdgeRows rows = build_edge_rows(Vp, E, v1.data(), v2.data(), held);
+  const double width = opt->robust_loss_width;
+  if (E == 0) {  // an empty problem: solved
+    sum->termination = 0;
+    sum->usable = 1;
+  }
+  return one_shot_batch(device, "nonlinear rotations: no such device", E, t0, sum, [&](OneShot* s) -> int {
+    PositionGraph G;  // (an edge has two views, so n >= 1)
+    memset(&G, 0, sizeof(G));
+    G.num_views = Vp;
+    G.num_pairs = E;
+    G.fixed_view = held;
+    int *d_v1, *d_v2, *d_ptr, *d_lptr;
+    int2 *d_row, *d_lrow;
+    double *d_rel, *d_held, *d_rec, *d_res;
+    TMI_HIP(s->upload(&d_v1, (const int*)v1.data(), (size_t)E));
+    TMI_HIP(s->upload(&d_v2, (const int*)v2.data(), (size_t)E));
+    TMI_HIP(s->upload(&d_ptr, rows.row_ptr.data(), rows.row_ptr.size()));
+    TMI_HIP(s->upload(&d_row, rows.row.data(), rows.row.size()));
+    TMI_HIP(s->upload(&d_lptr, rows.lap_ptr.data(), rows.lap_ptr.size()));
+    TMI_HIP(s->upload(&d_lrow, rows.lap_row.data(), rows.lap_row.size()));
+    TMI_HIP(s->upload(&d_rel, rel.data(), rel.size()));
+    TMI_HIP(s->upload(&d_held, held_h.data(), held_h.size()));
+    TMI_HIP(s->alloc(&d_rec, (size_t)nlr::kRecordPlanes * E));
+    TMI_HIP(s->alloc(&d_res, (size_t)3 * E));
+    G.pair_view1 = d_v1;
+    G.pair_view2 = d_v2;
+    G.t = d_rel;
+    G.row_ptr = d_ptr;
+    G.row = d_row;
+    G.lap_ptr = d_lptr;
+    G.lap_row = d_lrow;
+    NormalLm L;
+    int rc;
+    if ((rc = L.alloc(s, N, E))) return rc;
+    hipStream_t st = s->stream;
+    const dim3 edge_grid(L.nbE), view_grid((n + 255) / 256), block(256);
+    rc = normal_lm_solve(
+        s, opt, sum, L, x_h,
+        [&](bool first_scaled) {
+          hipLaunchKernelGGL(nlr_edge_kernel<true>, edge_grid, block, 0, st, G, width, L.x, nullptr, d_held, d_rec,
+                             d_res, L.p_cost, nullptr);
+          if (first_scaled)
+            hipLaunchKernelGGL(nlp_scale_kernel<nlr::RotationBlocks>, view_grid, block, 0, st, G, n, d_rec, L.scale);
+          hipLaunchKernelGGL(nlp_assemble_kernel<nlr::RotationBlocks>, dim3(n), block, 0, st, G, N, d_rec, L.scale, L.M,
+                             L.diag, L.g, L.gabs);
+        },
+        [&]() {
+          hipLaunchKernelGGL(nlr_edge_kernel<false>, edge_grid, block, 0, st, G, width, L.cand, L.step, d_held, d_rec,
+                             nullptr, L.p_cost, L.p_mcc);
+        });
+    if (rc) return rc;
+    std::vector<double> res_h(pair_residual ? (size_t)3 * E : 0);
+    if (pair_residual) {
+      TMI_HIP(hipMemcpyAsync(res_h.data(), d_res, res_h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+      TMI_HIP(hipStreamSynchronize(st));
+    }
+    // the results, only now: a failure above leaves the caller's arrays as they were
+    for (int p = 0; p < Vp; ++p)
+      if (p != held) std::copy(x_h.begin() + (size_t)3 * column_of(p), x_h.begin() + (size_t)3 * column_of(p) + 3,
+                               view_rotation + (size_t)3 * view_of[p]);
+    if (pair_residual) {
+      std::fill(pair_residual, pair_residual + (size_t)3 * E_all, 0.0);
+      for (int e = 0; e < E; ++e)
+        std::copy(res_h.begin() + (size_t)3 * e, res_h.begin() + (size_t)3 * e + 3, pair_residual + (size_t)3 * edge_of[e]);
+    }
+    if (iteration_cost) std::copy(L.cost_trace.begin(), L.cost_trace.end(), iteration_cost);
+    if (iteration_radius) std::copy(L.radius_trace.begin(), L.radius_trace.end(), iteration_radius);
+    if (iteration_step_accepted) std::copy(L.outcome_trace.begin(), L.outcome_trace.end(), iteration_step_accepted);
+    sum->num_views = Vp;
+    sum->num_pairs = E;
     return TMI_BA_OK;
   });
 }

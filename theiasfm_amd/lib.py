@@ -40,6 +40,7 @@ EXPORTS = (
     "tmi_ba_robust_rotation_options_init", "tmi_ba_estimate_global_rotations_robust",
     "tmi_ba_lud_position_options_init", "tmi_ba_estimate_global_positions_lud",
     "tmi_ba_nonlinear_position_options_init", "tmi_ba_estimate_global_positions_nonlinear",
+    "tmi_ba_nonlinear_rotation_options_init", "tmi_ba_estimate_global_rotations_nonlinear",
     "tmi_ba_localization_options_init", "tmi_ba_localize_views",
     "tmi_ba_match_options_init", "tmi_ba_match_features",
     "tmi_ba_cascade_match_options_init", "tmi_ba_match_features_cascade",
@@ -199,6 +200,13 @@ def load():
         PB, NO, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
         C.POINTER(abi.CNonlinearPositionSummary)]
     L.tmi_ba_estimate_global_positions_nonlinear.restype = C.c_int32
+    NR = C.POINTER(abi.CNonlinearRotationOptions)
+    L.tmi_ba_nonlinear_rotation_options_init.argtypes = [NR]
+    L.tmi_ba_nonlinear_rotation_options_init.restype = None
+    L.tmi_ba_estimate_global_rotations_nonlinear.argtypes = [
+        PB, NR, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+        C.POINTER(abi.CNonlinearRotationSummary)]
+    L.tmi_ba_estimate_global_rotations_nonlinear.restype = C.c_int32
     ZO = C.POINTER(abi.CLocalizationOptions)
     L.tmi_ba_localization_options_init.argtypes = [ZO]
     L.tmi_ba_localization_options_init.restype = None
@@ -662,6 +670,41 @@ def estimate_global_positions_nonlinear(batch: abi.ViewPairBatch, fixed_view: in
     ran = ps.num_iterations + 1
     return dict(positions=pos, initial_positions=initial, residuals=res, costs=costs[:ran].copy(),
                 radii=radii[:ran].copy(), outcomes=outcomes[:ran].copy(), summary=ps)
+
+
+def estimate_global_rotations_nonlinear(batch: abi.ViewPairBatch, view_rotation, options=None, view_given=None,
+                                        device: int = -1, want_outputs: bool = True):
+    """NonlinearRotationEstimator::EstimateRotations on the device.  batch: num_views, the pairs and pair_rotation2 are
+    read.  view_rotation [V, 3]: the start (not modified).  options: a CNonlinearRotationOptions (default: the
+    reference's, fixed_view = -1).  view_given [V] (None: every view): the views that have an initialisation; the others
+    come back as they were.  want_outputs False passes NULL for every optional output.
+    Returns a dict: rotations [V, 3], summary (CNonlinearRotationSummary) and, with want_outputs, residuals [P, 3] (0 for
+    a skipped edge), costs, radii and outcomes (entry 0 the start, then one per iteration run: 1 accepted, 0 rejected,
+    -1 invalid, 2 / 3 ended by the parameter / function tolerance).  Raises EngineError on any failure."""
+    L = load()
+    o = options if options is not None else abi.nonlinear_rotation_options()
+    rot = np.array(view_rotation, dtype=np.float64).reshape(-1, 3)
+    if rot.shape[0] != batch.num_views:
+        raise ValueError("view_rotation must hold batch.num_views rows")
+    given = None if view_given is None else np.ascontiguousarray(view_given, dtype=np.uint8)
+    if given is not None and given.shape != (batch.num_views,):
+        raise ValueError("view_given must hold batch.num_views entries")
+    k = max(int(o.max_num_iterations), 0) + 1
+    res = np.zeros((batch.num_pairs, 3))
+    costs, radii, outcomes = np.zeros(k), np.zeros(k), np.zeros(k, dtype=np.int32)
+    cb = batch.as_c()
+    rs = abi.CNonlinearRotationSummary()
+    ptr = (lambda a: a.ctypes.data) if want_outputs else (lambda a: None)
+    st = L.tmi_ba_estimate_global_rotations_nonlinear(
+        C.byref(cb), C.byref(o), None if given is None else given.ctypes.data, int(device), rot.ctypes.data, ptr(costs),
+        ptr(radii), ptr(outcomes), ptr(res), C.byref(rs))
+    if st != 0:
+        raise EngineError(st, "tmi_ba_estimate_global_rotations_nonlinear")
+    out = dict(rotations=rot, summary=rs)
+    if want_outputs:
+        ran = rs.num_iterations + 1
+        out.update(residuals=res, costs=costs[:ran].copy(), radii=radii[:ran].copy(), outcomes=outcomes[:ran].copy())
+    return out
 
 
 def localize_views(problem: abi.Problem, view_error_threshold, options=None, ba_options=None, view_mask=None,
