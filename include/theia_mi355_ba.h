@@ -1313,6 +1313,79 @@ int32_t tmi_ba_estimate_global_rotations_nonlinear(const tmi_ba_view_pair_batch*
                                                    int32_t* iteration_step_accepted, double* pair_residual,
                                                    tmi_ba_nonlinear_rotation_summary* summary);
 
+/* ---- LinearRotationEstimator: global orientations as the three smallest eigenvectors of a block Laplacian ----
+ * reference: linear_rotation_estimator.cc:78-203 (GlobalRotationEstimatorType::LINEAR,
+ * global_reconstruction_estimator.cc:340-344; Martinec and Pajdla, CVPR 2007) with ProjectToRotationMatrix
+ * (pose/util.cc:121-133).  max_iterations and tolerance are Spectra's defaults maxit and tol, which the reference leaves
+ * alone.  The only rotation estimator that needs no initialisation. */
+typedef struct tmi_ba_linear_rotation_options {
+  int32_t  max_iterations;   /* 1000                                                                        */
+  double   tolerance;        /* 1e-10: the stop rule's residual, relative to 2 x the largest degree         */
+  double   relative_shift;   /* 1e-9: M + mu I is factored, mu = relative_shift x the largest degree        */
+  uint64_t seed;             /* 0: the start block's splitmix64 stream                                      */
+} tmi_ba_linear_rotation_options;
+void tmi_ba_linear_rotation_options_init(tmi_ba_linear_rotation_options* options);
+
+typedef struct tmi_ba_linear_rotation_summary {
+  int32_t num_views;             /* views in the problem: those with an edge                                */
+  int32_t num_pairs;
+  int32_t order;                 /* 3 num_views, the order of the matrix                                    */
+  int32_t num_iterations;        /* subspace iterations run                                                 */
+  int32_t converged;             /* the stop rule was met within max_iterations                             */
+  int32_t usable;                /* 0: a pivot of M + mu I was not positive; nothing was written            */
+  int32_t num_reflected;         /* views whose projection was negated (determinant < 0)                    */
+  double  eigenvalue[4];         /* the three Ritz values of the result and the fourth, ascending           */
+  double  residual[3];           /* |M q - theta q|_2 of the three Ritz pairs                               */
+  double  seconds;
+  double  kernel_seconds;        /* device time; the sum of the three below                                 */
+  double  factor_seconds;        /* the factorisation of M + mu I                                           */
+  double  substitution_seconds;  /* forward / backward substitution on the block of 6                       */
+  double  graph_seconds;         /* assembly, M Q, Gram-Schmidt, Rayleigh-Ritz, the reductions, projection  */
+} tmi_ba_linear_rotation_summary;
+
+/* EstimateRotations on the device.  The batch is tmi_ba_view_pair_batch: num_views, pair_view1 / pair_view2 and
+ * pair_rotation2 are read; the batch's view_rotation and pair_position2 are not.  view_rotation [3 * num_views],
+ * angle-axis, is written only: there is no start.  The views of the problem are those with an edge, in ascending index
+ * (the order of the matrix is n = 3 x their number); every other view's view_rotation is never written.
+ *   1. :90-152   M, symmetric of order n: with R12 = AngleAxisToRotationMatrix(rotation_2) every edge adds I3 to both
+ *                diagonal blocks, -R12^T at block (view1, view2) and -R12 at block (view2, view1): the matrix of
+ *                sum |X2 - R12 X1|_F^2 over 3 x 3 blocks X_i.  Its diagonal is the views' degrees.
+ *   2. :173-181  The three eigenvectors of the smallest eigenvalues.  The reference: Spectra shift-invert Lanczos at
+ *                sigma = 0 on a sparse LL^T of M itself.  HERE (DEVIATION): subspace iteration with Rayleigh-Ritz on a
+ *                block of 6 columns (the reference's ncv) through one dense Cholesky factorisation of M + mu I,
+ *                mu = relative_shift x the largest degree.  The shift moves every eigenvalue by mu and no eigenvector; it
+ *                makes the noise-free problem, whose M is exactly singular, factorable.
+ *                Start block Q [n][6]: Q[i][j] = 2 u - 1, u = ((word >> 11) + 0.5) 2^-53, word 6 i + j of the splitmix64
+ *                stream from state `seed` (the generator documented at tmi_ba_localize_views).
+ *                Each iteration: Y = (M + mu I)^-1 Q; Y orthonormalised by modified Gram-Schmidt, two passes;
+ *                T = Y^T (M Y) with M applied from the edge list, not from the factor; T = W diag(theta) W^T by cyclic
+ *                Jacobi (12 sweeps over the pairs (0,1) (0,2) .. (4,5), theta ascending, the first of equals first, every
+ *                column of W signed so that its coefficient of largest magnitude, the first of equals, is positive);
+ *                Q = Y W.  Stop when |M q_j - theta_j q_j|_2 <= tolerance x 2 x the largest degree (Gershgorin's bound on
+ *                the largest eigenvalue) for j = 0, 1, 2, or after max_iterations.
+ *   3. :188-200  Per view the 3 x 3 block of rows of the first three columns of Q is projected to SO(3): U V^T of its
+ *                SVD (one-sided Jacobi), negated when the determinant is negative, then RotationMatrixToAngleAxis.  A
+ *                block of rank two is completed by the cross product of its two left vectors; one of lower rank gives a
+ *                finite value that is no rotation (the reference's is arbitrary there too).
+ * THE GAUGE.  The result is defined up to one rotation G applied on the right of every view's matrix, R_i G, and which G
+ * comes out depends on rounding wherever two of the three eigenvalues are close: two correct implementations agree in
+ * the loop rotations R_j R_i^T, not in view_rotation itself.  num_reflected is 0 or num_views unless the noise is gross.
+ * Fixed orders, no FMA contraction, no atomics: the same bits from call to call.  The loop runs on the host; every kernel
+ * is a plain grid launch.
+ * TMI_BA_OK whenever the solve ran: summary->converged and ->usable say how; the last Ritz vectors are projected and
+ * written unless usable == 0.  TMI_BA_ERR_UNSUPPORTED when n exceeds the dense solver's cap (11000, the knob
+ * TMI_BA_ROTATION_MAX_ORDER), before anything of that size is allocated.
+ * TMI_BA_ERR_INVALID_ARGUMENT, before the device is looked for: a null batch, options, view_rotation or summary,
+ * num_pairs == 0 (the reference CHECK_GTs its constraints), a missing array, a view index out of range, view1 == view2,
+ * a repeated unordered pair, a non-finite rotation_2, max_iterations <= 0, a tolerance that is not positive and finite,
+ * a relative_shift that is negative or not finite, and (DEVIATION) view pairs that are not connected: with c components
+ * the null space has 3 c dimensions and the three smallest eigenvectors mix the components; the reference returns
+ * garbage there and its pipeline runs RemoveDisconnectedViewPairs first.
+ * On every failure view_rotation is left as it was. */
+int32_t tmi_ba_estimate_global_rotations_linear(const tmi_ba_view_pair_batch* batch,
+                                                const tmi_ba_linear_rotation_options* options, int32_t device,
+                                                double* view_rotation, tmi_ba_linear_rotation_summary* summary);
+
 /* ---- batched LocalizeViewToReconstruction: P3P RANSAC for many candidate views ------------------
  * reference: LocalizeViewToReconstruction (localize_view_to_reconstruction.cc:213-257), the inner loop of the
  * incremental and hybrid pipelines (incremental_reconstruction_estimator.cc:219-233), on its CALIBRATED path:

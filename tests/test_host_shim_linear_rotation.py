@@ -1,0 +1,44 @@
+"""The linear rotation estimator shim (theiasfm_amd/host/linear_rotation_ops.cc) through
+tests/cpp/test_linear_rotation_estimator_shim.cc, compiled here with g++ -Wall -Werror into pytest's tmp_path.  The
+program checks the defaults and the refusals (no constraints, a pair added twice, constraints that are not connected:
+false, nothing written) on any machine; without a device that the call returns false and leaves the map unchanged; with
+one (-m gpu) a 12-view noisy graph against the C ABI called directly on the same flattened input, bit for bit, that a
+key present beforehand keeps its value, and that constraint-by-constraint use equals the one-call form."""
+import os
+import subprocess
+import sys
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import __graft_entry__ as entry  # noqa: E402
+
+LIB = os.path.join(ROOT, "theiasfm_amd", "lib")
+
+
+def _compile(tmp_path):
+    entry.build_engine()
+    exe = str(tmp_path / "test_linear_rotation_estimator_shim")
+    cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-pthread", "-I" + os.path.join(ROOT, "include"), "-o", exe,
+           os.path.join(ROOT, "tests", "cpp", "test_linear_rotation_estimator_shim.cc"),
+           os.path.join(ROOT, "theiasfm_amd", "host", "linear_rotation_ops.cc"),
+           "-L" + LIB, "-ltheia_mi355_ba", "-Wl,-rpath," + LIB, "-Wl,-rpath,/opt/rocm/lib",
+           "-Wl,-rpath-link,/opt/rocm/lib"]
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr
+    return exe
+
+
+def test_linear_rotation_estimator_shim(tmp_path):
+    """Whatever the machine has: without a device false and an unchanged map, with one the full comparison."""
+    p = subprocess.run([_compile(tmp_path)], capture_output=True, text=True, timeout=600)
+    print(p.stdout, p.stderr)
+    assert p.returncode == 0 and "OK" in p.stdout, p.stdout + p.stderr
+
+
+@pytest.mark.gpu
+def test_linear_rotation_estimator_shim_on_the_device(tmp_path):
+    p = subprocess.run([_compile(tmp_path), "--need-device"], capture_output=True, text=True, timeout=600)
+    print(p.stdout, p.stderr)
+    assert p.returncode == 0 and "linear rotation estimator shim: OK" in p.stdout, p.stdout + p.stderr

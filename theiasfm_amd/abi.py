@@ -615,6 +615,50 @@ class CNonlinearRotationSummary(C.Structure):
     _fields_ = list(CNonlinearPositionSummary._fields_)
 
 
+class CLinearRotationOptions(C.Structure):
+    """tmi_ba_linear_rotation_options (Spectra's maxit and tol, the shift of the factored matrix, the start's seed)."""
+    _fields_ = [
+        ("max_iterations", C.c_int32),
+        ("tolerance", C.c_double),
+        ("relative_shift", C.c_double),
+        ("seed", C.c_uint64),
+    ]
+
+
+def linear_rotation_options(**overrides) -> CLinearRotationOptions:
+    """The defaults of tmi_ba_linear_rotation_options_init."""
+    o = CLinearRotationOptions()
+    o.max_iterations = 1000
+    o.tolerance = 1e-10
+    o.relative_shift = 1e-9
+    o.seed = 0
+    for k, v in overrides.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
+class CLinearRotationSummary(C.Structure):
+    """tmi_ba_linear_rotation_summary."""
+    _fields_ = [
+        ("num_views", C.c_int32),
+        ("num_pairs", C.c_int32),
+        ("order", C.c_int32),
+        ("num_iterations", C.c_int32),
+        ("converged", C.c_int32),
+        ("usable", C.c_int32),
+        ("num_reflected", C.c_int32),
+        ("eigenvalue", C.c_double * 4),
+        ("residual", C.c_double * 3),
+        ("seconds", C.c_double),
+        ("kernel_seconds", C.c_double),
+        ("factor_seconds", C.c_double),
+        ("substitution_seconds", C.c_double),
+        ("graph_seconds", C.c_double),
+    ]
+
+
 class CLocalizationOptions(C.Structure):
     """tmi_ba_localization_options (RansacParameters, sample_consensus_estimator.h:57-65, and
     LocalizeViewToReconstructionOptions, localize_view_to_reconstruction.h:48-72)."""

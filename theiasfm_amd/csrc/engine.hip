@@ -45,6 +45,7 @@
 #include "position_kernels.h"
 #include "position_nonlinear_kernels.h"
 #include "rotation_nonlinear_kernels.h"
+#include "rotation_linear_kernels.h"
 #include "localize_kernels.h"
 #include "match_kernels.h"
 #include "cascade_match_kernels.h"

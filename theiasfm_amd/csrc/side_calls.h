@@ -2764,6 +2764,215 @@ int32_t tmi_ba_estimate_global_rotations_nonlinear(const tmi_ba_view_pair_batch*
   });
 }
 
+// ---- LinearRotationEstimator (rotation_linear_kernels.h) -----------------------------------------
+void tmi_ba_linear_rotation_options_init(tmi_ba_linear_rotation_options* o) {
+  if (!o) return;
+  o->max_iterations = 1000;  // Spectra's maxit and tol, which linear_rotation_estimator.cc:173-177 leaves alone
+  o->tolerance = 1e-10;
+  o->relative_shift = 1e-9;  // 200 x the factorisation's rounding n eps 2 at the order cap
+  o->seed = 0;
+}
+
+int32_t tmi_ba_estimate_global_rotations_linear(const tmi_ba_view_pair_batch* Bh,
+                                                const tmi_ba_linear_rotation_options* opt, int32_t device,
+                                                double* view_rotation, tmi_ba_linear_rotation_summary* sum) {
+  if (!Bh || !opt || !view_rotation || !sum)
+    return bad_argument("linear rotations: null batch, options, view_rotation or summary");
+  memset(sum, 0, sizeof(*sum));
+  const double t0 = now_s();
+  // argument errors before the device is touched; the batch's own view_rotation is not this call's
+  tmi_ba_view_pair_batch checked = *Bh;
+  checked.view_rotation = nullptr;
+  if (const char* why = check_view_pair_batch(&checked, false, Bh->pair_rotation2)) return bad_argument(why);
+  const int V = Bh->num_views, E = Bh->num_pairs;
+  if (E == 0) return bad_argument("linear rotations: no relative rotation constraint (the reference CHECK_GTs them)");
+  if (opt->max_iterations <= 0) return bad_argument("linear rotations: max_iterations is not positive");
+  if (!(opt->tolerance > 0.0) || !std::isfinite(opt->tolerance))
+    return bad_argument("linear rotations: tolerance is not positive and finite");
+  if (!(opt->relative_shift >= 0.0) || !std::isfinite(opt->relative_shift))
+    return bad_argument("linear rotations: relative_shift is negative or not finite");
+  // the views of the problem: those with an edge, in ascending index
+  std::vector<int> view_index((size_t)V, -1), view_of;
+  for (int e = 0; e < E; ++e) view_index[Bh->pair_view1[e]] = view_index[Bh->pair_view2[e]] = 0;
+  for (int v = 0; v < V; ++v)
+    if (view_index[v] == 0) {
+      view_index[v] = (int)view_of.size();
+      view_of.push_back(v);
+    }
+  const int Vp = (int)view_of.size();
+  // the cap before anything of the matrix's size is allocated
+  if ((int64_t)3 * Vp > rotation_order_cap()) {
+    g_last_error = "linear rotations: 3 (views with an edge) exceeds the dense solver's cap (see the header)";
+    return TMI_BA_ERR_UNSUPPORTED;
+  }
+  const int n = 3 * Vp;  // (<= the cap)
+  std::vector<int32_t> v1((size_t)E), v2((size_t)E);
+  std::vector<int> parent((size_t)Vp);
+  for (int p = 0; p < Vp; ++p) parent[p] = p;
+  auto find = [&](int p) {
+    while (parent[p] != p) p = parent[p] = parent[parent[p]];
+    return p;
+  };
+  int components = Vp;
+  for (int e = 0; e < E; ++e) {
+    v1[e] = view_index[Bh->pair_view1[e]];
+    v2[e] = view_index[Bh->pair_view2[e]];
+    const int a = find(v1[e]), b = find(v2[e]);
+    if (a != b) {
+      parent[std::max(a, b)] = std::min(a, b);
+      --components;
+    }
+  }
+  if (components != 1)
+    return bad_argument("linear rotations: the view pairs are not connected (with c components the null space has 3 c "
+                        "dimensions; RemoveDisconnectedViewPairs comes first)");
+  const EdgeRows rows = build_edge_rows(Vp, E, v1.data(), v2.data(), Vp);
+  int max_degree = 0;
+  for (int p = 0; p < Vp; ++p) max_degree = std::max(max_degree, rows.row_ptr[(size_t)p + 1] - rows.row_ptr[p]);
+  const double lambda_bound = 2.0 * (double)max_degree;  // Gershgorin
+  const double mu = opt->relative_shift * (double)max_degree;
+  const double threshold = opt->tolerance * lambda_bound;
+  return one_shot_batch(device, "linear rotations: no such device", E, t0, sum, [&](OneShot* s) -> int {
+    hipStream_t st = s->stream;
+    const int nb = (n + 255) / 256;
+    const size_t block_words = (size_t)n * lin::kBlock;
+    int *d_ptr, *d_flag, *d_refl;
+    int2* d_row;
+    double *d_rel, *d_R, *d_A, *d_cdiag, *d_Q, *d_Y, *d_Z, *d_W, *d_tmp, *d_mgs[2], *d_gram, *d_res[3], *d_small, *d_rot;
+    TMI_HIP(s->upload(&d_ptr, rows.row_ptr.data(), rows.row_ptr.size()));
+    TMI_HIP(s->upload(&d_row, rows.row.data(), rows.row.size()));
+    TMI_HIP(s->upload(&d_rel, Bh->pair_rotation2, (size_t)3 * E));
+    TMI_HIP(s->alloc(&d_R, (size_t)9 * E));
+    TMI_HIP(s->alloc(&d_A, (size_t)n * n));  // M + mu I, overwritten by its factor
+    TMI_HIP(s->alloc(&d_cdiag, (size_t)kPanel * ((size_t)(n + kPanel - 1) / kPanel) * kPanel));
+    TMI_HIP(s->alloc(&d_Q, block_words));
+    TMI_HIP(s->alloc(&d_Y, block_words));
+    TMI_HIP(s->alloc(&d_Z, block_words));
+    TMI_HIP(s->alloc(&d_W, block_words));
+    TMI_HIP(s->alloc(&d_tmp, block_words));
+    for (double*& p : d_mgs) TMI_HIP(s->alloc(&p, (size_t)nb * lin::kBlock));
+    TMI_HIP(s->alloc(&d_gram, (size_t)nb * lin::kGram));
+    for (double*& p : d_res) TMI_HIP(s->alloc(&p, (size_t)nb));
+    TMI_HIP(s->alloc(&d_small, (size_t)lin::kSmallWords));
+    TMI_HIP(s->alloc(&d_rot, (size_t)3 * Vp));
+    TMI_HIP(s->alloc(&d_refl, (size_t)Vp));
+    TMI_HIP(s->alloc(&d_flag, 1));
+    PinnedWords pinned;  // the small block, then the pivot flag
+    TMI_HIP(pinned.alloc((lin::kSmallWords + 1) * sizeof(double)));
+    double* h_small = static_cast<double*>(pinned.p);
+    int* h_flag = reinterpret_cast<int*>(h_small + lin::kSmallWords);
+    lin::Graph G;
+    G.num_views = Vp;
+    G.num_pairs = E;
+    G.row_ptr = d_ptr;
+    G.row = d_row;
+    G.R = d_R;
+    const dim3 block(256), rows_grid(nb);
+    sum->num_views = Vp;
+    sum->num_pairs = E;
+    sum->order = n;
+    double factor_seconds = 0.0, subst_seconds = 0.0, graph_seconds = 0.0;
+    auto times = [&]() {
+      sum->factor_seconds = factor_seconds;
+      sum->substitution_seconds = subst_seconds;
+      sum->graph_seconds = graph_seconds;
+      sum->kernel_seconds = factor_seconds + subst_seconds + graph_seconds;
+    };
+    // what the queue has run into by now, after the stream has been waited for
+    auto settle = [&]() -> int {
+      const hipError_t le = hipGetLastError();
+      const hipError_t se = hipStreamSynchronize(st);
+      TMI_HIP(le);
+      TMI_HIP(se);
+      return TMI_BA_OK;
+    };
+    int rc;
+
+    // ---- the matrix, its factor and the start block: marks 0-1 and 2-3 graph kernels, 1-2 the factorisation ----
+    StreamTimer timer(st, 4);
+    TMI_HIP(timer.status);
+    TMI_HIP(timer.mark());
+    hipLaunchKernelGGL(lin_edge_matrix_kernel, dim3((E + 255) / 256), block, 0, st, E, d_rel, d_R);
+    hipLaunchKernelGGL(lin_assemble_kernel, dim3(Vp), block, 0, st, G, n, mu, d_A);
+    TMI_HIP(timer.mark());
+    TMI_HIP(hipMemsetAsync(d_flag, 0, sizeof(int), st));
+    dense_cholesky_factor(d_A, n, d_cdiag, d_flag, st);
+    TMI_HIP(timer.mark());
+    hipLaunchKernelGGL(lin_start_kernel, dim3(((int)block_words + 255) / 256), block, 0, st, n, (unsigned long long)opt->seed,
+                       d_Q);
+    TMI_HIP(timer.mark());
+    TMI_HIP(hipMemcpyAsync(h_flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
+    if ((rc = settle())) return rc;
+    graph_seconds += timer.seconds(0, 1) + timer.seconds(2, 3);
+    factor_seconds += timer.seconds(1, 2);
+    if (*h_flag) {  // a pivot of M + mu I that is not positive: nothing is written
+      times();
+      return TMI_BA_OK;
+    }
+    sum->usable = 1;
+
+    // ---- subspace iteration with Rayleigh-Ritz: marks 0-1 the substitution, 1-2 everything else ----
+    ReduceJobs jobs;
+    memset(&jobs, 0, sizeof(jobs));
+    for (int q = 0; q < 3; ++q) {
+      jobs.part[q] = d_res[q];
+      jobs.count[q] = nb;
+    }
+    int iter = 0, launches = 0;
+    bool converged = false;
+    while (iter < opt->max_iterations && !converged) {
+      ++iter;
+      timer.marked = 0;
+      TMI_HIP(timer.mark());
+      TMI_HIP(hipMemcpyAsync(d_W, d_Q, block_words * sizeof(double), hipMemcpyDeviceToDevice, st));
+      dense_cholesky_substitute<lin::kBlock>(d_A, n, d_W, d_Y, d_tmp, st);
+      TMI_HIP(timer.mark());
+      for (int pass = 0; pass < 2; ++pass)
+        for (int j = 0; j <= lin::kBlock; ++j, ++launches)
+          hipLaunchKernelGGL(lin_mgs_kernel, rows_grid, block, 0, st, n, j, d_Y, d_mgs[(launches + 1) & 1],
+                             d_mgs[launches & 1]);
+      hipLaunchKernelGGL(lin_apply_kernel, dim3((Vp * lin::kBlock + 255) / 256), block, 0, st, G, d_Y, d_Z);
+      hipLaunchKernelGGL(lin_gram_kernel, rows_grid, block, 0, st, n, d_Y, d_Z, d_gram);
+      hipLaunchKernelGGL(lin_ritz_kernel, dim3(1), dim3(64), 0, st, d_gram, nb, d_small);
+      hipLaunchKernelGGL(lin_rotate_kernel, rows_grid, block, 0, st, n, d_small, d_Y, d_Z, d_Q, d_res[0], d_res[1],
+                         d_res[2]);
+      hipLaunchKernelGGL(reduce_partials_kernel, dim3(3), block, 0, st, jobs, d_small + lin::kSmallResidual);
+      TMI_HIP(timer.mark());
+      TMI_HIP(hipMemcpyAsync(h_small, d_small, lin::kSmallWords * sizeof(double), hipMemcpyDeviceToHost, st));
+      if ((rc = settle())) return rc;
+      subst_seconds += timer.seconds(0, 1);
+      graph_seconds += timer.seconds(1, 2);
+      converged = true;
+      for (int j = 0; j < 3; ++j) {
+        sum->residual[j] = std::sqrt(h_small[lin::kSmallResidual + j]);
+        converged = converged && sum->residual[j] <= threshold;
+      }
+    }
+    for (int j = 0; j < 4; ++j) sum->eigenvalue[j] = h_small[lin::kSmallTheta + j];
+    sum->num_iterations = iter;
+    sum->converged = converged;
+
+    // ---- the projection of the last Ritz vectors ----
+    std::vector<double> rot_h((size_t)3 * Vp);
+    std::vector<int> refl_h((size_t)Vp);
+    timer.marked = 0;
+    TMI_HIP(timer.mark());
+    hipLaunchKernelGGL(lin_project_kernel, dim3((Vp + 255) / 256), block, 0, st, Vp, d_Q, d_rot, d_refl);
+    TMI_HIP(timer.mark());
+    TMI_HIP(hipMemcpyAsync(rot_h.data(), d_rot, rot_h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    TMI_HIP(hipMemcpyAsync(refl_h.data(), d_refl, refl_h.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+    if ((rc = settle())) return rc;
+    graph_seconds += timer.seconds(0, 1);
+    times();
+    // the results, only now: a failure above leaves the caller's array as it was
+    for (int p = 0; p < Vp; ++p) {
+      std::copy(rot_h.begin() + (size_t)3 * p, rot_h.begin() + (size_t)3 * p + 3, view_rotation + (size_t)3 * view_of[p]);
+      sum->num_reflected += refl_h[p];
+    }
+    return TMI_BA_OK;
+  });
+}
+
 }  // extern "C"
 
 // ---- the sample-consensus scaffold of the batched RANSAC calls (ransac_core.h) -----------------

@@ -41,6 +41,7 @@ EXPORTS = (
     "tmi_ba_lud_position_options_init", "tmi_ba_estimate_global_positions_lud",
     "tmi_ba_nonlinear_position_options_init", "tmi_ba_estimate_global_positions_nonlinear",
     "tmi_ba_nonlinear_rotation_options_init", "tmi_ba_estimate_global_rotations_nonlinear",
+    "tmi_ba_linear_rotation_options_init", "tmi_ba_estimate_global_rotations_linear",
     "tmi_ba_localization_options_init", "tmi_ba_localize_views",
     "tmi_ba_match_options_init", "tmi_ba_match_features",
     "tmi_ba_cascade_match_options_init", "tmi_ba_match_features_cascade",
@@ -207,7 +208,13 @@ def load():
         PB, NR, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
         C.POINTER(abi.CNonlinearRotationSummary)]
     L.tmi_ba_estimate_global_rotations_nonlinear.restype = C.c_int32
-    ZO = C.POINTER(abi.CLocalizationOptions)
+    LR = C.POINTER(abi.CLinearRotationOptions)
+    L.tmi_ba_linear_rotation_options_init.argtypes = [LR]
+    L.tmi_ba_linear_rotation_options_init.restype = None
+    L.tmi_ba_estimate_global_rotations_linear.argtypes = [
+        PB, LR, C.c_int32, C.c_void_p, C.POINTER(abi.CLinearRotationSummary)]
+    L.tmi_ba_estimate_global_rotations_linear.restype = C.c_int32
+    ZO =C.POINTER(abi.CLocalizationOptions)
     L.tmi_ba_localization_options_init.argtypes = [ZO]
     L.tmi_ba_localization_options_init.restype = None
     L.tmi_ba_localize_views.argtypes = [P, ZO, O, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 9 + [
@@ -705,6 +712,26 @@ def estimate_global_rotations_nonlinear(batch: abi.ViewPairBatch, view_rotation,
         ran = rs.num_iterations + 1
         out.update(residuals=res, costs=costs[:ran].copy(), radii=radii[:ran].copy(), outcomes=outcomes[:ran].copy())
     return out
+
+
+def estimate_global_rotations_linear(batch: abi.ViewPairBatch, options=None, device: int = -1, view_rotation=None):
+    """LinearRotationEstimator::EstimateRotations on the device.  batch: num_views, the pairs and pair_rotation2 are
+    read.  options: a CLinearRotationOptions (default: tmi_ba_linear_rotation_options_init's).  view_rotation [V, 3]
+    (default zeros, not modified): what the views without an edge keep -- there is no start.
+    Returns a dict: rotations [V, 3] and summary (CLinearRotationSummary); with summary.usable == 0 the rotations are
+    as given.  Raises EngineError on any failure."""
+    L = load()
+    o = options if options is not None else abi.linear_rotation_options()
+    rot = (np.zeros((batch.num_views, 3)) if view_rotation is None
+           else np.array(view_rotation, dtype=np.float64).reshape(-1, 3))
+    if rot.shape[0] != batch.num_views:
+        raise ValueError("view_rotation must hold batch.num_views rows")
+    cb = batch.as_c()
+    rs = abi.CLinearRotationSummary()
+    st = L.tmi_ba_estimate_global_rotations_linear(C.byref(cb), C.byref(o), int(device), rot.ctypes.data, C.byref(rs))
+    if st != 0:
+        raise EngineError(st, "tmi_ba_estimate_global_rotations_linear")
+    return dict(rotations=rot, summary=rs)
 
 
 def localize_views(problem: abi.Problem, view_error_threshold, options=None, ba_options=None, view_mask=None,
