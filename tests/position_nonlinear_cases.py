@@ -66,6 +66,7 @@ def _coincident():
 
 CASES = {
     "two views": lambda: _case(model.scene_on_pairs(2, [(0, 1)], 1.0, 5), 0, dict(seed=2)),
+    "two views, the last fixed": lambda: _case(model.scene_on_pairs(2, [(0, 1)], 1.0, 5), 1, dict(seed=2)),
     "reference 4/6 no noise": lambda: _reference("reference 4/6 no noise", 0.0),
     "reference 4/6 1 degree": lambda: _reference("reference 4/6 1 degree", 1.0),
     "shuffled path of 70": lambda: _case(_shuffled_path(70, 31), 35, dict(seed=4, max_num_iterations=40)),

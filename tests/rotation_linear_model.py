@@ -1,5 +1,5 @@
 """A numpy restatement of tmi_ba_estimate_global_rotations_linear (theiasfm_amd/csrc/rotation_linear_kernels.h and its
-host loop in side_calls.h), step for step: the matrix M of linear_rotation_estimator.cc:90-152, the start block from the
+host loop in pose_graph_calls.h), step for step: the matrix M of linear_rotation_estimator.cc:90-152, the start block from the
 splitmix64 stream, the factorisation of M + mu I, subspace iteration on six columns with two passes of modified
 Gram-Schmidt on unnormalised dots, Rayleigh-Ritz by cyclic Jacobi with the device's sweep order, ordering and sign rule,
 the stop rule, and the projection by a one-sided Jacobi SVD.  The factorisation and the sums are numpy's, so the device

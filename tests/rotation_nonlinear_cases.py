@@ -110,6 +110,8 @@ def _mixed_solution():
 
 _SHAPES = {
     "two views": lambda: _case(model.scene_on_pairs(2, [(0, 1)], 0.02, 11), 0, dict(max_num_iterations=1), seed=12),
+    "two views (the last)": lambda: _case(model.scene_on_pairs(2, [(0, 1)], 0.02, 11), 1, dict(max_num_iterations=1),
+                                          seed=12),
     "triangle": lambda: _case(model.scene_on_pairs(3, [(0, 1), (2, 1), (2, 0)], 0.02, 13), 1, seed=14),
     "22 views": lambda: _case(_random(22, 60, 21), 21, seed=22),
     "43 views": lambda: _case(_random(43, 120, 23), 0, seed=24),

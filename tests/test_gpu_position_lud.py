@@ -90,6 +90,7 @@ def _reference(views, pairs, noise, outliers=0.0):
 
 CASES = {("order", 3 * (V - 1)): functools.partial(_order_case, V) for V in (2, 22, 23, 43, 44, 65, 66, 130)}
 CASES.update({
+    "two views, the first fixed": lambda: _scene(2, [(0, 1)], 1.0, 26),  # (("order", 3) fixes the last)
     "path": lambda: _scene(20, _path(20), 1.0, 21),
     "path with chords": lambda: _scene(40, _path(40) + _chords(40, 50, np.random.default_rng(3), _path(40)), 1.0, 22),
     "star, hub fixed": lambda: _star(0),

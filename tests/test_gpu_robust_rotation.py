@@ -90,6 +90,7 @@ def _duplicates():
 
 CASES = {("order", n): functools.partial(_order_case, n) for n in (1, 3, 31, 32, 33, 63, 64, 65, 129)}
 CASES.update({
+    "two views, the last fixed": lambda: _scene(2, [(0, 1)], 1.0, 25) + (1,),  # (("order", 1) fixes the first)
     "path": lambda: _scene(20, _path(20), 1.0, 21) + (0,),
     "path with chords": lambda: _scene(40, _path(40) + _chords(40, 50, np.random.default_rng(3), _path(40)), 1.0, 22) + (0,),
     "K12": lambda: _scene(12, [(a, b) for a in range(12) for b in range(a + 1, 12)], 1.0, 23) + (0,),

@@ -1,0 +1,1092 @@
+// Host side of the global pose estimators: RobustRotationEstimator, LeastUnsquaredDeviationPositionEstimator,
+// NonlinearPositionEstimator, NonlinearRotationEstimator and LinearRotationEstimator on one scaffold.  Every call turns a
+// view table and an edge list into the rows of a PoseGraph (pose_graph.h; built by pose_graph_host.h, uploaded by
+// PoseGraphDevice), works on ONE dense symmetric positive definite matrix of order <= kRotationMaxOrder (DenseSpd) and
+// loops on the host around a substitution, a few per-edge and per-view kernels and one read-back of a few sums and the
+// pivot flag (ScalarFetch), with its device time in three classes (ClassSeconds).  Included by engine.hip after
+// side_calls.h: OneShot, StreamTimer, PinnedWords, one_shot_batch, bad_argument, all_finite and check_view_pair_batch
+// are side_calls.h's.
+#pragma once
+
+#include "pose_graph_host.h"
+
+namespace {
+// The largest order n = V - 1 the calls take (TMI_BA_ROTATION_MAX_ORDER lowers it: a diagnostic knob, so that a small
+// graph reaches the refusal).
+int rotation_order_cap() {
+  int cap = kRotationMaxOrder;
+  if (const char* e = getenv("TMI_BA_ROTATION_MAX_ORDER")) cap = std::max(0, std::min(cap, atoi(e)));
+  return cap;
+}
+
+// The rows of a graph on the device.  upload() is the only place that uploads them: G is complete after it, with
+// edge_value the caller's device array.
+struct PoseGraphDevice {
+  PoseGraph G;
+  int upload(OneShot* s, int V, int fixed_view, const EdgeRows& rows, int E, const int32_t* view1, const int32_t* view2,
+             const double* edge_value) {
+    int *d_v1, *d_v2, *d_ptr, *d_lptr;
+    int2 *d_row, *d_lrow;
+    TMI_HIP(s->upload(&d_v1, (const int*)view1, (size_t)E));
+    TMI_HIP(s->upload(&d_v2, (const int*)view2, (size_t)E));
+    TMI_HIP(s->upload(&d_ptr, rows.row_ptr.data(), rows.row_ptr.size()));
+    TMI_HIP(s->upload(&d_row, rows.row.data(), rows.row.size()));
+    TMI_HIP(s->upload(&d_lptr, rows.lap_ptr.data(), rows.lap_ptr.size()));
+    TMI_HIP(s->upload(&d_lrow, rows.lap_row.data(), rows.lap_row.size()));
+    G = PoseGraph{V, E, fixed_view, d_v1, d_v2, edge_value, d_ptr, d_row, d_lptr, d_lrow};
+    return TMI_BA_OK;
+  }
+};
+
+// Device time in three classes.  begin(c) marks the stream and says that what is queued until the next mark belongs to
+// class c; end() closes the last interval (ScalarFetch::fetch calls it); collect(), after the stream has been waited
+// for, adds the intervals to their classes.  An interval that is read only after the NEXT synchronisation -- a
+// linearisation, queued after the step that it follows has been read back -- has marks of its own (begin_deferred,
+// end_deferred) and belongs to the graph kernels.
+struct ClassSeconds {
+  enum Class { kFactor = 0, kSubstitution = 1, kGraph = 2 };
+  double seconds[3] = {0.0, 0.0, 0.0};
+  StreamTimer timer, deferred;
+  Class of[StreamTimer::kMaxMarks] = {};
+  bool pending = false;
+  explicit ClassSeconds(hipStream_t st) : timer(st, StreamTimer::kMaxMarks), deferred(st, 2) {}
+  hipError_t status() const { return timer.status != hipSuccess ? timer.status : deferred.status; }
+  hipError_t begin(Class c) {
+    of[timer.marked] = c;
+    return timer.mark();
+  }
+  hipError_t end() { return timer.marked > 0 ? timer.mark() : hipSuccess; }
+  hipError_t begin_deferred() {
+    deferred.marked = 0;
+    return deferred.mark();
+  }
+  hipError_t end_deferred() {
+    pending = true;
+    return deferred.mark();
+  }
+  void collect() {
+    for (int m = 0; m + 1 < timer.marked; ++m) seconds[of[m]] += timer.seconds(m, m + 1);
+    timer.marked = 0;
+    if (pending) seconds[kGraph] += deferred.seconds();
+    pending = false;
+  }
+  template <class Sum>
+  void write(Sum* sum) const {
+    sum->factor_seconds = seconds[kFactor];
+    sum->substitution_seconds = seconds[kSubstitution];
+    sum->graph_seconds = seconds[kGraph];
+    sum->kernel_seconds = seconds[kFactor] + seconds[kSubstitution] + seconds[kGraph];
+  }
+};
+
+// The dense symmetric positive definite matrix of a call (dense_cholesky.h): A [N][N], overwritten by its factor, the
+// factorisation's workspace, the substitution's [nrhs N] and the pivot flag (cleared here; a pivot that is not positive
+// sets it).
+struct DenseSpd {
+  int N = 0;
+  double *A = nullptr, *cdiag = nullptr, *tmp = nullptr;
+  int* flag = nullptr;
+  int32_t* factorizations = nullptr;  // the summary's counter (null: none)
+  int alloc(OneShot* s, int N_, int nrhs, int32_t* counter) {
+    N = N_;
+    factorizations = counter;
+    TMI_HIP(s->alloc(&A, (size_t)N * N));
+    TMI_HIP(s->alloc(&cdiag, (size_t)kPanel * ((size_t)(N + kPanel - 1) / kPanel) * kPanel));
+    TMI_HIP(s->alloc(&tmp, (size_t)nrhs * N));
+    TMI_HIP(s->alloc(&flag, 1));
+    TMI_HIP(hipMemsetAsync(flag, 0, sizeof(int), s->stream));
+    return TMI_BA_OK;
+  }
+  void factor(hipStream_t st) {
+    dense_cholesky_factor(A, N, cdiag, flag, st);
+    if (factorizations) ++*factorizations;
+  }
+  template <int NRHS>
+  void substitute(hipStream_t st, double* rhs, double* x) {
+    dense_cholesky_substitute<NRHS>(A, N, rhs, x, tmp, st);
+  }
+};
+
+// The read-back that ends every step of a loop: a few sums of block parts (set(); reduce_partials_kernel), optionally
+// max |.| of a vector behind them (absmax), into the device words d_norms, and from there with the pivot flag into
+// pinned memory.
+struct ScalarFetch {
+  PinnedWords pinned;
+  double *h_norms = nullptr, *d_norms = nullptr;
+  int *h_flag = nullptr, *d_flag = nullptr;
+  ReduceJobs jobs;
+  const double* absmax = nullptr;  // [absmax_n]: its max |.| goes behind the sums
+  int absmax_n = 0;
+  int alloc(OneShot* s, int* pivot_flag, int words = 6) {
+    d_flag = pivot_flag;
+    memset(&jobs, 0, sizeof(jobs));
+    TMI_HIP(s->alloc(&d_norms, (size_t)words + 2));
+    TMI_HIP(pinned.alloc(((size_t)words + 2) * sizeof(double)));
+    h_norms = static_cast<double*>(pinned.p);
+    h_flag = reinterpret_cast<int*>(h_norms + words);
+    return TMI_BA_OK;
+  }
+  void set(int q, const double* part, int count) {
+    jobs.part[q] = part;
+    jobs.count[q] = count;
+  }
+  int flag() const { return *h_flag; }
+  hipError_t clear_flag(hipStream_t st) { return hipMemsetAsync(d_flag, 0, sizeof(int), st); }
+  // The sums of the first `count` quantities into d_norms[at ..], the closing mark, then `words` doubles of d_norms
+  // (< 0: the sums, and max |.| where it is asked for) and the pivot flag (with_flag) to the host, the stream waited
+  // for, and the marked intervals to their classes.
+  int fetch(OneShot* s, ClassSeconds* T, int count, int at = 0, int words = -1, bool with_flag = true) {
+    hipStream_t st = s->stream;
+    if (count > 0) hipLaunchKernelGGL(reduce_partials_kernel, dim3(count), dim3(256), 0, st, jobs, d_norms + at);
+    if (absmax) hipLaunchKernelGGL(nlp_absmax_kernel, dim3(1), dim3(256), 0, st, absmax_n, absmax, d_norms + count);
+    if (words < 0) words = count + (absmax ? 1 : 0);
+    TMI_HIP(T->end());
+    const hipError_t le = hipGetLastError();
+    hipError_t ce = hipSuccess;
+    if (words > 0) ce = hipMemcpyAsync(h_norms, d_norms, (size_t)words * sizeof(double), hipMemcpyDeviceToHost, st);
+    if (ce == hipSuccess && with_flag) ce = hipMemcpyAsync(h_flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, st);
+    const hipError_t se = hipStreamSynchronize(st);
+    TMI_HIP(le);
+    TMI_HIP(ce);
+    TMI_HIP(se);
+    T->collect();
+    return TMI_BA_OK;
+  }
+};
+
+// ---- RobustRotationEstimator (rotation_kernels.h) ----------------------------------------------
+// What the rotation estimator asks of its arguments; null: fine.
+const char* check_rotation_arguments(const tmi_ba_relative_rotation_batch* B, const tmi_ba_robust_rotation_options* o,
+                                     int fixed_view, const double* view_rotation) {
+  const int V = B->num_views, E = B->num_pairs;
+  if (V < 0 || E < 0) return "robust rotations: negative size";
+  if (E == 0) return "robust rotations: no relative rotation (the reference CHECK_GTs the number of constraints)";
+  if (!B->pair_view1 || !B->pair_view2 || !B->pair_rotation) return "robust rotations: missing array";
+  if (fixed_view < 0 || fixed_view >= V) return "robust rotations: fixed_view out of range";
+  if (!(o->l1_step_convergence_threshold > 0.0) || !std::isfinite(o->l1_step_convergence_threshold) ||
+      !(o->irls_step_convergence_threshold > 0.0) || !std::isfinite(o->irls_step_convergence_threshold))
+    return "robust rotations: a step threshold that is not positive and finite";
+  if (!(o->irls_loss_parameter_sigma > 0.0) || !std::isfinite(o->irls_loss_parameter_sigma))
+    return "robust rotations: sigma is not positive and finite";
+  if (o->max_num_l1_iterations < 0 || o->max_num_irls_iterations < 0)
+    return "robust rotations: negative iteration count";
+  for (int e = 0; e < E; ++e) {
+    const int a = B->pair_view1[e], b = B->pair_view2[e];
+    if (a < 0 || a >= V || b < 0 || b >= V) return "robust rotations: view index out of range";
+    if (a == b) return "robust rotations: a view paired with itself";
+  }
+  if (!all_finite(view_rotation, (size_t)3 * V)) return "robust rotations: non-finite view_rotation";
+  if (!all_finite(B->pair_rotation, (size_t)3 * E)) return "robust rotations: non-finite pair_rotation";
+  if (!view_components(V, E, B->pair_view1, B->pair_view2).all_reach(fixed_view))
+    return "robust rotations: a view is not connected to fixed_view";
+  return nullptr;
+}
+}  // namespace
+extern "C" {
+
+void tmi_ba_robust_rotation_options_init(tmi_ba_robust_rotation_options* o) {
+  if (!o) return;
+  o->max_num_l1_iterations = 5;  // robust_rotation_estimator.h:63-82
+  o->l1_step_convergence_threshold = 0.001;
+  o->max_num_irls_iterations = 100;
+  o->irls_step_convergence_threshold = 0.001;
+  o->irls_loss_parameter_sigma = 5.0 * (M_PI / 180.0);
+}
+
+int32_t tmi_ba_estimate_global_rotations_robust(const tmi_ba_relative_rotation_batch* Bh,
+                                                const tmi_ba_robust_rotation_options* opt, int32_t fixed_view,
+                                                int32_t device, double* view_rotation, double* pair_residual,
+                                                int32_t* l1_admm_iterations, double* l1_average_step,
+                                                double* irls_average_step, double* irls_squared_residual,
+                                                tmi_ba_robust_rotation_summary* sum) {
+  if (!Bh || !opt || !view_rotation || !sum)
+    return bad_argument("robust rotations: null batch, options, view_rotation or summary");
+  memset(sum, 0, sizeof(*sum));
+  const double t0 = now_s();
+  // argument errors before the device is touched
+  if (const char* why = check_rotation_arguments(Bh, opt, fixed_view, view_rotation)) return bad_argument(why);
+  const int V = Bh->num_views, E = Bh->num_pairs, n = V - 1;
+  if (n > rotation_order_cap()) {
+    g_last_error = "robust rotations: num_views - 1 exceeds the dense solver's cap (see the header)";
+    return TMI_BA_ERR_UNSUPPORTED;
+  }
+  if (E > (1 << 30)) return bad_argument("robust rotations: more than 2^30 pairs");
+  const EdgeRows rows = build_edge_rows(V, E, Bh->pair_view1, Bh->pair_view2, fixed_view);
+  const int L1 = opt->max_num_l1_iterations, IR = opt->max_num_irls_iterations;
+  std::vector<int> admm_trace;
+  std::vector<double> l1_trace, irls_trace, irls_sq_trace;
+  return one_shot_batch(device, "robust rotations: no such device", E, t0, sum, [&](OneShot* s) -> int {
+    int rc;
+    double *d_rel, *d_o, *d_r, *d_w, *d_z, *d_u, *d_dz, *d_rhs, *d_x, *d_diag_w, *d_part;
+    TMI_HIP(s->upload(&d_rel, Bh->pair_rotation, (size_t)3 * E));
+    TMI_HIP(s->upload(&d_o, (const double*)view_rotation, (size_t)3 * V));
+    PoseGraphDevice graph;
+    if ((rc = graph.upload(s, V, fixed_view, rows, E, Bh->pair_view1, Bh->pair_view2, d_rel))) return rc;
+    const PoseGraph& G = graph.G;
+    TMI_HIP(s->alloc(&d_r, (size_t)3 * E));
+    TMI_HIP(s->alloc(&d_w, (size_t)E));
+    TMI_HIP(s->alloc(&d_z, (size_t)3 * E));
+    TMI_HIP(s->alloc(&d_u, (size_t)3 * E));
+    TMI_HIP(s->alloc(&d_dz, (size_t)3 * E));
+    TMI_HIP(s->alloc(&d_rhs, (size_t)3 * n));
+    TMI_HIP(s->alloc(&d_x, (size_t)3 * n));
+    TMI_HIP(s->alloc(&d_diag_w, (size_t)n));
+    const int nbE = (E + 255) / 256, nbV = (n + 255) / 256;
+    TMI_HIP(s->alloc(&d_part, (size_t)4 * nbE + (size_t)3 * nbV));
+    double *p_r = d_part, *p_ax = p_r + nbE, *p_z = p_ax + nbE, *p_rr = p_z + nbE, *p_s = p_rr + nbE, *p_t = p_s + nbV,
+           *p_step = p_t + nbV;
+    DenseSpd lap;  // the Laplacian, order n, three right-hand sides
+    if ((rc = lap.alloc(s, n, 3, &sum->num_factorizations))) return rc;
+    ScalarFetch F;  // the ADMM norms, or |r|^2 and the step sum
+    if ((rc = F.alloc(s, lap.flag))) return rc;
+    hipStream_t st = s->stream;
+    const dim3 edge_grid(nbE), view_grid(nbV), block(256);
+    const double sigma = opt->irls_loss_parameter_sigma;
+    ClassSeconds T(st);
+    TMI_HIP(T.status());
+    const char* pivot = "robust rotations: a pivot of the Laplacian's Cholesky factorisation is not positive";
+
+    // ---- ComputeResiduals, and the factorisation of the L1 phase (:149-155) ----
+    TMI_HIP(T.begin(T.kFactor));
+    if (L1 > 0) {
+      hipLaunchKernelGGL(laplacian_assemble_kernel, dim3(n), block, 0, st, G, n, nullptr, nullptr, lap.A);
+      lap.factor(st);
+    }
+    TMI_HIP(T.begin(T.kGraph));
+    hipLaunchKernelGGL(rotation_residual_kernel, edge_grid, block, 0, st, G, d_o, sigma, d_r, d_w, p_rr);
+    F.set(0, p_rr, nbE);
+    if ((rc = F.fetch(s, &T, 1))) return rc;
+    if (F.flag()) {
+      s->error = pivot;
+      return TMI_BA_ERR_LINEAR_SOLVER;
+    }
+    double r_sq = F.h_norms[0];
+
+    // ---- SolveL1Regression (:156-169) ----
+    const double rho = 1.0, alpha = 1.0, abs_tol = 1e-4, rel_tol = 1e-2;  // l1_solver.h:89-98
+    const double primal_abs = std::sqrt(3.0 * (double)E) * abs_tol, dual_abs = std::sqrt(3.0 * (double)n) * abs_tol;
+    int budget = 5;
+    for (int outer = 0; outer < L1; ++outer) {
+      const double rhs_norm = std::sqrt(r_sq);
+      TMI_HIP(T.begin(T.kGraph));
+      TMI_HIP(hipMemsetAsync(d_z, 0, (size_t)3 * E * sizeof(double), st));
+      TMI_HIP(hipMemsetAsync(d_u, 0, (size_t)3 * E * sizeof(double), st));
+      TMI_HIP(hipMemsetAsync(d_dz, 0, (size_t)3 * E * sizeof(double), st));
+      hipLaunchKernelGGL(admm_view_kernel, view_grid, block, 0, st, G, n, rho, d_r, d_z, d_u, d_dz, d_rhs, p_s, p_t);
+      F.set(0, p_r, nbE);
+      F.set(1, p_ax, nbE);
+      F.set(2, p_z, nbE);
+      F.set(3, p_s, nbV);
+      F.set(4, p_t, nbV);
+      int ran = 0;
+      for (int it = 0; it < budget; ++it) {
+        TMI_HIP(T.begin(T.kSubstitution));
+        lap.substitute<3>(st, d_rhs, d_x);
+        TMI_HIP(T.begin(T.kGraph));
+        hipLaunchKernelGGL(admm_edge_kernel, edge_grid, block, 0, st, G, rho, alpha, d_x, d_r, d_z, d_u, d_dz, p_r, p_ax,
+                           p_z);
+        hipLaunchKernelGGL(admm_view_kernel, view_grid, block, 0, st, G, n, rho, d_r, d_z, d_u, d_dz, d_rhs, p_s, p_t);
+        if ((rc = F.fetch(s, &T, 5))) return rc;
+        ++ran;
+        if (admm_converged(F.h_norms, rhs_norm, primal_abs, dual_abs, rel_tol).converged) break;
+      }
+      // UpdateGlobalRotations, ComputeResiduals, ComputeAverageStepSize
+      TMI_HIP(T.begin(T.kGraph));
+      hipLaunchKernelGGL(rotation_update_kernel, view_grid, block, 0, st, n, fixed_view, d_x, d_o, p_step);
+      hipLaunchKernelGGL(rotation_residual_kernel, edge_grid, block, 0, st, G, d_o, sigma, d_r, d_w, p_rr);
+      F.set(0, p_rr, nbE);
+      F.set(1, p_step, nbV);
+      if ((rc = F.fetch(s, &T, 2))) return rc;
+      r_sq = F.h_norms[0];
+      const double avg = F.h_norms[1] / (double)n;
+      admm_trace.push_back(ran);
+      l1_trace.push_back(avg);
+      sum->num_l1_iterations++;
+      sum->num_admm_iterations += ran;
+      if (avg <= opt->l1_step_convergence_threshold) {
+        sum->l1_converged = 1;
+        break;
+      }
+      budget *= 2;
+    }
+
+    // ---- SolveIRLS (:189-234) ----
+    F.set(0, p_rr, nbE);
+    F.set(1, p_step, nbV);
+    for (int it = 0; it < IR; ++it) {
+      TMI_HIP(T.begin(T.kFactor));
+      hipLaunchKernelGGL(irls_rhs_kernel, view_grid, block, 0, st, G, n, d_w, d_r, d_rhs, d_diag_w);
+      hipLaunchKernelGGL(laplacian_assemble_kernel, dim3(n), block, 0, st, G, n, d_w, d_diag_w, lap.A);
+      lap.factor(st);
+      TMI_HIP(T.begin(T.kSubstitution));
+      lap.substitute<3>(st, d_rhs, d_x);
+      TMI_HIP(T.begin(T.kGraph));
+      hipLaunchKernelGGL(rotation_update_kernel, view_grid, block, 0, st, n, fixed_view, d_x, d_o, p_step);
+      hipLaunchKernelGGL(rotation_residual_kernel, edge_grid, block, 0, st, G, d_o, sigma, d_r, d_w, p_rr);
+      if ((rc = F.fetch(s, &T, 2))) return rc;
+      if (F.flag()) {
+        s->error = pivot;
+        return TMI_BA_ERR_LINEAR_SOLVER;
+      }
+      r_sq = F.h_norms[0];
+      const double avg = F.h_norms[1] / (double)n;
+      irls_trace.push_back(avg);
+      irls_sq_trace.push_back(r_sq);
+      sum->num_irls_iterations++;
+      if (avg < opt->irls_step_convergence_threshold) {
+        sum->irls_converged = 1;
+        break;
+      }
+    }
+
+    // the results, only now: a failure above leaves the caller's arrays as they were
+    std::vector<double> o_h((size_t)3 * V), r_h(pair_residual ? (size_t)3 * E : 0);
+    TMI_HIP(hipMemcpyAsync(o_h.data(), d_o, o_h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (pair_residual) TMI_HIP(hipMemcpyAsync(r_h.data(), d_r, r_h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    TMI_HIP(hipStreamSynchronize(st));
+    std::copy(o_h.begin(), o_h.end(), view_rotation);
+    if (pair_residual) std::copy(r_h.begin(), r_h.end(), pair_residual);
+    if (l1_admm_iterations) std::copy(admm_trace.begin(), admm_trace.end(), l1_admm_iterations);
+    if (l1_average_step) std::copy(l1_trace.begin(), l1_trace.end(), l1_average_step);
+    if (irls_average_step) std::copy(irls_trace.begin(), irls_trace.end(), irls_average_step);
+    if (irls_squared_residual) std::copy(irls_sq_trace.begin(), irls_sq_trace.end(), irls_squared_residual);
+    sum->num_views = V;
+    sum->num_pairs = E;
+    T.write(sum);
+    return TMI_BA_OK;
+  });
+}
+}  // extern "C"
+
+// ---- LeastUnsquaredDeviationPositionEstimator (position_kernels.h) ------------------------------
+namespace {
+// What the position estimator asks of its arguments beyond check_view_pair_batch, the connection to fixed_view apart;
+// null: fine.  Nothing is allocated here.
+const char* check_lud_arguments(const tmi_ba_view_pair_batch* B, const tmi_ba_lud_position_options* o, int fixed_view) {
+  if (B->num_pairs == 0) return "LUD positions: no view pair";
+  if (fixed_view < 0 || fixed_view >= B->num_views) return "LUD positions: fixed_view out of range";
+  for (const double x : {o->rho, o->alpha, o->absolute_tolerance, o->relative_tolerance})
+    if (!(x > 0.0) || !std::isfinite(x)) return "LUD positions: rho, alpha or a tolerance that is not positive and finite";
+  if (o->max_num_iterations < 1) return "LUD positions: max_num_iterations < 1 (the reference CHECK_GTs it)";
+  return nullptr;
+}
+}  // namespace
+extern "C" {
+
+void tmi_ba_lud_position_options_init(tmi_ba_lud_position_options* o) {
+  if (!o) return;
+  o->max_num_iterations = 1000;  // math/constrained_l1_solver.h:64-74
+  o->rho = 10.0;
+  o->alpha = 1.2;
+  o->absolute_tolerance = 1e-4;
+  o->relative_tolerance = 1e-2;
+}
+
+int32_t tmi_ba_estimate_global_positions_lud(const tmi_ba_view_pair_batch* Bh, const tmi_ba_lud_position_options* opt,
+                                             int32_t fixed_view, int32_t device, double* view_position,
+                                             double* pair_scale, double* pair_residual, double* admm_r_norm,
+                                             double* admm_s_norm, tmi_ba_lud_position_summary* sum) {
+  if (!Bh || !opt || !view_position || !sum)
+    return bad_argument("LUD positions: null batch, options, view_position or summary");
+  memset(sum, 0, sizeof(*sum));
+  const double t0 = now_s();
+  // argument errors before the device is touched
+  if (const char* why = check_view_pair_batch(Bh, false, Bh->pair_position2)) return bad_argument(why);
+  if (const char* why = check_lud_arguments(Bh, opt, fixed_view)) return bad_argument(why);
+  const int V = Bh->num_views, E = Bh->num_pairs, n = V - 1;
+  // the cap before anything of the views' size is allocated, the union-find included
+  if ((int64_t)3 * n > rotation_order_cap()) {
+    g_last_error = "LUD positions: 3 (num_views - 1) exceeds the dense solver's cap (see the header)";
+    return TMI_BA_ERR_UNSUPPORTED;
+  }
+  const int N = 3 * n;  // (<= the cap)
+  if (!view_components(V, E, Bh->pair_view1, Bh->pair_view2).all_reach(fixed_view))
+    return bad_argument("LUD positions: a view is not connected to fixed_view");
+  const EdgeRows rows = build_edge_rows(V, E, Bh->pair_view1, Bh->pair_view2, fixed_view);
+  const int max_it = opt->max_num_iterations;
+  const double rho = opt->rho, alpha = opt->alpha;
+  std::vector<double> r_trace, s_trace;
+  return one_shot_batch(device, "LUD positions: no such device", E, t0, sum, [&](OneShot* s) -> int {
+    int rc;
+    double *d_pos, *d_t, *d_rot = nullptr, *d_qs, *d_z, *d_u, *d_dz, *d_scale, *d_ax, *d_rhs, *d_p, *d_part;
+    TMI_HIP(s->upload(&d_pos, Bh->pair_position2, (size_t)3 * E));
+    d_t = d_pos;
+    if (Bh->view_rotation) {
+      TMI_HIP(s->upload(&d_rot, Bh->view_rotation, (size_t)3 * V));
+      TMI_HIP(s->alloc(&d_t, (size_t)3 * E));
+    }
+    PoseGraphDevice graph;
+    if ((rc = graph.upload(s, V, fixed_view, rows, E, Bh->pair_view1, Bh->pair_view2, d_t))) return rc;
+    const PoseGraph& G = graph.G;
+    const std::vector<double> ones((size_t)E, 1.0);  // the scale entries of A^T b
+    TMI_HIP(s->upload(&d_qs, ones.data(), ones.size()));
+    TMI_HIP(s->alloc(&d_z, (size_t)4 * E));
+    TMI_HIP(s->alloc(&d_u, (size_t)4 * E));
+    TMI_HIP(s->alloc(&d_dz, (size_t)4 * E));
+    TMI_HIP(s->alloc(&d_scale, (size_t)E));
+    TMI_HIP(s->alloc(&d_ax, (size_t)3 * E));
+    TMI_HIP(s->alloc(&d_rhs, (size_t)N));
+    TMI_HIP(s->alloc(&d_p, (size_t)N));
+    const int nbE = (E + 255) / 256, nbV = (n + 255) / 256;
+    // the blocks' parts: |A x - z - b|^2, |A x|^2, |z|^2 [nbE each], then |rho A^T dz|^2 and |rho A^T u|^2, each the
+    // edges' parts [nbE] followed by the views' [nbV] and reduced as one quantity
+    TMI_HIP(s->alloc(&d_part, (size_t)5 * nbE + (size_t)2 * nbV));
+    double *p_r = d_part, *p_ax = p_r + nbE, *p_z = p_ax + nbE, *p_s = p_z + nbE, *p_t = p_s + nbE + nbV;
+    DenseSpd S;  // order N, one right-hand side
+    if ((rc = S.alloc(s, N, 1, &sum->num_factorizations))) return rc;
+    ScalarFetch F;  // the ADMM norms
+    if ((rc = F.alloc(s, S.flag))) return rc;
+    F.set(0, p_r, nbE);
+    F.set(1, p_ax, nbE);
+    F.set(2, p_z, nbE);
+    F.set(3, p_s, nbE + nbV);
+    F.set(4, p_t, nbE + nbV);
+    hipStream_t st = s->stream;
+    const dim3 edge_grid(nbE), view_grid(nbV), block(256);
+    TMI_HIP(hipMemsetAsync(d_z, 0, (size_t)4 * E * sizeof(double), st));
+    TMI_HIP(hipMemsetAsync(d_u, 0, (size_t)4 * E * sizeof(double), st));
+    TMI_HIP(hipMemsetAsync(d_dz, 0, (size_t)4 * E * sizeof(double), st));
+    ClassSeconds T(st);
+    TMI_HIP(T.status());
+
+    // ---- the directions, S and its factor, and the right-hand side of the first solve: A^T b ----
+    TMI_HIP(T.begin(T.kFactor));
+    if (Bh->view_rotation)
+      hipLaunchKernelGGL(lud_direction_kernel, edge_grid, block, 0, st, E, d_rot, G.pair_view1, d_pos, d_t);
+    hipLaunchKernelGGL(lud_assemble_kernel, dim3(n), block, 0, st, G, N, S.A);
+    S.factor(st);
+    TMI_HIP(T.begin(T.kGraph));
+    hipLaunchKernelGGL(lud_view_kernel, view_grid, block, 0, st, G, n, rho, d_qs, d_z, d_u, d_dz, d_rhs, p_s + nbE,
+                       p_t + nbE);
+    if ((rc = F.fetch(s, &T, 0))) return rc;  // (no sum yet: the pivot flag alone)
+    if (F.flag()) {
+      s->error = "LUD positions: a pivot of the Cholesky factorisation of S is not positive";
+      return TMI_BA_ERR_LINEAR_SOLVER;
+    }
+
+    // ---- ConstrainedL1Solver::Solve (:112-170) ----
+    const double rhs_norm = std::sqrt((double)E);  // |b|
+    const double primal_abs = std::sqrt(4.0 * (double)E) * opt->absolute_tolerance;
+    const double dual_abs = std::sqrt(3.0 * (double)n + (double)E) * opt->absolute_tolerance;
+    for (int it = 0; it < max_it; ++it) {
+      TMI_HIP(T.begin(T.kSubstitution));
+      S.substitute<1>(st, d_rhs, d_p);
+      TMI_HIP(T.begin(T.kGraph));
+      hipLaunchKernelGGL(lud_edge_kernel, edge_grid, block, 0, st, G, rho, alpha, d_p, d_qs, d_z, d_u, d_dz, d_scale,
+                         d_ax, p_r, p_ax, p_z, p_s, p_t);
+      hipLaunchKernelGGL(lud_view_kernel, view_grid, block, 0, st, G, n, rho, d_qs, d_z, d_u, d_dz, d_rhs, p_s + nbE,
+                         p_t + nbE);
+      if ((rc = F.fetch(s, &T, 5))) return rc;
+      sum->num_admm_iterations++;
+      const AdmmNorms norms = admm_converged(F.h_norms, rhs_norm, primal_abs, dual_abs, opt->relative_tolerance);
+      r_trace.push_back(norms.r_norm);
+      s_trace.push_back(norms.s_norm);
+      if (norms.converged) {
+        sum->converged = 1;
+        break;
+      }
+    }
+
+    // the results, only now: a failure above leaves the caller's arrays as they were
+    std::vector<double> p_h((size_t)N), scale_h(pair_scale ? (size_t)E : 0), ax_h(pair_residual ? (size_t)3 * E : 0);
+    TMI_HIP(hipMemcpyAsync(p_h.data(), d_p, p_h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (pair_scale) TMI_HIP(hipMemcpyAsync(scale_h.data(), d_scale, scale_h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (pair_residual) TMI_HIP(hipMemcpyAsync(ax_h.data(), d_ax, ax_h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    TMI_HIP(hipStreamSynchronize(st));
+    scatter_free(V, fixed_view, nullptr, p_h.data(), view_position);
+    std::fill(view_position + (size_t)3 * fixed_view, view_position + (size_t)3 * fixed_view + 3, 0.0);
+    if (pair_scale) std::copy(scale_h.begin(), scale_h.end(), pair_scale);
+    if (pair_residual) std::copy(ax_h.begin(), ax_h.end(), pair_residual);
+    if (admm_r_norm) std::copy(r_trace.begin(), r_trace.end(), admm_r_norm);
+    if (admm_s_norm) std::copy(s_trace.begin(), s_trace.end(), admm_s_norm);
+    sum->num_views = V;
+    sum->num_pairs = E;
+    T.write(sum);
+    return TMI_BA_OK;
+  });
+}
+}  // extern "C"
+
+// ---- NonlinearPositionEstimator (position_nonlinear_kernels.h) ----------------------------------
+namespace {
+// The device memory of the Levenberg-Marquardt loop on dense normal equations of order N over E edges that the nonlinear
+// position and rotation estimators share (normal_lm_solve), and the traces it leaves.
+struct NormalLm {
+  int N = 0, nbE = 0, nbN = 0;
+  double *x, *cand, *step, *y, *rhs, *scale, *diag, *g, *gabs, *M, *part;
+  DenseSpd damped;  // the damped copy of M, overwritten by the factor
+  ScalarFetch F;    // cost, model cost change, |step|^2, |candidate|^2, max |gradient|
+  double *p_cost, *p_mcc, *p_step, *p_x;  // the blocks' parts: cost and model cost change [nbE], |step|^2, |x|^2 [nbN]
+  std::vector<double> cost_trace, radius_trace;
+  std::vector<int32_t> outcome_trace;
+  int alloc(OneShot* s, int N_, int E, int32_t* factorizations) {
+    N = N_;
+    nbE = (E + 255) / 256;
+    nbN = (N + 255) / 256;
+    TMI_HIP(s->alloc(&x, (size_t)N));
+    const std::vector<double> ones((size_t)N, 1.0);  // the scales without jacobi_scaling
+    TMI_HIP(s->upload(&scale, ones.data(), ones.size()));
+    TMI_HIP(hipStreamSynchronize(s->stream));  // (ones goes out of scope)
+    TMI_HIP(s->alloc(&cand, (size_t)N));
+    TMI_HIP(s->alloc(&step, (size_t)N));
+    TMI_HIP(s->alloc(&y, (size_t)N));
+    TMI_HIP(s->alloc(&rhs, (size_t)N));
+    TMI_HIP(s->alloc(&diag, (size_t)N));
+    TMI_HIP(s->alloc(&g, (size_t)N));
+    TMI_HIP(s->alloc(&gabs, (size_t)N));
+    TMI_HIP(s->alloc(&M, (size_t)N * N));  // the assembled normal matrix, kept across rejected steps
+    TMI_HIP(s->alloc(&part, (size_t)2 * nbE + (size_t)2 * nbN));
+    int rc;
+    if ((rc = damped.alloc(s, N, 1, factorizations))) return rc;
+    if ((rc = F.alloc(s, damped.flag))) return rc;
+    p_cost = part;
+    p_mcc = p_cost + nbE;
+    p_step = p_mcc + nbE;
+    p_x = p_step + nbN;
+    F.set(0, p_cost, nbE);
+    F.set(1, p_mcc, nbE);
+    F.set(2, p_step, nbN);
+    F.set(3, p_x, nbN);
+    F.absmax = gabs;
+    F.absmax_n = N;
+    return TMI_BA_OK;
+  }
+};
+
+// Ceres 1.14's TrustRegionMinimizer with the Levenberg-Marquardt strategy on the dense normal equations, the rules of
+// tmi_ba_solver_solve (steps 6 and 7 of tmi_ba_estimate_global_positions_nonlinear).  x_h [N] is the start and receives
+// the last accepted point.  linearize(first_scaled) queues, at L.x: the records, the residuals and the cost parts
+// (L.p_cost), the Jacobi scales into L.scale where first_scaled, then L.M, L.diag, L.g and L.gabs.  candidate() queues, at
+// L.cand with L.step: the cost parts and the parts of the model cost change (L.p_mcc).  Opt has the trust-region fields of
+// tmi_ba_nonlinear_position_options; Sum the counters and times of tmi_ba_nonlinear_position_summary.
+// Device time: an iteration's damped copy and factorisation, its substitution, then the step, the candidate and the
+// reductions; a linearisation with its assembly is read after the next synchronisation (ClassSeconds' deferred marks).
+template <class Opt, class Sum, class Linearize, class Candidate>
+int normal_lm_solve(OneShot* s, const Opt* opt, Sum* sum, NormalLm& L, std::vector<double>& x_h, Linearize linearize_at,
+                    Candidate candidate_at) {
+  const int N = L.N, nbE = L.nbE, nbN = L.nbN, max_it = opt->max_num_iterations;
+  double*& d_x = L.x;
+  double*& d_cand = L.cand;
+  double *d_step = L.step, *d_y = L.y, *d_rhs = L.rhs, *d_scale = L.scale, *d_diag = L.diag, *d_g = L.g, *d_M = L.M;
+  double *p_mcc = L.p_mcc, *p_step = L.p_step, *p_x = L.p_x;
+  DenseSpd& damped = L.damped;
+  ScalarFetch& F = L.F;
+  const double* h_norms = F.h_norms;
+  std::vector<double>&cost_trace = L.cost_trace, &radius_trace = L.radius_trace;
+  std::vector<int32_t>& outcome_trace = L.outcome_trace;
+  hipStream_t st = s->stream;
+  const dim3 entry_grid(nbN), block(256);
+  TMI_HIP(hipMemcpyAsync(d_x, x_h.data(), (size_t)N * sizeof(double), hipMemcpyHostToDevice, st));
+  TMI_HIP(hipMemsetAsync(d_y, 0, (size_t)N * sizeof(double), st));
+  ClassSeconds T(st);
+  TMI_HIP(T.status());
+  // records, residuals and the cost parts at d_x, then M, its diagonal and the gradient
+  bool scaled = !opt->jacobi_scaling;
+  auto linearize = [&]() -> int {
+    TMI_HIP(T.begin_deferred());
+    linearize_at(!scaled);
+    scaled = true;
+    TMI_HIP(T.end_deferred());
+    return TMI_BA_OK;
+  };
+  int rc;
+
+  // ---- the first linearisation, its cost and |x| (the step kernel on y = 0) ----
+  if ((rc = linearize())) return rc;
+  hipLaunchKernelGGL(nlp_step_kernel, entry_grid, block, 0, st, N, d_x, d_scale, d_y, d_step, d_cand, p_step, p_x);
+  TMI_HIP(hipMemsetAsync(p_mcc, 0, (size_t)nbE * sizeof(double), st));
+  if ((rc = F.fetch(s, &T, 4))) return rc;
+  double cost = h_norms[0], x_norm = std::sqrt(h_norms[3]);
+  sum->initial_cost = cost;
+
+  double radius = opt->initial_trust_region_radius, decrease_factor = 2.0;
+  int invalid_run = 0, iter = 0, termination = 1;
+  bool need_gradient_check = true;
+  cost_trace.push_back(cost);
+  radius_trace.push_back(radius);
+  outcome_trace.push_back(1);
+  auto record = [&](int outcome) {
+    cost_trace.push_back(cost);
+    radius_trace.push_back(radius);
+    outcome_trace.push_back(outcome);
+  };
+  for (;;) {
+    if (iter >= max_it) break;
+    ++iter;
+    TMI_HIP(T.begin(T.kFactor));
+    hipLaunchKernelGGL(nlp_copy_lower_kernel, dim3(N), block, 0, st, N, d_M, damped.A);
+    hipLaunchKernelGGL(nlp_lm_diagonal_kernel, entry_grid, block, 0, st, N, d_diag, opt->min_lm_diagonal,
+                       opt->max_lm_diagonal, radius, damped.A);
+    damped.factor(st);
+    TMI_HIP(T.begin(T.kSubstitution));
+    TMI_HIP(hipMemcpyAsync(d_rhs, d_g, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, st));
+    damped.substitute<1>(st, d_rhs, d_y);
+    TMI_HIP(T.begin(T.kGraph));
+    hipLaunchKernelGGL(nlp_step_kernel, entry_grid, block, 0, st, N, d_x, d_scale, d_y, d_step, d_cand, p_step, p_x);
+    candidate_at();
+    if ((rc = F.fetch(s, &T, 4))) return rc;
+    bool usable = true;
+    if (F.flag()) {  // a non-positive pivot: the linear solve failed, an invalid step as in Ceres
+      usable = false;
+      TMI_HIP(F.clear_flag(st));
+    }
+    if (need_gradient_check) {
+      need_gradient_check = false;
+      if (!(h_norms[4] > opt->gradient_tolerance)) {
+        termination = 0;
+        --iter;
+        break;
+      }
+    }
+    const double cand_cost = h_norms[0], model_cost_change = h_norms[1], step_sq = h_norms[2], cand_x_sq = h_norms[3];
+    if (!(model_cost_change > 0.0)) usable = false;
+    if (!usable) {
+      // HandleInvalidStep
+      sum->num_unsuccessful_steps++;
+      if (++invalid_run >= opt->max_num_consecutive_invalid_steps) {
+        record(-1);
+        termination = 2;
+        break;
+      }
+      radius /= decrease_factor;
+      decrease_factor *= 2.0;
+      record(-1);
+      if (radius < opt->min_trust_region_radius) {
+        termination = 0;
+        break;
+      }
+      continue;
+    }
+    invalid_run = 0;
+    if (std::sqrt(step_sq) <= opt->parameter_tolerance * (x_norm + opt->parameter_tolerance)) {
+      record(2);
+      termination = 0;
+      break;
+    }
+    const double cost_change = cost - cand_cost;
+    if (std::fabs(cost_change) <= opt->function_tolerance * cost) {
+      record(3);
+      termination = 0;
+      break;
+    }
+    const double relative_decrease = cost_change / model_cost_change;
+    if (relative_decrease > opt->min_relative_decrease) {  // IsStepSuccessful
+      std::swap(d_x, d_cand);
+      cost = cand_cost;
+      x_norm = std::sqrt(cand_x_sq);
+      sum->num_successful_steps++;
+      radius = radius / std::fmax(1.0 / 3.0, 1.0 - std::pow(2.0 * relative_decrease - 1.0, 3));
+      radius = std::fmin(opt->max_trust_region_radius, radius);
+      decrease_factor = 2.0;
+      if ((rc = linearize())) return rc;
+      need_gradient_check = true;
+      record(1);
+    } else {
+      sum->num_unsuccessful_steps++;
+      radius /= decrease_factor;
+      decrease_factor *= 2.0;
+      record(0);
+    }
+    if (radius < opt->min_trust_region_radius) {
+      termination = 0;
+      break;
+    }
+  }
+
+  TMI_HIP(hipMemcpyAsync(x_h.data(), d_x, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
+  TMI_HIP(hipStreamSynchronize(st));
+  T.collect();
+  sum->num_iterations = iter;
+  sum->termination = termination;
+  sum->usable = termination != 2;
+  sum->final_cost = cost;
+  T.write(sum);
+  return TMI_BA_OK;
+}
+
+// What the nonlinear position estimator asks of its arguments beyond check_view_pair_batch, the connection to fixed_view
+// apart; empty: fine.  Nothing is allocated here.
+std::string check_nonlinear_position_arguments(const tmi_ba_view_pair_batch* B,
+                                               const tmi_ba_nonlinear_position_options* o, int fixed_view,
+                                               const double* view_position) {
+  if (B->num_pairs == 0) return "nonlinear positions: no view pair";
+  if (fixed_view < 0 || fixed_view >= B->num_views) return "nonlinear positions: fixed_view out of range";
+  const std::string why = trust_region_options_error(o, "nonlinear positions", " (the reference CHECK_GTs it)");
+  if (!why.empty()) return why;
+  if (o->positions_given && !all_finite(view_position, (size_t)3 * B->num_views))
+    return "nonlinear positions: positions_given with a non-finite position";
+  return std::string();
+}
+
+// Component k of view v of the random start: 100 (2 u - 1), u from word 3 v + k of the splitmix64 stream of `seed`.
+double nonlinear_position_start(uint64_t seed, int v, int k) {
+  uint64_t z = seed + ((uint64_t)3 * (uint64_t)v + (uint64_t)k + 1) * 0x9e3779b97f4a7c15ULL;
+  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ULL;
+  z = (z ^ (z >> 27)) * 0x94d049bb133111ebULL;
+  z ^= z >> 31;
+  const double u = ((double)(z >> 11) + 0.5) * (1.0 / 9007199254740992.0);
+  const double centred = 2.0 * u - 1.0;
+  return 100.0 * centred;
+}
+}  // namespace
+extern "C" {
+
+void tmi_ba_nonlinear_position_options_init(tmi_ba_nonlinear_position_options* o) {
+  if (!o) return;
+  set_trust_region_options(o, ceres_default_lm_args(400, TMI_BA_LOSS_HUBER, 0.1));  // nonlinear_position_estimator.h:70-72
+  o->positions_given = 0;
+  o->seed = 0;
+}
+
+int32_t tmi_ba_estimate_global_positions_nonlinear(const tmi_ba_view_pair_batch* Bh,
+                                                   const tmi_ba_nonlinear_position_options* opt, int32_t fixed_view,
+                                                   int32_t device, double* view_position, double* initial_position,
+                                                   double* iteration_cost, double* iteration_radius,
+                                                   int32_t* iteration_step_accepted, double* pair_residual,
+                                                   tmi_ba_nonlinear_position_summary* sum) {
+  if (!Bh || !opt || !view_position || !sum)
+    return bad_argument("nonlinear positions: null batch, options, view_position or summary");
+  memset(sum, 0, sizeof(*sum));
+  sum->termination = 2;
+  const double t0 = now_s();
+  // argument errors before the device is touched
+  if (const char* why = check_view_pair_batch(Bh, false, Bh->pair_position2)) return bad_argument(why);
+  const std::string why = check_nonlinear_position_arguments(Bh, opt, fixed_view, view_position);
+  if (!why.empty()) return bad_argument(why.c_str());
+  const int V = Bh->num_views, E = Bh->num_pairs, n = V - 1;
+  // the cap before anything of the views' size is allocated, the union-find included
+  if ((int64_t)3 * n > rotation_order_cap()) {
+    g_last_error = "nonlinear positions: 3 (num_views - 1) exceeds the dense solver's cap (see the header)";
+    return TMI_BA_ERR_UNSUPPORTED;
+  }
+  const int N = 3 * n;  // (<= the cap)
+  if (!view_components(V, E, Bh->pair_view1, Bh->pair_view2).all_reach(fixed_view))
+    return bad_argument("nonlinear positions: a view is not connected to fixed_view");
+  const EdgeRows rows = build_edge_rows(V, E, Bh->pair_view1, Bh->pair_view2, fixed_view);
+  // the start: x [n][3] over the free views
+  std::vector<double> start((size_t)3 * V);
+  for (int v = 0; v < V; ++v)
+    for (int k = 0; k < 3; ++k)
+      start[(size_t)3 * v + k] = v == fixed_view ? 0.0
+                                 : opt->positions_given ? view_position[(size_t)3 * v + k]
+                                                        : nonlinear_position_start(opt->seed, v, k);
+  std::vector<double> x_h((size_t)N);
+  gather_free(V, fixed_view, nullptr, start.data(), x_h.data());
+  const double width = opt->robust_loss_width;
+  return one_shot_batch(device, "nonlinear positions: no such device", E, t0, sum, [&](OneShot* s) -> int {
+    int rc;
+    double *d_pos, *d_t, *d_rot = nullptr, *d_rec, *d_res;
+    TMI_HIP(s->upload(&d_pos, Bh->pair_position2, (size_t)3 * E));
+    d_t = d_pos;
+    if (Bh->view_rotation) {
+      TMI_HIP(s->upload(&d_rot, Bh->view_rotation, (size_t)3 * V));
+      TMI_HIP(s->alloc(&d_t, (size_t)3 * E));
+    }
+    PoseGraphDevice graph;
+    if ((rc = graph.upload(s, V, fixed_view, rows, E, Bh->pair_view1, Bh->pair_view2, d_t))) return rc;
+    const PoseGraph& G = graph.G;
+    TMI_HIP(s->alloc(&d_rec, (size_t)9 * E));
+    TMI_HIP(s->alloc(&d_res, (size_t)3 * E));
+    NormalLm L;
+    if ((rc = L.alloc(s, N, E, &sum->num_factorizations))) return rc;
+    hipStream_t st = s->stream;
+    const dim3 edge_grid(L.nbE), view_grid((n + 255) / 256), block(256);
+    // the directions, then the loop
+    if (Bh->view_rotation)
+      hipLaunchKernelGGL(lud_direction_kernel, edge_grid, block, 0, st, E, d_rot, G.pair_view1, d_pos, d_t);
+    rc = normal_lm_solve(
+        s, opt, sum, L, x_h,
+        [&](bool first_scaled) {
+          hipLaunchKernelGGL(nlp_edge_kernel<true>, edge_grid, block, 0, st, G, width, L.x, nullptr, d_rec, d_res,
+                             L.p_cost, nullptr);
+          if (first_scaled)
+            hipLaunchKernelGGL(nlp_scale_kernel<nlp::PositionBlocks>, view_grid, block, 0, st, G, n, d_rec, L.scale);
+          hipLaunchKernelGGL(nlp_assemble_kernel<nlp::PositionBlocks>, dim3(n), block, 0, st, G, N, d_rec, L.scale, L.M,
+                             L.diag, L.g, L.gabs);
+        },
+        [&]() {
+          hipLaunchKernelGGL(nlp_edge_kernel<false>, edge_grid, block, 0, st, G, width, L.cand, L.step, d_rec, nullptr,
+                             L.p_cost, L.p_mcc);
+        });
+    if (rc) return rc;
+    std::vector<double> res_h(pair_residual ? (size_t)3 * E : 0);
+    if (pair_residual) {
+      TMI_HIP(hipMemcpyAsync(res_h.data(), d_res, res_h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+      TMI_HIP(hipStreamSynchronize(st));
+    }
+    // the results, only now: a failure above leaves the caller's arrays as they were
+    scatter_free(V, fixed_view, nullptr, x_h.data(), view_position);
+    std::fill(view_position + (size_t)3 * fixed_view, view_position + (size_t)3 * fixed_view + 3, 0.0);
+    if (initial_position) std::copy(start.begin(), start.end(), initial_position);
+    if (pair_residual) std::copy(res_h.begin(), res_h.end(), pair_residual);
+    if (iteration_cost) std::copy(L.cost_trace.begin(), L.cost_trace.end(), iteration_cost);
+    if (iteration_radius) std::copy(L.radius_trace.begin(), L.radius_trace.end(), iteration_radius);
+    if (iteration_step_accepted) std::copy(L.outcome_trace.begin(), L.outcome_trace.end(), iteration_step_accepted);
+    sum->num_views = V;
+    sum->num_pairs = E;
+    return TMI_BA_OK;
+  });
+}
+
+// ---- NonlinearRotationEstimator (rotation_nonlinear_kernels.h) ----------------------------------
+void tmi_ba_nonlinear_rotation_options_init(tmi_ba_nonlinear_rotation_options* o) {
+  if (!o) return;
+  // nonlinear_rotation_estimator.h (width 0.1), nonlinear_rotation_estimator.cc:94 (200 iterations)
+  set_trust_region_options(o, ceres_default_lm_args(200, TMI_BA_LOSS_SOFTLONE, 0.1));
+  o->fixed_view = -1;
+}
+
+int32_t tmi_ba_estimate_global_rotations_nonlinear(const tmi_ba_view_pair_batch* Bh,
+                                                   const tmi_ba_nonlinear_rotation_options* opt,
+                                                   const uint8_t* view_given, int32_t device, double* view_rotation,
+                                                   double* iteration_cost, double* iteration_radius,
+                                                   int32_t* iteration_step_accepted, double* pair_residual,
+                                                   tmi_ba_nonlinear_rotation_summary* sum) {
+  if (!Bh || !opt || !view_rotation || !sum)
+    return bad_argument("nonlinear rotations: null batch, options, view_rotation or summary");
+  memset(sum, 0, sizeof(*sum));
+  sum->termination = 2;
+  const double t0 = now_s();
+  // argument errors before the device is touched; the batch's own view_rotation is not this call's
+  tmi_ba_view_pair_batch checked = *Bh;
+  checked.view_rotation = nullptr;
+  if (const char* why = check_view_pair_batch(&checked, false, Bh->pair_rotation2)) return bad_argument(why);
+  const int V = Bh->num_views, E_all = Bh->num_pairs, fixed_view = opt->fixed_view;
+  // the reference's two refusals (nonlinear_rotation_estimator.cc:53-62)
+  if (E_all == 0) return bad_argument("nonlinear rotations: no relative rotation constraint");
+  int num_given = 0;
+  for (int v = 0; v < V; ++v) num_given += !view_given || view_given[v];
+  if (num_given == 0) return bad_argument("nonlinear rotations: no view has an initialisation");
+  if (fixed_view < -1 || fixed_view >= V) return bad_argument("nonlinear rotations: fixed_view out of range");
+  if (fixed_view >= 0 && view_given && !view_given[fixed_view])
+    return bad_argument("nonlinear rotations: fixed_view has no initialisation");
+  const std::string why = trust_region_options_error(opt, "nonlinear rotations", "");
+  if (!why.empty()) return bad_argument(why.c_str());
+  for (int v = 0; v < V; ++v)
+    if ((!view_given || view_given[v]) && !all_finite(view_rotation + (size_t)3 * v, 3))
+      return bad_argument("nonlinear rotations: a marked view with a non-finite rotation");
+  // the problem: the edges between marked views in the caller's order, and the marked views with such an edge
+  const ViewSubset P = build_view_subset(V, E_all, Bh->pair_view1, Bh->pair_view2, view_given);
+  const int E = (int)P.edge_of.size(), Vp = (int)P.view_of.size();
+  // the held view's index in the problem; Vp: no view is held
+  const int held = fixed_view >= 0 && P.view_index[fixed_view] >= 0 ? P.view_index[fixed_view] : Vp;
+  const int n = held < Vp ? Vp - 1 : Vp;
+  // the cap before anything of the views' size is allocated
+  if ((int64_t)3 * n > rotation_order_cap()) {
+    g_last_error = "nonlinear rotations: 3 (free views) exceeds the dense solver's cap (see the header)";
+    return TMI_BA_ERR_UNSUPPORTED;
+  }
+  const int N = 3 * n;  // (<= the cap)
+  std::vector<double> rel((size_t)3 * E), x_h((size_t)N), held_h(3, 0.0);
+  for (int e = 0; e < E; ++e)
+    std::copy(Bh->pair_rotation2 + (size_t)3 * P.edge_of[e], Bh->pair_rotation2 + (size_t)3 * P.edge_of[e] + 3,
+              rel.begin() + (size_t)3 * e);
+  gather_free(Vp, held, P.view_of.data(), view_rotation, x_h.data());
+  if (held < Vp) std::copy(view_rotation + (size_t)3 * P.view_of[held], view_rotation + (size_t)3 * P.view_of[held] + 3,
+                           held_h.begin());
+  const EdgeRows rows = build_edge_rows(Vp, E, P.v1.data(), P.v2.data(), held);
+  const double width = opt->robust_loss_width;
+  if (E == 0) {  // an empty problem: solved
+    sum->termination = 0;
+    sum->usable = 1;
+  }
+  return one_shot_batch(device, "nonlinear rotations: no such device", E, t0, sum, [&](OneShot* s) -> int {
+    int rc;  // (an edge has two views, so n >= 1)
+    double *d_rel, *d_held, *d_rec, *d_res;
+    TMI_HIP(s->upload(&d_rel, rel.data(), rel.size()));
+    TMI_HIP(s->upload(&d_held, held_h.data(), held_h.size()));
+    PoseGraphDevice graph;
+    if ((rc = graph.upload(s, Vp, held, rows, E, P.v1.data(), P.v2.data(), d_rel))) return rc;
+    const PoseGraph& G = graph.G;
+    TMI_HIP(s->alloc(&d_rec, (size_t)nlr::kRecordPlanes * E));
+    TMI_HIP(s->alloc(&d_res, (size_t)3 * E));
+    NormalLm L;
+    if ((rc = L.alloc(s, N, E, &sum->num_factorizations))) return rc;
+    hipStream_t st = s->stream;
+    const dim3 edge_grid(L.nbE), view_grid((n + 255) / 256), block(256);
+    rc = normal_lm_solve(
+        s, opt, sum, L, x_h,
+        [&](bool first_scaled) {
+          hipLaunchKernelGGL(nlr_edge_kernel<true>, edge_grid, block, 0, st, G, width, L.x, nullptr, d_held, d_rec,
+                             d_res, L.p_cost, nullptr);
+          if (first_scaled)
+            hipLaunchKernelGGL(nlp_scale_kernel<nlr::RotationBlocks>, view_grid, block, 0, st, G, n, d_rec, L.scale);
+          hipLaunchKernelGGL(nlp_assemble_kernel<nlr::RotationBlocks>, dim3(n), block, 0, st, G, N, d_rec, L.scale, L.M,
+                             L.diag, L.g, L.gabs);
+        },
+        [&]() {
+          hipLaunchKernelGGL(nlr_edge_kernel<false>, edge_grid, block, 0, st, G, width, L.cand, L.step, d_held, d_rec,
+                             nullptr, L.p_cost, L.p_mcc);
+        });
+    if (rc) return rc;
+    std::vector<double> res_h(pair_residual ? (size_t)3 * E : 0);
+    if (pair_residual) {
+      TMI_HIP(hipMemcpyAsync(res_h.data(), d_res, res_h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+      TMI_HIP(hipStreamSynchronize(st));
+    }
+    // the results, only now: a failure above leaves the caller's arrays as they were (the held view's is not written)
+    scatter_free(Vp, held, P.view_of.data(), x_h.data(), view_rotation);
+    if (pair_residual) {
+      std::fill(pair_residual, pair_residual + (size_t)3 * E_all, 0.0);
+      for (int e = 0; e < E; ++e)
+        std::copy(res_h.begin() + (size_t)3 * e, res_h.begin() + (size_t)3 * e + 3, pair_residual + (size_t)3 * P.edge_of[e]);
+    }
+    if (iteration_cost) std::copy(L.cost_trace.begin(), L.cost_trace.end(), iteration_cost);
+    if (iteration_radius) std::copy(L.radius_trace.begin(), L.radius_trace.end(), iteration_radius);
+    if (iteration_step_accepted) std::copy(L.outcome_trace.begin(), L.outcome_trace.end(), iteration_step_accepted);
+    sum->num_views = Vp;
+    sum->num_pairs = E;
+    return TMI_BA_OK;
+  });
+}
+
+// ---- LinearRotationEstimator (rotation_linear_kernels.h) -----------------------------------------
+void tmi_ba_linear_rotation_options_init(tmi_ba_linear_rotation_options* o) {
+  if (!o) return;
+  o->max_iterations = 1000;  // Spectra's maxit and tol, which linear_rotation_estimator.cc:173-177 leaves alone
+  o->tolerance = 1e-10;
+  o->relative_shift = 1e-9;  // 200 x the factorisation's rounding n eps 2 at the order cap
+  o->seed = 0;
+}
+
+int32_t tmi_ba_estimate_global_rotations_linear(const tmi_ba_view_pair_batch* Bh,
+                                                const tmi_ba_linear_rotation_options* opt, int32_t device,
+                                                double* view_rotation, tmi_ba_linear_rotation_summary* sum) {
+  if (!Bh || !opt || !view_rotation || !sum)
+    return bad_argument("linear rotations: null batch, options, view_rotation or summary");
+  memset(sum, 0, sizeof(*sum));
+  const double t0 = now_s();
+  // argument errors before the device is touched; the batch's own view_rotation is not this call's
+  tmi_ba_view_pair_batch checked = *Bh;
+  checked.view_rotation = nullptr;
+  if (const char* why = check_view_pair_batch(&checked, false, Bh->pair_rotation2)) return bad_argument(why);
+  const int V = Bh->num_views, E = Bh->num_pairs;
+  if (E == 0) return bad_argument("linear rotations: no relative rotation constraint (the reference CHECK_GTs them)");
+  if (opt->max_iterations <= 0) return bad_argument("linear rotations: max_iterations is not positive");
+  if (!(opt->tolerance > 0.0) || !std::isfinite(opt->tolerance))
+    return bad_argument("linear rotations: tolerance is not positive and finite");
+  if (!(opt->relative_shift >= 0.0) || !std::isfinite(opt->relative_shift))
+    return bad_argument("linear rotations: relative_shift is negative or not finite");
+  // the views of the problem: those with an edge, in ascending index
+  const ViewSubset P = build_view_subset(V, E, Bh->pair_view1, Bh->pair_view2, nullptr);
+  const int Vp = (int)P.view_of.size();
+  // the cap before anything of the matrix's size is allocated
+  if ((int64_t)3 * Vp > rotation_order_cap()) {
+    g_last_error = "linear rotations: 3 (views with an edge) exceeds the dense solver's cap (see the header)";
+    return TMI_BA_ERR_UNSUPPORTED;
+  }
+  const int n = 3 * Vp;  // (<= the cap)
+  if (view_components(Vp, E, P.v1.data(), P.v2.data()).count != 1)
+    return bad_argument("linear rotations: the view pairs are not connected (with c components the null space has 3 c "
+                        "dimensions; RemoveDisconnectedViewPairs comes first)");
+  const EdgeRows rows = build_edge_rows(Vp, E, P.v1.data(), P.v2.data(), Vp);
+  int max_degree = 0;
+  for (int p = 0; p < Vp; ++p) max_degree = std::max(max_degree, rows.row_ptr[(size_t)p + 1] - rows.row_ptr[p]);
+  const double lambda_bound = 2.0 * (double)max_degree;  // Gershgorin
+  const double mu = opt->relative_shift * (double)max_degree;
+  const double threshold = opt->tolerance * lambda_bound;
+  return one_shot_batch(device, "linear rotations: no such device", E, t0, sum, [&](OneShot* s) -> int {
+    int rc;
+    hipStream_t st = s->stream;
+    const int nb = (n + 255) / 256;
+    const size_t block_words = (size_t)n * lin::kBlock;
+    int* d_refl;
+    double *d_rel, *d_R, *d_Q, *d_Y, *d_Z, *d_W, *d_mgs[2], *d_gram, *d_res[3], *d_rot;
+    TMI_HIP(s->upload(&d_rel, Bh->pair_rotation2, (size_t)3 * E));
+    TMI_HIP(s->alloc(&d_R, (size_t)9 * E));
+    PoseGraphDevice graph;  // no view is held
+    if ((rc = graph.upload(s, Vp, Vp, rows, E, P.v1.data(), P.v2.data(), d_R))) return rc;
+    const PoseGraph& G = graph.G;
+    TMI_HIP(s->alloc(&d_Q, block_words));
+    TMI_HIP(s->alloc(&d_Y, block_words));
+    TMI_HIP(s->alloc(&d_Z, block_words));
+    TMI_HIP(s->alloc(&d_W, block_words));
+    for (double*& p : d_mgs) TMI_HIP(s->alloc(&p, (size_t)nb * lin::kBlock));
+    TMI_HIP(s->alloc(&d_gram, (size_t)nb * lin::kGram));
+    for (double*& p : d_res) TMI_HIP(s->alloc(&p, (size_t)nb));
+    TMI_HIP(s->alloc(&d_rot, (size_t)3 * Vp));
+    TMI_HIP(s->alloc(&d_refl, (size_t)Vp));
+    DenseSpd shifted;  // M + mu I, overwritten by its factor; kBlock right-hand sides
+    if ((rc = shifted.alloc(s, n, lin::kBlock, nullptr))) return rc;
+    ScalarFetch F;  // the small block: its last three words are the sums of the residuals' parts
+    if ((rc = F.alloc(s, shifted.flag, lin::kSmallWords))) return rc;
+    for (int q = 0; q < 3; ++q) F.set(q, d_res[q], nb);
+    double* d_small = F.d_norms;
+    const double* h_small = F.h_norms;
+    const dim3 block(256), rows_grid(nb);
+    sum->num_views = Vp;
+    sum->num_pairs = E;
+    sum->order = n;
+    ClassSeconds T(st);
+    TMI_HIP(T.status());
+
+    // ---- the matrix, its factor and the start block ----
+    TMI_HIP(T.begin(T.kGraph));
+    hipLaunchKernelGGL(lin_edge_matrix_kernel, dim3((E + 255) / 256), block, 0, st, E, d_rel, d_R);
+    hipLaunchKernelGGL(lin_assemble_kernel, dim3(Vp), block, 0, st, G, n, mu, shifted.A);
+    TMI_HIP(T.begin(T.kFactor));
+    shifted.factor(st);
+    TMI_HIP(T.begin(T.kGraph));
+    hipLaunchKernelGGL(lin_start_kernel, dim3(((int)block_words + 255) / 256), block, 0, st, n, (unsigned long long)opt->seed,
+                       d_Q);
+    if ((rc = F.fetch(s, &T, 0))) return rc;  // (no sum yet: the pivot flag alone)
+    if (F.flag()) {  // a pivot of M + mu I that is not positive: nothing is written
+      T.write(sum);
+      return TMI_BA_OK;
+    }
+    sum->usable = 1;
+
+    // ---- subspace iteration with Rayleigh-Ritz ----
+    int iter = 0, launches = 0;
+    bool converged = false;
+    while (iter < opt->max_iterations && !converged) {
+      ++iter;
+      TMI_HIP(T.begin(T.kSubstitution));
+      TMI_HIP(hipMemcpyAsync(d_W, d_Q, block_words * sizeof(double), hipMemcpyDeviceToDevice, st));
+      shifted.substitute<lin::kBlock>(st, d_W, d_Y);
+      TMI_HIP(T.begin(T.kGraph));
+      for (int pass = 0; pass < 2; ++pass)
+        for (int j = 0; j <= lin::kBlock; ++j, ++launches)
+          hipLaunchKernelGGL(lin_mgs_kernel, rows_grid, block, 0, st, n, j, d_Y, d_mgs[(launches + 1) & 1],
+                             d_mgs[launches & 1]);
+      hipLaunchKernelGGL(lin_apply_kernel, dim3((Vp * lin::kBlock + 255) / 256), block, 0, st, G, d_Y, d_Z);
+      hipLaunchKernelGGL(lin_gram_kernel, rows_grid, block, 0, st, n, d_Y, d_Z, d_gram);
+      hipLaunchKernelGGL(lin_ritz_kernel, dim3(1), dim3(64), 0, st, d_gram, nb, d_small);
+      hipLaunchKernelGGL(lin_rotate_kernel, rows_grid, block, 0, st, n, d_small, d_Y, d_Z, d_Q, d_res[0], d_res[1],
+                         d_res[2]);
+      // the whole small block, without the flag: the factor is not touched again
+      if ((rc = F.fetch(s, &T, 3, lin::kSmallResidual, lin::kSmallWords, /*with_flag=*/false))) return rc;
+      converged = true;
+      for (int j = 0; j < 3; ++j) {
+        sum->residual[j] = std::sqrt(h_small[lin::kSmallResidual + j]);
+        converged = converged && sum->residual[j] <= threshold;
+      }
+    }
+    for (int j = 0; j < 4; ++j) sum->eigenvalue[j] = h_small[lin::kSmallTheta + j];
+    sum->num_iterations = iter;
+    sum->converged = converged;
+
+    // ---- the projection of the last Ritz vectors ----
+    std::vector<double> rot_h((size_t)3 * Vp);
+    std::vector<int> refl_h((size_t)Vp);
+    TMI_HIP(T.begin(T.kGraph));
+    hipLaunchKernelGGL(lin_project_kernel, dim3((Vp + 255) / 256), block, 0, st, Vp, d_Q, d_rot, d_refl);
+    TMI_HIP(T.end());
+    TMI_HIP(hipMemcpyAsync(rot_h.data(), d_rot, rot_h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    TMI_HIP(hipMemcpyAsync(refl_h.data(), d_refl, refl_h.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+    const hipError_t le = hipGetLastError();
+    const hipError_t se = hipStreamSynchronize(st);
+    TMI_HIP(le);
+    TMI_HIP(se);
+    T.collect();
+    T.write(sum);
+    // the results, only now: a failure above leaves the caller's array as it was
+    for (int p = 0; p < Vp; ++p) {
+      std::copy(rot_h.begin() + (size_t)3 * p, rot_h.begin() + (size_t)3 * p + 3, view_rotation + (size_t)3 * P.view_of[p]);
+      sum->num_reflected += refl_h[p];
+    }
+    return TMI_BA_OK;
+  });
+}
+
+}  // extern "C"

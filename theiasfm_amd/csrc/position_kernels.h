@@ -23,31 +23,19 @@
 // lud_view_kernel       one thread per free view, one walk of its row in ascending edge index: the position part of the
 //                       three A^T products, the right-hand side of the next solve (q_p with t_e q_s[e] / d_e subtracted at
 //                       view1 and added at view2) and the block's parts of the squared norms (:154, :158-160).
-// Sums over the edges and the views: rot::block_sum and reduce_partials_kernel (rotation_kernels.h), a reduction of fixed
+// Sums over the edges and the views: pg::block_sum and reduce_partials_kernel (pose_graph.h), a reduction of fixed
 // shape.  The edges' and the views' parts of one norm lie side by side in one array and are reduced as one quantity.
 //
-// Every kernel is a plain grid launch; nothing waits on another workgroup.  The loop stays on the host (side_calls.h).
+// Every kernel is a plain grid launch; nothing waits on another workgroup.  The loop stays on the host (pose_graph_calls.h).
 // The arithmetic written here is never contracted into FMA (#pragma clang fp contract(off) in every body), so a CPU
 // model that evaluates the same expressions in the same order sees the same roundings.
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "rotation_kernels.h"
+#include "pose_graph.h"
+#include "track_estimate_kernels.h"
 
 namespace tmi {
-
-struct PositionGraph {
-  int num_views;
-  int num_pairs;
-  int fixed_view;
-  const int* pair_view1;  // [E]
-  const int* pair_view2;
-  const double* t;        // [3 E] the directions in the global frame
-  const int* row_ptr;     // [V + 1] CSR of the undirected graph
-  const int2* row;        // [2 E] (neighbour, edge << 1 | (this view is the edge's view2)), ascending edge index
-  const int* lap_ptr;     // [n + 1] per column: the entries whose neighbour is free
-  const int2* lap_row;    // (neighbour's column, edge), ascending (neighbour, edge)
-};
 
 namespace lud {
 
@@ -62,27 +50,13 @@ __device__ __forceinline__ double load_direction(const double* __restrict__ t, i
   out[0] = t[3 * (size_t)e];
   out[1] = t[3 * (size_t)e + 1];
   out[2] = t[3 * (size_t)e + 2];
-  return rot::sq3(out[0], out[1], out[2]) + 1.0;
+  return pg::sq3(out[0], out[1], out[2]) + 1.0;
 }
 
 // entry (i, j) of W_e
 __device__ __forceinline__ double w_entry(const double t[3], double d, int i, int j) {
 #pragma clang fp contract(off)
   return (i == j ? 1.0 : 0.0) - (t[i] * t[j]) / d;
-}
-
-// One row of the ADMM update (:141-150): b its right-hand side, l1: shrinkage by kappa, otherwise max(., 0).
-__device__ __forceinline__ void admm_row(double ax, double b, bool l1, double alpha, double kappa, double& z, double& u,
-                                         double& dz, double& res) {
-#pragma clang fp contract(off)
-  double ax_hat = alpha * ax;
-  ax_hat += (1.0 - alpha) * (z + b);
-  const double v = (ax_hat - b) + u;
-  const double znew = l1 ? fmax(0.0, v - kappa) - fmax(0.0, -v - kappa) : fmax(v, 0.0);
-  dz = znew - z;
-  u = u + ((ax_hat - znew) - b);
-  res = (ax - znew) - b;
-  z = znew;
 }
 
 }  // namespace lud
@@ -104,7 +78,7 @@ __global__ __launch_bounds__(256) void lud_direction_kernel(int E, const double*
 }
 
 // blockIdx.x = the free view's column c; S is N x N row major, N = 3 n.
-__global__ __launch_bounds__(256) void lud_assemble_kernel(PositionGraph G, int N, double* __restrict__ S) {
+__global__ __launch_bounds__(256) void lud_assemble_kernel(PoseGraph G, int N, double* __restrict__ S) {
 #pragma clang fp contract(off)
   const int c = blockIdx.x;
   double* rows = S + (size_t)3 * c * N;  // rows 3 c .. 3 c + 2 are contiguous
@@ -119,7 +93,7 @@ __global__ __launch_bounds__(256) void lud_assemble_kernel(PositionGraph G, int 
       const int2 nxt = G.lap_row[q];
       if (nxt.x != ent.x) break;
       double t[3];
-      const double d = lud::load_direction(G.t, nxt.y, t);
+      const double d = lud::load_direction(G.edge_value, nxt.y, t);
 #pragma unroll
       for (int i = 0; i < 3; ++i)
 #pragma unroll
@@ -132,11 +106,11 @@ __global__ __launch_bounds__(256) void lud_assemble_kernel(PositionGraph G, int 
   }
   if (threadIdx.x < 9) {
     const int i = threadIdx.x / 3, j = threadIdx.x - 3 * i;
-    const int v = rot::view_of(c, G.fixed_view);
+    const int v = pg::view_of(c, G.fixed_view);
     double sum = 0.0;
     for (int r = G.row_ptr[v]; r < G.row_ptr[v + 1]; ++r) {
       double t[3];
-      const double d = lud::load_direction(G.t, G.row[r].y >> 1, t);
+      const double d = lud::load_direction(G.edge_value, G.row[r].y >> 1, t);
       const double ti = i == 0 ? t[0] : (i == 1 ? t[1] : t[2]), tj = j == 0 ? t[0] : (j == 1 ? t[1] : t[2]);
       sum += (i == j ? 1.0 : 0.0) - (ti * tj) / d;  // (lud::w_entry on selects: a dynamic index would go to scratch)
     }
@@ -148,7 +122,7 @@ __global__ __launch_bounds__(256) void lud_assemble_kernel(PositionGraph G, int 
 // ones); z, u, dz [4 E]: rows 3 e + k, then 3 E + e.  scale [E] = s_e and ax [3 E] = the L1 rows of A x are the call's
 // outputs after the last iteration.  part_s / part_t: the blocks' parts of the scale entries of |-rho A^T dz|^2 and
 // |rho A^T u|^2.
-__global__ __launch_bounds__(256) void lud_edge_kernel(PositionGraph G, double rho, double alpha,
+__global__ __launch_bounds__(256) void lud_edge_kernel(PoseGraph G, double rho, double alpha,
                                                        const double* __restrict__ p, double* __restrict__ qs,
                                                        double* __restrict__ z, double* __restrict__ u,
                                                        double* __restrict__ dz, double* __restrict__ scale,
@@ -161,10 +135,10 @@ __global__ __launch_bounds__(256) void lud_edge_kernel(PositionGraph G, double r
   const int E = G.num_pairs;
   double rr = 0.0, aa = 0.0, zz = 0.0, ss = 0.0, tt = 0.0;
   if (e < E) {
-    const int c1 = rot::column_of(G.pair_view1[e], G.fixed_view), c2 = rot::column_of(G.pair_view2[e], G.fixed_view);
+    const int c1 = pg::column_of(G.pair_view1[e], G.fixed_view), c2 = pg::column_of(G.pair_view2[e], G.fixed_view);
     const double kappa = 1.0 / rho;
     double t[3], dp[3];
-    const double d = lud::load_direction(G.t, e, t);
+    const double d = lud::load_direction(G.edge_value, e, t);
 #pragma unroll
     for (int k = 0; k < 3; ++k) dp[k] = (c2 >= 0 ? p[3 * c2 + k] : 0.0) - (c1 >= 0 ? p[3 * c1 + k] : 0.0);
     const double s = (qs[e] + lud::dot3(t, dp)) / d;
@@ -175,7 +149,7 @@ __global__ __launch_bounds__(256) void lud_edge_kernel(PositionGraph G, double r
       axv[k] = dp[k] - s * t[k];
       zn[k] = z[i];
       un[k] = u[i];
-      lud::admm_row(axv[k], 0.0, true, alpha, kappa, zn[k], un[k], dzn[k], res[k]);
+      pg::admm_row(axv[k], 0.0, true, alpha, kappa, zn[k], un[k], dzn[k], res[k]);
       z[i] = zn[k];
       u[i] = un[k];
       dz[i] = dzn[k];
@@ -184,24 +158,24 @@ __global__ __launch_bounds__(256) void lud_edge_kernel(PositionGraph G, double r
     }
     const size_t i = 3 * (size_t)E + e;
     double zs = z[i], us = u[i], dzs, ress;
-    lud::admm_row(s, 1.0, false, alpha, kappa, zs, us, dzs, ress);
+    pg::admm_row(s, 1.0, false, alpha, kappa, zs, us, dzs, ress);
     z[i] = zs;
     u[i] = us;
     dz[i] = dzs;
     scale[e] = s;
     qs[e] = ((1.0 + zs) - us) - lud::dot3(t, y);
     const double sd = -rho * (dzs - lud::dot3(t, dzn)), su = rho * (us - lud::dot3(t, un));
-    rr = rot::sq3(res[0], res[1], res[2]) + ress * ress;
-    aa = rot::sq3(axv[0], axv[1], axv[2]) + s * s;
-    zz = rot::sq3(zn[0], zn[1], zn[2]) + zs * zs;
+    rr = pg::sq3(res[0], res[1], res[2]) + ress * ress;
+    aa = pg::sq3(axv[0], axv[1], axv[2]) + s * s;
+    zz = pg::sq3(zn[0], zn[1], zn[2]) + zs * zs;
     ss = sd * sd;
     tt = su * su;
   }
-  const double r_total = rot::block_sum(rr, part);
-  const double a_total = rot::block_sum(aa, part);
-  const double z_total = rot::block_sum(zz, part);
-  const double s_total = rot::block_sum(ss, part);
-  const double t_total = rot::block_sum(tt, part);
+  const double r_total = pg::block_sum(rr, part);
+  const double a_total = pg::block_sum(aa, part);
+  const double z_total = pg::block_sum(zz, part);
+  const double s_total = pg::block_sum(ss, part);
+  const double t_total = pg::block_sum(tt, part);
   if (threadIdx.x == 0) {
     part_r[blockIdx.x] = r_total;
     part_ax[blockIdx.x] = a_total;
@@ -213,7 +187,7 @@ __global__ __launch_bounds__(256) void lud_edge_kernel(PositionGraph G, double r
 
 // rhs [n][3] = the position part of A^T (b + z - u) with t_e q_s[e] / d_e subtracted at view1 and added at view2;
 // part_s / part_t: the blocks' parts of the position entries of |-rho A^T dz|^2 and |rho A^T u|^2.
-__global__ __launch_bounds__(256) void lud_view_kernel(PositionGraph G, int n, double rho, const double* __restrict__ qs,
+__global__ __launch_bounds__(256) void lud_view_kernel(PoseGraph G, int n, double rho, const double* __restrict__ qs,
                                                        const double* __restrict__ z, const double* __restrict__ u,
                                                        const double* __restrict__ dz, double* __restrict__ rhs,
                                                        double* __restrict__ part_s, double* __restrict__ part_t) {
@@ -222,7 +196,7 @@ __global__ __launch_bounds__(256) void lud_view_kernel(PositionGraph G, int n, d
   const int c = blockIdx.x * 256 + threadIdx.x;
   double ss = 0.0, tt = 0.0;
   if (c < n) {
-    const int v = rot::view_of(c, G.fixed_view);
+    const int v = pg::view_of(c, G.fixed_view);
     double acc[3] = {0.0, 0.0, 0.0}, sch[3] = {0.0, 0.0, 0.0}, as[3] = {0.0, 0.0, 0.0}, at[3] = {0.0, 0.0, 0.0};
     const int r0 = G.row_ptr[v], r1 = G.row_ptr[v + 1];
     for (int r = r0; r < r1; ++r) {
@@ -231,7 +205,7 @@ __global__ __launch_bounds__(256) void lud_view_kernel(PositionGraph G, int n, d
       const size_t e3 = 3 * (size_t)e;
       const double sign = (code & 1) ? 1.0 : -1.0;
       double t[3];
-      const double d = lud::load_direction(G.t, e, t);
+      const double d = lud::load_direction(G.edge_value, e, t);
       const double g = qs[e] / d;
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
@@ -248,11 +222,11 @@ __global__ __launch_bounds__(256) void lud_view_kernel(PositionGraph G, int n, d
       as[k] = -rho * as[k];
       at[k] = rho * at[k];
     }
-    ss = rot::sq3(as[0], as[1], as[2]);
-    tt = rot::sq3(at[0], at[1], at[2]);
+    ss = pg::sq3(as[0], as[1], as[2]);
+    tt = pg::sq3(at[0], at[1], at[2]);
   }
-  const double s_total = rot::block_sum(ss, part);
-  const double t_total = rot::block_sum(tt, part);
+  const double s_total = pg::block_sum(ss, part);
+  const double t_total = pg::block_sum(tt, part);
   if (threadIdx.x == 0) {
     part_s[blockIdx.x] = s_total;
     part_t[blockIdx.x] = t_total;

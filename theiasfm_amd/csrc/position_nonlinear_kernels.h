@@ -1,5 +1,5 @@
 // theia::NonlinearPositionEstimator (nonlinear_position_estimator.cc:86-214; Wilson and Snavely, ECCV 2014) on the view
-// table and edge list of the LUD estimator (PositionGraph, position_kernels.h): camera positions from global
+// table and edge list of the LUD estimator (PoseGraph, pose_graph.h): camera positions from global
 // orientations and relative translation directions by Levenberg-Marquardt on r_e = d / |d| - t_e, d = p[view2] - p[view1]
 // (pairwise_translation_error.h:63-88), under HuberLoss with Ceres' corrector.
 //
@@ -8,7 +8,7 @@
 // (00, 01, 02, 11, 12, 22) and q_e = J~^T r~ -- with J~ and r~ the corrected Jacobian with respect to p[view2] and the
 // corrected residual; the Jacobian with respect to p[view1] is -J~.  The normal matrix M of order N = 3 n (row major,
 // lower triangle) has +B_e in the diagonal blocks of both views and -B_e in block (view1, view2); the gradient has +q_e
-// at view2 and -q_e at view1.  M is kept; every factorisation works on a damped copy (side_calls.h).
+// at view2 and -q_e at view1.  M is kept; every factorisation works on a damped copy (pose_graph_calls.h).
 //
 // nlp_edge_kernel<true>   one thread per edge: residual, both norm branches, both Huber branches, the record, the
 //                         residual itself (an output of the call) and the block's part of the cost.
@@ -30,18 +30,19 @@
 // nlp_step_kernel         one thread per entry: step = -(scale y), candidate = x + step, the block's parts of |step|^2
 //                         and |candidate|^2.
 // nlp_absmax_kernel       one workgroup: max |unscaled gradient| (a maximum does not depend on the order).
-// Sums: rot::block_sum and reduce_partials_kernel (rotation_kernels.h), a reduction of fixed shape.
+// Sums: pg::block_sum and reduce_partials_kernel (pose_graph.h), a reduction of fixed shape.
 // nlp_scale_kernel and nlp_assemble_kernel are templates on a policy that says where an edge's record holds the entries
 // of the blocks and of the gradient (nlp::PositionBlocks here: the walks, the orders and the arithmetic above); the
 // nonlinear rotation estimator instantiates them, and uses the other kernels as they are, with nlr::RotationBlocks
 // (rotation_nonlinear_kernels.h).  G.fixed_view = G.num_views means that no view is fixed (that estimator's case).
 //
 // Every kernel is a plain grid launch; nothing waits on another workgroup and no atomic is used.  The loop stays on the
-// host (side_calls.h).  The arithmetic written here is never contracted into FMA (#pragma clang fp contract(off) in every
+// host (pose_graph_calls.h).  The arithmetic written here is never contracted into FMA (#pragma clang fp contract(off) in every
 // body), so a CPU model that evaluates the same expressions in the same order sees the same roundings.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "pose_graph.h"
 #include "position_kernels.h"
 
 namespace tmi {
@@ -59,13 +60,13 @@ __device__ __forceinline__ double evaluate(const double p1[3], const double p2[3
                                            double r[3], double rt[3], double Jt[6]) {
 #pragma clang fp contract(off)
   const double d[3] = {p2[0] - p1[0], p2[1] - p1[1], p2[2] - p1[2]};
-  double norm = sqrt(rot::sq3(d[0], d[1], d[2]));
+  double norm = sqrt(pg::sq3(d[0], d[1], d[2]));
   const bool small = norm < 1e-12;
   if (small) norm = 1.0;
   const double u[3] = {d[0] / norm, d[1] / norm, d[2] / norm};
 #pragma unroll
   for (int k = 0; k < 3; ++k) r[k] = u[k] - t[k];
-  const double sq = rot::sq3(r[0], r[1], r[2]);
+  const double sq = pg::sq3(r[0], r[1], r[2]);
   double rho[3];
   loss_eval(1, width, sq, rho);
   // Ceres' corrector (corrector.cc) where |r|^2 = 0 or rho'' <= 0: sqrt(rho') on the residual and on the Jacobian.
@@ -85,7 +86,7 @@ __device__ __forceinline__ double evaluate(const double p1[3], const double p2[3
 
 // the position of view v in x [n][3]; the fixed view is at 0
 __device__ __forceinline__ void load_position(const double* __restrict__ x, int v, int fixed, double p[3]) {
-  const int c = rot::column_of(v, fixed);
+  const int c = pg::column_of(v, fixed);
 #pragma unroll
   for (int k = 0; k < 3; ++k) p[k] = c >= 0 ? x[3 * c + k] : 0.0;
 }
@@ -117,7 +118,7 @@ struct PositionBlocks {
 // RECORDS: x the point of the linearisation; rec [9][E], residual [3 E] and part_cost are written.
 // otherwise: x the candidate, step [n][3] what led to it; part_cost and part_mcc are written, rec is read.
 template <bool RECORDS>
-__global__ __launch_bounds__(256) void nlp_edge_kernel(PositionGraph G, double width, const double* __restrict__ x,
+__global__ __launch_bounds__(256) void nlp_edge_kernel(PoseGraph G, double width, const double* __restrict__ x,
                                                        const double* __restrict__ step, double* __restrict__ rec,
                                                        double* __restrict__ residual, double* __restrict__ part_cost,
                                                        double* __restrict__ part_mcc) {
@@ -131,7 +132,7 @@ __global__ __launch_bounds__(256) void nlp_edge_kernel(PositionGraph G, double w
     double p1[3], p2[3], t[3], r[3], rt[3], Jt[6];
     nlp::load_position(x, v1, G.fixed_view, p1);
     nlp::load_position(x, v2, G.fixed_view, p2);
-    lud::load_direction(G.t, e, t);
+    lud::load_direction(G.edge_value, e, t);
     cost = 0.5 * nlp::evaluate(p1, p2, t, width, r, rt, Jt);
     if (RECORDS) {
       // B = Jt^T Jt and q = Jt^T rt, Jt symmetric: rows (0 1 2), (1 3 4), (2 4 5)
@@ -159,22 +160,22 @@ __global__ __launch_bounds__(256) void nlp_edge_kernel(PositionGraph G, double w
       mcc = -(lud::dot3(sd, q) + 0.5 * lud::dot3(sd, Bs));
     }
   }
-  const double cost_total = rot::block_sum(cost, part);
+  const double cost_total = pg::block_sum(cost, part);
   if (threadIdx.x == 0) part_cost[blockIdx.x] = cost_total;
   if (!RECORDS) {
-    const double mcc_total = rot::block_sum(mcc, part);
+    const double mcc_total = pg::block_sum(mcc, part);
     if (threadIdx.x == 0) part_mcc[blockIdx.x] = mcc_total;
   }
 }
 
 template <class Blocks>
-__global__ __launch_bounds__(256) void nlp_scale_kernel(PositionGraph G, int n, const double* __restrict__ rec,
+__global__ __launch_bounds__(256) void nlp_scale_kernel(PoseGraph G, int n, const double* __restrict__ rec,
                                                         double* __restrict__ scale) {
 #pragma clang fp contract(off)
   const int c = blockIdx.x * 256 + threadIdx.x;
   if (c >= n) return;
   const size_t E = (size_t)G.num_pairs;
-  const int v = rot::view_of(c, G.fixed_view);
+  const int v = pg::view_of(c, G.fixed_view);
   double d0 = 0.0, d1 = 0.0, d2 = 0.0;
   for (int r = G.row_ptr[v]; r < G.row_ptr[v + 1]; ++r) {
     const int code = G.row[r].y;
@@ -191,7 +192,7 @@ __global__ __launch_bounds__(256) void nlp_scale_kernel(PositionGraph G, int n, 
 // blockIdx.x = the free view's column c; M is N x N row major, N = 3 n.  diag [N]: the scaled diagonal of M; g [N]: the
 // scaled gradient; gabs [N]: |the unscaled gradient|.
 template <class Blocks>
-__global__ __launch_bounds__(256) void nlp_assemble_kernel(PositionGraph G, int N, const double* __restrict__ rec,
+__global__ __launch_bounds__(256) void nlp_assemble_kernel(PoseGraph G, int N, const double* __restrict__ rec,
                                                            const double* __restrict__ scale, double* __restrict__ M,
                                                            double* __restrict__ diag, double* __restrict__ g,
                                                            double* __restrict__ gabs) {
@@ -210,7 +211,7 @@ __global__ __launch_bounds__(256) void nlp_assemble_kernel(PositionGraph G, int 
     const int2 ent = G.lap_row[r];
     if (ent.x >= c) continue;                              // the other triangle
     if (r > r0 && G.lap_row[r - 1].x == ent.x) continue;  // not the first of its neighbour's run
-    const int row_view = rot::view_of(c, G.fixed_view);
+    const int row_view = pg::view_of(c, G.fixed_view);
     double sum[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     for (int q = r; q < r1; ++q) {
       const int2 nxt = G.lap_row[q];
@@ -228,7 +229,7 @@ __global__ __launch_bounds__(256) void nlp_assemble_kernel(PositionGraph G, int 
         rows[(size_t)i * N + 3 * ent.x + j] = Blocks::finish_off((sum[3 * i + j] * scale[3 * c + i]) * scale[3 * ent.x + j]);
   }
   if (threadIdx.x < 9) {
-    const int v = rot::view_of(c, G.fixed_view);
+    const int v = pg::view_of(c, G.fixed_view);
     const int row_begin = G.row_ptr[v], row_end = G.row_ptr[v + 1];
     if (threadIdx.x < 6) {
       // the lower triangle of the diagonal block: (0,0) (1,0) (1,1) (2,0) (2,1) (2,2)
@@ -287,8 +288,8 @@ __global__ __launch_bounds__(256) void nlp_step_kernel(int N, const double* __re
     ss = s * s;
     xx = xc * xc;
   }
-  const double s_total = rot::block_sum(ss, part);
-  const double x_total = rot::block_sum(xx, part);
+  const double s_total = pg::block_sum(ss, part);
+  const double x_total = pg::block_sum(xx, part);
   if (threadIdx.x == 0) {
     part_step[blockIdx.x] = s_total;
     part_x[blockIdx.x] = x_total;

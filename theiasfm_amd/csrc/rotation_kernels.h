@@ -25,40 +25,22 @@
 // admm_edge_kernel           one thread per edge: A x, the z and u updates (:147-156), z - z_old, and the blocks'
 //                            parts of |A x - z - b|^2, |A x|^2 and |z|^2 (:159, :162-163).
 // irls_rhs_kernel            one thread per free view: A^T W r and the view's weight sum (:206-216).
-// reduce_partials_kernel     one workgroup per quantity: thread t adds the block parts t, t + 256, ... in ascending
-//                            order, then a binary LDS tree -- with the tree inside every block (rot::block_sum) a
-//                            reduction of fixed shape, the same bits on every run (as translation_moments_kernel).
+// The graph (PoseGraph), the sums (pg::block_sum, reduce_partials_kernel) and the ADMM row update (pg::admm_row) are
+// pose_graph.h's.
 //
-// Every kernel is a plain grid launch; nothing waits on another workgroup.  The loops stay on the host (side_calls.h).
+// Every kernel is a plain grid launch; nothing waits on another workgroup.  The loops stay on the host
+// (pose_graph_calls.h).
 // The arithmetic written here is never contracted into FMA (#pragma clang fp contract(off) in every body), so a CPU
 // model that evaluates the same expressions in the same order sees the same roundings.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "pose_graph.h"
 #include "track_estimate_kernels.h"
 
 namespace tmi {
 
 constexpr int kRotationMaxOrder = 11000;  // n = V - 1: the dense matrix is 8 n^2 bytes = 968 MB
-constexpr int kRotationMaxJobs = 5;       // quantities of one reduce_partials_kernel launch
-
-struct RotationGraph {
-  int num_views;
-  int num_pairs;
-  int fixed_view;
-  const int* pair_view1;   // [E]
-  const int* pair_view2;
-  const double* relative;  // [3 E] TwoViewInfo::rotation_2
-  const int* row_ptr;      // [V + 1] CSR of the undirected graph
-  const int2* row;         // [2 E] (neighbour, edge << 1 | (this view is the edge's view2)), ascending edge index
-  const int* lap_ptr;      // [n + 1] per column: the entries whose neighbour is free
-  const int2* lap_row;     // (neighbour's column, edge), ascending (neighbour, edge)
-};
-
-struct ReduceJobs {
-  const double* part[kRotationMaxJobs];
-  int count[kRotationMaxJobs];
-};
 
 namespace rot {
 
@@ -128,34 +110,9 @@ __device__ __forceinline__ void multiply_rotations(const double a[3], const doub
   rotation_matrix_to_angle_axis(P, out);
 }
 
-// the sum of v over the 256 threads of the workgroup by a binary tree in LDS; valid in thread 0
-__device__ __forceinline__ double block_sum(double v, double* part) {
-#pragma clang fp contract(off)
-  const int tid = threadIdx.x;
-  part[tid] = v;
-  __syncthreads();
-  for (int half = 128; half > 0; half >>= 1) {
-    if (tid < half) part[tid] += part[tid + half];
-    __syncthreads();
-  }
-  const double total = part[0];
-  __syncthreads();  // (part is reused by the next sum)
-  return total;
-}
-
-__device__ __forceinline__ double sq3(double x, double y, double z) {
-#pragma clang fp contract(off)
-  return (x * x + y * y) + z * z;
-}
-
-// the view of column c
-__device__ __forceinline__ int view_of(int c, int fixed) { return c + (c >= fixed); }
-// the column of view v (-1: the fixed view)
-__device__ __forceinline__ int column_of(int v, int fixed) { return v == fixed ? -1 : v - (v > fixed); }
-
 }  // namespace rot
 
-__global__ __launch_bounds__(256) void rotation_residual_kernel(RotationGraph G, const double* __restrict__ o,
+__global__ __launch_bounds__(256) void rotation_residual_kernel(PoseGraph G, const double* __restrict__ o,
                                                                 double sigma, double* __restrict__ r,
                                                                 double* __restrict__ w, double* __restrict__ part_rr) {
 #pragma clang fp contract(off)
@@ -166,18 +123,18 @@ __global__ __launch_bounds__(256) void rotation_residual_kernel(RotationGraph G,
     const int a = G.pair_view1[e], b = G.pair_view2[e];
     const double o1[3] = {o[3 * a], o[3 * a + 1], o[3 * a + 2]};
     const double m2[3] = {-o[3 * b], -o[3 * b + 1], -o[3 * b + 2]};
-    const double rel[3] = {G.relative[3 * (size_t)e], G.relative[3 * (size_t)e + 1], G.relative[3 * (size_t)e + 2]};
+    const double rel[3] = {G.edge_value[3 * (size_t)e], G.edge_value[3 * (size_t)e + 1], G.edge_value[3 * (size_t)e + 2]};
     double t[3], res[3];
     rot::multiply_rotations(rel, o1, t);
     rot::multiply_rotations(m2, t, res);
     r[3 * (size_t)e] = res[0];
     r[3 * (size_t)e + 1] = res[1];
     r[3 * (size_t)e + 2] = res[2];
-    sq = rot::sq3(res[0], res[1], res[2]);
+    sq = pg::sq3(res[0], res[1], res[2]);
     const double d = sq + sigma * sigma;
     w[e] = sigma / (d * d);
   }
-  const double total = rot::block_sum(sq, part);
+  const double total = pg::block_sum(sq, part);
   if (threadIdx.x == 0) part_rr[blockIdx.x] = total;
 }
 
@@ -188,7 +145,7 @@ __global__ __launch_bounds__(256) void rotation_update_kernel(int n, int fixed, 
   const int c = blockIdx.x * 256 + threadIdx.x;
   double len = 0.0;
   if (c < n) {
-    const int v = rot::view_of(c, fixed);
+    const int v = pg::view_of(c, fixed);
     const double cur[3] = {o[3 * v], o[3 * v + 1], o[3 * v + 2]};
     const double s[3] = {step[3 * c], step[3 * c + 1], step[3 * c + 2]};
     double next[3];
@@ -196,14 +153,14 @@ __global__ __launch_bounds__(256) void rotation_update_kernel(int n, int fixed, 
     o[3 * v] = next[0];
     o[3 * v + 1] = next[1];
     o[3 * v + 2] = next[2];
-    len = sqrt(rot::sq3(s[0], s[1], s[2]));
+    len = sqrt(pg::sq3(s[0], s[1], s[2]));
   }
-  const double total = rot::block_sum(len, part);
+  const double total = pg::block_sum(len, part);
   if (threadIdx.x == 0) part_step[blockIdx.x] = total;
 }
 
 // blockIdx.x = the row (column index c).  w null: unit weights; diag null: the degree.
-__global__ __launch_bounds__(256) void laplacian_assemble_kernel(RotationGraph G, int n, const double* __restrict__ w,
+__global__ __launch_bounds__(256) void laplacian_assemble_kernel(PoseGraph G, int n, const double* __restrict__ w,
                                                                  const double* __restrict__ diag,
                                                                  double* __restrict__ A) {
 #pragma clang fp contract(off)
@@ -224,13 +181,13 @@ __global__ __launch_bounds__(256) void laplacian_assemble_kernel(RotationGraph G
     row[ent.x] = -sum;  // (ent.x != c: no view pairs with itself; one thread per neighbour)
   }
   if (threadIdx.x == 0) {
-    const int v = rot::view_of(c, G.fixed_view);
+    const int v = pg::view_of(c, G.fixed_view);
     row[c] = diag ? diag[c] : (double)(G.row_ptr[v + 1] - G.row_ptr[v]);
   }
 }
 
 // rhs [n][3] = A^T (b + z - u); part_s / part_t: the blocks' parts of |-rho A^T dz|^2 and |rho A^T u|^2
-__global__ __launch_bounds__(256) void admm_view_kernel(RotationGraph G, int n, double rho, const double* __restrict__ b,
+__global__ __launch_bounds__(256) void admm_view_kernel(PoseGraph G, int n, double rho, const double* __restrict__ b,
                                                         const double* __restrict__ z, const double* __restrict__ u,
                                                         const double* __restrict__ dz, double* __restrict__ rhs,
                                                         double* __restrict__ part_s, double* __restrict__ part_t) {
@@ -239,7 +196,7 @@ __global__ __launch_bounds__(256) void admm_view_kernel(RotationGraph G, int n, 
   const int c = blockIdx.x * 256 + threadIdx.x;
   double ss = 0.0, tt = 0.0;
   if (c < n) {
-    const int v = rot::view_of(c, G.fixed_view);
+    const int v = pg::view_of(c, G.fixed_view);
     double acc[3] = {0.0, 0.0, 0.0}, as[3] = {0.0, 0.0, 0.0}, at[3] = {0.0, 0.0, 0.0};
     const int r0 = G.row_ptr[v], r1 = G.row_ptr[v + 1];
     for (int r = r0; r < r1; ++r) {
@@ -260,11 +217,11 @@ __global__ __launch_bounds__(256) void admm_view_kernel(RotationGraph G, int n, 
       as[k] = -rho * as[k];
       at[k] = rho * at[k];
     }
-    ss = rot::sq3(as[0], as[1], as[2]);
-    tt = rot::sq3(at[0], at[1], at[2]);
+    ss = pg::sq3(as[0], as[1], as[2]);
+    tt = pg::sq3(at[0], at[1], at[2]);
   }
-  const double s_total = rot::block_sum(ss, part);
-  const double t_total = rot::block_sum(tt, part);
+  const double s_total = pg::block_sum(ss, part);
+  const double t_total = pg::block_sum(tt, part);
   if (threadIdx.x == 0) {
     part_s[blockIdx.x] = s_total;
     part_t[blockIdx.x] = t_total;
@@ -272,7 +229,7 @@ __global__ __launch_bounds__(256) void admm_view_kernel(RotationGraph G, int n, 
 }
 
 // l1_solver.h:147-163 with the shrinkage by 1 / rho
-__global__ __launch_bounds__(256) void admm_edge_kernel(RotationGraph G, double rho, double alpha,
+__global__ __launch_bounds__(256) void admm_edge_kernel(PoseGraph G, double rho, double alpha,
                                                         const double* __restrict__ x, const double* __restrict__ b,
                                                         double* __restrict__ z, double* __restrict__ u,
                                                         double* __restrict__ dz, double* __restrict__ part_r,
@@ -282,7 +239,7 @@ __global__ __launch_bounds__(256) void admm_edge_kernel(RotationGraph G, double 
   const int e = blockIdx.x * 256 + threadIdx.x;
   double rr = 0.0, aa = 0.0, zz = 0.0;
   if (e < G.num_pairs) {
-    const int c1 = rot::column_of(G.pair_view1[e], G.fixed_view), c2 = rot::column_of(G.pair_view2[e], G.fixed_view);
+    const int c1 = pg::column_of(G.pair_view1[e], G.fixed_view), c2 = pg::column_of(G.pair_view2[e], G.fixed_view);
     const double kappa = 1.0 / rho;
     double res[3], axv[3], zn[3];
 #pragma unroll
@@ -290,25 +247,21 @@ __global__ __launch_bounds__(256) void admm_edge_kernel(RotationGraph G, double 
       const size_t i = 3 * (size_t)e + k;
       const double x1 = c1 >= 0 ? x[3 * c1 + k] : 0.0, x2 = c2 >= 0 ? x[3 * c2 + k] : 0.0;
       const double ax = x2 - x1;
-      const double bb = b[i], zo = z[i], uo = u[i];
-      double ax_hat = alpha * ax;
-      ax_hat += (1.0 - alpha) * (zo + bb);
-      const double v = (ax_hat - bb) + uo;
-      const double znew = fmax(0.0, v - kappa) - fmax(0.0, -v - kappa);
-      z[i] = znew;
-      dz[i] = znew - zo;
-      u[i] = uo + ((ax_hat - znew) - bb);
-      res[k] = (ax - znew) - bb;
+      double zk = z[i], uk = u[i], dzk;
+      pg::admm_row(ax, b[i], /*l1=*/true, alpha, kappa, zk, uk, dzk, res[k]);
+      z[i] = zk;
+      dz[i] = dzk;
+      u[i] = uk;
       axv[k] = ax;
-      zn[k] = znew;
+      zn[k] = zk;
     }
-    rr = rot::sq3(res[0], res[1], res[2]);
-    aa = rot::sq3(axv[0], axv[1], axv[2]);
-    zz = rot::sq3(zn[0], zn[1], zn[2]);
+    rr = pg::sq3(res[0], res[1], res[2]);
+    aa = pg::sq3(axv[0], axv[1], axv[2]);
+    zz = pg::sq3(zn[0], zn[1], zn[2]);
   }
-  const double r_total = rot::block_sum(rr, part);
-  const double a_total = rot::block_sum(aa, part);
-  const double z_total = rot::block_sum(zz, part);
+  const double r_total = pg::block_sum(rr, part);
+  const double a_total = pg::block_sum(aa, part);
+  const double z_total = pg::block_sum(zz, part);
   if (threadIdx.x == 0) {
     part_r[blockIdx.x] = r_total;
     part_ax[blockIdx.x] = a_total;
@@ -317,13 +270,13 @@ __global__ __launch_bounds__(256) void admm_edge_kernel(RotationGraph G, double 
 }
 
 // rhs [n][3] = A^T W r, diag [n] = the view's weight sum, both in ascending edge index
-__global__ __launch_bounds__(256) void irls_rhs_kernel(RotationGraph G, int n, const double* __restrict__ w,
+__global__ __launch_bounds__(256) void irls_rhs_kernel(PoseGraph G, int n, const double* __restrict__ w,
                                                        const double* __restrict__ r, double* __restrict__ rhs,
                                                        double* __restrict__ diag) {
 #pragma clang fp contract(off)
   const int c = blockIdx.x * 256 + threadIdx.x;
   if (c >= n) return;
-  const int v = rot::view_of(c, G.fixed_view);
+  const int v = pg::view_of(c, G.fixed_view);
   double acc[3] = {0.0, 0.0, 0.0}, d = 0.0;
   const int r0 = G.row_ptr[v], r1 = G.row_ptr[v + 1];
   for (int q = r0; q < r1; ++q) {
@@ -338,25 +291,6 @@ __global__ __launch_bounds__(256) void irls_rhs_kernel(RotationGraph G, int n, c
 #pragma unroll
   for (int k = 0; k < 3; ++k) rhs[3 * c + k] = acc[k];
   diag[c] = d;
-}
-
-// blockIdx.x = the quantity: out[q] = the sum of jobs.part[q][0 .. jobs.count[q])
-__global__ __launch_bounds__(256) void reduce_partials_kernel(ReduceJobs jobs, double* __restrict__ out) {
-#pragma clang fp contract(off)
-  __shared__ double part[256];
-  const int q = blockIdx.x;
-  const double* p = jobs.part[0];
-  int count = jobs.count[0];
-#pragma unroll
-  for (int j = 1; j < kRotationMaxJobs; ++j)  // (selects: a dynamic index into the argument would go to scratch)
-    if (q == j) {
-      p = jobs.part[j];
-      count = jobs.count[j];
-    }
-  double acc = 0.0;
-  for (int i = threadIdx.x; i < count; i += 256) acc += p[i];
-  const double total = rot::block_sum(acc, part);
-  if (threadIdx.x == 0) out[q] = total;
 }
 
 }  // namespace tmi

@@ -31,11 +31,13 @@
 //                         a one-sided Jacobi SVD (Hestenes), negated where the determinant is negative
 //                         (ProjectToRotationMatrix, pose/util.cc:121-133), then RotationMatrixToAngleAxis
 //
-// Every kernel is a plain grid launch, nothing waits on another workgroup, the loop is the host's.  No FMA contraction,
+// Every kernel is a plain grid launch, nothing waits on another workgroup, the loop is the host's
+// (pose_graph_calls.h; the graph is pose_graph.h's PoseGraph with no view held).  No FMA contraction,
 // no atomics, every sum of fixed shape: the same bits from call to call.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "pose_graph.h"
 #include "ransac_core.h"
 #include "rotation_kernels.h"
 
@@ -48,14 +50,6 @@ constexpr int kJacobiSweeps = 12;  // of the 6 x 6 problem; convergence is quadr
 constexpr int kSvdSweeps = 12;     // of the 3 x 3 one-sided Jacobi
 // the doubles of the small result block: W [36] row major (column j the j-th Ritz vector), theta [6], residual^2 [3]
 constexpr int kSmallW = 0, kSmallTheta = 36, kSmallResidual = 42, kSmallWords = 48;
-
-struct Graph {
-  int num_views;
-  int num_pairs;
-  const int* row_ptr;  // [V + 1] CSR of the undirected graph
-  const int2* row;     // [2 E] (neighbour, edge << 1 | (this view is the edge's view2)), ascending edge index
-  const double* R;     // [9 E] the relative rotation matrices, column major
-};
 
 // the sum over the workgroups of value k of parts [num_blocks][stride], ascending
 __device__ __forceinline__ double sum_parts(const double* __restrict__ parts, int num_blocks, int stride, int k) {
@@ -107,8 +101,8 @@ __device__ __forceinline__ void jacobi_row(double A[kBlock][kBlock], double W[kB
 template <int P, int Q>
 __device__ __forceinline__ void svd_pair(double A[3][3], double V[3][3]) {
 #pragma clang fp contract(off)
-  const double alpha = rot::sq3(A[P][0], A[P][1], A[P][2]);
-  const double beta = rot::sq3(A[Q][0], A[Q][1], A[Q][2]);
+  const double alpha = pg::sq3(A[P][0], A[P][1], A[P][2]);
+  const double beta = pg::sq3(A[Q][0], A[Q][1], A[Q][2]);
   const double gamma = (A[P][0] * A[Q][0] + A[P][1] * A[Q][1]) + A[P][2] * A[Q][2];
   if (gamma == 0.0) return;
   const double zeta = (beta - alpha) / (2.0 * gamma);
@@ -140,7 +134,7 @@ __global__ __launch_bounds__(256) void lin_edge_matrix_kernel(int num_pairs, con
 }
 
 // blockIdx.x = the view; A [n][n], n = 3 V, receives M + mu I
-__global__ __launch_bounds__(256) void lin_assemble_kernel(lin::Graph G, int n, double mu, double* __restrict__ A) {
+__global__ __launch_bounds__(256) void lin_assemble_kernel(PoseGraph G, int n, double mu, double* __restrict__ A) {
 #pragma clang fp contract(off)
   const int v = blockIdx.x;
   double* rows = A + (size_t)3 * v * n;
@@ -149,7 +143,7 @@ __global__ __launch_bounds__(256) void lin_assemble_kernel(lin::Graph G, int n, 
   const int r0 = G.row_ptr[v], r1 = G.row_ptr[v + 1];
   for (int r = r0 + threadIdx.x; r < r1; r += 256) {
     const int2 ent = G.row[r];
-    const double* R = G.R + 9 * (size_t)(ent.y >> 1);
+    const double* R = G.edge_value + 9 * (size_t)(ent.y >> 1);
     const bool second = ent.y & 1;
     // block (view1, view2) = -R^T, block (view2, view1) = -R; R(a, b) = R[a + 3 b]
 #pragma unroll
@@ -169,7 +163,7 @@ __global__ __launch_bounds__(256) void lin_start_kernel(int n, unsigned long lon
 }
 
 // one thread per (view, column)
-__global__ __launch_bounds__(256) void lin_apply_kernel(lin::Graph G, const double* __restrict__ Q,
+__global__ __launch_bounds__(256) void lin_apply_kernel(PoseGraph G, const double* __restrict__ Q,
                                                         double* __restrict__ Z) {
 #pragma clang fp contract(off)
   const int t = blockIdx.x * 256 + threadIdx.x;
@@ -179,7 +173,7 @@ __global__ __launch_bounds__(256) void lin_apply_kernel(lin::Graph G, const doub
   double acc[3] = {0.0, 0.0, 0.0};
   for (int r = r0; r < r1; ++r) {
     const int2 ent = G.row[r];
-    const double* R = G.R + 9 * (size_t)(ent.y >> 1);
+    const double* R = G.edge_value + 9 * (size_t)(ent.y >> 1);
     const bool second = ent.y & 1;
     const double* q = Q + (size_t)3 * ent.x * lin::kBlock + j;
     const double x0 = q[0], x1 = q[lin::kBlock], x2 = q[2 * lin::kBlock];
@@ -239,7 +233,7 @@ __global__ __launch_bounds__(256) void lin_mgs_kernel(int n, int j, double* __re
     if (k == j) yj = y[k];
 #pragma unroll
   for (int k = 0; k < lin::kBlock; ++k) {
-    const double total = rot::block_sum(k >= j ? yj * y[k] : 0.0, part);
+    const double total = pg::block_sum(k >= j ? yj * y[k] : 0.0, part);
     if (threadIdx.x == 0) next[(size_t)blockIdx.x * lin::kBlock + k] = total;
   }
 }
@@ -261,7 +255,7 @@ __global__ __launch_bounds__(256) void lin_gram_kernel(int n, const double* __re
   for (int a = 0; a < lin::kBlock; ++a)
 #pragma unroll
     for (int b = a; b < lin::kBlock; ++b) {
-      const double total = rot::block_sum(q[a] * z[b], part);
+      const double total = pg::block_sum(q[a] * z[b], part);
       if (threadIdx.x == 0) parts[(size_t)blockIdx.x * lin::kGram + at] = total;
       ++at;
     }
@@ -349,9 +343,9 @@ __global__ __launch_bounds__(256) void lin_rotate_kernel(int n, const double* __
       r[j] = d * d;
     }
   }
-  const double t0 = rot::block_sum(r[0], part);
-  const double t1 = rot::block_sum(r[1], part);
-  const double t2 = rot::block_sum(r[2], part);
+  const double t0 = pg::block_sum(r[0], part);
+  const double t1 = pg::block_sum(r[1], part);
+  const double t2 = pg::block_sum(r[2], part);
   if (threadIdx.x == 0) {
     res0[blockIdx.x] = t0;
     res1[blockIdx.x] = t1;
@@ -382,7 +376,7 @@ __global__ __launch_bounds__(256) void lin_project_kernel(int num_views, const d
   double sigma[3];
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
-    sigma[c] = sqrt(rot::sq3(A[c][0], A[c][1], A[c][2]));
+    sigma[c] = sqrt(pg::sq3(A[c][0], A[c][1], A[c][2]));
     const double inv = sigma[c] > 0.0 ? 1.0 / sigma[c] : 0.0;
 #pragma unroll
     for (int r = 0; r < 3; ++r) A[c][r] *= inv;  // A[c] = u_c

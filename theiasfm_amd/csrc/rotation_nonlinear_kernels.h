@@ -1,10 +1,10 @@
 // theia::NonlinearRotationEstimator (nonlinear_rotation_estimator.cc:49-100) on the view table and edge list of the
-// nonlinear position estimator (PositionGraph, position_kernels.h; G.t holds the relative rotations): global orientations
+// nonlinear position estimator (PoseGraph, pose_graph.h; G.edge_value holds the relative rotations): global orientations
 // from relative rotations by Levenberg-Marquardt on r_e = RotationMatrixToAngleAxis(R2 R1^T Rrel^T)
 // (pairwise_rotation_error.h:65-95, weight 1) under SoftLOneLoss with Ceres' corrector.
 //
 // The unknowns are the angle-axis rotations of the n free views, x laid out [n][3]; free view v has column
-// rot::column_of(v, fixed).  G.fixed_view = G.num_views says that no view is held: every view has a column then.  The two
+// pg::column_of(v, fixed).  G.fixed_view = G.num_views says that no view is held: every view has a column then.  The two
 // halves of an edge's Jacobian, J1 with respect to x[view1] and J2 with respect to x[view2], are independent, so an edge
 // leaves a record of 27 doubles in planes of E:
 //    0.. 5  B11 = J1~^T J1~, upper triangle (00, 01, 02, 11, 12, 22)
@@ -25,10 +25,12 @@
 //                         has the same bits -- and from the records of the current linearisation the block's part of the
 //                         model cost change -(s . q + (s^T B s) / 2), s the step over the edge's two views.
 //
-// Plain grid launches, no atomics, no expression contracted into FMA.
+// Plain grid launches, no atomics, no expression contracted into FMA.  The host loop is normal_lm_solve
+// (pose_graph_calls.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "pose_graph.h"
 #include "position_nonlinear_kernels.h"
 
 namespace tmi {
@@ -272,7 +274,7 @@ __device__ __forceinline__ void pairwise_rotation_error(const double x1[3], cons
 // the rotation of view v in x [n][3]; a held view's is read from `held` (the caller's value; null for a step: 0)
 __device__ __forceinline__ void load_rotation(const double* __restrict__ x, int v, int fixed,
                                               const double* __restrict__ held, double p[3]) {
-  const int c = rot::column_of(v, fixed);
+  const int c = pg::column_of(v, fixed);
 #pragma unroll
   for (int k = 0; k < 3; ++k) p[k] = c >= 0 ? x[3 * c + k] : (held ? held[k] : 0.0);
 }
@@ -301,7 +303,7 @@ struct RotationBlocks {
 // otherwise: x the candidate, step [n][3] what led to it; part_cost and part_mcc are written, rec is read.
 // held [3]: the rotation of the held view (not read where no view is held).
 template <bool RECORDS>
-__global__ __launch_bounds__(256) void nlr_edge_kernel(PositionGraph G, double width, const double* __restrict__ x,
+__global__ __launch_bounds__(256) void nlr_edge_kernel(PoseGraph G, double width, const double* __restrict__ x,
                                                        const double* __restrict__ step,
                                                        const double* __restrict__ held, double* __restrict__ rec,
                                                        double* __restrict__ residual, double* __restrict__ part_cost,
@@ -316,11 +318,11 @@ __global__ __launch_bounds__(256) void nlr_edge_kernel(PositionGraph G, double w
     double x1[3], x2[3], rel[3];
     nlr::load_rotation(x, v1, G.fixed_view, held, x1);
     nlr::load_rotation(x, v2, G.fixed_view, held, x2);
-    lud::load_direction(G.t, e, rel);
+    lud::load_direction(G.edge_value, e, rel);
     constexpr int N3 = RECORDS ? 3 : 0;
     nlr::Dual<2 * N3> err[3];
     nlr::pairwise_rotation_error<N3>(x1, x2, rel, err);
-    const double sq = rot::sq3(err[0].a, err[1].a, err[2].a);
+    const double sq = pg::sq3(err[0].a, err[1].a, err[2].a);
     double rho[3];
     loss_eval(2, width, sq, rho);
     cost = 0.5 * rho[0];
@@ -383,10 +385,10 @@ __global__ __launch_bounds__(256) void nlr_edge_kernel(PositionGraph G, double w
       mcc = -(lin + 0.5 * sq_form);
     }
   }
-  const double cost_total = rot::block_sum(cost, part);
+  const double cost_total = pg::block_sum(cost, part);
   if (threadIdx.x == 0) part_cost[blockIdx.x] = cost_total;
   if (!RECORDS) {
-    const double mcc_total = rot::block_sum(mcc, part);
+    const double mcc_total = pg::block_sum(mcc, part);
     if (threadIdx.x == 0) part_mcc[blockIdx.x] = mcc_total;
   }
 }

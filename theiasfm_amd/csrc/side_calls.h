@@ -1,6 +1,9 @@
 // Host side of the one-shot calls and the batched small-problem solvers (small_lm.h): the C entry points beside the LM
 // driver, and the scaffold they share.  Included by engine.hip after the driver: tmi_ba_solver, create_impl,
-// prepare_cameras, launch_track_lm and TMI_HIP are the driver's.
+// prepare_cameras, launch_track_lm and TMI_HIP are the driver's.  The five global pose estimators (robust, nonlinear and
+// linear rotations, LUD and nonlinear positions) with rotation_order_cap, NormalLm and normal_lm_solve are in
+// pose_graph_calls.h, which is included after this file and uses OneShot, StreamTimer, PinnedWords, one_shot_batch,
+// bad_argument, all_finite and check_view_pair_batch from here.
 #pragma once
 
 namespace {
@@ -1636,1343 +1639,6 @@ int32_t tmi_ba_filter_view_pairs_from_orientation(const tmi_ba_view_pair_batch* 
     return TMI_BA_OK;
   });
 }
-}  // extern "C"
-
-// ---- RobustRotationEstimator (rotation_kernels.h) ----------------------------------------------
-namespace {
-// The largest order n = V - 1 the call takes (TMI_BA_ROTATION_MAX_ORDER lowers it: a diagnostic knob, so that a small
-// graph reaches the refusal).
-int rotation_order_cap() {
-  int cap = kRotationMaxOrder;
-  if (const char* e = getenv("TMI_BA_ROTATION_MAX_ORDER")) cap = std::max(0, std::min(cap, atoi(e)));
-  return cap;
-}
-
-// The CSR of the undirected graph in ascending edge index -- row: (neighbour, edge << 1 | (this view is the edge's
-// view2)) -- and per free view (column c = v - (v > fixed_view)) the entries with a free neighbour sorted by
-// (neighbour's column, edge), for the matrix assembly of the rotation and the position estimator.
-struct EdgeRows {
-  std::vector<int> row_ptr;   // [V + 1]
-  std::vector<int2> row;      // [2 E]
-  std::vector<int> lap_ptr;   // [n + 1]
-  std::vector<int2> lap_row;  // [<= 2 E]
-};
-
-// fixed_view = V: no view is fixed and every view has a column (the nonlinear rotation estimator's gauge-free problem).
-EdgeRows build_edge_rows(int V, int E, const int32_t* view1, const int32_t* view2, int fixed_view) {
-  const int n = fixed_view < V ? V - 1 : V;
-  EdgeRows rows;
-  std::vector<int>& row_ptr = rows.row_ptr;
-  std::vector<int>& lap_ptr = rows.lap_ptr;
-  std::vector<int2>& row = rows.row;
-  std::vector<int2>& lap_row = rows.lap_row;
-  auto column_of = [&](int v) { return v == fixed_view ? -1 : v - (v > fixed_view); };
-  row_ptr.assign((size_t)V + 1, 0);
-  lap_ptr.assign((size_t)n + 1, 0);
-  row.resize((size_t)2 * E);
-  for (int e = 0; e < E; ++e) {
-    row_ptr[(size_t)view1[e] + 1]++;
-    row_ptr[(size_t)view2[e] + 1]++;
-  }
-  for (int v = 0; v < V; ++v) row_ptr[(size_t)v + 1] += row_ptr[v];
-  std::vector<int> fill(row_ptr.begin(), row_ptr.end() - 1);
-  for (int e = 0; e < E; ++e) {
-    const int a = view1[e], b = view2[e];
-    row[(size_t)fill[a]++] = make_int2(b, e << 1);
-    row[(size_t)fill[b]++] = make_int2(a, (e << 1) | 1);
-  }
-  lap_row.reserve((size_t)2 * E);
-  for (int c = 0; c < n; ++c) {
-    const int v = c + (c >= fixed_view);
-    const size_t first = lap_row.size();
-    for (int r = row_ptr[v]; r < row_ptr[(size_t)v + 1]; ++r) {
-      const int nc = column_of(row[r].x);
-      if (nc >= 0) lap_row.push_back(make_int2(nc, row[r].y >> 1));
-    }
-    std::sort(lap_row.begin() + first, lap_row.end(),
-              [](const int2& p, const int2& q) { return p.x != q.x ? p.x < q.x : p.y < q.y; });
-    lap_ptr[(size_t)c + 1] = (int)lap_row.size();
-  }
-  return rows;
-}
-
-// What the rotation estimator asks of its arguments; null: fine.
-const char* check_rotation_arguments(const tmi_ba_relative_rotation_batch* B, const tmi_ba_robust_rotation_options* o,
-                                     int fixed_view, const double* view_rotation) {
-  const int V = B->num_views, E = B->num_pairs;
-  if (V < 0 || E < 0) return "robust rotations: negative size";
-  if (E == 0) return "robust rotations: no relative rotation (the reference CHECK_GTs the number of constraints)";
-  if (!B->pair_view1 || !B->pair_view2 || !B->pair_rotation) return "robust rotations: missing array";
-  if (fixed_view < 0 || fixed_view >= V) return "robust rotations: fixed_view out of range";
-  if (!(o->l1_step_convergence_threshold > 0.0) || !std::isfinite(o->l1_step_convergence_threshold) ||
-      !(o->irls_step_convergence_threshold > 0.0) || !std::isfinite(o->irls_step_convergence_threshold))
-    return "robust rotations: a step threshold that is not positive and finite";
-  if (!(o->irls_loss_parameter_sigma > 0.0) || !std::isfinite(o->irls_loss_parameter_sigma))
-    return "robust rotations: sigma is not positive and finite";
-  if (o->max_num_l1_iterations < 0 || o->max_num_irls_iterations < 0)
-    return "robust rotations: negative iteration count";
-  // union-find: every view must reach fixed_view
-  std::vector<int> parent((size_t)V);
-  for (int v = 0; v < V; ++v) parent[v] = v;
-  auto find = [&](int v) {
-    while (parent[v] != v) v = parent[v] = parent[parent[v]];
-    return v;
-  };
-  for (int e = 0; e < E; ++e) {
-    const int a = B->pair_view1[e], b = B->pair_view2[e];
-    if (a < 0 || a >= V || b < 0 || b >= V) return "robust rotations: view index out of range";
-    if (a == b) return "robust rotations: a view paired with itself";
-    const int ra = find(a), rb = find(b);
-    if (ra != rb) parent[std::max(ra, rb)] = std::min(ra, rb);
-  }
-  if (!all_finite(view_rotation, (size_t)3 * V)) return "robust rotations: non-finite view_rotation";
-  if (!all_finite(B->pair_rotation, (size_t)3 * E)) return "robust rotations: non-finite pair_rotation";
-  const int root = find(fixed_view);
-  for (int v = 0; v < V; ++v)
-    if (find(v) != root) return "robust rotations: a view is not connected to fixed_view";
-  return nullptr;
-}
-}  // namespace
-extern "C" {
-
-void tmi_ba_robust_rotation_options_init(tmi_ba_robust_rotation_options* o) {
-  if (!o) return;
-  o->max_num_l1_iterations = 5;  // robust_rotation_estimator.h:63-82
-  o->l1_step_convergence_threshold = 0.001;
-  o->max_num_irls_iterations = 100;
-  o->irls_step_convergence_threshold = 0.001;
-  o->irls_loss_parameter_sigma = 5.0 * (M_PI / 180.0);
-}
-
-int32_t tmi_ba_estimate_global_rotations_robust(const tmi_ba_relative_rotation_batch* Bh,
-                                                const tmi_ba_robust_rotation_options* opt, int32_t fixed_view,
-                                                int32_t device, double* view_rotation, double* pair_residual,
-                                                int32_t* l1_admm_iterations, double* l1_average_step,
-                                                double* irls_average_step, double* irls_squared_residual,
-                                                tmi_ba_robust_rotation_summary* sum) {
-  if (!Bh || !opt || !view_rotation || !sum)
-    return bad_argument("robust rotations: null batch, options, view_rotation or summary");
-  memset(sum, 0, sizeof(*sum));
-  const double t0 = now_s();
-  // argument errors before the device is touched
-  if (const char* why = check_rotation_arguments(Bh, opt, fixed_view, view_rotation)) return bad_argument(why);
-  const int V = Bh->num_views, E = Bh->num_pairs, n = V - 1;
-  if (n > rotation_order_cap()) {
-    g_last_error = "robust rotations: num_views - 1 exceeds the dense solver's cap (see the header)";
-    return TMI_BA_ERR_UNSUPPORTED;
-  }
-  if (E > (1 << 30)) return bad_argument("robust rotations: more than 2^30 pairs");
-  const EdgeRows rows = build_edge_rows(V, E, Bh->pair_view1, Bh->pair_view2, fixed_view);
-  const int L1 = opt->max_num_l1_iterations, IR = opt->max_num_irls_iterations;
-  std::vector<int> admm_trace;
-  std::vector<double> l1_trace, irls_trace, irls_sq_trace;
-  return one_shot_batch(device, "robust rotations: no such device", E, t0, sum, [&](OneShot* s) -> int {
-    RotationGraph G;
-    memset(&G, 0, sizeof(G));
-    G.num_views = V;
-    G.num_pairs = E;
-    G.fixed_view = fixed_view;
-    int *d_v1, *d_v2, *d_ptr, *d_lptr, *d_flag;
-    int2 *d_row, *d_lrow;
-    double *d_rel, *d_o, *d_r, *d_w, *d_z, *d_u, *d_dz, *d_rhs, *d_tmp, *d_x, *d_diag_w, *d_A, *d_cdiag, *d_part, *d_norms;
-    TMI_HIP(s->upload(&d_v1, (const int*)Bh->pair_view1, (size_t)E));
-    TMI_HIP(s->upload(&d_v2, (const int*)Bh->pair_view2, (size_t)E));
-    TMI_HIP(s->upload(&d_ptr, rows.row_ptr.data(), rows.row_ptr.size()));
-    TMI_HIP(s->upload(&d_row, rows.row.data(), rows.row.size()));
-    TMI_HIP(s->upload(&d_lptr, rows.lap_ptr.data(), rows.lap_ptr.size()));
-    TMI_HIP(s->upload(&d_lrow, rows.lap_row.data(), rows.lap_row.size()));
-    TMI_HIP(s->upload(&d_rel, Bh->pair_rotation, (size_t)3 * E));
-    TMI_HIP(s->upload(&d_o, (const double*)view_rotation, (size_t)3 * V));
-    TMI_HIP(s->alloc(&d_r, (size_t)3 * E));
-    TMI_HIP(s->alloc(&d_w, (size_t)E));
-    TMI_HIP(s->alloc(&d_z, (size_t)3 * E));
-    TMI_HIP(s->alloc(&d_u, (size_t)3 * E));
-    TMI_HIP(s->alloc(&d_dz, (size_t)3 * E));
-    TMI_HIP(s->alloc(&d_rhs, (size_t)3 * n));
-    TMI_HIP(s->alloc(&d_tmp, (size_t)3 * n));
-    TMI_HIP(s->alloc(&d_x, (size_t)3 * n));
-    TMI_HIP(s->alloc(&d_diag_w, (size_t)n));
-    TMI_HIP(s->alloc(&d_A, (size_t)n * n));
-    TMI_HIP(s->alloc(&d_cdiag, (size_t)kPanel * ((size_t)(n + kPanel - 1) / kPanel) * kPanel));
-    const int nbE = (E + 255) / 256, nbV = (n + 255) / 256;
-    TMI_HIP(s->alloc(&d_part, (size_t)4 * nbE + (size_t)3 * nbV));
-    TMI_HIP(s->alloc(&d_norms, 8));
-    TMI_HIP(s->alloc(&d_flag, 1));
-    double *p_r = d_part, *p_ax = p_r + nbE, *p_z = p_ax + nbE, *p_rr = p_z + nbE, *p_s = p_rr + nbE, *p_t = p_s + nbV,
-           *p_step = p_t + nbV;
-    PinnedWords pinned;  // [0..5) the ADMM norms or (|r|^2, the step sum), then the pivot flag
-    TMI_HIP(pinned.alloc(8 * sizeof(double)));
-    double* h_norms = static_cast<double*>(pinned.p);
-    int* h_flag = reinterpret_cast<int*>(h_norms + 6);
-    G.pair_view1 = d_v1;
-    G.pair_view2 = d_v2;
-    G.relative = d_rel;
-    G.row_ptr = d_ptr;
-    G.row = d_row;
-    G.lap_ptr = d_lptr;
-    G.lap_row = d_lrow;
-    TMI_HIP(hipMemsetAsync(d_flag, 0, sizeof(int), s->stream));
-    hipStream_t st = s->stream;
-    const dim3 edge_grid(nbE), view_grid(nbV), block(256);
-    const double sigma = opt->irls_loss_parameter_sigma;
-    // device time in three classes; every section ends in a fetch(), which synchronises
-    StreamTimer timer(st, StreamTimer::kMaxMarks);
-    TMI_HIP(timer.status);
-    enum { kFactor = 0, kSubst = 1, kGraph = 2 };
-    double seconds[3] = {0.0, 0.0, 0.0};
-    int section[3] = {kGraph, kGraph, kGraph};  // what runs between marks 0-1, 1-2 and 2-3
-    // the sums of `count` quantities into h_norms, and the pivot flag, then the time of the marked sections
-    auto fetch = [&](const ReduceJobs& jobs, int count) -> int {
-      hipLaunchKernelGGL(reduce_partials_kernel, dim3(count), block, 0, st, jobs, d_norms);
-      TMI_HIP(timer.mark());
-      const hipError_t le = hipGetLastError();
-      hipError_t ce = hipMemcpyAsync(h_norms, d_norms, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, st);
-      if (ce == hipSuccess) ce = hipMemcpyAsync(h_flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, st);
-      const hipError_t se = hipStreamSynchronize(st);
-      TMI_HIP(le);
-      TMI_HIP(ce);
-      TMI_HIP(se);
-      for (int m = 0; m + 1 < timer.marked; ++m) seconds[section[m]] += timer.seconds(m, m + 1);
-      timer.marked = 0;
-      return TMI_BA_OK;
-    };
-    auto assemble_and_factor = [&](const double* w, const double* diag_w) {
-      hipLaunchKernelGGL(laplacian_assemble_kernel, dim3(n), block, 0, st, G, n, w, diag_w, d_A);
-      dense_cholesky_factor(d_A, n, d_cdiag, d_flag, st);
-      sum->num_factorizations++;
-    };
-    auto residuals = [&]() {
-      hipLaunchKernelGGL(rotation_residual_kernel, edge_grid, block, 0, st, G, d_o, sigma, d_r, d_w, p_rr);
-    };
-    const char* pivot = "robust rotations: a pivot of the Laplacian's Cholesky factorisation is not positive";
-    ReduceJobs jobs;
-    memset(&jobs, 0, sizeof(jobs));
-    int rc;
-
-    // ---- ComputeResiduals, and the factorisation of the L1 phase (:149-155) ----
-    TMI_HIP(timer.mark());
-    if (L1 > 0) assemble_and_factor(nullptr, nullptr);
-    TMI_HIP(timer.mark());
-    section[0] = kFactor;
-    section[1] = kGraph;
-    residuals();
-    jobs.part[0] = p_rr;
-    jobs.count[0] = nbE;
-    if ((rc = fetch(jobs, 1))) return rc;
-    if (*h_flag) {
-      s->error = pivot;
-      return TMI_BA_ERR_LINEAR_SOLVER;
-    }
-    double r_sq = h_norms[0];
-
-    // ---- SolveL1Regression (:156-169) ----
-    const double rho = 1.0, alpha = 1.0, abs_tol = 1e-4, rel_tol = 1e-2;  // l1_solver.h:89-98
-    const double primal_abs = std::sqrt(3.0 * (double)E) * abs_tol, dual_abs = std::sqrt(3.0 * (double)n) * abs_tol;
-    int budget = 5;
-    for (int outer = 0; outer < L1; ++outer) {
-      const double rhs_norm = std::sqrt(r_sq);
-      TMI_HIP(timer.mark());
-      TMI_HIP(hipMemsetAsync(d_z, 0, (size_t)3 * E * sizeof(double), st));
-      TMI_HIP(hipMemsetAsync(d_u, 0, (size_t)3 * E * sizeof(double), st));
-      TMI_HIP(hipMemsetAsync(d_dz, 0, (size_t)3 * E * sizeof(double), st));
-      hipLaunchKernelGGL(admm_view_kernel, view_grid, block, 0, st, G, n, rho, d_r, d_z, d_u, d_dz, d_rhs, p_s, p_t);
-      int ran = 0;
-      for (int it = 0; it < budget; ++it) {
-        TMI_HIP(timer.mark());  // (the first iteration's second mark: the section before it is the set-up above)
-        section[0] = kGraph;
-        section[timer.marked - 1] = kSubst;
-        section[timer.marked] = kGraph;
-        dense_cholesky_substitute<3>(d_A, n, d_rhs, d_x, d_tmp, st);
-        TMI_HIP(timer.mark());
-        hipLaunchKernelGGL(admm_edge_kernel, edge_grid, block, 0, st, G, rho, alpha, d_x, d_r, d_z, d_u, d_dz, p_r, p_ax,
-                           p_z);
-        hipLaunchKernelGGL(admm_view_kernel, view_grid, block, 0, st, G, n, rho, d_r, d_z, d_u, d_dz, d_rhs, p_s, p_t);
-        const double* parts[5] = {p_r, p_ax, p_z, p_s, p_t};
-        for (int q = 0; q < 5; ++q) {
-          jobs.part[q] = parts[q];
-          jobs.count[q] = q < 3 ? nbE : nbV;
-        }
-        if ((rc = fetch(jobs, 5))) return rc;
-        ++ran;
-        const double r_norm = std::sqrt(h_norms[0]), s_norm = std::sqrt(h_norms[3]);
-        const double max_norm = std::max({std::sqrt(h_norms[1]), std::sqrt(h_norms[2]), rhs_norm});
-        const double primal_eps = primal_abs + rel_tol * max_norm;
-        const double dual_eps = dual_abs + rel_tol * std::sqrt(h_norms[4]);
-        if (r_norm < primal_eps && s_norm < dual_eps) break;
-      }
-      // UpdateGlobalRotations, ComputeResiduals, ComputeAverageStepSize
-      TMI_HIP(timer.mark());
-      hipLaunchKernelGGL(rotation_update_kernel, view_grid, block, 0, st, n, fixed_view, d_x, d_o, p_step);
-      residuals();
-      section[0] = kGraph;
-      jobs.part[0] = p_rr;
-      jobs.count[0] = nbE;
-      jobs.part[1] = p_step;
-      jobs.count[1] = nbV;
-      if ((rc = fetch(jobs, 2))) return rc;
-      r_sq = h_norms[0];
-      const double avg = h_norms[1] / (double)n;
-      admm_trace.push_back(ran);
-      l1_trace.push_back(avg);
-      sum->num_l1_iterations++;
-      sum->num_admm_iterations += ran;
-      if (avg <= opt->l1_step_convergence_threshold) {
-        sum->l1_converged = 1;
-        break;
-      }
-      budget *= 2;
-    }
-
-    // ---- SolveIRLS (:189-234) ----
-    for (int it = 0; it < IR; ++it) {
-      TMI_HIP(timer.mark());
-      hipLaunchKernelGGL(irls_rhs_kernel, view_grid, block, 0, st, G, n, d_w, d_r, d_rhs, d_diag_w);
-      assemble_and_factor(d_w, d_diag_w);
-      TMI_HIP(timer.mark());
-      dense_cholesky_substitute<3>(d_A, n, d_rhs, d_x, d_tmp, st);
-      TMI_HIP(timer.mark());
-      section[0] = kFactor;
-      section[1] = kSubst;
-      section[2] = kGraph;
-      hipLaunchKernelGGL(rotation_update_kernel, view_grid, block, 0, st, n, fixed_view, d_x, d_o, p_step);
-      residuals();
-      jobs.part[0] = p_rr;
-      jobs.count[0] = nbE;
-      jobs.part[1] = p_step;
-      jobs.count[1] = nbV;
-      if ((rc = fetch(jobs, 2))) return rc;
-      if (*h_flag) {
-        s->error = pivot;
-        return TMI_BA_ERR_LINEAR_SOLVER;
-      }
-      r_sq = h_norms[0];
-      const double avg = h_norms[1] / (double)n;
-      irls_trace.push_back(avg);
-      irls_sq_trace.push_back(r_sq);
-      sum->num_irls_iterations++;
-      if (avg < opt->irls_step_convergence_threshold) {
-        sum->irls_converged = 1;
-        break;
-      }
-    }
-
-    // the results, only now: a failure above leaves the caller's arrays as they were
-    std::vector<double> o_h((size_t)3 * V), r_h(pair_residual ? (size_t)3 * E : 0);
-    TMI_HIP(hipMemcpyAsync(o_h.data(), d_o, o_h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (pair_residual) TMI_HIP(hipMemcpyAsync(r_h.data(), d_r, r_h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    TMI_HIP(hipStreamSynchronize(st));
-    std::copy(o_h.begin(), o_h.end(), view_rotation);
-    if (pair_residual) std::copy(r_h.begin(), r_h.end(), pair_residual);
-    if (l1_admm_iterations) std::copy(admm_trace.begin(), admm_trace.end(), l1_admm_iterations);
-    if (l1_average_step) std::copy(l1_trace.begin(), l1_trace.end(), l1_average_step);
-    if (irls_average_step) std::copy(irls_trace.begin(), irls_trace.end(), irls_average_step);
-    if (irls_squared_residual) std::copy(irls_sq_trace.begin(), irls_sq_trace.end(), irls_squared_residual);
-    sum->num_views = V;
-    sum->num_pairs = E;
-    sum->factor_seconds = seconds[kFactor];
-    sum->substitution_seconds = seconds[kSubst];
-    sum->graph_seconds = seconds[kGraph];
-    sum->kernel_seconds = seconds[kFactor] + seconds[kSubst] + seconds[kGraph];
-    return TMI_BA_OK;
-  });
-}
-}  // extern "C"
-
-// ---- LeastUnsquaredDeviationPositionEstimator (position_kernels.h) ------------------------------
-namespace {
-// What the position estimator asks of its arguments beyond check_view_pair_batch, the connection to fixed_view apart;
-// null: fine.  Nothing is allocated here.
-const char* check_lud_arguments(const tmi_ba_view_pair_batch* B, const tmi_ba_lud_position_options* o, int fixed_view) {
-  if (B->num_pairs == 0) return "LUD positions: no view pair";
-  if (fixed_view < 0 || fixed_view >= B->num_views) return "LUD positions: fixed_view out of range";
-  for (const double x : {o->rho, o->alpha, o->absolute_tolerance, o->relative_tolerance})
-    if (!(x > 0.0) || !std::isfinite(x)) return "LUD positions: rho, alpha or a tolerance that is not positive and finite";
-  if (o->max_num_iterations < 1) return "LUD positions: max_num_iterations < 1 (the reference CHECK_GTs it)";
-  return nullptr;
-}
-
-// Union-find over the (checked) edges: does every view reach fixed_view?
-bool every_view_reaches(const tmi_ba_view_pair_batch* B, int fixed_view) {
-  const int V = B->num_views, E = B->num_pairs;
-  std::vector<int> parent((size_t)V);
-  for (int v = 0; v < V; ++v) parent[v] = v;
-  auto find = [&](int v) {
-    while (parent[v] != v) v = parent[v] = parent[parent[v]];
-    return v;
-  };
-  for (int e = 0; e < E; ++e) {
-    const int ra = find(B->pair_view1[e]), rb = find(B->pair_view2[e]);
-    if (ra != rb) parent[std::max(ra, rb)] = std::min(ra, rb);
-  }
-  const int root = find(fixed_view);
-  for (int v = 0; v < V; ++v)
-    if (find(v) != root) return false;
-  return true;
-}
-}  // namespace
-extern "C" {
-
-void tmi_ba_lud_position_options_init(tmi_ba_lud_position_options* o) {
-  if (!o) return;
-  o->max_num_iterations = 1000;  // math/constrained_l1_solver.h:64-74
-  o->rho = 10.0;
-  o->alpha = 1.2;
-  o->absolute_tolerance = 1e-4;
-  o->relative_tolerance = 1e-2;
-}
-
-int32_t tmi_ba_estimate_global_positions_lud(const tmi_ba_view_pair_batch* Bh, const tmi_ba_lud_position_options* opt,
-                                             int32_t fixed_view, int32_t device, double* view_position,
-                                             double* pair_scale, double* pair_residual, double* admm_r_norm,
-                                             double* admm_s_norm, tmi_ba_lud_position_summary* sum) {
-  if (!Bh || !opt || !view_position || !sum)
-    return bad_argument("LUD positions: null batch, options, view_position or summary");
-  memset(sum, 0, sizeof(*sum));
-  const double t0 = now_s();
-  // argument errors before the device is touched
-  if (const char* why = check_view_pair_batch(Bh, false, Bh->pair_position2)) return bad_argument(why);
-  if (const char* why = check_lud_arguments(Bh, opt, fixed_view)) return bad_argument(why);
-  const int V = Bh->num_views, E = Bh->num_pairs, n = V - 1;
-  // the cap before anything of the views' size is allocated, the union-find included
-  if ((int64_t)3 * n > rotation_order_cap()) {
-    g_last_error = "LUD positions: 3 (num_views - 1) exceeds the dense solver's cap (see the header)";
-    return TMI_BA_ERR_UNSUPPORTED;
-  }
-  const int N = 3 * n;  // (<= the cap)
-  if (!every_view_reaches(Bh, fixed_view)) return bad_argument("LUD positions: a view is not connected to fixed_view");
-  const EdgeRows rows = build_edge_rows(V, E, Bh->pair_view1, Bh->pair_view2, fixed_view);
-  const int max_it = opt->max_num_iterations;
-  const double rho = opt->rho, alpha = opt->alpha;
-  std::vector<double> r_trace, s_trace;
-  return one_shot_batch(device, "LUD positions: no such device", E, t0, sum, [&](OneShot* s) -> int {
-    PositionGraph G;
-    memset(&G, 0, sizeof(G));
-    G.num_views = V;
-    G.num_pairs = E;
-    G.fixed_view = fixed_view;
-    int *d_v1, *d_v2, *d_ptr, *d_lptr, *d_flag;
-    int2 *d_row, *d_lrow;
-    double *d_pos, *d_t, *d_rot = nullptr, *d_qs, *d_z, *d_u, *d_dz, *d_scale, *d_ax, *d_rhs, *d_tmp, *d_p, *d_S, *d_cdiag, *d_part,
-        *d_norms;
-    TMI_HIP(s->upload(&d_v1, (const int*)Bh->pair_view1, (size_t)E));
-    TMI_HIP(s->upload(&d_v2, (const int*)Bh->pair_view2, (size_t)E));
-    TMI_HIP(s->upload(&d_ptr, rows.row_ptr.data(), rows.row_ptr.size()));
-    TMI_HIP(s->upload(&d_row, rows.row.data(), rows.row.size()));
-    TMI_HIP(s->upload(&d_lptr, rows.lap_ptr.data(), rows.lap_ptr.size()));
-    TMI_HIP(s->upload(&d_lrow, rows.lap_row.data(), rows.lap_row.size()));
-    TMI_HIP(s->upload(&d_pos, Bh->pair_position2, (size_t)3 * E));
-    d_t = d_pos;
-    if (Bh->view_rotation) {
-      TMI_HIP(s->upload(&d_rot, Bh->view_rotation, (size_t)3 * V));
-      TMI_HIP(s->alloc(&d_t, (size_t)3 * E));
-    }
-    const std::vector<double> ones((size_t)E, 1.0);  // the scale entries of A^T b
-    TMI_HIP(s->upload(&d_qs, ones.data(), ones.size()));
-    TMI_HIP(s->alloc(&d_z, (size_t)4 * E));
-    TMI_HIP(s->alloc(&d_u, (size_t)4 * E));
-    TMI_HIP(s->alloc(&d_dz, (size_t)4 * E));
-    TMI_HIP(s->alloc(&d_scale, (size_t)E));
-    TMI_HIP(s->alloc(&d_ax, (size_t)3 * E));
-    TMI_HIP(s->alloc(&d_rhs, (size_t)N));
-    TMI_HIP(s->alloc(&d_tmp, (size_t)N));
-    TMI_HIP(s->alloc(&d_p, (size_t)N));
-    TMI_HIP(s->alloc(&d_S, (size_t)N * N));
-    TMI_HIP(s->alloc(&d_cdiag, (size_t)kPanel * ((size_t)(N + kPanel - 1) / kPanel) * kPanel));
-    const int nbE = (E + 255) / 256, nbV = (n + 255) / 256;
-    // the blocks' parts: |A x - z - b|^2, |A x|^2, |z|^2 [nbE each], then |rho A^T dz|^2 and |rho A^T u|^2, each the
-    // edges' parts [nbE] followed by the views' [nbV] and reduced as one quantity
-    TMI_HIP(s->alloc(&d_part, (size_t)5 * nbE + (size_t)2 * nbV));
-    TMI_HIP(s->alloc(&d_norms, 8));
-    TMI_HIP(s->alloc(&d_flag, 1));
-    double *p_r = d_part, *p_ax = p_r + nbE, *p_z = p_ax + nbE, *p_s = p_z + nbE, *p_t = p_s + nbE + nbV;
-    PinnedWords pinned;  // [0..5) the ADMM norms, then the pivot flag
-    TMI_HIP(pinned.alloc(8 * sizeof(double)));
-    double* h_norms = static_cast<double*>(pinned.p);
-    int* h_flag = reinterpret_cast<int*>(h_norms + 6);
-    G.pair_view1 = d_v1;
-    G.pair_view2 = d_v2;
-    G.t = d_t;
-    G.row_ptr = d_ptr;
-    G.row = d_row;
-    G.lap_ptr = d_lptr;
-    G.lap_row = d_lrow;
-    hipStream_t st = s->stream;
-    const dim3 edge_grid(nbE), view_grid(nbV), block(256);
-    TMI_HIP(hipMemsetAsync(d_flag, 0, sizeof(int), st));
-    TMI_HIP(hipMemsetAsync(d_z, 0, (size_t)4 * E * sizeof(double), st));
-    TMI_HIP(hipMemsetAsync(d_u, 0, (size_t)4 * E * sizeof(double), st));
-    TMI_HIP(hipMemsetAsync(d_dz, 0, (size_t)4 * E * sizeof(double), st));
-    ReduceJobs jobs;
-    memset(&jobs, 0, sizeof(jobs));
-    const double* parts[5] = {p_r, p_ax, p_z, p_s, p_t};
-    for (int q = 0; q < 5; ++q) {
-      jobs.part[q] = parts[q];
-      jobs.count[q] = q < 3 ? nbE : nbE + nbV;
-    }
-    // device time in three classes: marks 0-1 the set-up (first iteration only) or the substitution, 1-2 the graph
-    // kernels; every iteration ends in a synchronisation
-    StreamTimer timer(st, 3);
-    TMI_HIP(timer.status);
-    double factor_seconds = 0.0, subst_seconds = 0.0, graph_seconds = 0.0;
-
-    // ---- the directions, S and its factor, and the right-hand side of the first solve: A^T b ----
-    TMI_HIP(timer.mark());
-    if (Bh->view_rotation) hipLaunchKernelGGL(lud_direction_kernel, edge_grid, block, 0, st, E, d_rot, d_v1, d_pos, d_t);
-    hipLaunchKernelGGL(lud_assemble_kernel, dim3(n), block, 0, st, G, N, d_S);
-    dense_cholesky_factor(d_S, N, d_cdiag, d_flag, st);
-    sum->num_factorizations = 1;
-    TMI_HIP(timer.mark());
-    hipLaunchKernelGGL(lud_view_kernel, view_grid, block, 0, st, G, n, rho, d_qs, d_z, d_u, d_dz, d_rhs, p_s + nbE,
-                       p_t + nbE);
-    TMI_HIP(timer.mark());
-    {
-      const hipError_t le = hipGetLastError();
-      const hipError_t ce = hipMemcpyAsync(h_flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, st);
-      const hipError_t se = hipStreamSynchronize(st);
-      TMI_HIP(le);
-      TMI_HIP(ce);
-      TMI_HIP(se);
-    }
-    factor_seconds += timer.seconds(0, 1);
-    graph_seconds += timer.seconds(1, 2);
-    if (*h_flag) {
-      s->error = "LUD positions: a pivot of the Cholesky factorisation of S is not positive";
-      return TMI_BA_ERR_LINEAR_SOLVER;
-    }
-
-    // ---- ConstrainedL1Solver::Solve (:112-170) ----
-    const double rhs_norm = std::sqrt((double)E);  // |b|
-    const double primal_abs = std::sqrt(4.0 * (double)E) * opt->absolute_tolerance;
-    const double dual_abs = std::sqrt(3.0 * (double)n + (double)E) * opt->absolute_tolerance;
-    for (int it = 0; it < max_it; ++it) {
-      timer.marked = 0;
-      TMI_HIP(timer.mark());
-      dense_cholesky_substitute<1>(d_S, N, d_rhs, d_p, d_tmp, st);
-      TMI_HIP(timer.mark());
-      hipLaunchKernelGGL(lud_edge_kernel, edge_grid, block, 0, st, G, rho, alpha, d_p, d_qs, d_z, d_u, d_dz, d_scale,
-                         d_ax, p_r, p_ax, p_z, p_s, p_t);
-      hipLaunchKernelGGL(lud_view_kernel, view_grid, block, 0, st, G, n, rho, d_qs, d_z, d_u, d_dz, d_rhs, p_s + nbE,
-                         p_t + nbE);
-      hipLaunchKernelGGL(reduce_partials_kernel, dim3(5), block, 0, st, jobs, d_norms);
-      TMI_HIP(timer.mark());
-      const hipError_t le = hipGetLastError();
-      hipError_t ce = hipMemcpyAsync(h_norms, d_norms, 5 * sizeof(double), hipMemcpyDeviceToHost, st);
-      if (ce == hipSuccess) ce = hipMemcpyAsync(h_flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, st);
-      const hipError_t se = hipStreamSynchronize(st);
-      TMI_HIP(le);
-      TMI_HIP(ce);
-      TMI_HIP(se);
-      subst_seconds += timer.seconds(0, 1);
-      graph_seconds += timer.seconds(1, 2);
-      sum->num_admm_iterations++;
-      const double r_norm = std::sqrt(h_norms[0]), s_norm = std::sqrt(h_norms[3]);
-      const double max_norm = std::max({std::sqrt(h_norms[1]), std::sqrt(h_norms[2]), rhs_norm});
-      const double primal_eps = primal_abs + opt->relative_tolerance * max_norm;
-      const double dual_eps = dual_abs + opt->relative_tolerance * std::sqrt(h_norms[4]);
-      r_trace.push_back(r_norm);
-      s_trace.push_back(s_norm);
-      if (r_norm < primal_eps && s_norm < dual_eps) {
-        sum->converged = 1;
-        break;
-      }
-    }
-
-    // the results, only now: a failure above leaves the caller's arrays as they were
-    std::vector<double> p_h((size_t)N), scale_h(pair_scale ? (size_t)E : 0), ax_h(pair_residual ? (size_t)3 * E : 0);
-    TMI_HIP(hipMemcpyAsync(p_h.data(), d_p, p_h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (pair_scale) TMI_HIP(hipMemcpyAsync(scale_h.data(), d_scale, scale_h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (pair_residual) TMI_HIP(hipMemcpyAsync(ax_h.data(), d_ax, ax_h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    TMI_HIP(hipStreamSynchronize(st));
-    for (int v = 0; v < V; ++v)
-      for (int k = 0; k < 3; ++k)
-        view_position[(size_t)3 * v + k] = v == fixed_view ? 0.0 : p_h[(size_t)3 * (v - (v > fixed_view)) + k];
-    if (pair_scale) std::copy(scale_h.begin(), scale_h.end(), pair_scale);
-    if (pair_residual) std::copy(ax_h.begin(), ax_h.end(), pair_residual);
-    if (admm_r_norm) std::copy(r_trace.begin(), r_trace.end(), admm_r_norm);
-    if (admm_s_norm) std::copy(s_trace.begin(), s_trace.end(), admm_s_norm);
-    sum->num_views = V;
-    sum->num_pairs = E;
-    sum->factor_seconds = factor_seconds;
-    sum->substitution_seconds = subst_seconds;
-    sum->graph_seconds = graph_seconds;
-    sum->kernel_seconds = factor_seconds + subst_seconds + graph_seconds;
-    return TMI_BA_OK;
-  });
-}
-}  // extern "C"
-
-// ---- NonlinearPositionEstimator (position_nonlinear_kernels.h) ----------------------------------
-namespace {
-// The device memory of the Levenberg-Marquardt loop on dense normal equations of order N over E edges that the nonlinear
-// position and rotation estimators share (normal_lm_solve), and the traces it leaves.
-struct NormalLm {
-  int N = 0, nbE = 0, nbN = 0;
-  double *x, *cand, *step, *y, *rhs, *tmp, *scale, *diag, *g, *gabs, *M, *A, *cdiag, *part, *norms;
-  int* flag;
-  double *p_cost, *p_mcc, *p_step, *p_x;  // the blocks' parts: cost and model cost change [nbE], |step|^2, |x|^2 [nbN]
-  std::vector<double> cost_trace, radius_trace;
-  std::vector<int32_t> outcome_trace;
-  int alloc(OneShot* s, int N_, int E) {
-    N = N_;
-    nbE = (E + 255) / 256;
-    nbN = (N + 255) / 256;
-    TMI_HIP(s->alloc(&x, (size_t)N));
-    const std::vector<double> ones((size_t)N, 1.0);  // the scales without jacobi_scaling
-    TMI_HIP(s->upload(&scale, ones.data(), ones.size()));
-    TMI_HIP(hipStreamSynchronize(s->stream));  // (ones goes out of scope)
-    TMI_HIP(s->alloc(&cand, (size_t)N));
-    TMI_HIP(s->alloc(&step, (size_t)N));
-    TMI_HIP(s->alloc(&y, (size_t)N));
-    TMI_HIP(s->alloc(&rhs, (size_t)N));
-    TMI_HIP(s->alloc(&tmp, (size_t)N));
-    TMI_HIP(s->alloc(&diag, (size_t)N));
-    TMI_HIP(s->alloc(&g, (size_t)N));
-    TMI_HIP(s->alloc(&gabs, (size_t)N));
-    TMI_HIP(s->alloc(&M, (size_t)N * N));  // the assembled normal matrix, kept across rejected steps
-    TMI_HIP(s->alloc(&A, (size_t)N * N));  // its damped copy, overwritten by the factor
-    TMI_HIP(s->alloc(&cdiag, (size_t)kPanel * ((size_t)(N + kPanel - 1) / kPanel) * kPanel));
-    TMI_HIP(s->alloc(&part, (size_t)2 * nbE + (size_t)2 * nbN));
-    TMI_HIP(s->alloc(&norms, 8));
-    TMI_HIP(s->alloc(&flag, 1));
-    p_cost = part;
-    p_mcc = p_cost + nbE;
-    p_step = p_mcc + nbE;
-    p_x = p_step + nbN;
-    return TMI_BA_OK;
-  }
-};
-
-// Ceres 1.14's TrustRegionMinimizer with the Levenberg-Marquardt strategy on the dense normal equations, the rules of
-// tmi_ba_solver_solve (steps 6 and 7 of tmi_ba_estimate_global_positions_nonlinear).  x_h [N] is the start and receives
-// the last accepted point.  linearize(first_scaled) queues, at L.x: the records, the residuals and the cost parts
-// (L.p_cost), the Jacobi scales into L.scale where first_scaled, then L.M, L.diag, L.g and L.gabs.  candidate() queues, at
-// L.cand with L.step: the cost parts and the parts of the model cost change (L.p_mcc).  Opt has the trust-region fields of
-// tmi_ba_nonlinear_position_options; Sum the counters and times of tmi_ba_nonlinear_position_summary.
-template <class Opt, class Sum, class Linearize, class Candidate>
-int normal_lm_solve(OneShot* s, const Opt* opt, Sum* sum, NormalLm& L, std::vector<double>& x_h, Linearize linearize_at,
-                    Candidate candidate_at) {
-  const int N = L.N, nbE = L.nbE, nbN = L.nbN, max_it = opt->max_num_iterations;
-  double*& d_x = L.x;
-  double*& d_cand = L.cand;
-  double *d_step = L.step, *d_y = L.y, *d_rhs = L.rhs, *d_tmp = L.tmp, *d_scale = L.scale, *d_diag = L.diag, *d_g = L.g,
-         *d_gabs = L.gabs, *d_M = L.M, *d_A = L.A, *d_cdiag = L.cdiag, *d_norms = L.norms;
-  int* d_flag = L.flag;
-  double *p_cost = L.p_cost, *p_mcc = L.p_mcc, *p_step = L.p_step, *p_x = L.p_x;
-  std::vector<double>&cost_trace = L.cost_trace, &radius_trace = L.radius_trace;
-  std::vector<int32_t>& outcome_trace = L.outcome_trace;
-  hipStream_t st = s->stream;
-  const dim3 entry_grid(nbN), block(256);
-  TMI_HIP(hipMemcpyAsync(d_x, x_h.data(), (size_t)N * sizeof(double), hipMemcpyHostToDevice, st));
-  PinnedWords pinned;  // [0..5) cost, model cost change, |step|^2, |candidate|^2, max |gradient|; then the pivot flag
-  TMI_HIP(pinned.alloc(8 * sizeof(double)));
-  double* h_norms = static_cast<double*>(pinned.p);
-  int* h_flag = reinterpret_cast<int*>(h_norms + 6);
-  TMI_HIP(hipMemsetAsync(d_flag, 0, sizeof(int), st));
-  TMI_HIP(hipMemsetAsync(d_y, 0, (size_t)N * sizeof(double), st));
-  ReduceJobs jobs;
-  memset(&jobs, 0, sizeof(jobs));
-  const double* parts[4] = {p_cost, p_mcc, p_step, p_x};
-  for (int q = 0; q < 4; ++q) {
-    jobs.part[q] = parts[q];
-    jobs.count[q] = q < 2 ? nbE : nbN;
-  }
-  // device time in three classes.  An iteration's marks: 0-1 the damped copy and the factorisation, 1-2 the
-  // substitution, 2-3 the step, the candidate and the reductions; a linearisation with its assembly has a timer of
-  // its own, read after the next synchronisation.
-  StreamTimer timer(st, 4), lin_timer(st, 2);
-  TMI_HIP(timer.status);
-  TMI_HIP(lin_timer.status);
-  double factor_seconds = 0.0, subst_seconds = 0.0, graph_seconds = 0.0;
-  bool lin_pending = false;
-  // the sums of the first `count` quantities and max |gradient| into h_norms, and the pivot flag
-  auto fetch = [&](int count) -> int {
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3(count), block, 0, st, jobs, d_norms);
-    hipLaunchKernelGGL(nlp_absmax_kernel, dim3(1), block, 0, st, N, d_gabs, d_norms + 4);
-    if (timer.marked > 0) TMI_HIP(timer.mark());
-    const hipError_t le = hipGetLastError();
-    hipError_t ce = hipMemcpyAsync(h_norms, d_norms, 5 * sizeof(double), hipMemcpyDeviceToHost, st);
-    if (ce == hipSuccess) ce = hipMemcpyAsync(h_flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, st);
-    const hipError_t se = hipStreamSynchronize(st);
-    TMI_HIP(le);
-    TMI_HIP(ce);
-    TMI_HIP(se);
-    if (lin_pending) graph_seconds += lin_timer.seconds();
-    lin_pending = false;
-    return TMI_BA_OK;
-  };
-  // records, residuals and the cost parts at d_x, then M, its diagonal and the gradient
-  bool scaled = !opt->jacobi_scaling;
-  auto linearize = [&]() -> int {
-    lin_timer.marked = 0;
-    TMI_HIP(lin_timer.mark());
-    linearize_at(!scaled);
-    scaled = true;
-    TMI_HIP(lin_timer.mark());
-    lin_pending = true;
-    return TMI_BA_OK;
-  };
-  int rc;
-
-  // ---- the first linearisation, its cost and |x| (the step kernel on y = 0) ----
-  if ((rc = linearize())) return rc;
-  hipLaunchKernelGGL(nlp_step_kernel, entry_grid, block, 0, st, N, d_x, d_scale, d_y, d_step, d_cand, p_step, p_x);
-  TMI_HIP(hipMemsetAsync(p_mcc, 0, (size_t)nbE * sizeof(double), st));
-  if ((rc = fetch(4))) return rc;
-  double cost = h_norms[0], x_norm = std::sqrt(h_norms[3]);
-  sum->initial_cost = cost;
-
-  double radius = opt->initial_trust_region_radius, decrease_factor = 2.0;
-  int invalid_run = 0, iter = 0, termination = 1;
-  bool need_gradient_check = true;
-  cost_trace.push_back(cost);
-  radius_trace.push_back(radius);
-  outcome_trace.push_back(1);
-  auto record = [&](int outcome) {
-    cost_trace.push_back(cost);
-    radius_trace.push_back(radius);
-    outcome_trace.push_back(outcome);
-  };
-  for (;;) {
-    if (iter >= max_it) break;
-    ++iter;
-    timer.marked = 0;
-    TMI_HIP(timer.mark());
-    hipLaunchKernelGGL(nlp_copy_lower_kernel, dim3(N), block, 0, st, N, d_M, d_A);
-    hipLaunchKernelGGL(nlp_lm_diagonal_kernel, entry_grid, block, 0, st, N, d_diag, opt->min_lm_diagonal,
-                       opt->max_lm_diagonal, radius, d_A);
-    dense_cholesky_factor(d_A, N, d_cdiag, d_flag, st);
-    sum->num_factorizations++;
-    TMI_HIP(timer.mark());
-    TMI_HIP(hipMemcpyAsync(d_rhs, d_g, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, st));
-    dense_cholesky_substitute<1>(d_A, N, d_rhs, d_y, d_tmp, st);
-    TMI_HIP(timer.mark());
-    hipLaunchKernelGGL(nlp_step_kernel, entry_grid, block, 0, st, N, d_x, d_scale, d_y, d_step, d_cand, p_step, p_x);
-    candidate_at();
-    if ((rc = fetch(4))) return rc;
-    factor_seconds += timer.seconds(0, 1);
-    subst_seconds += timer.seconds(1, 2);
-    graph_seconds += timer.seconds(2, 3);
-    bool usable = true;
-    if (*h_flag) {  // a non-positive pivot: the linear solve failed, an invalid step as in Ceres
-      usable = false;
-      TMI_HIP(hipMemsetAsync(d_flag, 0, sizeof(int), st));
-    }
-    if (need_gradient_check) {
-      need_gradient_check = false;
-      if (!(h_norms[4] > opt->gradient_tolerance)) {
-        termination = 0;
-        --iter;
-        break;
-      }
-    }
-    const double cand_cost = h_norms[0], model_cost_change = h_norms[1], step_sq = h_norms[2], cand_x_sq = h_norms[3];
-    if (!(model_cost_change > 0.0)) usable = false;
-    if (!usable) {
-      // HandleInvalidStep
-      sum->num_unsuccessful_steps++;
-      if (++invalid_run >= opt->max_num_consecutive_invalid_steps) {
-        record(-1);
-        termination = 2;
-        break;
-      }
-      radius /= decrease_factor;
-      decrease_factor *= 2.0;
-      record(-1);
-      if (radius < opt->min_trust_region_radius) {
-        termination = 0;
-        break;
-      }
-      continue;
-    }
-    invalid_run = 0;
-    if (std::sqrt(step_sq) <= opt->parameter_tolerance * (x_norm + opt->parameter_tolerance)) {
-      record(2);
-      termination = 0;
-      break;
-    }
-    const double cost_change = cost - cand_cost;
-    if (std::fabs(cost_change) <= opt->function_tolerance * cost) {
-      record(3);
-      termination = 0;
-      break;
-    }
-    const double relative_decrease = cost_change / model_cost_change;
-    if (relative_decrease > opt->min_relative_decrease) {  // IsStepSuccessful
-      std::swap(d_x, d_cand);
-      cost = cand_cost;
-      x_norm = std::sqrt(cand_x_sq);
-      sum->num_successful_steps++;
-      radius = radius / std::fmax(1.0 / 3.0, 1.0 - std::pow(2.0 * relative_decrease - 1.0, 3));
-      radius = std::fmin(opt->max_trust_region_radius, radius);
-      decrease_factor = 2.0;
-      if ((rc = linearize())) return rc;
-      need_gradient_check = true;
-      record(1);
-    } else {
-      sum->num_unsuccessful_steps++;
-      radius /= decrease_factor;
-      decrease_factor *= 2.0;
-      record(0);
-    }
-    if (radius < opt->min_trust_region_radius) {
-      termination = 0;
-      break;
-    }
-  }
-
-  TMI_HIP(hipMemcpyAsync(x_h.data(), d_x, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
-  TMI_HIP(hipStreamSynchronize(st));
-  if (lin_pending) graph_seconds += lin_timer.seconds();
-  sum->num_iterations = iter;
-  sum->termination = termination;
-  sum->usable = termination != 2;
-  sum->final_cost = cost;
-  sum->factor_seconds = factor_seconds;
-  sum->substitution_seconds = subst_seconds;
-  sum->graph_seconds = graph_seconds;
-  sum->kernel_seconds = factor_seconds + subst_seconds + graph_seconds;
-  return TMI_BA_OK;
-}
-
-// What the nonlinear position estimator asks of its arguments beyond check_view_pair_batch, the connection to fixed_view
-// apart; null: fine.  Nothing is allocated here.
-const char* check_nonlinear_position_arguments(const tmi_ba_view_pair_batch* B,
-                                               const tmi_ba_nonlinear_position_options* o, int fixed_view,
-                                               const double* view_position) {
-  if (B->num_pairs == 0) return "nonlinear positions: no view pair";
-  if (fixed_view < 0 || fixed_view >= B->num_views) return "nonlinear positions: fixed_view out of range";
-  if (!(o->robust_loss_width > 0.0) || !std::isfinite(o->robust_loss_width))
-    return "nonlinear positions: robust_loss_width is not positive and finite (the reference CHECK_GTs it)";
-  if (o->max_num_iterations < 0) return "nonlinear positions: max_num_iterations < 0";
-  for (const double x : {o->function_tolerance, o->gradient_tolerance, o->parameter_tolerance,
-                         o->initial_trust_region_radius, o->max_trust_region_radius, o->min_trust_region_radius,
-                         o->min_relative_decrease, o->min_lm_diagonal, o->max_lm_diagonal})
-    if (!(x >= 0.0)) return "nonlinear positions: a radius, tolerance or LM diagonal bound that is negative or NaN";
-  if (!(o->initial_trust_region_radius > 0.0)) return "nonlinear positions: initial_trust_region_radius is 0";
-  if (o->positions_given && !all_finite(view_position, (size_t)3 * B->num_views))
-    return "nonlinear positions: positions_given with a non-finite position";
-  return nullptr;
-}
-
-// Component k of view v of the random start: 100 (2 u - 1), u from word 3 v + k of the splitmix64 stream of `seed`.
-double nonlinear_position_start(uint64_t seed, int v, int k) {
-  uint64_t z = seed + ((uint64_t)3 * (uint64_t)v + (uint64_t)k + 1) * 0x9e3779b97f4a7c15ULL;
-  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ULL;
-  z = (z ^ (z >> 27)) * 0x94d049bb133111ebULL;
-  z ^= z >> 31;
-  const double u = ((double)(z >> 11) + 0.5) * (1.0 / 9007199254740992.0);
-  const double centred = 2.0 * u - 1.0;
-  return 100.0 * centred;
-}
-}  // namespace
-extern "C" {
-
-void tmi_ba_nonlinear_position_options_init(tmi_ba_nonlinear_position_options* o) {
-  if (!o) return;
-  const SmallLmArgs A = ceres_default_lm_args(400, TMI_BA_LOSS_HUBER, 0.1);  // nonlinear_position_estimator.h:70-72
-  o->max_num_iterations = A.max_num_iterations;
-  o->robust_loss_width = A.loss_width;
-  o->positions_given = 0;
-  o->seed = 0;
-  o->jacobi_scaling = A.jacobi_scaling;
-  o->max_num_consecutive_invalid_steps = A.max_num_consecutive_invalid_steps;
-  o->function_tolerance = A.function_tolerance;
-  o->gradient_tolerance = A.gradient_tolerance;
-  o->parameter_tolerance = A.parameter_tolerance;
-  o->initial_trust_region_radius = A.initial_radius;
-  o->max_trust_region_radius = A.max_radius;
-  o->min_trust_region_radius = A.min_radius;
-  o->min_relative_decrease = A.min_relative_decrease;
-  o->min_lm_diagonal = A.lm_lo;
-  o->max_lm_diagonal = A.lm_hi;
-}
-
-int32_t tmi_ba_estimate_global_positions_nonlinear(const tmi_ba_view_pair_batch* Bh,
-                                                   const tmi_ba_nonlinear_position_options* opt, int32_t fixed_view,
-                                                   int32_t device, double* view_position, double* initial_position,
-                                                   double* iteration_cost, double* iteration_radius,
-                                                   int32_t* iteration_step_accepted, double* pair_residual,
-                                                   tmi_ba_nonlinear_position_summary* sum) {
-  if (!Bh || !opt || !view_position || !sum)
-    return bad_argument("nonlinear positions: null batch, options, view_position or summary");
-  memset(sum, 0, sizeof(*sum));
-  sum->termination = 2;
-  const double t0 = now_s();
-  // argument errors before the device is touched
-  if (const char* why = check_view_pair_batch(Bh, false, Bh->pair_position2)) return bad_argument(why);
-  if (const char* why = check_nonlinear_position_arguments(Bh, opt, fixed_view, view_position)) return bad_argument(why);
-  const int V = Bh->num_views, E = Bh->num_pairs, n = V - 1;
-  // the cap before anything of the views' size is allocated, the union-find included
-  if ((int64_t)3 * n > rotation_order_cap()) {
-    g_last_error = "nonlinear positions: 3 (num_views - 1) exceeds the dense solver's cap (see the header)";
-    return TMI_BA_ERR_UNSUPPORTED;
-  }
-  const int N = 3 * n;  // (<= the cap)
-  if (!every_view_reaches(Bh, fixed_view))
-    return bad_argument("nonlinear positions: a view is not connected to fixed_view");
-  const EdgeRows rows = build_edge_rows(V, E, Bh->pair_view1, Bh->pair_view2, fixed_view);
-  // the start: x [n][3] over the free views
-  std::vector<double> start((size_t)3 * V);
-  for (int v = 0; v < V; ++v)
-    for (int k = 0; k < 3; ++k)
-      start[(size_t)3 * v + k] = v == fixed_view ? 0.0
-                                 : opt->positions_given ? view_position[(size_t)3 * v + k]
-                                                        : nonlinear_position_start(opt->seed, v, k);
-  std::vector<double> x_h((size_t)N);
-  for (int v = 0; v < V; ++v)
-    if (v != fixed_view) std::copy(start.begin() + 3 * v, start.begin() + 3 * v + 3, x_h.begin() + 3 * (v - (v > fixed_view)));
-  const double width = opt->robust_loss_width;
-  return one_shot_batch(device, "nonlinear positions: no such device", E, t0, sum, [&](OneShot* s) -> int {
-    PositionGraph G;
-    memset(&G, 0, sizeof(G));
-    G.num_views = V;
-    G.num_pairs = E;
-    G.fixed_view = fixed_view;
-    int *d_v1, *d_v2, *d_ptr, *d_lptr;
-    int2 *d_row, *d_lrow;
-    double *d_pos, *d_t, *d_rot = nullptr, *d_rec, *d_res;
-    TMI_HIP(s->upload(&d_v1, (const int*)Bh->pair_view1, (size_t)E));
-    TMI_HIP(s->upload(&d_v2, (const int*)Bh->pair_view2, (size_t)E));
-    TMI_HIP(s->upload(&d_ptr, rows.row_ptr.data(), rows.row_ptr.size()));
-    TMI_HIP(s->upload(&d_row, rows.row.data(), rows.row.size()));
-    TMI_HIP(s->upload(&d_lptr, rows.lap_ptr.data(), rows.lap_ptr.size()));
-    TMI_HIP(s->upload(&d_lrow, rows.lap_row.data(), rows.lap_row.size()));
-    TMI_HIP(s->upload(&d_pos, Bh->pair_position2, (size_t)3 * E));
-    d_t = d_pos;
-    if (Bh->view_rotation) {
-      TMI_HIP(s->upload(&d_rot, Bh->view_rotation, (size_t)3 * V));
-      TMI_HIP(s->alloc(&d_t, (size_t)3 * E));
-    }
-    TMI_HIP(s->alloc(&d_rec, (size_t)9 * E));
-    TMI_HIP(s->alloc(&d_res, (size_t)3 * E));
-    G.pair_view1 = d_v1;
-    G.pair_view2 = d_v2;
-    G.t = d_t;
-    G.row_ptr = d_ptr;
-    G.row = d_row;
-    G.lap_ptr = d_lptr;
-    G.lap_row = d_lrow;
-    NormalLm L;
-    int rc;
-    if ((rc = L.alloc(s, N, E))) return rc;
-    hipStream_t st = s->stream;
-    const dim3 edge_grid(L.nbE), view_grid((n + 255) / 256), block(256);
-    // the directions, then the loop
-    if (Bh->view_rotation) hipLaunchKernelGGL(lud_direction_kernel, edge_grid, block, 0, st, E, d_rot, d_v1, d_pos, d_t);
-    rc = normal_lm_solve(
-        s, opt, sum, L, x_h,
-        [&](bool first_scaled) {
-          hipLaunchKernelGGL(nlp_edge_kernel<true>, edge_grid, block, 0, st, G, width, L.x, nullptr, d_rec, d_res,
-                             L.p_cost, nullptr);
-          if (first_scaled)
-            hipLaunchKernelGGL(nlp_scale_kernel<nlp::PositionBlocks>, view_grid, block, 0, st, G, n, d_rec, L.scale);
-          hipLaunchKernelGGL(nlp_assemble_kernel<nlp::PositionBlocks>, dim3(n), block, 0, st, G, N, d_rec, L.scale, L.M,
-                             L.diag, L.g, L.gabs);
-        },
-        [&]() {
-          hipLaunchKernelGGL(nlp_edge_kernel<false>, edge_grid, block, 0, st, G, width, L.cand, L.step, d_rec, nullptr,
-                             L.p_cost, L.p_mcc);
-        });
-    if (rc) return rc;
-    const std::vector<double>&cost_trace = L.cost_trace, &radius_trace = L.radius_trace;
-    const std::vector<int32_t>& outcome_trace = L.outcome_trace;
-    std::vector<double> res_h(pair_residual ? (size_t)3 * E : 0);
-    if (pair_residual) {
-      TMI_HIP(hipMemcpyAsync(res_h.data(), d_res, res_h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-      TMI_HIP(hipStreamSynchronize(st));
-    }
-    // the results, only now: a failure above leaves the caller's arrays as they were
-    for (int v = 0; v < V; ++v)
-      for (int k = 0; k < 3; ++k)
-        view_position[(size_t)3 * v + k] = v == fixed_view ? 0.0 : x_h[(size_t)3 * (v - (v > fixed_view)) + k];
-    if (initial_position) std::copy(start.begin(), start.end(), initial_position);
-    if (pair_residual) std::copy(res_h.begin(), res_h.end(), pair_residual);
-    if (iteration_cost) std::copy(cost_trace.begin(), cost_trace.end(), iteration_cost);
-    if (iteration_radius) std::copy(radius_trace.begin(), radius_trace.end(), iteration_radius);
-    if (iteration_step_accepted) std::copy(outcome_trace.begin(), outcome_trace.end(), iteration_step_accepted);
-    sum->num_views = V;
-    sum->num_pairs = E;
-    return TMI_BA_OK;
-  });
-}
-
-// ---- NonlinearRotationEstimator (rotation_nonlinear_kernels.h) ----------------------------------
-void tmi_ba_nonlinear_rotation_options_init(tmi_ba_nonlinear_rotation_options* o) {
-  if (!o) return;
-  // nonlinear_rotation_estimator.h (width 0.1), nonlinear_rotation_estimator.cc:94 (200 iterations)
-  const SmallLmArgs A = ceres_default_lm_args(200, TMI_BA_LOSS_SOFTLONE, 0.1);
-  o->max_num_iterations = A.max_num_iterations;
-  o->robust_loss_width = A.loss_width;
-  o->fixed_view = -1;
-  o->jacobi_scaling = A.jacobi_scaling;
-  o->max_num_consecutive_invalid_steps = A.max_num_consecutive_invalid_steps;
-  o->function_tolerance = A.function_tolerance;
-  o->gradient_tolerance = A.gradient_tolerance;
-  o->parameter_tolerance = A.parameter_tolerance;
-  o->initial_trust_region_radius = A.initial_radius;
-  o->max_trust_region_radius = A.max_radius;
-  o->min_trust_region_radius = A.min_radius;
-  o->min_relative_decrease = A.min_relative_decrease;
-  o->min_lm_diagonal = A.lm_lo;
-  o->max_lm_diagonal = A.lm_hi;
-}
-
-int32_t tmi_ba_estimate_global_rotations_nonlinear(const tmi_ba_view_pair_batch* Bh,
-                                                   const tmi_ba_nonlinear_rotation_options* opt,
-                                                   const uint8_t* view_given, int32_t device, double* view_rotation,
-                                                   double* iteration_cost, double* iteration_radius,
-                                                   int32_t* iteration_step_accepted, double* pair_residual,
-                                                   tmi_ba_nonlinear_rotation_summary* sum) {
-  if (!Bh || !opt || !view_rotation || !sum)
-    return bad_argument("nonlinear rotations: null batch, options, view_rotation or summary");
-  memset(sum, 0, sizeof(*sum));
-  sum->termination = 2;
-  const double t0 = now_s();
-  // argument errors before the device is touched; the batch's own view_rotation is not this call's
-  tmi_ba_view_pair_batch checked = *Bh;
-  checked.view_rotation = nullptr;
-  if (const char* why = check_view_pair_batch(&checked, false, Bh->pair_rotation2)) return bad_argument(why);
-  const int V = Bh->num_views, E_all = Bh->num_pairs, fixed_view = opt->fixed_view;
-  // the reference's two refusals (nonlinear_rotation_estimator.cc:53-62)
-  if (E_all == 0) return bad_argument("nonlinear rotations: no relative rotation constraint");
-  int num_given = 0;
-  for (int v = 0; v < V; ++v) num_given += !view_given || view_given[v];
-  if (num_given == 0) return bad_argument("nonlinear rotations: no view has an initialisation");
-  if (fixed_view < -1 || fixed_view >= V) return bad_argument("nonlinear rotations: fixed_view out of range");
-  if (fixed_view >= 0 && view_given && !view_given[fixed_view])
-    return bad_argument("nonlinear rotations: fixed_view has no initialisation");
-  if (!(opt->robust_loss_width > 0.0) || !std::isfinite(opt->robust_loss_width))
-    return bad_argument("nonlinear rotations: robust_loss_width is not positive and finite");
-  if (opt->max_num_iterations < 0) return bad_argument("nonlinear rotations: max_num_iterations < 0");
-  for (const double x : {opt->function_tolerance, opt->gradient_tolerance, opt->parameter_tolerance,
-                         opt->initial_trust_region_radius, opt->max_trust_region_radius, opt->min_trust_region_radius,
-                         opt->min_relative_decrease, opt->min_lm_diagonal, opt->max_lm_diagonal})
-    if (!(x >= 0.0)) return bad_argument("nonlinear rotations: a radius, tolerance or LM diagonal bound that is negative or NaN");
-  if (!(opt->initial_trust_region_radius > 0.0)) return bad_argument("nonlinear rotations: initial_trust_region_radius is 0");
-  for (int v = 0; v < V; ++v)
-    if ((!view_given || view_given[v]) && !all_finite(view_rotation + (size_t)3 * v, 3))
-      return bad_argument("nonlinear rotations: a marked view with a non-finite rotation");
-  // the problem: the edges between marked views in the caller's order, and the marked views with such an edge
-  std::vector<int> edge_of;  // [E] the caller's index of edge e of the problem
-  std::vector<int> view_index((size_t)V, -1), view_of;
-  for (int e = 0; e < E_all; ++e) {
-    const int a = Bh->pair_view1[e], b = Bh->pair_view2[e];
-    if (view_given && (!view_given[a] || !view_given[b])) continue;
-    edge_of.push_back(e);
-    view_index[a] = view_index[b] = 0;
-  }
-  for (int v = 0; v < V; ++v)
-    if (view_index[v] == 0) {
-      view_index[v] = (int)view_of.size();
-      view_of.push_back(v);
-    }
-  const int E = (int)edge_of.size(), Vp = (int)view_of.size();
-  // the held view's index in the problem; Vp: no view is held
-  const int held = fixed_view >= 0 && view_index[fixed_view] >= 0 ? view_index[fixed_view] : Vp;
-  const int n = held < Vp ? Vp - 1 : Vp;
-  // the cap before anything of the views' size is allocated
-  if ((int64_t)3 * n > rotation_order_cap()) {
-    g_last_error = "nonlinear rotations: 3 (free views) exceeds the dense solver's cap (see the header)";
-    return TMI_BA_ERR_UNSUPPORTED;
-  }
-  const int N = 3 * n;  // (<= the cap)
-  std::vector<int32_t> v1((size_t)E), v2((size_t)E);
-  std::vector<double> rel((size_t)3 * E), x_h((size_t)N), held_h(3, 0.0);
-  for (int e = 0; e < E; ++e) {
-    v1[e] = view_index[Bh->pair_view1[edge_of[e]]];
-    v2[e] = view_index[Bh->pair_view2[edge_of[e]]];
-    std::copy(Bh->pair_rotation2 + (size_t)3 * edge_of[e], Bh->pair_rotation2 + (size_t)3 * edge_of[e] + 3,
-              rel.begin() + (size_t)3 * e);
-  }
-  auto column_of = [&](int p) { return p == held ? -1 : p - (p > held); };
-  for (int p = 0; p < Vp; ++p) {
-    const double* src = view_rotation + (size_t)3 * view_of[p];
-    std::copy(src, src + 3, p == held ? held_h.begin() : x_h.begin() + (size_t)3 * column_of(p));
-  }
-  const EdgeRows rows = build_edge_rows(Vp, E, v1.data(), v2.data(), held);
-  const double width = opt->robust_loss_width;
-  if (E == 0) {  // an empty problem: solved
-    sum->termination = 0;
-    sum->usable = 1;
-  }
-  return one_shot_batch(device, "nonlinear rotations: no such device", E, t0, sum, [&](OneShot* s) -> int {
-    PositionGraph G;  // (an edge has two views, so n >= 1)
-    memset(&G, 0, sizeof(G));
-    G.num_views = Vp;
-    G.num_pairs = E;
-    G.fixed_view = held;
-    int *d_v1, *d_v2, *d_ptr, *d_lptr;
-    int2 *d_row, *d_lrow;
-    double *d_rel, *d_held, *d_rec, *d_res;
-    TMI_HIP(s->upload(&d_v1, (const int*)v1.data(), (size_t)E));
-    TMI_HIP(s->upload(&d_v2, (const int*)v2.data(), (size_t)E));
-    TMI_HIP(s->upload(&d_ptr, rows.row_ptr.data(), rows.row_ptr.size()));
-    TMI_HIP(s->upload(&d_row, rows.row.data(), rows.row.size()));
-    TMI_HIP(s->upload(&d_lptr, rows.lap_ptr.data(), rows.lap_ptr.size()));
-    TMI_HIP(s->upload(&d_lrow, rows.lap_row.data(), rows.lap_row.size()));
-    TMI_HIP(s->upload(&d_rel, rel.data(), rel.size()));
-    TMI_HIP(s->upload(&d_held, held_h.data(), held_h.size()));
-    TMI_HIP(s->alloc(&d_rec, (size_t)nlr::kRecordPlanes * E));
-    TMI_HIP(s->alloc(&d_res, (size_t)3 * E));
-    G.pair_view1 = d_v1;
-    G.pair_view2 = d_v2;
-    G.t = d_rel;
-    G.row_ptr = d_ptr;
-    G.row = d_row;
-    G.lap_ptr = d_lptr;
-    G.lap_row = d_lrow;
-    NormalLm L;
-    int rc;
-    if ((rc = L.alloc(s, N, E))) return rc;
-    hipStream_t st = s->stream;
-    const dim3 edge_grid(L.nbE), view_grid((n + 255) / 256), block(256);
-    rc = normal_lm_solve(
-        s, opt, sum, L, x_h,
-        [&](bool first_scaled) {
-          hipLaunchKernelGGL(nlr_edge_kernel<true>, edge_grid, block, 0, st, G, width, L.x, nullptr, d_held, d_rec,
-                             d_res, L.p_cost, nullptr);
-          if (first_scaled)
-            hipLaunchKernelGGL(nlp_scale_kernel<nlr::RotationBlocks>, view_grid, block, 0, st, G, n, d_rec, L.scale);
-          hipLaunchKernelGGL(nlp_assemble_kernel<nlr::RotationBlocks>, dim3(n), block, 0, st, G, N, d_rec, L.scale, L.M,
-                             L.diag, L.g, L.gabs);
-        },
-        [&]() {
-          hipLaunchKernelGGL(nlr_edge_kernel<false>, edge_grid, block, 0, st, G, width, L.cand, L.step, d_held, d_rec,
-                             nullptr, L.p_cost, L.p_mcc);
-        });
-    if (rc) return rc;
-    std::vector<double> res_h(pair_residual ? (size_t)3 * E : 0);
-    if (pair_residual) {
-      TMI_HIP(hipMemcpyAsync(res_h.data(), d_res, res_h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-      TMI_HIP(hipStreamSynchronize(st));
-    }
-    // the results, only now: a failure above leaves the caller's arrays as they were
-    for (int p = 0; p < Vp; ++p)
-      if (p != held) std::copy(x_h.begin() + (size_t)3 * column_of(p), x_h.begin() + (size_t)3 * column_of(p) + 3,
-                               view_rotation + (size_t)3 * view_of[p]);
-    if (pair_residual) {
-      std::fill(pair_residual, pair_residual + (size_t)3 * E_all, 0.0);
-      for (int e = 0; e < E; ++e)
-        std::copy(res_h.begin() + (size_t)3 * e, res_h.begin() + (size_t)3 * e + 3, pair_residual + (size_t)3 * edge_of[e]);
-    }
-    if (iteration_cost) std::copy(L.cost_trace.begin(), L.cost_trace.end(), iteration_cost);
-    if (iteration_radius) std::copy(L.radius_trace.begin(), L.radius_trace.end(), iteration_radius);
-    if (iteration_step_accepted) std::copy(L.outcome_trace.begin(), L.outcome_trace.end(), iteration_step_accepted);
-    sum->num_views = Vp;
-    sum->num_pairs = E;
-    return TMI_BA_OK;
-  });
-}
-
-// ---- LinearRotationEstimator (rotation_linear_kernels.h) -----------------------------------------
-void tmi_ba_linear_rotation_options_init(tmi_ba_linear_rotation_options* o) {
-  if (!o) return;
-  o->max_iterations = 1000;  // Spectra's maxit and tol, which linear_rotation_estimator.cc:173-177 leaves alone
-  o->tolerance = 1e-10;
-  o->relative_shift = 1e-9;  // 200 x the factorisation's rounding n eps 2 at the order cap
-  o->seed = 0;
-}
-
-int32_t tmi_ba_estimate_global_rotations_linear(const tmi_ba_view_pair_batch* Bh,
-                                                const tmi_ba_linear_rotation_options* opt, int32_t device,
-                                                double* view_rotation, tmi_ba_linear_rotation_summary* sum) {
-  if (!Bh || !opt || !view_rotation || !sum)
-    return bad_argument("linear rotations: null batch, options, view_rotation or summary");
-  memset(sum, 0, sizeof(*sum));
-  const double t0 = now_s();
-  // argument errors before the device is touched; the batch's own view_rotation is not this call's
-  tmi_ba_view_pair_batch checked = *Bh;
-  checked.view_rotation = nullptr;
-  if (const char* why = check_view_pair_batch(&checked, false, Bh->pair_rotation2)) return bad_argument(why);
-  const int V = Bh->num_views, E = Bh->num_pairs;
-  if (E == 0) return bad_argument("linear rotations: no relative rotation constraint (the reference CHECK_GTs them)");
-  if (opt->max_iterations <= 0) return bad_argument("linear rotations: max_iterations is not positive");
-  if (!(opt->tolerance > 0.0) || !std::isfinite(opt->tolerance))
-    return bad_argument("linear rotations: tolerance is not positive and finite");
-  if (!(opt->relative_shift >= 0.0) || !std::isfinite(opt->relative_shift))
-    return bad_argument("linear rotations: relative_shift is negative or not finite");
-  // the views of the problem: those with an edge, in ascending index
-  std::vector<int> view_index((size_t)V, -1), view_of;
-  for (int e = 0; e < E; ++e) view_index[Bh->pair_view1[e]] = view_index[Bh->pair_view2[e]] = 0;
-  for (int v = 0; v < V; ++v)
-    if (view_index[v] == 0) {
-      view_index[v] = (int)view_of.size();
-      view_of.push_back(v);
-    }
-  const int Vp = (int)view_of.size();
-  // the cap before anything of the matrix's size is allocated
-  if ((int64_t)3 * Vp > rotation_order_cap()) {
-    g_last_error = "linear rotations: 3 (views with an edge) exceeds the dense solver's cap (see the header)";
-    return TMI_BA_ERR_UNSUPPORTED;
-  }
-  const int n = 3 * Vp;  // (<= the cap)
-  std::vector<int32_t> v1((size_t)E), v2((size_t)E);
-  std::vector<int> parent((size_t)Vp);
-  for (int p = 0; p < Vp; ++p) parent[p] = p;
-  auto find = [&](int p) {
-    while (parent[p] != p) p = parent[p] = parent[parent[p]];
-    return p;
-  };
-  int components = Vp;
-  for (int e = 0; e < E; ++e) {
-    v1[e] = view_index[Bh->pair_view1[e]];
-    v2[e] = view_index[Bh->pair_view2[e]];
-    const int a = find(v1[e]), b = find(v2[e]);
-    if (a != b) {
-      parent[std::max(a, b)] = std::min(a, b);
-      --components;
-    }
-  }
-  if (components != 1)
-    return bad_argument("linear rotations: the view pairs are not connected (with c components the null space has 3 c "
-                        "dimensions; RemoveDisconnectedViewPairs comes first)");
-  const EdgeRows rows = build_edge_rows(Vp, E, v1.data(), v2.data(), Vp);
-  int max_degree = 0;
-  for (int p = 0; p < Vp; ++p) max_degree = std::max(max_degree, rows.row_ptr[(size_t)p + 1] - rows.row_ptr[p]);
-  const double lambda_bound = 2.0 * (double)max_degree;  // Gershgorin
-  const double mu = opt->relative_shift * (double)max_degree;
-  const double threshold = opt->tolerance * lambda_bound;
-  return one_shot_batch(device, "linear rotations: no such device", E, t0, sum, [&](OneShot* s) -> int {
-    hipStream_t st = s->stream;
-    const int nb = (n + 255) / 256;
-    const size_t block_words = (size_t)n * lin::kBlock;
-    int *d_ptr, *d_flag, *d_refl;
-    int2* d_row;
-    double *d_rel, *d_R, *d_A, *d_cdiag, *d_Q, *d_Y, *d_Z, *d_W, *d_tmp, *d_mgs[2], *d_gram, *d_res[3], *d_small, *d_rot;
-    TMI_HIP(s->upload(&d_ptr, rows.row_ptr.data(), rows.row_ptr.size()));
-    TMI_HIP(s->upload(&d_row, rows.row.data(), rows.row.size()));
-    TMI_HIP(s->upload(&d_rel, Bh->pair_rotation2, (size_t)3 * E));
-    TMI_HIP(s->alloc(&d_R, (size_t)9 * E));
-    TMI_HIP(s->alloc(&d_A, (size_t)n * n));  // M + mu I, overwritten by its factor
-    TMI_HIP(s->alloc(&d_cdiag, (size_t)kPanel * ((size_t)(n + kPanel - 1) / kPanel) * kPanel));
-    TMI_HIP(s->alloc(&d_Q, block_words));
-    TMI_HIP(s->alloc(&d_Y, block_words));
-    TMI_HIP(s->alloc(&d_Z, block_words));
-    TMI_HIP(s->alloc(&d_W, block_words));
-    TMI_HIP(s->alloc(&d_tmp, block_words));
-    for (double*& p : d_mgs) TMI_HIP(s->alloc(&p, (size_t)nb * lin::kBlock));
-    TMI_HIP(s->alloc(&d_gram, (size_t)nb * lin::kGram));
-    for (double*& p : d_res) TMI_HIP(s->alloc(&p, (size_t)nb));
-    TMI_HIP(s->alloc(&d_small, (size_t)lin::kSmallWords));
-    TMI_HIP(s->alloc(&d_rot, (size_t)3 * Vp));
-    TMI_HIP(s->alloc(&d_refl, (size_t)Vp));
-    TMI_HIP(s->alloc(&d_flag, 1));
-    PinnedWords pinned;  // the small block, then the pivot flag
-    TMI_HIP(pinned.alloc((lin::kSmallWords + 1) * sizeof(double)));
-    double* h_small = static_cast<double*>(pinned.p);
-    int* h_flag = reinterpret_cast<int*>(h_small + lin::kSmallWords);
-    lin::Graph G;
-    G.num_views = Vp;
-    G.num_pairs = E;
-    G.row_ptr = d_ptr;
-    G.row = d_row;
-    G.R = d_R;
-    const dim3 block(256), rows_grid(nb);
-    sum->num_views = Vp;
-    sum->num_pairs = E;
-    sum->order = n;
-    double factor_seconds = 0.0, subst_seconds = 0.0, graph_seconds = 0.0;
-    auto times = [&]() {
-      sum->factor_seconds = factor_seconds;
-      sum->substitution_seconds = subst_seconds;
-      sum->graph_seconds = graph_seconds;
-      sum->kernel_seconds = factor_seconds + subst_seconds + graph_seconds;
-    };
-    // what the queue has run into by now, after the stream has been waited for
-    auto settle = [&]() -> int {
-      const hipError_t le = hipGetLastError();
-      const hipError_t se = hipStreamSynchronize(st);
-      TMI_HIP(le);
-      TMI_HIP(se);
-      return TMI_BA_OK;
-    };
-    int rc;
-
-    // ---- the matrix, its factor and the start block: marks 0-1 and 2-3 graph kernels, 1-2 the factorisation ----
-    StreamTimer timer(st, 4);
-    TMI_HIP(timer.status);
-    TMI_HIP(timer.mark());
-    hipLaunchKernelGGL(lin_edge_matrix_kernel, dim3((E + 255) / 256), block, 0, st, E, d_rel, d_R);
-    hipLaunchKernelGGL(lin_assemble_kernel, dim3(Vp), block, 0, st, G, n, mu, d_A);
-    TMI_HIP(timer.mark());
-    TMI_HIP(hipMemsetAsync(d_flag, 0, sizeof(int), st));
-    dense_cholesky_factor(d_A, n, d_cdiag, d_flag, st);
-    TMI_HIP(timer.mark());
-    hipLaunchKernelGGL(lin_start_kernel, dim3(((int)block_words + 255) / 256), block, 0, st, n, (unsigned long long)opt->seed,
-                       d_Q);
-    TMI_HIP(timer.mark());
-    TMI_HIP(hipMemcpyAsync(h_flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
-    if ((rc = settle())) return rc;
-    graph_seconds += timer.seconds(0, 1) + timer.seconds(2, 3);
-    factor_seconds += timer.seconds(1, 2);
-    if (*h_flag) {  // a pivot of M + mu I that is not positive: nothing is written
-      times();
-      return TMI_BA_OK;
-    }
-    sum->usable = 1;
-
-    // ---- subspace iteration with Rayleigh-Ritz: marks 0-1 the substitution, 1-2 everything else ----
-    ReduceJobs jobs;
-    memset(&jobs, 0, sizeof(jobs));
-    for (int q = 0; q < 3; ++q) {
-      jobs.part[q] = d_res[q];
-      jobs.count[q] = nb;
-    }
-    int iter = 0, launches = 0;
-    bool converged = false;
-    while (iter < opt->max_iterations && !converged) {
-      ++iter;
-      timer.marked = 0;
-      TMI_HIP(timer.mark());
-      TMI_HIP(hipMemcpyAsync(d_W, d_Q, block_words * sizeof(double), hipMemcpyDeviceToDevice, st));
-      dense_cholesky_substitute<lin::kBlock>(d_A, n, d_W, d_Y, d_tmp, st);
-      TMI_HIP(timer.mark());
-      for (int pass = 0; pass < 2; ++pass)
-        for (int j = 0; j <= lin::kBlock; ++j, ++launches)
-          hipLaunchKernelGGL(lin_mgs_kernel, rows_grid, block, 0, st, n, j, d_Y, d_mgs[(launches + 1) & 1],
-                             d_mgs[launches & 1]);
-      hipLaunchKernelGGL(lin_apply_kernel, dim3((Vp * lin::kBlock + 255) / 256), block, 0, st, G, d_Y, d_Z);
-      hipLaunchKernelGGL(lin_gram_kernel, rows_grid, block, 0, st, n, d_Y, d_Z, d_gram);
-      hipLaunchKernelGGL(lin_ritz_kernel, dim3(1), dim3(64), 0, st, d_gram, nb, d_small);
-      hipLaunchKernelGGL(lin_rotate_kernel, rows_grid, block, 0, st, n, d_small, d_Y, d_Z, d_Q, d_res[0], d_res[1],
-                         d_res[2]);
-      hipLaunchKernelGGL(reduce_partials_kernel, dim3(3), block, 0, st, jobs, d_small + lin::kSmallResidual);
-      TMI_HIP(timer.mark());
-      TMI_HIP(hipMemcpyAsync(h_small, d_small, lin::kSmallWords * sizeof(double), hipMemcpyDeviceToHost, st));
-      if ((rc = settle())) return rc;
-      subst_seconds += timer.seconds(0, 1);
-      graph_seconds += timer.seconds(1, 2);
-      converged = true;
-      for (int j = 0; j < 3; ++j) {
-        sum->residual[j] = std::sqrt(h_small[lin::kSmallResidual + j]);
-        converged = converged && sum->residual[j] <= threshold;
-      }
-    }
-    for (int j = 0; j < 4; ++j) sum->eigenvalue[j] = h_small[lin::kSmallTheta + j];
-    sum->num_iterations = iter;
-    sum->converged = converged;
-
-    // ---- the projection of the last Ritz vectors ----
-    std::vector<double> rot_h((size_t)3 * Vp);
-    std::vector<int> refl_h((size_t)Vp);
-    timer.marked = 0;
-    TMI_HIP(timer.mark());
-    hipLaunchKernelGGL(lin_project_kernel, dim3((Vp + 255) / 256), block, 0, st, Vp, d_Q, d_rot, d_refl);
-    TMI_HIP(timer.mark());
-    TMI_HIP(hipMemcpyAsync(rot_h.data(), d_rot, rot_h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    TMI_HIP(hipMemcpyAsync(refl_h.data(), d_refl, refl_h.size() * sizeof(int), hipMemcpyDeviceToHost, st));
-    if ((rc = settle())) return rc;
-    graph_seconds += timer.seconds(0, 1);
-    times();
-    // the results, only now: a failure above leaves the caller's array as it was
-    for (int p = 0; p < Vp; ++p) {
-      std::copy(rot_h.begin() + (size_t)3 * p, rot_h.begin() + (size_t)3 * p + 3, view_rotation + (size_t)3 * view_of[p]);
-      sum->num_reflected += refl_h[p];
-    }
-    return TMI_BA_OK;
-  });
-}
-
 }  // extern "C"
 
 // ---- the sample-consensus scaffold of the batched RANSAC calls (ransac_core.h) -----------------
