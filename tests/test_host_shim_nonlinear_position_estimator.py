@@ -4,30 +4,15 @@ program checks the options' defaults against the reference's and every refusal (
 without a device that the call returns false and leaves the position map unchanged; with one (-m gpu) the reference's
 4-view scene within its bound, the id mapping in ascending order against the C ABI called directly, the views without a
 kept pair and the smallest id at the origin."""
-import os
 import subprocess
-import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import __graft_entry__ as entry  # noqa: E402
-
-LIB = os.path.join(ROOT, "theiasfm_amd", "lib")
+from shim_build import compile_shim
 
 
 def _compile(tmp_path):
-    entry.build_engine()
-    exe = str(tmp_path / "test_nonlinear_position_estimator_shim")
-    cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-pthread", "-I" + os.path.join(ROOT, "include"), "-o", exe,
-           os.path.join(ROOT, "tests", "cpp", "test_nonlinear_position_estimator_shim.cc"),
-           os.path.join(ROOT, "theiasfm_amd", "host", "nonlinear_position_ops.cc"),
-           "-L" + LIB, "-ltheia_mi355_ba", "-Wl,-rpath," + LIB, "-Wl,-rpath,/opt/rocm/lib",
-           "-Wl,-rpath-link,/opt/rocm/lib"]
-    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert p.returncode == 0, p.stderr
-    return exe
+    return compile_shim(tmp_path, "test_nonlinear_position_estimator_shim.cc", ["nonlinear_position_ops.cc"])
 
 
 def test_nonlinear_position_estimator_shim(tmp_path):

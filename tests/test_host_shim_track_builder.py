@@ -5,30 +5,16 @@ bulk add == single adds and an unknown view.  The same program also runs as a st
 address and undefined-behaviour sanitizers (its own main; nothing is loaded into python)."""
 import os
 import subprocess
-import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import __graft_entry__ as entry  # noqa: E402
+from shim_build import compile_shim
 
-LIB = os.path.join(ROOT, "theiasfm_amd", "lib")
-HOST = os.path.join(ROOT, "theiasfm_amd", "host")
 NO_DEVICE = dict(HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1")
 
 
-def _compile(tmp_path, name="test_track_builder_shim", extra=()):
-    entry.build_engine()
-    exe = str(tmp_path / name)
-    cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-pthread", *extra, "-I" + os.path.join(ROOT, "include"),
-           "-o", exe, os.path.join(ROOT, "tests", "cpp", "test_track_builder_shim.cc"),
-           os.path.join(HOST, "track_builder_ops.cc"),
-           "-L" + LIB, "-ltheia_mi355_ba", "-Wl,-rpath," + LIB, "-Wl,-rpath,/opt/rocm/lib",
-           "-Wl,-rpath-link,/opt/rocm/lib"]
-    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert p.returncode == 0, p.stderr
-    return exe
+def _compile(tmp_path, extra=()):
+    return compile_shim(tmp_path, "test_track_builder_shim.cc", ["track_builder_ops.cc"], extra)
 
 
 def test_track_builder_shim_without_a_device(tmp_path):
@@ -42,7 +28,7 @@ def test_track_builder_shim_under_host_sanitizers(tmp_path):
     """The stand-alone program with -fsanitize=address,undefined on the shim and the test (the engine library is not
     instrumented), no device visible.  Leak checking is off: the HIP runtime's start-up allocations are not the
     shim's."""
-    exe = _compile(tmp_path, "test_track_builder_shim_san",
+    exe = _compile(tmp_path,
                    ("-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"))
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", **NO_DEVICE)
     p = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=env)

@@ -3,28 +3,14 @@ tests/cpp/test_two_view_verification_shim.cc, compiled here with g++ into pytest
 batch call equals the C ABI bit for bit, position_2 has unit norm, inlier_indices are the status-0 indices in order."""
 import os
 import subprocess
-import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import __graft_entry__ as entry  # noqa: E402
-
-LIB = os.path.join(ROOT, "theiasfm_amd", "lib")
+from shim_build import compile_shim
 
 
 def _compile(tmp_path):
-    entry.build_engine()
-    exe = str(tmp_path / "test_two_view_verification_shim")
-    cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-pthread", "-I" + os.path.join(ROOT, "include"), "-o", exe,
-           os.path.join(ROOT, "tests", "cpp", "test_two_view_verification_shim.cc"),
-           os.path.join(ROOT, "theiasfm_amd", "host", "two_view_verify_ops.cc"),
-           "-L" + LIB, "-ltheia_mi355_ba", "-Wl,-rpath," + LIB, "-Wl,-rpath,/opt/rocm/lib",
-           "-Wl,-rpath-link,/opt/rocm/lib"]
-    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert p.returncode == 0, p.stderr
-    return exe
+    return compile_shim(tmp_path, "test_two_view_verification_shim.cc", ["two_view_verify_ops.cc"])
 
 
 def test_two_view_verification_shim_test_compiles(tmp_path):

@@ -3,31 +3,15 @@ tests/cpp/test_view_graph_shim.cc, compiled here with g++ -Wall -Werror into pyt
 has, the program checks the ViewGraph semantics of the reference's view_graph_test.cc; without a device that
 RemoveDisconnectedViewPairs, OrientationsFromMaximumSpanningTree and the ViewGraph forms of the two filters change
 nothing; with one (-m gpu) that they agree with the C ABI."""
-import os
 import subprocess
-import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import __graft_entry__ as entry  # noqa: E402
-
-LIB = os.path.join(ROOT, "theiasfm_amd", "lib")
+from shim_build import compile_shim
 
 
 def _compile(tmp_path):
-    entry.build_engine()
-    exe = str(tmp_path / "test_view_graph_shim")
-    cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-pthread", "-I" + os.path.join(ROOT, "include"), "-o", exe,
-           os.path.join(ROOT, "tests", "cpp", "test_view_graph_shim.cc"),
-           os.path.join(ROOT, "theiasfm_amd", "host", "view_graph_ops.cc"),
-           os.path.join(ROOT, "theiasfm_amd", "host", "view_pair_filter_ops.cc"),
-           "-L" + LIB, "-ltheia_mi355_ba", "-Wl,-rpath," + LIB, "-Wl,-rpath,/opt/rocm/lib",
-           "-Wl,-rpath-link,/opt/rocm/lib"]
-    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert p.returncode == 0, p.stderr
-    return exe
+    return compile_shim(tmp_path, "test_view_graph_shim.cc", ["view_graph_ops.cc", "view_pair_filter_ops.cc"])
 
 
 def test_view_graph_shim(tmp_path):

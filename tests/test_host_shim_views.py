@@ -3,29 +3,15 @@ in ascending ViewId order -- success, costs and parameters -- on a private-intri
 reconstruction (tests/cpp/test_views_shim.cc, compiled here with g++ into pytest's tmp_path)."""
 import os
 import subprocess
-import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import __graft_entry__ as entry  # noqa: E402
-
-LIB = os.path.join(ROOT, "theiasfm_amd", "lib")
+from shim_build import compile_shim
 
 
 def _compile(tmp_path):
-    entry.build_engine()
-    exe = str(tmp_path / "test_views_shim")
-    cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-pthread", "-I" + os.path.join(ROOT, "include"), "-o", exe,
-           os.path.join(ROOT, "tests", "cpp", "test_views_shim.cc"),
-           os.path.join(ROOT, "theiasfm_amd", "host", "bundle_adjuster.cc"),
-           os.path.join(ROOT, "theiasfm_amd", "host", "view_ops.cc"),
-           "-L" + LIB, "-ltheia_mi355_ba", "-Wl,-rpath," + LIB, "-Wl,-rpath,/opt/rocm/lib",
-           "-Wl,-rpath-link,/opt/rocm/lib"]
-    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert p.returncode == 0, p.stderr
-    return exe
+    # (this program is built with -Wall, without -Werror)
+    return compile_shim(tmp_path, "test_views_shim.cc", ["bundle_adjuster.cc", "view_ops.cc"], ("-Wno-error",))
 
 
 def test_views_shim_compiles(tmp_path):

@@ -4,9 +4,9 @@
 // tmi_ba_view_pair_batch -- a rotation per view, numbered in ascending ViewId order, and the TwoViewInfo of every
 // edge -- and filtered in one device call.
 #include <cstdio>
-#include <map>
 #include <vector>
 
+#include "flat_view_graph.h"
 #include "theia/sfm/filter_view_pairs_from_orientation.h"
 #include "theia/sfm/filter_view_pairs_from_relative_translation.h"
 #include "theia_mi355_ba.h"
@@ -17,45 +17,24 @@ using EdgeList = std::vector<std::pair<ViewIdPair, TwoViewInfo*>>;
 
 // The edges that go to the device (`sent`: their places in the caller's vector) on dense view indices.
 struct FlatEdges {
-  std::vector<double> rotation, rotation2, position2;
-  std::vector<int32_t> view1, view2;
+  flat_view_graph::FlatViewGraph graph;
+  std::vector<double> rotation;
   std::vector<size_t> sent;
-  tmi_ba_view_pair_batch Batch() const {
-    tmi_ba_view_pair_batch B;
-    B.num_views = static_cast<int32_t>(rotation.size() / 3);
-    B.view_rotation = rotation.data();
-    B.num_pairs = static_cast<int32_t>(sent.size());
-    B.pair_view1 = view1.data();
-    B.pair_view2 = view2.data();
-    B.pair_rotation2 = rotation2.data();
-    B.pair_position2 = position2.data();
-    return B;
-  }
+  tmi_ba_view_pair_batch Batch() const { return graph.Batch(rotation.data()); }
 };
 
-// usable[e] != 0: edge e has an info and both orientations.
+// usable[e] != 0: edge e has an info and both orientations.  The views of the usable edges get a row; the usable edges
+// are sent in the caller's order.
 FlatEdges Flatten(const std::unordered_map<ViewId, Eigen::Vector3d>& orientations, const EdgeList& edges,
                   const std::vector<char>& usable) {
   FlatEdges flat;
-  std::map<ViewId, int> index;  // ascending ViewId -> dense index
+  for (size_t e = 0; e < edges.size(); ++e)
+    if (usable[e]) flat.graph.views.Add(edges[e].first);
+  flat.graph.views.Finish();
+  flat.rotation = flat.graph.views.Gather(orientations);
   for (size_t e = 0; e < edges.size(); ++e) {
     if (!usable[e]) continue;
-    index[edges[e].first.first] = 0;
-    index[edges[e].first.second] = 0;
-  }
-  for (auto& entry : index) {
-    entry.second = static_cast<int>(flat.rotation.size() / 3);
-    const Eigen::Vector3d& r = orientations.find(entry.first)->second;
-    for (int a = 0; a < 3; ++a) flat.rotation.push_back(r[a]);
-  }
-  for (size_t e = 0; e < edges.size(); ++e) {
-    if (!usable[e]) continue;
-    flat.view1.push_back(index[edges[e].first.first]);
-    flat.view2.push_back(index[edges[e].first.second]);
-    for (int a = 0; a < 3; ++a) {
-      flat.rotation2.push_back(edges[e].second->rotation_2[a]);
-      flat.position2.push_back(edges[e].second->position_2[a]);
-    }
+    flat.graph.AddPair(edges[e].first, &edges[e].second->rotation_2, &edges[e].second->position_2);
     flat.sent.push_back(e);
   }
   return flat;
@@ -104,19 +83,14 @@ int FilterViewPairsFromRelativeTranslation(const FilterViewPairsFromRelativeTran
                            "axes: nothing filtered\n");
       return 0;
     }
-    for (const Eigen::Vector3d& a : options.axes)
-      for (int k = 0; k < 3; ++k) axes.push_back(a[k]);
+    for (const Eigen::Vector3d& a : options.axes) flat_view_graph::Append(a, &axes);
   }
   std::vector<uint8_t> flag(flat.sent.size(), 0);
   tmi_ba_view_pair_filter_summary fs;
   const int rc = tmi_ba_filter_view_pairs_from_relative_translation(
       &B, &o, axes.empty() ? nullptr : axes.data(), axes.empty() ? 0 : 1, device, flag.data(), nullptr, nullptr,
       nullptr, &fs);
-  if (rc != TMI_BA_OK) {
-    std::fprintf(stderr, "[theia::FilterViewPairsFromRelativeTranslation] device call failed: %s\n",
-                 tmi_ba_last_error());
-    return 0;
-  }
+  if (flat_view_graph::DeviceCallFailed("[theia::FilterViewPairsFromRelativeTranslation]", rc)) return 0;
   std::vector<char> remove(edges->size(), 0);
   for (size_t p = 0; p < flat.sent.size(); ++p) remove[flat.sent[p]] = flag[p] != 0;
   return EraseMarked(remove, edges);
@@ -137,10 +111,7 @@ int FilterViewPairsFromOrientation(const std::unordered_map<ViewId, Eigen::Vecto
     tmi_ba_view_pair_filter_summary fs;
     const int rc = tmi_ba_filter_view_pairs_from_orientation(&B, max_relative_rotation_difference_degrees, device,
                                                              flag.data(), nullptr, &fs);
-    if (rc != TMI_BA_OK) {
-      std::fprintf(stderr, "[theia::FilterViewPairsFromOrientation] device call failed: %s\n", tmi_ba_last_error());
-      return 0;
-    }
+    if (flat_view_graph::DeviceCallFailed("[theia::FilterViewPairsFromOrientation]", rc)) return 0;
   }
   // :94-103: an edge with a view that has no orientation is removed
   std::vector<char> remove(edges->size(), 0);
