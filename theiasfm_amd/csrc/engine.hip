@@ -4012,6 +4012,7 @@ int32_t tmi_ba_solve(tmi_ba_problem* P, const tmi_ba_options* O, tmi_ba_summary*
 }  // extern "C"
 
 // ---- one-shot calls and the batched small-problem solvers -----------------------------------------
+#include "one_shot.h"
 #include "side_calls.h"
 #include "pose_graph_calls.h"
 

@@ -3,9 +3,7 @@
 // view table and an edge list into the rows of a PoseGraph (pose_graph.h; built by pose_graph_host.h, uploaded by
 // PoseGraphDevice), works on ONE dense symmetric positive definite matrix of order <= kRotationMaxOrder (DenseSpd) and
 // loops on the host around a substitution, a few per-edge and per-view kernels and one read-back of a few sums and the
-// pivot flag (ScalarFetch), with its device time in three classes (ClassSeconds).  Included by engine.hip after
-// side_calls.h: OneShot, StreamTimer, PinnedWords, one_shot_batch, bad_argument, all_finite and check_view_pair_batch
-// are side_calls.h's.
+// pivot flag (ScalarFetch), with its device time in three classes (ClassSeconds).  Written on one_shot.h.
 #pragma once
 
 #include "pose_graph_host.h"
@@ -93,8 +91,7 @@ struct DenseSpd {
     TMI_HIP(s->alloc(&A, (size_t)N * N));
     TMI_HIP(s->alloc(&cdiag, (size_t)kPanel * ((size_t)(N + kPanel - 1) / kPanel) * kPanel));
     TMI_HIP(s->alloc(&tmp, (size_t)nrhs * N));
-    TMI_HIP(s->alloc(&flag, 1));
-    TMI_HIP(hipMemsetAsync(flag, 0, sizeof(int), s->stream));
+    TMI_HIP(s->alloc_filled(&flag, 1, 0));
     return TMI_BA_OK;
   }
   void factor(hipStream_t st) {
@@ -111,7 +108,7 @@ struct DenseSpd {
 // max |.| of a vector behind them (absmax), into the device words d_norms, and from there with the pivot flag into
 // pinned memory.
 struct ScalarFetch {
-  PinnedWords pinned;
+  Pinned<double> pinned;
   double *h_norms = nullptr, *d_norms = nullptr;
   int *h_flag = nullptr, *d_flag = nullptr;
   ReduceJobs jobs;
@@ -121,8 +118,8 @@ struct ScalarFetch {
     d_flag = pivot_flag;
     memset(&jobs, 0, sizeof(jobs));
     TMI_HIP(s->alloc(&d_norms, (size_t)words + 2));
-    TMI_HIP(pinned.alloc(((size_t)words + 2) * sizeof(double)));
-    h_norms = static_cast<double*>(pinned.p);
+    TMI_HIP(pinned.alloc((size_t)words + 2));
+    h_norms = pinned.get();
     h_flag = reinterpret_cast<int*>(h_norms + words);
     return TMI_BA_OK;
   }
@@ -141,14 +138,10 @@ struct ScalarFetch {
     if (absmax) hipLaunchKernelGGL(nlp_absmax_kernel, dim3(1), dim3(256), 0, st, absmax_n, absmax, d_norms + count);
     if (words < 0) words = count + (absmax ? 1 : 0);
     TMI_HIP(T->end());
-    const hipError_t le = hipGetLastError();
-    hipError_t ce = hipSuccess;
-    if (words > 0) ce = hipMemcpyAsync(h_norms, d_norms, (size_t)words * sizeof(double), hipMemcpyDeviceToHost, st);
-    if (ce == hipSuccess && with_flag) ce = hipMemcpyAsync(h_flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, st);
-    const hipError_t se = hipStreamSynchronize(st);
-    TMI_HIP(le);
-    TMI_HIP(ce);
-    TMI_HIP(se);
+    ReadBack rb(st);
+    rb.add(h_norms, d_norms, (size_t)words);
+    if (with_flag) rb.add(h_flag, d_flag, 1);
+    TMI_HIP(rb.finish());
     T->collect();
     return TMI_BA_OK;
   }
@@ -215,7 +208,7 @@ int32_t tmi_ba_estimate_global_rotations_robust(const tmi_ba_relative_rotation_b
   const int L1 = opt->max_num_l1_iterations, IR = opt->max_num_irls_iterations;
   std::vector<int> admm_trace;
   std::vector<double> l1_trace, irls_trace, irls_sq_trace;
-  return one_shot_batch(device, "robust rotations: no such device", E, t0, sum, [&](OneShot* s) -> int {
+  return one_shot_batch(device, "robust rotations: no such device", E, t0, &sum->seconds, [&](OneShot* s) -> int {
     int rc;
     double *d_rel, *d_o, *d_r, *d_w, *d_z, *d_u, *d_dz, *d_rhs, *d_x, *d_diag_w, *d_part;
     TMI_HIP(s->upload(&d_rel, Bh->pair_rotation, (size_t)3 * E));
@@ -341,8 +334,8 @@ int32_t tmi_ba_estimate_global_rotations_robust(const tmi_ba_relative_rotation_b
 
     // the results, only now: a failure above leaves the caller's arrays as they were
     std::vector<double> o_h((size_t)3 * V), r_h(pair_residual ? (size_t)3 * E : 0);
-    TMI_HIP(hipMemcpyAsync(o_h.data(), d_o, o_h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (pair_residual) TMI_HIP(hipMemcpyAsync(r_h.data(), d_r, r_h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    TMI_HIP(s->download(o_h.data(), d_o, o_h.size()));
+    TMI_HIP(s->download(r_h.data(), d_r, r_h.size()));
     TMI_HIP(hipStreamSynchronize(st));
     std::copy(o_h.begin(), o_h.end(), view_rotation);
     if (pair_residual) std::copy(r_h.begin(), r_h.end(), pair_residual);
@@ -406,7 +399,7 @@ int32_t tmi_ba_estimate_global_positions_lud(const tmi_ba_view_pair_batch* Bh, c
   const int max_it = opt->max_num_iterations;
   const double rho = opt->rho, alpha = opt->alpha;
   std::vector<double> r_trace, s_trace;
-  return one_shot_batch(device, "LUD positions: no such device", E, t0, sum, [&](OneShot* s) -> int {
+  return one_shot_batch(device, "LUD positions: no such device", E, t0, &sum->seconds, [&](OneShot* s) -> int {
     int rc;
     double *d_pos, *d_t, *d_rot = nullptr, *d_qs, *d_z, *d_u, *d_dz, *d_scale, *d_ax, *d_rhs, *d_p, *d_part;
     TMI_HIP(s->upload(&d_pos, Bh->pair_position2, (size_t)3 * E));
@@ -489,9 +482,9 @@ int32_t tmi_ba_estimate_global_positions_lud(const tmi_ba_view_pair_batch* Bh, c
 
     // the results, only now: a failure above leaves the caller's arrays as they were
     std::vector<double> p_h((size_t)N), scale_h(pair_scale ? (size_t)E : 0), ax_h(pair_residual ? (size_t)3 * E : 0);
-    TMI_HIP(hipMemcpyAsync(p_h.data(), d_p, p_h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (pair_scale) TMI_HIP(hipMemcpyAsync(scale_h.data(), d_scale, scale_h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (pair_residual) TMI_HIP(hipMemcpyAsync(ax_h.data(), d_ax, ax_h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    TMI_HIP(s->download(p_h.data(), d_p, p_h.size()));
+    TMI_HIP(s->download(scale_h.data(), d_scale, scale_h.size()));
+    TMI_HIP(s->download(ax_h.data(), d_ax, ax_h.size()));
     TMI_HIP(hipStreamSynchronize(st));
     scatter_free(V, fixed_view, nullptr, p_h.data(), view_position);
     std::fill(view_position + (size_t)3 * fixed_view, view_position + (size_t)3 * fixed_view + 3, 0.0);
@@ -693,7 +686,7 @@ int normal_lm_solve(OneShot* s, const Opt* opt, Sum* sum, NormalLm& L, std::vect
     }
   }
 
-  TMI_HIP(hipMemcpyAsync(x_h.data(), d_x, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
+  TMI_HIP(s->download(x_h.data(), d_x, (size_t)N));
   TMI_HIP(hipStreamSynchronize(st));
   T.collect();
   sum->num_iterations = iter;
@@ -773,7 +766,7 @@ int32_t tmi_ba_estimate_global_positions_nonlinear(const tmi_ba_view_pair_batch*
   std::vector<double> x_h((size_t)N);
   gather_free(V, fixed_view, nullptr, start.data(), x_h.data());
   const double width = opt->robust_loss_width;
-  return one_shot_batch(device, "nonlinear positions: no such device", E, t0, sum, [&](OneShot* s) -> int {
+  return one_shot_batch(device, "nonlinear positions: no such device", E, t0, &sum->seconds, [&](OneShot* s) -> int {
     int rc;
     double *d_pos, *d_t, *d_rot = nullptr, *d_rec, *d_res;
     TMI_HIP(s->upload(&d_pos, Bh->pair_position2, (size_t)3 * E));
@@ -811,7 +804,7 @@ int32_t tmi_ba_estimate_global_positions_nonlinear(const tmi_ba_view_pair_batch*
     if (rc) return rc;
     std::vector<double> res_h(pair_residual ? (size_t)3 * E : 0);
     if (pair_residual) {
-      TMI_HIP(hipMemcpyAsync(res_h.data(), d_res, res_h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+      TMI_HIP(s->download(res_h.data(), d_res, res_h.size()));
       TMI_HIP(hipStreamSynchronize(st));
     }
     // the results, only now: a failure above leaves the caller's arrays as they were
@@ -890,7 +883,7 @@ int32_t tmi_ba_estimate_global_rotations_nonlinear(const tmi_ba_view_pair_batch*
     sum->termination = 0;
     sum->usable = 1;
   }
-  return one_shot_batch(device, "nonlinear rotations: no such device", E, t0, sum, [&](OneShot* s) -> int {
+  return one_shot_batch(device, "nonlinear rotations: no such device", E, t0, &sum->seconds, [&](OneShot* s) -> int {
     int rc;  // (an edge has two views, so n >= 1)
     double *d_rel, *d_held, *d_rec, *d_res;
     TMI_HIP(s->upload(&d_rel, rel.data(), rel.size()));
@@ -921,7 +914,7 @@ int32_t tmi_ba_estimate_global_rotations_nonlinear(const tmi_ba_view_pair_batch*
     if (rc) return rc;
     std::vector<double> res_h(pair_residual ? (size_t)3 * E : 0);
     if (pair_residual) {
-      TMI_HIP(hipMemcpyAsync(res_h.data(), d_res, res_h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+      TMI_HIP(s->download(res_h.data(), d_res, res_h.size()));
       TMI_HIP(hipStreamSynchronize(st));
     }
     // the results, only now: a failure above leaves the caller's arrays as they were (the held view's is not written)
@@ -985,7 +978,7 @@ int32_t tmi_ba_estimate_global_rotations_linear(const tmi_ba_view_pair_batch* Bh
   const double lambda_bound = 2.0 * (double)max_degree;  // Gershgorin
   const double mu = opt->relative_shift * (double)max_degree;
   const double threshold = opt->tolerance * lambda_bound;
-  return one_shot_batch(device, "linear rotations: no such device", E, t0, sum, [&](OneShot* s) -> int {
+  return one_shot_batch(device, "linear rotations: no such device", E, t0, &sum->seconds, [&](OneShot* s) -> int {
     int rc;
     hipStream_t st = s->stream;
     const int nb = (n + 255) / 256;
@@ -1072,12 +1065,10 @@ int32_t tmi_ba_estimate_global_rotations_linear(const tmi_ba_view_pair_batch* Bh
     TMI_HIP(T.begin(T.kGraph));
     hipLaunchKernelGGL(lin_project_kernel, dim3((Vp + 255) / 256), block, 0, st, Vp, d_Q, d_rot, d_refl);
     TMI_HIP(T.end());
-    TMI_HIP(hipMemcpyAsync(rot_h.data(), d_rot, rot_h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    TMI_HIP(hipMemcpyAsync(refl_h.data(), d_refl, refl_h.size() * sizeof(int), hipMemcpyDeviceToHost, st));
-    const hipError_t le = hipGetLastError();
-    const hipError_t se = hipStreamSynchronize(st);
-    TMI_HIP(le);
-    TMI_HIP(se);
+    TMI_HIP(s->download(rot_h.data(), d_rot, rot_h.size()));
+    TMI_HIP(s->download(refl_h.data(), d_refl, refl_h.size()));
+    ReadBack rb(st);  // (the launch error is taken after the copies here)
+    TMI_HIP(rb.finish());
     T.collect();
     T.write(sum);
     // the results, only now: a failure above leaves the caller's array as it was

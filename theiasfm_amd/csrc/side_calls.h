@@ -1,186 +1,10 @@
 // Host side of the one-shot calls and the batched small-problem solvers (small_lm.h): the C entry points beside the LM
-// driver, and the scaffold they share.  Included by engine.hip after the driver: tmi_ba_solver, create_impl,
-// prepare_cameras, launch_track_lm and TMI_HIP are the driver's.  The five global pose estimators (robust, nonlinear and
-// linear rotations, LUD and nonlinear positions) with rotation_order_cap, NormalLm and normal_lm_solve are in
-// pose_graph_calls.h, which is included after this file and uses OneShot, StreamTimer, PinnedWords, one_shot_batch,
-// bad_argument, all_finite and check_view_pair_batch from here.
+// driver, written on one_shot.h.  Included by engine.hip after the driver: tmi_ba_solver, prepare_cameras,
+// launch_track_lm and TMI_HIP are the driver's.  The five global pose estimators (robust, nonlinear and linear
+// rotations, LUD and nonlinear positions) are in pose_graph_calls.h.
 #pragma once
 
 namespace {
-// Device memory of one call, freed on every way out, and the stream it runs on: a stream of its own (open) or a
-// borrowed one.  error: what TMI_HIP reports.
-struct OneShot {
-  std::string error;
-  std::vector<void*> allocs;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
-  explicit OneShot(hipStream_t borrowed = nullptr) : stream(borrowed) {}
-  OneShot(const OneShot&) = delete;
-  OneShot& operator=(const OneShot&) = delete;
-  // a stream of its own on `device` (< 0: the current device)
-  int open(int device) {
-    OneShot* s = this;
-    if (device >= 0) TMI_HIP(hipSetDevice(device));
-    TMI_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-    own_stream = true;
-    return TMI_BA_OK;
-  }
-  template <class T>
-  hipError_t alloc(T** p, size_t n) {
-    *p = nullptr;
-    const hipError_t e = hipMalloc((void**)p, std::max<size_t>(n, 1) * sizeof(T));
-    if (e == hipSuccess) allocs.push_back((void*)*p);
-    return e;
-  }
-  template <class T>
-  hipError_t upload(T** p, const T* h, size_t n) {
-    hipError_t e = alloc(p, n);
-    if (e == hipSuccess && n) e = hipMemcpyAsync(*p, h, n * sizeof(T), hipMemcpyHostToDevice, stream);
-    return e;
-  }
-  // per-item outputs of a batched solve, preset to "nothing to solve" (-1, 0, 0, 0)
-  int alloc_outputs(SmallLmOut* o, size_t n) {
-    OneShot* s = this;
-    TMI_HIP(alloc(&o->term, n));
-    TMI_HIP(alloc(&o->iters, n));
-    TMI_HIP(alloc(&o->c0, n));
-    TMI_HIP(alloc(&o->c1, n));
-    n = std::max<size_t>(n, 1);
-    TMI_HIP(hipMemsetAsync(o->term, 0xff, n, stream));
-    TMI_HIP(hipMemsetAsync(o->iters, 0, n * sizeof(int), stream));
-    TMI_HIP(hipMemsetAsync(o->c0, 0, n * sizeof(double), stream));
-    TMI_HIP(hipMemsetAsync(o->c1, 0, n * sizeof(double), stream));
-    return TMI_BA_OK;
-  }
-  ~OneShot() {
-    if (own_stream) hipStreamDestroy(stream);
-    for (void* p : allocs) hipFree(p);
-  }
-};
-
-// Device time between marks on a stream: every mark() records the next event; seconds(a, b) is the time from mark a to
-// mark b once the stream has been synchronised (0 where the runtime cannot tell).  The events are destroyed on every
-// way out.
-struct StreamTimer {
-  static constexpr int kMaxMarks = 4;
-  hipStream_t stream;
-  hipEvent_t ev[kMaxMarks] = {};
-  hipError_t status = hipSuccess;  // of creating the events: TMI_HIP(timer.status) before the first mark
-  int marked = 0;
-  explicit StreamTimer(hipStream_t stream_, int marks = 2) : stream(stream_) {
-    for (int i = 0; i < marks && status == hipSuccess; ++i) status = hipEventCreate(&ev[i]);
-  }
-  StreamTimer(const StreamTimer&) = delete;
-  StreamTimer& operator=(const StreamTimer&) = delete;
-  hipError_t mark() { return hipEventRecord(ev[marked++], stream); }
-  double seconds(int a = 0, int b = 1) const {
-    float ms = 0.f;
-    hipEventElapsedTime(&ms, ev[a], ev[b]);
-    return 1e-3 * ms;
-  }
-  ~StreamTimer() {
-    for (hipEvent_t e : ev)
-      if (e) hipEventDestroy(e);
-  }
-};
-
-// The caller's per-item arrays (each may be null).
-struct ItemArrays {
-  int8_t* term;
-  int32_t* iters;
-  double* c0;
-  double* c1;
-};
-
-// One batched small-problem solve: launch() queues it on `stream` between two events (sum->kernel_seconds), then the n
-// per-item outputs d are read back, counted (*num_items: termination >= 0; successes 0 and 1) and item i is written to
-// the caller's arrays at map[i] (null: the identity; map[i] < 0: padding).  term_h (optional): the terminations.
-// TMI_HIP reports into s->error.
-template <class Holder, class Sum, class Launch>
-int run_small_lm(Holder* s, hipStream_t stream, const SmallLmOut& d, size_t n, const int* map, Launch launch,
-                 const ItemArrays& out, Sum* sum, int64_t* num_items, std::vector<signed char>* term_h = nullptr) {
-  StreamTimer timer(stream);
-  TMI_HIP(timer.status);
-  timer.mark();
-  launch();
-  timer.mark();
-  const hipError_t le = hipGetLastError();
-  std::vector<signed char> term(n);
-  std::vector<int> iters(n);
-  std::vector<double> c0(out.c0 ? n : 0), c1(out.c1 ? n : 0);
-  hipError_t ce = hipSuccess;
-  if (n) {
-    ce = hipMemcpyAsync(term.data(), d.term, n, hipMemcpyDeviceToHost, stream);
-    if (ce == hipSuccess) ce = hipMemcpyAsync(iters.data(), d.iters, n * sizeof(int), hipMemcpyDeviceToHost, stream);
-    if (ce == hipSuccess && out.c0) ce = hipMemcpyAsync(c0.data(), d.c0, n * sizeof(double), hipMemcpyDeviceToHost, stream);
-    if (ce == hipSuccess && out.c1) ce = hipMemcpyAsync(c1.data(), d.c1, n * sizeof(double), hipMemcpyDeviceToHost, stream);
-  }
-  const hipError_t se = hipStreamSynchronize(stream);
-  TMI_HIP(le);
-  TMI_HIP(ce);
-  TMI_HIP(se);
-  for (size_t i = 0; i < n; ++i) {
-    const int p = map ? map[i] : (int)i;
-    if (p < 0) continue;
-    const int t = term[i];
-    if (t >= 0) {
-      ++*num_items;
-      if (t == 0 || t == 1) sum->num_success++;
-      sum->total_iterations += iters[i];
-    }
-    if (out.term) out.term[p] = (int8_t)t;
-    if (out.iters) out.iters[p] = iters[i];
-    if (out.c0) out.c0[p] = c0[i];
-    if (out.c1) out.c1[p] = c1[i];
-  }
-  sum->kernel_seconds = timer.seconds();
-  if (term_h) term_h->swap(term);
-  return TMI_BA_OK;
-}
-
-// One-shot form of a resident track entry point: call(s) on a light handle of P, the points downloaded into
-// `download` afterwards if it is given (the cameras are constant on these paths), the handle destroyed on every way
-// out.
-template <class Call>
-int with_light_handle(const tmi_ba_problem* P, const tmi_ba_options* O, tmi_ba_problem* download, Call call) {
-  tmi_ba_solver* s = new tmi_ba_solver();
-  int rc = create_impl(s, P, O, 0, 1, /*light=*/true);
-  if (rc == TMI_BA_OK) rc = call(s);
-  if (rc == TMI_BA_OK && download) rc = tmi_ba_solver_download(s, download);
-  if (rc != TMI_BA_OK) g_last_error = s->error;
-  tmi_ba_solver_destroy(s);
-  return rc;
-}
-
-// An argument error and its message, before the device is touched.
-int bad_argument(const char* why) {
-  g_last_error = why;
-  return TMI_BA_ERR_INVALID_ARGUMENT;
-}
-
-// The device part of a one-shot batch call, after its argument checks: TMI_BA_ERR_NO_DEVICE without a device, `device`
-// checked against the count (no_such_device: the message, or null for none), nothing to do for an empty batch; then
-// body(OneShot*) on a stream of its own, its error handed to tmi_ba_last_error, and sum->seconds since t0.
-template <class Sum, class Body>
-int one_shot_batch(int device, const char* no_such_device, int num_items, double t0, Sum* sum, Body body) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    g_last_error = "no HIP device visible (the device path has no CPU fallback)";
-    return TMI_BA_ERR_NO_DEVICE;
-  }
-  if (device >= ndev) {
-    if (no_such_device) g_last_error = no_such_device;
-    return TMI_BA_ERR_INVALID_ARGUMENT;
-  }
-  if (num_items == 0) return TMI_BA_OK;
-  OneShot s;
-  int rc = s.open(device);
-  if (rc == TMI_BA_OK) rc = body(&s);
-  if (rc) g_last_error = s.error;
-  sum->seconds = now_s() - t0;
-  return rc;
-}
-
 // A per-view index of the handle's observation slots: fill_keys(keys) queues the kernel that writes one
 // (view << 32 | x) key per slot, the keys are radix-sorted into keys_sorted [No_pad] and view_ptr [Nc + 1] is derived
 // from them.  The temporaries are freed on every way out; the stream is synchronised if there was anything to sort.
@@ -257,14 +81,12 @@ int32_t tmi_ba_solver_filter_outlier_tracks(tmi_ba_solver* s, double max_inlier_
       hipLaunchKernelGGL(filter_finish_kernel, dim3((st.Np_pad + 255) / 256), dim3(256), 0, s->stream, s->d_pt_orig,
                          st.Np_pad, s->d_trk_flag, s->d_trk_mean, track_flag ? s->d_out_u8 : nullptr,
                          track_mean_sq_error ? s->d_out_f64 : nullptr, s->d_counters);
-    TMI_HIP(hipMemcpyAsync(s->h_counters, s->d_counters, 4 * sizeof(int), hipMemcpyDeviceToHost, s->stream));
+    TMI_HIP(download(s->stream, s->h_counters, s->d_counters, 4));
     const size_t ntot = (size_t)st.Np_total;
     unsigned char* stage_u8 = s->h_stage;
     double* stage_f64 = reinterpret_cast<double*>(s->h_stage + 8 * ntot);
-    if (track_flag && ntot > 0)
-      TMI_HIP(hipMemcpyAsync(stage_u8, s->d_out_u8, ntot, hipMemcpyDeviceToHost, s->stream));
-    if (track_mean_sq_error && ntot > 0)
-      TMI_HIP(hipMemcpyAsync(stage_f64, s->d_out_f64, ntot * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    if (track_flag) TMI_HIP(download(s->stream, stage_u8, s->d_out_u8, ntot));
+    if (track_mean_sq_error) TMI_HIP(download(s->stream, stage_f64, s->d_out_f64, ntot));
     TMI_HIP(hipStreamSynchronize(s->stream));
     if (track_flag && ntot > 0) memcpy(track_flag, stage_u8, ntot);
     if (track_mean_sq_error && ntot > 0) memcpy(track_mean_sq_error, stage_f64, ntot * sizeof(double));
@@ -274,10 +96,8 @@ int32_t tmi_ba_solver_filter_outlier_tracks(tmi_ba_solver* s, double max_inlier_
   } else {
     std::vector<unsigned char> flag((size_t)st.Np_pad);
     std::vector<double> mean(track_mean_sq_error ? (size_t)st.Np_pad : 0);
-    if (!flag.empty())
-      TMI_HIP(hipMemcpyAsync(flag.data(), s->d_trk_flag, flag.size(), hipMemcpyDeviceToHost, s->stream));
-    if (!mean.empty())
-      TMI_HIP(hipMemcpyAsync(mean.data(), s->d_trk_mean, mean.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    TMI_HIP(download(s->stream, flag.data(), s->d_trk_flag, flag.size()));
+    TMI_HIP(download(s->stream, mean.data(), s->d_trk_mean, mean.size()));
     TMI_HIP(hipStreamSynchronize(s->stream));
     for (int lp = 0; lp < st.Np_pad; ++lp) {
       const int p = st.pt_orig[lp];
@@ -467,8 +287,7 @@ int32_t tmi_ba_solver_adjust_views(tmi_ba_solver* s, const tmi_ba_options* O, co
     }, s->d_view_keys, s->d_view_ptr);
     if (rc) return rc;
     std::vector<long long> vptr_h((size_t)Nc + 1, 0);
-    TMI_HIP(hipMemcpyAsync(vptr_h.data(), s->d_view_ptr, ((size_t)Nc + 1) * sizeof(long long), hipMemcpyDeviceToHost,
-                           stream));
+    TMI_HIP(download(stream, vptr_h.data(), s->d_view_ptr, vptr_h.size()));
     TMI_HIP(hipStreamSynchronize(stream));
     std::vector<int4> cam_h((size_t)Nc);
     for (int c = 0; c < Nc; ++c) {
@@ -608,9 +427,8 @@ int32_t tmi_ba_adjust_views(tmi_ba_problem* P, const tmi_ba_options* O, const ui
                       {view_termination, view_iterations, view_initial_cost, view_final_cost}, sum);
   if (rc == TMI_BA_OK && Nc) {
     // the kernel wrote back exactly the usable views' cameras and their groups' free intrinsics
-    TMI_HIP(hipMemcpyAsync(P->extrinsics, B.ext, (size_t)6 * Nc * sizeof(double), hipMemcpyDeviceToHost, stream));
-    if (n_intr)
-      TMI_HIP(hipMemcpyAsync(P->intrinsics, B.intr, (size_t)n_intr * sizeof(double), hipMemcpyDeviceToHost, stream));
+    TMI_HIP(s->download(P->extrinsics, B.ext, (size_t)6 * Nc));
+    TMI_HIP(s->download(P->intrinsics, B.intr, (size_t)n_intr));
     TMI_HIP(hipStreamSynchronize(stream));
   }
   if (rc) g_last_error = s->error;
@@ -680,12 +498,10 @@ int32_t tmi_ba_solver_estimate_tracks(tmi_ba_solver* s, const tmi_ba_track_estim
                        term, d_status);
   }
   timer.mark();
-  const hipError_t le = hipGetLastError();
+  ReadBack rb(stream);
   std::vector<signed char> status_h(npad);
-  if (npad) TMI_HIP(hipMemcpyAsync(status_h.data(), d_status, npad, hipMemcpyDeviceToHost, stream));
-  const hipError_t se = hipStreamSynchronize(stream);
-  TMI_HIP(le);
-  TMI_HIP(se);
+  TMI_HIP(download(stream, status_h.data(), d_status, npad));
+  TMI_HIP(rb.finish());
   auto count = [sum](int code) {
     if (code < 0) return;
     sum->num_attempts++;
@@ -760,7 +576,7 @@ int32_t tmi_ba_adjust_two_views_angular(tmi_ba_two_view_angular_batch* Bh, int32
   for (int p = 0; p < P; ++p)
     if (Bh->correspondence_ptr[p + 1] < Bh->correspondence_ptr[p]) return TMI_BA_ERR_INVALID_ARGUMENT;
   if (N > 0 && (!Bh->features1 || !Bh->features2)) return TMI_BA_ERR_INVALID_ARGUMENT;
-  return one_shot_batch(device, nullptr, P, t0, sum, [&](OneShot* s) -> int {
+  return one_shot_batch(device, nullptr, P, t0, &sum->seconds, [&](OneShot* s) -> int {
     TwoViewAngularBatch B;
     memset(&B, 0, sizeof(B));
     B.num_pairs = P;
@@ -784,8 +600,8 @@ int32_t tmi_ba_adjust_two_views_angular(tmi_ba_two_view_angular_batch* Bh, int32
     }, ItemArrays{pair_termination, pair_iterations, pair_initial_cost, pair_final_cost}, sum, &sum->num_tracks, &term);
     if (rc) return rc;
     std::vector<double> rot((size_t)3 * P), pos((size_t)3 * P);
-    TMI_HIP(hipMemcpyAsync(rot.data(), B.rot2, rot.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    TMI_HIP(hipMemcpyAsync(pos.data(), B.pos2, pos.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    TMI_HIP(s->download(rot.data(), B.rot2, rot.size()));
+    TMI_HIP(s->download(pos.data(), B.pos2, pos.size()));
     TMI_HIP(hipStreamSynchronize(s->stream));
     for (int p = 0; p < P; ++p) {
       if (term[p] != 0 && term[p] != 1) continue;  // termination != FAILURE: write back
@@ -834,7 +650,7 @@ int32_t tmi_ba_optimize_relative_positions(tmi_ba_relative_position_batch* Bh, i
   }
   const int64_t N = P ? Bh->correspondence_ptr[P] : 0;
   if (N > 0 && (!Bh->features1 || !Bh->features2)) return bad_argument("relative positions: missing array");
-  return one_shot_batch(device, "relative positions: no such device", P, t0, sum, [&](OneShot* s) -> int {
+  return one_shot_batch(device, "relative positions: no such device", P, t0, &sum->seconds, [&](OneShot* s) -> int {
     RelativePositionBatch B;
     memset(&B, 0, sizeof(B));
     B.num_pairs = P;
@@ -883,19 +699,16 @@ int32_t tmi_ba_optimize_relative_positions(tmi_ba_relative_position_batch* Bh, i
     }
     hipLaunchKernelGGL(relative_position_kernel, dim3((P + 3) / 4), dim3(256), 0, s->stream, B);
     timer.mark();
-    const hipError_t le = hipGetLastError();
+    ReadBack rb(s->stream);
     std::vector<double> pos((size_t)3 * P), cost((size_t)P);
     std::vector<signed char> status((size_t)P);
     std::vector<int> iters((size_t)P), front((size_t)P);
-    hipError_t ce = hipMemcpyAsync(pos.data(), B.pos2, pos.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream);
-    if (ce == hipSuccess) ce = hipMemcpyAsync(cost.data(), B.cost, (size_t)P * sizeof(double), hipMemcpyDeviceToHost, s->stream);
-    if (ce == hipSuccess) ce = hipMemcpyAsync(status.data(), B.status, (size_t)P, hipMemcpyDeviceToHost, s->stream);
-    if (ce == hipSuccess) ce = hipMemcpyAsync(iters.data(), B.iters, (size_t)P * sizeof(int), hipMemcpyDeviceToHost, s->stream);
-    if (ce == hipSuccess) ce = hipMemcpyAsync(front.data(), B.in_front, (size_t)P * sizeof(int), hipMemcpyDeviceToHost, s->stream);
-    const hipError_t se = hipStreamSynchronize(s->stream);
-    TMI_HIP(le);
-    TMI_HIP(ce);
-    TMI_HIP(se);
+    rb.add(pos.data(), B.pos2, pos.size());
+    rb.add(cost.data(), B.cost, cost.size());
+    rb.add(status.data(), B.status, status.size());
+    rb.add(iters.data(), B.iters, iters.size());
+    rb.add(front.data(), B.in_front, front.size());
+    TMI_HIP(rb.finish());
     for (int p = 0; p < P; ++p) {
       const int st = status[p];
       if (st >= 0) {
@@ -984,7 +797,7 @@ int32_t tmi_ba_solver_select_good_tracks(tmi_ba_solver* s, int32_t long_track_le
   hipLaunchKernelGGL(select_init_kernel, dim3(nb_init), dim3(256), 0, stream, S);
   if (st.nslices > 0) hipLaunchKernelGGL(select_bounds_kernel, dim3(s->nblocks_tracks), dim3(256), 0, stream, s->v, S);
   hipLaunchKernelGGL(select_offsets_kernel, dim3(1), dim3(1024), 0, stream, S);
-  TMI_HIP(hipMemcpyAsync(s->h_cell_total, s->d_cell_off + Nc, sizeof(long long), hipMemcpyDeviceToHost, stream));
+  TMI_HIP(download(stream, s->h_cell_total, s->d_cell_off + Nc, 1));
   TMI_HIP(hipStreamSynchronize(stream));
   const long long ncells = *s->h_cell_total;
   if (ncells > ((long long)1 << 31)) {
@@ -1043,13 +856,13 @@ int32_t tmi_ba_solver_select_good_tracks(tmi_ba_solver* s, int32_t long_track_le
                        st.Np_pad, s->d_trk_iter, s->d_trk_mean, long_track_length_threshold,
                        stats_len ? s->d_out_i32 : nullptr, stats_err ? s->d_out_f64 : nullptr);
   }
-  TMI_HIP(hipMemcpyAsync(s->h_counters, s->d_counters, 4 * sizeof(int), hipMemcpyDeviceToHost, stream));
+  TMI_HIP(download(stream, s->h_counters, s->d_counters, 4));
   unsigned char* stage_u8 = s->h_stage;
   int* stage_i32 = reinterpret_cast<int*>(s->h_stage + 4 * (size_t)std::max(Np, 1));
   double* stage_f64 = reinterpret_cast<double*>(s->h_stage + 8 * (size_t)std::max(Np, 1));
-  if (Np > 0) TMI_HIP(hipMemcpyAsync(stage_u8, s->d_out_u8, (size_t)Np, hipMemcpyDeviceToHost, stream));
-  if (stats_len && Np > 0) TMI_HIP(hipMemcpyAsync(stage_i32, s->d_out_i32, (size_t)Np * sizeof(int), hipMemcpyDeviceToHost, stream));
-  if (stats_err && Np > 0) TMI_HIP(hipMemcpyAsync(stage_f64, s->d_out_f64, (size_t)Np * sizeof(double), hipMemcpyDeviceToHost, stream));
+  TMI_HIP(download(stream, stage_u8, s->d_out_u8, (size_t)Np));
+  if (stats_len) TMI_HIP(download(stream, stage_i32, s->d_out_i32, (size_t)Np));
+  if (stats_err) TMI_HIP(download(stream, stage_f64, s->d_out_f64, (size_t)Np));
   TMI_HIP(hipStreamSynchronize(stream));
   if (Np > 0) memcpy(selected, stage_u8, (size_t)Np);
   if (stats_len && Np > 0) memcpy(stats_len, stage_i32, (size_t)Np * sizeof(int));
@@ -1179,9 +992,9 @@ struct TwoViewCameras {
     e2.resize(6 * P);
     k1.resize(10 * P);
     k2.resize(10 * P);
-    TMI_HIP(hipMemcpyAsync(e2.data(), B.ext2, e2.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    TMI_HIP(hipMemcpyAsync(k1.data(), B.intr1, k1.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    TMI_HIP(hipMemcpyAsync(k2.data(), B.intr2, k2.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    TMI_HIP(s->download(e2.data(), B.ext2, e2.size()));
+    TMI_HIP(s->download(k1.data(), B.intr1, k1.size()));
+    TMI_HIP(s->download(k2.data(), B.intr2, k2.size()));
     return TMI_BA_OK;
   }
   void write_back(tmi_ba_two_view_batch* Bh, int p) const {
@@ -1202,7 +1015,7 @@ int32_t tmi_ba_adjust_two_views(tmi_ba_two_view_batch* Bh, int32_t point_dof, in
   const double t0 = now_s();
   if (const int bad = validate_two_view_batch(Bh, point_dof, max_num_iterations)) return bad;
   const int P = Bh->num_pairs;
-  return one_shot_batch(device, nullptr, P, t0, sum, [&](OneShot* s) -> int {
+  return one_shot_batch(device, nullptr, P, t0, &sum->seconds, [&](OneShot* s) -> int {
     const int64_t N = Bh->correspondence_ptr[P];
     TwoViewUpload up;
     int rc = up.upload(s, Bh);
@@ -1225,7 +1038,7 @@ int32_t tmi_ba_adjust_two_views(tmi_ba_two_view_batch* Bh, int32_t point_dof, in
     TwoViewCameras cams;
     std::vector<double> pts((size_t)4 * N);
     if ((rc = cams.download(s, B))) return rc;
-    if (N) TMI_HIP(hipMemcpyAsync(pts.data(), B.points, pts.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    TMI_HIP(s->download(pts.data(), B.points, pts.size()));
     TMI_HIP(hipStreamSynchronize(s->stream));
     for (int p = 0; p < P; ++p) {
       if (term[p] != 0 && term[p] != 1) continue;  // IsSolutionUsable: write back
@@ -1259,7 +1072,7 @@ int32_t tmi_ba_verify_two_views(tmi_ba_two_view_batch* Bh, const tmi_ba_two_view
   if (vo->min_num_inlier_matches < 0) return bad_argument("two-view verification: negative min_num_inlier_matches");
   const int P = Bh->num_pairs;
   if (P > 0 && Bh->correspondence_ptr[0] < 0) return bad_argument("two-view verification: negative correspondence_ptr");
-  return one_shot_batch(device, nullptr, P, t0, sum, [&](OneShot* s) -> int {
+  return one_shot_batch(device, nullptr, P, t0, &sum->seconds, [&](OneShot* s) -> int {
     sum->num_pairs = P;
     const int64_t N = Bh->correspondence_ptr[P];
     TwoViewUpload up;  // the caller's correspondences: what the triangulation reads
@@ -1274,10 +1087,9 @@ int32_t tmi_ba_verify_two_views(tmi_ba_two_view_batch* Bh, const tmi_ba_two_view
     TMI_HIP(s->alloc(&O.orig, Nn));
     TMI_HIP(s->alloc(&O.corr_end, (size_t)P));
     TMI_HIP(s->alloc(&O.points_out, 4 * Nn));
-    TMI_HIP(s->alloc(&O.corr_status, Nn));
+    TMI_HIP(s->alloc_filled(&O.corr_status, Nn, 0xff));
     TMI_HIP(s->alloc(&O.pair_status, (size_t)P));
     TMI_HIP(s->alloc(&O.pair_count, (size_t)P));
-    TMI_HIP(hipMemsetAsync(O.corr_status, 0xff, Nn, s->stream));
     TwoViewBatch C = B;  // the compacted survivors: what the solve and the last filter read
     C.feat1 = O.feat1_c;
     C.feat2 = O.feat2_c;
@@ -1323,12 +1135,10 @@ int32_t tmi_ba_verify_two_views(tmi_ba_two_view_batch* Bh, const tmi_ba_two_view
     std::vector<signed char> cst((size_t)N), pst((size_t)P);
     std::vector<int> cnt((size_t)P);
     if ((rc = cams.download(s, B))) return rc;
-    TMI_HIP(hipMemcpyAsync(pst.data(), O.pair_status, (size_t)P, hipMemcpyDeviceToHost, s->stream));
-    TMI_HIP(hipMemcpyAsync(cnt.data(), O.pair_count, (size_t)P * sizeof(int), hipMemcpyDeviceToHost, s->stream));
-    if (N) {
-      TMI_HIP(hipMemcpyAsync(pts.data(), O.points_out, pts.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-      TMI_HIP(hipMemcpyAsync(cst.data(), O.corr_status, (size_t)N, hipMemcpyDeviceToHost, s->stream));
-    }
+    TMI_HIP(s->download(pst.data(), O.pair_status, pst.size()));
+    TMI_HIP(s->download(cnt.data(), O.pair_count, cnt.size()));
+    TMI_HIP(s->download(pts.data(), O.points_out, pts.size()));
+    TMI_HIP(s->download(cst.data(), O.corr_status, cst.size()));
     TMI_HIP(hipStreamSynchronize(s->stream));
     int64_t* const pair_counter[5] = {&sum->num_pairs_verified, &sum->num_pairs_too_few_matches,
                                       &sum->num_pairs_too_few_triangulated, &sum->num_pairs_failed_ba,
@@ -1359,45 +1169,6 @@ int32_t tmi_ba_verify_two_views(tmi_ba_two_view_batch* Bh, const tmi_ba_two_view
 // ---- the view-pair filters (view_pair_filter_kernels.h) --------------------------------------
 }  // extern "C"
 namespace {
-bool all_finite(const double* x, size_t n) {
-  for (size_t i = 0; i < n; ++i)
-    if (!std::isfinite(x[i])) return false;
-  return true;
-}
-
-// What both filters ask of a batch; `pair_values` is the per-edge array the call reads.  null: fine.
-const char* check_view_pair_batch(const tmi_ba_view_pair_batch* B, bool need_rotation, const double* pair_values) {
-  const int V = B->num_views, E = B->num_pairs;
-  if (V < 0 || E < 0) return "view pairs: negative size";
-  if (need_rotation && V > 0 && !B->view_rotation) return "view pairs: missing view_rotation";
-  if (E > 0 && (!B->pair_view1 || !B->pair_view2 || !pair_values)) return "view pairs: missing array";
-  if (E > (1 << 30)) return "view pairs: more than 2^30 pairs";
-  std::vector<uint64_t> keys((size_t)E);
-  for (int e = 0; e < E; ++e) {
-    const int a = B->pair_view1[e], b = B->pair_view2[e];
-    if (a < 0 || a >= V || b < 0 || b >= V) return "view pairs: view index out of range";
-    if (a == b) return "view pairs: a view paired with itself";
-    keys[e] = ((uint64_t)std::min(a, b) << 32) | (uint64_t)std::max(a, b);
-  }
-  std::sort(keys.begin(), keys.end());
-  if (std::adjacent_find(keys.begin(), keys.end()) != keys.end()) return "view pairs: an unordered pair appears twice";
-  if (B->view_rotation && !all_finite(B->view_rotation, (size_t)3 * V)) return "view pairs: non-finite view_rotation";
-  if (!all_finite(pair_values, (size_t)3 * E)) return "view pairs: non-finite pair value";
-  return nullptr;
-}
-
-// Pinned host memory of one call, freed on every way out.
-struct PinnedWords {
-  void* p = nullptr;
-  PinnedWords() = default;
-  PinnedWords(const PinnedWords&) = delete;
-  PinnedWords& operator=(const PinnedWords&) = delete;
-  hipError_t alloc(size_t bytes) { return hipHostMalloc(&p, bytes, hipHostMallocDefault); }
-  ~PinnedWords() {
-    if (p) hipHostFree(p);
-  }
-};
-
 // The axis generator documented at tmi_ba_filter_view_pairs_from_relative_translation.
 struct AxisDeviates {
   uint64_t state;
@@ -1480,7 +1251,7 @@ int32_t tmi_ba_filter_view_pairs_from_relative_translation(const tmi_ba_view_pai
       row[(size_t)fill[b]++] = make_int2(a, (e << 1) | 1);
     }
   }
-  return one_shot_batch(device, "translation filter: no such device", E, t0, sum, [&](OneShot* s) -> int {
+  return one_shot_batch(device, "translation filter: no such device", E, t0, &sum->seconds, [&](OneShot* s) -> int {
     ViewPairGraph G;
     memset(&G, 0, sizeof(G));
     G.num_views = V;
@@ -1509,9 +1280,9 @@ int32_t tmi_ba_filter_view_pairs_from_relative_translation(const tmi_ba_view_pai
     const bool lds = V <= mfas_lds_view_cap();
     const size_t state_stride = (((size_t)V + 1) & ~(size_t)1) * 20;
     if (!lds) TMI_HIP(s->alloc(&d_state, state_stride * K));
-    PinnedWords pinned;  // [0..6) the moments, then the count of removed pairs
-    TMI_HIP(pinned.alloc(8 * sizeof(double)));
-    double* h_moments = static_cast<double*>(pinned.p);
+    Pinned<double> pinned;  // [0..6) the moments, then the count of removed pairs
+    TMI_HIP(pinned.alloc(8));
+    double* h_moments = pinned.get();
     int* h_counter = reinterpret_cast<int*>(h_moments + 6);
     G.pair_view1 = d_v1;
     G.pair_view2 = d_v2;
@@ -1531,7 +1302,7 @@ int32_t tmi_ba_filter_view_pairs_from_relative_translation(const tmi_ba_view_pai
       hipLaunchKernelGGL(translation_moments_kernel, dim3(1), block, 0, s->stream, E, d_t, d_moments);
       TMI_HIP(timer.mark());
       TMI_HIP(hipGetLastError());
-      TMI_HIP(hipMemcpyAsync(h_moments, d_moments, 6 * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+      TMI_HIP(s->download(h_moments, d_moments, 6));
       TMI_HIP(hipStreamSynchronize(s->stream));
       // :216-221 -- the variance goes where RandGaussian takes a standard deviation, as in the reference
       AxisDeviates rng(opt->seed);
@@ -1568,19 +1339,13 @@ int32_t tmi_ba_filter_view_pairs_from_relative_translation(const tmi_ba_view_pai
     hipLaunchKernelGGL(bad_weight_sum_kernel, edge_grid, block, 0, s->stream, E, K, d_contrib, threshold, d_flag,
                        d_weight, d_counter);
     TMI_HIP(order_timer.mark());
-    const hipError_t le = hipGetLastError();
-    hipError_t ce = hipMemcpyAsync(h_counter, d_counter, sizeof(int), hipMemcpyDeviceToHost, s->stream);
-    if (ce == hipSuccess && pair_removed) ce = hipMemcpyAsync(pair_removed, d_flag, (size_t)E, hipMemcpyDeviceToHost, s->stream);
-    if (ce == hipSuccess && pair_bad_weight)
-      ce = hipMemcpyAsync(pair_bad_weight, d_weight, (size_t)E * sizeof(double), hipMemcpyDeviceToHost, s->stream);
-    if (ce == hipSuccess && rotated_translation)
-      ce = hipMemcpyAsync(rotated_translation, d_t, (size_t)3 * E * sizeof(double), hipMemcpyDeviceToHost, s->stream);
-    if (ce == hipSuccess && iteration_order)
-      ce = hipMemcpyAsync(iteration_order, d_order, (size_t)K * V * sizeof(int), hipMemcpyDeviceToHost, s->stream);
-    const hipError_t se = hipStreamSynchronize(s->stream);
-    TMI_HIP(le);
-    TMI_HIP(ce);
-    TMI_HIP(se);
+    ReadBack rb(s->stream);
+    rb.add(h_counter, d_counter, 1);
+    rb.add(pair_removed, d_flag, (size_t)E);
+    rb.add(pair_bad_weight, d_weight, (size_t)E);
+    rb.add(rotated_translation, d_t, (size_t)3 * E);
+    rb.add(iteration_order, d_order, (size_t)K * V);
+    TMI_HIP(rb.finish());
     if (axes) std::copy(axes_h.begin(), axes_h.end(), axes);
     sum->num_pairs = E;
     sum->num_pairs_removed = *h_counter;
@@ -1603,7 +1368,7 @@ int32_t tmi_ba_filter_view_pairs_from_orientation(const tmi_ba_view_pair_batch* 
     return bad_argument("orientation filter: negative threshold");
   const int V = Bh->num_views, E = Bh->num_pairs;
   const double max_rad = max_relative_rotation_difference_degrees * (M_PI / 180.0);  // :80-84
-  return one_shot_batch(device, "orientation filter: no such device", E, t0, sum, [&](OneShot* s) -> int {
+  return one_shot_batch(device, "orientation filter: no such device", E, t0, &sum->seconds, [&](OneShot* s) -> int {
     int *d_v1, *d_v2, *d_counter;
     double *d_rot, *d_rot2, *d_angle;
     unsigned char* d_flag;
@@ -1613,26 +1378,21 @@ int32_t tmi_ba_filter_view_pairs_from_orientation(const tmi_ba_view_pair_batch* 
     TMI_HIP(s->upload(&d_rot2, Bh->pair_rotation2, (size_t)3 * E));
     TMI_HIP(s->alloc(&d_angle, (size_t)E));
     TMI_HIP(s->alloc(&d_flag, (size_t)E));
-    TMI_HIP(s->alloc(&d_counter, 1));
-    PinnedWords pinned;
-    TMI_HIP(pinned.alloc(sizeof(int)));
-    int* h_counter = static_cast<int*>(pinned.p);
-    TMI_HIP(hipMemsetAsync(d_counter, 0, sizeof(int), s->stream));
+    TMI_HIP(s->alloc_filled(&d_counter, 1, 0));
+    Pinned<int> pinned;
+    TMI_HIP(pinned.alloc(1));
+    int* h_counter = pinned.get();
     StreamTimer timer(s->stream);
     TMI_HIP(timer.status);
     TMI_HIP(timer.mark());
     hipLaunchKernelGGL(orientation_filter_kernel, dim3((E + 255) / 256), dim3(256), 0, s->stream, E, d_rot, d_v1, d_v2,
                        d_rot2, max_rad * max_rad, d_flag, d_angle, d_counter);
     TMI_HIP(timer.mark());
-    const hipError_t le = hipGetLastError();
-    hipError_t ce = hipMemcpyAsync(h_counter, d_counter, sizeof(int), hipMemcpyDeviceToHost, s->stream);
-    if (ce == hipSuccess && pair_removed) ce = hipMemcpyAsync(pair_removed, d_flag, (size_t)E, hipMemcpyDeviceToHost, s->stream);
-    if (ce == hipSuccess && pair_angle)
-      ce = hipMemcpyAsync(pair_angle, d_angle, (size_t)E * sizeof(double), hipMemcpyDeviceToHost, s->stream);
-    const hipError_t se = hipStreamSynchronize(s->stream);
-    TMI_HIP(le);
-    TMI_HIP(ce);
-    TMI_HIP(se);
+    ReadBack rb(s->stream);
+    rb.add(h_counter, d_counter, 1);
+    rb.add(pair_removed, d_flag, (size_t)E);
+    rb.add(pair_angle, d_angle, (size_t)E);
+    TMI_HIP(rb.finish());
     sum->num_pairs = E;
     sum->num_pairs_removed = *h_counter;
     sum->kernel_seconds = timer.seconds();
@@ -1751,10 +1511,7 @@ struct RansacRun {
     TMI_HIP(s->alloc(&d_slot_inlier, M));
     TMI_HIP(s->alloc(&d_num_inliers, (size_t)S));
     TMI_HIP(s->alloc(&d_status, (size_t)S));
-    if (want_hypothesis_cost) {
-      TMI_HIP(s->alloc(&B.hypothesis_cost, hyp));
-      TMI_HIP(hipMemsetAsync(B.hypothesis_cost, 0xff, std::max<size_t>(hyp, 1) * sizeof(int), s->stream));
-    }
+    if (want_hypothesis_cost) TMI_HIP(s->alloc_filled(&B.hypothesis_cost, hyp, 0xff));
     B.num_selected = S;
     B.max_iterations = K;
     B.chunk = chunk;
@@ -1797,7 +1554,7 @@ struct RansacRun {
       hipLaunchKernelGGL(ransac_replay_kernel<P>, dim3((unsigned)((B.num_active + 63) / 64)), dim3(64), 0, stream, B);
       if (phases) TMI_HIP(phase.mark());
       TMI_HIP(hipGetLastError());
-      TMI_HIP(hipMemcpyAsync(state.data(), B.state, state.size() * sizeof(RansacState), hipMemcpyDeviceToHost, stream));
+      TMI_HIP(s->download(state.data(), B.state, state.size()));
       TMI_HIP(hipStreamSynchronize(stream));  // (also: `active` is free to change)
       if (phases) {
         phases->hypothesis_seconds += phase.seconds(0, 1);
@@ -1812,19 +1569,16 @@ struct RansacRun {
   // After the final kernel: the statuses, the inlier counts and (want_mask) the inlier mask come to the host, the
   // stream is synchronised, and the costs of attempted item v go to row sel_rank[v] of the caller's hypothesis_cost.
   int read_back(OneShot* s, bool want_mask, int slots, const std::vector<int>& sel_rank, int32_t* hypothesis_cost) {
-    const hipStream_t stream = s->stream;
     const size_t KS = (size_t)K * slots;
     status.resize((size_t)S);
     num_inliers.resize((size_t)S);
     slot_inlier.resize(want_mask ? M : 0);
     std::vector<int> hyp_h(hypothesis_cost ? (size_t)S * KS : 0);
-    TMI_HIP(hipMemcpyAsync(status.data(), d_status, (size_t)S, hipMemcpyDeviceToHost, stream));
-    TMI_HIP(hipMemcpyAsync(num_inliers.data(), d_num_inliers, (size_t)S * sizeof(int), hipMemcpyDeviceToHost, stream));
-    if (!slot_inlier.empty())
-      TMI_HIP(hipMemcpyAsync(slot_inlier.data(), d_slot_inlier, M, hipMemcpyDeviceToHost, stream));
-    if (!hyp_h.empty())
-      TMI_HIP(hipMemcpyAsync(hyp_h.data(), B.hypothesis_cost, hyp_h.size() * sizeof(int), hipMemcpyDeviceToHost, stream));
-    TMI_HIP(hipStreamSynchronize(stream));
+    TMI_HIP(s->download(status.data(), d_status, status.size()));
+    TMI_HIP(s->download(num_inliers.data(), d_num_inliers, num_inliers.size()));
+    TMI_HIP(s->download(slot_inlier.data(), d_slot_inlier, slot_inlier.size()));
+    TMI_HIP(s->download(hyp_h.data(), B.hypothesis_cost, hyp_h.size()));
+    TMI_HIP(hipStreamSynchronize(s->stream));
     if (hypothesis_cost)
       for (int v = 0; v < S; ++v)
         std::copy(hyp_h.begin() + (size_t)v * KS, hyp_h.begin() + ((size_t)v + 1) * KS,
@@ -1984,7 +1738,7 @@ int32_t tmi_ba_localize_views(tmi_ba_problem* P, const tmi_ba_localization_optio
   }
   run.plan(L, LocalizeProblem::kSample);
   const std::vector<unsigned> sel_stream(sel_view.begin(), sel_view.end());  // a view's sample stream is its camera index
-  return one_shot_batch(O->device, "localize views: no such device", S, t0, sum, [&](OneShot* s) -> int {
+  return one_shot_batch(O->device, "localize views: no such device", S, t0, &sum->seconds, [&](OneShot* s) -> int {
     const hipStream_t stream = s->stream;
     ViewBatch VB;
     memset(&VB, 0, sizeof(VB));
@@ -2047,13 +1801,11 @@ int32_t tmi_ba_localize_views(tmi_ba_problem* P, const tmi_ba_localization_optio
       sum->kernel_seconds += vs.kernel_seconds;
       for (int v = 0; v < S; ++v)
         if (run.status[v] == 0 && term[sel_view[v]] != 0 && term[sel_view[v]] != 1) run.status[v] = 4;
-      if (n_intr) {
-        // (the kernel wrote back exactly the usable views' free intrinsics)
-        TMI_HIP(hipMemcpyAsync(P->intrinsics, VB.intr, (size_t)n_intr * sizeof(double), hipMemcpyDeviceToHost, stream));
-      }
+      // (the kernel wrote back exactly the usable views' free intrinsics)
+      TMI_HIP(s->download(P->intrinsics, VB.intr, (size_t)n_intr));
     }
     std::vector<double> ext_h((size_t)6 * Nc);
-    TMI_HIP(hipMemcpyAsync(ext_h.data(), VB.ext, ext_h.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+    TMI_HIP(s->download(ext_h.data(), VB.ext, ext_h.size()));
     TMI_HIP(hipStreamSynchronize(stream));
     const RansacItemArrays out = {view_status,         view_num_inliers,   view_num_iterations,
                                   view_best_iteration, view_best_solution, view_confidence};
@@ -2095,22 +1847,6 @@ constexpr long long kMatchRowBytes = 34;
 constexpr long long kMatchWorkBudgetBytes = 64ll << 20;
 constexpr long long kMatchMaxChunkRows = 0x7ffffff0ll;
 
-// Page-locked host memory of one call, freed on every way out.
-struct PinnedBuffer {
-  void* p = nullptr;
-  PinnedBuffer() {}
-  PinnedBuffer(const PinnedBuffer&) = delete;
-  PinnedBuffer& operator=(const PinnedBuffer&) = delete;
-  hipError_t alloc(size_t bytes) { return hipHostMalloc(&p, std::max<size_t>(bytes, 16), hipHostMallocDefault); }
-  ~PinnedBuffer() {
-    if (p) hipHostFree(p);
-  }
-};
-// one_shot_batch writes the call's time to sum->seconds; tmi_ba_match_summary calls that field total_seconds and is
-// filled after the capacity check, so the scaffold gets this stand-in.
-struct MatchSeconds {
-  double seconds;
-};
 
 // The call the two matchers share.  Cascade == false: tmi_ba_match_features (match_nn_kernel gives every row its
 // neighbour triple).  Cascade == true: tmi_ba_match_features_cascade (the images are hashed once, then
@@ -2193,9 +1929,8 @@ int32_t match_features_call(const Options* M, int32_t num_images, const int64_t*
       sum->distance_evaluations += n1 * n2 * (symmetric ? 2 : 1);
     }
   pair_match_begin[0] = 0;
-  MatchSeconds secs = {0.0};
   const std::string no_device = what + ": no such device";
-  const int rc = one_shot_batch(M->device, no_device.c_str(), num_pairs, t0, &secs, [&](OneShot* s) -> int {
+  const int rc = one_shot_batch(M->device, no_device.c_str(), num_pairs, t0, &sum->total_seconds, [&](OneShot* s) -> int {
     const hipStream_t stream = s->stream;
     float* d_desc;
     TMI_HIP(s->upload(&d_desc, descriptors, (size_t)total_rows * (size_t)dim));
@@ -2220,8 +1955,7 @@ int32_t match_features_call(const Options* M, int32_t num_images, const int64_t*
       TMI_HIP(s->alloc(&d_bucket_begin, (size_t)num_images * kCascadeGroups * (kCascadeBuckets + 1)));
       TMI_HIP(s->alloc(&d_bucket_rows, (size_t)kCascadeGroups * (size_t)total_rows));
       TMI_HIP(s->alloc(&d_task_image, 2 * (size_t)max_pairs));
-      TMI_HIP(s->alloc(&d_counters, 4 * (size_t)kCascadeCounterShards));
-      TMI_HIP(hipMemsetAsync(d_counters, 0, 4 * (size_t)kCascadeCounterShards * sizeof(unsigned long long), stream));
+      TMI_HIP(s->alloc_filled(&d_counters, 4 * (size_t)kCascadeCounterShards, 0));
       StreamTimer timer(stream);
       TMI_HIP(timer.status);
       TMI_HIP(timer.mark());
@@ -2238,8 +1972,7 @@ int32_t match_features_call(const Options* M, int32_t num_images, const int64_t*
       TMI_HIP(timer.mark());
       TMI_HIP(hipGetLastError());
       std::vector<CascadeRecord> rec_h((image_hash || image_bucket_ids) ? (size_t)total_rows : 0);
-      if (!rec_h.empty())
-        TMI_HIP(hipMemcpyAsync(rec_h.data(), d_rec, rec_h.size() * sizeof(CascadeRecord), hipMemcpyDeviceToHost, stream));
+      TMI_HIP(s->download(rec_h.data(), d_rec, rec_h.size()));
       TMI_HIP(hipStreamSynchronize(stream));  // (also: begin_h and hash_blocks are free to go)
       sum->kernel_seconds += timer.seconds();
       for (size_t r = 0; r < rec_h.size(); ++r) {
@@ -2272,10 +2005,12 @@ int32_t match_features_call(const Options* M, int32_t num_images, const int64_t*
     TMI_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, d_flag, d_scan, (int)(R + 1), stream));
     unsigned char* d_scan_tmp;
     TMI_HIP(s->alloc(&d_scan_tmp, std::max<size_t>(scan_bytes, 16)));
-    PinnedBuffer h_counts_buf, h_out_buf;
-    TMI_HIP(h_counts_buf.alloc((4 * (size_t)max_pairs + 1) * sizeof(int)));
-    TMI_HIP(h_out_buf.alloc(R * sizeof(MatchRecord)));
-    const int* h_counts = (const int*)h_counts_buf.p;
+    Pinned<int> h_counts_buf;
+    Pinned<MatchRecord> h_out_buf;
+    TMI_HIP(h_counts_buf.alloc(4 * (size_t)max_pairs + 1));
+    TMI_HIP(h_out_buf.alloc(R));
+    int* const h_counts = h_counts_buf.get();
+    MatchRecord* const rec = h_out_buf.get();
     const size_t lds = match_lds_bytes(dim);
     const bool staged = dim <= kMatchMaxStagedDim;
     int64_t total = 0;
@@ -2355,7 +2090,7 @@ int32_t match_features_call(const Options* M, int32_t num_images, const int64_t*
       TMI_HIP(timer.mark());
       TMI_HIP(hipGetLastError());
       // the counts, then exactly the chunk's matches
-      TMI_HIP(hipMemcpyAsync(h_counts_buf.p, d_counts, (4 * (size_t)np + 1) * sizeof(int), hipMemcpyDeviceToHost, stream));
+      TMI_HIP(s->download(h_counts, d_counts, 4 * (size_t)np + 1));
       TMI_HIP(hipStreamSynchronize(stream));  // (also: tasks, blocks and fwd_task are free to change)
       sum->kernel_seconds += timer.seconds();
       const int chunk_total = h_counts[4 * np];
@@ -2371,9 +2106,8 @@ int32_t match_features_call(const Options* M, int32_t num_images, const int64_t*
       }
       if (chunk_total && total + chunk_total <= match_capacity) {
         const size_t n = (size_t)chunk_total;
-        TMI_HIP(hipMemcpyAsync(h_out_buf.p, d_out, n * sizeof(MatchRecord), hipMemcpyDeviceToHost, stream));
+        TMI_HIP(s->download(rec, d_out, n));
         TMI_HIP(hipStreamSynchronize(stream));
-        const MatchRecord* rec = (const MatchRecord*)h_out_buf.p;
         for (size_t i = 0; i < n; ++i) {
           match_feature1[total + i] = rec[i].feature1;
           match_feature2[total + i] = rec[i].feature2;
@@ -2387,7 +2121,7 @@ int32_t match_features_call(const Options* M, int32_t num_images, const int64_t*
     sum->num_matches = total;
     if constexpr (Cascade) {
       unsigned long long counters_h[4 * kCascadeCounterShards];
-      TMI_HIP(hipMemcpyAsync(counters_h, d_counters, sizeof(counters_h), hipMemcpyDeviceToHost, stream));
+      TMI_HIP(s->download(counters_h, d_counters, (size_t)4 * kCascadeCounterShards));
       TMI_HIP(hipStreamSynchronize(stream));
       for (int i = 0; i < kCascadeCounterShards; ++i) {
         sum->candidates_examined += (int64_t)counters_h[4 * i];
@@ -2510,7 +2244,7 @@ int32_t tmi_ba_build_tracks(const tmi_ba_track_build_options* O, int64_t num_edg
   const unsigned cap = (unsigned)O->max_track_length;
   const unsigned min_length = (unsigned)std::max(O->min_track_length, 2);  // a set of one node is always dropped
   bool too_small = false;
-  const int rc = one_shot_batch(O->device, "build tracks: no such device", (int)E, t0, sum, [&](OneShot* s) -> int {
+  const int rc = one_shot_batch(O->device, "build tracks: no such device", (int)E, t0, &sum->seconds, [&](OneShot* s) -> int {
     const hipStream_t stream = s->stream;
     auto grid = [](long long n) { return dim3((unsigned)((n + 255) / 256)); };
     StreamTimer nodes_timer(stream), components_timer(stream), cap_timer(stream, 4), output_timer(stream, 4);
@@ -2519,11 +2253,10 @@ int32_t tmi_ba_build_tracks(const tmi_ba_track_build_options* O, int64_t num_edg
     TMI_HIP(cap_timer.status);
     TMI_HIP(output_timer.status);
     unsigned long long* d_counters;
-    TMI_HIP(s->alloc(&d_counters, (size_t)kTbCounters));
-    TMI_HIP(hipMemsetAsync(d_counters, 0, kTbCounters * sizeof(unsigned long long), stream));
+    TMI_HIP(s->alloc_filled(&d_counters, (size_t)kTbCounters, 0));
     unsigned long long counters[kTbCounters];
     auto read_counters = [&]() -> int {
-      TMI_HIP(hipMemcpyAsync(counters, d_counters, sizeof(counters), hipMemcpyDeviceToHost, stream));
+      TMI_HIP(s->download(counters, d_counters, (size_t)kTbCounters));
       TMI_HIP(hipStreamSynchronize(stream));
       if (counters[kTbError]) {
         s->error = "build tracks: a device loop reached its bound";
@@ -2542,16 +2275,14 @@ int32_t tmi_ba_build_tracks(const tmi_ba_track_build_options* O, int64_t num_edg
     TMI_HIP(s->alloc(&d_key_sorted, (size_t)N2));
     TMI_HIP(s->alloc(&d_index, (size_t)N2));
     TMI_HIP(s->alloc(&d_index_sorted, (size_t)N2));
-    TMI_HIP(s->alloc(&d_head, (size_t)N2 + 1));
-    TMI_HIP(s->alloc(&d_first, (size_t)N2 + 1));
+    TMI_HIP(s->alloc_filled(&d_head, (size_t)N2 + 1, 0));
+    TMI_HIP(s->alloc_filled(&d_first, (size_t)N2 + 1, 0));
     TMI_HIP(s->alloc(&d_heads_before, (size_t)N2 + 1));
     TMI_HIP(s->alloc(&d_firsts_before, (size_t)N2 + 1));
     TMI_HIP(s->alloc(&d_run_node, (size_t)N2));
     TMI_HIP(s->alloc(&d_node_view, (size_t)N2));
     TMI_HIP(s->alloc(&d_node_feature, (size_t)N2));
     TMI_HIP(s->alloc(&d_endpoint_node, (size_t)N2));
-    TMI_HIP(hipMemsetAsync(d_head, 0, ((size_t)N2 + 1) * sizeof(unsigned), stream));
-    TMI_HIP(hipMemsetAsync(d_first, 0, ((size_t)N2 + 1) * sizeof(unsigned), stream));
     TMI_HIP(nodes_timer.mark());
     hipLaunchKernelGGL(tb_keys_kernel, grid(N2), dim3(256), 0, stream, d_view, d_feature, N2, d_key, d_index);
     TMI_TB(tb_sort_pairs(s, d_key, d_key_sorted, d_index, d_index_sorted, (size_t)N2, 64));
@@ -2565,7 +2296,7 @@ int32_t tmi_ba_build_tracks(const tmi_ba_track_build_options* O, int64_t num_edg
     TMI_HIP(nodes_timer.mark());
     TMI_HIP(hipGetLastError());
     unsigned num_nodes = 0;
-    TMI_HIP(hipMemcpyAsync(&num_nodes, d_firsts_before + N2, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+    TMI_HIP(s->download(&num_nodes, d_firsts_before + N2, 1));
     TMI_HIP(hipStreamSynchronize(stream));
     if (num_nodes < 2 || (long long)num_nodes > N2) {
       s->error = "build tracks: the device reported an impossible node count";
@@ -2581,8 +2312,7 @@ int32_t tmi_ba_build_tracks(const tmi_ba_track_build_options* O, int64_t num_edg
     TMI_HIP(s->alloc(&d_parent, N));
     TMI_HIP(s->alloc(&d_iota, N));
     TMI_HIP(s->alloc(&d_component, N));
-    TMI_HIP(s->alloc(&d_size, N));
-    TMI_HIP(hipMemsetAsync(d_size, 0, N * sizeof(unsigned), stream));
+    TMI_HIP(s->alloc_filled(&d_size, N, 0));
     TMI_HIP(components_timer.mark());
     hipLaunchKernelGGL(tb_iota_kernel, grid(N), dim3(256), 0, stream, d_parent, num_nodes);
     hipLaunchKernelGGL(tb_iota_kernel, grid(N), dim3(256), 0, stream, d_iota, num_nodes);  // the sorts' values
@@ -2650,8 +2380,8 @@ int32_t tmi_ba_build_tracks(const tmi_ba_track_build_options* O, int64_t num_edg
       TMI_HIP(cap_timer.mark());
       TMI_HIP(hipGetLastError());
       unsigned num_replayed = 0, listed = 0;
-      TMI_HIP(hipMemcpyAsync(&num_replayed, d_edge_before + E, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
-      TMI_HIP(hipMemcpyAsync(&listed, d_before + N, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+      TMI_HIP(s->download(&num_replayed, d_edge_before + E, 1));
+      TMI_HIP(s->download(&listed, d_before + N, 1));
       TMI_HIP(hipStreamSynchronize(stream));
       if (listed != num_oversize || num_replayed < 1 || (long long)num_replayed > E) {
         s->error = "build tracks: the device reported an impossible replay plan";
@@ -2692,9 +2422,8 @@ int32_t tmi_ba_build_tracks(const tmi_ba_track_build_options* O, int64_t num_edg
     TMI_HIP(s->alloc(&d_view_key_sorted, N));
     TMI_HIP(s->alloc(&d_by_view_node, N));
     TMI_HIP(s->alloc(&d_keep, N));
-    TMI_HIP(s->alloc(&d_obs_flag, N + 1));
+    TMI_HIP(s->alloc_filled(&d_obs_flag, N + 1, 0));
     TMI_HIP(s->alloc(&d_obs_before, N + 1));
-    TMI_HIP(hipMemsetAsync(d_obs_flag, 0, (N + 1) * sizeof(unsigned), stream));
     TMI_HIP(hipMemsetAsync(d_flag, 0, (N + 1) * sizeof(unsigned), stream));
     hipLaunchKernelGGL(tb_view_keys_kernel, grid(N), dim3(256), 0, stream, d_final, d_node_view, num_nodes, d_view_key);
     TMI_TB(tb_sort_pairs(s, d_view_key, d_view_key_sorted, d_iota, d_by_view_node, N, 32 + node_bits));
@@ -2707,8 +2436,8 @@ int32_t tmi_ba_build_tracks(const tmi_ba_track_build_options* O, int64_t num_edg
     TMI_HIP(output_timer.mark());
     TMI_HIP(hipGetLastError());
     unsigned num_obs = 0, num_tracks = 0;
-    TMI_HIP(hipMemcpyAsync(&num_obs, d_obs_before + N, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
-    TMI_HIP(hipMemcpyAsync(&num_tracks, d_before + N, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+    TMI_HIP(s->download(&num_obs, d_obs_before + N, 1));
+    TMI_HIP(s->download(&num_tracks, d_before + N, 1));
     TMI_TB(read_counters());
     if (num_oversize) sum->phase_seconds[2] = cap_timer.seconds(0, 1) + cap_timer.seconds(2, 3);
     sum->num_sets = (int64_t)counters[kTbSets];
@@ -2741,16 +2470,12 @@ int32_t tmi_ba_build_tracks(const tmi_ba_track_build_options* O, int64_t num_edg
     TMI_HIP(hipGetLastError());
     if (!too_small) {
       static_assert(sizeof(long long) == sizeof(int64_t), "track_begin is read back as it is");
-      TMI_HIP(hipMemcpyAsync(track_begin, d_track_begin, ((size_t)num_tracks + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
-      if (num_obs) {
-        TMI_HIP(hipMemcpyAsync(obs_view, d_obs_view, (size_t)num_obs * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-        TMI_HIP(hipMemcpyAsync(obs_feature, d_obs_feature, (size_t)num_obs * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-      }
+      TMI_HIP(s->download((long long*)track_begin, d_track_begin, (size_t)num_tracks + 1));
+      TMI_HIP(s->download(obs_view, d_obs_view, (size_t)num_obs));
+      TMI_HIP(s->download(obs_feature, d_obs_feature, (size_t)num_obs));
     }
-    if (endpoint_node)
-      TMI_HIP(hipMemcpyAsync(endpoint_node, d_endpoint_node, (size_t)N2 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    if (endpoint_label)
-      TMI_HIP(hipMemcpyAsync(endpoint_label, d_endpoint_label, (size_t)N2 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    TMI_HIP(s->download(endpoint_node, d_endpoint_node, (size_t)N2));
+    TMI_HIP(s->download(endpoint_label, d_endpoint_label, (size_t)N2));
     TMI_HIP(hipStreamSynchronize(stream));
     sum->phase_seconds[3] = output_timer.seconds(0, 1) + output_timer.seconds(2, 3);
     sum->kernel_seconds = sum->phase_seconds[0] + sum->phase_seconds[1] + sum->phase_seconds[2] + sum->phase_seconds[3];
@@ -2814,10 +2539,8 @@ int vg_queue_components(OneShot* s, const tmi_ba_view_pair_batch* B, const uint8
   TMI_HIP(s->alloc(&D->keep, (size_t)E));
   TMI_HIP(s->alloc(&d_parent, (size_t)V));
   TMI_HIP(s->alloc(&D->label, (size_t)V));
-  TMI_HIP(s->alloc(&D->size, (size_t)V));
-  TMI_HIP(s->alloc(&D->counters, (size_t)kVgCounters));
-  TMI_HIP(hipMemsetAsync(D->size, 0, (size_t)V * sizeof(unsigned), stream));
-  TMI_HIP(hipMemsetAsync(D->counters, 0, kVgCounters * sizeof(unsigned long long), stream));
+  TMI_HIP(s->alloc_filled(&D->size, (size_t)V, 0));
+  TMI_HIP(s->alloc_filled(&D->counters, (size_t)kVgCounters, 0));
   TMI_HIP(timer->mark());
   hipLaunchKernelGGL(tb_iota_kernel, grid(V), dim3(256), 0, stream, d_parent, (unsigned)V);
   hipLaunchKernelGGL(vg_union_kernel, grid(E), dim3(256), 0, stream, D->view1, D->view2, D->mask, E, (unsigned)V, d_parent,
@@ -2862,7 +2585,7 @@ int32_t tmi_ba_largest_connected_component(const tmi_ba_view_pair_batch* Bh, con
   std::vector<int32_t> label_h((size_t)V);
   std::vector<uint8_t> in_largest_h((size_t)V, 0), keep_h((size_t)E, 0);
   for (int v = 0; v < V; ++v) label_h[v] = v;  // (E == 0: every view is its own component)
-  const int rc = one_shot_batch(device, "largest component: no such device", E, t0, &sum, [&](OneShot* s) -> int {
+  const int rc = one_shot_batch(device, "largest component: no such device", E, t0, &sum.seconds, [&](OneShot* s) -> int {
     const hipStream_t stream = s->stream;
     ViewGraphDevice D;
     unsigned char* d_in_largest;
@@ -2876,10 +2599,10 @@ int32_t tmi_ba_largest_connected_component(const tmi_ba_view_pair_batch* Bh, con
     TMI_HIP(hipGetLastError());
     unsigned long long counters[kVgCounters];
     static_assert(sizeof(unsigned) == sizeof(int32_t), "labels are read back as they are");
-    TMI_HIP(hipMemcpyAsync(counters, D.counters, sizeof(counters), hipMemcpyDeviceToHost, stream));
-    TMI_HIP(hipMemcpyAsync(label_h.data(), D.label, (size_t)V * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-    TMI_HIP(hipMemcpyAsync(in_largest_h.data(), d_in_largest, (size_t)V, hipMemcpyDeviceToHost, stream));
-    TMI_HIP(hipMemcpyAsync(keep_h.data(), D.keep, (size_t)E, hipMemcpyDeviceToHost, stream));
+    TMI_HIP(s->download(counters, D.counters, (size_t)kVgCounters));
+    TMI_HIP(s->download((unsigned*)label_h.data(), D.label, label_h.size()));
+    TMI_HIP(s->download(in_largest_h.data(), d_in_largest, in_largest_h.size()));
+    TMI_HIP(s->download(keep_h.data(), D.keep, keep_h.size()));
     TMI_HIP(hipStreamSynchronize(stream));
     if (counters[kVgError]) {
       s->error = "largest component: a device loop reached its bound";
@@ -2920,7 +2643,7 @@ int32_t tmi_ba_orientations_from_maximum_spanning_tree(const tmi_ba_view_pair_ba
   std::vector<double> orientation_h;
   std::vector<int32_t> parent_h, parent_pair_h, depth_h;
   std::vector<uint8_t> in_tree_h;
-  const int rc = one_shot_batch(device, "spanning tree: no such device", E, t0, &sum.component, [&](OneShot* s) -> int {
+  const int rc = one_shot_batch(device, "spanning tree: no such device", E, t0, &sum.component.seconds, [&](OneShot* s) -> int {
     const hipStream_t stream = s->stream;
     auto grid = [](long long n) { return dim3((unsigned)((n + 255) / 256)); };
     ViewGraphDevice D;
@@ -2943,20 +2666,17 @@ int32_t tmi_ba_orientations_from_maximum_spanning_tree(const tmi_ba_view_pair_ba
     TMI_HIP(s->alloc(&d_weight_key, Es));
     TMI_HIP(s->alloc(&d_weight_key_sorted, Es));
     TMI_HIP(s->alloc(&d_edge_of_rank, Es));
-    TMI_HIP(s->alloc(&d_in_tree, Es));
+    TMI_HIP(s->alloc_filled(&d_in_tree, Es, 0));
     TMI_HIP(s->alloc(&d_row, 2 * Es));  // (a tree has fewer edges than views; the flags can never exceed E)
     TMI_HIP(s->alloc(&d_comp, Vs));
     TMI_HIP(s->alloc(&d_hook, Vs));
     TMI_HIP(s->alloc(&d_best, Vs));
-    TMI_HIP(s->alloc(&d_degree, Vs + 1));
+    TMI_HIP(s->alloc_filled(&d_degree, Vs + 1, 0));
     TMI_HIP(s->alloc(&d_row_ptr, Vs + 1));
     TMI_HIP(s->alloc(&d_cursor, Vs + 1));
     TMI_HIP(s->alloc(&d_tree, 5 * Vs));
-    TMI_HIP(s->alloc(&d_orientation, 3 * Vs));
-    TMI_HIP(hipMemsetAsync(d_in_tree, 0, Es, stream));
-    TMI_HIP(hipMemsetAsync(d_degree, 0, (Vs + 1) * sizeof(unsigned), stream));
     TMI_HIP(hipMemsetAsync(d_tree, 0xff, 3 * Vs * sizeof(int), stream));
-    TMI_HIP(hipMemsetAsync(d_orientation, 0, 3 * Vs * sizeof(double), stream));
+    TMI_HIP(s->alloc_filled(&d_orientation, 3 * Vs, 0));
     // step 1
     TMI_VG(vg_queue_components(s, Bh, pair_mask, &D, &timer));
     // step 2: the ranks of the reference's order, then the Boruvka rounds
@@ -2991,12 +2711,12 @@ int32_t tmi_ba_orientations_from_maximum_spanning_tree(const tmi_ba_view_pair_ba
     parent_pair_h.resize(Vs);
     depth_h.resize(Vs);
     in_tree_h.resize(Es);
-    TMI_HIP(hipMemcpyAsync(counters, D.counters, sizeof(counters), hipMemcpyDeviceToHost, stream));
-    TMI_HIP(hipMemcpyAsync(orientation_h.data(), d_orientation, 3 * Vs * sizeof(double), hipMemcpyDeviceToHost, stream));
-    TMI_HIP(hipMemcpyAsync(parent_h.data(), d_tree, Vs * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-    TMI_HIP(hipMemcpyAsync(parent_pair_h.data(), d_tree + Vs, Vs * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-    TMI_HIP(hipMemcpyAsync(depth_h.data(), d_tree + 2 * Vs, Vs * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-    TMI_HIP(hipMemcpyAsync(in_tree_h.data(), d_in_tree, Es, hipMemcpyDeviceToHost, stream));
+    TMI_HIP(s->download(counters, D.counters, (size_t)kVgCounters));
+    TMI_HIP(s->download(orientation_h.data(), d_orientation, 3 * Vs));
+    TMI_HIP(s->download(parent_h.data(), d_tree, Vs));
+    TMI_HIP(s->download(parent_pair_h.data(), d_tree + Vs, Vs));
+    TMI_HIP(s->download(depth_h.data(), d_tree + 2 * Vs, Vs));
+    TMI_HIP(s->download(in_tree_h.data(), d_in_tree, Es));
     TMI_HIP(hipStreamSynchronize(stream));
     if (counters[kVgError]) {
       s->error = "spanning tree: a device loop reached its bound";
@@ -3152,7 +2872,7 @@ int32_t two_view_ransac_call(
   }
   run.plan(L, kSample);
   const std::string no_device = what + ": no such device";
-  return one_shot_batch(L->device, no_device.c_str(), S, t0, sum, [&](OneShot* s) -> int {
+  return one_shot_batch(L->device, no_device.c_str(), S, t0, &sum->seconds, [&](OneShot* s) -> int {
     const hipStream_t stream = s->stream;
     double *d_xs, *d_model_out;
     TMI_HIP(s->upload(&d_xs, (const double*)xs.data(), xs.size()));
@@ -3171,7 +2891,7 @@ int32_t two_view_ransac_call(
     TMI_HIP(timer.mark());
     TMI_HIP(hipGetLastError());
     std::vector<double> model_h((size_t)17 * S);
-    TMI_HIP(hipMemcpyAsync(model_h.data(), d_model_out, model_h.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+    TMI_HIP(s->download(model_h.data(), d_model_out, model_h.size()));
     if (const int rc = run.read_back(s, corr_inlier != nullptr, kSlots, sel_rank, hypothesis_cost)) return rc;
     sum->kernel_seconds = timer.seconds();
     sum->num_chunks = run.chunks_run;
