@@ -1386,6 +1386,124 @@ int32_t tmi_ba_estimate_global_rotations_linear(const tmi_ba_view_pair_batch* ba
                                                 const tmi_ba_linear_rotation_options* options, int32_t device,
                                                 double* view_rotation, tmi_ba_linear_rotation_summary* summary);
 
+/* ---- LinearPositionEstimator: global positions as the smallest eigenvector of the view triplets' constraints ----
+ * reference: linear_position_estimator.cc:163-470 (GlobalPositionEstimatorType::LINEAR_TRIPLET; Jiang, Cui and Tan,
+ * ICCV 2013) with TripletExtractor (math/graph/triplet_extractor.h), FindCommonTracksInViews and
+ * ComputeTripletBaselineRatios (compute_triplet_baseline_ratios.cc:55-156).  The only position estimator that needs no
+ * start, and the only pose estimator here that reads the tracks.  max_iterations and tolerance are Spectra's defaults. */
+typedef struct tmi_ba_linear_position_options {
+  int32_t  max_iterations;   /* 1000                                                                        */
+  double   tolerance;        /* 1e-10: the stop rule's residual, relative to |M|_inf                        */
+  double   relative_shift;   /* 1e-9: M + mu I is factored, mu = relative_shift x the largest diagonal entry */
+  uint64_t seed;             /* 0: the start block's splitmix64 stream                                      */
+  double   min_triangulation_angle_degrees; /* 2.0: kMinTriangulationAngle, compute_triplet_baseline_ratios.cc:60 */
+} tmi_ba_linear_position_options;
+void tmi_ba_linear_position_options_init(tmi_ba_linear_position_options* options);
+
+typedef struct tmi_ba_linear_position_summary {
+  int32_t num_views;                 /* of the batch                                                        */
+  int32_t num_pairs;
+  int32_t num_triplets;              /* triangles of the view graph                                         */
+  int32_t num_triplets_with_baseline;/* those with at least one usable common track                         */
+  int32_t num_triplet_components;    /* components of the triplets with a baseline                          */
+  int32_t num_chosen_triplets;       /* triplets of the chosen component                                    */
+  int32_t num_chosen_views;          /* views of the chosen component: the estimated views                  */
+  int32_t triplets_written;          /* 1: triplet_capacity sufficed and the optional arrays were written   */
+  int64_t num_dropped_ratios;        /* common tracks dropped for a ratio that is not finite and positive   */
+  int32_t order;                     /* 3 (num_chosen_views - 1), the order of the matrix                   */
+  int32_t num_iterations;            /* subspace iterations run                                             */
+  int32_t converged;                 /* the stop rule was met within max_iterations                         */
+  int32_t usable;                    /* 0: no triplet with a baseline, or a pivot of M + mu I was not positive;
+                                        nothing was written                                                 */
+  double  eigenvalue[2];             /* the Ritz value of the result and the next                           */
+  double  residual;                  /* |M q - theta q|_2 of the result                                     */
+  double  matrix_norm;               /* |M|_inf, the largest absolute row sum                               */
+  int32_t sign_votes;                /* the integer sum of the votes, before any flip                       */
+  int32_t flipped;                   /* 1: the sum was negative and every position was negated              */
+  double  seconds;
+  double  kernel_seconds;            /* device time; the sum of the five below                              */
+  double  triplet_seconds;           /* triangle count, scan and fill                                       */
+  double  baseline_seconds;          /* features, common tracks, triangulations and the order statistics    */
+  double  factor_seconds;            /* the factorisation of M + mu I                                       */
+  double  substitution_seconds;      /* forward / backward substitution on the block of 6                   */
+  double  graph_seconds;             /* components, records, assembly, M Y, Gram-Schmidt, Rayleigh-Ritz, the vote */
+} tmi_ba_linear_position_summary;
+
+/* EstimatePositions on the device.  The problem supplies the camera model and intrinsics of every view (camera i is view
+ * i of the batch: num_cameras == num_views) and all observations (view, track, pixel), as tmi_ba_localize_views reads
+ * them; extrinsics, points and the estimated flags are not consulted (FindCommonTracksInViews does not consult them).
+ * Of the batch pair_view1 / pair_view2 (view1 < view2), pair_rotation2, pair_position2 and view_rotation (the global
+ * orientations) are read.  view_position [3 * num_views] and view_estimated [num_views] are written on success:
+ * view_estimated is 1 for the views of the chosen triplet component and 0 for every other view, whose position is never
+ * written.  The optional arrays (each may be NULL) have room for triplet_capacity triplets: triplet_view [3 *] the
+ * views a < b < c, triplet_pair [3 *] the batch indices of the pairs (a, b), (a, c), (b, c), triplet_baseline [3 *]
+ * (0, 0, 0 where there is none), triplet_num_common, triplet_num_used, triplet_component (the smallest triplet of the
+ * component, -1 for a triplet without a baseline).  With a capacity below summary->num_triplets none of them is
+ * written, summary->triplets_written is 0, and the solve runs all the same.
+ *   1. triplet_extractor.h:166-226   Every triangle of the view graph once, as (a < b < c), numbered in lexicographic
+ *                order (DEVIATION: the reference's order is that of its hash sets).  One wavefront per edge (a, b)
+ *                intersects the two sorted adjacency rows for c > b: a count pass, a scan, a fill pass.
+ *   2. :423-430, compute_triplet_baseline_ratios.cc:110-112   Per observation, once: the feature is
+ *                PixelToNormalizedCoordinates(pixel), then hnormalized(), then homogeneous().normalized().
+ *   3. compute_triplet_baseline_ratios.cc:55-156   Per triplet the common tracks of the three views (the views' track
+ *                lists are sorted; every track of the first is looked up in the other two).  Per common track three
+ *                two-view triangulations, origins {0, position_2}, directions {f1, R2^T f2}, R2 =
+ *                AngleAxisToRotationMatrix(rotation_2): SufficientTriangulationAngle at
+ *                min_triangulation_angle_degrees, then TriangulateMidpoint.  The track counts only if all three succeed;
+ *                its ratios are depth1_12 / depth1_13 and depth2_12 / depth2_23.  The baseline is (1, r2[m], r3[m]),
+ *                r[m] the element of index count / 2 of the sorted ratios, what nth_element leaves there.  The selection
+ *                is exact for any count: by rank counting in LDS where the shortest of the three track lists has at most
+ *                1024 tracks, in per-triplet scratch in global memory otherwise.
+ *                DEVIATION: a track with a ratio that is not finite and positive is dropped and counted
+ *                (num_dropped_ratios); the reference would hand a NaN to nth_element.
+ *                DEVIATION: a triplet with no usable track is removed here; the reference leaves its baseline at zero
+ *                and the NaN that follows poisons the whole matrix.
+ *   4. triplet_extractor.h:232-259, :67-84   The components of the triplets that survived step 3 (DEVIATION in order: the
+ *                reference forms them before it knows the baselines): two triplets are joined when they share a view
+ *                PAIR; sharing one view does not join them.  Union-find with the smaller root kept.  The largest
+ *                component wins, between equals the one with the smallest triplet number (the reference's std::sort on
+ *                sizes leaves this open).  No surviving triplet: TMI_BA_OK, usable = 0, nothing written.
+ *   5. :230-248, :295-421   The views of the chosen component in ascending index are the unknowns and the first of them is
+ *                held at the origin (DEVIATION: the reference holds whichever view its hash order meets first; with noise
+ *                the answer depends on this choice).  w = 1 / sqrt(the fewest chosen triplets any of the three views is
+ *                in).  Per triplet: t_ij = -R_i^T position_2 with R_i = AngleAxisToRotationMatrix(view_rotation[i])
+ *                (Ceres' formula, DEVIATION: the reference's Eigen::AngleAxisd divides by a zero angle), the three
+ *                rotations Quaterniond::FromTwoVectors(..).toRotationMatrix() by Eigen's formula (DEVIATION: where the two
+ *                vectors are within 1e-12 of antiparallel Eigen takes an axis from an SVD; here the rotation is by pi
+ *                about normalized(v0 x e_k), e_k the coordinate axis of v0's smallest |component|, the first of equals),
+ *                the three scale ratios and the nine 3 x 3 constraint blocks, kept as one record per triplet.  The matrix
+ *                is M = A^T A, dense, of order n = 3 (V' - 1), rows and columns of the held view left out; a block (i, j)
+ *                is the sum over the triplets with both views in ascending triplet number, one writer per block.
+ *   6. :195-208  The eigenvector of the smallest eigenvalue.  The reference: Spectra, 1 wanted, ncv 6, sigma 0.  HERE
+ *                (DEVIATION): the subspace iteration of tmi_ba_estimate_global_rotations_linear, step 2 there, with the
+ *                same block of 6 columns, start, Gram-Schmidt, Jacobi order and sign rule, through one dense Cholesky
+ *                factorisation of M + mu I, mu = relative_shift x the largest diagonal entry of M.  M Y is applied from
+ *                the triplet records as A^T (A Y), never from the factor.  Stop when |M q_0 - theta_0 q_0|_2 <=
+ *                tolerance x |M|_inf, the largest absolute row sum, or after max_iterations.  The noise-free problem has
+ *                eigenvalue exactly 0: the shift is what makes it factorable.  A pivot that is not positive: usable = 0,
+ *                nothing written.
+ *   7. :210-222, :432-470   A free view takes its segment of q_0 (|q_0| = 1 over the free views), the held view 0.  Then
+ *                the vote over every batch edge whose two views are both estimated: +1 where
+ *                AngleAxisRotatePoint(view_rotation[view1], normalized(p2 - p1)) . position_2 > 0 and -1 otherwise; all
+ *                positions are negated when the integer sum is negative.
+ * Fixed orders, no floating-point atomics, no FMA contraction in the new kernels: the same bytes from call to call.
+ * TMI_BA_ERR_UNSUPPORTED when n exceeds the dense solver's cap (11000, the knob TMI_BA_ROTATION_MAX_ORDER) before
+ * anything of that size is allocated, and for more than 2^30 triplets.
+ * TMI_BA_ERR_INVALID_ARGUMENT, before the device is looked for: a null problem, batch, options, view_position,
+ * view_estimated or summary, num_pairs == 0, a missing array, num_cameras != num_views, a bad intrinsics group or
+ * observation index, a view that observes a track twice, a view index out of range, pair_view1 >= pair_view2 (the
+ * reference's ViewIdPair keys are ordered and its look-ups for a sorted triplet rely on that), a repeated pair, a
+ * non-finite rotation_2, position_2 or orientation of a view with an edge, max_iterations <= 0, a tolerance that is not
+ * positive and finite, a negative or non-finite relative_shift, a triangulation angle outside (0, 180), a negative
+ * triplet_capacity.  On every failure the outputs are left as they were. */
+int32_t tmi_ba_estimate_global_positions_linear(const tmi_ba_problem* problem, const tmi_ba_view_pair_batch* batch,
+                                                const tmi_ba_linear_position_options* options, int32_t device,
+                                                double* view_position, uint8_t* view_estimated,
+                                                int32_t triplet_capacity, int32_t* triplet_view, int32_t* triplet_pair,
+                                                double* triplet_baseline, int32_t* triplet_num_common,
+                                                int32_t* triplet_num_used, int32_t* triplet_component,
+                                                tmi_ba_linear_position_summary* summary);
+
 /* ---- batched LocalizeViewToReconstruction: P3P RANSAC for many candidate views ------------------
  * reference: LocalizeViewToReconstruction (localize_view_to_reconstruction.cc:213-257), the inner loop of the
  * incremental and hybrid pipelines (incremental_reconstruction_estimator.cc:219-233), on its CALIBRATED path:

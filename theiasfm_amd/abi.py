@@ -659,6 +659,64 @@ class CLinearRotationSummary(C.Structure):
     ]
 
 
+class CLinearPositionOptions(C.Structure):
+    """tmi_ba_linear_position_options (Spectra's maxit and tol, the shift of the factored matrix, the start's seed, the
+    triangulation angle of ComputeTripletBaselineRatios)."""
+    _fields_ = [
+        ("max_iterations", C.c_int32),
+        ("tolerance", C.c_double),
+        ("relative_shift", C.c_double),
+        ("seed", C.c_uint64),
+        ("min_triangulation_angle_degrees", C.c_double),
+    ]
+
+
+def linear_position_options(**overrides) -> CLinearPositionOptions:
+    """The defaults of tmi_ba_linear_position_options_init."""
+    o = CLinearPositionOptions()
+    o.max_iterations = 1000
+    o.tolerance = 1e-10
+    o.relative_shift = 1e-9
+    o.seed = 0
+    o.min_triangulation_angle_degrees = 2.0
+    for k, v in overrides.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
+class CLinearPositionSummary(C.Structure):
+    """tmi_ba_linear_position_summary."""
+    _fields_ = [
+        ("num_views", C.c_int32),
+        ("num_pairs", C.c_int32),
+        ("num_triplets", C.c_int32),
+        ("num_triplets_with_baseline", C.c_int32),
+        ("num_triplet_components", C.c_int32),
+        ("num_chosen_triplets", C.c_int32),
+        ("num_chosen_views", C.c_int32),
+        ("triplets_written", C.c_int32),
+        ("num_dropped_ratios", C.c_int64),
+        ("order", C.c_int32),
+        ("num_iterations", C.c_int32),
+        ("converged", C.c_int32),
+        ("usable", C.c_int32),
+        ("eigenvalue", C.c_double * 2),
+        ("residual", C.c_double),
+        ("matrix_norm", C.c_double),
+        ("sign_votes", C.c_int32),
+        ("flipped", C.c_int32),
+        ("seconds", C.c_double),
+        ("kernel_seconds", C.c_double),
+        ("triplet_seconds", C.c_double),
+        ("baseline_seconds", C.c_double),
+        ("factor_seconds", C.c_double),
+        ("substitution_seconds", C.c_double),
+        ("graph_seconds", C.c_double),
+    ]
+
+
 class CLocalizationOptions(C.Structure):
     """tmi_ba_localization_options (RansacParameters, sample_consensus_estimator.h:57-65, and
     LocalizeViewToReconstructionOptions, localize_view_to_reconstruction.h:48-72)."""

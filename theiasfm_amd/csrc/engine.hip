@@ -51,6 +51,7 @@
 #include "cascade_match_kernels.h"
 #include "track_build_kernels.h"
 #include "view_graph_kernels.h"
+#include "position_linear_kernels.h"
 #include "two_view_ransac_kernels.h"
 #include "two_view_calibrated_kernels.h"
 #include "select_kernels.h"

@@ -1079,5 +1079,407 @@ int32_t tmi_ba_estimate_global_rotations_linear(const tmi_ba_view_pair_batch* Bh
     return TMI_BA_OK;
   });
 }
+}  // extern "C"
+
+// ---- LinearPositionEstimator (position_linear_kernels.h) ------------------------------------------
+namespace {
+// What the linear position estimator asks of its batch and options; null: fine.
+const char* check_linear_position_arguments(const tmi_ba_view_pair_batch* B, const tmi_ba_linear_position_options* o) {
+  const int V = B->num_views, E = B->num_pairs;
+  if (V < 0 || E < 0) return "linear positions: negative size";
+  if (E == 0) return "linear positions: no view pair";
+  if (!B->pair_view1 || !B->pair_view2 || !B->pair_rotation2 || !B->pair_position2 || !B->view_rotation)
+    return "linear positions: missing array";
+  if (E > (1 << 30)) return "linear positions: more than 2^30 pairs";
+  std::vector<uint64_t> keys((size_t)E);
+  std::vector<uint8_t> has_edge((size_t)V, 0);
+  for (int e = 0; e < E; ++e) {
+    const int a = B->pair_view1[e], b = B->pair_view2[e];
+    if (a < 0 || a >= V || b < 0 || b >= V) return "linear positions: view index out of range";
+    if (a >= b) return "linear positions: pair_view1 >= pair_view2 (the reference's ViewIdPair keys are ordered)";
+    keys[e] = ((uint64_t)a << 32) | (uint64_t)b;
+    has_edge[a] = has_edge[b] = 1;
+  }
+  std::sort(keys.begin(), keys.end());
+  if (std::adjacent_find(keys.begin(), keys.end()) != keys.end()) return "linear positions: a pair appears twice";
+  if (!all_finite(B->pair_rotation2, (size_t)3 * E) || !all_finite(B->pair_position2, (size_t)3 * E))
+    return "linear positions: non-finite rotation_2 or position_2";
+  for (int v = 0; v < V; ++v)
+    if (has_edge[v] && !all_finite(B->view_rotation + (size_t)3 * v, 3))
+      return "linear positions: non-finite orientation of a view with an edge";
+  if (o->max_iterations <= 0) return "linear positions: max_iterations is not positive";
+  if (!(o->tolerance > 0.0) || !std::isfinite(o->tolerance)) return "linear positions: tolerance is not positive and finite";
+  if (!(o->relative_shift >= 0.0) || !std::isfinite(o->relative_shift))
+    return "linear positions: relative_shift is negative or not finite";
+  if (!(o->min_triangulation_angle_degrees > 0.0) || !(o->min_triangulation_angle_degrees < 180.0))
+    return "linear positions: min_triangulation_angle_degrees outside (0, 180)";
+  return nullptr;
+}
+}  // namespace
+extern "C" {
+
+void tmi_ba_linear_position_options_init(tmi_ba_linear_position_options* o) {
+  if (!o) return;
+  o->max_iterations = 1000;  // Spectra's maxit and tol, which linear_position_estimator.cc:200-205 leaves alone
+  o->tolerance = 1e-10;
+  o->relative_shift = 1e-9;  // as tmi_ba_linear_rotation_options
+  o->seed = 0;
+  o->min_triangulation_angle_degrees = 2.0;  // compute_triplet_baseline_ratios.cc:60
+}
+
+int32_t tmi_ba_estimate_global_positions_linear(const tmi_ba_problem* P, const tmi_ba_view_pair_batch* Bh,
+                                                const tmi_ba_linear_position_options* opt, int32_t device,
+                                                double* view_position, uint8_t* view_estimated,
+                                                int32_t triplet_capacity, int32_t* triplet_view, int32_t* triplet_pair,
+                                                double* triplet_baseline, int32_t* triplet_num_common,
+                                                int32_t* triplet_num_used, int32_t* triplet_component,
+                                                tmi_ba_linear_position_summary* sum) {
+  if (!P || !Bh || !opt || !view_position || !view_estimated || !sum)
+    return bad_argument("linear positions: null problem, batch, options, view_position, view_estimated or summary");
+  memset(sum, 0, sizeof(*sum));
+  const double t0 = now_s();
+  // argument errors before the device is looked for
+  if (const char* why = check_linear_position_arguments(Bh, opt)) return bad_argument(why);
+  if (triplet_capacity < 0) return bad_argument("linear positions: negative triplet_capacity");
+  const int V = Bh->num_views, E = Bh->num_pairs, G = P->num_groups;
+  const int64_t No = P->num_observations;
+  if (P->num_cameras != V) return bad_argument("linear positions: num_cameras differs from the batch's num_views");
+  if (G < 0 || No < 0) return bad_argument("linear positions: negative size");
+  if (!P->camera_group || (G && (!P->group_model || !P->group_offset)) || (No && (!P->obs_camera || !P->obs_point || !P->obs_xy)))
+    return bad_argument("linear positions: missing array");
+  if (No >= (int64_t)0x7fffffffLL) return bad_argument("linear positions: more than 2^31 observations");
+  const int n_intr = G ? P->group_offset[G] : 0;
+  if (n_intr && !P->intrinsics) return bad_argument("linear positions: missing intrinsics");
+  for (int g = 0; g < G; ++g) {
+    const int o = P->group_offset[g], nk = P->group_offset[g + 1] - o;
+    if (P->group_model[g] < 0 || P->group_model[g] > 4 || nk != tmi_ba_intrinsics_size(P->group_model[g]) || o < 0)
+      return bad_argument("linear positions: bad intrinsics group");
+  }
+  std::vector<int4> cam((size_t)V);
+  for (int c = 0; c < V; ++c) {
+    const int g = P->camera_group[c];
+    if (g < 0 || g >= G) return bad_argument("linear positions: bad camera group");
+    cam[c] = make_int4(P->group_model[g], P->group_offset[g], P->group_offset[g + 1] - P->group_offset[g], 0);
+  }
+  for (int64_t i = 0; i < No; ++i)
+    if (P->obs_camera[i] < 0 || P->obs_camera[i] >= V || P->obs_point[i] < 0)
+      return bad_argument("linear positions: bad observation index");
+  const ViewTracks tracks = build_view_tracks(V, No, P->obs_camera, P->obs_point);
+  if (tracks.repeated) return bad_argument("linear positions: a view observes a track twice");
+  const SortedAdjacency adjacency = build_sorted_adjacency(V, E, Bh->pair_view1, Bh->pair_view2);
+  std::vector<int> slot_cam((size_t)No);
+  std::vector<double> slot_xy((size_t)2 * No);
+  for (int v = 0; v < V; ++v)
+    for (int r = tracks.ptr[v]; r < tracks.ptr[(size_t)v + 1]; ++r) {
+      slot_cam[r] = v;
+      slot_xy[(size_t)2 * r] = P->obs_xy[2 * tracks.obs[r]];
+      slot_xy[(size_t)2 * r + 1] = P->obs_xy[2 * tracks.obs[r] + 1];
+    }
+  const double cos_min = std::cos(opt->min_triangulation_angle_degrees * (M_PI / 180.0));
+  const int order_cap = rotation_order_cap();
+  sum->num_views = V;
+  sum->num_pairs = E;
+  return one_shot_batch(device, "linear positions: no such device", E, t0, &sum->seconds, [&](OneShot* s) -> int {
+    int rc;
+    hipStream_t st = s->stream;
+    const dim3 block(256);
+    auto grid = [](long long n) { return dim3((unsigned)std::max(1LL, (n + 255) / 256)); };
+    const int slots = 2 * E;
+    int *d_adj_ptr, *d_owner, *d_track_ptr, *d_track, *d_slot_cam, *d_count, *d_offset, *d_v1, *d_v2;
+    int2* d_adj;
+    int4* d_cam;
+    double *d_slot_xy, *d_intr, *d_feature, *d_rot2, *d_pos2, *d_orient;
+    unsigned long long *d_counters, *d_total;
+    TMI_HIP(s->upload(&d_adj_ptr, adjacency.ptr.data(), adjacency.ptr.size()));
+    TMI_HIP(s->upload(&d_adj, adjacency.adj.data(), adjacency.adj.size()));
+    TMI_HIP(s->upload(&d_owner, adjacency.owner.data(), adjacency.owner.size()));
+    TMI_HIP(s->upload(&d_track_ptr, tracks.ptr.data(), tracks.ptr.size()));
+    TMI_HIP(s->upload(&d_track, tracks.track.data(), tracks.track.size()));
+    TMI_HIP(s->upload(&d_slot_cam, slot_cam.data(), slot_cam.size()));
+    TMI_HIP(s->upload(&d_slot_xy, slot_xy.data(), slot_xy.size()));
+    TMI_HIP(s->upload(&d_cam, cam.data(), cam.size()));
+    TMI_HIP(s->upload(&d_intr, (const double*)P->intrinsics, (size_t)n_intr));
+    TMI_HIP(s->upload(&d_rot2, Bh->pair_rotation2, (size_t)3 * E));
+    TMI_HIP(s->upload(&d_pos2, Bh->pair_position2, (size_t)3 * E));
+    TMI_HIP(s->upload(&d_orient, Bh->view_rotation, (size_t)3 * V));
+    TMI_HIP(s->upload(&d_v1, (const int*)Bh->pair_view1, (size_t)E));
+    TMI_HIP(s->upload(&d_v2, (const int*)Bh->pair_view2, (size_t)E));
+    TMI_HIP(s->alloc(&d_count, (size_t)slots));
+    TMI_HIP(s->alloc(&d_offset, (size_t)slots + 1));
+    TMI_HIP(s->alloc(&d_feature, (size_t)3 * No));
+    TMI_HIP(s->alloc_filled(&d_counters, (size_t)lpos::kCounters, 0));
+    TMI_HIP(s->alloc(&d_total, 2));
+    StreamTimer triplet_timer(st, 4), baseline_timer(st, 2), component_timer(st, 2);
+    TMI_HIP(triplet_timer.status);
+    TMI_HIP(baseline_timer.status);
+    TMI_HIP(component_timer.status);
+    unsigned long long total_h[2] = {0, 0};
+
+    // ---- step 1: the triangles, counted, scanned, filled ----
+    TMI_HIP(triplet_timer.mark());
+    hipLaunchKernelGGL(lpos_triplet_kernel<false>, dim3((slots + 3) / 4), block, 0, st, slots, d_adj_ptr, d_adj, d_owner,
+                       d_track_ptr, d_count, nullptr, nullptr, nullptr, nullptr);
+    hipLaunchKernelGGL(lpos_scan_kernel, dim3(1), block, 0, st, d_count, slots, -1, d_offset, d_total);
+    TMI_HIP(triplet_timer.mark());
+    {
+      ReadBack rb(st);
+      rb.add(total_h, d_total, 1);
+      TMI_HIP(rb.finish());
+    }
+    if (total_h[0] > (1ull << 30)) {
+      s->error = "linear positions: more than 2^30 triplets";
+      return TMI_BA_ERR_UNSUPPORTED;
+    }
+    const int T = (int)total_h[0];
+    sum->num_triplets = T;
+    sum->triplet_seconds = triplet_timer.seconds(0, 1);
+    sum->kernel_seconds = sum->triplet_seconds;
+    if (T == 0) return TMI_BA_OK;  // (usable = 0: nothing is written)
+    int *d_tview, *d_tpair, *d_shortest, *d_scratch_at, *d_common, *d_used;
+    unsigned *d_first, *d_link, *d_parent, *d_label, *d_size;
+    double *d_baseline, *d_scratch;
+    TMI_HIP(s->alloc(&d_tview, (size_t)3 * T));
+    TMI_HIP(s->alloc(&d_tpair, (size_t)3 * T));
+    TMI_HIP(s->alloc(&d_shortest, (size_t)T));
+    TMI_HIP(s->alloc(&d_scratch_at, (size_t)T + 1));
+    TMI_HIP(triplet_timer.mark());
+    hipLaunchKernelGGL(lpos_triplet_kernel<true>, dim3((slots + 3) / 4), block, 0, st, slots, d_adj_ptr, d_adj, d_owner,
+                       d_track_ptr, nullptr, d_offset, d_tview, d_tpair, d_shortest);
+    hipLaunchKernelGGL(lpos_scan_kernel, dim3(1), block, 0, st, d_shortest, T, (int)lpos::kSelectCap, d_scratch_at,
+                       d_total + 1);
+    TMI_HIP(triplet_timer.mark());
+    {
+      ReadBack rb(st);
+      rb.add(total_h + 1, d_total + 1, 1);
+      TMI_HIP(rb.finish());
+    }
+    if (total_h[1] > (1ull << 30)) {
+      s->error = "linear positions: the selection scratch of the triplets exceeds 2^30 ratios";
+      return TMI_BA_ERR_UNSUPPORTED;
+    }
+    sum->triplet_seconds += triplet_timer.seconds(2, 3);
+
+    // ---- steps 2 to 4: features, baselines, the components of the survivors ----
+    TMI_HIP(s->alloc(&d_scratch, (size_t)total_h[1]));
+    TMI_HIP(s->alloc(&d_baseline, (size_t)3 * T));
+    TMI_HIP(s->alloc(&d_common, (size_t)T));
+    TMI_HIP(s->alloc(&d_used, (size_t)T));
+    TMI_HIP(s->alloc_filled(&d_first, (size_t)E, 0xff));
+    TMI_HIP(s->alloc(&d_link, (size_t)6 * T));
+    TMI_HIP(s->alloc(&d_parent, (size_t)T));
+    TMI_HIP(s->alloc(&d_label, (size_t)T));
+    TMI_HIP(s->alloc_filled(&d_size, (size_t)T, 0));
+    TMI_HIP(baseline_timer.mark());
+    hipLaunchKernelGGL(lpos_feature_kernel, grid(No), block, 0, st, (int)No, d_slot_cam, d_slot_xy, d_cam, d_intr, d_feature);
+    hipLaunchKernelGGL(lpos_baseline_kernel, dim3(T), block, 0, st, d_tview, d_tpair, d_track_ptr, d_track, d_feature,
+                       d_rot2, d_pos2, cos_min, d_shortest, d_scratch_at, d_scratch, d_baseline, d_common, d_used,
+                       d_counters);
+    TMI_HIP(baseline_timer.mark());
+    TMI_HIP(component_timer.mark());
+    hipLaunchKernelGGL(lpos_first_kernel, grid(T), block, 0, st, T, d_tpair, d_used, d_first);
+    hipLaunchKernelGGL(lpos_link_kernel, grid(T), block, 0, st, T, d_tpair, d_used, d_first, d_link);
+    hipLaunchKernelGGL(tb_iota_kernel, grid(T), block, 0, st, d_parent, (unsigned)T);
+    hipLaunchKernelGGL(tb_union_kernel, grid((long long)3 * T), block, 0, st, d_link, (long long)3 * T, (unsigned)T,
+                       d_parent, d_counters);
+    hipLaunchKernelGGL(tb_flatten_kernel, grid(T), block, 0, st, d_parent, (unsigned)T, d_label, d_counters);
+    hipLaunchKernelGGL(tb_sizes_kernel, grid(T), block, 0, st, d_label, (unsigned)T, d_size);
+    hipLaunchKernelGGL(lpos_component_stats_kernel, grid(T), block, 0, st, T, d_used, d_label, d_size, d_counters);
+    TMI_HIP(component_timer.mark());
+    std::vector<int> tview_h((size_t)3 * T), tpair_h((size_t)3 * T), common_h((size_t)T), used_h((size_t)T);
+    std::vector<unsigned> label_h((size_t)T);
+    std::vector<double> baseline_h((size_t)3 * T);
+    unsigned long long counters_h[lpos::kCounters];
+    {
+      ReadBack rb(st);
+      rb.add(tview_h.data(), d_tview, tview_h.size());
+      rb.add(tpair_h.data(), d_tpair, tpair_h.size());
+      rb.add(common_h.data(), d_common, common_h.size());
+      rb.add(used_h.data(), d_used, used_h.size());
+      rb.add(label_h.data(), d_label, label_h.size());
+      rb.add(baseline_h.data(), d_baseline, baseline_h.size());
+      rb.add(counters_h, d_counters, (size_t)lpos::kCounters);
+      TMI_HIP(rb.finish());
+    }
+    if (counters_h[lpos::kError]) {
+      s->error = "linear positions: a device loop reached its bound";
+      return TMI_BA_ERR_DEVICE;
+    }
+    sum->baseline_seconds = baseline_timer.seconds();
+    double graph_before = component_timer.seconds();
+    sum->graph_seconds = graph_before;
+    sum->kernel_seconds = sum->triplet_seconds + sum->baseline_seconds + sum->graph_seconds;
+    sum->num_dropped_ratios = (int64_t)counters_h[lpos::kDroppedRatios];
+    sum->num_triplet_components = (int32_t)counters_h[lpos::kComponents];
+    for (int t = 0; t < T; ++t) sum->num_triplets_with_baseline += used_h[t] > 0;
+    if (!counters_h[lpos::kBest]) return TMI_BA_OK;  // no triplet survived: usable = 0, nothing is written
+    const unsigned chosen_label = 0xffffffffu - (unsigned)counters_h[lpos::kBest];
+    std::vector<int> chosen, cview, cpair;
+    std::vector<double> cbase;
+    for (int t = 0; t < T; ++t)
+      if (used_h[t] > 0 && label_h[t] == chosen_label) {
+        chosen.push_back(t);
+        for (int k = 0; k < 3; ++k) {
+          cview.push_back(tview_h[(size_t)3 * t + k]);
+          cpair.push_back(tpair_h[(size_t)3 * t + k]);
+          cbase.push_back(baseline_h[(size_t)3 * t + k]);
+        }
+      }
+    const int C = (int)chosen.size();
+    if ((unsigned long long)C != (counters_h[lpos::kBest] >> 32)) {
+      s->error = "linear positions: the device reported impossible totals";
+      return TMI_BA_ERR_DEVICE;
+    }
+    const TripletRows rows = build_triplet_rows(V, C, cview.data());
+    const int Vc = (int)rows.views.size(), columns = Vc - 1;
+    sum->num_chosen_triplets = C;
+    sum->num_chosen_views = Vc;
+    // the cap before anything of the matrix's size is allocated
+    if ((int64_t)3 * columns > order_cap) {
+      s->error = "linear positions: 3 (estimated views - 1) exceeds the dense solver's cap (see the header)";
+      return TMI_BA_ERR_UNSUPPORTED;
+    }
+    const int n = 3 * columns;  // (<= the cap; >= 6: a triplet has three views)
+    sum->order = n;
+
+    // ---- step 5: the records and M = A^T A ----
+    const int nb = (n + 255) / 256, B = (int)rows.block_pq.size();
+    const size_t block_words = (size_t)n * lin::kBlock;
+    int *d_cview, *d_cpair, *d_view_count, *d_column, *d_view_ptr, *d_block_ptr, *d_view_column;
+    int2 *d_view_entry, *d_block_pq, *d_block_entry;
+    double *d_cbase, *d_record, *d_rowsum, *d_diag, *d_scal, *d_Q, *d_Y, *d_Z, *d_W, *d_U, *d_mgs[2], *d_gram, *d_res[3],
+        *d_position;
+    TMI_HIP(s->upload(&d_cview, cview.data(), cview.size()));
+    TMI_HIP(s->upload(&d_cpair, cpair.data(), cpair.size()));
+    TMI_HIP(s->upload(&d_cbase, cbase.data(), cbase.size()));
+    TMI_HIP(s->upload(&d_view_count, rows.view_count.data(), rows.view_count.size()));
+    TMI_HIP(s->upload(&d_view_column, rows.view_column.data(), rows.view_column.size()));
+    TMI_HIP(s->upload(&d_column, rows.column.data(), rows.column.size()));
+    TMI_HIP(s->upload(&d_view_ptr, rows.view_ptr.data(), rows.view_ptr.size()));
+    TMI_HIP(s->upload(&d_view_entry, rows.view_entry.data(), rows.view_entry.size()));
+    TMI_HIP(s->upload(&d_block_ptr, rows.block_ptr.data(), rows.block_ptr.size()));
+    TMI_HIP(s->upload(&d_block_pq, rows.block_pq.data(), rows.block_pq.size()));
+    TMI_HIP(s->upload(&d_block_entry, rows.block_entry.data(), rows.block_entry.size()));
+    TMI_HIP(s->alloc(&d_record, (size_t)lpos::kRecord * C));
+    TMI_HIP(s->alloc(&d_rowsum, (size_t)n));
+    TMI_HIP(s->alloc(&d_diag, (size_t)n));
+    TMI_HIP(s->alloc(&d_scal, 2));
+    TMI_HIP(s->alloc(&d_Q, block_words));
+    TMI_HIP(s->alloc(&d_Y, block_words));
+    TMI_HIP(s->alloc(&d_Z, block_words));
+    TMI_HIP(s->alloc(&d_W, block_words));
+    TMI_HIP(s->alloc(&d_U, (size_t)9 * C * lin::kBlock));
+    for (double*& p : d_mgs) TMI_HIP(s->alloc(&p, (size_t)nb * lin::kBlock));
+    TMI_HIP(s->alloc(&d_gram, (size_t)nb * lin::kGram));
+    for (double*& p : d_res) TMI_HIP(s->alloc(&p, (size_t)nb));
+    TMI_HIP(s->alloc(&d_position, (size_t)3 * V));
+    DenseSpd shifted;  // M + mu I, overwritten by its factor; kBlock right-hand sides
+    if ((rc = shifted.alloc(s, n, lin::kBlock, nullptr))) return rc;
+    ScalarFetch F;  // the small block: its last three words are the sums of the residuals' parts
+    if ((rc = F.alloc(s, shifted.flag, lin::kSmallWords))) return rc;
+    for (int q = 0; q < 3; ++q) F.set(q, d_res[q], nb);
+    double* d_small = F.d_norms;
+    const double* h_small = F.h_norms;
+    const dim3 rows_grid(nb);
+    ClassSeconds T3(st);
+    TMI_HIP(T3.status());
+    auto write_times = [&]() {
+      T3.write(sum);
+      sum->graph_seconds += graph_before;
+      sum->kernel_seconds += graph_before + sum->triplet_seconds + sum->baseline_seconds;
+    };
+    double scal_h[2] = {0.0, 0.0};
+    TMI_HIP(T3.begin(T3.kGraph));
+    hipLaunchKernelGGL(lpos_record_kernel, grid(C), block, 0, st, C, d_cview, d_cpair, d_cbase, d_view_count, d_orient,
+                       d_pos2, d_record);
+    TMI_HIP(hipMemsetAsync(shifted.A, 0, (size_t)n * n * sizeof(double), st));
+    hipLaunchKernelGGL(lpos_assemble_kernel, grid((long long)9 * B), block, 0, st, B, d_block_ptr, d_block_pq,
+                       d_block_entry, d_record, n, shifted.A);
+    hipLaunchKernelGGL(lpos_rowsum_kernel, dim3(n), block, 0, st, n, shifted.A, d_rowsum, d_diag);
+    hipLaunchKernelGGL(lpos_scalars_kernel, dim3(1), block, 0, st, n, d_rowsum, d_diag, d_scal);
+    hipLaunchKernelGGL(lpos_shift_kernel, rows_grid, block, 0, st, n, opt->relative_shift, d_scal, shifted.A);
+    TMI_HIP(T3.begin(T3.kFactor));
+    shifted.factor(st);
+    TMI_HIP(T3.begin(T3.kGraph));
+    hipLaunchKernelGGL(lin_start_kernel, dim3(((int)block_words + 255) / 256), block, 0, st, n, (unsigned long long)opt->seed,
+                       d_Q);
+    TMI_HIP(s->download(scal_h, d_scal, 2));
+    if ((rc = F.fetch(s, &T3, 0))) return rc;  // (no sum yet: the pivot flag alone)
+    sum->matrix_norm = scal_h[1];
+    if (F.flag()) {  // a pivot of M + mu I that is not positive: nothing is written
+      write_times();
+      return TMI_BA_OK;
+    }
+    const double threshold = opt->tolerance * scal_h[1];
+
+    // ---- step 6: subspace iteration with Rayleigh-Ritz ----
+    int iter = 0, launches = 0;
+    bool converged = false;
+    while (iter < opt->max_iterations && !converged) {
+      ++iter;
+      TMI_HIP(T3.begin(T3.kSubstitution));
+      TMI_HIP(hipMemcpyAsync(d_W, d_Q, block_words * sizeof(double), hipMemcpyDeviceToDevice, st));
+      shifted.substitute<lin::kBlock>(st, d_W, d_Y);
+      TMI_HIP(T3.begin(T3.kGraph));
+      for (int pass = 0; pass < 2; ++pass)
+        for (int j = 0; j <= lin::kBlock; ++j, ++launches)
+          hipLaunchKernelGGL(lin_mgs_kernel, rows_grid, block, 0, st, n, j, d_Y, d_mgs[(launches + 1) & 1],
+                             d_mgs[launches & 1]);
+      hipLaunchKernelGGL(lpos_apply_rows_kernel, grid((long long)C * lin::kBlock), block, 0, st, C, d_column, d_record,
+                         d_Y, d_U);
+      hipLaunchKernelGGL(lpos_apply_cols_kernel, grid((long long)columns * lin::kBlock), block, 0, st, columns, d_view_ptr,
+                         d_view_entry, d_record, d_U, d_Z);
+      hipLaunchKernelGGL(lin_gram_kernel, rows_grid, block, 0, st, n, d_Y, d_Z, d_gram);
+      hipLaunchKernelGGL(lin_ritz_kernel, dim3(1), dim3(64), 0, st, d_gram, nb, d_small);
+      hipLaunchKernelGGL(lin_rotate_kernel, rows_grid, block, 0, st, n, d_small, d_Y, d_Z, d_Q, d_res[0], d_res[1],
+                         d_res[2]);
+      if ((rc = F.fetch(s, &T3, 3, lin::kSmallResidual, lin::kSmallWords, /*with_flag=*/false))) return rc;
+      sum->residual = std::sqrt(h_small[lin::kSmallResidual]);
+      converged = sum->residual <= threshold;
+    }
+    sum->eigenvalue[0] = h_small[lin::kSmallTheta];
+    sum->eigenvalue[1] = h_small[lin::kSmallTheta + 1];
+    sum->num_iterations = iter;
+    sum->converged = converged;
+
+    // ---- step 7: the positions and the sign vote ----
+    std::vector<double> position_h((size_t)3 * V);
+    TMI_HIP(T3.begin(T3.kGraph));
+    hipLaunchKernelGGL(lpos_position_kernel, grid(V), block, 0, st, V, d_view_column, d_Q, d_position);
+    hipLaunchKernelGGL(lpos_vote_kernel, grid(E), block, 0, st, E, d_v1, d_v2, d_view_column, d_position, d_orient, d_pos2,
+                       d_counters);
+    TMI_HIP(T3.end());
+    {
+      ReadBack rb(st);
+      rb.add(position_h.data(), d_position, position_h.size());
+      rb.add(counters_h, d_counters, (size_t)lpos::kCounters);
+      TMI_HIP(rb.finish());
+    }
+    T3.collect();
+    write_times();
+    sum->sign_votes = (int32_t)((long long)counters_h[lpos::kVotesFor] - (long long)counters_h[lpos::kVotesAgainst]);
+    sum->flipped = sum->sign_votes < 0;
+    sum->usable = 1;
+    // the results, only now: a failure above leaves the caller's arrays as they were
+    for (int v = 0; v < V; ++v) {
+      view_estimated[v] = rows.view_column[v] > -2;
+      if (rows.view_column[v] > -2)
+        for (int k = 0; k < 3; ++k) {
+          const double x = position_h[(size_t)3 * v + k];
+          view_position[(size_t)3 * v + k] = sum->flipped ? -x : x;
+        }
+    }
+    if (triplet_capacity >= T) {
+      sum->triplets_written = 1;
+      if (triplet_view) std::copy(tview_h.begin(), tview_h.end(), triplet_view);
+      if (triplet_pair) std::copy(tpair_h.begin(), tpair_h.end(), triplet_pair);
+      if (triplet_baseline) std::copy(baseline_h.begin(), baseline_h.end(), triplet_baseline);
+      if (triplet_num_common) std::copy(common_h.begin(), common_h.end(), triplet_num_common);
+      if (triplet_num_used) std::copy(used_h.begin(), used_h.end(), triplet_num_used);
+      if (triplet_component)
+        for (int t = 0; t < T; ++t) triplet_component[t] = used_h[t] > 0 ? (int32_t)label_h[t] : -1;
+    }
+    return TMI_BA_OK;
+  });
+}
 
 }  // extern "C"

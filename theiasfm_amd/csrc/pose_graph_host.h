@@ -140,6 +140,134 @@ inline void scatter_free(int V, int held, const int* view_of, const double* x, d
                              full + (size_t)3 * (view_of ? view_of[p] : p));
 }
 
+// ---- the linear position estimator's rows (position_linear_kernels.h) ---------------------------------------------
+// The adjacency rows of the (checked: no pair twice) edges with every row in ascending neighbour: adj (neighbour, edge),
+// owner the row's view per slot.  The triangle finder intersects two such rows.
+struct SortedAdjacency {
+  std::vector<int> ptr;    // [V + 1]
+  std::vector<int2> adj;   // [2 E]
+  std::vector<int> owner;  // [2 E]
+};
+
+inline SortedAdjacency build_sorted_adjacency(int V, int E, const int32_t* view1, const int32_t* view2) {
+  SortedAdjacency S;
+  S.ptr.assign((size_t)V + 1, 0);
+  S.adj.resize((size_t)2 * E);
+  S.owner.resize((size_t)2 * E);
+  for (int e = 0; e < E; ++e) {
+    S.ptr[(size_t)view1[e] + 1]++;
+    S.ptr[(size_t)view2[e] + 1]++;
+  }
+  for (int v = 0; v < V; ++v) S.ptr[(size_t)v + 1] += S.ptr[v];
+  std::vector<int> fill(S.ptr.begin(), S.ptr.end() - 1);
+  for (int e = 0; e < E; ++e) {
+    S.adj[(size_t)fill[view1[e]]++] = make_int2(view2[e], e);
+    S.adj[(size_t)fill[view2[e]]++] = make_int2(view1[e], e);
+  }
+  for (int v = 0; v < V; ++v) {
+    std::sort(S.adj.begin() + S.ptr[v], S.adj.begin() + S.ptr[(size_t)v + 1],
+              [](const int2& p, const int2& q) { return p.x < q.x; });
+    std::fill(S.owner.begin() + S.ptr[v], S.owner.begin() + S.ptr[(size_t)v + 1], v);
+  }
+  return S;
+}
+
+// The (checked: indices in range) observations in view-major order, a view's in ascending track: track and obs (the
+// caller's observation) per slot.  repeated: some view observes a track twice.
+struct ViewTracks {
+  std::vector<int> ptr;      // [V + 1]
+  std::vector<int> track;    // [No]
+  std::vector<int64_t> obs;  // [No]
+  bool repeated = false;
+};
+
+inline ViewTracks build_view_tracks(int V, int64_t num_obs, const int32_t* obs_view, const int32_t* obs_track) {
+  ViewTracks T;
+  T.ptr.assign((size_t)V + 1, 0);
+  for (int64_t i = 0; i < num_obs; ++i) T.ptr[(size_t)obs_view[i] + 1]++;
+  for (int v = 0; v < V; ++v) T.ptr[(size_t)v + 1] += T.ptr[v];
+  std::vector<std::pair<int, int64_t>> slot((size_t)num_obs);
+  std::vector<int> fill(T.ptr.begin(), T.ptr.end() - 1);
+  for (int64_t i = 0; i < num_obs; ++i) slot[(size_t)fill[obs_view[i]]++] = {obs_track[i], i};
+  T.track.resize((size_t)num_obs);
+  T.obs.resize((size_t)num_obs);
+  for (int v = 0; v < V; ++v) {
+    std::sort(slot.begin() + T.ptr[v], slot.begin() + T.ptr[(size_t)v + 1]);
+    for (int r = T.ptr[v]; r < T.ptr[(size_t)v + 1]; ++r) {
+      T.track[r] = slot[r].first;
+      T.obs[r] = slot[r].second;
+      if (r > T.ptr[v] && slot[r].first == slot[(size_t)r - 1].first) T.repeated = true;
+    }
+  }
+  return T;
+}
+
+// The unknowns and the rows of A^T A over C chosen triplets (view [3 C], ascending triplet number): the views of the
+// triplets in ascending index, the first of them held (column -1), every other with a column; per free column its
+// triplets (view_entry: triplet, slot) and per 3 x 3 block (row column, column column) of the matrix the triplets that
+// hold both views (block_entry: triplet, 3 x the row's slot + the column's), all in ascending triplet.
+struct TripletRows {
+  std::vector<int> views;         // [V'] the estimated views, ascending; views[0] is held
+  std::vector<int> view_column;   // [V] >= 0: the column, -1: the held view, -2: not estimated
+  std::vector<int> view_count;    // [V] chosen triplets of the view
+  std::vector<int> column;        // [3 C] the slots' columns
+  std::vector<int> view_ptr;      // [V']  (V' - 1 columns)
+  std::vector<int2> view_entry;
+  std::vector<int> block_ptr;     // [B + 1]
+  std::vector<int2> block_pq;     // [B]
+  std::vector<int2> block_entry;
+};
+
+inline TripletRows build_triplet_rows(int V, int C, const int* view) {
+  TripletRows R;
+  R.view_column.assign((size_t)V, -2);
+  R.view_count.assign((size_t)V, 0);
+  for (size_t i = 0; i < (size_t)3 * C; ++i) R.view_count[view[i]]++;
+  for (int v = 0; v < V; ++v)
+    if (R.view_count[v] > 0) {
+      R.view_column[v] = (int)R.views.size() - 1;
+      R.views.push_back(v);
+    }
+  const int columns = std::max(0, (int)R.views.size() - 1);
+  R.column.resize((size_t)3 * C);
+  R.view_ptr.assign((size_t)columns + 1, 0);
+  for (size_t i = 0; i < (size_t)3 * C; ++i) {
+    R.column[i] = R.view_column[view[i]];
+    if (R.column[i] >= 0) R.view_ptr[(size_t)R.column[i] + 1]++;
+  }
+  for (int p = 0; p < columns; ++p) R.view_ptr[(size_t)p + 1] += R.view_ptr[p];
+  R.view_entry.resize((size_t)R.view_ptr[columns]);
+  std::vector<int> fill(R.view_ptr.begin(), R.view_ptr.end() - 1);
+  for (int c = 0; c < C; ++c)
+    for (int s = 0; s < 3; ++s) {
+      const int p = R.column[(size_t)3 * c + s];
+      if (p >= 0) R.view_entry[(size_t)fill[p]++] = make_int2(c, s);
+    }
+  R.block_ptr.push_back(0);
+  std::vector<std::pair<int, int2>> row;  // (column column, entry) of one row column
+  for (int p = 0; p < columns; ++p) {
+    row.clear();
+    for (int r = R.view_ptr[p]; r < R.view_ptr[(size_t)p + 1]; ++r) {
+      const int2 ent = R.view_entry[r];
+      for (int s = 0; s < 3; ++s) {
+        const int q = R.column[(size_t)3 * ent.x + s];
+        if (q >= 0) row.push_back({q, make_int2(ent.x, 3 * ent.y + s)});
+      }
+    }
+    std::stable_sort(row.begin(), row.end(),
+                     [](const std::pair<int, int2>& a, const std::pair<int, int2>& b) { return a.first < b.first; });
+    for (size_t i = 0; i < row.size(); ++i) {
+      if (i == 0 || row[i].first != row[i - 1].first) {
+        if (i > 0) R.block_ptr.push_back((int)R.block_entry.size());
+        R.block_pq.push_back(make_int2(p, row[i].first));
+      }
+      R.block_entry.push_back(row[i].second);
+    }
+    if (!row.empty()) R.block_ptr.push_back((int)R.block_entry.size());
+  }
+  return R;
+}
+
 // The stopping test of the two ADMM loops (l1_solver.h:157-170, constrained_l1_solver.cc:152-164) on the five squared
 // norms of an iteration: |A x - z - b|^2, |A x|^2, |z|^2, |rho A^T dz|^2, |rho A^T u|^2.
 struct AdmmNorms {

@@ -42,6 +42,7 @@ EXPORTS = (
     "tmi_ba_nonlinear_position_options_init", "tmi_ba_estimate_global_positions_nonlinear",
     "tmi_ba_nonlinear_rotation_options_init", "tmi_ba_estimate_global_rotations_nonlinear",
     "tmi_ba_linear_rotation_options_init", "tmi_ba_estimate_global_rotations_linear",
+    "tmi_ba_linear_position_options_init", "tmi_ba_estimate_global_positions_linear",
     "tmi_ba_localization_options_init", "tmi_ba_localize_views",
     "tmi_ba_match_options_init", "tmi_ba_match_features",
     "tmi_ba_cascade_match_options_init", "tmi_ba_match_features_cascade",
@@ -214,6 +215,13 @@ def load():
     L.tmi_ba_estimate_global_rotations_linear.argtypes = [
         PB, LR, C.c_int32, C.c_void_p, C.POINTER(abi.CLinearRotationSummary)]
     L.tmi_ba_estimate_global_rotations_linear.restype = C.c_int32
+    LP = C.POINTER(abi.CLinearPositionOptions)
+    L.tmi_ba_linear_position_options_init.argtypes = [LP]
+    L.tmi_ba_linear_position_options_init.restype = None
+    L.tmi_ba_estimate_global_positions_linear.argtypes = [
+        P, PB, LP, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + [
+        C.POINTER(abi.CLinearPositionSummary)]
+    L.tmi_ba_estimate_global_positions_linear.restype = C.c_int32
     ZO =C.POINTER(abi.CLocalizationOptions)
     L.tmi_ba_localization_options_init.argtypes = [ZO]
     L.tmi_ba_localization_options_init.restype = None
@@ -677,6 +685,50 @@ def estimate_global_positions_nonlinear(batch: abi.ViewPairBatch, fixed_view: in
     ran = ps.num_iterations + 1
     return dict(positions=pos, initial_positions=initial, residuals=res, costs=costs[:ran].copy(),
                 radii=radii[:ran].copy(), outcomes=outcomes[:ran].copy(), summary=ps)
+
+
+def estimate_global_positions_linear(problem: abi.Problem, batch: abi.ViewPairBatch, options=None, device: int = -1,
+                                      triplet_capacity=None, view_position=None, view_estimated=None):
+    """LinearPositionEstimator::EstimatePositions on the device.  problem: the cameras of every view (camera i is view
+    i) and all observations.  batch: the pairs (view1 < view2), pair_rotation2, pair_position2 and view_rotation, the
+    global orientations.  options: a CLinearPositionOptions (default: tmi_ba_linear_position_options_init's).
+    triplet_capacity: room of the optional triplet arrays (0: not asked for).  None runs the WHOLE call twice, once to
+    learn summary.num_triplets and once with that capacity: convenient for tests, twice the cost; a caller who times
+    the call or knows a bound passes a capacity.
+    view_position [V, 3] / view_estimated [V]: what the arrays hold where the call writes nothing (default zeros).
+    Returns a dict: positions [V, 3], estimated [V] uint8, summary (CLinearPositionSummary) and, where
+    summary.triplets_written, triplet_view [T, 3], triplet_pair [T, 3], triplet_baseline [T, 3], triplet_num_common,
+    triplet_num_used, triplet_component [T] (else None each).  Raises EngineError on any failure."""
+    L = load()
+    o = options if options is not None else abi.linear_position_options()
+    V = batch.num_views
+    cp, cb = problem.as_c(), batch.as_c()
+
+    def call(capacity):
+        pos = np.zeros((V, 3)) if view_position is None else np.array(view_position, dtype=np.float64).reshape(V, 3)
+        est = np.zeros(V, dtype=np.uint8) if view_estimated is None else np.array(view_estimated, dtype=np.uint8).reshape(V)
+        tv, tp = np.zeros((capacity, 3), dtype=np.int32), np.zeros((capacity, 3), dtype=np.int32)
+        tb = np.zeros((capacity, 3))
+        tc, tu, tl = (np.zeros(capacity, dtype=np.int32) for _ in range(3))
+        ps = abi.CLinearPositionSummary()
+        ptr = (lambda a: a.ctypes.data) if capacity > 0 else (lambda a: None)
+        st = L.tmi_ba_estimate_global_positions_linear(
+            C.byref(cp), C.byref(cb), C.byref(o), int(device), pos.ctypes.data, est.ctypes.data, int(capacity), ptr(tv),
+            ptr(tp), ptr(tb), ptr(tc), ptr(tu), ptr(tl), C.byref(ps))
+        if st != 0:
+            raise EngineError(st, "tmi_ba_estimate_global_positions_linear")
+        return pos, est, (tv, tp, tb, tc, tu, tl), ps
+
+    pos, est, trip, ps = call(0 if triplet_capacity is None else int(triplet_capacity))
+    if triplet_capacity is None and ps.num_triplets > 0:
+        pos, est, trip, ps = call(ps.num_triplets)
+    T = ps.num_triplets
+    written = bool(ps.triplets_written) and (triplet_capacity is None or int(triplet_capacity) > 0)
+    names = ("triplet_view", "triplet_pair", "triplet_baseline", "triplet_num_common", "triplet_num_used",
+             "triplet_component")
+    out = dict(positions=pos, estimated=est, summary=ps)
+    out.update({k: (a[:T].copy() if written else None) for k, a in zip(names, trip)})
+    return out
 
 
 def estimate_global_rotations_nonlinear(batch: abi.ViewPairBatch, view_rotation, options=None, view_given=None,
