@@ -18,7 +18,8 @@
 //    pixels are centred on the principal point prior or, without one, on (image_width / 2, image_height / 2), as a
 //    PINHOLE camera set from the priors centres them (pinhole_camera_model.cc:85-90) -- no distortion priors.
 // twoview_info->visibility_score is 0, as in the reference: it computes the score from *inlier_indices BEFORE assigning
-// them, after clearing them on entry (estimate_twoview_info.cc:243-245, :260).  num_homography_inliers is not written.
+// them, after clearing them on entry (estimate_twoview_info.cc:243-245, :260).  num_homography_inliers is not written
+// here, as in the reference: CountHomographyInliers (theia/sfm/estimators/estimate_homography.h) is what sets it.
 // options.rng cannot be honoured; the samples come from options.seed, an extension field.
 #ifndef THEIA_MI355_SFM_ESTIMATE_TWOVIEW_INFO_H_
 #define THEIA_MI355_SFM_ESTIMATE_TWOVIEW_INFO_H_

@@ -7,9 +7,11 @@
 //
 // The RANSAC of EstimateTwoViewInfo (:128-134) that runs before this step exists for both branches
 // (theia/sfm/estimate_twoview_info.h on tmi_ba_estimate_uncalibrated_relative_poses and, with inlier-count scoring,
-// tmi_ba_estimate_calibrated_relative_poses; DESIGN.md sections 8.10 and 8.11).  Out of scope: guided matching (:157-168) and the
-// homography inlier count (:124).  The caller hands over what VerifyMatches has once those ran: the two cameras
-// (SetupCameras :56-68) and the pair's correspondences.
+// tmi_ba_estimate_calibrated_relative_poses; DESIGN.md sections 8.10 and 8.11), and so does the homography inlier count
+// VerifyMatches takes first (:124, :326-363: theia/sfm/estimators/estimate_homography.h, CountHomographyInliers on
+// tmi_ba_estimate_homographies).  Out of scope: guided matching
+// (:157-168).  The caller hands over what VerifyMatches has once those ran: the two cameras (SetupCameras :56-68) and
+// the pair's correspondences.
 #ifndef THEIA_MI355_TWO_VIEW_MATCH_GEOMETRIC_VERIFICATION_H_
 #define THEIA_MI355_TWO_VIEW_MATCH_GEOMETRIC_VERIFICATION_H_
 #include <vector>

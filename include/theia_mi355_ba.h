@@ -2068,6 +2068,80 @@ int32_t tmi_ba_estimate_calibrated_relative_poses(
     double* rotation, double* position, uint8_t* corr_inlier, int32_t* hypothesis_cost,
     tmi_ba_two_view_ransac_summary* summary);
 
+/* ---- batched EstimateHomography: four-point RANSAC for many view pairs, inlier-count or MLESAC scoring ----
+ * reference: the first step of TwoViewMatchGeometricVerification::VerifyMatches, CountHomographyInliers
+ * (two_view_match_geometric_verification.cc:124, :326-363): EstimateHomography with RansacType::RANSAC
+ * (estimators/estimate_homography.cc:54-117) over FourPointHomography (pose/four_point_homography.cc:72-101) and
+ * SampleConsensusEstimator::Estimate (solvers/sample_consensus_estimator.h:246-344) with InlierSupport (use_mle == 0)
+ * or MLEQualityMeasurement (use_mle != 0, solvers/mle_quality_measurement.h:58-71; the scoring CountHomographyInliers
+ * passes on by default).  Not provided: PROSAC, LMED and exhaustive sampling, use_Tdd_test.
+ * A one-shot call shaped like tmi_ba_estimate_uncalibrated_relative_poses, whose summary, pair_offset, pair_mask,
+ * pair_stream, samples / samples_given, integer outputs and corr_inlier it shares.  What differs: feature1 / feature2
+ * are in WHATEVER units the caller uses (pixels, centred pixels, normalised coordinates: H maps feature1 to feature2 in
+ * them) and pair_error_threshold is RansacParameters::error_thresh in those units SQUARED; the model is homography [9];
+ * the options are tmi_ba_homography_ransac_options, those of the sibling calls plus use_mle.  Per selected pair, in
+ * this order:
+ *   1. n < 4                                                                                       -> status 1.
+ *   2. The sample of iteration i: step 2 of the uncalibrated call with 8 replaced by 4 (samples[4 (max_iterations p +
+ *      i) + k]; word c = 4 (q 2^32 + i) + k; four swaps).  THE SAMPLE SEQUENCES ARE NOT THE REFERENCE'S.
+ *   3. FourPointHomography on the four points.  Per image NormalizeImagePoints (pose/util.cc:82-115): the centroid (sums
+ *      in sample order, / 4), rms = sqrt(sum((dx^2 + dy^2)) / 4), nf = sqrt(2) / rms, T = [nf 0 -nf cx; 0 nf -nf cy;
+ *      0 0 1]; the normalised points hnormalized(T x) = (nf x + (-(nf cx)), nf y + (-(nf cy))).  The 8x9 rows of
+ *      CreateActionConstraint (:55-64) in the reference's row and column order, for the normalised (a, b) of image 1 and
+ *      (c, d) of image 2: row 2k = (0, 0, 0, -a, -b, -1, a d, b d, d), row 2k + 1 = (a, b, 1, 0, 0, 0, -(a c), -(b c),
+ *      -c).  The null vector by elimination with FULL pivoting under the eight-point call's rules: the pivot is the
+ *      entry of largest magnitude, strict >, ties to the lowest (row, column); the rank counts the pivots with
+ *      |pivot| > 8 DBL_EPSILON |largest pivot|; back-substitution from 1 in the last permuted column, each sum in
+ *      ascending column order; the vector is normalised to unit length with its largest-magnitude entry (the first among
+ *      equals) positive.  H = T2^-1 M T1 with M(i, j) = null[3 i + j] and T2^-1 = [1/nf 0 cx; 0 1/nf cy; 0 0 1] in
+ *      closed form: first G = M T1, then T2^-1 G.
+ *      DEVIATIONS: the reference takes the null vector from a Jacobi SVD of A^T A (the same vector up to rounding and
+ *      sign where the rank is 8); and a rank other than 8 gives NO MODEL -- three collinear points, a repeated point --
+ *      as does a nf that is not finite (rms == 0, tested before the elimination), where the reference returns true for
+ *      any sample and scores whatever vector the SVD leaves in a null space of dimension 2 or more.
+ *   4. The residual of a correspondence (estimate_homography.cc:90-96, the asymmetric transfer error):
+ *      p = H (x1, y1, 1), each row as (H0 x1 + H1 y1) + H2, r = (x2 - p0 / p2)^2 + (y2 - p1 / p2)^2.  Inlier iff
+ *      r < threshold; a NaN r is an outlier.
+ *   5. The cost of the ONE model of a sample.  use_mle == 0: the number of outliers, an integer.  use_mle != 0:
+ *      MLEQualityMeasurement::ComputeCost, the double sum over the correspondences of (r < threshold ? r : threshold),
+ *      and the integer inlier count of the same pass.  The sum has ONE FIXED SHAPE: lane l of 64 adds its
+ *      correspondences l, l + 64, ... in ascending order starting from +0.0; the 64 partial sums are combined by the xor
+ *      butterfly with offsets 32, 16, 8, 4, 2, 1 (lane l takes its own value + that of lane l ^ offset; every lane ends
+ *      with the same value since addition is commutative).  Two runs give the same bytes.
+ *   6. The replay is step 5 of tmi_ba_localize_views with a sample size of 4 and one model per sample: ascending
+ *      iteration order, strict < on the cost (int from INT_MAX, or double from DBL_MAX); the bound is updated from the
+ *      INLIER COUNT, which under MLE is not the cost, and only ever goes down; inlier_ratio < 4 / n skips the update;
+ *      ComputeMaxIterations(4, ...) from a host-made table; a sample without a model counts as an iteration; THE RESULT
+ *      DOES NOT DEPEND ON chunk_iterations (0: max(min_iterations, 64)).
+ *   7. Final: the inlier mask of the best model, num_inliers, confidence = 1 - (1 - (num_inliers / n)^4)^num_iterations
+ *      (host); no model in any iteration -> status 2; otherwise status 0 and homography [9] column-major as the
+ *      reference stores an Eigen::Matrix3d, as estimated: no scale is imposed.
+ * hypothesis_cost [num_selected * max_iterations] (optional, for tests): the integer cost of every replayed hypothesis,
+ * or n - inliers under MLE; -1 for no model or not replayed.  hypothesis_cost_real [num_selected * max_iterations]
+ * (optional, for tests): the MLE cost, NaN where hypothesis_cost is -1; passing it with use_mle == 0 is an argument
+ * error.  Steps 3 to 5 use + - * / and sqrt only and are never contracted into FMA.  The argument errors and their order
+ * relative to the device check are those of the uncalibrated call, with 4 in place of 8. */
+typedef struct tmi_ba_homography_ransac_options {
+  double   failure_probability;  /* 0.01                                                                       */
+  double   min_inlier_ratio;     /* 0                                                                          */
+  int32_t  min_iterations;       /* 10                                                                         */
+  int32_t  max_iterations;       /* 1000                                                                       */
+  int32_t  chunk_iterations;     /* 0 = the engine's choice                                                    */
+  int32_t  device;               /* -1 = the current device                                                    */
+  uint64_t seed;                 /* 0                                                                          */
+  int32_t  use_mle;              /* 0 = inlier-count scoring; nonzero = MLESAC (RansacParameters::use_mle)     */
+  int32_t  reserved;             /* 0                                                                          */
+} tmi_ba_homography_ransac_options;
+void tmi_ba_homography_ransac_options_init(tmi_ba_homography_ransac_options* options);
+
+int32_t tmi_ba_estimate_homographies(
+    const tmi_ba_homography_ransac_options* options, int32_t num_pairs, const int64_t* pair_offset,
+    const double* feature1, const double* feature2, const double* pair_error_threshold, const uint8_t* pair_mask,
+    const uint32_t* pair_stream, const int32_t* samples, int32_t samples_given, int8_t* pair_status,
+    int32_t* pair_num_correspondences, int32_t* pair_num_inliers, int32_t* pair_num_iterations,
+    int32_t* pair_best_iteration, double* pair_confidence, double* homography, uint8_t* corr_inlier,
+    int32_t* hypothesis_cost, double* hypothesis_cost_real, tmi_ba_two_view_ransac_summary* summary);
+
 /* Test hook: FNV-1a checksums of the static structure arrays resident in HBM -- built in HBM by
  * sort / scan kernels (one rank, no shared intrinsics blocks; TMI_BA_HOST_SETUP=1 disables) or on
  * host threads otherwise.  out[0] = 1 when the device built it; the other slots are documented at

@@ -797,6 +797,33 @@ def two_view_ransac_options(**overrides) -> CTwoViewRansacOptions:
     return o
 
 
+class CHomographyRansacOptions(C.Structure):
+    """tmi_ba_homography_ransac_options: the fields of tmi_ba_two_view_ransac_options plus use_mle."""
+    _fields_ = CTwoViewRansacOptions._fields_ + [
+        ("use_mle", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
+def homography_ransac_options(**overrides) -> CHomographyRansacOptions:
+    """The defaults of tmi_ba_homography_ransac_options_init."""
+    o = CHomographyRansacOptions()
+    o.failure_probability = 0.01
+    o.min_inlier_ratio = 0.0
+    o.min_iterations = 10
+    o.max_iterations = 1000
+    o.chunk_iterations = 0
+    o.device = -1
+    o.seed = 0
+    o.use_mle = 0
+    o.reserved = 0
+    for k, v in overrides.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
 CALIBRATED_SLOTS = 10  # models per sample of tmi_ba_estimate_calibrated_relative_poses (the stride of its hypothesis_cost)
 
 

@@ -54,6 +54,7 @@
 #include "position_linear_kernels.h"
 #include "two_view_ransac_kernels.h"
 #include "two_view_calibrated_kernels.h"
+#include "homography_kernels.h"
 #include "select_kernels.h"
 #include "structure_gpu.h"
 #include <hipcub/hipcub.hpp>

@@ -25,6 +25,21 @@
 // iterations at or beyond the item's current max_iterations are not evaluated, those evaluated beyond the point where
 // the replay stops are discarded.  ComputeMaxIterations is a host-made table over the inlier count (log and pow of the
 // host's libm, so that a CPU model gets the same integers).
+//
+// MLESAC scoring (MLEQualityMeasurement::ComputeCost, solvers/mle_quality_measurement.h:58-71) is a second pair of
+// kernels beside the integer ones, for a problem P that also gives residual(model, x), the real residual `outlier` is
+// written on:
+//
+//   ransac_score_mle_kernel<P>   the wavefront of ransac_score_kernel: lane l adds min(r, thresh) of its correspondences
+//                                l, l + 64, .. in ascending order from +0.0 and counts those with r < thresh; the 64
+//                                partial sums are combined by the xor butterfly with offsets 32, 16, 8, 4, 2, 1 (every
+//                                lane ends with the same double: one fixed shape, the same bytes on every run)
+//   ransac_replay_mle_kernel<P>  the replay with a double cost (strict <, initially DBL_MAX); the bound is updated from
+//                                the INLIER COUNT of the same pass, which under MLE is not the cost
+//
+// ransac_hypothesis_kernel and ransac_final_inliers serve both scorings.  What the MLE kernels need beyond RansacBatch is
+// a struct of its own (RansacMle), passed beside it, so that RansacBatch, RansacState and the integer kernels are what
+// they were before MLE existed.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -67,6 +82,14 @@ struct RansacBatch {
   int* cost;                      // [num_active chunk kSlots]
   RansacState* state;             // [num_selected]
   int* hypothesis_cost;           // [num_selected max_iterations kSlots] or null
+};
+
+// What the MLE kernels carry beside a RansacBatch.  RansacState::best_cost holds n - inliers of the best model.
+struct RansacMle {
+  double* cost;                   // [num_active chunk kSlots] per chunk: the MLE cost
+  int* inliers;                   // [num_active chunk kSlots] per chunk: the correspondences with r < thresh
+  double* best_cost;              // [num_selected] carried from chunk to chunk; DBL_MAX: no model yet
+  double* hypothesis_cost;        // [num_selected max_iterations kSlots] or null; preset to NaN by the host
 };
 
 // Word c of the splitmix64 stream from state `seed`: the output mix of seed + (c + 1) gamma.
@@ -277,6 +300,121 @@ __device__ __forceinline__ int ransac_final_inliers(const RansacBatch& B, int s,
   count = ransac_wave_sum(count);
   if (lane == 0) num_inliers[s] = count;
   return count;
+}
+
+// ---- MLESAC scoring ----------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double ransac_wave_sum_real(double c) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) c = c + __shfl_xor(c, off, 64);
+  return c;
+}
+
+template <class P>
+__global__ __launch_bounds__(256) void ransac_score_mle_kernel(RansacBatch B, RansacMle E) {
+#pragma clang fp contract(off)
+  constexpr int G = P::kScoreSlots, kGroups = P::kSlots / G;
+  static_assert(P::kSlots % G == 0, "kScoreSlots divides kSlots");
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int lane = threadIdx.x & 63;
+  const long long id = (long long)blockIdx.x * 4 + wave;  // (active, iteration, group of slots)
+  if (id >= (long long)B.num_active * B.chunk * kGroups) return;
+  int any = 0;
+#pragma unroll
+  for (int k = 0; k < G; ++k) any |= B.has_model[G * id + k];
+  if (any == 0) return;
+  const int s = B.active[(int)(id / ((long long)B.chunk * kGroups))];
+  const long long o0 = B.sel_ptr[s];
+  const int n = (int)(B.sel_ptr[s + 1] - o0);
+  const double thresh = B.threshold[s];
+  const double* __restrict__ m = B.models + (long long)P::kModel * G * id;
+  double c[G];
+  int in[G];
+#pragma unroll
+  for (int k = 0; k < G; ++k) {
+    c[k] = 0.0;
+    in[k] = 0;
+  }
+  for (int q = lane; q < n; q += 64) {
+    const long long o = o0 + q;
+    double x[P::kPlanes];
+#pragma unroll
+    for (int r = 0; r < P::kPlanes; ++r) x[r] = B.plane[r][o];
+#pragma unroll
+    for (int k = 0; k < G; ++k) {
+      const double r = P::residual(m + P::kModel * k, x);
+      const bool inlier = r < thresh;  // (a NaN residual is an outlier)
+      c[k] = c[k] + (inlier ? r : thresh);
+      in[k] += inlier ? 1 : 0;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < G; ++k) {
+    c[k] = ransac_wave_sum_real(c[k]);
+    in[k] = ransac_wave_sum(in[k]);
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < G; ++k) {
+      E.cost[G * id + k] = c[k];
+      E.inliers[G * id + k] = in[k];
+    }
+  }
+}
+
+template <class P>
+__global__ __launch_bounds__(64) void ransac_replay_mle_kernel(RansacBatch B, RansacMle E) {
+  const int a = blockIdx.x * 64 + threadIdx.x;
+  if (a >= B.num_active) return;
+  const int s = B.active[a];
+  RansacState* sp = B.state + s;
+  double best_cost = E.best_cost[s];
+  int best_outliers = sp->best_cost, best_iteration = sp->best_iteration, best_solution = sp->best_solution;
+  int max_iterations = sp->max_iterations, num_iterations = sp->num_iterations;
+  const long long o0 = B.sel_ptr[s];
+  const int n = (int)(B.sel_ptr[s + 1] - o0);
+  const int* __restrict__ bound = B.bound_table + o0 + s;
+  long long best_id = -1;
+  for (int j = 0; j < B.chunk; ++j) {
+    const int i = B.chunk_start + j;
+    if (i >= max_iterations) break;
+    const long long id0 = ((long long)a * B.chunk + j) * P::kSlots;
+#pragma unroll
+    for (int k = 0; k < P::kSlots; ++k) {
+      const long long h = ((long long)s * B.max_iterations + i) * P::kSlots + k;
+      if (B.has_model[id0 + k] != 0) {
+        const double c = E.cost[id0 + k];
+        const int inliers = E.inliers[id0 + k];
+        if (c < best_cost) {
+          best_cost = c;
+          best_outliers = n - inliers;
+          best_iteration = i;
+          best_solution = k;
+          best_id = id0 + k;
+          if (inliers >= P::kSample) {  // (inlier_ratio < kSample / n skips the update of the bound)
+            const int m = bound[inliers];
+            if (m < max_iterations) max_iterations = m;
+          }
+        }
+        if (B.hypothesis_cost) B.hypothesis_cost[h] = n - inliers;
+        if (E.hypothesis_cost) E.hypothesis_cost[h] = c;
+      } else if (B.hypothesis_cost) {
+        B.hypothesis_cost[h] = -1;
+      }
+    }
+    num_iterations = i + 1;
+  }
+  E.best_cost[s] = best_cost;
+  sp->best_cost = best_outliers;
+  sp->best_iteration = best_iteration;
+  sp->best_solution = best_solution;
+  sp->max_iterations = max_iterations;
+  sp->num_iterations = num_iterations;
+  if (num_iterations >= max_iterations) sp->done = 1;
+  if (best_id >= 0) {
+    const double* m = B.models + P::kModel * best_id;
+    for (int q = 0; q < P::kModel; ++q) sp->model[q] = m[q];
+  }
 }
 #endif  // __HIPCC__
 

@@ -2951,3 +2951,225 @@ int32_t tmi_ba_estimate_calibrated_relative_poses(
       corr_inlier, hypothesis_cost, sum);
 }
 }  // extern "C"
+
+// ---- batched EstimateHomography: four-point RANSAC, either scoring (homography_kernels.h) ----
+namespace {
+// The MLESAC half of a RansacRun: the double costs, the inlier counts and the double best cost beside RansacBatch, and
+// the chunk loop over the MLE kernels.  (The loop is written out once more rather than shared with
+// RansacRun::chunks: the two differ in the kernels launched, and the integer calls' loop stays as it is.)
+struct RansacMleRun : RansacRun {
+  RansacMle E = {};
+
+  template <class P>
+  int upload_mle(OneShot* s, bool want_hypothesis_cost_real) {
+    memset(&E, 0, sizeof(E));
+    const size_t slots = (size_t)S * chunk * P::kSlots, hyp = (size_t)S * K * P::kSlots;
+    const std::vector<double> best((size_t)S, std::numeric_limits<double>::max());
+    TMI_HIP(s->alloc(&E.cost, slots));
+    TMI_HIP(s->alloc(&E.inliers, slots));
+    TMI_HIP(s->upload(&E.best_cost, best.data(), best.size()));
+    TMI_HIP(hipStreamSynchronize(s->stream));  // (`best` goes out of scope)
+    if (want_hypothesis_cost_real) {
+      const std::vector<double> nan(hyp, std::numeric_limits<double>::quiet_NaN());
+      TMI_HIP(s->upload(&E.hypothesis_cost, nan.data(), nan.size()));
+      TMI_HIP(hipStreamSynchronize(s->stream));
+    }
+    return TMI_BA_OK;
+  }
+
+  template <class P>
+  int chunks_mle(OneShot* s, tmi_ba_two_view_ransac_summary* phases) {
+    const hipStream_t stream = s->stream;
+    std::vector<int> active;
+    const int max_chunks = (K + chunk - 1) / chunk;
+    for (int ch = 0; ch < max_chunks; ++ch) {
+      active.clear();
+      for (int v = 0; v < S; ++v)
+        if (!state[v].done) active.push_back(v);
+      if (active.empty()) break;
+      TMI_HIP(hipMemcpyAsync(d_active, active.data(), active.size() * sizeof(int), hipMemcpyHostToDevice, stream));
+      B.num_active = (int)active.size();
+      B.chunk_start = ch * chunk;
+      const long long items = (long long)B.num_active * chunk;
+      StreamTimer phase(stream, 4);
+      TMI_HIP(phase.status);
+      TMI_HIP(phase.mark());
+      hipLaunchKernelGGL(ransac_hypothesis_kernel<P>, dim3((unsigned)((items + P::kThreads - 1) / P::kThreads)),
+                         dim3(P::kThreads), 0, stream, B);
+      TMI_HIP(phase.mark());
+      hipLaunchKernelGGL(ransac_score_mle_kernel<P>, dim3((unsigned)((items * (P::kSlots / P::kScoreSlots) + 3) / 4)),
+                         dim3(256), 0, stream, B, E);
+      TMI_HIP(phase.mark());
+      hipLaunchKernelGGL(ransac_replay_mle_kernel<P>, dim3((unsigned)((B.num_active + 63) / 64)), dim3(64), 0, stream,
+                         B, E);
+      TMI_HIP(phase.mark());
+      TMI_HIP(hipGetLastError());
+      TMI_HIP(s->download(state.data(), B.state, state.size()));
+      TMI_HIP(hipStreamSynchronize(stream));  // (also: `active` is free to change)
+      phases->hypothesis_seconds += phase.seconds(0, 1);
+      phases->score_seconds += phase.seconds(1, 2);
+      phases->replay_seconds += phase.seconds(2, 3);
+      ++chunks_run;
+    }
+    return TMI_BA_OK;
+  }
+};
+}  // namespace
+
+extern "C" {
+void tmi_ba_homography_ransac_options_init(tmi_ba_homography_ransac_options* o) {
+  if (!o) return;
+  o->failure_probability = 0.01;  // sample_consensus_estimator.h:57-65
+  o->min_inlier_ratio = 0.0;
+  o->min_iterations = 10;         // estimate_twoview_info.h:70
+  o->max_iterations = 1000;       // estimate_twoview_info.h:71
+  o->chunk_iterations = 0;
+  o->device = -1;
+  o->seed = 0;
+  o->use_mle = 0;
+  o->reserved = 0;
+}
+
+// The argument checks, the presets and the packing are those of two_view_ransac_call with a sample of four, written out
+// again: that function's outputs and instantiations stay as they are.
+int32_t tmi_ba_estimate_homographies(
+    const tmi_ba_homography_ransac_options* L, int32_t num_pairs, const int64_t* pair_offset, const double* feature1,
+    const double* feature2, const double* pair_error_threshold, const uint8_t* pair_mask, const uint32_t* pair_stream,
+    const int32_t* samples, int32_t samples_given, int8_t* pair_status, int32_t* pair_num_correspondences,
+    int32_t* pair_num_inliers, int32_t* pair_num_iterations, int32_t* pair_best_iteration, double* pair_confidence,
+    double* homography, uint8_t* corr_inlier, int32_t* hypothesis_cost, double* hypothesis_cost_real,
+    tmi_ba_two_view_ransac_summary* sum) {
+  using P = HomographyProblem;
+  constexpr int kSample = P::kSample;
+  auto bad = [&](const char* why) { return bad_argument((std::string("homographies: ") + why).c_str()); };
+  if (!L || !sum) return bad("null options or summary");
+  memset(sum, 0, sizeof(*sum));
+  const double t0 = now_s();
+  // argument errors before the device is looked for
+  const int Npair = num_pairs;
+  if (Npair < 0) return bad("negative size");
+  if (!pair_offset) return bad("missing array");
+  if (pair_offset[0] != 0) return bad("pair_offset must start at 0");
+  for (int p = 0; p < Npair; ++p)
+    if (pair_offset[p + 1] < pair_offset[p]) return bad("pair_offset decreases");
+  const int64_t total = pair_offset[Npair];
+  if (total >= (int64_t)0x7fffffffLL) return bad("more than 2^31 correspondences");
+  if (total && (!feature1 || !feature2)) return bad("missing array");
+  if (const char* why = ransac_options_error(L, samples, samples_given)) return bad(why);
+  const bool mle = L->use_mle != 0;
+  if (hypothesis_cost_real && !mle) return bad("hypothesis_cost_real without use_mle");
+  const int K = L->max_iterations;
+  std::vector<int> selected, sel_pair, sel_rank;  // sel_pair: the attempted ones, the device's slots
+  for (int p = 0; p < Npair; ++p) {
+    if (pair_mask && !pair_mask[p]) continue;
+    const int64_t n = pair_offset[p + 1] - pair_offset[p];
+    if (n >= kSample) {
+      if (!pair_error_threshold) return bad("missing pair_error_threshold");
+      if (!(pair_error_threshold[p] > 0.0)) return bad("error threshold must be positive");
+      if (samples_given)
+        for (int64_t i = 0; i < K; ++i) {
+          const int32_t* t = samples + kSample * ((int64_t)K * p + i);
+          for (int a = 0; a < kSample; ++a) {
+            bool wrong = t[a] < 0 || t[a] >= n;
+            for (int b = 0; b < a; ++b) wrong = wrong || t[a] == t[b];
+            if (wrong) return bad("a sample with a repeated or out-of-range index");
+          }
+        }
+      sel_pair.push_back(p);
+      sel_rank.push_back((int)selected.size());
+    }
+    selected.push_back(p);
+  }
+  const int num_selected = (int)selected.size(), S = (int)sel_pair.size();
+  // nothing below fails on an argument: preset the outputs
+  for (int p = 0; p < Npair; ++p) {
+    const bool sel = !pair_mask || pair_mask[p];
+    if (pair_status) pair_status[p] = (int8_t)(sel ? 1 : -1);
+    if (pair_num_correspondences) pair_num_correspondences[p] = sel ? (int32_t)(pair_offset[p + 1] - pair_offset[p]) : 0;
+    if (pair_num_inliers) pair_num_inliers[p] = 0;
+    if (pair_num_iterations) pair_num_iterations[p] = 0;
+    if (pair_best_iteration) pair_best_iteration[p] = -1;
+    if (pair_confidence) pair_confidence[p] = 0.0;
+    if (homography) std::fill(homography + 9 * (size_t)p, homography + 9 * (size_t)p + 9, 0.0);
+  }
+  if (corr_inlier && total) memset(corr_inlier, 0, (size_t)total);
+  const size_t hyp_all = (size_t)num_selected * (size_t)K;
+  if (hypothesis_cost) std::fill(hypothesis_cost, hypothesis_cost + hyp_all, -1);
+  if (hypothesis_cost_real)
+    std::fill(hypothesis_cost_real, hypothesis_cost_real + hyp_all, std::numeric_limits<double>::quiet_NaN());
+  sum->num_pairs = num_selected;
+  sum->num_too_few_correspondences = num_selected - S;
+  // the attempted pairs' correspondences, pair-major, structure of arrays
+  RansacMleRun run;
+  std::vector<long long>& sel_ptr = run.sel_ptr;
+  sel_ptr.assign((size_t)S + 1, 0);
+  for (int s = 0; s < S; ++s) sel_ptr[(size_t)s + 1] = sel_ptr[s] + (pair_offset[sel_pair[s] + 1] - pair_offset[sel_pair[s]]);
+  const size_t M = (size_t)sel_ptr[S];
+  std::vector<double> xs(4 * std::max<size_t>(M, 1));
+  double *hx1 = xs.data(), *hy1 = hx1 + M, *hx2 = hy1 + M, *hy2 = hx2 + M;
+  std::vector<double> thresh((size_t)S);
+  std::vector<unsigned> stream_id((size_t)S);
+  for (int s = 0; s < S; ++s) {
+    const int p = sel_pair[s];
+    const int64_t o0 = pair_offset[p];
+    const int n = (int)(pair_offset[p + 1] - o0);
+    for (int m = 0; m < n; ++m) {
+      const size_t o = (size_t)sel_ptr[s] + m;
+      hx1[o] = feature1[2 * (o0 + m)];
+      hy1[o] = feature1[2 * (o0 + m) + 1];
+      hx2[o] = feature2[2 * (o0 + m)];
+      hy2[o] = feature2[2 * (o0 + m) + 1];
+    }
+    thresh[s] = pair_error_threshold[p];
+    stream_id[s] = pair_stream ? pair_stream[p] : (unsigned)p;
+  }
+  run.plan(L, kSample);
+  return one_shot_batch(L->device, "homographies: no such device", S, t0, &sum->seconds, [&](OneShot* s) -> int {
+    const hipStream_t stream = s->stream;
+    double *d_xs, *d_model_out;
+    TMI_HIP(s->upload(&d_xs, (const double*)xs.data(), xs.size()));
+    if (const int rc = run.upload<P>(s, L->seed, sel_pair, stream_id, thresh, samples_given ? samples : nullptr,
+                                     (size_t)Npair, hypothesis_cost != nullptr))
+      return rc;
+    if (mle)
+      if (const int rc = run.upload_mle<P>(s, hypothesis_cost_real != nullptr)) return rc;
+    RansacBatch& B = run.B;
+    for (int q = 0; q < P::kPlanes; ++q) B.plane[q] = d_xs + q * M;  // x1, y1, x2, y2
+    TMI_HIP(s->alloc(&d_model_out, (size_t)9 * S));
+    StreamTimer timer(stream);
+    TMI_HIP(timer.status);
+    TMI_HIP(timer.mark());
+    if (const int rc = mle ? run.chunks_mle<P>(s, sum) : run.chunks<P>(s, sum)) return rc;
+    hipLaunchKernelGGL(homography_final_kernel, dim3(S), dim3(64), 0, stream, B, run.d_slot_inlier, run.d_num_inliers,
+                       run.d_status, d_model_out);
+    TMI_HIP(timer.mark());
+    TMI_HIP(hipGetLastError());
+    std::vector<double> model_h((size_t)9 * S), real_h(hypothesis_cost_real ? (size_t)S * K : 0);
+    TMI_HIP(s->download(model_h.data(), d_model_out, model_h.size()));
+    TMI_HIP(s->download(real_h.data(), run.E.hypothesis_cost, real_h.size()));
+    if (const int rc = run.read_back(s, corr_inlier != nullptr, 1, sel_rank, hypothesis_cost)) return rc;
+    sum->kernel_seconds = timer.seconds();
+    sum->num_chunks = run.chunks_run;
+    const RansacItemArrays out = {pair_status,         pair_num_inliers, pair_num_iterations,
+                                  pair_best_iteration, nullptr,          pair_confidence};
+    for (int v = 0; v < S; ++v) {
+      const int p = sel_pair[v];
+      const int n = (int)(sel_ptr[(size_t)v + 1] - sel_ptr[v]);
+      const int code = run.status[v];
+      const RansacState& st = run.state[v];
+      if (code == 0) sum->num_estimated++; else sum->num_no_model++;
+      sum->total_iterations += st.num_iterations;
+      sum->total_scores += (int64_t)st.num_iterations * n;
+      run.item_results(v, p, code, out);
+      if (homography) std::copy(model_h.begin() + 9 * (size_t)v, model_h.begin() + 9 * (size_t)v + 9, homography + 9 * (size_t)p);
+      if (corr_inlier)
+        std::copy(run.slot_inlier.begin() + (size_t)sel_ptr[v], run.slot_inlier.begin() + (size_t)sel_ptr[(size_t)v + 1],
+                  corr_inlier + pair_offset[p]);
+      if (hypothesis_cost_real)
+        std::copy(real_h.begin() + (size_t)v * K, real_h.begin() + ((size_t)v + 1) * K,
+                  hypothesis_cost_real + (size_t)sel_rank[v] * K);
+    }
+    return TMI_BA_OK;
+  });
+}
+}  // extern "C"

@@ -49,6 +49,7 @@ EXPORTS = (
     "tmi_ba_track_build_options_init", "tmi_ba_build_tracks",
     "tmi_ba_two_view_ransac_options_init", "tmi_ba_estimate_uncalibrated_relative_poses",
     "tmi_ba_estimate_calibrated_relative_poses",
+    "tmi_ba_homography_ransac_options_init", "tmi_ba_estimate_homographies",
     "tmi_ba_solver_structure_checksums",
     "tmi_ba_solver_operator_info",
 )
@@ -256,6 +257,12 @@ def load():
     L.tmi_ba_estimate_calibrated_relative_poses.argtypes = [RO, C.c_int32] + [C.c_void_p] * 7 + [C.c_int32] + [
         C.c_void_p] * 12 + [C.POINTER(abi.CTwoViewRansacSummary)]
     L.tmi_ba_estimate_calibrated_relative_poses.restype = C.c_int32
+    HO = C.POINTER(abi.CHomographyRansacOptions)
+    L.tmi_ba_homography_ransac_options_init.argtypes = [HO]
+    L.tmi_ba_homography_ransac_options_init.restype = None
+    L.tmi_ba_estimate_homographies.argtypes = [HO, C.c_int32] + [C.c_void_p] * 7 + [C.c_int32] + [
+        C.c_void_p] * 10 + [C.POINTER(abi.CTwoViewRansacSummary)]
+    L.tmi_ba_estimate_homographies.restype = C.c_int32
     L.tmi_ba_solver_structure_checksums.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     L.tmi_ba_solver_structure_checksums.restype = C.c_int32
     L.tmi_ba_solver_operator_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
@@ -1266,3 +1273,62 @@ class Solver:
             self.close()
         except Exception:
             pass
+
+
+def estimate_homographies(pair_offset, feature1, feature2, pair_error_threshold, options=None, pair_mask=None,
+                          pair_stream=None, samples=None, want_hypothesis_cost: bool = False,
+                          want_hypothesis_cost_real: bool = False):
+    """Batched EstimateHomography (the homography inlier count of the two-view geometric verification: four-point
+    RANSAC with inlier-count or, options.use_mle, MLESAC scoring) over the pairs pair_mask selects (None = all).
+    pair_offset [P + 1] int64; feature1 / feature2 [N, 2] in the caller's units; pair_error_threshold [P] the squared
+    threshold in those units.  pair_stream: optional [P] uint32 sample-stream ids (None: the pair index).  samples:
+    optional [P, max_iterations, 4] int32 sample table (otherwise drawn from options.seed).
+    Returns a dict: status [P] int8, num_correspondences, num_inliers, num_iterations, best_iteration [P] int32,
+    confidence [P], homography [P, 9] (column-major, no scale imposed), corr_inlier [N] uint8, hypothesis_cost
+    [num_selected, max_iterations] int32 or None, hypothesis_cost_real [num_selected, max_iterations] float64 or None
+    (an argument error without options.use_mle), summary (CTwoViewRansacSummary).  Raises EngineError on any failure."""
+    L = load()
+    o = options if options is not None else abi.homography_ransac_options()
+    po = np.ascontiguousarray(pair_offset, dtype=np.int64)
+    if po.ndim != 1 or po.shape[0] < 1:
+        raise ValueError("pair_offset must have num_pairs + 1 entries")
+    npair = po.shape[0] - 1
+    f1 = np.ascontiguousarray(feature1, dtype=np.float64).reshape(-1, 2)
+    f2 = np.ascontiguousarray(feature2, dtype=np.float64).reshape(-1, 2)
+    total = max(int(po[-1]), 0)
+    if f1.shape[0] != total or f2.shape[0] != total:
+        raise ValueError(f"feature1 and feature2 must have pair_offset[-1] = {total} rows")
+    th = None if pair_error_threshold is None else np.ascontiguousarray(pair_error_threshold, dtype=np.float64)
+    if th is not None and th.shape != (npair,):
+        raise ValueError(f"pair_error_threshold must have num_pairs = {npair} entries")
+    pm = None if pair_mask is None else np.ascontiguousarray(pair_mask, dtype=np.uint8)
+    if pm is not None and pm.shape != (npair,):
+        raise ValueError(f"pair_mask must have num_pairs = {npair} entries")
+    ps = None if pair_stream is None else np.ascontiguousarray(pair_stream, dtype=np.uint32)
+    if ps is not None and ps.shape != (npair,):
+        raise ValueError(f"pair_stream must have num_pairs = {npair} entries")
+    k = max(int(o.max_iterations), 0)
+    sm = None
+    if samples is not None:
+        sm = np.ascontiguousarray(samples, dtype=np.int32)
+        if sm.shape != (npair, k, 4):
+            raise ValueError(f"samples must have shape (num_pairs, max_iterations, 4) = ({npair}, {k}, 4)")
+    nsel = npair if pm is None else int(np.count_nonzero(pm))
+    status = np.full(npair, -1, dtype=np.int8)
+    i32 = [np.zeros(npair, dtype=np.int32) for _ in range(4)]
+    conf = np.zeros(npair)
+    hm = np.zeros((npair, 9))
+    inl = np.zeros(total, dtype=np.uint8)
+    hyp = np.full((nsel, min(k, 1 << 20)), -1, dtype=np.int32) if want_hypothesis_cost else None
+    hyr = np.full((nsel, min(k, 1 << 20)), np.nan) if want_hypothesis_cost_real else None
+    rs = abi.CTwoViewRansacSummary()
+    ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+    st = L.tmi_ba_estimate_homographies(
+        C.byref(o), npair, po.ctypes.data, f1.ctypes.data, f2.ctypes.data, ptr(th), ptr(pm), ptr(ps), ptr(sm),
+        0 if sm is None else 1, status.ctypes.data, *[a.ctypes.data for a in i32], conf.ctypes.data, hm.ctypes.data,
+        inl.ctypes.data, ptr(hyp), ptr(hyr), C.byref(rs))
+    if st != 0:
+        raise EngineError(st, "tmi_ba_estimate_homographies")
+    return dict(status=status, num_correspondences=i32[0], num_inliers=i32[1], num_iterations=i32[2],
+                best_iteration=i32[3], confidence=conf, homography=hm, corr_inlier=inl, hypothesis_cost=hyp,
+                hypothesis_cost_real=hyr, summary=rs)
