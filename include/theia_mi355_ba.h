@@ -45,7 +45,9 @@ typedef enum tmi_ba_status {
   TMI_BA_ERR_EVALUATION_FAILED = 6,/* residual undefined at the start point  */
   TMI_BA_ERR_LINEAR_SOLVER = 7,    /* reduced system could not be solved     */
   TMI_BA_ERR_COLLECTIVE = 8,       /* the all-reduce callback reported error */
-  TMI_BA_ERR_CAPACITY = 9          /* an output array of the caller is too small (tmi_ba_match_features) */
+  TMI_BA_ERR_CAPACITY = 9,         /* an output array of the caller is too small (tmi_ba_match_features) */
+  TMI_BA_ERR_NULL_SPACE_TOO_LARGE = 10, /* tmi_ba_extract_parallel_rigid_subgraph: more than max_null_dimension */
+  TMI_BA_ERR_NOT_CONVERGED = 11    /* tmi_ba_extract_parallel_rigid_subgraph: max_iterations reached     */
 } tmi_ba_status;
 
 /* ---- enums mirrored from the reference ---------------------------------- */
@@ -1385,6 +1387,87 @@ typedef struct tmi_ba_linear_rotation_summary {
 int32_t tmi_ba_estimate_global_rotations_linear(const tmi_ba_view_pair_batch* batch,
                                                 const tmi_ba_linear_rotation_options* options, int32_t device,
                                                 double* view_rotation, tmi_ba_linear_rotation_summary* summary);
+
+/* ---- ExtractMaximallyParallelRigidSubgraph: the largest set of views whose positions the edges fix up to scale ----
+ * reference: extract_maximally_parallel_rigid_subgraph.cc:53-228 (Kennedy, Daniilidis, Naroditsky and Taylor, IROS 2012;
+ * the first step of FilterRelativeTranslation with extract_maximal_rigid_subgraph,
+ * global_reconstruction_estimator.cc:382-387). */
+typedef struct tmi_ba_rigid_subgraph_options {
+  double  relative_shift;      /* 1e-9: L + mu I is factored, mu = relative_shift x the largest diagonal entry of L  */
+  double  null_tolerance;      /* 1e-9: a Ritz value <= null_tolerance x the largest diagonal entry is null          */
+  int32_t max_null_dimension;  /* 128 (the hard cap): a larger null space is TMI_BA_ERR_NULL_SPACE_TOO_LARGE         */
+  int32_t max_iterations;      /* 100: block iterations over all block widths                                       */
+  int32_t device;              /* -1: the current device                                                            */
+} tmi_ba_rigid_subgraph_options;
+void tmi_ba_rigid_subgraph_options_init(tmi_ba_rigid_subgraph_options* options);
+
+typedef struct tmi_ba_rigid_subgraph_summary {
+  int32_t num_views;             /* views of the problem: those with an edge inside the mask                 */
+  int32_t num_pairs;             /* edges of the problem                                                     */
+  int32_t order;                 /* n = 3 num_views                                                          */
+  int32_t null_dimension;        /* k                                                                        */
+  int32_t block_width;           /* m of the last block: 8, 16, ... 128                                      */
+  int32_t iterations;            /* block iterations over all widths                                         */
+  int32_t fixed_view;            /* the fixed view of the component that won (the caller's index; -1: none)  */
+  int32_t num_kept;              /* views with keep = 1                                                      */
+  double  largest_diagonal;      /* of L: what both tolerances are relative to                               */
+  double  stop_tolerance;        /* 1e-3 x null_tolerance x largest_diagonal                                 */
+  double  max_residual;          /* the largest |L q_j - theta_j q_j|_2 of the null pairs                    */
+  double  largest_null_value;    /* the Ritz values on both sides of the cut                                 */
+  double  smallest_other_value;  /* (0 where the block holds no such pair)                                   */
+  double  seconds;
+  double  kernel_seconds;        /* device time; the sum of the four below                                   */
+  double  factor_seconds;        /* the matrix and the factorisation of L + mu I                             */
+  double  substitution_seconds;  /* forward / backward substitution on the block                             */
+  double  graph_seconds;         /* L Y, Gram-Schmidt, Rayleigh-Ritz, the reductions                         */
+  double  search_seconds;        /* the rows of M, the pair sweep, the count and the pick                    */
+} tmi_ba_rigid_subgraph_summary;
+
+/* ExtractMaximallyParallelRigidSubgraph on the device.  The batch is tmi_ba_view_pair_batch: view_rotation (the
+ * orientations), pair_view1 / pair_view2 and pair_position2 are read; pair_rotation2 is not.  view_mask [num_views]
+ * (NULL: every view): 0 = the view and its edges are not there.  The views of the problem are those with an edge
+ * between two views of the mask, in ascending index; n = 3 x their number.
+ *   1. :61-84    Per edge d = R(orientation of view1)^T position_2 (Ceres' AngleAxisToRotationMatrix) and C = [d]x; the
+ *                edge's rows of the measurement matrix A are [-C at view1, +C at view2].
+ *   2. :196-197  L = A^T A, of order n: C^T C = |d|^2 I - d d^T is added to both diagonal blocks of the edge (a view's
+ *                sum runs in the caller's edge order) and -C^T C is the block between its views.  A is never formed.
+ *   3. :196-198  N [n][k], a basis of the null space of L.  The reference: the kernel of a full-pivot LU.  HERE
+ *                (DEVIATION): an orthonormal basis by block inverse iteration with Rayleigh-Ritz through one dense
+ *                Cholesky factorisation of L + mu I.  The block has m = 8 columns (start: 2 u - 1, u from word m i + c of
+ *                the splitmix64 stream of state 0); an iteration is Y = (L + mu I)^-1 Q, modified Gram-Schmidt in
+ *                column order (two passes), T = Y^T (L Y) with L applied from the edge list, T = W diag(theta) W^T by
+ *                cyclic Jacobi (16 sweeps in round-robin order), Q = Y W.  A pair is null when
+ *                theta <= null_tolerance x largest_diagonal.  When all m pairs are null, m doubles and the iteration
+ *                starts over; past max_null_dimension (or 128) that is TMI_BA_ERR_NULL_SPACE_TOO_LARGE, so a null space
+ *                is only accepted below the block's width.  Stop when the null count is below m, unchanged, and every
+ *                null pair's residual |L q - theta q|_2 is <= stop_tolerance, for two iterations in a row.
+ *                Step 4 does not depend on the basis: parallel rows stay parallel under any invertible change of it.
+ *   4. :104-168  For every fixed view f: M = N - replicate(N_f), the row norms, the rows normalised (a row of norm 0 is
+ *                left alone), in that order.  A view i != f is a zero view when its three norms are < 1e-10.  Views i, j
+ *                are parallel when both are neither f nor zero views and 1 - |<M_i,d, M_j,d>| < 1e-5 for d = x, y, z.  The
+ *                component of f is f, every zero view, and every view that is parallel to at least one other view.
+ *   5. :207-227  The largest component wins, the smallest f among equals.
+ * keep [num_views]: 1 for the views of that component, 0 for every other view -- also (DEVIATION) for a view without an
+ * edge or outside the mask, which is no part of the system here; the reference sizes its matrix by the orientation map,
+ * gives such a view three zero columns, hence three more null directions, and keeps it as a zero view.
+ * component_size [num_views] (optional): the size of the component found with each view fixed, 0 outside the problem.
+ * null_space (optional; room for 3 num_views x max_null_dimension doubles): N, [order][null_dimension] row major over
+ * the problem's views, every column signed so that its entry of largest magnitude, the first of equals, is positive.
+ * Fixed orders, no FMA contraction, no atomics: the same bytes from call to call.
+ * Argument checks, in this order, all TMI_BA_ERR_INVALID_ARGUMENT before the device is looked for: a null batch,
+ * options, keep or summary; the batch (negative size, a missing array, more than 2^30 pairs, a view index out of range,
+ * view1 == view2, a repeated unordered pair, a non-finite orientation or position_2); relative_shift negative or not
+ * finite; null_tolerance not positive and finite; max_null_dimension outside [1, 128]; max_iterations <= 0.  Then
+ * TMI_BA_ERR_UNSUPPORTED when n exceeds the dense solver's cap (11000, the knob TMI_BA_ROTATION_MAX_ORDER), before
+ * anything of that size is allocated; TMI_BA_ERR_NO_DEVICE; a device that does not exist (INVALID_ARGUMENT).  From the
+ * device: TMI_BA_ERR_LINEAR_SOLVER (a pivot of L + mu I is not positive, or every direction is zero),
+ * TMI_BA_ERR_NOT_CONVERGED (max_iterations), TMI_BA_ERR_NULL_SPACE_TOO_LARGE.  A problem without an edge is
+ * TMI_BA_OK with keep all 0.  On every failure keep, component_size and null_space are left as they were; the summary
+ * holds what was known. */
+int32_t tmi_ba_extract_parallel_rigid_subgraph(const tmi_ba_view_pair_batch* batch, const uint8_t* view_mask,
+                                               const tmi_ba_rigid_subgraph_options* options, uint8_t* keep,
+                                               int32_t* component_size, double* null_space,
+                                               tmi_ba_rigid_subgraph_summary* summary);
 
 /* ---- LinearPositionEstimator: global positions as the smallest eigenvector of the view triplets' constraints ----
  * reference: linear_position_estimator.cc:163-470 (GlobalPositionEstimatorType::LINEAR_TRIPLET; Jiang, Cui and Tan,

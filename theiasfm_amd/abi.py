@@ -55,11 +55,13 @@ KERNEL_CLASS_NAMES = (
 ERR_INVALID_ARGUMENT = 1
 ERR_UNSUPPORTED = 5
 ERR_CAPACITY = 9
+ERR_NULL_SPACE_TOO_LARGE = 10
+ERR_NOT_CONVERGED = 11
 
 STATUS_NAMES = {
     0: "OK", 1: "INVALID_ARGUMENT", 2: "NO_DEVICE", 3: "DEVICE", 4: "OUT_OF_MEMORY",
     5: "UNSUPPORTED", 6: "EVALUATION_FAILED", 7: "LINEAR_SOLVER", 8: "COLLECTIVE",
-    9: "CAPACITY",
+    9: "CAPACITY", 10: "NULL_SPACE_TOO_LARGE", 11: "NOT_CONVERGED",
 }
 
 
@@ -637,6 +639,60 @@ def linear_rotation_options(**overrides) -> CLinearRotationOptions:
             raise AttributeError(k)
         setattr(o, k, v)
     return o
+
+
+class CRigidSubgraphOptions(C.Structure):
+    """tmi_ba_rigid_subgraph_options (the shift of the factored matrix, the null test, the caps, the device)."""
+    _fields_ = [
+        ("relative_shift", C.c_double),
+        ("null_tolerance", C.c_double),
+        ("max_null_dimension", C.c_int32),
+        ("max_iterations", C.c_int32),
+        ("device", C.c_int32),
+    ]
+
+
+RIGID_SUBGRAPH_MAX_NULL_DIMENSION = 128
+
+
+def rigid_subgraph_options(**overrides) -> CRigidSubgraphOptions:
+    """The defaults of tmi_ba_rigid_subgraph_options_init."""
+    o = CRigidSubgraphOptions()
+    o.relative_shift = 1e-9
+    o.null_tolerance = 1e-9
+    o.max_null_dimension = RIGID_SUBGRAPH_MAX_NULL_DIMENSION
+    o.max_iterations = 100
+    o.device = -1
+    for k, v in overrides.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
+class CRigidSubgraphSummary(C.Structure):
+    """tmi_ba_rigid_subgraph_summary."""
+    _fields_ = [
+        ("num_views", C.c_int32),
+        ("num_pairs", C.c_int32),
+        ("order", C.c_int32),
+        ("null_dimension", C.c_int32),
+        ("block_width", C.c_int32),
+        ("iterations", C.c_int32),
+        ("fixed_view", C.c_int32),
+        ("num_kept", C.c_int32),
+        ("largest_diagonal", C.c_double),
+        ("stop_tolerance", C.c_double),
+        ("max_residual", C.c_double),
+        ("largest_null_value", C.c_double),
+        ("smallest_other_value", C.c_double),
+        ("seconds", C.c_double),
+        ("kernel_seconds", C.c_double),
+        ("factor_seconds", C.c_double),
+        ("substitution_seconds", C.c_double),
+        ("graph_seconds", C.c_double),
+        ("search_seconds", C.c_double),
+    ]
 
 
 class CLinearRotationSummary(C.Structure):

@@ -46,6 +46,7 @@
 #include "position_nonlinear_kernels.h"
 #include "rotation_nonlinear_kernels.h"
 #include "rotation_linear_kernels.h"
+#include "rigid_subgraph_kernels.h"
 #include "localize_kernels.h"
 #include "match_kernels.h"
 #include "cascade_match_kernels.h"

@@ -1482,4 +1482,265 @@ int32_t tmi_ba_estimate_global_positions_linear(const tmi_ba_problem* P, const t
   });
 }
 
+// ---- ExtractMaximallyParallelRigidSubgraph (rigid_subgraph_kernels.h) ------------------------------
+void tmi_ba_rigid_subgraph_options_init(tmi_ba_rigid_subgraph_options* o) {
+  if (!o) return;
+  o->relative_shift = 1e-9;  // DESIGN 8.21 (and 8.17): well above the factorisation's rounding n eps |L| at the order cap
+  o->null_tolerance = 1e-9;
+  o->max_null_dimension = rsg::kMaxWidth;
+  o->max_iterations = 100;
+  o->device = -1;
+}
+
+int32_t tmi_ba_extract_parallel_rigid_subgraph(const tmi_ba_view_pair_batch* Bh, const uint8_t* view_mask,
+                                               const tmi_ba_rigid_subgraph_options* opt, uint8_t* keep,
+                                               int32_t* component_size, double* null_space,
+                                               tmi_ba_rigid_subgraph_summary* sum) {
+  if (!Bh || !opt || !keep || !sum) return bad_argument("rigid subgraph: null batch, options, keep or summary");
+  memset(sum, 0, sizeof(*sum));
+  sum->fixed_view = -1;
+  const double t0 = now_s();
+  if (const char* why = check_view_pair_batch(Bh, true, Bh->pair_position2)) return bad_argument(why);
+  if (!(opt->relative_shift >= 0.0) || !std::isfinite(opt->relative_shift))
+    return bad_argument("rigid subgraph: relative_shift is negative or not finite");
+  if (!(opt->null_tolerance > 0.0) || !std::isfinite(opt->null_tolerance))
+    return bad_argument("rigid subgraph: null_tolerance is not positive and finite");
+  if (opt->max_null_dimension < 1 || opt->max_null_dimension > rsg::kMaxWidth)
+    return bad_argument("rigid subgraph: max_null_dimension is not in [1, 128]");
+  if (opt->max_iterations <= 0) return bad_argument("rigid subgraph: max_iterations is not positive");
+  const int V = Bh->num_views;
+  // the views of the problem: those with an edge between two views of the mask, in ascending index
+  const ViewSubset P = build_view_subset(V, Bh->num_pairs, Bh->pair_view1, Bh->pair_view2, view_mask);
+  const int Vp = (int)P.view_of.size(), E = (int)P.edge_of.size();
+  if ((int64_t)3 * Vp > rotation_order_cap()) {
+    g_last_error = "rigid subgraph: 3 (views with an edge) exceeds the dense solver's cap (see the header)";
+    return TMI_BA_ERR_UNSUPPORTED;
+  }
+  const int n = 3 * Vp;  // (<= the cap)
+  std::vector<double> orient_h((size_t)3 * Vp), pos_h((size_t)3 * E);
+  for (int p = 0; p < Vp; ++p)
+    std::copy(Bh->view_rotation + (size_t)3 * P.view_of[p], Bh->view_rotation + (size_t)3 * P.view_of[p] + 3,
+              orient_h.begin() + (size_t)3 * p);
+  for (int e = 0; e < E; ++e)
+    std::copy(Bh->pair_position2 + (size_t)3 * P.edge_of[e], Bh->pair_position2 + (size_t)3 * P.edge_of[e] + 3,
+              pos_h.begin() + (size_t)3 * e);
+  const EdgeRows rows = build_edge_rows(Vp, E, P.v1.data(), P.v2.data(), Vp);
+  std::vector<uint8_t> keep_h;
+  std::vector<int> size_h;
+  std::vector<double> null_h;
+  const int rc = one_shot_batch(opt->device, "rigid subgraph: no such device", E, t0, &sum->seconds, [&](OneShot* s) -> int {
+    int rc;
+    hipStream_t st = s->stream;
+    const int nb = (n + 255) / 256;
+    const int W = rsg::kMaxWidth;
+    double *d_orient, *d_pos, *d_S, *d_D, *d_Q, *d_Y, *d_Z, *d_W, *d_mgs[2], *d_gram, *d_res, *d_small;
+    TMI_HIP(s->upload(&d_orient, orient_h.data(), orient_h.size()));
+    TMI_HIP(s->upload(&d_pos, pos_h.data(), pos_h.size()));
+    TMI_HIP(s->alloc(&d_S, (size_t)6 * E));
+    PoseGraphDevice graph;  // no view is held
+    if ((rc = graph.upload(s, Vp, Vp, rows, E, P.v1.data(), P.v2.data(), d_S))) return rc;
+    const PoseGraph& G = graph.G;
+    TMI_HIP(s->alloc(&d_D, (size_t)6 * Vp));
+    for (double** p : {&d_Q, &d_Y, &d_Z, &d_W}) TMI_HIP(s->alloc(p, (size_t)n * W));
+    for (double*& p : d_mgs) TMI_HIP(s->alloc(&p, (size_t)nb * W));
+    TMI_HIP(s->alloc(&d_gram, (size_t)nb * W * W));
+    TMI_HIP(s->alloc(&d_res, (size_t)nb * W));
+    TMI_HIP(s->alloc(&d_small, (size_t)2 * W * W + 2 * W + 2));  // (the last words: the largest diagonal entry)
+    double* d_scale = d_small + (size_t)2 * W * W + 2 * W;
+    DenseSpd shifted;  // L + mu I, overwritten by its factor; kChunk right-hand sides at a time
+    if ((rc = shifted.alloc(s, n, rsg::kChunk, nullptr))) return rc;
+    Pinned<double> pinned;
+    TMI_HIP(pinned.alloc((size_t)2 * W + 2));
+    double* h_small = pinned.get();
+    int* h_flag = reinterpret_cast<int*>(h_small + 2 * W + 1);
+    static bool attr_set = false;
+    if (!attr_set) {
+      TMI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&rsg_ritz_kernel),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)rsg::ritz_lds_bytes(W)));
+      attr_set = true;
+    }
+    const dim3 block(256), rows_grid(nb);
+    sum->num_views = Vp;
+    sum->num_pairs = E;
+    sum->order = n;
+    ClassSeconds T(st);
+    TMI_HIP(T.status());
+
+    // ---- the matrix and its factor ----
+    TMI_HIP(T.begin(T.kGraph));
+    hipLaunchKernelGGL(rsg_edge_kernel, dim3((E + 255) / 256), block, 0, st, E, d_orient, G.pair_view1, d_pos, d_S);
+    hipLaunchKernelGGL(rsg_diag_kernel, dim3((6 * Vp + 255) / 256), block, 0, st, G, d_D);
+    hipLaunchKernelGGL(rsg_scale_kernel, dim3(1), block, 0, st, Vp, d_D, d_scale);
+    hipLaunchKernelGGL(rsg_assemble_kernel, dim3(Vp), block, 0, st, G, n, d_D, d_scale, opt->relative_shift, shifted.A);
+    TMI_HIP(T.begin(T.kFactor));
+    shifted.factor(st);
+    TMI_HIP(T.end());
+    {
+      ReadBack rb(st);
+      rb.add(h_small, d_scale, 1);
+      rb.add(h_flag, shifted.flag, 1);
+      TMI_HIP(rb.finish());
+    }
+    T.collect();
+    const double scale = h_small[0];
+    sum->largest_diagonal = scale;
+    if (*h_flag || !(scale > 0.0)) {  // a pivot of L + mu I that is not positive, or no direction at all
+      T.write(sum);
+      s->error = "rigid subgraph: L + mu I could not be factored (every position_2 zero, or relative_shift too small)";
+      return TMI_BA_ERR_LINEAR_SOLVER;
+    }
+    const double null_threshold = opt->null_tolerance * scale;
+    const double stop_tolerance = 1e-3 * null_threshold;
+    sum->stop_tolerance = stop_tolerance;
+
+    // ---- the null space: block inverse iteration with Rayleigh-Ritz, the block doubled while all of it is null ----
+    int m = rsg::kStartWidth, k = -1, iter = 0;
+    for (;;) {
+      const int me = std::min(m, n);  // the columns from me on are zero and stay zero: the block cannot outgrow R^n
+      const size_t block_words = (size_t)n * m;
+      const int chunks = m / rsg::kChunk;
+      TMI_HIP(hipMemsetAsync(d_Q, 0, block_words * sizeof(double), st));
+      hipLaunchKernelGGL(rsg_start_kernel, dim3((n * me + 255) / 256), block, 0, st, n, me, d_Q);
+      int previous = -1, stable = 0, launches = 0;
+      bool all_null = false;
+      k = -1;
+      while (k < 0 && !all_null) {
+        if (iter >= opt->max_iterations) {
+          sum->block_width = m;
+          sum->iterations = iter;
+          T.write(sum);
+          s->error = "rigid subgraph: the null space did not settle within max_iterations";
+          return TMI_BA_ERR_NOT_CONVERGED;
+        }
+        ++iter;
+        TMI_HIP(T.begin(T.kSubstitution));
+        TMI_HIP(hipMemcpyAsync(d_W, d_Q, block_words * sizeof(double), hipMemcpyDeviceToDevice, st));
+        for (int c = 0; c < chunks; ++c)
+          shifted.substitute<rsg::kChunk>(st, d_W + (size_t)c * n * rsg::kChunk, d_Y + (size_t)c * n * rsg::kChunk);
+        TMI_HIP(T.begin(T.kGraph));
+        for (int pass = 0; pass < 2; ++pass)
+          for (int j = 0; j <= m; ++j, ++launches)
+            hipLaunchKernelGGL(rsg_mgs_kernel, rows_grid, block, 0, st, n, m, j, d_Y, d_mgs[(launches + 1) & 1],
+                               d_mgs[launches & 1]);
+        hipLaunchKernelGGL(rsg_apply_kernel, dim3((Vp * m + 255) / 256), block, 0, st, G, m, d_Y, d_Z);
+        hipLaunchKernelGGL(rsg_gram_kernel, dim3(nb, m), dim3(128), 0, st, n, m, d_Y, d_Z, d_gram);
+        hipLaunchKernelGGL(rsg_ritz_kernel, dim3(1), block, rsg::ritz_lds_bytes(m), st, d_gram, nb, m, me, d_small);
+        hipLaunchKernelGGL(rsg_rotate_kernel, dim3(nb, chunks), block, 0, st, n, m, d_small, d_Y, d_Z, d_Q, d_res);
+        hipLaunchKernelGGL(rsg_residual_kernel, dim3(1), dim3(128), 0, st, d_res, nb, m, d_small);
+        TMI_HIP(T.end());
+        {
+          ReadBack rb(st);  // theta [m], residual^2 [m]
+          rb.add(h_small, d_small + (size_t)2 * m * m, (size_t)2 * m);
+          TMI_HIP(rb.finish());
+        }
+        T.collect();
+        int count = 0;
+        while (count < me && h_small[count] <= null_threshold) ++count;
+        double worst = 0.0;
+        for (int j = 0; j < count; ++j) worst = std::max(worst, std::sqrt(h_small[m + j]));
+        if (count == me && me < n) {
+          all_null = true;
+        } else {
+          stable = (count == previous && worst <= stop_tolerance) ? stable + 1 : (worst <= stop_tolerance ? 1 : 0);
+          previous = count;
+          if (stable >= 2) {
+            k = count;
+            sum->max_residual = worst;
+            sum->largest_null_value = count > 0 ? h_small[count - 1] : 0.0;
+            sum->smallest_other_value = count < me ? h_small[count] : 0.0;
+          }
+        }
+      }
+      sum->block_width = m;
+      sum->iterations = iter;
+      if (k >= 0) break;
+      if (m >= opt->max_null_dimension || 2 * m > rsg::kMaxWidth) {
+        k = rsg::kMaxWidth + 1;  // at least m dimensions, and no wider block is allowed
+        break;
+      }
+      m *= 2;
+    }
+    if (k > opt->max_null_dimension) {
+      T.write(sum);
+      s->error = "rigid subgraph: the null space has more dimensions than max_null_dimension";
+      return TMI_BA_ERR_NULL_SPACE_TOO_LARGE;
+    }
+    sum->null_dimension = k;
+
+    // ---- the search ----
+    double *d_N, *d_Mt, *d_norms;
+    unsigned char* d_flag;
+    int *d_size, *d_pick;
+    const int kk = std::max(k, 1);  // (k = 0: no null direction, every row of M is zero and every view a zero view)
+    const size_t per_fixed = (size_t)3 * kk * Vp;
+    const int batch = (int)std::max<size_t>(1, std::min<size_t>((size_t)Vp, ((size_t)256 << 20) / (per_fixed * sizeof(double))));
+    TMI_HIP(s->alloc_filled(&d_N, (size_t)n * kk, 0));
+    TMI_HIP(s->alloc(&d_Mt, per_fixed * batch));
+    TMI_HIP(s->alloc(&d_norms, (size_t)3 * Vp * batch));
+    TMI_HIP(s->alloc(&d_flag, (size_t)Vp * Vp));
+    TMI_HIP(s->alloc(&d_size, (size_t)Vp));
+    TMI_HIP(s->alloc(&d_pick, 2));
+    StreamTimer search(st);
+    TMI_HIP(search.status);
+    TMI_HIP(search.mark());
+    if (k > 0) hipLaunchKernelGGL(rsg_null_kernel, dim3((n * k + 255) / 256), block, 0, st, n, k, d_Q, d_N);
+    for (int f0 = 0; f0 < Vp; f0 += batch) {
+      const int F = std::min(batch, Vp - f0);
+      const long long threads = (long long)F * 3 * Vp;
+      hipLaunchKernelGGL(rsg_rows_kernel, dim3((unsigned)((threads + 255) / 256)), block, 0, st, Vp, kk, f0, F, d_N, d_Mt,
+                         d_norms);
+      hipLaunchKernelGGL(rsg_component_kernel, dim3((Vp + 255) / 256, F), block, rsg::component_lds_bytes(kk), st, Vp, kk,
+                         f0, d_Mt, d_norms, d_flag);
+    }
+    hipLaunchKernelGGL(rsg_count_kernel, dim3(Vp), block, 0, st, Vp, d_flag, d_size);
+    hipLaunchKernelGGL(rsg_pick_kernel, dim3(1), block, 0, st, Vp, d_size, d_pick);
+    TMI_HIP(search.mark());
+    int pick_h[2] = {0, 0};
+    size_h.resize((size_t)Vp);
+    if (null_space) null_h.resize((size_t)n * k);
+    {
+      ReadBack rb(st);
+      rb.add(pick_h, d_pick, 2);
+      rb.add(size_h.data(), d_size, size_h.size());
+      rb.add(null_h.data(), d_N, null_h.size());
+      TMI_HIP(rb.finish());
+    }
+    keep_h.resize((size_t)Vp);
+    {
+      ReadBack rb(st);  // the flags of the picked view
+      rb.add(keep_h.data(), (const uint8_t*)d_flag + (size_t)pick_h[0] * Vp, keep_h.size());
+      TMI_HIP(rb.finish());
+    }
+    T.write(sum);
+    sum->search_seconds = search.seconds();
+    sum->kernel_seconds += sum->search_seconds;
+    sum->fixed_view = P.view_of[pick_h[0]];
+    sum->num_kept = pick_h[1];
+    return TMI_BA_OK;
+  });
+  if (rc != TMI_BA_OK) return rc;
+  // the results, only now: a failure above leaves the caller's arrays as they were
+  std::fill(keep, keep + V, (uint8_t)0);
+  if (component_size) std::fill(component_size, component_size + V, 0);
+  for (size_t p = 0; p < keep_h.size(); ++p) {
+    keep[P.view_of[p]] = keep_h[p];
+    if (component_size) component_size[P.view_of[p]] = size_h[p];
+  }
+  if (null_space) {
+    // the sign rule: the entry of largest magnitude of each column, the first of equals, is positive
+    const int k = sum->null_dimension;
+    for (int c = 0; c < k; ++c) {
+      double big = 0.0;
+      bool negative = false;
+      for (int i = 0; i < n; ++i)
+        if (std::fabs(null_h[(size_t)i * k + c]) > big) {
+          big = std::fabs(null_h[(size_t)i * k + c]);
+          negative = null_h[(size_t)i * k + c] < 0.0;
+        }
+      for (int i = 0; i < n; ++i) null_space[(size_t)i * k + c] = negative ? -null_h[(size_t)i * k + c] : null_h[(size_t)i * k + c];
+    }
+  }
+  return TMI_BA_OK;
+}
+
 }  // extern "C"

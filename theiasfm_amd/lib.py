@@ -42,6 +42,7 @@ EXPORTS = (
     "tmi_ba_nonlinear_position_options_init", "tmi_ba_estimate_global_positions_nonlinear",
     "tmi_ba_nonlinear_rotation_options_init", "tmi_ba_estimate_global_rotations_nonlinear",
     "tmi_ba_linear_rotation_options_init", "tmi_ba_estimate_global_rotations_linear",
+    "tmi_ba_rigid_subgraph_options_init", "tmi_ba_extract_parallel_rigid_subgraph",
     "tmi_ba_linear_position_options_init", "tmi_ba_estimate_global_positions_linear",
     "tmi_ba_localization_options_init", "tmi_ba_localize_views",
     "tmi_ba_match_options_init", "tmi_ba_match_features",
@@ -216,6 +217,12 @@ def load():
     L.tmi_ba_estimate_global_rotations_linear.argtypes = [
         PB, LR, C.c_int32, C.c_void_p, C.POINTER(abi.CLinearRotationSummary)]
     L.tmi_ba_estimate_global_rotations_linear.restype = C.c_int32
+    RS = C.POINTER(abi.CRigidSubgraphOptions)
+    L.tmi_ba_rigid_subgraph_options_init.argtypes = [RS]
+    L.tmi_ba_rigid_subgraph_options_init.restype = None
+    L.tmi_ba_extract_parallel_rigid_subgraph.argtypes = [
+        PB, C.c_void_p, RS, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(abi.CRigidSubgraphSummary)]
+    L.tmi_ba_extract_parallel_rigid_subgraph.restype = C.c_int32
     LP = C.POINTER(abi.CLinearPositionOptions)
     L.tmi_ba_linear_position_options_init.argtypes = [LP]
     L.tmi_ba_linear_position_options_init.restype = None
@@ -791,6 +798,40 @@ def estimate_global_rotations_linear(batch: abi.ViewPairBatch, options=None, dev
     if st != 0:
         raise EngineError(st, "tmi_ba_estimate_global_rotations_linear")
     return dict(rotations=rot, summary=rs)
+
+
+def extract_parallel_rigid_subgraph(batch: abi.ViewPairBatch, options=None, view_mask=None,
+                                    want_null_space: bool = False, outputs=None):
+    """ExtractMaximallyParallelRigidSubgraph on the device.  batch: view_rotation (the orientations), the pairs and
+    pair_position2 are read.  options: a CRigidSubgraphOptions (default: tmi_ba_rigid_subgraph_options_init's).
+    view_mask [V]: 0 = the view and its edges are not there.  outputs: a dict with keep [V] uint8, component_size [V]
+    int32 and (with want_null_space) null_space [3 V * max_null_dimension] float64 to write into (default: fresh
+    zeros) -- a failure leaves them as they were.
+    Returns a dict: keep [V] uint8, component_size [V] int32, null_space [n, k] (None unless asked for) and summary
+    (CRigidSubgraphSummary).  Raises EngineError on any failure; the error carries .summary."""
+    L = load()
+    o = options if options is not None else abi.rigid_subgraph_options()
+    V = batch.num_views
+    if batch.view_rotation is None:
+        raise ValueError("the batch needs view_rotation: the orientations")
+    mask, mask_p = _mask_pointer(view_mask, V) if view_mask is not None else (None, None)
+    out = outputs if outputs is not None else {}
+    keep = out.get("keep", np.zeros(V, dtype=np.uint8))
+    size = out.get("component_size", np.zeros(V, dtype=np.int32))
+    null = out.get("null_space", np.zeros(3 * V * max(int(o.max_null_dimension), 1))) if want_null_space else None
+    if keep.dtype != np.uint8 or keep.shape != (V,) or size.dtype != np.int32 or size.shape != (V,):
+        raise ValueError("keep must be [V] uint8 and component_size [V] int32")
+    cb = batch.as_c()
+    rs = abi.CRigidSubgraphSummary()
+    st = L.tmi_ba_extract_parallel_rigid_subgraph(C.byref(cb), mask_p, C.byref(o), keep.ctypes.data, size.ctypes.data,
+                                                  null.ctypes.data if null is not None else None, C.byref(rs))
+    if st != 0:
+        err = EngineError(st, "tmi_ba_extract_parallel_rigid_subgraph")
+        err.summary = rs
+        raise err
+    n, k = int(rs.order), int(rs.null_dimension)
+    return dict(keep=keep, component_size=size, null_space=None if null is None else null[:n * k].reshape(n, k).copy(),
+                summary=rs)
 
 
 def localize_views(problem: abi.Problem, view_error_threshold, options=None, ba_options=None, view_mask=None,
