@@ -2225,6 +2225,88 @@ int32_t tmi_ba_estimate_homographies(
     int32_t* pair_best_iteration, double* pair_confidence, double* homography, uint8_t* corr_inlier,
     int32_t* hypothesis_cost, double* hypothesis_cost_real, tmi_ba_two_view_ransac_summary* summary);
 
+/* ---- batched EstimateAbsolutePoseWithKnownOrientation: two-point position RANSAC for many views -----------
+ * reference: EstimateAbsolutePoseWithKnownOrientation with RansacType::RANSAC
+ * (estimators/estimate_absolute_pose_with_known_orientation.cc:54-150; what the assume_known_orientation branch of
+ * LocalizeViewToReconstruction, localize_view_to_reconstruction.cc:160-185, calls -- that branch itself stays refused)
+ * over PositionFromTwoRays (pose/position_from_two_rays.cc:56-83) and SampleConsensusEstimator::Estimate
+ * (solvers/sample_consensus_estimator.h:246-344) with InlierSupport (use_mle == 0) or MLEQualityMeasurement
+ * (use_mle != 0, solvers/mle_quality_measurement.h:58-71).  Not provided: PROSAC, LMED and exhaustive sampling,
+ * use_Tdd_test.
+ * A one-shot call shaped like tmi_ba_estimate_homographies, whose options, summary (an item is a view here),
+ * item_offset / item_mask / item_stream, samples / samples_given, integer outputs, corr_inlier and the two
+ * hypothesis-cost arrays it shares.  feature [2 n] are NORMALISED image coordinates (principal point removed, divided
+ * by the focal length), NOT yet rotated; world_point [3 n]; item_orientation [3 per item] the view's angle-axis
+ * (world to camera); item_error_threshold is RansacParameters::error_thresh, squared normalised units.  The estimator
+ * has no min_num_inliers.  Per selected item, in this order:
+ *   1. n < 2                                                                                       -> status 1.
+ *   2. RotateCorrespondences (:54-73), one device thread per correspondence: R = ceres::AngleAxisToRotationMatrix of
+ *      the item's orientation (the engine's restatement, first-order branch at theta^2 <= DBL_EPSILON; it calls sin and
+ *      cos, the only such functions in the call), ray_i = (R(0,i) u + R(1,i) v) + R(2,i), the rotated feature
+ *      (ray_0 / ray_2, ray_1 / ray_2).  rotated_feature [2 n] (optional): what this step left, 0 for items not attempted;
+ *      every later step is a function of it that uses + - * / and sqrt only, never contracted into FMA.
+ *   3. The sample of iteration i: step 2 of the homography call with 4 replaced by 2 (samples[2 (max_iterations p + i)
+ *      + k]; word c = 2 (q 2^32 + i) + k; two swaps).  THE SAMPLE SEQUENCES ARE NOT THE REFERENCE'S.
+ *   4. PositionFromTwoRays on the two (rotated feature (u_k, v_k), point (X_k, Y_k, Z_k)): the least-squares solution
+ *      of the 4x3 system with rows [1 0 -u_k], [0 1 -v_k] and right side b = (X_1 - u_1 Z_1, Y_1 - v_1 Z_1,
+ *      X_2 - u_2 Z_2, Y_2 - v_2 Z_2) through its normal equations in closed form: du = u_1 - u_2, dv = v_1 - v_2,
+ *      q = du du + dv dv, c_z = -((du (b_0 - b_2) + dv (b_1 - b_3)) / q), c_x = ((b_0 + u_1 c_z) + (b_2 + u_2 c_z)) / 2,
+ *      c_y = ((b_1 + v_1 c_z) + (b_3 + v_2 c_z)) / 2.  RANK RULE: the pivots of the normal equations are 2, 2 and q / 2;
+ *      with n22 = (u_1^2 + v_1^2) + (u_2^2 + v_2^2) their largest diagonal entry is max(2, n22); rank 3 iff
+ *      q / 2 > (3 DBL_EPSILON)^2 max(2, n22), else NO MODEL.  (The reference: ColPivHouseholderQR::rank() != 3 at
+ *      3 DBL_EPSILON on R's diagonal, the square roots of such pivots; the two rules differ by a bounded factor at a
+ *      boundary only two rotated features equal to 1e-15 reach.)
+ *   5. The residual (:106-113): d = X - c, r = (d_0 / d_2 - u)^2 + (d_1 / d_2 - v)^2.  There is NO cheirality test, as in
+ *      the reference.  Inlier iff r < threshold; a NaN r is an outlier.
+ *   6. The cost, the replay and the chunking: steps 5 and 6 of the homography call with a sample size of 2 (the fixed
+ *      64-lane shape of the MLE sum included; inlier_ratio < 2 / n skips the update of the bound).
+ *   7. Final: the inlier mask of the best model, num_inliers, confidence = 1 - (1 - (num_inliers / n)^2)^num_iterations
+ *      (host); no model in any iteration -> status 2; otherwise status 0 and position [3].
+ * The argument errors and their order relative to the device check are those of the homography call, with 2 in place
+ * of 4; item_orientation is a required array whenever num_items > 0. */
+int32_t tmi_ba_estimate_positions_known_orientation(
+    const tmi_ba_homography_ransac_options* options, int32_t num_items, const int64_t* item_offset,
+    const double* feature, const double* world_point, const double* item_orientation,
+    const double* item_error_threshold, const uint8_t* item_mask, const uint32_t* item_stream, const int32_t* samples,
+    int32_t samples_given, int8_t* item_status, int32_t* item_num_correspondences, int32_t* item_num_inliers,
+    int32_t* item_num_iterations, int32_t* item_best_iteration, double* item_confidence, double* position,
+    uint8_t* corr_inlier, int32_t* hypothesis_cost, double* hypothesis_cost_real, double* rotated_feature,
+    tmi_ba_two_view_ransac_summary* summary);
+
+/* ---- batched EstimateRelativePoseWithKnownOrientation: two-point baseline RANSAC for many view pairs ------
+ * reference: EstimateRelativePoseWithKnownOrientation with RansacType::RANSAC
+ * (estimators/estimate_relative_pose_with_known_orientation.cc:19-82) over RelativePoseFromTwoPointsWithKnownRotation
+ * (pose/relative_pose_from_two_points_with_known_rotation.cc:51-88), either scoring.  Not provided: PROSAC, LMED and
+ * exhaustive sampling, use_Tdd_test.
+ * The call above with two features per correspondence and no world point.  The reference takes correspondences the
+ * caller has already rotated, rf = hnormalize(R^t K^-1 [u v 1]^t) (relative_pose_from_two_points_with_known_rotation.h:
+ * 43-47); here feature1 / feature2 [2 n] are normalised and NOT rotated, and step 2 rotates feature1 by
+ * pair_orientation1 and feature2 by pair_orientation2 ([3 per pair] each, the two views' angle-axes; all zero: the
+ * features pass through bit for bit).  rotated_feature1 / rotated_feature2 [2 n] (optional) as above.  What differs:
+ *   1. n < 2                                                                                       -> status 1.
+ *   4. The rows e_k = (-y1 + y2, -x2 + x1, y1 x2 - x1 y2) of the two sampled correspondences (:65-74).  RANK RULE: two
+ *      steps of elimination with FULL pivoting under the sibling calls' rules (the pivot is the entry of largest
+ *      magnitude, strict >, ties to the lowest (row, column)); rank 2 iff both pivots are > 0 and
+ *      min(p0, p1) > 2 DBL_EPSILON max(p0, p1) -- FullPivLU's rule for a 2x3 matrix -- else NO MODEL
+ *      (dimensionOfKernel() != 1).  The null vector is c = e_0 x e_1, each entry a b - c d as written, divided by
+ *      sqrt((c_0^2 + c_1^2) + c_2^2); a norm that is 0 or not finite gives no model.  SIGN RULE: the sign of e_0 x e_1
+ *      as computed, rows in sample order, NO flip; the reference's sign is whatever FullPivLU::kernel() leaves, and
+ *      only the direction up to sign is the estimate (position [3] is +-(c2 - c1) / |c2 - c1| in the rotated frame).
+ *   5. The residual (:52-58): SquaredSampsonDistance (pose/util.cc:56-68) of (feature1, feature2) under
+ *      F = CrossProductMatrix(-t) = [0 t2 -t1; -t2 0 t0; t1 -t0 0], the zero entries left out of the sums:
+ *      l = (t2 y1 - t1, t0 - t2 x1, t1 x1 - t0 y1), num = (x2 l0 + y2 l1) + l2, g = (t1 - y2 t2, x2 t2 - t0),
+ *      r = num^2 / (((g0^2 + g1^2) + l0^2) + l1^2).  The reference's Error has NO behind-camera rule and never returns
+ *      DBL_MAX, so neither does this.
+ *   7. confidence with the exponent 2; position [3] has unit length. */
+int32_t tmi_ba_estimate_relative_positions_known_orientation(
+    const tmi_ba_homography_ransac_options* options, int32_t num_pairs, const int64_t* pair_offset,
+    const double* feature1, const double* feature2, const double* pair_orientation1, const double* pair_orientation2,
+    const double* pair_error_threshold, const uint8_t* pair_mask, const uint32_t* pair_stream, const int32_t* samples,
+    int32_t samples_given, int8_t* pair_status, int32_t* pair_num_correspondences, int32_t* pair_num_inliers,
+    int32_t* pair_num_iterations, int32_t* pair_best_iteration, double* pair_confidence, double* position,
+    uint8_t* corr_inlier, int32_t* hypothesis_cost, double* hypothesis_cost_real, double* rotated_feature1,
+    double* rotated_feature2, tmi_ba_two_view_ransac_summary* summary);
+
 /* Test hook: FNV-1a checksums of the static structure arrays resident in HBM -- built in HBM by
  * sort / scan kernels (one rank, no shared intrinsics blocks; TMI_BA_HOST_SETUP=1 disables) or on
  * host threads otherwise.  out[0] = 1 when the device built it; the other slots are documented at

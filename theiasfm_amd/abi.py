@@ -880,6 +880,13 @@ def homography_ransac_options(**overrides) -> CHomographyRansacOptions:
     return o
 
 
+def known_orientation_ransac_options(**overrides) -> CHomographyRansacOptions:
+    """The options of tmi_ba_estimate_positions_known_orientation and
+    tmi_ba_estimate_relative_positions_known_orientation: tmi_ba_homography_ransac_options as it is."""
+    return homography_ransac_options(**overrides)
+
+
+KNOWN_ORIENTATION_SAMPLE = 2  # correspondences per sample of the two known-orientation calls
 CALIBRATED_SLOTS = 10  # models per sample of tmi_ba_estimate_calibrated_relative_poses (the stride of its hypothesis_cost)
 
 

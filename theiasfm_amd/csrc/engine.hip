@@ -56,6 +56,7 @@
 #include "two_view_ransac_kernels.h"
 #include "two_view_calibrated_kernels.h"
 #include "homography_kernels.h"
+#include "known_orientation_kernels.h"
 #include "select_kernels.h"
 #include "structure_gpu.h"
 #include <hipcub/hipcub.hpp>

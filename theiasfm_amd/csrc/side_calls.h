@@ -3173,3 +3173,220 @@ int32_t tmi_ba_estimate_homographies(
   });
 }
 }  // extern "C"
+
+// ---- the two known-orientation position RANSACs: a sample of two, either scoring (known_orientation_kernels.h) ----
+namespace {
+// What one of the two calls hands to the shared body below.  feature[k] [2n] are rotated on the device by
+// orientation[k] [3 per item] into planes (2k, 2k + 1); extra [extra_width n] (the world points) fills the planes after
+// them unrotated.  rotated[k] (optional): the caller's [2n] for the features the RANSAC saw.
+struct KnownOrientationInput {
+  int num_features;              // 1 (absolute) or 2 (relative)
+  const double* feature[2];
+  const double* orientation[2];
+  double* rotated[2];
+  const double* extra;
+  int extra_width;               // 3 or 0
+};
+
+// The argument checks, the presets and the packing are those of tmi_ba_estimate_homographies with a sample of two; the
+// rotation launches come before the chunk loop and are part of kernel_seconds.
+template <class P, class Final>
+int32_t known_orientation_call(const char* what, const tmi_ba_homography_ransac_options* L, int32_t num_items,
+                               const int64_t* item_offset, const KnownOrientationInput& in,
+                               const double* item_error_threshold, const uint8_t* item_mask,
+                               const uint32_t* item_stream, const int32_t* samples, int32_t samples_given,
+                               int8_t* item_status, int32_t* item_num_correspondences, int32_t* item_num_inliers,
+                               int32_t* item_num_iterations, int32_t* item_best_iteration, double* item_confidence,
+                               double* model, uint8_t* corr_inlier, int32_t* hypothesis_cost,
+                               double* hypothesis_cost_real, tmi_ba_two_view_ransac_summary* sum, Final final_kernel) {
+  constexpr int kSample = P::kSample;
+  auto bad = [&](const char* why) { return bad_argument((std::string(what) + ": " + why).c_str()); };
+  if (!L || !sum) return bad("null options or summary");
+  memset(sum, 0, sizeof(*sum));
+  const double t0 = now_s();
+  // argument errors before the device is looked for
+  const int N = num_items;
+  if (N < 0) return bad("negative size");
+  if (!item_offset) return bad("missing array");
+  if (item_offset[0] != 0) return bad("item_offset must start at 0");
+  for (int p = 0; p < N; ++p)
+    if (item_offset[p + 1] < item_offset[p]) return bad("item_offset decreases");
+  const int64_t total = item_offset[N];
+  if (total >= (int64_t)0x7fffffffLL) return bad("more than 2^31 correspondences");
+  for (int k = 0; k < in.num_features; ++k)
+    if ((total && !in.feature[k]) || (N && !in.orientation[k])) return bad("missing array");
+  if (total && in.extra_width && !in.extra) return bad("missing array");
+  if (const char* why = ransac_options_error(L, samples, samples_given)) return bad(why);
+  const bool mle = L->use_mle != 0;
+  if (hypothesis_cost_real && !mle) return bad("hypothesis_cost_real without use_mle");
+  const int K = L->max_iterations;
+  std::vector<int> selected, sel_item, sel_rank;  // sel_item: the attempted ones, the device's slots
+  for (int p = 0; p < N; ++p) {
+    if (item_mask && !item_mask[p]) continue;
+    const int64_t n = item_offset[p + 1] - item_offset[p];
+    if (n >= kSample) {
+      if (!item_error_threshold) return bad("missing error threshold");
+      if (!(item_error_threshold[p] > 0.0)) return bad("error threshold must be positive");
+      if (samples_given)
+        for (int64_t i = 0; i < K; ++i) {
+          const int32_t* t = samples + kSample * ((int64_t)K * p + i);
+          for (int a = 0; a < kSample; ++a) {
+            bool wrong = t[a] < 0 || t[a] >= n;
+            for (int b = 0; b < a; ++b) wrong = wrong || t[a] == t[b];
+            if (wrong) return bad("a sample with a repeated or out-of-range index");
+          }
+        }
+      sel_item.push_back(p);
+      sel_rank.push_back((int)selected.size());
+    }
+    selected.push_back(p);
+  }
+  const int num_selected = (int)selected.size(), S = (int)sel_item.size();
+  // nothing below fails on an argument: preset the outputs
+  for (int p = 0; p < N; ++p) {
+    const bool sel = !item_mask || item_mask[p];
+    if (item_status) item_status[p] = (int8_t)(sel ? 1 : -1);
+    if (item_num_correspondences) item_num_correspondences[p] = sel ? (int32_t)(item_offset[p + 1] - item_offset[p]) : 0;
+    if (item_num_inliers) item_num_inliers[p] = 0;
+    if (item_num_iterations) item_num_iterations[p] = 0;
+    if (item_best_iteration) item_best_iteration[p] = -1;
+    if (item_confidence) item_confidence[p] = 0.0;
+    if (model) std::fill(model + 3 * (size_t)p, model + 3 * (size_t)p + 3, 0.0);
+  }
+  if (corr_inlier && total) memset(corr_inlier, 0, (size_t)total);
+  for (int k = 0; k < in.num_features; ++k)
+    if (in.rotated[k] && total) std::fill(in.rotated[k], in.rotated[k] + 2 * (size_t)total, 0.0);
+  const size_t hyp_all = (size_t)num_selected * (size_t)K;
+  if (hypothesis_cost) std::fill(hypothesis_cost, hypothesis_cost + hyp_all, -1);
+  if (hypothesis_cost_real)
+    std::fill(hypothesis_cost_real, hypothesis_cost_real + hyp_all, std::numeric_limits<double>::quiet_NaN());
+  sum->num_pairs = num_selected;
+  sum->num_too_few_correspondences = num_selected - S;
+  // the attempted items' correspondences, item-major, structure of arrays
+  RansacMleRun run;
+  std::vector<long long>& sel_ptr = run.sel_ptr;
+  sel_ptr.assign((size_t)S + 1, 0);
+  for (int s = 0; s < S; ++s) sel_ptr[(size_t)s + 1] = sel_ptr[s] + (item_offset[sel_item[s] + 1] - item_offset[sel_item[s]]);
+  const size_t M = (size_t)sel_ptr[S];
+  std::vector<double> xs((size_t)P::kPlanes * std::max<size_t>(M, 1));
+  std::vector<double> thresh((size_t)S), orient((size_t)in.num_features * 3 * std::max(S, 1));
+  std::vector<unsigned> stream_id((size_t)S);
+  for (int s = 0; s < S; ++s) {
+    const int p = sel_item[s];
+    const int64_t o0 = item_offset[p];
+    const int n = (int)(item_offset[p + 1] - o0);
+    for (int m = 0; m < n; ++m) {
+      const size_t o = (size_t)sel_ptr[s] + m;
+      for (int k = 0; k < in.num_features; ++k) {
+        xs[(size_t)(2 * k) * M + o] = in.feature[k][2 * (o0 + m)];
+        xs[(size_t)(2 * k + 1) * M + o] = in.feature[k][2 * (o0 + m) + 1];
+      }
+      for (int q = 0; q < in.extra_width; ++q)
+        xs[(size_t)(2 * in.num_features + q) * M + o] = in.extra[(size_t)in.extra_width * (o0 + m) + q];
+    }
+    for (int k = 0; k < in.num_features; ++k)
+      for (int q = 0; q < 3; ++q) orient[(size_t)3 * ((size_t)k * S + s) + q] = in.orientation[k][3 * (size_t)p + q];
+    thresh[s] = item_error_threshold[p];
+    stream_id[s] = item_stream ? item_stream[p] : (unsigned)p;
+  }
+  run.plan(L, kSample);
+  const std::string no_device = std::string(what) + ": no such device";
+  return one_shot_batch(L->device, no_device.c_str(), S, t0, &sum->seconds, [&](OneShot* s) -> int {
+    const hipStream_t stream = s->stream;
+    double *d_xs, *d_orient, *d_model_out;
+    TMI_HIP(s->upload(&d_xs, (const double*)xs.data(), xs.size()));
+    TMI_HIP(s->upload(&d_orient, (const double*)orient.data(), orient.size()));
+    if (const int rc = run.upload<P>(s, L->seed, sel_item, stream_id, thresh, samples_given ? samples : nullptr,
+                                     (size_t)N, hypothesis_cost != nullptr))
+      return rc;
+    if (mle)
+      if (const int rc = run.upload_mle<P>(s, hypothesis_cost_real != nullptr)) return rc;
+    RansacBatch& B = run.B;
+    for (int q = 0; q < P::kPlanes; ++q) B.plane[q] = d_xs + q * M;
+    TMI_HIP(s->alloc(&d_model_out, (size_t)3 * S));
+    StreamTimer timer(stream);
+    TMI_HIP(timer.status);
+    TMI_HIP(timer.mark());
+    for (int k = 0; k < in.num_features && M > 0; ++k)
+      hipLaunchKernelGGL(rotate_features_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, stream, S, B.sel_ptr,
+                         d_orient + (size_t)3 * k * S, B.plane[2 * k], B.plane[2 * k + 1]);
+    if (const int rc = mle ? run.chunks_mle<P>(s, sum) : run.chunks<P>(s, sum)) return rc;
+    hipLaunchKernelGGL(final_kernel, dim3(S), dim3(64), 0, stream, B, run.d_slot_inlier, run.d_num_inliers, run.d_status,
+                       d_model_out);
+    TMI_HIP(timer.mark());
+    TMI_HIP(hipGetLastError());
+    const bool want_rotated = in.rotated[0] || (in.num_features > 1 && in.rotated[1]);
+    std::vector<double> model_h((size_t)3 * S), real_h(hypothesis_cost_real ? (size_t)S * K : 0),
+        rot_h(want_rotated ? (size_t)2 * in.num_features * M : 0);
+    TMI_HIP(s->download(model_h.data(), d_model_out, model_h.size()));
+    TMI_HIP(s->download(real_h.data(), run.E.hypothesis_cost, real_h.size()));
+    TMI_HIP(s->download(rot_h.data(), d_xs, rot_h.size()));
+    if (const int rc = run.read_back(s, corr_inlier != nullptr, 1, sel_rank, hypothesis_cost)) return rc;
+    sum->kernel_seconds = timer.seconds();
+    sum->num_chunks = run.chunks_run;
+    const RansacItemArrays out = {item_status,         item_num_inliers, item_num_iterations,
+                                  item_best_iteration, nullptr,          item_confidence};
+    for (int v = 0; v < S; ++v) {
+      const int p = sel_item[v];
+      const int n = (int)(sel_ptr[(size_t)v + 1] - sel_ptr[v]);
+      const int code = run.status[v];
+      const RansacState& st = run.state[v];
+      if (code == 0) sum->num_estimated++; else sum->num_no_model++;
+      sum->total_iterations += st.num_iterations;
+      sum->total_scores += (int64_t)st.num_iterations * n;
+      run.item_results(v, p, code, out);
+      if (model) std::copy(model_h.begin() + 3 * (size_t)v, model_h.begin() + 3 * (size_t)v + 3, model + 3 * (size_t)p);
+      if (corr_inlier)
+        std::copy(run.slot_inlier.begin() + (size_t)sel_ptr[v], run.slot_inlier.begin() + (size_t)sel_ptr[(size_t)v + 1],
+                  corr_inlier + item_offset[p]);
+      if (hypothesis_cost_real)
+        std::copy(real_h.begin() + (size_t)v * K, real_h.begin() + ((size_t)v + 1) * K,
+                  hypothesis_cost_real + (size_t)sel_rank[v] * K);
+      for (int k = 0; k < in.num_features; ++k)
+        if (in.rotated[k])
+          for (int m = 0; m < n; ++m) {
+            const size_t o = (size_t)sel_ptr[v] + m;
+            in.rotated[k][2 * (item_offset[p] + m)] = rot_h[(size_t)(2 * k) * M + o];
+            in.rotated[k][2 * (item_offset[p] + m) + 1] = rot_h[(size_t)(2 * k + 1) * M + o];
+          }
+    }
+    return TMI_BA_OK;
+  });
+}
+}  // namespace
+
+extern "C" {
+int32_t tmi_ba_estimate_positions_known_orientation(
+    const tmi_ba_homography_ransac_options* L, int32_t num_items, const int64_t* item_offset, const double* feature,
+    const double* world_point, const double* item_orientation, const double* item_error_threshold,
+    const uint8_t* item_mask, const uint32_t* item_stream, const int32_t* samples, int32_t samples_given,
+    int8_t* item_status, int32_t* item_num_correspondences, int32_t* item_num_inliers, int32_t* item_num_iterations,
+    int32_t* item_best_iteration, double* item_confidence, double* position, uint8_t* corr_inlier,
+    int32_t* hypothesis_cost, double* hypothesis_cost_real, double* rotated_feature,
+    tmi_ba_two_view_ransac_summary* sum) {
+  const KnownOrientationInput in = {1, {feature, nullptr}, {item_orientation, nullptr}, {rotated_feature, nullptr},
+                                    world_point, 3};
+  return known_orientation_call<KnownOrientationAbsoluteProblem>(
+      "positions with known orientation", L, num_items, item_offset, in, item_error_threshold, item_mask, item_stream,
+      samples, samples_given, item_status, item_num_correspondences, item_num_inliers, item_num_iterations,
+      item_best_iteration, item_confidence, position, corr_inlier, hypothesis_cost, hypothesis_cost_real, sum,
+      known_orientation_absolute_final_kernel);
+}
+
+int32_t tmi_ba_estimate_relative_positions_known_orientation(
+    const tmi_ba_homography_ransac_options* L, int32_t num_pairs, const int64_t* pair_offset, const double* feature1,
+    const double* feature2, const double* pair_orientation1, const double* pair_orientation2,
+    const double* pair_error_threshold, const uint8_t* pair_mask, const uint32_t* pair_stream, const int32_t* samples,
+    int32_t samples_given, int8_t* pair_status, int32_t* pair_num_correspondences, int32_t* pair_num_inliers,
+    int32_t* pair_num_iterations, int32_t* pair_best_iteration, double* pair_confidence, double* position,
+    uint8_t* corr_inlier, int32_t* hypothesis_cost, double* hypothesis_cost_real, double* rotated_feature1,
+    double* rotated_feature2, tmi_ba_two_view_ransac_summary* sum) {
+  const KnownOrientationInput in = {2, {feature1, feature2}, {pair_orientation1, pair_orientation2},
+                                    {rotated_feature1, rotated_feature2}, nullptr, 0};
+  return known_orientation_call<KnownOrientationRelativeProblem>(
+      "relative positions with known orientation", L, num_pairs, pair_offset, in, pair_error_threshold, pair_mask,
+      pair_stream, samples, samples_given, pair_status, pair_num_correspondences, pair_num_inliers, pair_num_iterations,
+      pair_best_iteration, pair_confidence, position, corr_inlier, hypothesis_cost, hypothesis_cost_real, sum,
+      known_orientation_relative_final_kernel);
+}
+}  // extern "C"

@@ -51,6 +51,7 @@ EXPORTS = (
     "tmi_ba_two_view_ransac_options_init", "tmi_ba_estimate_uncalibrated_relative_poses",
     "tmi_ba_estimate_calibrated_relative_poses",
     "tmi_ba_homography_ransac_options_init", "tmi_ba_estimate_homographies",
+    "tmi_ba_estimate_positions_known_orientation", "tmi_ba_estimate_relative_positions_known_orientation",
     "tmi_ba_solver_structure_checksums",
     "tmi_ba_solver_operator_info",
 )
@@ -270,6 +271,12 @@ def load():
     L.tmi_ba_estimate_homographies.argtypes = [HO, C.c_int32] + [C.c_void_p] * 7 + [C.c_int32] + [
         C.c_void_p] * 10 + [C.POINTER(abi.CTwoViewRansacSummary)]
     L.tmi_ba_estimate_homographies.restype = C.c_int32
+    L.tmi_ba_estimate_positions_known_orientation.argtypes = [HO, C.c_int32] + [C.c_void_p] * 8 + [C.c_int32] + [
+        C.c_void_p] * 11 + [C.POINTER(abi.CTwoViewRansacSummary)]
+    L.tmi_ba_estimate_positions_known_orientation.restype = C.c_int32
+    L.tmi_ba_estimate_relative_positions_known_orientation.argtypes = [HO, C.c_int32] + [C.c_void_p] * 9 + [
+        C.c_int32] + [C.c_void_p] * 12 + [C.POINTER(abi.CTwoViewRansacSummary)]
+    L.tmi_ba_estimate_relative_positions_known_orientation.restype = C.c_int32
     L.tmi_ba_solver_structure_checksums.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     L.tmi_ba_solver_structure_checksums.restype = C.c_int32
     L.tmi_ba_solver_operator_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
@@ -1373,3 +1380,97 @@ def estimate_homographies(pair_offset, feature1, feature2, pair_error_threshold,
     return dict(status=status, num_correspondences=i32[0], num_inliers=i32[1], num_iterations=i32[2],
                 best_iteration=i32[3], confidence=conf, homography=hm, corr_inlier=inl, hypothesis_cost=hyp,
                 hypothesis_cost_real=hyr, summary=rs)
+
+
+def _known_orientation(symbol, item_offset, features, extra, orientations, item_error_threshold, options, item_mask,
+                       item_stream, samples, want_hypothesis_cost, want_hypothesis_cost_real):
+    """The shared body of the two known-orientation calls: `features` the one or two [N, 2] arrays, `extra` the
+    [N, 3] world points or None, `orientations` one [P, 3] array per feature array."""
+    L = load()
+    o = options if options is not None else abi.homography_ransac_options()
+    po = np.ascontiguousarray(item_offset, dtype=np.int64)
+    if po.ndim != 1 or po.shape[0] < 1:
+        raise ValueError("item_offset must have num_items + 1 entries")
+    nitem = po.shape[0] - 1
+    total = max(int(po[-1]), 0)
+    fs = [np.ascontiguousarray(f, dtype=np.float64).reshape(-1, 2) for f in features]
+    if any(f.shape[0] != total for f in fs):
+        raise ValueError(f"every feature array must have item_offset[-1] = {total} rows")
+    xs = []
+    if extra is not None:
+        xs = [np.ascontiguousarray(extra, dtype=np.float64).reshape(-1, 3)]
+        if xs[0].shape[0] != total:
+            raise ValueError(f"world_point must have item_offset[-1] = {total} rows")
+    os_ = [np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 3) for a in orientations]
+    if any(a.shape[0] != nitem for a in os_):
+        raise ValueError(f"every orientation array must have num_items = {nitem} rows")
+    th = None if item_error_threshold is None else np.ascontiguousarray(item_error_threshold, dtype=np.float64)
+    if th is not None and th.shape != (nitem,):
+        raise ValueError(f"the error thresholds must have num_items = {nitem} entries")
+    pm = None if item_mask is None else np.ascontiguousarray(item_mask, dtype=np.uint8)
+    if pm is not None and pm.shape != (nitem,):
+        raise ValueError(f"the mask must have num_items = {nitem} entries")
+    ps = None if item_stream is None else np.ascontiguousarray(item_stream, dtype=np.uint32)
+    if ps is not None and ps.shape != (nitem,):
+        raise ValueError(f"the streams must have num_items = {nitem} entries")
+    k = max(int(o.max_iterations), 0)
+    sm = None
+    if samples is not None:
+        sm = np.ascontiguousarray(samples, dtype=np.int32)
+        if sm.shape != (nitem, k, 2):
+            raise ValueError(f"samples must have shape (num_items, max_iterations, 2) = ({nitem}, {k}, 2)")
+    nsel = nitem if pm is None else int(np.count_nonzero(pm))
+    status = np.full(nitem, -1, dtype=np.int8)
+    i32 = [np.zeros(nitem, dtype=np.int32) for _ in range(4)]
+    conf = np.zeros(nitem)
+    pos = np.zeros((nitem, 3))
+    inl = np.zeros(total, dtype=np.uint8)
+    hyp = np.full((nsel, min(k, 1 << 20)), -1, dtype=np.int32) if want_hypothesis_cost else None
+    hyr = np.full((nsel, min(k, 1 << 20)), np.nan) if want_hypothesis_cost_real else None
+    rot = [np.zeros((total, 2)) for _ in fs]
+    rs = abi.CTwoViewRansacSummary()
+    ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+    st = getattr(L, symbol)(
+        C.byref(o), nitem, po.ctypes.data, *[a.ctypes.data for a in fs + xs + os_], ptr(th), ptr(pm), ptr(ps), ptr(sm),
+        0 if sm is None else 1, status.ctypes.data, *[a.ctypes.data for a in i32], conf.ctypes.data, pos.ctypes.data,
+        inl.ctypes.data, ptr(hyp), ptr(hyr), *[a.ctypes.data for a in rot], C.byref(rs))
+    if st != 0:
+        raise EngineError(st, symbol)
+    return dict(status=status, num_correspondences=i32[0], num_inliers=i32[1], num_iterations=i32[2],
+                best_iteration=i32[3], confidence=conf, position=pos, corr_inlier=inl, hypothesis_cost=hyp,
+                hypothesis_cost_real=hyr, rotated=rot, summary=rs)
+
+
+def estimate_positions_known_orientation(item_offset, feature, world_point, item_orientation, item_error_threshold,
+                                         options=None, item_mask=None, item_stream=None, samples=None,
+                                         want_hypothesis_cost: bool = False, want_hypothesis_cost_real: bool = False):
+    """Batched EstimateAbsolutePoseWithKnownOrientation (two-point position RANSAC with inlier-count or,
+    options.use_mle, MLESAC scoring) over the views item_mask selects (None = all).  item_offset [P + 1] int64; feature
+    [N, 2] normalised and NOT rotated; world_point [N, 3]; item_orientation [P, 3] angle-axis; item_error_threshold [P]
+    squared, normalised units.  item_stream, samples ([P, max_iterations, 2]) as in estimate_homographies.
+    Returns a dict: status [P] int8, num_correspondences, num_inliers, num_iterations, best_iteration [P] int32,
+    confidence [P], position [P, 3], corr_inlier [N] uint8, hypothesis_cost / hypothesis_cost_real
+    [num_selected, max_iterations] or None, rotated_feature [N, 2] (what the RANSAC saw; 0 for views not attempted),
+    summary (CTwoViewRansacSummary).  Raises EngineError on any failure."""
+    out = _known_orientation("tmi_ba_estimate_positions_known_orientation", item_offset, [feature], world_point,
+                             [item_orientation], item_error_threshold, options, item_mask, item_stream, samples,
+                             want_hypothesis_cost, want_hypothesis_cost_real)
+    out["rotated_feature"] = out.pop("rotated")[0]
+    return out
+
+
+def estimate_relative_positions_known_orientation(pair_offset, feature1, feature2, pair_orientation1,
+                                                  pair_orientation2, pair_error_threshold, options=None,
+                                                  pair_mask=None, pair_stream=None, samples=None,
+                                                  want_hypothesis_cost: bool = False,
+                                                  want_hypothesis_cost_real: bool = False):
+    """Batched EstimateRelativePoseWithKnownOrientation (two-point baseline-direction RANSAC, either scoring) over the
+    pairs pair_mask selects.  feature1 / feature2 [N, 2] normalised and NOT rotated; pair_orientation1 /
+    pair_orientation2 [P, 3] the two views' angle-axes (zeros: the features are taken as already rotated).  The other
+    arguments and the returned dict are those of estimate_positions_known_orientation, with position [P, 3] the unit
+    direction (its sign is not part of the estimate) and rotated_feature1 / rotated_feature2 [N, 2]."""
+    out = _known_orientation("tmi_ba_estimate_relative_positions_known_orientation", pair_offset,
+                             [feature1, feature2], None, [pair_orientation1, pair_orientation2], pair_error_threshold,
+                             options, pair_mask, pair_stream, samples, want_hypothesis_cost, want_hypothesis_cost_real)
+    out["rotated_feature1"], out["rotated_feature2"] = out.pop("rotated")
+    return out
