@@ -1824,6 +1824,110 @@ int32_t tmi_ba_match_features_cascade(const tmi_ba_cascade_match_options* option
                                       int32_t* match_feature2, float* match_distance, uint32_t* image_hash,
                                       uint16_t* image_bucket_ids, tmi_ba_cascade_match_summary* summary);
 
+/* ---- batched GuidedEpipolarMatcher: more matches along the epipolar lines of a known two-view geometry ----
+ * reference: GuidedEpipolarMatcher (matching/guided_epipolar_matcher.{h,cc}; line numbers below are the .cc's), the
+ * step of TwoViewMatchGeometricVerification::VerifyMatches (two_view_match_geometric_verification.cc:157-167) between
+ * the pose estimate and the triangulation.  A one-shot call without a tmi_ba_problem for many image pairs, shaped like
+ * tmi_ba_match_features: image m owns the rows image_begin[m] .. image_begin[m + 1] - 1 of `descriptors` [rows x dim,
+ * fp32, row-major] and of `keypoints` [rows x 2, fp64: x, y]; every image that a selected pair names goes to the
+ * device once however many pairs name it (summary->rows_uploaded).  Pair p is (pair_image1[p], pair_image2[p]) with
+ * fundamental_matrix [9 p .. 9 p + 8], row-major, which maps a point of image 1 to its line in image 2, and the input
+ * matches pair_match_begin[p] .. pair_match_begin[p + 1] - 1 of match_feature1 / match_feature2 (row indices local to
+ * the two images).  pair_mask (optional): a pair with pair_mask[p] == 0 is not computed, its status is -1 and it adds
+ * nothing.  pair_stream (optional): the random stream q of pair p (default q = p), so that a pair computed alone
+ * repeats what it gave in a batch.  Per selected pair, N1 and N2 rows, c = guided_matching_max_distance_pixels:
+ *   a. Matched sets (:102-142).  A feature of either image that occurs in an input match is matched.  The box
+ *      (top_left, bottom_right) is the minimum and the maximum of x and of y over the UNMATCHED features of image 2.
+ *      No unmatched feature in image 2, or none in image 1: status 1, nothing added, no groups.
+ *   b. Epipolar lines (:214-236), per unmatched feature (x, y) of image 1, in fp64 with + - * / sqrt only, every
+ *      operation rounded on its own (no FMA): l_r = (F[3r] x + F[3r + 1] y) + F[3r + 2] for r = 0, 1, 2; n =
+ *      sqrt(l_0 l_0 + l_1 l_1); l_r = l_r / n.  The intersections of FindEpipolarLineIntersection (:320-356) in its
+ *      order: left (tl.x, -(l_2 + l_0 tl.x) / l_1), top (-(l_2 + l_1 tl.y) / l_0, tl.y), right (br.x, -(l_2 + l_0
+ *      br.x) / l_1), bottom (-(l_2 + l_1 br.y) / l_0, br.y); each is kept when its free coordinate v satisfies
+ *      v >= low && v <= high of the box with IEEE comparisons (a NaN or an infinity fails, which is how the reference
+ *      treats vertical and horizontal lines).  Exactly two kept intersections are the endpoints, otherwise the
+ *      feature is skipped.  Each of the four coordinates is truncated toward zero.  DEVIATION: the reference casts to
+ *      uint16_t, undefined outside its range; here a truncated coordinate outside [0, 65535] skips the feature.
+ *      code = x1 << 48 | y1 << 32 | x2 << 16 | y2 (:60-71).
+ *   c. Groups (:239-273).  The features that were not skipped, sorted by (code, feature index) ascending (the order
+ *      std::sort gives the reference's pairs).  In that order: the decoded endpoints e0 = (x1, y1), e1 = (x2, y2) as
+ *      doubles; a new group (endpoints E0 = e0, E1 = e1, no features) starts at the first feature and whenever
+ *      (E0.x - e0.x)^2 + (E0.y - e0.y)^2 > c c, E0 the current group's running first endpoint; then the feature joins
+ *      the current group, w = 1.0 / (number of its features), and E0 = (1.0 - w) E0 + w e0, E1 = (1.0 - w) E1 + w e1
+ *      per coordinate.  Groups are numbered from 0 in this order.  The scan is sequential by definition.
+ *   d. Four grids (:108-113, :438-480) of cell size 2 c with offsets (0, 0), (c, 0), (0, c), (c, c).  The cell centre
+ *      of a point in the grid of offset (ox, oy): (int)(((floor((x - ox) / (2.0 c)) * 2.0) * c + c) + ox), the same in
+ *      y with oy, truncated toward zero.  A cell holds the UNMATCHED features of image 2 with that centre.  (Centres
+ *      are assumed to fit an int32, as in the reference.)
+ *   e. Candidates of a group (:284-318).  num_steps = (int)(sqrt(dx dx + dy dy) / c) with (dx, dy) = E1 - E0; delta =
+ *      (E0 - E1) / (double)num_steps; s = E1; num_steps times: s = s + delta, then of the four centres of s the
+ *      closest one, squared distance (cx - s.x)^2 + (cy - s.y)^2, strict < in grid order 0..3 (:416-436), and that
+ *      cell's features join the candidate SET.  The set has no order (a bitmap over the N2 rows here).  With fewer
+ *      than min_num_candidates members, draws t = |set| .. min_num_candidates - 1 insert a row of image 2, matched
+ *      ones included, duplicates collapsing (:308-314).  DEVIATION: the reference draws from its own generator; here
+ *      draw t is min((int)(u N2), N2 - 1), u = ((word >> 11) + 0.5) 2^-53, word number 64 (q 2^32 + g) + t of the
+ *      splitmix64 stream of `seed` (the stream of the RANSAC calls), g the group's number.
+ *   f. Search (:358-414, :172-184).  For every feature of the group the best and the second-best candidate under
+ *      steps 1 and 2 of tmi_ba_match_features: fp32, t = a[k] - b[k], acc = acc + t * t for ascending k, no FMA, the
+ *      total order (distance, then lower row index), a NaN distance never wins.  DEVIATION: the search is exact, where
+ *      the reference asks an approximate FLANN kd-tree.  Fewer than two candidates: no match (DEVIATION: the reference
+ *      reads past the end).  Ratio test as typed at :150, :177: (double)d0 < (double)d1 * (lowes_ratio * lowes_ratio),
+ *      the square formed in double.  A passing feature adds (feature1, best row, d0).  The added matches of a pair
+ *      come out in ascending (group, position in the group); nothing makes the image-2 side unique, as in the
+ *      reference.
+ * THE RESULT DOES NOT DEPEND ON HOW THE DEVICE IS DRIVEN: steps a to f leave nothing open.
+ * Outputs: pair_status [num_pairs] (0 ok, 1 nothing to match, -1 masked out), pair_num_groups [num_pairs],
+ * pair_added_begin [num_pairs + 1] (int64) and added_feature1 / added_feature2 / added_distance [added_capacity], the
+ * distance the fp32 squared distance d0.  With added_capacity smaller than the total the call returns
+ * TMI_BA_ERR_CAPACITY with the needed total in summary->num_added; the per-pair arrays and the test outputs are filled
+ * all the same and nothing is written to the three added arrays.
+ * Test outputs, each may be null; row(p) = the sum of N1 over the pairs before p, masked ones included:
+ * feature_group [row(num_pairs)]: entry row(p) + i is the group number of feature i of image 1 in pair p, or -1;
+ * group_endpoints [4 row(num_pairs)] and group_num_candidates [row(num_pairs)]: group g of pair p is entry row(p) + g
+ * (E0.x, E0.y, E1.x, E1.y after the scan; the size of the candidate set after the fill); other entries are 0.
+ * summary: num_pairs the selected pairs, num_groups, num_candidates (the set sizes summed over the groups),
+ * distance_evaluations (set size times features, summed over the groups), rows_uploaded.
+ * Limits: an image has at most 131072 rows (the candidate bitmap of a group is 16 KiB of LDS).  TMI_BA_ERR_UNSUPPORTED,
+ * also before the device is looked for: 0 < c < 1/16 (c >= 1/16 bounds a walk at 2^21 steps); the rows of image 1
+ * summed over the selected pairs, or four times those of image 2, reaching 2^31.
+ * TMI_BA_ERR_INVALID_ARGUMENT, before the device (options->device) is looked for: a null options or summary, a missing
+ * array, a negative count, dim < 1, image_begin that does not start at 0 or decreases, pair_match_begin likewise, an
+ * image or match index out of range, c <= 0 or not finite, lowes_ratio not finite, min_num_candidates outside
+ * [0, 64], an image of more than 131072 rows. */
+typedef struct tmi_ba_guided_match_options {
+  double   guided_matching_max_distance_pixels;  /* 2.0                                   */
+  double   lowes_ratio;                          /* 0.8                                   */
+  int32_t  min_num_candidates;                   /* 50 (kMinNumMatchesFound)              */
+  int32_t  device;                               /* -1 = the current device               */
+  uint64_t seed;                                 /* 0                                     */
+  int32_t  reserved[2];                          /* 0                                     */
+} tmi_ba_guided_match_options;
+void tmi_ba_guided_match_options_init(tmi_ba_guided_match_options* options);
+
+typedef struct tmi_ba_guided_match_summary {
+  int64_t num_added;             /* over all pairs (the needed added_capacity)                                   */
+  int64_t num_groups;
+  int64_t num_candidates;        /* candidate set sizes after the fill, summed over the groups                   */
+  int64_t distance_evaluations;  /* set size times group features, summed over the groups                        */
+  int64_t rows_uploaded;         /* descriptor rows sent to the device: each named image once                    */
+  int32_t num_pairs;             /* selected by the mask                                                          */
+  int32_t num_pairs_ok;          /* status 0                                                                      */
+  double  seconds;
+  double  kernel_seconds;        /* first to last launch of the call                                              */
+} tmi_ba_guided_match_summary;
+
+int32_t tmi_ba_guided_epipolar_match(const tmi_ba_guided_match_options* options, int32_t num_images,
+                                     const int64_t* image_begin, const float* descriptors, int32_t dim,
+                                     const double* keypoints, int32_t num_pairs, const int32_t* pair_image1,
+                                     const int32_t* pair_image2, const double* fundamental_matrix,
+                                     const int64_t* pair_match_begin, const int32_t* match_feature1,
+                                     const int32_t* match_feature2, const uint8_t* pair_mask,
+                                     const uint32_t* pair_stream, int64_t added_capacity, int8_t* pair_status,
+                                     int32_t* pair_num_groups, int64_t* pair_added_begin, int32_t* added_feature1,
+                                     int32_t* added_feature2, float* added_distance, int32_t* feature_group,
+                                     double* group_endpoints, int32_t* group_num_candidates,
+                                     tmi_ba_guided_match_summary* summary);
+
 /* ---- TrackBuilder: the tracks of a reconstruction from the verified matches of all view pairs, by union-find ----
  * reference: TrackBuilder (track_builder.cc:53-151) on ConnectedComponents<uint64_t> (connected_components.h:87-162),
  * driven from reconstruction_builder.cc:173,358,432-439 with the defaults of reconstruction_builder.h:81-85

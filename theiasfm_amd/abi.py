@@ -949,6 +949,48 @@ class CMatchSummary(C.Structure):
     ]
 
 
+class CGuidedMatchOptions(C.Structure):
+    """tmi_ba_guided_match_options (GuidedEpipolarMatcher::Options, guided_epipolar_matcher.h:64-75)."""
+    _fields_ = [
+        ("guided_matching_max_distance_pixels", C.c_double),
+        ("lowes_ratio", C.c_double),
+        ("min_num_candidates", C.c_int32),
+        ("device", C.c_int32),
+        ("seed", C.c_uint64),
+        ("reserved", C.c_int32 * 2),
+    ]
+
+
+def guided_match_options(**overrides) -> CGuidedMatchOptions:
+    """The defaults of tmi_ba_guided_match_options_init."""
+    o = CGuidedMatchOptions()
+    o.guided_matching_max_distance_pixels = 2.0
+    o.lowes_ratio = 0.8
+    o.min_num_candidates = 50
+    o.device = -1
+    o.seed = 0
+    for k, v in overrides.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
+class CGuidedMatchSummary(C.Structure):
+    """tmi_ba_guided_match_summary."""
+    _fields_ = [
+        ("num_added", C.c_int64),
+        ("num_groups", C.c_int64),
+        ("num_candidates", C.c_int64),
+        ("distance_evaluations", C.c_int64),
+        ("rows_uploaded", C.c_int64),
+        ("num_pairs", C.c_int32),
+        ("num_pairs_ok", C.c_int32),
+        ("seconds", C.c_double),
+        ("kernel_seconds", C.c_double),
+    ]
+
+
 class CCascadeMatchOptions(C.Structure):
     """tmi_ba_cascade_match_options: the fields and defaults of tmi_ba_match_options."""
     _fields_ = list(CMatchOptions._fields_)

@@ -50,6 +50,7 @@
 #include "localize_kernels.h"
 #include "match_kernels.h"
 #include "cascade_match_kernels.h"
+#include "guided_match_kernels.h"
 #include "track_build_kernels.h"
 #include "view_graph_kernels.h"
 #include "position_linear_kernels.h"

@@ -3390,3 +3390,316 @@ int32_t tmi_ba_estimate_relative_positions_known_orientation(
       known_orientation_relative_final_kernel);
 }
 }  // extern "C"
+
+// ---- batched GuidedEpipolarMatcher (guided_match_kernels.h) ------------------------------------
+#define TMI_GM(call)                  \
+  do {                                \
+    const int rc_ = (call);           \
+    if (rc_ != TMI_BA_OK) return rc_; \
+  } while (0)
+extern "C" {
+void tmi_ba_guided_match_options_init(tmi_ba_guided_match_options* o) {
+  if (!o) return;
+  o->guided_matching_max_distance_pixels = 2.0;  // guided_epipolar_matcher.h:64-75
+  o->lowes_ratio = 0.8;
+  o->min_num_candidates = 50;  // kMinNumMatchesFound, guided_epipolar_matcher.cc:279
+  o->device = -1;
+  o->seed = 0;
+  o->reserved[0] = o->reserved[1] = 0;
+}
+
+int32_t tmi_ba_guided_epipolar_match(const tmi_ba_guided_match_options* O, int32_t num_images,
+                                     const int64_t* image_begin, const float* descriptors, int32_t dim,
+                                     const double* keypoints, int32_t num_pairs, const int32_t* pair_image1,
+                                     const int32_t* pair_image2, const double* fundamental_matrix,
+                                     const int64_t* pair_match_begin, const int32_t* match_feature1,
+                                     const int32_t* match_feature2, const uint8_t* pair_mask,
+                                     const uint32_t* pair_stream, int64_t added_capacity, int8_t* pair_status,
+                                     int32_t* pair_num_groups, int64_t* pair_added_begin, int32_t* added_feature1,
+                                     int32_t* added_feature2, float* added_distance, int32_t* feature_group,
+                                     double* group_endpoints, int32_t* group_num_candidates,
+                                     tmi_ba_guided_match_summary* sum) {
+  auto bad = [&](const char* why) { return bad_argument((std::string("guided epipolar match: ") + why).c_str()); };
+  if (!O || !sum) return bad("null options or summary");
+  memset(sum, 0, sizeof(*sum));
+  const double t0 = now_s();
+  // argument errors before the device is looked for
+  if (num_images < 0 || num_pairs < 0 || added_capacity < 0) return bad("negative count");
+  if (dim < 1) return bad("dim < 1");
+  if (!image_begin) return bad("missing image_begin");
+  const double c = O->guided_matching_max_distance_pixels;
+  if (!(c > 0.0) || !std::isfinite(c)) return bad("guided_matching_max_distance_pixels is not in (0, inf)");
+  if (c < 0.0625) {  // a supported-range limit, not an argument error: it bounds a walk at 2^21 steps
+    g_last_error = "guided epipolar match: guided_matching_max_distance_pixels below 1/16 is not supported";
+    return TMI_BA_ERR_UNSUPPORTED;
+  }
+  if (!std::isfinite(O->lowes_ratio)) return bad("lowes_ratio is not finite");
+  if (O->min_num_candidates < 0 || O->min_num_candidates > kGmMaxCandidatesFill)
+    return bad("min_num_candidates is not in [0, 64]");
+  if (image_begin[0] != 0) return bad("image_begin must start at 0");
+  for (int m = 0; m < num_images; ++m) {
+    if (image_begin[m + 1] < image_begin[m]) return bad("image_begin decreases");
+    if (image_begin[m + 1] - image_begin[m] > kGmMaxImageRows) return bad("an image of more than 131072 rows");
+  }
+  const int64_t total_rows = image_begin[num_images];
+  if (total_rows && (!descriptors || !keypoints)) return bad("missing descriptors or keypoints");
+  if (num_pairs && (!pair_image1 || !pair_image2 || !fundamental_matrix || !pair_status || !pair_num_groups))
+    return bad("missing pair array");
+  if (!pair_match_begin || !pair_added_begin) return bad("missing pair_match_begin or pair_added_begin");
+  if (pair_match_begin[0] != 0) return bad("pair_match_begin must start at 0");
+  for (int p = 0; p < num_pairs; ++p)
+    if (pair_match_begin[p + 1] < pair_match_begin[p]) return bad("pair_match_begin decreases");
+  const int64_t num_matches = pair_match_begin[num_pairs];
+  if (num_matches && (!match_feature1 || !match_feature2)) return bad("missing match array");
+  if (added_capacity && (!added_feature1 || !added_feature2 || !added_distance)) return bad("missing added array");
+  for (int p = 0; p < num_pairs; ++p) {
+    const int i1 = pair_image1[p], i2 = pair_image2[p];
+    if (i1 < 0 || i1 >= num_images || i2 < 0 || i2 >= num_images) return bad("image index out of range");
+    const int64_t n1 = image_begin[i1 + 1] - image_begin[i1], n2 = image_begin[i2 + 1] - image_begin[i2];
+    for (int64_t m = pair_match_begin[p]; m < pair_match_begin[p + 1]; ++m)
+      if (match_feature1[m] < 0 || match_feature1[m] >= n1 || match_feature2[m] < 0 || match_feature2[m] >= n2)
+        return bad("match index out of range");
+  }
+  // the selected pairs, their ROW1 / ROW2 and the rows of the test outputs; every named image gets its device rows
+  std::vector<GmPair> pairs;
+  std::vector<int> sel_pair;
+  std::vector<int64_t> out_row((size_t)num_pairs + 1, 0);
+  std::vector<long long> device_row((size_t)num_images, -1);
+  std::vector<int> match_row1, match_row2;
+  long long rows1 = 0, rows2 = 0, uploaded = 0;
+  int max_n2 = 0;
+  for (int p = 0; p < num_pairs; ++p) {
+    const int i1 = pair_image1[p], i2 = pair_image2[p];
+    const int n1 = (int)(image_begin[i1 + 1] - image_begin[i1]), n2 = (int)(image_begin[i2 + 1] - image_begin[i2]);
+    out_row[(size_t)p + 1] = out_row[p] + n1;
+    pair_status[p] = -1;
+    pair_num_groups[p] = 0;
+    pair_added_begin[p] = 0;
+    if (pair_mask && !pair_mask[p]) continue;
+    for (int im : {i1, i2})
+      if (device_row[im] < 0) {
+        device_row[im] = uploaded;
+        uploaded += image_begin[im + 1] - image_begin[im];
+      }
+    GmPair P;
+    memset(&P, 0, sizeof(P));
+    P.row1 = device_row[i1];
+    P.row2 = device_row[i2];
+    P.n1 = n1;
+    P.n2 = n2;
+    P.base1 = (int)rows1;
+    P.base2 = (int)rows2;
+    P.stream = pair_stream ? pair_stream[p] : (unsigned)p;
+    std::copy(fundamental_matrix + 9 * (size_t)p, fundamental_matrix + 9 * (size_t)p + 9, P.F);
+    rows1 += n1;
+    rows2 += n2;
+    if (rows1 >= 0x7fffffffLL || 4 * rows2 >= 0x7fffffffLL || num_matches >= 0x7fffffffLL) {
+      g_last_error = "guided epipolar match: the rows of the selected pairs exceed 2^31";
+      return TMI_BA_ERR_UNSUPPORTED;
+    }
+    for (int64_t m = pair_match_begin[p]; m < pair_match_begin[p + 1]; ++m) {
+      match_row1.push_back(P.base1 + match_feature1[m]);
+      match_row2.push_back(P.base2 + match_feature2[m]);
+    }
+    max_n2 = std::max(max_n2, n2);
+    pairs.push_back(P);
+    sel_pair.push_back(p);
+  }
+  pair_added_begin[num_pairs] = 0;
+  const int64_t out_rows = out_row[num_pairs];
+  if (feature_group) std::fill(feature_group, feature_group + out_rows, -1);
+  if (group_endpoints) std::fill(group_endpoints, group_endpoints + 4 * out_rows, 0.0);
+  if (group_num_candidates) std::fill(group_num_candidates, group_num_candidates + out_rows, 0);
+  const int S = (int)pairs.size();
+  sum->num_pairs = S;
+  const double ratio_sq = O->lowes_ratio * O->lowes_ratio;  // formed in double (guided_epipolar_matcher.cc:150)
+  const int rc = one_shot_batch(O->device, "guided epipolar match: no such device", S, t0, &sum->seconds, [&](OneShot* s) -> int {
+    const hipStream_t stream = s->stream;
+    auto grid = [](long long n) { return dim3((unsigned)((n + 255) / 256)); };
+    const size_t R1 = (size_t)rows1, R2 = (size_t)rows2, E = 4 * R2, M = match_row1.size();
+    // every named image once
+    float* d_desc;
+    double* d_keys;
+    TMI_HIP(s->alloc(&d_desc, (size_t)uploaded * (size_t)dim));
+    TMI_HIP(s->alloc(&d_keys, 2 * (size_t)uploaded));
+    for (int m = 0; m < num_images; ++m) {
+      const size_t n = (size_t)(image_begin[m + 1] - image_begin[m]);
+      if (device_row[m] < 0 || n == 0) continue;
+      TMI_HIP(hipMemcpyAsync(d_desc + (size_t)device_row[m] * dim, descriptors + (size_t)image_begin[m] * dim,
+                             n * (size_t)dim * sizeof(float), hipMemcpyHostToDevice, stream));
+      TMI_HIP(hipMemcpyAsync(d_keys + 2 * (size_t)device_row[m], keypoints + 2 * (size_t)image_begin[m],
+                             2 * n * sizeof(double), hipMemcpyHostToDevice, stream));
+    }
+    sum->rows_uploaded = uploaded;
+    GmPair* d_pairs;
+    GmPairState* d_state;
+    int *d_match_row1, *d_match_row2, *d_slot_first, *d_slot_size, *d_row_group, *d_num_groups, *d_slot_num_candidates;
+    int* d_counts;
+    unsigned char *d_matched1, *d_matched2;
+    unsigned *d_u2, *d_ubegin, *d_num_lines, *d_vbegin, *d_pair_key, *d_pair_key_gathered, *d_pair_key_sorted;
+    unsigned *d_iota1, *d_row_by_code, *d_pos_row, *d_segment_key, *d_segment_key_gathered, *d_segment_key_sorted;
+    unsigned *d_iota2, *d_entry_by_cell, *d_entry_sorted, *d_pass, *d_scan;
+    unsigned long long *d_code, *d_code_sorted, *d_cell_key, *d_cell_key_sorted, *d_counters;
+    double* d_slot_endpoints;
+    GmNn nn;
+    GmRecord* d_out;
+    TMI_HIP(s->upload(&d_pairs, pairs.data(), (size_t)S));
+    TMI_HIP(s->upload(&d_match_row1, match_row1.data(), M));
+    TMI_HIP(s->upload(&d_match_row2, match_row2.data(), M));
+    TMI_HIP(s->alloc(&d_state, (size_t)S));
+    TMI_HIP(s->alloc_filled(&d_matched1, R1, 0));
+    TMI_HIP(s->alloc_filled(&d_matched2, R2, 0));
+    TMI_HIP(s->alloc_filled(&d_u2, (size_t)S + 1, 0));
+    TMI_HIP(s->alloc(&d_ubegin, (size_t)S + 1));
+    TMI_HIP(s->alloc_filled(&d_num_lines, (size_t)S + 1, 0));
+    TMI_HIP(s->alloc(&d_vbegin, (size_t)S + 1));
+    TMI_HIP(s->alloc(&d_code, R1));
+    TMI_HIP(s->alloc(&d_code_sorted, R1));
+    TMI_HIP(s->alloc(&d_pair_key, R1));
+    TMI_HIP(s->alloc(&d_pair_key_gathered, R1));
+    TMI_HIP(s->alloc(&d_pair_key_sorted, R1));
+    TMI_HIP(s->alloc(&d_iota1, R1));
+    TMI_HIP(s->alloc(&d_row_by_code, R1));
+    TMI_HIP(s->alloc(&d_pos_row, R1));
+    TMI_HIP(s->alloc(&d_cell_key, E));
+    TMI_HIP(s->alloc(&d_cell_key_sorted, E));
+    TMI_HIP(s->alloc(&d_segment_key, E));
+    TMI_HIP(s->alloc(&d_segment_key_gathered, E));
+    TMI_HIP(s->alloc(&d_segment_key_sorted, E));
+    TMI_HIP(s->alloc(&d_iota2, E));
+    TMI_HIP(s->alloc(&d_entry_by_cell, E));
+    TMI_HIP(s->alloc(&d_entry_sorted, E));
+    TMI_HIP(s->alloc_filled(&d_slot_first, R1, 0));
+    TMI_HIP(s->alloc_filled(&d_slot_size, R1, 0));
+    TMI_HIP(s->alloc_filled(&d_slot_endpoints, 4 * R1, 0));
+    TMI_HIP(s->alloc_filled(&d_slot_num_candidates, R1, 0));
+    TMI_HIP(s->alloc_filled(&d_row_group, R1, 0xff));
+    TMI_HIP(s->alloc_filled(&d_num_groups, (size_t)S, 0));
+    TMI_HIP(s->alloc(&nn.best_d, R1));
+    TMI_HIP(s->alloc(&nn.best_i, R1));
+    TMI_HIP(s->alloc(&nn.second_d, R1));
+    TMI_HIP(s->alloc_filled(&d_pass, R1 + 1, 0));
+    TMI_HIP(s->alloc(&d_scan, R1 + 1));
+    TMI_HIP(s->alloc(&d_out, R1));
+    TMI_HIP(s->alloc(&d_counts, 4 * (size_t)S + 1));
+    TMI_HIP(s->alloc_filled(&d_counters, (size_t)4, 0));
+    const int bitmap_words = ((max_n2 + 31) / 32 + 3) & ~3;
+    const size_t lds = (size_t)bitmap_words * sizeof(unsigned) + (size_t)kGmListCap * sizeof(int);
+    const int* vbegin = reinterpret_cast<const int*>(d_vbegin);
+    const int* ubegin = reinterpret_cast<const int*>(d_ubegin);
+    StreamTimer timer(stream);
+    TMI_HIP(timer.status);
+    TMI_HIP(timer.mark());
+    // a, b
+    if (M) hipLaunchKernelGGL(gm_mark_kernel, grid((long long)M), dim3(256), 0, stream, d_match_row1, d_match_row2, (long long)M, d_matched1, d_matched2);
+    hipLaunchKernelGGL(gm_box_kernel, dim3((unsigned)S), dim3(256), 0, stream, d_pairs, d_keys, d_matched1, d_matched2, d_state, d_u2);
+    TMI_GM(tb_exclusive_sum(s, d_u2, d_ubegin, (size_t)S + 1));
+    if (R1) {
+      hipLaunchKernelGGL(gm_lines_kernel, grid((long long)R1), dim3(256), 0, stream, d_pairs, S, (int)R1, d_keys, d_matched1, d_state, d_code,
+                         d_pair_key, d_iota1, d_num_lines);
+      // c: (pair, code, feature) by two stable sorts, the feature order being the initial one
+      TMI_GM(tb_sort_pairs(s, d_code, d_code_sorted, d_iota1, d_row_by_code, R1, 64));
+      hipLaunchKernelGGL(gm_gather_kernel, grid((long long)R1), dim3(256), 0, stream, d_pair_key, d_row_by_code, (int)R1, d_pair_key_gathered);
+      TMI_GM(tb_sort_pairs(s, d_pair_key_gathered, d_pair_key_sorted, d_row_by_code, d_pos_row, R1, tb_bits((unsigned)S + 1)));
+    }
+    TMI_GM(tb_exclusive_sum(s, d_num_lines, d_vbegin, (size_t)S + 1));
+    hipLaunchKernelGGL(gm_group_kernel, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, stream, d_pairs, S, vbegin, d_pos_row, d_code, c,
+                       d_slot_first, d_slot_size, d_slot_endpoints, d_row_group, d_num_groups);
+    // d
+    if (E) {
+      hipLaunchKernelGGL(gm_cells_kernel, grid((long long)E), dim3(256), 0, stream, d_pairs, S, (int)R2, d_keys, d_matched2, d_state, c,
+                         d_cell_key, d_segment_key, d_iota2);
+      TMI_GM(tb_sort_pairs(s, d_cell_key, d_cell_key_sorted, d_iota2, d_entry_by_cell, E, 64));
+      hipLaunchKernelGGL(gm_gather_kernel, grid((long long)E), dim3(256), 0, stream, d_segment_key, d_entry_by_cell, (int)E, d_segment_key_gathered);
+      TMI_GM(tb_sort_pairs(s, d_segment_key_gathered, d_segment_key_sorted, d_entry_by_cell, d_entry_sorted, E, tb_bits(4u * (unsigned)S + 1)));
+    }
+    // e, f: a workgroup per slot
+    if (R1) {
+      hipLaunchKernelGGL(gm_search_kernel, dim3((unsigned)R1), dim3(kGmThreads), lds, stream, d_pairs, S, vbegin, ubegin, d_u2, d_num_groups,
+                         d_slot_first, d_slot_size, d_slot_endpoints, d_pos_row, d_entry_sorted, d_cell_key, d_desc, (int)dim, c, ratio_sq,
+                         (int)O->min_num_candidates, (unsigned long long)O->seed, bitmap_words, nn, d_pass, d_slot_num_candidates,
+                         d_counters);
+    }
+    TMI_GM(tb_exclusive_sum(s, d_pass, d_scan, R1 + 1));
+    if (R1) hipLaunchKernelGGL(gm_compact_kernel, grid((long long)R1), dim3(256), 0, stream, d_pairs, S, vbegin, d_pos_row, nn, d_pass, d_scan, d_out);
+    hipLaunchKernelGGL(gm_pair_kernel, dim3((unsigned)(S / 256 + 1)), dim3(256), 0, stream, d_state, vbegin, d_num_groups, d_scan, S, d_counts);
+    TMI_HIP(timer.mark());
+    // the read-back: counts and the test outputs, then exactly the added matches
+    std::vector<int> counts(4 * (size_t)S + 1), vbegin_h((size_t)S + 1);
+    const bool want_slots = group_endpoints || group_num_candidates;
+    std::vector<int> row_group_h(feature_group ? R1 : 0), slot_nc_h(group_num_candidates ? R1 : 0);
+    std::vector<double> slot_ep_h(group_endpoints ? 4 * R1 : 0);
+    unsigned long long counters_h[4] = {0, 0, 0, 0};
+    ReadBack rb(stream);
+    rb.add(counts.data(), d_counts, counts.size());
+    rb.add(vbegin_h.data(), vbegin, want_slots ? vbegin_h.size() : 0);
+    rb.add(row_group_h.data(), d_row_group, row_group_h.size());
+    rb.add(slot_nc_h.data(), d_slot_num_candidates, slot_nc_h.size());
+    rb.add(slot_ep_h.data(), d_slot_endpoints, slot_ep_h.size());
+    rb.add(counters_h, d_counters, (size_t)4);
+    TMI_HIP(rb.finish());
+    sum->kernel_seconds = timer.seconds();
+    sum->num_groups = (int64_t)counters_h[0];
+    sum->num_candidates = (int64_t)counters_h[1];
+    sum->distance_evaluations = (int64_t)counters_h[2];
+    const int total = counts[4 * (size_t)S];
+    if (total < 0 || (size_t)total > R1) {
+      s->error = "guided epipolar match: the device reported an impossible match count";
+      return TMI_BA_ERR_DEVICE;
+    }
+    for (int i = 0; i < S; ++i) {
+      const int p = sel_pair[i], ng = counts[4 * (size_t)i + 1];
+      if (ng < 0 || ng > pairs[i].n1 || counts[4 * (size_t)i + 2] < 0 || counts[4 * (size_t)i + 2] > total) {
+        s->error = "guided epipolar match: the device reported an impossible group count";
+        return TMI_BA_ERR_DEVICE;
+      }
+      pair_status[p] = (int8_t)counts[4 * (size_t)i];
+      pair_num_groups[p] = ng;
+      if (counts[4 * (size_t)i] == 0) sum->num_pairs_ok++;
+      if (feature_group) std::copy(row_group_h.begin() + pairs[i].base1, row_group_h.begin() + pairs[i].base1 + pairs[i].n1, feature_group + out_row[p]);
+      if (want_slots && (vbegin_h[i] < 0 || (size_t)vbegin_h[i] + (size_t)ng > R1)) {
+        s->error = "guided epipolar match: the device reported an impossible group table";
+        return TMI_BA_ERR_DEVICE;
+      }
+      for (int g = 0; g < ng && want_slots; ++g) {
+        const size_t slot = (size_t)vbegin_h[i] + (size_t)g;
+        if (group_num_candidates) group_num_candidates[out_row[p] + g] = slot_nc_h[slot];
+        if (group_endpoints) std::copy(slot_ep_h.begin() + 4 * slot, slot_ep_h.begin() + 4 * slot + 4, group_endpoints + 4 * (out_row[p] + g));
+      }
+    }
+    // pair_added_begin over ALL pairs: a pair that is masked out begins where its successor does
+    {
+      int next = total;
+      int i = S - 1;
+      pair_added_begin[num_pairs] = total;
+      for (int p = num_pairs - 1; p >= 0; --p) {
+        if (i >= 0 && sel_pair[i] == p) {
+          next = counts[4 * (size_t)i + 2];
+          --i;
+        }
+        pair_added_begin[p] = next;
+      }
+    }
+    sum->num_added = total;
+    if (total && total <= added_capacity) {
+      std::vector<GmRecord> rec((size_t)total);
+      ReadBack rb2(stream);
+      rb2.add(rec.data(), d_out, rec.size());
+      TMI_HIP(rb2.finish());
+      for (size_t i = 0; i < rec.size(); ++i) {
+        added_feature1[i] = rec[i].feature1;
+        added_feature2[i] = rec[i].feature2;
+        added_distance[i] = rec[i].distance;
+      }
+    }
+    return TMI_BA_OK;
+  });
+  sum->seconds = now_s() - t0;
+  if (rc == TMI_BA_OK && sum->num_added > added_capacity) {
+    g_last_error = "guided epipolar match: added_capacity is smaller than the number of added matches (summary->num_added)";
+    return TMI_BA_ERR_CAPACITY;
+  }
+  return rc;
+}
+}  // extern "C"
+#undef TMI_GM

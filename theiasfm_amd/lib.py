@@ -47,6 +47,7 @@ EXPORTS = (
     "tmi_ba_localization_options_init", "tmi_ba_localize_views",
     "tmi_ba_match_options_init", "tmi_ba_match_features",
     "tmi_ba_cascade_match_options_init", "tmi_ba_match_features_cascade",
+    "tmi_ba_guided_match_options_init", "tmi_ba_guided_epipolar_match",
     "tmi_ba_track_build_options_init", "tmi_ba_build_tracks",
     "tmi_ba_two_view_ransac_options_init", "tmi_ba_estimate_uncalibrated_relative_poses",
     "tmi_ba_estimate_calibrated_relative_poses",
@@ -243,6 +244,12 @@ def load():
     L.tmi_ba_match_features.argtypes = [MO, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                         C.c_void_p, C.c_int64] + [C.c_void_p] * 6 + [C.POINTER(abi.CMatchSummary)]
     L.tmi_ba_match_features.restype = C.c_int32
+    GO = C.POINTER(abi.CGuidedMatchOptions)
+    L.tmi_ba_guided_match_options_init.argtypes = [GO]
+    L.tmi_ba_guided_match_options_init.restype = None
+    L.tmi_ba_guided_epipolar_match.argtypes = [GO, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32] + [
+        C.c_void_p] * 8 + [C.c_int64] + [C.c_void_p] * 9 + [C.POINTER(abi.CGuidedMatchSummary)]
+    L.tmi_ba_guided_epipolar_match.restype = C.c_int32
     KO = C.POINTER(abi.CCascadeMatchOptions)
     L.tmi_ba_cascade_match_options_init.argtypes = [KO]
     L.tmi_ba_cascade_match_options_init.restype = None
@@ -963,6 +970,82 @@ def match_features_cascade(image_begin, descriptors, projections, pair_image1, p
     return _match_call("tmi_ba_match_features_cascade", abi.CCascadeMatchSummary, abi.cascade_match_options,
                        image_begin, descriptors, projections, pair_image1, pair_image2, options, match_capacity,
                        bool(want_hash))
+
+
+def guided_epipolar_match(image_begin, descriptors, keypoints, pair_image1, pair_image2, fundamental_matrix,
+                          pair_match_begin, match_feature1, match_feature2, options=None, pair_mask=None,
+                          pair_stream=None, added_capacity=None, want_groups=False):
+    """Batched GuidedEpipolarMatcher (tmi_ba_guided_epipolar_match): more matches along the epipolar lines of the pairs
+    (pair_image1[p], pair_image2[p]).  image_begin [num_images + 1] int64 row offsets into descriptors [rows, dim]
+    float32 and keypoints [rows, 2] float64; fundamental_matrix [P, 9] (row-major, image-1 point to image-2 line);
+    the input matches of pair p are pair_match_begin[p] .. pair_match_begin[p + 1] - 1 of match_feature1 /
+    match_feature2.  added_capacity: None sizes the arrays for the most there can be (the rows of image 1 over the
+    pairs); a capacity that is too small comes back as `status` == abi.ERR_CAPACITY with summary.num_added the needed
+    total.  want_groups adds the test outputs.
+    Returns a dict: status, pair_status [P] int8, pair_num_groups [P] int32, pair_added_begin [P + 1] int64, feature1 /
+    feature2 [total] int32, distance [total] float32, summary (CGuidedMatchSummary) and, with want_groups, pair_row
+    [P + 1] int64 (row(p) of the header), feature_group, group_endpoints [rows, 4], group_num_candidates.  Raises
+    EngineError on any other failure."""
+    L = load()
+    o = options if options is not None else abi.guided_match_options()
+    ib = np.ascontiguousarray(image_begin, dtype=np.int64)
+    desc = np.ascontiguousarray(descriptors, dtype=np.float32)
+    keys = np.ascontiguousarray(keypoints, dtype=np.float64)
+    if ib.ndim != 1 or ib.shape[0] < 1:
+        raise ValueError("image_begin must have num_images + 1 entries")
+    if desc.ndim != 2 or desc.shape[0] != int(ib[-1]):
+        raise ValueError("descriptors must be [image_begin[-1], dim]")
+    if keys.shape != (desc.shape[0], 2):
+        raise ValueError("keypoints must be [rows, 2]")
+    p1 = np.ascontiguousarray(pair_image1, dtype=np.int32)
+    p2 = np.ascontiguousarray(pair_image2, dtype=np.int32)
+    if p1.ndim != 1 or p1.shape != p2.shape:
+        raise ValueError("pair_image1 and pair_image2 must be one-dimensional and of one length")
+    num_images, num_pairs = ib.shape[0] - 1, p1.shape[0]
+    F = np.ascontiguousarray(fundamental_matrix, dtype=np.float64).reshape(-1)
+    if F.shape[0] != 9 * num_pairs:
+        raise ValueError("fundamental_matrix must be [num_pairs, 9]")
+    mb = np.ascontiguousarray(pair_match_begin, dtype=np.int64)
+    m1 = np.ascontiguousarray(match_feature1, dtype=np.int32)
+    m2 = np.ascontiguousarray(match_feature2, dtype=np.int32)
+    if mb.shape != (num_pairs + 1,) or m1.ndim != 1 or m1.shape != m2.shape:
+        raise ValueError("pair_match_begin must have num_pairs + 1 entries and the match arrays one length")
+    if mb.shape[0] and int(mb.max()) > m1.shape[0]:
+        raise ValueError("pair_match_begin points past the match arrays")
+    mask = None if pair_mask is None else np.ascontiguousarray(pair_mask, dtype=np.uint8)
+    strm = None if pair_stream is None else np.ascontiguousarray(pair_stream, dtype=np.uint32)
+    for a in (mask, strm):
+        if a is not None and a.shape != (num_pairs,):
+            raise ValueError("pair_mask and pair_stream must have num_pairs entries")
+    ok = (p1 >= 0) & (p1 < num_images)
+    n1 = np.where(ok, np.diff(ib)[np.where(ok, p1, 0)], 0) if num_images else np.zeros(num_pairs, np.int64)
+    pair_row = np.concatenate([[0], np.cumsum(np.maximum(n1, 0))]).astype(np.int64)
+    rows = int(pair_row[-1])
+    cap = rows if added_capacity is None else int(added_capacity)
+    status = np.zeros(num_pairs, dtype=np.int8)
+    ngroups = np.zeros(num_pairs, dtype=np.int32)
+    begin = np.zeros(num_pairs + 1, dtype=np.int64)
+    f1 = np.zeros(max(cap, 0), dtype=np.int32)
+    f2 = np.zeros(max(cap, 0), dtype=np.int32)
+    dist = np.zeros(max(cap, 0), dtype=np.float32)
+    fg = np.zeros(rows, dtype=np.int32) if want_groups else None
+    ge = np.zeros((rows, 4), dtype=np.float64) if want_groups else None
+    gn = np.zeros(rows, dtype=np.int32) if want_groups else None
+    ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+    gs = abi.CGuidedMatchSummary()
+    st = L.tmi_ba_guided_epipolar_match(
+        C.byref(o), num_images, ib.ctypes.data, desc.ctypes.data, desc.shape[1], keys.ctypes.data, num_pairs,
+        p1.ctypes.data, p2.ctypes.data, F.ctypes.data, mb.ctypes.data, m1.ctypes.data, m2.ctypes.data, ptr(mask),
+        ptr(strm), cap, status.ctypes.data, ngroups.ctypes.data, begin.ctypes.data, f1.ctypes.data, f2.ctypes.data,
+        dist.ctypes.data, ptr(fg), ptr(ge), ptr(gn), C.byref(gs))
+    if st not in (0, abi.ERR_CAPACITY):
+        raise EngineError(st, "tmi_ba_guided_epipolar_match")
+    n = 0 if st else int(begin[-1])
+    out = dict(status=st, pair_status=status, pair_num_groups=ngroups, pair_added_begin=begin, feature1=f1[:n],
+               feature2=f2[:n], distance=dist[:n], summary=gs, added_arrays=(f1, f2, dist))
+    if want_groups:
+        out.update(pair_row=pair_row, feature_group=fg, group_endpoints=ge, group_num_candidates=gn)
+    return out
 
 
 def build_tracks(endpoint_view, endpoint_feature, options=None, track_capacity=None, obs_capacity=None,
