@@ -405,7 +405,10 @@ int32_t tmi_ba_solve(tmi_ba_problem* problem, const tmi_ba_options* options,
  *              camera-major orders, Schur block structure, pair lists),
  *              upload.  `rank`/`world` select the contiguous shard of tracks
  *              this process owns (0/1 for single GPU).
- *   solve    : run LM on the resident parameters (may be called repeatedly).
+ *   solve    : run LM on the resident parameters (may be called repeatedly).  The options of a solve need not
+ *              be the ones of create: schur_mode, residual_precision, device and (outside the cluster
+ *              preconditioners) visibility_clustering_type are fixed at create and ignored here -- the solve
+ *              gives the bits of create's values -- while a point_dof that differs is TMI_BA_ERR_INVALID_ARGUMENT.
  *   reset    : restore the parameters uploaded at create time (or by the last set_parameters).
  *   set_parameters : new values of extrinsics / intrinsics / points for the SAME residual set and
  *              constancy flags (the caller moved cameras or re-triangulated tracks between two

@@ -508,6 +508,59 @@ static void TestResidentSessionGpu() {
   ReleaseBundleAdjustmentSession();
 }
 
+// The session keeps one handle across calls whose options differ in a field tmi_ba_solver_solve reads (SameShape,
+// bundle_adjuster.cc, looks at the problem-shaping ones only): the loss, inner iterations, the iteration cap.  The
+// second call must give what the same call gives on a session of its own, bit for bit.
+static void TestResidentSessionOptionSwitchGpu() {
+  BundleAdjustmentOptions first;
+  first.linear_solver_type = ceres::ITERATIVE_SCHUR;
+  first.max_num_iterations = 1;
+  first.use_inner_iterations = false;
+  first.keep_problem_resident = true;
+  first.function_tolerance = first.gradient_tolerance = first.parameter_tolerance = -1.0;
+  BundleAdjustmentOptions second = first;
+  second.loss_function_type = LossFunctionType::HUBER;
+  second.robust_loss_width = 0.1;  // (narrow enough to act on these residuals, see the cost check below)
+  second.use_inner_iterations = true;
+  second.max_num_iterations = 3;
+  auto snapshot = [](const Reconstruction& r) {
+    std::vector<double> v;
+    for (ViewId id = 0; id < (ViewId)r.NumViews(); ++id) {
+      for (int a = 0; a < 6; ++a) v.push_back(r.View(id)->Camera().extrinsics()[a]);
+      for (int a = 0; a < 7; ++a) v.push_back(r.View(id)->Camera().intrinsics()[a]);
+    }
+    for (TrackId id = 0; id < (TrackId)r.NumTracks(); ++id)
+      for (int a = 0; a < 4; ++a) v.push_back(r.Track(id)->Point()[a]);
+    return v;
+  };
+  for (const bool shared : {false, true}) {
+    // A: first call, then the second on the SAME session.  B: the first call without a session (same bits, see
+    // TestResidentSessionGpu), then the second on a session that is new.
+    Reconstruction A, B;
+    BuildScene(&A, 7, 260, shared, 37, 0.3);
+    BuildScene(&B, 7, 260, shared, 37, 0.3);
+    ReleaseBundleAdjustmentSession();
+    const BundleAdjustmentSummary a1 = BundleAdjustReconstruction(first, &A);
+    EXPECT(a1.success && BundleAdjustmentSessionIsResident(&A));
+    const BundleAdjustmentSummary a2 = BundleAdjustReconstruction(second, &A);
+    EXPECT(a2.success && BundleAdjustmentSessionIsResident(&A));  // (kept: the options differ in solve-time fields only)
+    ReleaseBundleAdjustmentSession();
+    BundleAdjustmentOptions first_one_shot = first;
+    first_one_shot.keep_problem_resident = false;
+    const BundleAdjustmentSummary b1 = BundleAdjustReconstruction(first_one_shot, &B);
+    EXPECT(b1.success && !BundleAdjustmentSessionIsResident(&B) && b1.final_cost == a1.final_cost);
+    const BundleAdjustmentSummary b2 = BundleAdjustReconstruction(second, &B);
+    EXPECT(b2.success && BundleAdjustmentSessionIsResident(&B));
+    EXPECT(a2.initial_cost == b2.initial_cost && a2.final_cost == b2.final_cost);
+    EXPECT(a2.initial_cost != a1.final_cost);  // (the robust loss: another cost at the same point)
+    EXPECT(snapshot(A) == snapshot(B));  // bit for bit
+    std::printf("resident session, options switched (%s intrinsics): %.6e -> %.6e, then %.6e -> %.6e; new session %.6e -> %.6e\n",
+                shared ? "shared" : "private", a1.initial_cost, a1.final_cost, a2.initial_cost, a2.final_cost,
+                b2.initial_cost, b2.final_cost);
+  }
+  ReleaseBundleAdjustmentSession();
+}
+
 // SetOutlierTracksToUnestimated (set_outlier_tracks_to_unestimated.cc:62-133) and the batched
 // BundleAdjustTracks, end to end through the shim.
 static void TestTrackOpsGpu() {
@@ -790,6 +843,7 @@ int main(int argc, char** argv) {
   if (mode == "gpu") {
     TestGpu();
     TestResidentSessionGpu();
+    TestResidentSessionOptionSwitchGpu();
     TestTrackOpsGpu();
     TestTwoViewsGpu();
     TestTwoViewsAngularGpu();

@@ -3464,6 +3464,11 @@ int32_t tmi_ba_solver_solve(tmi_ba_solver* s, const tmi_ba_options* O, tmi_ba_su
                "an exact linear solver type needs schur_mode = explicit at creation";
     return fail(TMI_BA_ERR_INVALID_ARGUMENT);
   }
+  // The operator of an LM iteration (and with it the Y-record switch) is chosen per iteration by schur_mode auto, and
+  // only in an iterative solve: an exact solve on a handle whose last iteration ran matrix-free would skip forming S.
+  // Every solve starts from what create left (tests/test_gpu_resident_sequences.py).
+  s->implicit_now = s->implicit;
+  v.write_y = (s->y_records && (!s->implicit || st.has_shared)) ? 1 : 0;
   double* d_sc = v.red + RL.scalars;  // 8 device scalars that get all-reduced
 
   // ---- iteration zero ---------------------------------------------------------------
